@@ -29,18 +29,24 @@ points.  Inputs are resident in HBM before the timed region.
       10-view x 5 000-point sequence through the drop-in classes: per view PnP (RANSAC + nonlinear), triangulation of
       the new points (DLT + nonlinear) and a global BA; a step is one registered view; `value` is views per second.
 
-Timing: W warm-up steps (every kernel class bracketed: which one dominates), the event-bracket calibration, then an
-untimed PRE-ROLL of the same steps until ~30 ms of GPU work have passed (`preroll_steps` in the line; `--no-preroll`
+Timing: W warm-up steps (every kernel class bracketed: which one dominates), with --full the event-bracket calibration,
+then an untimed PRE-ROLL of the same steps until ~30 ms of GPU work have passed (`preroll_steps` in the line; `--no-preroll`
 skips it): a step is 0.3 ms, so after the host-side calibration the clocks are down and K = 20 steps would be over before
-they are back up.  Then R (= --repeats, 5) timed regions back to back, each barrier + synchronize, EXACTLY K steps,
-synchronize + barrier, MAX over ranks; `value` / `ms_per_step` are the MEDIAN region, `value_runs` / `ms_per_step_runs`
+they are back up.  Then R (= --repeats: 1, 5 with --full) timed regions back to back, each barrier + synchronize,
+EXACTLY K steps, synchronize + barrier, MAX over ranks; `value` / `ms_per_step` are the MEDIAN region, `value_runs` / `ms_per_step_runs`
 list all of them (the error bar of a 5.6 ms measurement).
 N > 1: the replicated solves must leave every rank with the same cameras; `max_camera_deviation_across_ranks` records it.
 A non-zero deviation is not a lost run: the measurement is repeated with reduce(dst=0) + broadcast in place of the
 all-reduce (`--collective reduce_broadcast` forces that form) and `replica_drift` keeps the first figures.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, hipEvent-timed inside the timed
-region) and `cpu_baseline` (the NumPy oracle on the host cores, N = 1 only).
+Prints ONE JSON line (rank 0).  A plain run does only what the headline figure needs: set-up, W warm-up steps, the
+pre-roll, ONE timed region of exactly K steps (--repeats defaults to 1) and the line.  Every timed region starts from
+the seeded initial estimate, so with the same arguments the timed steps compute the same result from run to run.
+  --full          everything else as well: five timed regions (--repeats 5), the parity leg (3 iterations against the
+                  CPU oracle), `kernel_ms` and `roofline` (dominant kernel, hipEvent-timed inside the timed regions),
+                  `cpu_baseline` and the other CPU legs (N = 1), and for C3 with N > 1 the companion scaling figure
+  --dump-outputs DIR   after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float64,
+                  64 MB at most in all (a fixed, seeded column sample of a larger array)
 """
 import argparse
 import importlib
@@ -287,6 +293,25 @@ def finish(ctx, out):
         print(json.dumps(out))
 
 
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(ctx, dirname, arrays):
+    """--dump-outputs: rank 0 writes every array as <dirname>/<name>.npy in float64.  An array that does not fit its
+    share of DUMP_BYTES is cut to a fixed, seeded, sorted sample of its last axis (the same columns in every run)."""
+    if not dirname or ctx.rank != 0:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share and a.ndim > 0:
+            per_col = a.nbytes // a.shape[-1]
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[-1], max(1, share // per_col), replace=False))
+            a = a[..., keep]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 # ================================================================================================================
 # BA (C3 / C4)
 # ================================================================================================================
@@ -396,7 +421,7 @@ def ba_measure(args, ctx, sfm, strong, full, collective):
     engine.prob.reset_timing()
     ba.iterate(LAMBDA, max(1, args.warmup))
     sync()
-    event_overhead_ms = max(0.0, engine.prob.event_overhead(20) - EMPTY_KERNEL_MS)
+    event_overhead_ms = max(0.0, engine.prob.event_overhead(20) - EMPTY_KERNEL_MS) if full else 0.0
     breakdown = {}
     for kid, name in enumerate(native.KERNEL_NAMES):
         ms, n = engine.prob.kernel_time(kid)
@@ -404,9 +429,9 @@ def ba_measure(args, ctx, sfm, strong, full, collective):
     dominant = max((n for n in breakdown if n != "prep"), key=lambda n: breakdown[n])
     dom_id = native.KERNEL_NAMES.index(dominant)
 
-    # ---- timed regions: exactly K steps each, only the dominant kernel bracketed by hipEvents ----------
+    # ---- timed regions: exactly K steps each, only the dominant kernel bracketed by hipEvents (`full` only) ----------
     # (sampled: a hipEvent pair puts two ~6 us bubbles into the stream, 3.6 % of a C3 iteration if every launch is bracketed)
-    engine.prob.set_option(native.OPT_TIMING, 1 << dom_id)
+    engine.prob.set_option(native.OPT_TIMING, (1 << dom_id) if full else 0)
     stride = args.timing_stride if args.timing_stride > 0 else max(1, min(10, args.steps // 5))
     engine.prob.set_option(native.OPT_TIMING_STRIDE, stride)
     # The W warm-up steps above are followed by host-side calibration, so the GPU is idle and its clocks are down when the
@@ -421,9 +446,11 @@ def ba_measure(args, ctx, sfm, strong, full, collective):
         sync()
     engine.prob.reset_timing()
     # R back-to-back regions of EXACTLY K steps (the 5.6 ms headline gets an error bar); every region is
-    # barrier + synchronize | K steps | synchronize + barrier, MAX over ranks; `value` is the median region
+    # barrier + synchronize | K steps | synchronize + barrier, MAX over ranks; `value` is the median region.  Every region
+    # starts from the initial estimate (untimed upload): the pre-roll's length depends on timing, the result must not
     elapsed_runs = []
     for _ in range(max(1, args.repeats)):
+        engine.set_state(scene.cams_init, pts_l)
         sync()
         t0 = time.perf_counter()
         ba.iterate(LAMBDA, args.steps)
@@ -487,6 +514,7 @@ def ba_measure(args, ctx, sfm, strong, full, collective):
 
     extra = Holder()
     extra.scene, extra.uvn, extra.engine, extra.cams3, extra.pts3, extra.rmse_gpu3 = scene, uvn, engine, cams3, pts3, rmse_gpu3
+    extra.cams_end, extra.pts_end = cams_end, pts_end
     if not full:
         close_engine(engine)
         return out, extra
@@ -562,7 +590,7 @@ def run_ba(args, ctx):
     c4_fixed = args.config == "C4" and args.pts is None
     primary_strong = c4_fixed or args.scaling == "strong"
     collective = args.collective
-    out, extra = ba_measure(args, ctx, sfm, primary_strong, True, collective)
+    out, extra = ba_measure(args, ctx, sfm, primary_strong, args.full, collective)
     collective = out["config"].get("collective", collective)
     if ctx.use_dist and world > 1 and out.get("max_camera_deviation_across_ranks", 0.0) != 0.0 and collective in ("allreduce", "library"):
         # replicas drifted: the all-reduce did not hand every rank the same bytes.  Not a lost run: record it, repeat the
@@ -570,11 +598,13 @@ def run_ba(args, ctx):
         drift = {"max_camera_deviation_across_ranks": out["max_camera_deviation_across_ranks"], "value_with_drift": out["value"],
                  "ms_per_step_with_drift": out["ms_per_step"],
                  "note": "the all-reduce (%s) left the ranks with different [S | rhs] bits; re-measured with reduce(dst=0) + broadcast" % collective}
-        close_engine(extra.engine)
+        if args.full:
+            close_engine(extra.engine)
         collective = "reduce_broadcast"
-        out, extra = ba_measure(args, ctx, sfm, primary_strong, True, collective)
+        out, extra = ba_measure(args, ctx, sfm, primary_strong, args.full, collective)
         out["replica_drift"] = drift
-    if ctx.use_dist and world > 1 and args.config == "C3" and not args.single_scaling:
+    dump_outputs(ctx, args.dump_outputs, {"cams": extra.cams_end, "pts": extra.pts_end})
+    if args.full and ctx.use_dist and world > 1 and args.config == "C3" and not args.single_scaling:
         other, _extra2 = ba_measure(args, ctx, sfm, not primary_strong, False, collective)
         key = "weak_scaled" if primary_strong else "strong_scaled"
         out[key] = {k: other[k] for k in ("value", "unit", "ms_per_step", "value_runs", "ms_per_step_runs", "scaling", "hbm", "rmse_px") if k in other}
@@ -585,7 +615,7 @@ def run_ba(args, ctx):
     cams3, pts3, rmse_gpu3 = extra.cams3, extra.pts3, extra.rmse_gpu3
 
     # ---- CPU baseline (rank 0, N = 1): the NumPy block-sparse oracle on the same scene --------------------------
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         close_engine(engine)
         # (ii) cpu_ref_sparse, default BLAS threads: median of three runs of 3 iterations (the state after 3 feeds the parity figures)
         leg = cpu_leg("sparse", args.config, 3, 3, args.pts)
@@ -626,7 +656,7 @@ def run_ba(args, ctx):
         # ... and at the size the reference's own pipeline reaches (filter_size = 10 views, ba_processor.py:24, 44-46; its demo: 6 x 1260)
         out["drop_in_path_small"] = drop_in_path(sfm, sfm.scenes.make_scene(6, 1260, 1.0, seed=0))
 
-    if world > 1 or args.no_cpu_baseline:
+    if args.full and (world > 1 or args.no_cpu_baseline):      # (without --full, ba_measure has closed it)
         close_engine(engine)
     finish(ctx, out)
 
@@ -751,9 +781,15 @@ def run_tri_pnp(args, ctx):
                      "algorithmic_flops_per_launch": flops_per_launch, "algorithmic_bytes_per_launch": alg_bytes,
                      "traffic": None},
     }
-    # ---- parity + gather: the sharded result against this rank's kernel output, and against the oracle on a sample --------
-    oracle = importlib.import_module("sfm_oracle")
     if args.config == "TRI":
+        if args.dump_outputs:
+            dump_outputs(ctx, args.dump_outputs, {"points": shard.result()})
+    else:
+        rot, loc, st = shard.result()
+        dump_outputs(ctx, args.dump_outputs, {"rot": rot, "loc": loc, "status": st})
+    # ---- parity + gather (--full): the sharded result against this rank's kernel output, and against the oracle on a sample
+    oracle = importlib.import_module("sfm_oracle")
+    if args.full and args.config == "TRI":
         mine = shard.result()
         if world > 1:
             full = np.hstack(sh.gather_columns(mine, np.diff(sh.shard_points(per_rank * world, world)), device=None if ctx.rehearsal else ctx.device))
@@ -761,8 +797,7 @@ def run_tri_pnp(args, ctx):
         ns = min(20000, p1 - p0)
         want = oracle.nonlinear_triangulate_vec(x0[:, p0:p0 + ns], list(projs), [np.vstack((u[:, p0:p0 + ns], np.ones((1, ns)))) for u in uv], lam, iters)
         out["parity"] = {"max_rel_diff_vs_oracle_on_%d_points" % ns: float(np.max(np.abs(mine[:, :ns] - want)) / np.max(np.abs(want)))}
-    else:
-        rot, loc, st = shard.result()
+    elif args.full:
         if world > 1:
             packed = np.vstack((rot.reshape(-1, 9).T, loc.T, st[None, :].astype(np.float64)))
             full = np.hstack(sh.gather_columns(packed, np.diff(sh.shard_views(offsets, world)), device=None if ctx.rehearsal else ctx.device))
@@ -772,7 +807,7 @@ def run_tri_pnp(args, ctx):
         rot3, loc3, _ = shard.result()
         out["parity"] = {"status_nonzero": int(np.count_nonzero(st)),
                          "max_rel_diff_vs_oracle_first_view_3_iterations": float(max(np.max(np.abs(rot3[0] - r_or)), np.max(np.abs(loc3[0] - c_or.reshape(3))) / np.max(np.abs(c_or))))}
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         if args.config == "TRI":
             ns, t0 = 100000, time.perf_counter()
             oracle.nonlinear_triangulate_vec(x0[:, :ns], list(projs), [np.vstack((u[:, :ns], np.ones((1, ns)))) for u in uv], lam, 20)
@@ -931,6 +966,7 @@ def run_c5(args, ctx):
         cams, full = one_pass(rec)
         records.append(rec)
     torch.cuda.synchronize()
+    dump_outputs(ctx, args.dump_outputs, {"cams": cams, "pts": full})
     # the timed region of a step = the three drop-in calls of that view (every one of them synchronises before it returns);
     # creating the synthetic key points and filling the track tables stands in for the out-of-scope front end
     elapsed = sum(st["view_s"] for rec in records for st in rec)
@@ -960,7 +996,7 @@ def run_c5(args, ctx):
         "per_view": per_view,
         "roofline": None,
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # CPU leg on a bounded sample: view index 3 of the sequence (4 views, the points known by then) -- the oracle's nonlinear
         # PnP (per-point Python loop, 20 of the 300 iterations, scaled), vectorised nonlinear triangulation of that view's new
         # points, block-sparse BA.  The six-point RANSAC has no CPU restatement in oracle/ and is left out of the sample.
@@ -1048,7 +1084,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5, help="back-to-back timed regions of exactly --steps steps each; `value` is their median (BA configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity leg, kernel breakdown and roofline, the CPU baselines and (C3, N > 1) the companion scaling figure; "
+                         "five timed regions by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, 64 MB at most in all)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="back-to-back timed regions of exactly --steps steps each; `value` is their median (BA configs; default 1, 5 with --full)")
     ap.add_argument("--scaling", default="auto", choices=["auto", "weak", "strong"],
                     help="C3 with N > 1: which figure is `value` (auto = weak: 20 000 points per rank; strong = the fixed 50 x 20k scene split "
                          "over the ranks); the other one is timed as well and reported next to it")
@@ -1068,6 +1110,8 @@ def main():
     ap.add_argument("--cpu-iters", type=int, default=3, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-repeats", type=int, default=1, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if args.cpu_leg:                      # child of cpu_leg_child: CPU only, BLAS threads pinned by the parent
         leg = cpu_leg(args.cpu_leg, args.config if args.config in ("C3", "C4") else "C3", args.cpu_iters, args.cpu_repeats, args.pts)

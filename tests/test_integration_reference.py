@@ -1,49 +1,70 @@
-"""Build-container-only check of INTEGRATION.md section 1: the HIP mixins placed IN FRONT OF the real reference
-classes.  `/root/reference` does not exist on the GPU box, so the whole module is skipped there; no GPU call is
-made -- this pins the Python-level contract (method resolution order, name mangling, signatures, the attributes the
-reference constructors set and the mixins read)."""
+"""Check of INTEGRATION.md section 1: the HIP mixins placed IN FRONT OF the reference classes.  No GPU call is made --
+this pins the Python-level contract (method resolution order, name mangling, signatures, the attributes the reference
+constructors set and the mixins read).
+
+The reference is not part of this repository, so its classes are described by data captured from it
+(tests/golden/g11_reference_api.json, written by tools/capture_reference_api.py): per class the methods it defines
+with their parameter lists, the class-private names ``BaProcessor.process`` calls, and the attributes the constructor
+calls of ba_processor.py:463-488 leave on the instance.  The stand-in classes below are built from that record alone."""
 import inspect
+import json
 import os
-import sys
 import types
 
+import numpy as np
 import pytest
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout exists in the build container only")
+API = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g11_reference_api.json")
 
 
-REF_MODULES = ("ba_processor", "campose_processor", "epipolar_processor", "triangulation_processor", "utils",
-               "view_processor", "key_tracker")
+def _stand_in(name, rec, instances):
+    """A class with the reference class's name, methods (same parameter lists, bodies that refuse to run) and class
+    attributes; its constructor leaves exactly the attributes the recorded constructor call left."""
+    def method(mname, params):
+        def fn(*args, **kwargs):
+            raise NotImplementedError("stand-in for %s.%s" % (name, mname))
+        fn.__name__, fn.__qualname__ = mname, "%s.%s" % (name, mname)
+        fn.__signature__ = inspect.Signature([inspect.Parameter(p, getattr(inspect.Parameter, kind)) for p, kind in params])
+        return fn
+
+    ns = {m: method(m, params) for m, params in rec["methods"].items() if m != "__init__"}
+    ns.update({a: None for a in rec["attributes"]})
+    made = [i for i in instances if i["class"] == name]
+
+    def __init__(self, *args):
+        call = next(i for i in made if len(i["args"]) == len(args))
+        for attr, enc in call["attrs"].items():
+            if isinstance(enc, dict) and "arg" in enc:
+                value = args[enc["arg"]]
+            elif isinstance(enc, dict) and "array" in enc:
+                value = np.array(enc["array"], dtype=enc["dtype"])
+            else:
+                value = enc
+            setattr(self, attr, value)
+
+    if "__init__" in rec["methods"]:
+        ns["__init__"] = __init__
+        __init__.__signature__ = inspect.Signature([inspect.Parameter(p, getattr(inspect.Parameter, kind))
+                                                    for p, kind in rec["methods"]["__init__"]])
+    return type(name, (), ns)
 
 
 @pytest.fixture(scope="module")
-def ref():
-    """The reference's modules, imported for this test module only: sys.path, sys.modules (the reference's generically
-    named `utils`, the inert `cv2` placeholder) and sys.dont_write_bytecode are restored on teardown so that no later
-    test of the session picks them up."""
-    saved_path, saved_flag = list(sys.path), sys.dont_write_bytecode
-    saved_mods = {name: sys.modules.get(name) for name in REF_MODULES + ("cv2",)}
-    sys.dont_write_bytecode = True                    # the reference directory is read-only
-    sys.path.insert(0, REF)
-    if "cv2" not in sys.modules:
-        sys.modules["cv2"] = types.ModuleType("cv2")  # inert placeholder: OpenCV is absent, the hot path never calls it
-    for name in REF_MODULES:
-        sys.modules.pop(name, None)
-    import ba_processor
-    import campose_processor
-    import epipolar_processor
-    import triangulation_processor
-    import utils
-    yield types.SimpleNamespace(ba=ba_processor, cam=campose_processor, epi=epipolar_processor,
-                                tri=triangulation_processor, utils=utils)
-    sys.path[:] = saved_path
-    sys.dont_write_bytecode = saved_flag
-    for name, mod in saved_mods.items():
-        if mod is None:
-            sys.modules.pop(name, None)
-        else:
-            sys.modules[name] = mod
+def api():
+    with open(API) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope="module")
+def ref(api):
+    """The reference's modules as stand-ins: ref.ba.BaProcessor, ref.cam.CamposeProcessor, ref.epi.EpipolarProcessor,
+    ref.tri.TriangulationProcessor, ref.utils.RansacConfig."""
+    alias = {"ba_processor": "ba", "campose_processor": "cam", "epipolar_processor": "epi",
+             "triangulation_processor": "tri", "utils": "utils"}
+    mods = {short: types.SimpleNamespace() for short in alias.values()}
+    for name, rec in api["classes"].items():
+        setattr(mods[alias[rec["module"]]], name, _stand_in(name, rec, api["instances"]))
+    return types.SimpleNamespace(**mods)
 
 
 def _subclasses(sfm, ref):
@@ -64,7 +85,7 @@ def _subclasses(sfm, ref):
     return TriangulationProcessor, CamposeProcessor, BaProcessor, EpipolarProcessor
 
 
-def test_mixins_override_the_hot_path_of_the_real_classes(sfm, ref):
+def test_mixins_override_the_hot_path_of_the_real_classes(sfm, ref, api):
     hip = sfm.processors
     tri_cls, cam_cls, ba_cls, epi_cls = _subclasses(sfm, ref)
     overrides = [
@@ -86,7 +107,7 @@ def test_mixins_override_the_hot_path_of_the_real_classes(sfm, ref):
     # the BA entry is a name-mangled private method: `process` calls self.__execute_bundle_adjustment(), which the
     # compiler spells _BaProcessor__execute_bundle_adjustment inside class BaProcessor (ba_processor.py:267)
     mangled = "_BaProcessor__execute_bundle_adjustment"
-    assert mangled in ref.ba.BaProcessor.process.__code__.co_names
+    assert mangled in api["private_calls"]["BaProcessor.process"]
     assert mangled in vars(ref.ba.BaProcessor)
     assert getattr(ba_cls, mangled) is getattr(hip.HipBaMixin, mangled)
     assert getattr(ba_cls, mangled) is hip.HipBaMixin.execute_bundle_adjustment

@@ -7,7 +7,7 @@ cp $lib /tmp/keep.so
 for rep in ${AB_REPS:-1 2}; do
   for v in ${AB_VARIANTS:-old new}; do
     cp gpurun_ab/$v.so $lib
-    timeout -k 10 200 python bench.py --steps 40 --warmup 5 --no-cpu-baseline > $out/$v.$rep.log 2>&1 || exit 1
+    timeout -k 10 200 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline > $out/$v.$rep.log 2>&1 || exit 1
     python3 - $out/$v.$rep.log $v <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -24,13 +24,13 @@ fi
 tail -5 "$out/pytest_gpu.log"
 step 120 "$out/smoke.log" python __graft_entry__.py smoke
 tail -1 "$out/smoke.log"
-step 300 "$out/bench.log" python bench.py
+step 300 "$out/bench.log" python bench.py --full
 tail -c 600 "$out/bench.log"
-step 240 "$out/bench_tri.log" python bench.py --config TRI --steps 20 --warmup 2
+step 240 "$out/bench_tri.log" python bench.py --full --config TRI --steps 20 --warmup 2
 tail -c 400 "$out/bench_tri.log"
-step 240 "$out/bench_pnp.log" python bench.py --config PNP --steps 20 --warmup 2
+step 240 "$out/bench_pnp.log" python bench.py --full --config PNP --steps 20 --warmup 2
 tail -c 400 "$out/bench_pnp.log"
-step 300 "$out/bench_c5.log" python bench.py --config C5 --steps 18 --warmup 1
+step 300 "$out/bench_c5.log" python bench.py --full --config C5 --steps 18 --warmup 1
 tail -c 400 "$out/bench_c5.log"
 step 120 "$out/time_small.log" python tools/time_small.py
 grep -v amdgpu.ids "$out/time_small.log" | tail -20

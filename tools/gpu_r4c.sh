@@ -19,8 +19,8 @@ step 900 "$out/pytest_gpu.log" python -m pytest tests -m gpu -q -x --timeout 300
 tail -3 "$out/pytest_gpu.log"
 step 300 "$out/bench.log" python bench.py --steps 20 --warmup 3
 tail -c 600 "$out/bench.log"
-SFM_BENCH_REHEARSAL=1 step 600 "$out/rehearse2_selfspawn.log" python3 bench.py --gpus 2 --steps 5 --warmup 2 --repeats 3
+SFM_BENCH_REHEARSAL=1 step 600 "$out/rehearse2_selfspawn.log" python3 bench.py --full --gpus 2 --steps 5 --warmup 2 --repeats 3
 grep '^{' "$out/rehearse2_selfspawn.log" | cut -c 1-1500
-SFM_BENCH_REHEARSAL=1 step 300 "$out/rehearse2_repair.log" python3 bench.py --gpus 2 --steps 5 --warmup 2 --repeats 2 --pts 4000 --collective reduce_broadcast --scaling strong
+SFM_BENCH_REHEARSAL=1 step 300 "$out/rehearse2_repair.log" python3 bench.py --full --gpus 2 --steps 5 --warmup 2 --repeats 2 --pts 4000 --collective reduce_broadcast --scaling strong
 grep '^{' "$out/rehearse2_repair.log" | cut -c 1-600
 exit 0

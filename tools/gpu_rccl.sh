@@ -6,7 +6,7 @@ tag=${1:-rccl}
 out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
-tr() { port=$1; shift; timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port "$port" bench.py --gpus 1 "$@"; }
+tr() { port=$1; shift; timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port "$port" bench.py --gpus 1 --full "$@"; }
 tr 29541 --steps 100 --warmup 10 --no-cpu-baseline > "$out/torchrun_c3.log" 2>&1; echo "c3 rc=$?" | tee -a "$out/steps.log"
 grep '^{' "$out/torchrun_c3.log" > "$out/bench_torchrun_1rank_rccl_c3.json"
 # round 4: the library's own communicator inside sfm_ba_iterate (one C-ABI call for all K iterations), same box, interleaved

@@ -24,13 +24,13 @@ SFM_POOL_REDZONE=1 step 900 "$out/pytest_gpu_redzone.log" python -m pytest tests
 tail -1 "$out/pytest_gpu_redzone.log"
 step 120 "$out/smoke.log" python __graft_entry__.py smoke
 tail -1 "$out/smoke.log"
-step 300 "$out/bench.log" python bench.py
+step 300 "$out/bench.log" python bench.py --full
 tail -c 400 "$out/bench.log"
-step 240 "$out/bench_tri.log" python bench.py --config TRI --steps 20 --warmup 2
-step 240 "$out/bench_pnp.log" python bench.py --config PNP --steps 20 --warmup 2
-step 300 "$out/bench_c5.log" python bench.py --config C5 --steps 18 --warmup 1
-step 240 "$out/bench_c4_share.log" python bench.py --config C4 --pts 12500 --steps 10 --warmup 2 --no-cpu-baseline
-step 240 "$out/bench_c4_full.log" python bench.py --config C4 --steps 5 --warmup 1 --no-cpu-baseline
+step 240 "$out/bench_tri.log" python bench.py --full --config TRI --steps 20 --warmup 2
+step 240 "$out/bench_pnp.log" python bench.py --full --config PNP --steps 20 --warmup 2
+step 300 "$out/bench_c5.log" python bench.py --full --config C5 --steps 18 --warmup 1
+step 240 "$out/bench_c4_share.log" python bench.py --full --config C4 --pts 12500 --steps 10 --warmup 2 --no-cpu-baseline
+step 240 "$out/bench_c4_full.log" python bench.py --full --config C4 --steps 5 --warmup 1 --no-cpu-baseline
 step 240 "$out/bench_tri_pnp.log" python tools/bench_tri_pnp.py
 step 120 "$out/probe_solve.log" python tools/probe_solve.py
 step 120 "$out/flow_stamps.txt" python tools/flow_check.py stamps
