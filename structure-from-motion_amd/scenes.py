@@ -73,8 +73,78 @@ def visibility_mask(rng, n_cams, n_pts, visibility):
     return vis
 
 
+@dataclass(frozen=True)
+class Structure:
+    """Track-structured visibility, the shape the reference's incremental loop produces (ba_processor.py:137-267):
+    a point enters with its second registered view and is then seen by a run of consecutive views.
+
+    Every point gets a birth view and a track length ``1 + Geometric(1 / (mean_track - 1))`` (at least 2, mean
+    ``mean_track``) and is seen by the consecutive views ``[birth, birth + length)`` of its camera group, clipped at the
+    group's last view.  On top of that:
+
+    ``heavy``     fraction of points seen by every view of their group from their birth on (long tracks);
+    ``single``    fraction of points with exactly one observation;
+    ``empty``     camera indices with no observation at all (they are left out of every run);
+    ``clusters``  the cameras split into this many disjoint groups of consecutive indices, each point seen within one
+                  group only: the reduced camera system is block-diagonal;
+    ``hub``       camera indices that see every point (left out of the runs, added to every point afterwards).
+
+    Points are numbered in birth order, as the reference's incremental loop numbers them."""
+    mean_track: float = 4.0
+    heavy: float = 0.0
+    single: float = 0.0
+    empty: tuple = ()
+    clusters: int = 1
+    hub: tuple = ()
+
+    def groups(self, n_cams):
+        """The cameras each group's runs go over, in order: ``clusters`` consecutive index ranges without the empty
+        and hub cameras."""
+        skip = set(self.empty) | set(self.hub)
+        return [[int(c) for c in part if c not in skip] for part in np.array_split(np.arange(n_cams), self.clusters)]
+
+
+def structured_mask(rng, n_cams, n_pts, st):
+    """Visibility of a ``Structure`` (see there): (n_cams, n_pts) bool, columns in birth order."""
+    if st.mean_track < 2:
+        raise ValueError("mean_track must be >= 2")
+    if not 0 <= st.heavy + st.single <= 1:
+        raise ValueError("heavy + single must lie in [0, 1]")
+    if st.hub and st.single > 0:
+        raise ValueError("hub cameras see every point: no point can have a single observation")
+    if set(st.hub) & set(st.empty):
+        raise ValueError("a camera cannot be both a hub and empty")
+    groups = st.groups(n_cams)
+    if any(len(g) < 2 for g in groups):
+        raise ValueError("every camera group needs at least two cameras that are neither empty nor hubs")
+    group = rng.integers(0, len(groups), n_pts)
+    kind = rng.random(n_pts)                       # [0, single): one view; [single, single + heavy): to the group's end
+    single = kind < st.single
+    heavy = ~single & (kind < st.single + st.heavy)
+    length = 1 + (rng.geometric(1.0 / (st.mean_track - 1.0), n_pts) if st.mean_track > 2 else np.ones(n_pts, dtype=np.int64))
+    u = rng.random(n_pts)
+    vis = np.zeros((n_cams, n_pts), dtype=bool)
+    birth_cam = np.empty(n_pts, dtype=np.int64)
+    for p in range(n_pts):
+        g = groups[group[p]]
+        n = len(g)
+        if single[p]:
+            b = int(u[p] * n)
+            e = b + 1
+        else:
+            b = int(u[p] * (n - 1))                # at least two views left from the birth on
+            e = n if heavy[p] else min(n, b + int(length[p]))
+        vis[g[b:e], p] = True
+        birth_cam[p] = g[b]
+    vis[list(st.hub), :] = True
+    return vis[:, np.argsort(birth_cam, kind="stable")]
+
+
 def make_scene(n_cams, n_pts, visibility=1.0, seed=0, pixel_noise=0.5,
-               rot_noise=0.01, loc_noise=0.05, pt_noise=0.05):
+               rot_noise=0.01, loc_noise=0.05, pt_noise=0.05, structure=None):
+    """A seeded scene.  ``structure=None``: Bernoulli(``visibility``) per (camera, point) (``visibility_mask``; the
+    stream bench.py and the goldens are built from).  ``structure=Structure(...)``: track-structured visibility
+    (``visibility`` is then unused); the geometry is drawn the same way."""
     rng = np.random.default_rng(seed)
     intrinsic = UPENN_K.copy()
 
@@ -88,7 +158,10 @@ def make_scene(n_cams, n_pts, visibility=1.0, seed=0, pixel_noise=0.5,
         rots.append(Rotation.from_euler('zyx', ang).as_matrix())
         locs.append(rng.uniform(-1.5, 1.5, 3) * np.array([1.0, 0.3, 0.5]))
 
-    vis = visibility_mask(rng, n_cams, n_pts, visibility)
+    if structure is None:
+        vis = visibility_mask(rng, n_cams, n_pts, visibility)
+    else:
+        vis = structured_mask(rng, n_cams, n_pts, structure)
 
     # observation list sorted by (point, cam): the reference's BA loop order (ba_processor.py:304-306)
     pt_idx, cam_idx = np.nonzero(vis.T)
