@@ -401,6 +401,43 @@ int sfm_ba_reduced_system(int V, int N, int64_t M, const int* pt_ptr, const int*
                           double lambda, int quirks, int schur_mode,
                           double* S /*[7V][7V]*/, double* rhs /*[7V]*/);
 
+/* ---- descriptor matching: KeyTracker.__extend_list (key_tracker.py:213-317) ------------------------------------
+ * cv2.BFMatcher.knnMatch / .match of the new view's descriptors against every earlier view (key_tracker.py:248-263),
+ * the matcher built with NORM_L2 for key_type 'sift' / 'surf' and NORM_HAMMING otherwise (key_tracker.py:82-85).
+ * A descriptor set is uploaded once and stays resident; sfm_match runs one query set against n_refs reference sets
+ * in one launch.  Per (reference r, query i), at [r * n_query + i]: the best and second-best train index and float32
+ * distance by the order (distance, train index) -- ties go to the lower index -- and, in SFM_MATCH_MUTUAL, whether i
+ * is also the best query of its best train index (crossCheck, same tie rule).  Missing neighbours (a reference view
+ * with one descriptor has no second) are index -1, distance +inf.
+ * L2 distance = float32(sqrt(s)), correctly rounded; for integer-valued rows in [0, 255] (every uint8 set; float sets
+ * checked at creation) s = sum (a - b)^2 is exact (bf16 MFMA, int32), otherwise s is an fp32 sum of unspecified
+ * order.  Hamming distance = popcount(a ^ b) over the row's bytes, as a float.  Limits: L2 dim <= 256, Hamming rows
+ * <= 256 bytes.  The ratio test, crossCheck filtering, duplicate removal and table writes stay on the host
+ * (key_tracker.py:267-314, structure-from-motion_amd/matching.py). */
+#define SFM_MATCH_L2       0   /* cv2.NORM_L2 */
+#define SFM_MATCH_HAMMING  1   /* cv2.NORM_HAMMING */
+#define SFM_MATCH_KNN2     0   /* knnMatch(k=2): best and second best (key_tracker.py:259-260) */
+#define SFM_MATCH_NN1      1   /* match() without crossCheck: the best (key_tracker.py:262-263) */
+#define SFM_MATCH_MUTUAL   2   /* crossCheck: the best and the mutual flag (key_tracker.py:256-258, 83) */
+#define SFM_DESC_U8        0   /* uint8 rows (every SIFT / ORB descriptor OpenCV emits as uint8 or integer float32) */
+#define SFM_DESC_F32       1   /* float32 rows (L2 only) */
+#define SFM_DESC_INFO_N            1
+#define SFM_DESC_INFO_DIM          2
+#define SFM_DESC_INFO_EXACT        3   /* 1 when the exact integer L2 path applies to this set */
+#define SFM_DESC_INFO_UPLOAD_BYTES 4   /* host -> device bytes of the upload */
+typedef struct sfm_desc_set sfm_desc_set;
+/* Upload n rows of dim elements (bytes for Hamming) and convert them on the device.  n = 0 is a legal (empty) set. */
+int sfm_desc_create(int metric, int n, int dim, int dtype, const void* data, sfm_desc_set** out);
+int sfm_desc_destroy(sfm_desc_set* set);
+int sfm_desc_info(const sfm_desc_set* set, int what, int64_t* value);
+/* Blocking host form: every output is [n_refs][query n], caller-allocated; any output may be NULL.  A metric or dim
+ * that differs between the sets, an empty reference set or an unknown mode returns SFM_E_SHAPE. */
+int sfm_match(sfm_desc_set* query, int n_refs, sfm_desc_set* const* refs, int mode, int* best_idx, float* best_dist,
+              int* second_idx, float* second_dist, uint8_t* mutual);
+/* device form: the outputs are DEVICE pointers; enqueues on hip_stream (NULL = the library stream) and returns. */
+int sfm_match_dev(sfm_desc_set* query, int n_refs, sfm_desc_set* const* refs, int mode, int* d_best_idx, float* d_best_dist,
+                  int* d_second_idx, float* d_second_dist, uint8_t* d_mutual, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

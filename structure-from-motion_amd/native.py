@@ -23,6 +23,10 @@ K_PREP, K_LINEARIZE, K_SCHUR, K_SOLVE, K_BACKSUB, K_REDUCE, K_COUNT = 0, 1, 2, 3
 KERNEL_NAMES = ("prep", "linearize", "schur", "solve", "backsub", "reduce")
 INFO_SCHUR_KERNEL, INFO_UPLOAD_BYTES, INFO_N_CAMS, INFO_N_PTS, INFO_N_OBS, INFO_MAX_TRACK, INFO_GRAPH_REPLAYS = 1, 2, 3, 4, 5, 6, 7
 INFO_REDUCE_IN_SOLVE = 8
+MATCH_L2, MATCH_HAMMING = 0, 1
+MATCH_KNN2, MATCH_NN1, MATCH_MUTUAL = 0, 1, 2
+DESC_U8, DESC_F32 = 0, 1
+DESC_INFO_N, DESC_INFO_DIM, DESC_INFO_EXACT, DESC_INFO_UPLOAD_BYTES = 1, 2, 3, 4
 
 # every symbol include/sfm_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -42,6 +46,7 @@ EXPORTS = (
     "sfm_pool_mode", "sfm_tri_nonlinear_dev", "sfm_tri_linear_dev", "sfm_triangulate_dev", "sfm_pnp_nonlinear_batch_dev",
     "sfm_gather_points_dev", "sfm_ba_points_ptr", "sfm_ba_stream", "sfm_ba_event_overhead",
     "sfm_ba_get_state_rot", "sfm_ba_rederive_quaternions", "sfm_ba_flow_tasks", "sfm_ba_flow_tasks_deferred",
+    "sfm_desc_create", "sfm_desc_destroy", "sfm_desc_info", "sfm_match", "sfm_match_dev",
 )
 
 _lib = None
@@ -132,6 +137,12 @@ def load():
     lib.sfm_ba_event_overhead.argtypes = [vp, ctypes.c_int, _dp]
     lib.sfm_ba_get_state_rot.argtypes = [vp, _dp, _dp, _dp]
     lib.sfm_ba_rederive_quaternions.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+    lib.sfm_desc_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp)]
+    lib.sfm_desc_destroy.argtypes = [vp]
+    lib.sfm_desc_info.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
+    lib.sfm_match.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, _ip, ctypes.POINTER(ctypes.c_float), _ip,
+                              ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8)]
+    lib.sfm_match_dev.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -711,3 +722,87 @@ class BaProblem:
         self._lib.sfm_ba_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
         check(self._lib.sfm_ba_debug_stamps(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n))
         return out
+
+
+# ---- descriptor matching (KeyTracker.__extend_list, key_tracker.py:213-317) ------------------------------------
+class DescriptorSet:
+    """Device-resident descriptor rows of one view (sfm_desc_create ... sfm_desc_destroy).
+
+    ``metric`` is MATCH_L2 or MATCH_HAMMING; ``descriptors`` an (n, dim) array: uint8 (either metric) or float32 (L2),
+    or ``None`` / no rows for an empty set.  Integer-valued L2 rows in [0, 255] take the exact bf16-MFMA path
+    (``exact``)."""
+
+    def __init__(self, metric, descriptors):
+        self._lib = load()
+        self._h = None
+        d = np.zeros((0, 1), dtype=np.uint8) if descriptors is None else np.asarray(descriptors)
+        if d.size == 0 and d.ndim != 2:
+            d = d.reshape(0, 1)
+        if d.ndim != 2:
+            raise ValueError("descriptors must be (n, dim), got shape %s" % (d.shape,))
+        if d.dtype == np.uint8:
+            dtype = DESC_U8
+        elif metric == MATCH_L2:
+            d = d.astype(np.float32, copy=False); dtype = DESC_F32
+        else:
+            raise ValueError("Hamming matching needs uint8 descriptors, got %s" % d.dtype)
+        d = np.ascontiguousarray(d)
+        self.metric = int(metric)
+        self.n, self.dim = int(d.shape[0]), int(d.shape[1])
+        h = ctypes.c_void_p()
+        check(self._lib.sfm_desc_create(self.metric, self.n, self.dim, dtype, d.ctypes.data_as(ctypes.c_void_p) if self.n else None,
+                                        ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sfm_desc_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self, what):
+        v = ctypes.c_int64()
+        check(self._lib.sfm_desc_info(self._h, int(what), ctypes.byref(v)))
+        return int(v.value)
+
+    @property
+    def exact(self):
+        return bool(self.info(DESC_INFO_EXACT))
+
+    @property
+    def upload_bytes(self):
+        return self.info(DESC_INFO_UPLOAD_BYTES)
+
+
+def match(query, refs, mode=MATCH_KNN2):
+    """Brute-force matching of ``query`` (a DescriptorSet) against every set of ``refs`` in one device call.
+
+    Returns (best_idx, best_dist, second_idx, second_dist, mutual), each (len(refs), query.n): int32 / float32 /
+    int32 / float32 / bool.  Order (distance, train index); a missing neighbour is index -1, distance inf; ``mutual``
+    is only computed in MATCH_MUTUAL (all False otherwise)."""
+    lib = load()
+    refs = list(refs)
+    nr, nq = len(refs), query.n
+    bi = np.empty((nr, nq), dtype=np.int32); si = np.empty((nr, nq), dtype=np.int32)
+    bd = np.empty((nr, nq), dtype=np.float32); sd = np.empty((nr, nq), dtype=np.float32)
+    mu = np.zeros((nr, nq), dtype=np.uint8)
+    handles = (ctypes.c_void_p * max(nr, 1))(*[r._h for r in refs])
+    fp = ctypes.POINTER(ctypes.c_float)
+    check(lib.sfm_match(query._h, nr, handles, int(mode), iptr(bi), bd.ctypes.data_as(fp), iptr(si), sd.ctypes.data_as(fp),
+                        mu.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+    return bi, bd, si, sd, mu.astype(bool)
+
+
+def match_dev(query, refs, mode, d_best_idx, d_best_dist, d_second_idx, d_second_dist, d_mutual, stream=0):
+    """Stream-ordered form of ``match``: outputs are device pointers (integers) of (len(refs), query.n) arrays."""
+    refs = list(refs)
+    handles = (ctypes.c_void_p * max(len(refs), 1))(*[r._h for r in refs])
+    check(load().sfm_match_dev(query._h, len(refs), handles, int(mode), _vp(d_best_idx), _vp(d_best_dist), _vp(d_second_idx),
+                               _vp(d_second_dist), _vp(d_mutual), _vp(stream)))

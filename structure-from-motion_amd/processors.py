@@ -21,13 +21,14 @@ Reference interfaces mirrored (file:line in the reference repo):
   CamposeProcessor.nonlinear_estimate_cam_pose_pnp / construct_jacobian_matrix / estimate_cam_pose_pnp
       campose_processor.py:308-459 / 462-482 / 192-246
   BaProcessor.__execute_bundle_adjustment          ba_processor.py:274-439
+  KeyTracker.__extend_list                         key_tracker.py:213-317
 """
 import logging
 import math
 
 import numpy as np
 
-from . import native
+from . import matching, native
 from .geometry import (pack_cameras, quaternion_to_rotation_unchecked, quaternions_to_rotations)
 from .observations import KeyCache, ObservationTracker, build_observations, gather_normalised_keys
 from .q13 import det_branch_fires, reference_winner
@@ -533,3 +534,175 @@ class HipBaProcessor(HipBaMixin):
         self.epi_processor = epi_processor
         self.tri_processor = tri_processor
         self.campose_processor = campose_processor
+
+
+# ------------------------------------------------------------------------------------------------
+INVALID_MATCH_VAL = NOT_USED_TRI_VAL = -1          # key_tracker.py:8
+
+
+class HipKeyTrackerMixin:
+    """``KeyTracker.__extend_list`` (key_tracker.py:213-317) with the brute-force matching on the device.
+
+    Reads ``self.key_type`` / ``is_cross_check`` / ``track_list`` and ``view.key_pts`` / ``view.key_descriptors``;
+    writes the ``KeyTrack.table`` rows the reference writes.  Every view's descriptors stay resident on the device
+    (one ``native.DescriptorSet`` per view index) and are uploaded again only when the view's ``key_descriptors``
+    object is another one, so a new view uploads only itself.  The new view is matched against all earlier views in
+    one launch; the ratio / crossCheck filter, the duplicate removal (quirk Q14), the optional fundamental-matrix
+    inliers (``HipEpipolarProcessor``, per reference view in the reference's order: Python's global RNG stream is
+    consumed identically; quirk Q15) and the table writes run on the host (``matching.py``).
+    ``kt_upload_bytes`` reports the descriptor bytes uploaded so far; ``kt_release()`` frees the device copies."""
+
+    def kt_release(self):
+        sets = self.__dict__.pop("_hip_desc", None)
+        for _obj, ds in (sets or {}).values():
+            ds.close()
+
+    @property
+    def kt_upload_bytes(self):
+        return self.__dict__.get("_hip_desc_bytes", 0)
+
+    def _kt_metric(self):
+        return native.MATCH_L2 if self.key_type in ['sift', 'surf'] else native.MATCH_HAMMING    # key_tracker.py:82-85
+
+    def _kt_set(self, idx, descriptors):
+        sets = self.__dict__.setdefault("_hip_desc", {})
+        have = sets.get(idx)
+        if have is not None and have[0] is descriptors:
+            return have[1]
+        if have is not None:
+            have[1].close()
+        ds = native.DescriptorSet(self._kt_metric(), descriptors)
+        sets[idx] = (descriptors, ds)
+        self.__dict__["_hip_desc_bytes"] = self.kt_upload_bytes + ds.upload_bytes
+        return ds
+
+    def _extend_list(self, new_view, views, is_knn_match=False, is_fund_inlier=False, ransac_config=None):
+        key_num = len(new_view.key_pts)
+        new_track_idx = len(self.track_list)
+        refs = []
+        for ref_idx, ref_view in enumerate(views):
+            d = ref_view.key_descriptors
+            if d is None or len(d) == 0:      # undefined without cv2 (INTEGRATION.md, deviation of Q16)
+                raise ValueError("reference view {} has no descriptors".format(ref_idx))
+            refs.append(self._kt_set(ref_idx, d))
+        query = self._kt_set(new_track_idx, new_view.key_descriptors)
+        mode = matching.match_mode(is_knn_match, self.is_cross_check)
+        if refs and query.n:
+            nn = native.match(query, refs, mode)
+        else:
+            empty_i = np.full((len(refs), 0), -1, dtype=np.int32)
+            empty_f = np.zeros((len(refs), 0), dtype=np.float32)
+            nn = (empty_i, empty_f, empty_i, empty_f, np.zeros((len(refs), 0), dtype=bool))
+
+        for track in self.track_list:                                           # key_tracker.py:236-237
+            track.expand_table()
+        new_track = type(self.track_list[0])(len(self.track_list) + 1, key_num, new_track_idx)   # key_tracker.py:240
+
+        keys = KeyCache() if is_fund_inlier else None
+        all_views = list(views) + [new_view]
+        for ref_idx in range(len(refs)):                                        # key_tracker.py:247
+            q, t, d = matching.filter_matches(nn[0][ref_idx], nn[1][ref_idx], nn[2][ref_idx], nn[3][ref_idx], nn[4][ref_idx],
+                                              is_knn_match, self.is_cross_check)
+            n_in = None
+            if is_fund_inlier:                                                  # key_tracker.py:294-299
+                qk, tk, _dk = matching.dedup_matches(q, t, d)
+                ref_pts = np.ones((3, tk.shape[0])); que_pts = np.ones((3, qk.shape[0]))
+                ref_pts[0:2] = keys.keys(all_views, ref_idx)[tk].T
+                que_pts[0:2] = keys.keys(all_views, len(views))[qk].T
+                ep = HipEpipolarProcessor(ransac_config)
+                n_in = len(ep.determine_fundamental_mat([ref_pts, que_pts], ransac_config))
+            wq, wt = matching.table_writes(q, t, d, n_in)
+            self.track_list[ref_idx].table[new_track_idx, wt] = wq              # key_tracker.py:313
+            new_track.table[ref_idx, wq] = wt                                   # key_tracker.py:314
+        self.track_list.append(new_track)
+
+    # the reference calls the name-mangled private method (key_tracker.py:126)
+    def _KeyTracker__extend_list(self, new_view, views, is_knn_match=False, is_fund_inlier=False, ransac_config=None):
+        return self._extend_list(new_view, views, is_knn_match, is_fund_inlier, ransac_config)
+
+
+class HipKeyTrack:
+    """Mirror of key_tracker.KeyTrack (key_tracker.py:14-59)."""
+
+    def __init__(self, rows, cols, idx):
+        self.table = np.empty((rows, cols), dtype='int')
+        self.table.fill(INVALID_MATCH_VAL)
+        self.idx = idx
+        self.key_num = cols
+
+    def expand_table(self):
+        arr = np.full((1, self.key_num), INVALID_MATCH_VAL, dtype='int')
+        self.table = np.append(self.table, arr, 0)
+
+    def update_usage(self, used_indices, tri_indices):
+        # for (i, j), val in ndenumerate(used_indices): table[idx, val] = tri_indices[0, j]  (used_indices is 2-D)
+        used = np.asarray(used_indices)
+        self.table[self.idx, used.reshape(-1)] = np.asarray(tri_indices)[0, np.indices(used.shape)[1].reshape(-1)]
+
+    def extract_unconstructed_points(self):
+        return np.asarray(np.where(self.table[self.idx, :] == NOT_USED_TRI_VAL))
+
+    def extract_constructed_points(self):
+        indices = np.asarray(np.where(self.table[self.idx, :] != NOT_USED_TRI_VAL))
+        return indices, np.take(self.table[self.idx, :], indices)
+
+
+class HipKeyTracker(HipKeyTrackerMixin):
+    """Standalone KeyTracker (key_tracker.py:63-344) without cv2: the constructor's fields, ``add_new_view``,
+    ``generate_matched_pairs``, ``find_best_view``, ``is_visible`` and ``clear``, so that the BA drop-in runs on it."""
+
+    def __init__(self, key_type, is_cross_check, is_knn_match, is_fund_inlier, ransac_config):
+        self.key_type = key_type
+        self.is_cross_check = is_cross_check
+        self.is_knn_match = is_knn_match
+        self.is_fund_inlier = is_fund_inlier
+        self.ransac_config = ransac_config
+        self.track_list = []
+
+    def add_new_view(self, new_view, views, is_knn_match=None, is_fund_inlier=None, ransac_config=None):
+        # falsy -> instance default (key_tracker.py:114-119, quirk Q17)
+        if not is_knn_match:
+            is_knn_match = self.is_knn_match
+        if not is_fund_inlier:
+            is_fund_inlier = self.is_fund_inlier
+        if not ransac_config:
+            ransac_config = self.ransac_config
+        if len(self.track_list) == 0:
+            self.track_list.append(HipKeyTrack(1, len(new_view.key_pts), 0))
+        else:
+            self._KeyTracker__extend_list(new_view, views, is_knn_match, is_fund_inlier, ransac_config)
+
+    def generate_matched_pairs(self, ref_idx, que_idx, views):
+        """key_tracker.py:132-181 (entries ``row > 0`` only: key 0 of the query view is never paired, quirk Q3)."""
+        if ref_idx < 0 or que_idx < 0 or ref_idx >= len(self.track_list) or que_idx >= len(self.track_list):
+            print('{}:{} - invalid ref_idx {} or invalid que_idx {}'.format(
+                self.__class__.__name__, 'generate_matched_pairs', ref_idx, que_idx))
+            return None
+        row = self.track_list[ref_idx].table[que_idx:que_idx + 1, :]
+        r_idx = np.where(row > 0)[1]
+        q_idx = row[0, r_idx]
+        num = r_idx.shape[0]
+        ref_pts = np.zeros((3, num)); ref_pts[2] = 1.0
+        que_pts = np.zeros((3, num)); que_pts[2] = 1.0
+        for c, (pts, views_idx, idx) in enumerate(((ref_pts, ref_idx, r_idx), (que_pts, que_idx, q_idx))):
+            kp = views[views_idx].key_pts
+            for j, k in enumerate(idx.tolist()):
+                pts[0, j], pts[1, j] = kp[k].pt[0], kp[k].pt[1]
+        return [ref_pts, que_pts], r_idx.reshape(1, num).astype(int), q_idx.reshape(1, num).astype(int)
+
+    def find_best_view(self, input_idx):
+        if input_idx < 0 or input_idx >= len(self.track_list):
+            print('{}:{} - invalid input_idx {}'.format(self.__class__.__name__, 'find_best_view', input_idx))
+            return -1
+        return 0
+
+    def is_visible(self, view_idx, tri_pt_idx):
+        key_idx = np.where(self.track_list[view_idx].table[view_idx, :] == tri_pt_idx)
+        if np.any(key_idx):
+            key_idx = key_idx[0][0]
+        else:
+            key_idx = -1
+        return key_idx
+
+    def clear(self):
+        self.track_list = []

@@ -223,3 +223,79 @@ def reprojection_rmse(cams, pts, scene):
     v = k[1, 1] * py / pz + k[1, 2]
     err = (u - scene.uv_pix[0]) ** 2 + (v - scene.uv_pix[1]) ** 2
     return float(np.sqrt(err.mean()))
+
+
+# ---- descriptor views for KeyTracker.__extend_list (key_tracker.py:213-317) ----------------------------------------
+class KeyPoint:
+    """The part of ``cv2.KeyPoint`` the pipeline reads: ``pt`` = (x, y) pixels."""
+    __slots__ = ("pt",)
+
+    def __init__(self, x, y):
+        self.pt = (float(x), float(y))
+
+
+@dataclass
+class DescriptorViews:
+    """Per view: keys (pixels), SIFT-like uint8 descriptors (n, 128), ORB-like uint8 descriptors (n, 32), and the
+    3D point each key observes (-1 for a distractor)."""
+    intrinsic: np.ndarray
+    pts: np.ndarray    # (3, n_pts) the scene's points
+    rots: list
+    locs: list
+    pix: list          # (n_v, 2) float64
+    sift: list         # (n_v, 128) uint8
+    orb: list          # (n_v, 32) uint8
+    point: list        # (n_v,) int64
+
+    def key_pts(self, v):
+        return [KeyPoint(x, y) for x, y in self.pix[v]]
+
+
+def make_descriptor_views(n_views=5, n_pts=200, seed=0, visibility=0.8, n_distract=40, noise=2, orb_flips=10, n_dup=6):
+    """Seeded matching workload: a projected scene whose 3D points carry an integer SIFT-like base descriptor (norm
+    about 512, clipped to [0, 255]) observed with small integer noise per key, distractor keys with random
+    descriptors, and an ORB-like 256-bit variant (random base bits, ``orb_flips`` flipped per observation).  Each
+    view also repeats ``n_dup`` of its rows verbatim at the end (exact ties between train rows: the lower index must
+    win) and ``n_dup`` rows with extra noise (several queries on one train row: the duplicate removal, quirk Q14)."""
+    rng = np.random.default_rng(seed)
+    intrinsic = UPENN_K.copy()
+    pts = np.vstack((rng.uniform(-4, 4, n_pts), rng.uniform(-3, 3, n_pts), rng.uniform(8, 16, n_pts)))
+    base = rng.gamma(0.6, 1.0, (n_pts, 128))
+    base = np.clip(np.rint(base / np.linalg.norm(base, axis=1, keepdims=True) * 512.0), 0, 255)
+    orb_base = rng.integers(0, 2, (n_pts, 256), dtype=np.uint8)
+    rots, locs, pix, sift, orb, point = [], [], [], [], [], []
+    for v in range(n_views):
+        ang = rng.uniform(-0.1, 0.1, 3) if v else np.zeros(3)
+        rot = Rotation.from_euler('zyx', ang).as_matrix()
+        loc = np.array([0.4 * v, 0.05 * rng.normal(), 0.1 * rng.normal()]) if v else np.zeros(3)
+        seen = np.flatnonzero(rng.random(n_pts) < visibility)
+        uv, _ = _project(rot, loc, pts[:, seen], intrinsic)
+        d_s = np.clip(base[seen] + rng.integers(-noise, noise + 1, (seen.shape[0], 128)), 0, 255)
+        bits = orb_base[seen].copy()
+        for i in range(seen.shape[0]):
+            bits[i, rng.choice(256, orb_flips, replace=False)] ^= 1
+        dis_s = rng.gamma(0.6, 1.0, (n_distract, 128))
+        dis_s = np.clip(np.rint(dis_s / np.linalg.norm(dis_s, axis=1, keepdims=True) * 512.0), 0, 255)
+        dis_b = rng.integers(0, 2, (n_distract, 256), dtype=np.uint8)
+        dis_uv = np.vstack((rng.uniform(0, 1280, n_distract), rng.uniform(0, 960, n_distract)))
+        p = np.concatenate((seen, np.full(n_distract, -1)))
+        u = np.hstack((uv, dis_uv)).T
+        ds = np.vstack((d_s, dis_s))
+        db = np.vstack((bits, dis_b))
+        perm = rng.permutation(p.shape[0])
+        p, u, ds, db = p[perm], u[perm], ds[perm], db[perm]
+        same = rng.choice(p.shape[0], n_dup, replace=False)            # verbatim copies: exact ties
+        near = rng.choice(p.shape[0], n_dup, replace=False)            # noisy copies: duplicate train indices
+        ds_near = np.clip(ds[near] + rng.integers(-noise, noise + 1, (n_dup, 128)), 0, 255)
+        db_near = db[near].copy()
+        db_near[np.arange(n_dup), rng.integers(0, 256, n_dup)] ^= 1
+        p = np.concatenate((p, p[same], p[near]))
+        u = np.vstack((u, u[same], u[near] + rng.normal(0, 0.5, (n_dup, 2))))
+        ds = np.vstack((ds, ds[same], ds_near))
+        db = np.vstack((db, db[same], db_near))
+        rots.append(rot); locs.append(loc)
+        pix.append(u.astype(np.float64))
+        sift.append(ds.astype(np.uint8))
+        orb.append(np.packbits(db, axis=1))
+        point.append(p.astype(np.int64))
+    return DescriptorViews(intrinsic, pts, rots, locs, pix, sift, orb, point)
