@@ -228,7 +228,8 @@ __global__ __launch_bounds__(256) void match_simt_kernel(const void* __restrict_
           const float e = __uint_as_float(qv[i]) - __uint_as_float(trow[i]);
           acc = __builtin_fmaf(e, e, acc);
         }
-      v = __float_as_uint(__fsqrt_rn(acc));
+      // sqrtf, not __fsqrt_rn: HIP maps the latter to the bare v_sqrt_f32 (1 ulp), sqrtf is correctly rounded
+      v = __float_as_uint(sqrtf(acc));
     }
     const uint64_t key = ((uint64_t)v << 32) | (uint32_t)t;
     if (live) top2_insert(k1, k2, key);
