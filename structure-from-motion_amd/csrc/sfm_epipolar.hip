@@ -11,6 +11,9 @@
 //   essential_kernel / pose_candidates_kernel   single-thread 3x3 algebra (epipolar:60-95, campose:29-100)
 //   cheirality_kernel        both depths positive, per candidate (campose:133-189)
 // Everything is once-per-sequence work; the kernels are written for clarity, not throughput.
+//
+// Fixed by tests/test_gpu_two_view_paths.py: svd3 prescales B by an exact power of two, so that
+// pose_candidates(2^k E) and essential_from_fundamental(2^k F) are bit-identical to k = 0 over the whole normal range.
 #include <cmath>
 #include <vector>
 
@@ -19,7 +22,18 @@
 namespace sfm {
 
 // 3x3 SVD pieces: columns of B become sigma_c u_c, V the right singular vectors; ord[] sorts sigma descending.
+// B is first scaled by the power of two that brings max|B| into [1, 2): exact, so the result is that of 2^e B, whose
+// Jacobi sums al, be and al*be cannot overflow (they did from max|B| ~ 2^255) or lose bits to underflow (below ~2^-511).
+// sigma and the columns of B come out scaled by 2^e; every caller uses sigma only in ratios or as B / sigma.
 __device__ void svd3(double (&B)[3][3], double (&V)[3][3], double (&sig)[3], int (&ord)[3]) {
+  double mx = 0.0;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) mx = fmax(mx, fabs(B[i][j]));        // fmax skips NaN, which stays NaN below
+  if (mx > 0.0 && mx <= 1.7976931348623157e308) {
+    const int e = -ilogb(mx);
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) B[i][j] = ldexp(B[i][j], e);
+  }
   jacobi_right_vectors<3>(B, V, 40);
   for (int c = 0; c < 3; ++c) sig[c] = sqrt(B[0][c] * B[0][c] + B[1][c] * B[1][c] + B[2][c] * B[2][c]);
   ord[0] = 0; ord[1] = 1; ord[2] = 2;

@@ -471,10 +471,11 @@ def pnp_six_point_hypotheses(uv_pix, pts_h, intrinsic, samples, threshold):
     return rot, loc, cnt
 
 
-def fundamental_ransac(left, right, samples, threshold):
+def fundamental_ransac(left, right, samples, threshold, return_count=False):
     """Eight-point RANSAC (epipolar_processor.py:22-57).  left/right: (>=2, n) pixel rows; samples: (n_hyp, 8)
     indices drawn by the caller (ignored when n == 8).  Returns (F (3,3), inlier index list or None, best
-    hypothesis index or -1)."""
+    hypothesis index or -1); with ``return_count`` a fourth item, the inlier count that chose the winner (the
+    scoring kernel's, not the length of the list, which the finishing kernel recomputes)."""
     left = f64(np.asarray(left)[0:2]); right = f64(np.asarray(right)[0:2])
     n = left.shape[1]
     samples = i32(samples if samples is not None and n != 8 else np.arange(8)).reshape(-1, 8)
@@ -485,6 +486,8 @@ def fundamental_ransac(left, right, samples, threshold):
     check(lib.sfm_fundamental_ransac(n, dptr(left), dptr(right), samples.shape[0], iptr(samples), float(threshold),
                                      dptr(fund), iptr(mask), ctypes.byref(cnt), ctypes.byref(best)))
     inliers = None if best.value < 0 else np.flatnonzero(mask[:n]).tolist()
+    if return_count:
+        return fund, inliers, best.value, cnt.value
     return fund, inliers, best.value
 
 
