@@ -438,6 +438,48 @@ int sfm_match(sfm_desc_set* query, int n_refs, sfm_desc_set* const* refs, int mo
 int sfm_match_dev(sfm_desc_set* query, int n_refs, sfm_desc_set* const* refs, int mode, int* d_best_idx, float* d_best_dist,
                   int* d_second_idx, float* d_second_dist, uint8_t* d_mutual, void* hip_stream);
 
+/* ---- SIFT detection: ViewProcessor.__extract_keys (view_processor.py:151-164, 199-202) --------------------------
+ * cv.SIFT_create().detectAndCompute(img, None) by the contract of INTEGRATION.md 'SIFT detection' (firstOctave -1,
+ * nfeatures 0, no mask): keypoints sorted by (x, y asc; size desc; angle asc; response desc; octave desc) without
+ * duplicates, their cv2 fields after the firstOctave fixup, and (n, 128) float32 descriptors with integer values in
+ * [0, 255].  img is (height, width) gray or (height, width, 3) BGR uint8 with rows row_stride_bytes apart.  A bad
+ * shape, channel count or parameter returns SFM_E_SHAPE; an image whose octave count is <= 0 gives zero keypoints.
+ * The call is blocking; it enqueues on params->stream (NULL = the library stream). */
+typedef struct sfm_sift_params {
+  int n_octave_layers;        /* nOctaveLayers, 3; 1 .. 16 */
+  double contrast_threshold;  /* contrastThreshold, 0.04 */
+  double edge_threshold;      /* edgeThreshold, 10 */
+  double sigma;               /* sigma, 1.6 */
+  int keep_pyramid;           /* 1: keep the Gaussian and DoG levels on the device for sfm_sift_result_copy_level */
+  void* stream;               /* hipStream_t or NULL */
+} sfm_sift_params;
+#define SFM_SIFT_INFO_N             1   /* final keypoints */
+#define SFM_SIFT_INFO_N_OCTAVES     2
+#define SFM_SIFT_INFO_N_PRE         3   /* refined keypoints before orientation */
+#define SFM_SIFT_INFO_N_LAYERS      4
+#define SFM_SIFT_INFO_KEEPS_PYRAMID 5
+#define SFM_SIFT_LEVEL_GAUSS        0   /* levels 0 .. L + 2 of an octave */
+#define SFM_SIFT_LEVEL_DOG          1   /* levels 0 .. L + 1 of an octave */
+typedef struct sfm_sift_result sfm_sift_result;
+/* params NULL = the defaults above. */
+int sfm_sift_detect(const uint8_t* img, int height, int width, int channels, int64_t row_stride_bytes,
+                    const sfm_sift_params* params, sfm_sift_result** out);
+int sfm_sift_result_info(const sfm_sift_result* r, int what, int64_t* value);
+/* height and width of every level of pyramid octave `octave` (0 = the x2 base image). */
+int sfm_sift_result_level_shape(const sfm_sift_result* r, int octave, int* height, int* width);
+/* Caller-allocated [n] outputs (descriptors [n][128]); any may be NULL. */
+int sfm_sift_result_copy(const sfm_sift_result* r, float* x, float* y, float* size, float* angle, float* response,
+                         int32_t* octave, float* descriptors);
+/* Debug: the refined keypoints before orientation ([n_pre], pyramid coordinates, packed octave before the fixup), in
+ * the order (x, y asc; size desc; response desc; octave desc). */
+int sfm_sift_result_copy_pre(const sfm_sift_result* r, float* x, float* y, float* size, float* response, int32_t* octave);
+/* Debug: one Gaussian or DoG level ([height][width] of its octave); needs keep_pyramid. */
+int sfm_sift_result_copy_level(const sfm_sift_result* r, int kind, int octave, int level, float* out);
+int sfm_sift_result_destroy(sfm_sift_result* r);
+/* The float32 blur weights the library uses for a Gaussian of this sigma (ksize = rint(8 sigma + 1) | 1 taps; at
+ * most `capacity` are written; weights may be NULL to ask for ksize). */
+int sfm_sift_blur_kernel(double sigma, int capacity, float* weights, int* ksize);
+
 #ifdef __cplusplus
 }
 #endif

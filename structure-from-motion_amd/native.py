@@ -27,6 +27,8 @@ MATCH_L2, MATCH_HAMMING = 0, 1
 MATCH_KNN2, MATCH_NN1, MATCH_MUTUAL = 0, 1, 2
 DESC_U8, DESC_F32 = 0, 1
 DESC_INFO_N, DESC_INFO_DIM, DESC_INFO_EXACT, DESC_INFO_UPLOAD_BYTES = 1, 2, 3, 4
+SIFT_INFO_N, SIFT_INFO_N_OCTAVES, SIFT_INFO_N_PRE, SIFT_INFO_N_LAYERS, SIFT_INFO_KEEPS_PYRAMID = 1, 2, 3, 4, 5
+SIFT_LEVEL_GAUSS, SIFT_LEVEL_DOG = 0, 1
 
 # every symbol include/sfm_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -47,6 +49,8 @@ EXPORTS = (
     "sfm_gather_points_dev", "sfm_ba_points_ptr", "sfm_ba_stream", "sfm_ba_event_overhead",
     "sfm_ba_get_state_rot", "sfm_ba_rederive_quaternions", "sfm_ba_flow_tasks", "sfm_ba_flow_tasks_deferred",
     "sfm_desc_create", "sfm_desc_destroy", "sfm_desc_info", "sfm_match", "sfm_match_dev",
+    "sfm_sift_detect", "sfm_sift_result_info", "sfm_sift_result_level_shape", "sfm_sift_result_copy",
+    "sfm_sift_result_copy_pre", "sfm_sift_result_copy_level", "sfm_sift_result_destroy", "sfm_sift_blur_kernel",
 )
 
 _lib = None
@@ -143,6 +147,16 @@ def load():
     lib.sfm_match.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, _ip, ctypes.POINTER(ctypes.c_float), _ip,
                               ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8)]
     lib.sfm_match_dev.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, vp, vp, vp, vp, vp, vp]
+    fp = ctypes.POINTER(ctypes.c_float)
+    lib.sfm_sift_detect.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                    ctypes.POINTER(SiftParams), ctypes.POINTER(vp)]
+    lib.sfm_sift_result_info.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
+    lib.sfm_sift_result_level_shape.argtypes = [vp, ctypes.c_int, _ip, _ip]
+    lib.sfm_sift_result_copy.argtypes = [vp, fp, fp, fp, fp, fp, _ip, fp]
+    lib.sfm_sift_result_copy_pre.argtypes = [vp, fp, fp, fp, fp, _ip]
+    lib.sfm_sift_result_copy_level.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp]
+    lib.sfm_sift_result_destroy.argtypes = [vp]
+    lib.sfm_sift_blur_kernel.argtypes = [ctypes.c_double, ctypes.c_int, fp, _ip]
     _lib = lib
     return lib
 
@@ -809,3 +823,117 @@ def match_dev(query, refs, mode, d_best_idx, d_best_dist, d_second_idx, d_second
     handles = (ctypes.c_void_p * max(len(refs), 1))(*[r._h for r in refs])
     check(load().sfm_match_dev(query._h, len(refs), handles, int(mode), _vp(d_best_idx), _vp(d_best_dist), _vp(d_second_idx),
                                _vp(d_second_dist), _vp(d_mutual), _vp(stream)))
+
+
+# ---- SIFT detection (ViewProcessor.__extract_keys, view_processor.py:199-202) ------------------------------------
+class SiftParams(ctypes.Structure):
+    _fields_ = [("n_octave_layers", ctypes.c_int), ("contrast_threshold", ctypes.c_double),
+                ("edge_threshold", ctypes.c_double), ("sigma", ctypes.c_double), ("keep_pyramid", ctypes.c_int),
+                ("stream", ctypes.c_void_p)]
+
+
+def _sift_image(img):
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.size == 0 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)):
+        raise ValueError("SIFT input must be a non-empty (H, W) or (H, W, 3) uint8 image, got %s %s" % (a.dtype, a.shape))
+    return np.ascontiguousarray(a)
+
+
+class SiftResult:
+    """One sfm_sift_detect result (a context manager).  ``arrays()`` gives the keypoints and descriptors; the
+    debug reads (``level``, ``pre``) need ``keep_pyramid=True`` for the pyramid levels."""
+
+    def __init__(self, img, n_octave_layers=3, contrast_threshold=0.04, edge_threshold=10.0, sigma=1.6,
+                 keep_pyramid=False, stream=0):
+        self._lib = load()
+        self._h = None
+        a = _sift_image(img)
+        prm = SiftParams(int(n_octave_layers), float(contrast_threshold), float(edge_threshold), float(sigma),
+                         int(bool(keep_pyramid)), ctypes.c_void_p(stream) if stream else None)
+        h = ctypes.c_void_p()
+        ch = 1 if a.ndim == 2 else 3
+        check(self._lib.sfm_sift_detect(a.ctypes.data_as(ctypes.c_void_p), a.shape[0], a.shape[1], ch, a.strides[0],
+                                        ctypes.byref(prm), ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sfm_sift_result_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self, what):
+        v = ctypes.c_int64()
+        check(self._lib.sfm_sift_result_info(self._h, int(what), ctypes.byref(v)))
+        return int(v.value)
+
+    @property
+    def n(self):
+        return self.info(SIFT_INFO_N)
+
+    @property
+    def n_octaves(self):
+        return self.info(SIFT_INFO_N_OCTAVES)
+
+    @property
+    def n_layers(self):
+        return self.info(SIFT_INFO_N_LAYERS)
+
+    def level_shape(self, octave):
+        h, w = ctypes.c_int(), ctypes.c_int()
+        check(self._lib.sfm_sift_result_level_shape(self._h, int(octave), ctypes.byref(h), ctypes.byref(w)))
+        return h.value, w.value
+
+    def arrays(self):
+        """dict of x, y, size, angle, response (float32), octave (int32) and descriptors ((n, 128) float32)."""
+        n = self.n
+        out = {k: np.zeros(n, dtype=np.float32) for k in ("x", "y", "size", "angle", "response")}
+        out["octave"] = np.zeros(n, dtype=np.int32)
+        out["descriptors"] = np.zeros((n, 128), dtype=np.float32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        check(self._lib.sfm_sift_result_copy(self._h, *[out[k].ctypes.data_as(fp) for k in ("x", "y", "size", "angle", "response")],
+                                              iptr(out["octave"]), out["descriptors"].ctypes.data_as(fp)))
+        return out
+
+    def pre(self):
+        """The refined keypoints before orientation (pyramid coordinates, octave field before the fixup)."""
+        n = self.info(SIFT_INFO_N_PRE)
+        out = {k: np.zeros(n, dtype=np.float32) for k in ("x", "y", "size", "response")}
+        out["octave"] = np.zeros(n, dtype=np.int32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        check(self._lib.sfm_sift_result_copy_pre(self._h, *[out[k].ctypes.data_as(fp) for k in ("x", "y", "size", "response")],
+                                                 iptr(out["octave"])))
+        return out
+
+    def level(self, kind, octave, level):
+        """One Gaussian (kind SIFT_LEVEL_GAUSS) or DoG (SIFT_LEVEL_DOG) level as an (h, w) float32 array."""
+        h, w = self.level_shape(octave)
+        out = np.zeros((h, w), dtype=np.float32)
+        check(self._lib.sfm_sift_result_copy_level(self._h, int(kind), int(octave), int(level),
+                                                   out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out
+
+
+def sift_detect(img, **params):
+    """detectAndCompute(img, None) on the GPU: a dict of x, y, size, angle, response, octave and (n, 128) float32
+    descriptors, in the contract's order (INTEGRATION.md 'SIFT detection').  ``params``: n_octave_layers,
+    contrast_threshold, edge_threshold, sigma, stream."""
+    with SiftResult(img, **params) as r:
+        return r.arrays()
+
+
+def sift_blur_kernel(sigma):
+    """The float32 Gaussian weights the library blurs with for ``sigma``."""
+    lib = load()
+    k = ctypes.c_int()
+    check(lib.sfm_sift_blur_kernel(float(sigma), 0, None, ctypes.byref(k)))
+    w = np.zeros(k.value, dtype=np.float32)
+    check(lib.sfm_sift_blur_kernel(float(sigma), k.value, w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(k)))
+    return w

@@ -22,9 +22,11 @@ Reference interfaces mirrored (file:line in the reference repo):
       campose_processor.py:308-459 / 462-482 / 192-246
   BaProcessor.__execute_bundle_adjustment          ba_processor.py:274-439
   KeyTracker.__extend_list                         key_tracker.py:213-317
+  View / ViewProcessor.__extract_keys              view_processor.py:14-106 / 110-202
 """
 import logging
 import math
+import pickle
 
 import numpy as np
 
@@ -706,3 +708,119 @@ class HipKeyTracker(HipKeyTrackerMixin):
 
     def clear(self):
         self.track_list = []
+
+
+# ------------------------------------------------------------------------------------------------
+class HipKeyPoint:
+    """The ``cv2.KeyPoint`` fields the reference reads and writes (view_processor.py:100-101, 178-180)."""
+    __slots__ = ("pt", "size", "angle", "response", "octave", "class_id")
+
+    def __init__(self, x=0.0, y=0.0, size=0.0, angle=-1.0, response=0.0, octave=0, class_id=-1):
+        self.pt = (float(x), float(y))
+        self.size = float(size)
+        self.angle = float(angle)
+        self.response = float(response)
+        self.octave = int(octave)
+        self.class_id = int(class_id)
+
+    def __repr__(self):
+        return "HipKeyPoint(pt=%r, size=%r, angle=%r, response=%r, octave=%d)" % (
+            self.pt, self.size, self.angle, self.response, self.octave)
+
+
+def keypoints_from_arrays(kp):
+    """HipKeyPoint list of a ``native.sift_detect`` result (float32 fields widened to Python floats, as cv2 does)."""
+    return [HipKeyPoint(x, y, s, a, r, o) for x, y, s, a, r, o in
+            zip(kp["x"].tolist(), kp["y"].tolist(), kp["size"].tolist(), kp["angle"].tolist(), kp["response"].tolist(),
+                kp["octave"].tolist())]
+
+
+class HipViewProcessorMixin:
+    """``ViewProcessor.__extract_keys`` (view_processor.py:199-202) with SIFT detection on the device: returns
+    (list of HipKeyPoint, float32 (n, 128) descriptors), what ``detectAndCompute(img, None)`` returns for
+    ``SIFT_create()`` by the contract of INTEGRATION.md 'SIFT detection'.  An image without keypoints gives
+    ``([], None)``, as cv2 does."""
+
+    def _ViewProcessor__extract_keys(self, img):
+        if getattr(self, "key_type", "sift") != "sift":
+            raise ValueError("HipViewProcessorMixin: only key_type 'sift' runs on the device, got %r" % (self.key_type,))
+        kp = native.sift_detect(img)
+        if len(kp["x"]) == 0:
+            return [], None
+        return keypoints_from_arrays(kp), kp["descriptors"]
+
+
+class HipView:
+    """Standalone View (view_processor.py:14-106): the same constructor fields, ``update_cam_pose``,
+    ``update_intrinsic_mat`` and ``write_keys``."""
+
+    def __init__(self, img, idx, k, key_pts, key_descriptors):
+        self.img = img
+        self.idx = idx
+        self.ref_idx = idx
+        self.key_pts = key_pts
+        self.key_descriptors = key_descriptors
+        self.rot = np.identity(3, dtype=float)
+        self.loc = np.zeros((3, 1), dtype=float)
+        self.k = k
+        self.cam_pose = np.hstack((self.rot, self.loc))
+        self.cam_proj = self.k @ np.hstack((self.rot.T, self.rot.T @ -self.loc))
+        self.is_valid = False
+
+    def update_cam_pose(self, rot, loc):
+        self.rot = rot
+        self.loc = loc
+        self.cam_pose = np.hstack((self.rot, self.loc))
+        self.cam_proj = self.k @ np.hstack((self.rot.T, self.rot.T @ -self.loc))
+
+    def update_intrinsic_mat(self, k):
+        self.k = k
+        self.cam_proj = self.k @ np.hstack((self.rot.T, self.rot.T @ -self.loc))
+
+    def write_keys(self, key_file_path):
+        if key_file_path[-4:] != '.pkl':
+            logging.error('%s : incorrect key file path : %s', self.__class__.__name__, key_file_path)
+            return
+        temp_array = []
+        for idx, point in enumerate(self.key_pts):
+            temp_array.append((point.pt, point.size, point.angle, point.response, point.octave, point.class_id,
+                               self.key_descriptors[idx]))
+        with open(key_file_path, 'wb') as keys_file:
+            pickle.dump(temp_array, keys_file)
+
+
+class HipViewProcessor(HipViewProcessorMixin):
+    """Standalone ViewProcessor (view_processor.py:110-202) without cv2: ``generate_view``, ``add_view`` and keys read
+    back from ``.pkl``.  ``key_type='orb'`` raises ``ValueError``: the reference's ``cv.ORB_create(nkeys=1500)`` names
+    no ORB_create argument (INTEGRATION.md 'SIFT detection'); any other key type also raises, where the reference
+    logs and calls ``sys.exit(0)``."""
+
+    def __init__(self, key_type='sift'):
+        if key_type != 'sift':
+            raise ValueError("HipViewProcessor: only key_type 'sift' is supported, got %r" % (key_type,))
+        self.key_type = key_type
+        self.view_list = []
+
+    def add_view(self, view):
+        self.view_list.append(view)
+
+    def generate_view(self, img, index, k, key_path=None):
+        if not key_path:
+            key_pts, key_descriptors = self._ViewProcessor__extract_keys(img)
+        else:
+            key_pts, key_descriptors = self._ViewProcessor__read_keys(key_path, img)
+        return HipView(img, index, k, key_pts, key_descriptors)
+
+    def _ViewProcessor__read_keys(self, key_path, img):
+        try:
+            if key_path[-4:] != '.pkl':
+                logging.error('%s : incorrect key file path : %s', self.__class__.__name__, key_path)
+                return None
+            with open(key_path, 'rb') as f:
+                keys = pickle.load(f)
+            key_pts = [HipKeyPoint(p[0][0], p[0][1], p[1], p[2], p[3], p[4], p[5]) for p in keys]
+            key_descriptors = np.array([p[6] for p in keys])
+            return key_pts, key_descriptors
+        except FileNotFoundError:
+            logging.error('%s : pkl file %s not found ', key_path, self.__class__.__name__)
+            return self._ViewProcessor__extract_keys(img)
