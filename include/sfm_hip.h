@@ -412,8 +412,8 @@ int sfm_ba_reduced_system(int V, int N, int64_t M, const int* pt_ptr, const int*
  * L2 distance = float32(sqrt(s)), correctly rounded; for integer-valued rows in [0, 255] (every uint8 set; float sets
  * checked at creation) s = sum (a - b)^2 is exact (bf16 MFMA, int32), otherwise s is an fp32 sum of unspecified
  * order.  Hamming distance = popcount(a ^ b) over the row's bytes, as a float.  Limits: L2 dim <= 256, Hamming rows
- * <= 256 bytes.  The ratio test, crossCheck filtering, duplicate removal and table writes stay on the host
- * (key_tracker.py:267-314, structure-from-motion_amd/matching.py). */
+ * <= 256 bytes.  The ratio test, crossCheck filtering, duplicate removal and table writes (key_tracker.py:267-314) run
+ * on the host (structure-from-motion_amd/matching.py) or, from the device outputs, in the track store below. */
 #define SFM_MATCH_L2       0   /* cv2.NORM_L2 */
 #define SFM_MATCH_HAMMING  1   /* cv2.NORM_HAMMING */
 #define SFM_MATCH_KNN2     0   /* knnMatch(k=2): best and second best (key_tracker.py:259-260) */
@@ -479,6 +479,84 @@ int sfm_sift_result_destroy(sfm_sift_result* r);
 /* The float32 blur weights the library uses for a Gaussian of this sigma (ksize = rint(8 sigma + 1) | 1 taps; at
  * most `capacity` are written; weights may be NULL to ask for ksize). */
 int sfm_sift_blur_kernel(double sigma, int capacity, float* weights, int* ksize);
+
+/* ---- device-resident key tracks: KeyTrack / KeyTracker (key_tracker.py:14-59, 132-181, 213-317) --------------------
+ * One store per KeyTracker.  Per view it holds, on the device: the key count n, the key coordinates as doubles
+ * (KeyPoint.pt: float32 values widened exactly) and the view's KeyTrack.table as int32 rows of n entries, -1 = invalid
+ * match / not used.  Rows are allocated with spare capacity, so adding a view appends a row to every table without
+ * copying it.  A table has its own row count: sfm_track_add_view gives every existing table one more row and the new
+ * table (number of views) rows, as key_tracker.py:236-240 does; sfm_track_drop_last_view takes the last view away again
+ * and leaves the other tables' rows as they are (the state the reference is in when __extend_list raises).
+ * Host forms block and copy; _dev forms take DEVICE pointers and a stream (NULL = the library stream) and enqueue.
+ * The store remembers the stream of its last enqueue: a blocking form waits for that stream (not for the device), and
+ * an enqueue on a different stream first waits for the one before it. */
+#define SFM_TRACK_INFO_N_VIEWS        1
+#define SFM_TRACK_INFO_N_KEYS         2   /* of `view` */
+#define SFM_TRACK_INFO_N_ROWS         3   /* of `view`'s table */
+#define SFM_TRACK_INFO_UPLOAD_BYTES   4   /* host -> device bytes so far (coordinates, usage lists) */
+#define SFM_TRACK_INFO_DOWNLOAD_BYTES 5   /* device -> host bytes so far */
+#define SFM_TRACK_OK          0   /* per-reference status of an extend */
+#define SFM_TRACK_NO_SECOND   1   /* knn: a query without a second neighbour (the reference's IndexError, quirk Q16) */
+#define SFM_TRACK_ZERO_SECOND 2   /* knn: a second distance of 0 (the reference's ZeroDivisionError, quirk Q16) */
+#define SFM_TRACK_BAD_TRAIN   3   /* a kept train index outside the reference view's keys (never from sfm_match_dev) */
+typedef struct sfm_track_store sfm_track_store;
+int sfm_track_create(sfm_track_store** out);
+int sfm_track_destroy(sfm_track_store* s);
+/* `view` is ignored for the store-wide items. */
+int sfm_track_info(const sfm_track_store* s, int what, int view, int64_t* value);
+/* Add a view of n keys at (x[i], y[i]) (host arrays; n = 0 is legal): *view_out = its index. */
+int sfm_track_add_view(sfm_track_store* s, int n, const double* x, const double* y, int* view_out);
+int sfm_track_drop_last_view(sfm_track_store* s);
+/* key_tracker.py:247-291 for view `new_view` against the views 0 .. n_refs-1, from the [n_refs][n_query] arrays
+ * sfm_match_dev wrote (n_query = the new view's key count; arrays a mode does not read may be NULL):
+ *   filter : knn -- (double)d0 / (double)d1 < 0.7 in correctly rounded fp64; mutual -- the mutual flag; 1-NN -- all;
+ *            the survivors compacted in query order;
+ *   dedup  : quirk Q14 -- one entry per distinct train index t, ordered by the rank of t's first appearance; the entry
+ *            is the last later match i of t with dist[i] < dist_filtered[rank(t)], or t's first appearance.
+ * Nothing is raised on the device: a reference view whose knn result has a query without a second neighbour or with a
+ * zero second distance gets that status and its first offending query (the first query that hits either), and an empty
+ * kept list.  The kept lists stay in the store until the next call. */
+int sfm_track_match_dedup_dev(sfm_track_store* s, int new_view, int n_refs, int mode, const int* d_best_idx,
+                              const float* d_best_dist, const int* d_second_idx, const float* d_second_dist,
+                              const uint8_t* d_mutual, void* hip_stream);
+/* The same followed by the writes of key_tracker.py:305-314, table[ref][new_view, t] = q and table[new_view][ref, q] = t
+ * over each kept list, in one call with nothing downloaded in between; a reference view writes only if its status and
+ * that of every reference view before it is SFM_TRACK_OK (the reference would have raised before reaching it). */
+int sfm_track_extend_dev(sfm_track_store* s, int new_view, int n_refs, int mode, const int* d_best_idx,
+                         const float* d_best_dist, const int* d_second_idx, const float* d_second_dist,
+                         const uint8_t* d_mutual, void* hip_stream);
+/* sfm_match_dev of `query` (the new view's descriptors, one row per key) against refs[0 .. n_refs-1] (the descriptors of
+ * the views 0 .. n_refs-1) into buffers the store owns, then sfm_track_extend_dev (write != 0) or
+ * sfm_track_match_dedup_dev (write == 0) on them: no neighbour array visits the host. */
+int sfm_track_match_views(sfm_track_store* s, int new_view, sfm_desc_set* query, int n_refs, sfm_desc_set* const* refs,
+                          int mode, int write, void* hip_stream);
+/* Blocking: per reference view of the last match_dedup / extend the status, the first offending query (-1 if none)
+ * and the length of the kept list.  Any output may be NULL. */
+int sfm_track_extend_status(sfm_track_store* s, int n_refs, int* status, int* first_bad, int* n_kept);
+/* Blocking: the kept (query, train) list of reference view `ref`; q and t hold n_kept entries. */
+int sfm_track_kept_copy(sfm_track_store* s, int ref, int* q, int* t);
+/* The writes for reference view `ref` over the first n entries of its kept list (quirk Q15: the number of
+ * fundamental-matrix inliers; n < 0 or n > n_kept: the whole list).  Enqueues. */
+int sfm_track_write_kept(sfm_track_store* s, int ref, int n, void* hip_stream);
+/* KeyTracker.generate_matched_pairs (key_tracker.py:161-181): the entries > 0 of table[ref][que, :] in ascending key
+ * order (key 0 of the query view is never paired: quirk Q3).  Outputs, packed for the count n found:
+ * r_idx[n], q_idx[n], ref_pts (3, n) and que_pts (3, n) row-major doubles with row 2 = 1.0.  Every buffer must hold
+ * the reference view's key count (3 x for the points).  d_count[0] = n; d_count[1] != 0 if an entry named no key of
+ * the query view (its coordinates are then NaN; the host form returns SFM_E_SHAPE). */
+int sfm_track_pairs_dev(sfm_track_store* s, int ref, int que, int* d_count, int* d_r_idx, int* d_q_idx,
+                        double* d_ref_pts, double* d_que_pts, void* hip_stream);
+int sfm_track_pairs(sfm_track_store* s, int ref, int que, int* n, int* r_idx, int* q_idx, double* ref_pts,
+                    double* que_pts);
+/* KeyTrack.update_usage: table[view][view, keys[i]] = tri[i] (host arrays).  A key given twice takes the LAST value,
+ * as NumPy's fancy assignment does; a key outside [0, n) returns SFM_E_SHAPE and writes nothing. */
+int sfm_track_update_usage(sfm_track_store* s, int view, int n, const int* keys, const int* tri);
+/* KeyTrack.extract_constructed_points / extract_unconstructed_points: the keys of the view's own row that are != -1
+ * (with their values) / == -1, ascending.  Buffers hold the view's key count; tri may be NULL. */
+int sfm_track_constructed(sfm_track_store* s, int view, int* n, int* keys, int* tri);
+int sfm_track_unconstructed(sfm_track_store* s, int view, int* n, int* keys);
+/* Copy out one table ([rows][n keys]) or one of its rows. */
+int sfm_track_copy_table(sfm_track_store* s, int view, int* out);
+int sfm_track_copy_row(sfm_track_store* s, int view, int row, int* out);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,8 @@ DESC_U8, DESC_F32 = 0, 1
 DESC_INFO_N, DESC_INFO_DIM, DESC_INFO_EXACT, DESC_INFO_UPLOAD_BYTES = 1, 2, 3, 4
 SIFT_INFO_N, SIFT_INFO_N_OCTAVES, SIFT_INFO_N_PRE, SIFT_INFO_N_LAYERS, SIFT_INFO_KEEPS_PYRAMID = 1, 2, 3, 4, 5
 SIFT_LEVEL_GAUSS, SIFT_LEVEL_DOG = 0, 1
+TRACK_INFO_N_VIEWS, TRACK_INFO_N_KEYS, TRACK_INFO_N_ROWS, TRACK_INFO_UPLOAD_BYTES, TRACK_INFO_DOWNLOAD_BYTES = 1, 2, 3, 4, 5
+TRACK_OK, TRACK_NO_SECOND, TRACK_ZERO_SECOND, TRACK_BAD_TRAIN = 0, 1, 2, 3
 
 # every symbol include/sfm_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -51,6 +53,10 @@ EXPORTS = (
     "sfm_desc_create", "sfm_desc_destroy", "sfm_desc_info", "sfm_match", "sfm_match_dev",
     "sfm_sift_detect", "sfm_sift_result_info", "sfm_sift_result_level_shape", "sfm_sift_result_copy",
     "sfm_sift_result_copy_pre", "sfm_sift_result_copy_level", "sfm_sift_result_destroy", "sfm_sift_blur_kernel",
+    "sfm_track_create", "sfm_track_destroy", "sfm_track_info", "sfm_track_add_view", "sfm_track_drop_last_view",
+    "sfm_track_match_dedup_dev", "sfm_track_extend_dev", "sfm_track_match_views", "sfm_track_extend_status",
+    "sfm_track_kept_copy", "sfm_track_write_kept", "sfm_track_pairs_dev", "sfm_track_pairs", "sfm_track_update_usage",
+    "sfm_track_constructed", "sfm_track_unconstructed", "sfm_track_copy_table", "sfm_track_copy_row",
 )
 
 _lib = None
@@ -157,6 +163,25 @@ def load():
     lib.sfm_sift_result_copy_level.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp]
     lib.sfm_sift_result_destroy.argtypes = [vp]
     lib.sfm_sift_blur_kernel.argtypes = [ctypes.c_double, ctypes.c_int, fp, _ip]
+    ci = ctypes.c_int
+    lib.sfm_track_create.argtypes = [ctypes.POINTER(vp)]
+    lib.sfm_track_destroy.argtypes = [vp]
+    lib.sfm_track_info.argtypes = [vp, ci, ci, ctypes.POINTER(ctypes.c_int64)]
+    lib.sfm_track_add_view.argtypes = [vp, ci, _dp, _dp, _ip]
+    lib.sfm_track_drop_last_view.argtypes = [vp]
+    lib.sfm_track_match_dedup_dev.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    lib.sfm_track_extend_dev.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    lib.sfm_track_match_views.argtypes = [vp, ci, vp, ci, ctypes.POINTER(vp), ci, ci, vp]
+    lib.sfm_track_extend_status.argtypes = [vp, ci, _ip, _ip, _ip]
+    lib.sfm_track_kept_copy.argtypes = [vp, ci, _ip, _ip]
+    lib.sfm_track_write_kept.argtypes = [vp, ci, ci, vp]
+    lib.sfm_track_pairs_dev.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp]
+    lib.sfm_track_pairs.argtypes = [vp, ci, ci, _ip, _ip, _ip, _dp, _dp]
+    lib.sfm_track_update_usage.argtypes = [vp, ci, ci, _ip, _ip]
+    lib.sfm_track_constructed.argtypes = [vp, ci, _ip, _ip, _ip]
+    lib.sfm_track_unconstructed.argtypes = [vp, ci, _ip, _ip]
+    lib.sfm_track_copy_table.argtypes = [vp, ci, _ip]
+    lib.sfm_track_copy_row.argtypes = [vp, ci, ci, _ip]
     _lib = lib
     return lib
 
@@ -937,3 +962,141 @@ def sift_blur_kernel(sigma):
     w = np.zeros(k.value, dtype=np.float32)
     check(lib.sfm_sift_blur_kernel(float(sigma), k.value, w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(k)))
     return w
+
+
+# ---- device-resident key tracks (KeyTrack / KeyTracker, key_tracker.py:14-59, 132-181, 213-317) -------------------
+class TrackStore:
+    """The key coordinates and ``KeyTrack.table`` of every view of one KeyTracker on the device (sfm_track_create ...
+    sfm_track_destroy).  Tables come back as int32 arrays, -1 = invalid match / not used.  ``upload_bytes`` and
+    ``download_bytes`` count the traffic of the store itself (descriptors are counted by their ``DescriptorSet``)."""
+
+    def __init__(self):
+        self._lib = load()
+        self._h = None
+        h = ctypes.c_void_p()
+        check(self._lib.sfm_track_create(ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sfm_track_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self, what, view=0):
+        v = ctypes.c_int64()
+        check(self._lib.sfm_track_info(self._h, int(what), int(view), ctypes.byref(v)))
+        return int(v.value)
+
+    @property
+    def n_views(self):
+        return self.info(TRACK_INFO_N_VIEWS)
+
+    def n_keys(self, view):
+        return self.info(TRACK_INFO_N_KEYS, view)
+
+    def n_rows(self, view):
+        return self.info(TRACK_INFO_N_ROWS, view)
+
+    @property
+    def upload_bytes(self):
+        return self.info(TRACK_INFO_UPLOAD_BYTES)
+
+    @property
+    def download_bytes(self):
+        return self.info(TRACK_INFO_DOWNLOAD_BYTES)
+
+    def add_view(self, xy):
+        """Add a view whose keys sit at the rows of ``xy`` ((n, 2)); returns its index."""
+        xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+        x, y = np.ascontiguousarray(xy[:, 0]), np.ascontiguousarray(xy[:, 1])
+        out = ctypes.c_int()
+        check(self._lib.sfm_track_add_view(self._h, xy.shape[0], dptr(x), dptr(y), ctypes.byref(out)))
+        return out.value
+
+    def drop_last_view(self):
+        check(self._lib.sfm_track_drop_last_view(self._h))
+
+    def match_dedup_dev(self, new_view, n_refs, mode, d_best_idx, d_best_dist, d_second_idx, d_second_dist, d_mutual, stream=0):
+        """Filter + duplicate removal from DEVICE neighbour arrays ((n_refs, n_query), pointers as integers)."""
+        check(self._lib.sfm_track_match_dedup_dev(self._h, int(new_view), int(n_refs), int(mode), _vp(d_best_idx), _vp(d_best_dist),
+                                                  _vp(d_second_idx), _vp(d_second_dist), _vp(d_mutual), _vp(stream)))
+
+    def extend_dev(self, new_view, n_refs, mode, d_best_idx, d_best_dist, d_second_idx, d_second_dist, d_mutual, stream=0):
+        """Filter + duplicate removal + table writes in one call."""
+        check(self._lib.sfm_track_extend_dev(self._h, int(new_view), int(n_refs), int(mode), _vp(d_best_idx), _vp(d_best_dist),
+                                             _vp(d_second_idx), _vp(d_second_dist), _vp(d_mutual), _vp(stream)))
+
+    def match_views(self, new_view, query, refs, mode, write=True, stream=0):
+        """``sfm_match_dev`` of ``query`` against ``refs`` (DescriptorSets of the views 0 .. len(refs)-1) into the store's
+        own buffers, then the extend (``write``) or only filter + duplicate removal."""
+        refs = list(refs)
+        handles = (ctypes.c_void_p * max(len(refs), 1))(*[r._h for r in refs])
+        check(self._lib.sfm_track_match_views(self._h, int(new_view), query._h, len(refs), handles, int(mode), int(bool(write)),
+                                              _vp(stream)))
+
+    def extend_status(self, n_refs):
+        """(status, first offending query, kept length) per reference view of the last extend, as int32 arrays."""
+        st, bad, kept = (np.zeros(max(n_refs, 1), dtype=np.int32) for _ in range(3))
+        check(self._lib.sfm_track_extend_status(self._h, int(n_refs), iptr(st), iptr(bad), iptr(kept)))
+        return st[:n_refs], bad[:n_refs], kept[:n_refs]
+
+    def kept(self, ref, n_kept):
+        """The kept (query, train) lists of reference view ``ref`` (``n_kept`` from ``extend_status``)."""
+        q, t = np.zeros(max(n_kept, 1), dtype=np.int32), np.zeros(max(n_kept, 1), dtype=np.int32)
+        check(self._lib.sfm_track_kept_copy(self._h, int(ref), iptr(q), iptr(t)))
+        return q[:n_kept], t[:n_kept]
+
+    def write_kept(self, ref, n=-1, stream=0):
+        check(self._lib.sfm_track_write_kept(self._h, int(ref), int(n), _vp(stream)))
+
+    def pairs(self, ref, que):
+        """generate_matched_pairs: (r_idx (n,), q_idx (n,), ref_pts (3, n), que_pts (3, n))."""
+        cap = max(self.n_keys(ref), 1)
+        n = ctypes.c_int()
+        r, q = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+        rp, qp = np.zeros(3 * cap), np.zeros(3 * cap)
+        check(self._lib.sfm_track_pairs(self._h, int(ref), int(que), ctypes.byref(n), iptr(r), iptr(q), dptr(rp), dptr(qp)))
+        n = n.value
+        return r[:n], q[:n], rp[:3 * n].reshape(3, n), qp[:3 * n].reshape(3, n)
+
+    def pairs_dev(self, ref, que, d_count, d_r_idx, d_q_idx, d_ref_pts, d_que_pts, stream=0):
+        check(self._lib.sfm_track_pairs_dev(self._h, int(ref), int(que), _vp(d_count), _vp(d_r_idx), _vp(d_q_idx), _vp(d_ref_pts),
+                                            _vp(d_que_pts), _vp(stream)))
+
+    def update_usage(self, view, keys, tri):
+        keys, tri = i32(keys).reshape(-1), i32(tri).reshape(-1)
+        if keys.shape != tri.shape:
+            raise ValueError("update_usage: %d keys, %d point indices" % (keys.shape[0], tri.shape[0]))
+        check(self._lib.sfm_track_update_usage(self._h, int(view), keys.shape[0], iptr(keys), iptr(tri)))
+
+    def constructed(self, view):
+        cap = max(self.n_keys(view), 1)
+        n = ctypes.c_int()
+        k, t = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+        check(self._lib.sfm_track_constructed(self._h, int(view), ctypes.byref(n), iptr(k), iptr(t)))
+        return k[:n.value], t[:n.value]
+
+    def unconstructed(self, view):
+        cap = max(self.n_keys(view), 1)
+        n = ctypes.c_int()
+        k = np.zeros(cap, dtype=np.int32)
+        check(self._lib.sfm_track_unconstructed(self._h, int(view), ctypes.byref(n), iptr(k)))
+        return k[:n.value]
+
+    def table(self, view):
+        out = np.zeros((self.n_rows(view), self.n_keys(view)), dtype=np.int32)
+        check(self._lib.sfm_track_copy_table(self._h, int(view), iptr(out) if out.size else None))
+        return out
+
+    def row(self, view, row):
+        out = np.zeros(self.n_keys(view), dtype=np.int32)
+        check(self._lib.sfm_track_copy_row(self._h, int(view), int(row), iptr(out) if out.size else None))
+        return out

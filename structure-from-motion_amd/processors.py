@@ -376,7 +376,9 @@ class HipBaMixin:
     replaced, the problem is rebuilt from scratch.  The pixel coordinates of a key are read ONCE, when its view's key list is
     first seen (``observations.KeyCache``): ``view.key_pts`` is treated as immutable -- the reference's front end never edits a
     ``cv2.KeyPoint`` after detection (view_processor.py) -- and a caller that does edit ``key_pts[i].pt`` in place has to call
-    ``ba_release()`` (or hand the view a new list) for the edit to reach the device.
+    ``ba_release()`` (or hand the view a new list) for the edit to reach the device.  The track tables of a
+    ``HipDeviceKeyTracker`` follow the same rule the other way round: ``track_list[i].table`` is a host picture of the device
+    table, and a write into it is not propagated to the device (``HipDeviceKeyTrack``).
     ``ba_upload_bytes`` reports the PCIe bytes spent so far; ``ba_release()`` frees the device copy."""
 
     ba_quirk_flags = native.QUIRKS_REFERENCE
@@ -521,9 +523,11 @@ class HipBaMixin:
 
 
 class HipBaProcessor(HipBaMixin):
-    """Standalone holder of the BaProcessor constructor state (ba_processor.py:22-40).  The
-    incremental state machine ``process`` (ba:43-270) needs the OpenCV front end and stays in the
-    reference; use ``class BaProcessor(HipBaMixin, ba_processor.BaProcessor)`` for the full pipeline."""
+    """Standalone BaProcessor (ba_processor.py:22-270): the constructor state, the bundle adjustment of ``HipBaMixin`` and
+    the incremental state machine ``process(img, k)`` from pixels to poses, on the drop-ins of this module
+    (``HipViewProcessor``, ``HipKeyTracker`` or ``HipDeviceKeyTracker``, ``HipEpipolarProcessor``,
+    ``HipTriangulationProcessor``, ``HipCamposeProcessor``); no OpenCV is involved.  With the reference's own classes use
+    ``class BaProcessor(HipBaMixin, ba_processor.BaProcessor)`` instead, which keeps the reference's ``process``."""
 
     def __init__(self, view_processor, key_tracker, epi_processor, tri_processor, campose_processor,
                  filter_size=10, iteration=3, damping_factor=5):
@@ -536,6 +540,94 @@ class HipBaProcessor(HipBaMixin):
         self.epi_processor = epi_processor
         self.tri_processor = tri_processor
         self.campose_processor = campose_processor
+
+    def process(self, img, k):
+        """One frame of ba_processor.py:43-270: detect, match into the key tracks, then by the number of views so far
+        -- the first view only becomes valid; the second gets its pose from the essential matrix and seeds the point
+        cloud; every later one is registered by PnP against view 0's points, adds the points it shares with view 0 and
+        ends in a bundle adjustment over everything.  Prints, ``curr_data_idx``, ``ref_idx`` / ``is_valid`` and the two
+        ``sys.exit`` conditions are the reference's; its BA_DEBUG block (cv2.solvePnPRansac) is not ported."""
+        if self.curr_data_idx >= self.filter_size:
+            print('Bundle Adjustment processor is full')
+            return
+        idx = self.curr_data_idx
+        view = self.view_processor.generate_view(img, idx, k)                             # ba:49
+        self.key_tracker.add_new_view(view, self.view_processor.view_list)                # ba:52
+        self.view_processor.add_view(view)                                                # ba:55
+        views = self.view_processor.view_list
+        if idx == 0:
+            print('In one image state')
+            views[0].is_valid = True
+        elif idx == 1:
+            print('In epipolar state')
+            self._process_two_view(views, k)
+        else:
+            print('In cam pose state')
+            self._process_register(views, idx)
+        self.curr_data_idx += 1                                                           # ba:270
+
+    def _process_two_view(self, views, k):
+        """ba:66-132: views 0 and 1 from their matches alone."""
+        kt, tp, cp, ep = self.key_tracker, self.tri_processor, self.campose_processor, self.epi_processor
+        pairs, r_idx, q_idx = kt.generate_matched_pairs(0, 1, views)
+        ep.determine_fundamental_mat(pairs)
+        ep.extract_essential_mat(views[0].k, views[1].k)
+        r1, r2, c1, c2 = cp.extract_cam_pose_from_essential_mat(ep.esse_mat)
+        rots, locs = [r1, r1, r2, r2], [c1, c2, c1, c2]                                   # ba:83-89: the four (R, C) combinations
+        projs = [k @ np.hstack((r.T, -r.T @ c)) for r, c in zip(rots, locs)]
+        ref_proj = views[0].cam_proj
+        candidates = [tp.linear_triangulate([ref_proj, p], pairs) for p in projs]         # ba:93-96
+        best, valid = cp.disambiguate_cam_pose_four(ref_proj, projs, candidates)
+        views[1].update_cam_pose(rots[best], locs[best])
+        valid = np.array(valid)[np.newaxis, :]                                            # ba:109-110
+        in_front = [np.take_along_axis(pairs[0], valid, axis=1), np.take_along_axis(pairs[1], valid, axis=1)]
+        pts = tp.nonlinear_triangulate(np.take_along_axis(candidates[best], valid, axis=1), [ref_proj, projs[best]], in_front)
+        tri_idx = np.arange(0, pts.shape[1], dtype=int)[np.newaxis, :]
+        kt.track_list[0].update_usage(np.take(r_idx, valid), tri_idx)                     # ba:120-125
+        kt.track_list[1].update_usage(np.take(q_idx, valid), tri_idx)
+        views[1].is_valid = True
+        views[1].ref_idx = 0
+        tp.add_tri_pt(pts)
+
+    def _process_register(self, views, idx):
+        """ba:140-267: pose of view ``idx`` by PnP on the points its reference view already has, new points from the
+        matches that have none yet, bundle adjustment."""
+        import sys
+        kt, tp, cp = self.key_tracker, self.tri_processor, self.campose_processor
+        cur = views[idx]
+        ref = kt.find_best_view(idx)
+        ref_view = views[ref]
+        cur.ref_idx = ref
+        pairs, ref_key, _cur_key = kt.generate_matched_pairs(ref, idx, views)
+        ref_track = kt.track_list[ref]
+        built_key, built_pt = ref_track.extract_constructed_points()
+        if built_key.shape[1] != tp.tri_pts.shape[1]:                                     # ba:172-174
+            sys.exit('ERROR: even best_view_idx assumption does not work !!!')
+        used, in_pairs, in_built = np.intersect1d(ref_key, built_key, return_indices=True)
+        used = used[np.newaxis, :]
+        in_pairs, in_built = in_pairs[np.newaxis, :], in_built[np.newaxis, :]
+        known = np.take_along_axis(tp.tri_pts, np.take_along_axis(built_pt, in_built, axis=1), axis=1)
+        seen = np.take_along_axis(pairs[1], in_pairs, axis=1)
+        _inliers, rot, loc = cp.estimate_cam_pose_pnp(seen, known, cur.k)                # ba:191-192
+        cur.update_cam_pose(rot, loc)
+        cur.is_valid = True
+
+        free = ref_track.extract_unconstructed_points()
+        projs = [ref_view.cam_proj, cur.cam_proj]
+        fresh, in_pairs, _ = np.intersect1d(ref_key, free, return_indices=True)           # ba:229-230
+        fresh = fresh[np.newaxis, :]
+        both, _, _ = np.intersect1d(fresh, used, return_indices=True)
+        if np.any(both) != False:                                                         # noqa: E712  (sic, ba:235-237)
+            sys.exit('ERROR: the intersect of unused and used inters sets is NOT empty')
+        in_pairs = in_pairs[np.newaxis, :]
+        new_pts = tp.triangulate(projs, [np.take_along_axis(pairs[0], in_pairs, axis=1),
+                                         np.take_along_axis(pairs[1], in_pairs, axis=1)])
+        first = tp.tri_pts.shape[1]
+        tri_idx = np.arange(first, first + new_pts.shape[1], dtype=int)[np.newaxis, :]
+        ref_track.update_usage(fresh, tri_idx)                                            # ba:252-253
+        kt.track_list[idx].update_usage(np.take(ref_track.table[idx, :], fresh), tri_idx)    # ba:256-258
+        tp.add_tri_pt(new_pts)
+        self._BaProcessor__execute_bundle_adjustment()                                    # ba:267
 
 
 # ------------------------------------------------------------------------------------------------
@@ -575,7 +667,7 @@ class HipKeyTrackerMixin:
             have[1].close()
         ds = native.DescriptorSet(self._kt_metric(), descriptors)
         sets[idx] = (descriptors, ds)
-        self.__dict__["_hip_desc_bytes"] = self.kt_upload_bytes + ds.upload_bytes
+        self.__dict__["_hip_desc_bytes"] = self.__dict__.get("_hip_desc_bytes", 0) + ds.upload_bytes
         return ds
 
     def _extend_list(self, new_view, views, is_knn_match=False, is_fund_inlier=False, ransac_config=None):
@@ -710,6 +802,202 @@ class HipKeyTracker(HipKeyTrackerMixin):
         self.track_list = []
 
 
+class HipDeviceKeyTrack:
+    """``KeyTrack`` of a ``HipDeviceKeyTracker``: the table lives in the tracker's ``native.TrackStore``.
+
+    ``table`` is an int64 host copy, downloaded again only when the device copy has changed since the last read.  It is a
+    picture, not the table: writing into it does NOT reach the device (use ``update_usage``), just as editing
+    ``view.key_pts[i].pt`` after the view was added does not (the coordinates were copied when the view came in).
+    ``update_usage`` and the two ``extract_*`` methods run on the device copy and return what ``HipKeyTrack`` returns."""
+
+    def __init__(self, tracker, idx, key_num):
+        self._tracker = tracker
+        self.idx = idx
+        self.key_num = key_num
+        self._host = None
+        self._host_version = -1
+
+    @property
+    def table(self):
+        version = self._tracker._versions[self.idx]
+        if self._host is None or self._host_version != version:
+            self._host = self._tracker._store.table(self.idx).astype('int')
+            self._host_version = version
+        return self._host
+
+    @table.setter
+    def table(self, value):               # a host-side replacement (a slice for a smaller problem): the device keeps its own
+        self._host = value
+        self._host_version = self._tracker._versions[self.idx]
+
+    def update_usage(self, used_indices, tri_indices):
+        used = np.asarray(used_indices)
+        keys = used.reshape(-1).astype(np.int64)
+        tri = np.asarray(tri_indices)[0, np.indices(used.shape)[1].reshape(-1)]
+        keys = np.where(keys < 0, keys + self.key_num, keys)                 # NumPy's negative indices
+        if keys.shape[0] and (keys.min() < 0 or keys.max() >= self.key_num):
+            raise IndexError("index out of bounds for axis 1 with size {}".format(self.key_num))
+        self._tracker._store.update_usage(self.idx, keys, tri)
+        self._tracker._versions[self.idx] += 1
+
+    def extract_unconstructed_points(self):
+        return self._tracker._store.unconstructed(self.idx).astype(np.int64)[np.newaxis, :]
+
+    def extract_constructed_points(self):
+        keys, tri = self._tracker._store.constructed(self.idx)
+        return keys.astype(np.int64)[np.newaxis, :], tri.astype('int')[np.newaxis, :]
+
+
+class HipDeviceKeyTracker(HipKeyTrackerMixin):
+    """``HipKeyTracker`` with the key tracks resident on the device (``native.TrackStore``, csrc/sfm_track.hip): the same
+    constructor and methods, the same tables.  ``add_new_view`` uploads the new view's descriptors and key coordinates,
+    matches it against every earlier view and runs the ratio / crossCheck filter, the duplicate removal (quirk Q14)
+    and the table writes on the device, with no neighbour array on the host; only the per-view status comes back
+    (quirk Q16: the exception the reference raises, at the same query, tables left as the reference leaves them).  With
+    ``is_fund_inlier`` the kept lists come back, ``HipEpipolarProcessor`` runs per reference view in the reference's
+    order (Python's global RNG stream is consumed identically) and the prefixes are written (quirk Q15).
+
+    Key coordinates come from ``view.key_xy`` ((n, 2), attached by ``HipViewProcessor.generate_view``) or, without it,
+    from one pass over ``view.key_pts``; ``generate_matched_pairs`` reads the device copy, so its ``views`` argument is not
+    looked at.  ``track_list[i]`` is a ``HipDeviceKeyTrack``.  ``kt_upload_bytes`` counts descriptors, coordinates and
+    usage lists; ``kt_download_bytes`` what came back; ``kt_release()`` frees the device copies."""
+
+    def __init__(self, key_type, is_cross_check, is_knn_match, is_fund_inlier, ransac_config):
+        self.key_type = key_type
+        self.is_cross_check = is_cross_check
+        self.is_knn_match = is_knn_match
+        self.is_fund_inlier = is_fund_inlier
+        self.ransac_config = ransac_config
+        self.track_list = []
+        self._store = None
+        self._versions = []               # per view: bumped whenever the device table changes
+        self._xy = []                     # per view: the (n, 2) coordinates that went up (fundamental-inlier pairs)
+        self._retired_bytes = [0, 0]
+
+    def kt_release(self):
+        HipKeyTrackerMixin.kt_release(self)
+        if self._store is not None:
+            self._retired_bytes[0] += self._store.upload_bytes
+            self._retired_bytes[1] += self._store.download_bytes
+            self._store.close()
+            self._store = None
+
+    @property
+    def kt_upload_bytes(self):
+        return (self.__dict__.get("_hip_desc_bytes", 0) + self._retired_bytes[0]
+                + (self._store.upload_bytes if self._store is not None else 0))
+
+    @property
+    def kt_download_bytes(self):
+        return self._retired_bytes[1] + (self._store.download_bytes if self._store is not None else 0)
+
+    @staticmethod
+    def _key_xy(view):
+        xy = getattr(view, "key_xy", None)
+        if xy is None or len(xy) != len(view.key_pts):
+            xy = np.array([kp.pt for kp in view.key_pts], dtype=np.float64)
+        return np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+
+    def add_new_view(self, new_view, views, is_knn_match=None, is_fund_inlier=None, ransac_config=None):
+        # falsy -> instance default (key_tracker.py:114-119, quirk Q17)
+        if not is_knn_match:
+            is_knn_match = self.is_knn_match
+        if not is_fund_inlier:
+            is_fund_inlier = self.is_fund_inlier
+        if not ransac_config:
+            ransac_config = self.ransac_config
+        if len(self.track_list) == 0:
+            if self._store is not None:
+                self.kt_release()
+            self._store = native.TrackStore()
+            self._versions, self._xy = [0], [self._key_xy(new_view)]
+            self._store.add_view(self._xy[0])
+            self.track_list.append(HipDeviceKeyTrack(self, 0, len(new_view.key_pts)))
+        else:
+            self._KeyTracker__extend_list(new_view, views, is_knn_match, is_fund_inlier, ransac_config)
+
+    def _extend_list(self, new_view, views, is_knn_match=False, is_fund_inlier=False, ransac_config=None):
+        key_num = len(new_view.key_pts)
+        new_idx = len(self.track_list)
+        store = self._store
+        if store is None or store.n_views != new_idx:
+            raise native.SfmHipError("HipDeviceKeyTracker: the device store holds %s views, track_list %d"
+                                     % ("no" if store is None else store.n_views, new_idx))
+        if len(views) > new_idx:
+            raise ValueError("{} reference views for view {}".format(len(views), new_idx))
+        refs = []
+        for ref_idx, ref_view in enumerate(views):
+            d = ref_view.key_descriptors
+            if d is None or len(d) == 0:      # undefined without cv2 (INTEGRATION.md, deviation of Q16)
+                raise ValueError("reference view {} has no descriptors".format(ref_idx))
+            refs.append(self._kt_set(ref_idx, d))
+        query = self._kt_set(new_idx, new_view.key_descriptors)
+        if refs and query.n != key_num:
+            raise ValueError("{} descriptors for {} keys".format(query.n, key_num))
+        mode = matching.match_mode(is_knn_match, self.is_cross_check)
+        xy = self._key_xy(new_view)
+
+        store.add_view(xy)                                                      # key_tracker.py:236-240
+        self._versions = [v + 1 for v in self._versions] + [0]
+        self._xy.append(xy)
+        try:
+            store.match_views(new_idx, query, refs, mode, write=not is_fund_inlier)
+            status, bad, n_kept = store.extend_status(len(refs))
+            for ref_idx in range(len(refs)):                                    # key_tracker.py:247
+                if status[ref_idx] == native.TRACK_NO_SECOND:
+                    raise IndexError("tuple index out of range")                # item[1] of a one-element knnMatch result
+                if status[ref_idx] == native.TRACK_ZERO_SECOND:
+                    raise ZeroDivisionError("float division by zero")           # item[0].distance / item[1].distance
+                if status[ref_idx] != native.TRACK_OK:
+                    raise ValueError("reference view {}: query {} has a neighbour outside the view".format(ref_idx, bad[ref_idx]))
+                if is_fund_inlier:                                              # key_tracker.py:294-314
+                    qk, tk = store.kept(ref_idx, int(n_kept[ref_idx]))
+                    ref_pts = np.ones((3, tk.shape[0])); que_pts = np.ones((3, qk.shape[0]))
+                    ref_pts[0:2] = self._xy[ref_idx][tk].T
+                    que_pts[0:2] = xy[qk].T
+                    ep = HipEpipolarProcessor(ransac_config)
+                    n_in = len(ep.determine_fundamental_mat([ref_pts, que_pts], ransac_config))
+                    store.write_kept(ref_idx, n_in)
+        except BaseException:
+            # the reference has expanded every table and written the pairs before the failing one, and has not
+            # appended the new track: the same here
+            store.drop_last_view()
+            self._versions.pop()
+            self._xy.pop()
+            raise
+        self.track_list.append(HipDeviceKeyTrack(self, new_idx, key_num))
+
+    def generate_matched_pairs(self, ref_idx, que_idx, views):
+        """key_tracker.py:132-181 from the device copy (entries ``> 0`` only: quirk Q3).  Nothing goes up; the count and
+        the four result arrays come down."""
+        if ref_idx < 0 or que_idx < 0 or ref_idx >= len(self.track_list) or que_idx >= len(self.track_list):
+            print('{}:{} - invalid ref_idx {} or invalid que_idx {}'.format(
+                self.__class__.__name__, 'generate_matched_pairs', ref_idx, que_idx))
+            return None
+        r_idx, q_idx, ref_pts, que_pts = self._store.pairs(ref_idx, que_idx)
+        num = r_idx.shape[0]
+        return [ref_pts, que_pts], r_idx.reshape(1, num).astype(int), q_idx.reshape(1, num).astype(int)
+
+    def find_best_view(self, input_idx):
+        if input_idx < 0 or input_idx >= len(self.track_list):
+            print('{}:{} - invalid input_idx {}'.format(self.__class__.__name__, 'find_best_view', input_idx))
+            return -1
+        return 0
+
+    def is_visible(self, view_idx, tri_pt_idx):
+        key_idx = np.where(self._store.row(view_idx, view_idx) == tri_pt_idx)
+        if np.any(key_idx):
+            key_idx = key_idx[0][0]
+        else:
+            key_idx = -1
+        return key_idx
+
+    def clear(self):
+        self.kt_release()
+        self.track_list = []
+        self._versions, self._xy = [], []
+
+
 # ------------------------------------------------------------------------------------------------
 class HipKeyPoint:
     """The ``cv2.KeyPoint`` fields the reference reads and writes (view_processor.py:100-101, 178-180)."""
@@ -739,15 +1027,19 @@ class HipViewProcessorMixin:
     """``ViewProcessor.__extract_keys`` (view_processor.py:199-202) with SIFT detection on the device: returns
     (list of HipKeyPoint, float32 (n, 128) descriptors), what ``detectAndCompute(img, None)`` returns for
     ``SIFT_create()`` by the contract of INTEGRATION.md 'SIFT detection'.  An image without keypoints gives
-    ``([], None)``, as cv2 does."""
+    ``([], None)``, as cv2 does.  ``_hip_extract_keys`` returns the same two and the coordinates as an (n, 2) float64
+    array: the float32 values widened exactly, what ``key_pts[i].pt`` holds."""
 
-    def _ViewProcessor__extract_keys(self, img):
+    def _hip_extract_keys(self, img):
         if getattr(self, "key_type", "sift") != "sift":
             raise ValueError("HipViewProcessorMixin: only key_type 'sift' runs on the device, got %r" % (self.key_type,))
         kp = native.sift_detect(img)
         if len(kp["x"]) == 0:
-            return [], None
-        return keypoints_from_arrays(kp), kp["descriptors"]
+            return [], None, np.zeros((0, 2))
+        return keypoints_from_arrays(kp), kp["descriptors"], np.stack((kp["x"], kp["y"]), axis=1).astype(np.float64)
+
+    def _ViewProcessor__extract_keys(self, img):
+        return self._hip_extract_keys(img)[:2]
 
 
 class HipView:
@@ -806,10 +1098,13 @@ class HipViewProcessor(HipViewProcessorMixin):
 
     def generate_view(self, img, index, k, key_path=None):
         if not key_path:
-            key_pts, key_descriptors = self._ViewProcessor__extract_keys(img)
+            key_pts, key_descriptors, key_xy = self._hip_extract_keys(img)
         else:
             key_pts, key_descriptors = self._ViewProcessor__read_keys(key_path, img)
-        return HipView(img, index, k, key_pts, key_descriptors)
+            key_xy = np.array([p.pt for p in key_pts], dtype=np.float64).reshape(-1, 2)
+        view = HipView(img, index, k, key_pts, key_descriptors)
+        view.key_xy = key_xy              # (n, 2) float64 of key_pts[i].pt, read by HipDeviceKeyTracker
+        return view
 
     def _ViewProcessor__read_keys(self, key_path, img):
         try:
