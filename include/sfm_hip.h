@@ -495,6 +495,9 @@ int sfm_sift_blur_kernel(double sigma, int capacity, float* weights, int* ksize)
 #define SFM_TRACK_INFO_N_ROWS         3   /* of `view`'s table */
 #define SFM_TRACK_INFO_UPLOAD_BYTES   4   /* host -> device bytes so far (coordinates, usage lists) */
 #define SFM_TRACK_INFO_DOWNLOAD_BYTES 5   /* device -> host bytes so far */
+#define SFM_TRACK_INFO_OBS_VIEWS      6   /* views of the last sfm_obs_build, -1 if there is no list */
+#define SFM_TRACK_INFO_OBS_PTS        7   /* its points */
+#define SFM_TRACK_INFO_N_OBS          8   /* its observations */
 #define SFM_TRACK_OK          0   /* per-reference status of an extend */
 #define SFM_TRACK_NO_SECOND   1   /* knn: a query without a second neighbour (the reference's IndexError, quirk Q16) */
 #define SFM_TRACK_ZERO_SECOND 2   /* knn: a second distance of 0 (the reference's ZeroDivisionError, quirk Q16) */
@@ -557,6 +560,47 @@ int sfm_track_unconstructed(sfm_track_store* s, int view, int* n, int* keys);
 /* Copy out one table ([rows][n keys]) or one of its rows. */
 int sfm_track_copy_table(sfm_track_store* s, int view, int* out);
 int sfm_track_copy_row(sfm_track_store* s, int view, int row, int* out);
+
+/* ---- bundle-adjustment observations from the resident tracks (ba_processor.py:304-310, 339-342) --------------------
+ * (sfm_obs_*: they work on a track store, but are not part of the KeyTrack / KeyTracker surface the sfm_track_* names cover.)
+ * The normalised coordinates inv(K) @ [x, y, 1] / w of ALL n keys of `view` (host arrays u, v; n must be the view's
+ * key count).  The product is the host's BLAS product, whose bits a kernel cannot reproduce: the host computes it once
+ * per view (again when the view's intrinsic matrix changes) and the device only gathers from it.  16 n bytes, counted in
+ * SFM_TRACK_INFO_UPLOAD_BYTES.  Blocking. */
+int sfm_obs_set_normalised(sfm_track_store* s, int view, int n, const double* u, const double* v);
+/* The observation list of the loop ba_processor.py:304-310 over the views 0 .. n_views-1 and the points 0 .. n_pts-1,
+ * from the views' own rows table[v][v, :], in buffers the store owns: pt_ptr[n_pts + 1], cam_idx[M], key_idx[M], u[M],
+ * v[M], sorted by (point, view).  KeyTracker.is_visible's semantics (key_tracker.py:198-204, quirk Q3): view v sees
+ * point p iff some key k > 0 has table[v][v, k] == p, and the observation is then the SMALLEST such key, 0 included;
+ * entries < 0 or >= n_pts are ignored.  Every view with keys needs its normalised table.  *n_obs = M (may be NULL).
+ * The min / max-key scratch holds 2 n_views n_pts ints; above 2^28 ints (1 GiB) the call returns SFM_E_SHAPE.
+ * Blocking (the count M comes back, 4 bytes that SFM_TRACK_INFO_DOWNLOAD_BYTES leaves out); the list stays valid until
+ * the next build. */
+int sfm_obs_build(sfm_track_store* s, int n_views, int n_pts, int64_t* n_obs);
+/* Blocking: the list of the last build (uv is (2, M) row-major: all u, then all v).  Any output may be NULL; the sizes
+ * come from sfm_track_info (SFM_TRACK_INFO_OBS_PTS, SFM_TRACK_INFO_N_OBS).  Counted as download bytes. */
+int sfm_obs_copy(sfm_track_store* s, int* pt_ptr, int* cam_idx, int* key_idx, double* uv);
+
+/* A resident BA problem (see sfm_ba_create) whose structure is the store's current observation list, copied device to
+ * device: nothing is uploaded, SFM_INFO_UPLOAD_BYTES starts at 0.  Cameras and points are set as after sfm_ba_create.
+ * The problem keeps no reference to the store. */
+#define SFM_SYNC_REUSE    0   /* the list is the resident structure: nothing changed, nothing uploaded */
+#define SFM_SYNC_GROWN    1   /* every resident track is part of the list's track of the same point: the problem adopted the list */
+#define SFM_SYNC_REPLACED 2   /* anything else: the problem is unchanged, the caller builds a new one */
+int sfm_ba_create_from_tracks(sfm_track_store* s, sfm_ba_problem** out);
+/* Compare the store's current list (V2 views, N2 points) with the resident structure (V, N) on the device and bring the
+ * problem up to it.  REUSE: V2 == V, N2 == N and every track, camera index and u, v bit pattern is the same.  GROWN:
+ * V2 >= V, N2 >= N, n_new_cams == V2 - V, n_new_pts == N2 - N and every resident track is a subsequence of the new
+ * track of its point with bitwise equal u, v; the problem then becomes one of the new sizes that holds the list, the old
+ * cameras and points (device to device) and the new ones (cams_new (n_new_cams, 7), pts_new (3, n_new_pts) row-major,
+ * the only upload: 56 n_new_cams + 24 n_new_pts bytes), and keeps handle, options, stream, communicator and counters
+ * as sfm_ba_append does.  REPLACED: an observation went away, its key or its u, v changed, there are fewer views or
+ * points, or the counts do not match.  *n_new_obs = the observations added (0 unless GROWN; may be NULL).  Blocking. */
+int sfm_ba_sync_tracks(sfm_ba_problem* p, sfm_track_store* s, int n_new_cams, const double* cams_new, int n_new_pts,
+                       const double* pts_new, int* action, int64_t* n_new_obs);
+/* Blocking: the resident observation list in the layout sfm_ba_create takes: pt_ptr[N + 1], cam_idx[M], uv_norm (2, M)
+ * (sizes from sfm_ba_info).  Any output may be NULL. */
+int sfm_ba_get_structure(sfm_ba_problem* p, int* pt_ptr, int* cam_idx, double* uv_norm);
 
 #ifdef __cplusplus
 }

@@ -137,6 +137,29 @@ __global__ void ba_append_merge_kernel(int N, int N2, const int* __restrict__ ol
   }
 }
 
+// sfm_ba_sync_tracks: is every resident track a subsequence of the track the store built for the same point, with the same
+// bits in u and v?  One thread per resident point walks both camera-sorted tracks; the first point that fails goes
+// into *first_bad by an unsigned atomicMin (the word starts as all ones).
+__global__ void ba_tracks_compare_kernel(int N, const int* __restrict__ old_ptr, const int* __restrict__ old_cam,
+                                         const double* __restrict__ old_u, const double* __restrict__ old_v,
+                                         const int* __restrict__ new_ptr, const int* __restrict__ new_cam,
+                                         const double* __restrict__ new_u, const double* __restrict__ new_v,
+                                         unsigned* __restrict__ first_bad) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= N) return;
+  int i = new_ptr[p];
+  const int ne = new_ptr[p + 1];
+  bool ok = true;
+  for (int o = old_ptr[p]; o < old_ptr[p + 1] && ok; ++o) {
+    const int c = old_cam[o];
+    while (i < ne && new_cam[i] < c) ++i;
+    ok = i < ne && new_cam[i] == c && __double_as_longlong(new_u[i]) == __double_as_longlong(old_u[o]) &&
+         __double_as_longlong(new_v[i]) == __double_as_longlong(old_v[o]);
+    ++i;
+  }
+  if (!ok) atomicMin(first_bad, (unsigned)p);
+}
+
 // The reference packs every camera anew at the start of each BA call: q = convert_rotation_to_quaternion(view.rot)
 // (ba_processor.py:285-288), and view.rot is R(q) of the previous call's result (ba:412) -- so the quaternion a call starts
 // from is q(R(q_prev)), not q_prev.  For cameras the caller did not touch, that round trip is done here, on the device, from
@@ -254,6 +277,42 @@ static int ba_upload(sfm_ba_problem* p, void* dst, const void* src, size_t bytes
   SFM_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, p->stream));
   p->upload_bytes += (long long)bytes;
   return SFM_OK;
+}
+
+// p takes over the structure and state of q, a problem of the grown scene built on p's stream, and q leaves with p's old
+// buffers (sfm_ba_append, sfm_ba_sync_tracks).
+static int ba_adopt_grown(sfm_ba_problem* p, sfm_ba_problem* q, int n_new_cams) {
+  // the handle keeps its identity, options, stream and counters; the old buffers leave with q
+  q->schur_mode = p->schur_mode; q->debug = p->debug; q->timing = p->timing; q->quirks = p->quirks;
+  q->dev.debug = p->debug;
+  q->deterministic = p->deterministic && q->schur_mfma_ok && sizeof(double) * (size_t)q->dev.V * 35 <= 64 * 1024;
+  const bool had_external_red = p->dev.red != p->own_red;
+  ba_graph_drop(p);
+  std::swap(p->dev, q->dev);
+  std::swap(p->own_red, q->own_red);
+  std::swap(p->schur_ws, q->schur_ws);
+  std::swap(p->flow_tasks_red, q->flow_tasks_red); std::swap(p->flow_ntasks_red, q->flow_ntasks_red); std::swap(p->flow_camsum, q->flow_camsum);
+  p->reduce_deferred = false; p->last_reduce_deferred = false;
+  std::swap(p->schur_blk_ptr, q->schur_blk_ptr);
+  std::swap(p->schur_mfma_ok, q->schur_mfma_ok);
+  std::swap(p->rows_built, q->rows_built); std::swap(p->rows_ok, q->rows_ok);
+  std::swap(p->cam_ptr, q->cam_ptr); std::swap(p->cam_ent, q->cam_ent); std::swap(p->cam_pairs, q->cam_pairs);
+  std::swap(p->rows_table, q->rows_table); std::swap(p->rows_first, q->rows_first); std::swap(p->rows_ws, q->rows_ws);
+  std::swap(p->rows_R, q->rows_R); std::swap(p->rows_tpr, q->rows_tpr); std::swap(p->rows_wgs, q->rows_wgs);
+  std::swap(p->rows_groups, q->rows_groups); std::swap(p->rows_tpl, q->rows_tpl); std::swap(p->rows_cp, q->rows_cp);
+  std::swap(p->max_track, q->max_track);
+  // deterministic mode holds for the grown scene only while the dense product fits and the camera accumulators stay in
+  // LDS (V <= 234): beyond that the handle falls back to the default path instead of mixing the two reduce kernels
+  p->deterministic = q->deterministic;
+  // an externally bound reduced buffer has the wrong size when cameras were added: the library's own buffer takes
+  // over and the caller binds a new one (sfm_ba_reduced_buffer reports the new size); with the camera count
+  // unchanged the binding survives
+  if (had_external_red && n_new_cams == 0) p->dev.red = q->dev.red;
+  else p->dev.red = p->own_red;
+  q->dev.red = q->own_red;
+  p->cur = 0; p->prep_valid = false; p->red_clean = false; p->lin_rows = 0;
+  std::swap(p->dev.stamps, q->dev.stamps);      // the diagnostic stamp buffer stays with the handle
+  return sfm_ba_destroy(q);
 }
 
 }  // namespace sfm
@@ -578,37 +637,109 @@ int sfm_ba_append(sfm_ba_problem* p, int n_new_cams, const double* cams_new, int
   };
   const int st = run();
   if (st != SFM_OK) { (void)hipStreamSynchronize(s); sfm_ba_destroy(q); return st; }
-  // the handle keeps its identity, options, stream and counters; the old buffers leave with q
-  q->schur_mode = p->schur_mode; q->debug = p->debug; q->timing = p->timing; q->quirks = p->quirks;
-  q->dev.debug = p->debug;
-  q->deterministic = p->deterministic && q->schur_mfma_ok && sizeof(double) * (size_t)q->dev.V * 35 <= 64 * 1024;
-  const bool had_external_red = p->dev.red != p->own_red;
-  ba_graph_drop(p);
-  std::swap(p->dev, q->dev);
-  std::swap(p->own_red, q->own_red);
-  std::swap(p->schur_ws, q->schur_ws);
-  std::swap(p->flow_tasks_red, q->flow_tasks_red); std::swap(p->flow_ntasks_red, q->flow_ntasks_red); std::swap(p->flow_camsum, q->flow_camsum);
-  p->reduce_deferred = false; p->last_reduce_deferred = false;
-  std::swap(p->schur_blk_ptr, q->schur_blk_ptr);
-  std::swap(p->schur_mfma_ok, q->schur_mfma_ok);
-  std::swap(p->rows_built, q->rows_built); std::swap(p->rows_ok, q->rows_ok);
-  std::swap(p->cam_ptr, q->cam_ptr); std::swap(p->cam_ent, q->cam_ent); std::swap(p->cam_pairs, q->cam_pairs);
-  std::swap(p->rows_table, q->rows_table); std::swap(p->rows_first, q->rows_first); std::swap(p->rows_ws, q->rows_ws);
-  std::swap(p->rows_R, q->rows_R); std::swap(p->rows_tpr, q->rows_tpr); std::swap(p->rows_wgs, q->rows_wgs);
-  std::swap(p->rows_groups, q->rows_groups); std::swap(p->rows_tpl, q->rows_tpl); std::swap(p->rows_cp, q->rows_cp);
-  std::swap(p->max_track, q->max_track);
-  // deterministic mode holds for the grown scene only while the dense product fits and the camera accumulators stay in
-  // LDS (V <= 234): beyond that the handle falls back to the default path instead of mixing the two reduce kernels
-  p->deterministic = q->deterministic;
-  // an externally bound reduced buffer has the wrong size when cameras were added: the library's own buffer takes
-  // over and the caller binds a new one (sfm_ba_reduced_buffer reports the new size); with the camera count
-  // unchanged the binding survives
-  if (had_external_red && n_new_cams == 0) p->dev.red = q->dev.red;
-  else p->dev.red = p->own_red;
-  q->dev.red = q->own_red;
-  p->cur = 0; p->prep_valid = false; p->red_clean = false; p->lin_rows = 0;
-  std::swap(p->dev.stamps, q->dev.stamps);      // the diagnostic stamp buffer stays with the handle
-  return sfm_ba_destroy(q);
+  return ba_adopt_grown(p, q, n_new_cams);
+}
+
+int sfm_ba_create_from_tracks(sfm_track_store* store, sfm_ba_problem** out) {
+  SFM_TRY(ensure_init());
+  if (out == nullptr) { set_error("sfm_ba_create_from_tracks: out is null"); return SFM_E_SHAPE; }
+  *out = nullptr;
+  TrackObservations t;
+  SFM_TRY(track_observations(store, "sfm_ba_create_from_tracks", &t));      // waits for the store's pending work
+  if (t.n_views < 1) { set_error("sfm_ba_create_from_tracks: the list was built for %d views", t.n_views); return SFM_E_SHAPE; }
+  sfm_ba_problem* p = nullptr;
+  SFM_TRY(ba_alloc_problem(t.n_views, t.n_pts, t.n_obs, ctx().stream, &p));
+  BaDev& d = p->dev;
+  const size_t m = (size_t)t.n_obs;
+  auto run = [&]() -> int {
+    SFM_HIP(hipMemcpyAsync(d.pt_ptr, t.pt_ptr, sizeof(int) * ((size_t)t.n_pts + 1), hipMemcpyDeviceToDevice, p->stream));
+    if (m > 0) {
+      SFM_HIP(hipMemcpyAsync(d.cam_idx, t.cam_idx, sizeof(int) * m, hipMemcpyDeviceToDevice, p->stream));
+      SFM_HIP(hipMemcpyAsync(d.u, t.u, sizeof(double) * m, hipMemcpyDeviceToDevice, p->stream));
+      SFM_HIP(hipMemcpyAsync(d.v, t.v, sizeof(double) * m, hipMemcpyDeviceToDevice, p->stream));
+    }
+    SFM_TRY(ba_enqueue_structure(p));
+    return ba_finish_structure(p, "sfm_ba_create_from_tracks");      // synchronises: the store may build its next list
+  };
+  const int st = run();
+  if (st != SFM_OK) { (void)hipStreamSynchronize(p->stream); sfm_ba_destroy(p); return st; }
+  *out = p;
+  return SFM_OK;
+}
+
+int sfm_ba_sync_tracks(sfm_ba_problem* p, sfm_track_store* store, int n_new_cams, const double* cams_new, int n_new_pts,
+                       const double* pts_new, int* action, int64_t* n_new_obs) {
+  SFM_TRY(check_problem(p));
+  if (action == nullptr) { set_error("sfm_ba_sync_tracks: action is null"); return SFM_E_SHAPE; }
+  if ((n_new_cams > 0 && cams_new == nullptr) || (n_new_pts > 0 && pts_new == nullptr)) { set_error("sfm_ba_sync_tracks: new cameras or points are null"); return SFM_E_SHAPE; }
+  TrackObservations t;
+  SFM_TRY(track_observations(store, "sfm_ba_sync_tracks", &t));             // waits for the store's pending work
+  SFM_TRY(ba_flush(p));
+  BaDev& d = p->dev;
+  *action = SFM_SYNC_REPLACED;
+  if (n_new_obs) *n_new_obs = 0;
+  if (t.n_views < d.V || t.n_pts < d.N || n_new_cams != t.n_views - d.V || n_new_pts != t.n_pts - d.N) return SFM_OK;
+  hipStream_t s = p->stream;
+  if (d.N > 0) {
+    DevBuf<unsigned> bad;
+    SFM_TRY(bad.alloc(1, s));
+    SFM_HIP(hipMemsetAsync(bad.p, 0xFF, sizeof(unsigned), s));
+    ba_tracks_compare_kernel<<<(d.N + 255) / 256, 256, 0, s>>>(d.N, d.pt_ptr, d.cam_idx, d.u, d.v, t.pt_ptr, t.cam_idx, t.u, t.v, bad.p);
+    SFM_HIP(hipGetLastError());
+    unsigned first_bad = 0;
+    SFM_HIP(hipMemcpyAsync(&first_bad, bad.p, sizeof(first_bad), hipMemcpyDeviceToHost, s));
+    SFM_TRY(stream_sync(s));
+    if (first_bad != 0xFFFFFFFFu) return SFM_OK;
+  }
+  // every resident track is part of its new track: with the same sizes all round nothing was added either
+  if (t.n_views == d.V && t.n_pts == d.N && t.n_obs == d.M) { *action = SFM_SYNC_REUSE; return SFM_OK; }
+  const int V = d.V, N = d.N;
+  const long long M = d.M;
+  const size_t m2 = (size_t)t.n_obs;
+  sfm_ba_problem* q = nullptr;
+  SFM_TRY(ba_alloc_problem(t.n_views, t.n_pts, t.n_obs, s, &q));
+  BaDev& e = q->dev;
+  const long long uploaded = p->upload_bytes;
+  auto run = [&]() -> int {
+    // the store's list IS the merged (point, camera)-sorted list: adopt it, device to device
+    SFM_HIP(hipMemcpyAsync(e.pt_ptr, t.pt_ptr, sizeof(int) * ((size_t)t.n_pts + 1), hipMemcpyDeviceToDevice, s));
+    if (m2 > 0) {
+      SFM_HIP(hipMemcpyAsync(e.cam_idx, t.cam_idx, sizeof(int) * m2, hipMemcpyDeviceToDevice, s));
+      SFM_HIP(hipMemcpyAsync(e.u, t.u, sizeof(double) * m2, hipMemcpyDeviceToDevice, s));
+      SFM_HIP(hipMemcpyAsync(e.v, t.v, sizeof(double) * m2, hipMemcpyDeviceToDevice, s));
+    }
+    // state: old cameras / points stay on the device, the new ones are uploaded behind them
+    SFM_HIP(hipMemcpyAsync(e.cams, d.cams, sizeof(double) * 7 * V, hipMemcpyDeviceToDevice, s));
+    SFM_TRY(ba_upload(p, e.cams + 7 * (size_t)V, cams_new, sizeof(double) * 7 * n_new_cams));
+    double* dst[3] = {e.px, e.py, e.pz};
+    const double* old[3] = {d.px, d.py, d.pz};
+    for (int k = 0; k < 3; ++k) {
+      if (N > 0) SFM_HIP(hipMemcpyAsync(dst[k], old[k], sizeof(double) * N, hipMemcpyDeviceToDevice, s));
+      SFM_TRY(ba_upload(p, dst[k] + N, pts_new + (size_t)k * n_new_pts, sizeof(double) * n_new_pts));
+    }
+    SFM_TRY(ba_enqueue_structure(q));
+    return ba_finish_structure(q, "sfm_ba_sync_tracks");
+  };
+  const int st = run();
+  if (st != SFM_OK) { (void)hipStreamSynchronize(s); p->upload_bytes = uploaded; sfm_ba_destroy(q); return st; }
+  SFM_TRY(ba_adopt_grown(p, q, n_new_cams));
+  *action = SFM_SYNC_GROWN;
+  if (n_new_obs) *n_new_obs = (int64_t)(t.n_obs - M);
+  return SFM_OK;
+}
+
+int sfm_ba_get_structure(sfm_ba_problem* p, int* pt_ptr, int* cam_idx, double* uv_norm) {
+  SFM_TRY(check_problem(p));
+  const BaDev& d = p->dev;
+  hipStream_t s = p->stream;
+  const size_t m = (size_t)d.M;
+  if (pt_ptr) SFM_HIP(hipMemcpyAsync(pt_ptr, d.pt_ptr, sizeof(int) * ((size_t)d.N + 1), hipMemcpyDeviceToHost, s));
+  if (cam_idx && m > 0) SFM_HIP(hipMemcpyAsync(cam_idx, d.cam_idx, sizeof(int) * m, hipMemcpyDeviceToHost, s));
+  if (uv_norm && m > 0) {
+    SFM_HIP(hipMemcpyAsync(uv_norm, d.u, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipMemcpyAsync(uv_norm + m, d.v, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+  }
+  return stream_sync(s);
 }
 
 int sfm_ba_points_ptr(sfm_ba_problem* p, void** d_px, void** d_py, void** d_pz, int* n_pts) {

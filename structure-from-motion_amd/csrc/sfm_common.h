@@ -86,6 +86,18 @@ struct DevBuf {
   }
 };
 
+// The observation list a track store built last (sfm_obs_build), for the bundle adjustment to read:
+// device pointers the store owns, valid until its next build; the store's pending work has been waited for.
+struct TrackObservations {
+  int n_views, n_pts;
+  long long n_obs;
+  const int* pt_ptr;                  // [n_pts + 1]
+  const int* cam_idx;                 // [n_obs]
+  const double* u;                    // [n_obs]
+  const double* v;
+};
+int track_observations(sfm_track_store* s, const char* who, TrackObservations* out);      // sfm_track.hip
+
 // First-failure status word written by kernels: status[0] = code (0 = ok), status[1] = index.
 __device__ __forceinline__ void report_status(int* status, int code, int index) {
   if (code != SFM_OK && atomicCAS(&status[0], 0, code) == 0) status[1] = index;

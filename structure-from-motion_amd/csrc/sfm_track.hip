@@ -16,6 +16,18 @@
 // The order of the filtered list is what makes a single workgroup per reference view the natural shape; the lists
 // are a few thousand entries and a view is matched against at most a few dozen others, so the kernel is latency-bound
 // (five passes separated by workgroup barriers), not throughput-bound.
+//
+// sfm_obs_build: the bundle adjustment's observation list (observations.build_observations: the loop of
+// ba_processor.py:304-310 over KeyTracker.is_visible, key_tracker.py:198-204, quirk Q3) from the self rows table[v][v, :]
+// and per-view tables of normalised key coordinates the host uploaded (inv(K) @ [u, v, 1] is a BLAS product on the host;
+// the device only gathers its results):
+//   mark    one thread per key: id = table[v][v, k]; for 0 <= id < n_pts atomicMin(min_key[v][id], k), atomicMax(max_key[v][id], k)
+//   count   one thread per point: the views with max_key > 0 (np.any tests the index VALUES: a point whose only key is 0
+//           is invisible)
+//   scan    one workgroup: pt_ptr = exclusive scan of the counts
+//   fill    one thread per point, views ascending: camera v, key min_key (key_idx[0][0]: index 0 included when another
+//           matching index is non-zero) and the normalised coordinates of that key
+// Integer atomics only, each independent of the order it is applied in; no floating-point arithmetic at all.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -40,6 +52,8 @@ struct ViewDesc {                   // one view as the kernels see it
   const double* y;                  // [n]
   int n;                            // keys
   int key_off;                      // sum of the key counts of the views before it (offset into per-train scratch)
+  const double* nu;                 // [n] normalised coordinates (sfm_obs_set_normalised), NULL until they are set
+  const double* nv;
 };
 
 // Position of this thread's element among the kept elements of the workgroup's current chunk, and their number.
@@ -268,10 +282,84 @@ __global__ void track_usage_write_kernel(const ViewDesc* __restrict__ views, int
   last[k] = -1;                     // only the winner of a key resets it: the scratch is all -1 again afterwards
 }
 
+// ---- observation list ------------------------------------------------------------------------------------------
+__global__ void obs_init_kernel(size_t cells, int* __restrict__ min_key, int* __restrict__ max_key) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i < cells) { min_key[i] = INT_MAX; max_key[i] = -1; }
+}
+
+// grid (key chunks, views)
+__global__ void obs_mark_kernel(const ViewDesc* __restrict__ views, int n_pts, int* __restrict__ min_key, int* __restrict__ max_key) {
+  const int v = blockIdx.y;
+  const ViewDesc w = views[v];
+  const int* row = w.table + (size_t)v * w.n;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < w.n; k += gridDim.x * blockDim.x) {
+    const int id = row[k];
+    if (id >= 0 && id < n_pts) {
+      atomicMin(&min_key[(size_t)v * n_pts + id], k);
+      atomicMax(&max_key[(size_t)v * n_pts + id], k);
+    }
+  }
+}
+
+__global__ void obs_count_kernel(int n_views, int n_pts, const int* __restrict__ max_key, int* __restrict__ cnt) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pts) return;
+  int c = 0;
+  for (int v = 0; v < n_views; ++v) c += max_key[(size_t)v * n_pts + p] > 0;
+  cnt[p] = c;
+}
+
+// exclusive prefix sum, one workgroup: inclusive scan inside a wave, wave totals through LDS, a running carry per chunk
+__global__ __launch_bounds__(TB) void obs_scan_kernel(int n, const int* __restrict__ cnt, int* __restrict__ ptr) {
+  __shared__ int wsum[WAVES];
+  __shared__ int carry;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) carry = 0;
+  __syncthreads();
+  for (int base = 0; base < n; base += TB) {
+    const int q = base + tid;
+    const int a = q < n ? cnt[q] : 0;
+    int sa = a;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int t = __shfl_up(sa, off, 64);
+      if (lane >= off) sa += t;
+    }
+    if (lane == 63) wsum[wave] = sa;
+    __syncthreads();
+    int o = carry;
+    for (int w = 0; w < wave; ++w) o += wsum[w];
+    if (q < n) ptr[q] = o + sa - a;
+    __syncthreads();
+    if (tid == TB - 1) carry = o + sa;
+    __syncthreads();
+  }
+  if (tid == 0) ptr[n] = carry;
+}
+
+__global__ void obs_fill_kernel(const ViewDesc* __restrict__ views, int n_views, int n_pts, const int* __restrict__ min_key,
+                                const int* __restrict__ max_key, const int* __restrict__ ptr, int* __restrict__ cam_idx,
+                                int* __restrict__ key_idx, double* __restrict__ u, double* __restrict__ v_out) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pts) return;
+  int w = ptr[p];
+  for (int v = 0; v < n_views; ++v) {
+    if (max_key[(size_t)v * n_pts + p] <= 0) continue;
+    const int k = min_key[(size_t)v * n_pts + p];          // 0 <= k < views[v].n: a key index the mark kernel wrote
+    cam_idx[w] = v;
+    key_idx[w] = k;
+    u[w] = views[v].nu[k];
+    v_out[w] = views[v].nv[k];
+    ++w;
+  }
+}
+
 struct View {
   int n = 0, rows = 0, rows_cap = 0, key_off = 0;
   int* table = nullptr;
   double* xy = nullptr;             // x[n] then y[n]
+  double* norm = nullptr;           // u[n] then v[n]: normalised coordinates, NULL until sfm_obs_set_normalised
 };
 
 // grow-only device buffer owned by the store
@@ -305,6 +393,13 @@ struct sfm_track_store {
   Scratch staging;                  // host-form inputs and outputs
   Scratch neighbours;               // sfm_track_match_views: the five [n_refs][nq] arrays of sfm_match_dev
   int last_new = -1, last_refs = 0, last_nq = 0;   // what the kept lists in `lists` belong to
+  // the observation list of the last sfm_obs_build
+  Scratch obs_keys;                 // min_key, max_key: [n_views][n_pts] each, then cnt[n_pts]
+  Scratch obs_ptr;                  // pt_ptr[n_pts + 1]
+  Scratch obs_idx;                  // cam_idx[cap], key_idx[cap]
+  Scratch obs_uv;                   // u[cap], v[cap]
+  int obs_views = -1, obs_pts = 0, obs_cap = 0;      // obs_views < 0: no list
+  long long obs_m = 0;
   hipStream_t pending = nullptr;    // the stream of the last enqueue that has not been waited for
   bool has_pending = false;
   int64_t upload_bytes = 0, download_bytes = 0;
@@ -346,7 +441,12 @@ inline int* list_ptr(const sfm_track_store* s, int which) {      // 0 fq, 1 ft, 
   return static_cast<int*>(s->lists.p) + (size_t)which * s->last_refs * (s->last_nq > 0 ? s->last_nq : 1);
 }
 
-inline ViewDesc desc_of(const View& w) { return ViewDesc{w.table, w.xy, w.xy + w.n, w.n, w.key_off}; }
+inline ViewDesc desc_of(const View& w) {
+  return ViewDesc{w.table, w.xy, w.xy + w.n, w.n, w.key_off, w.norm, w.norm ? w.norm + w.n : nullptr};
+}
+
+// 2 V n_pts ints of min_key / max_key scratch at the most (1 GiB); beyond it sfm_obs_build returns SFM_E_SHAPE
+constexpr size_t OBS_SCRATCH_CAP = (size_t)1 << 28;
 
 int table_alloc(Uncommitted& mem, View& w, int rows_cap) {
   const size_t bytes = sizeof(int) * (size_t)rows_cap * (w.n > 0 ? w.n : 1);
@@ -454,8 +554,10 @@ int sfm_track_destroy(sfm_track_store* s) {
   for (View& w : s->views) {
     if (w.table) (void)hipFree(w.table);
     if (w.xy) (void)hipFree(w.xy);
+    if (w.norm) (void)hipFree(w.norm);
   }
   if (s->d_views) (void)hipFree(s->d_views);
+  s->obs_keys.release(); s->obs_ptr.release(); s->obs_idx.release(); s->obs_uv.release();
   s->lists.release(); s->train.release(); s->info.release(); s->usage_last.release(); s->staging.release(); s->neighbours.release();
   delete s;
   return SFM_OK;
@@ -468,6 +570,9 @@ int sfm_track_info(const sfm_track_store* s, int what, int view, int64_t* value)
     case SFM_TRACK_INFO_N_VIEWS: *value = (int64_t)s->views.size(); return SFM_OK;
     case SFM_TRACK_INFO_UPLOAD_BYTES: *value = s->upload_bytes; return SFM_OK;
     case SFM_TRACK_INFO_DOWNLOAD_BYTES: *value = s->download_bytes; return SFM_OK;
+    case SFM_TRACK_INFO_OBS_VIEWS: *value = s->obs_views; return SFM_OK;
+    case SFM_TRACK_INFO_OBS_PTS: *value = s->obs_views < 0 ? 0 : s->obs_pts; return SFM_OK;
+    case SFM_TRACK_INFO_N_OBS: *value = s->obs_views < 0 ? 0 : s->obs_m; return SFM_OK;
     case SFM_TRACK_INFO_N_KEYS:
     case SFM_TRACK_INFO_N_ROWS:
       SFM_TRY(valid_view(s, view, "sfm_track_info"));
@@ -540,6 +645,7 @@ int sfm_track_drop_last_view(sfm_track_store* s) {
   s->total_keys -= w.n;
   if (w.table) (void)hipFree(w.table);
   if (w.xy) (void)hipFree(w.xy);
+  if (w.norm) (void)hipFree(w.norm);
   s->views.pop_back();
   s->last_new = -1; s->last_refs = 0; s->last_nq = 0;
   return SFM_OK;
@@ -728,4 +834,119 @@ int sfm_track_copy_row(sfm_track_store* s, int view, int row, int* out) {
   return SFM_OK;
 }
 
+int sfm_obs_set_normalised(sfm_track_store* s, int view, int n, const double* u, const double* v) {
+  SFM_TRY(ensure_init());
+  if (!s) return SFM_E_HANDLE;
+  SFM_TRY(valid_view(s, view, "sfm_obs_set_normalised"));
+  View& w = s->views[view];
+  if (n != w.n || (n > 0 && (!u || !v))) { set_error("sfm_obs_set_normalised: %d coordinates for a view of %d keys", n, w.n); return SFM_E_SHAPE; }
+  if (n == 0) return SFM_OK;
+  SFM_TRY(settle(s));                                 // no kernel reads the table that is replaced
+  SFM_TRY(stream_sync(ctx().stream));
+  if (!w.norm) {
+    Uncommitted mem;
+    double* norm = nullptr;
+    SFM_TRY(mem.alloc(reinterpret_cast<void**>(&norm), sizeof(double) * 2 * (size_t)n));
+    View next = w;
+    next.norm = norm;
+    const ViewDesc d = desc_of(next);
+    SFM_HIP(hipMemcpy(s->d_views + view, &d, sizeof(d), hipMemcpyHostToDevice));
+    mem.commit();
+    w.norm = norm;
+  }
+  SFM_HIP(hipMemcpy(w.norm, u, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  SFM_HIP(hipMemcpy(w.norm + n, v, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  s->upload_bytes += 16ll * n;
+  return SFM_OK;
+}
+
+int sfm_obs_build(sfm_track_store* s, int n_views, int n_pts, int64_t* n_obs) {
+  SFM_TRY(ensure_init());
+  if (!s) return SFM_E_HANDLE;
+  if (n_views < 0 || n_views > (int)s->views.size() || n_pts < 0) {
+    set_error("sfm_obs_build: %d views of %d, %d points", n_views, (int)s->views.size(), n_pts);
+    return SFM_E_SHAPE;
+  }
+  const size_t cells = (size_t)n_views * (size_t)n_pts;
+  if (2 * cells > OBS_SCRATCH_CAP) {
+    set_error("sfm_obs_build: %d views x %d points need more than %zu ints of scratch", n_views, n_pts, OBS_SCRATCH_CAP);
+    return SFM_E_SHAPE;
+  }
+  long long keys = 0;                                 // an observation has a key of its own: M <= the keys of the views
+  int max_n = 0;
+  for (int v = 0; v < n_views; ++v) {
+    const View& w = s->views[v];
+    if (w.n > 0 && !w.norm) { set_error("sfm_obs_build: view %d has no normalised coordinates", v); return SFM_E_SHAPE; }
+    if (w.rows <= v) { set_error("sfm_obs_build: table %d has no row %d", v, v); return SFM_E_SHAPE; }
+    keys += w.n;
+    max_n = w.n > max_n ? w.n : max_n;
+  }
+  const size_t cap = (size_t)(keys < (long long)cells ? keys : (long long)cells);
+  if (cap > 0x7fffffffull) { set_error("sfm_obs_build: too many observations"); return SFM_E_SHAPE; }
+  hipStream_t st = ctx().stream;
+  SFM_TRY(settle(s));
+  s->obs_views = -1;
+  SFM_TRY(s->obs_keys.reserve(sizeof(int) * (2 * cells + (size_t)n_pts + 1)));
+  SFM_TRY(s->obs_ptr.reserve(sizeof(int) * ((size_t)n_pts + 1)));
+  SFM_TRY(s->obs_idx.reserve(sizeof(int) * 2 * (cap + 1)));
+  SFM_TRY(s->obs_uv.reserve(sizeof(double) * 2 * (cap + 1)));
+  int* min_key = static_cast<int*>(s->obs_keys.p);
+  int* max_key = min_key + cells;
+  int* cnt = max_key + cells;
+  int* ptr = static_cast<int*>(s->obs_ptr.p);
+  int* cam = static_cast<int*>(s->obs_idx.p);
+  double* u = static_cast<double*>(s->obs_uv.p);
+  if (cells > 0) {
+    obs_init_kernel<<<(unsigned)((cells + 255) / 256), 256, 0, st>>>(cells, min_key, max_key);
+    if (max_n > 0) {
+      const int bx = (max_n + 255) / 256 < 64 ? (max_n + 255) / 256 : 64;
+      obs_mark_kernel<<<dim3((unsigned)bx, (unsigned)n_views), 256, 0, st>>>(s->d_views, n_pts, min_key, max_key);
+    }
+  }
+  if (n_pts > 0) obs_count_kernel<<<(n_pts + 255) / 256, 256, 0, st>>>(n_views, n_pts, max_key, cnt);
+  obs_scan_kernel<<<1, TB, 0, st>>>(n_pts, cnt, ptr);
+  if (cells > 0) obs_fill_kernel<<<(n_pts + 255) / 256, 256, 0, st>>>(s->d_views, n_views, n_pts, min_key, max_key, ptr, cam, cam + cap + 1, u, u + cap + 1);
+  SFM_HIP(hipGetLastError());
+  int m = 0;
+  SFM_HIP(hipMemcpyAsync(&m, ptr + n_pts, sizeof(m), hipMemcpyDeviceToHost, st));
+  SFM_TRY(stream_sync(st));                           // (the count is the call's result, not data of the store: not in download_bytes)
+  s->obs_views = n_views; s->obs_pts = n_pts; s->obs_cap = (int)cap; s->obs_m = m;
+  if (n_obs) *n_obs = m;
+  return SFM_OK;
+}
+
+int sfm_obs_copy(sfm_track_store* s, int* pt_ptr, int* cam_idx, int* key_idx, double* uv) {
+  SFM_TRY(ensure_init());
+  if (!s) return SFM_E_HANDLE;
+  if (s->obs_views < 0) { set_error("sfm_obs_copy: no observation list has been built"); return SFM_E_SHAPE; }
+  SFM_TRY(settle(s));
+  const size_t m = (size_t)s->obs_m, cap1 = (size_t)s->obs_cap + 1;
+  const int* cam = static_cast<const int*>(s->obs_idx.p);
+  const double* u = static_cast<const double*>(s->obs_uv.p);
+  if (pt_ptr) { SFM_HIP(hipMemcpy(pt_ptr, s->obs_ptr.p, sizeof(int) * ((size_t)s->obs_pts + 1), hipMemcpyDeviceToHost)); s->download_bytes += 4ll * (s->obs_pts + 1); }
+  if (m == 0) return SFM_OK;
+  if (cam_idx) { SFM_HIP(hipMemcpy(cam_idx, cam, sizeof(int) * m, hipMemcpyDeviceToHost)); s->download_bytes += 4ll * (int64_t)m; }
+  if (key_idx) { SFM_HIP(hipMemcpy(key_idx, cam + cap1, sizeof(int) * m, hipMemcpyDeviceToHost)); s->download_bytes += 4ll * (int64_t)m; }
+  if (uv) {
+    SFM_HIP(hipMemcpy(uv, u, sizeof(double) * m, hipMemcpyDeviceToHost));
+    SFM_HIP(hipMemcpy(uv + m, u + cap1, sizeof(double) * m, hipMemcpyDeviceToHost));
+    s->download_bytes += 16ll * (int64_t)m;
+  }
+  return SFM_OK;
+}
+
 }  // extern "C"
+
+namespace sfm {
+
+int track_observations(sfm_track_store* s, const char* who, TrackObservations* out) {
+  if (!s) { set_error("%s: the track store is NULL", who); return SFM_E_HANDLE; }
+  if (s->obs_views < 0) { set_error("%s: the store has no observation list (sfm_obs_build)", who); return SFM_E_SHAPE; }
+  SFM_TRY(settle(s));
+  const int* cam = static_cast<const int*>(s->obs_idx.p);
+  const double* u = static_cast<const double*>(s->obs_uv.p);
+  *out = TrackObservations{s->obs_views, s->obs_pts, s->obs_m, static_cast<const int*>(s->obs_ptr.p), cam, u, u + (size_t)s->obs_cap + 1};
+  return SFM_OK;
+}
+
+}  // namespace sfm

@@ -30,7 +30,9 @@ DESC_INFO_N, DESC_INFO_DIM, DESC_INFO_EXACT, DESC_INFO_UPLOAD_BYTES = 1, 2, 3, 4
 SIFT_INFO_N, SIFT_INFO_N_OCTAVES, SIFT_INFO_N_PRE, SIFT_INFO_N_LAYERS, SIFT_INFO_KEEPS_PYRAMID = 1, 2, 3, 4, 5
 SIFT_LEVEL_GAUSS, SIFT_LEVEL_DOG = 0, 1
 TRACK_INFO_N_VIEWS, TRACK_INFO_N_KEYS, TRACK_INFO_N_ROWS, TRACK_INFO_UPLOAD_BYTES, TRACK_INFO_DOWNLOAD_BYTES = 1, 2, 3, 4, 5
+TRACK_INFO_OBS_VIEWS, TRACK_INFO_OBS_PTS, TRACK_INFO_N_OBS = 6, 7, 8
 TRACK_OK, TRACK_NO_SECOND, TRACK_ZERO_SECOND, TRACK_BAD_TRAIN = 0, 1, 2, 3
+SYNC_REUSE, SYNC_GROWN, SYNC_REPLACED = 0, 1, 2
 
 # every symbol include/sfm_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -57,6 +59,8 @@ EXPORTS = (
     "sfm_track_match_dedup_dev", "sfm_track_extend_dev", "sfm_track_match_views", "sfm_track_extend_status",
     "sfm_track_kept_copy", "sfm_track_write_kept", "sfm_track_pairs_dev", "sfm_track_pairs", "sfm_track_update_usage",
     "sfm_track_constructed", "sfm_track_unconstructed", "sfm_track_copy_table", "sfm_track_copy_row",
+    "sfm_obs_set_normalised", "sfm_obs_build", "sfm_obs_copy",
+    "sfm_ba_create_from_tracks", "sfm_ba_sync_tracks", "sfm_ba_get_structure",
 )
 
 _lib = None
@@ -182,6 +186,12 @@ def load():
     lib.sfm_track_unconstructed.argtypes = [vp, ci, _ip, _ip]
     lib.sfm_track_copy_table.argtypes = [vp, ci, _ip]
     lib.sfm_track_copy_row.argtypes = [vp, ci, ci, _ip]
+    lib.sfm_obs_set_normalised.argtypes = [vp, ci, ci, _dp, _dp]
+    lib.sfm_obs_build.argtypes = [vp, ci, ci, ctypes.POINTER(ctypes.c_int64)]
+    lib.sfm_obs_copy.argtypes = [vp, _ip, _ip, _ip, _dp]
+    lib.sfm_ba_create_from_tracks.argtypes = [vp, ctypes.POINTER(vp)]
+    lib.sfm_ba_sync_tracks.argtypes = [vp, vp, ci, _dp, ci, _dp, _ip, ctypes.POINTER(ctypes.c_int64)]
+    lib.sfm_ba_get_structure.argtypes = [vp, _ip, _ip, _dp]
     _lib = lib
     return lib
 
@@ -621,6 +631,44 @@ class BaProblem:
         check(self._lib.sfm_ba_create(self.n_cams, self.n_pts, self.n_obs, iptr(pt_ptr), iptr(cam_idx),
                                       dptr(uv_norm), ctypes.byref(h)))
         self._h = h
+
+    @classmethod
+    def from_tracks(cls, store):
+        """A problem whose structure is ``store``'s current observation list (``TrackStore.build_observations``), copied
+        device to device (sfm_ba_create_from_tracks): nothing is uploaded."""
+        self = cls.__new__(cls)
+        self._lib = load()
+        self._h = None
+        h = ctypes.c_void_p()
+        check(self._lib.sfm_ba_create_from_tracks(store._h, ctypes.byref(h)))
+        self._h = h
+        self._read_sizes()
+        return self
+
+    def _read_sizes(self):
+        self.n_cams, self.n_pts, self.n_obs = self.info(INFO_N_CAMS), self.info(INFO_N_PTS), self.info(INFO_N_OBS)
+
+    def sync_tracks(self, store, cams_new=None, pts_new=None):
+        """Bring the problem up to ``store``'s current observation list (sfm_ba_sync_tracks); ``cams_new`` (k, 7) and
+        ``pts_new`` (3, k) are the cameras and points the list has beyond the resident ones.  Returns
+        ``(action, n_new_obs)``: ``SYNC_REUSE`` (nothing changed), ``SYNC_GROWN`` (the problem took the list over; only the
+        new cameras and points went up) or ``SYNC_REPLACED`` (the problem is unchanged: build a new one)."""
+        cams_new = f64(np.zeros((0, 7)) if cams_new is None else cams_new).reshape(-1, 7)
+        pts_new = f64(np.zeros((3, 0)) if pts_new is None else pts_new).reshape(3, -1)
+        action, n_new = ctypes.c_int(), ctypes.c_int64()
+        check(self._lib.sfm_ba_sync_tracks(self._h, store._h, cams_new.shape[0], dptr(cams_new) if cams_new.size else None,
+                                           pts_new.shape[1], dptr(pts_new) if pts_new.size else None, ctypes.byref(action),
+                                           ctypes.byref(n_new)))
+        if action.value == SYNC_GROWN:
+            self._read_sizes()
+        return action.value, int(n_new.value)
+
+    def structure(self):
+        """(pt_ptr (N+1,), cam_idx (M,), uv_norm (2, M)): the resident observation list (sfm_ba_get_structure)."""
+        n, m = self.info(INFO_N_PTS), self.info(INFO_N_OBS)
+        pt_ptr, cam_idx, uv = np.zeros(n + 1, dtype=np.int32), np.zeros(m, dtype=np.int32), np.zeros((2, m))
+        check(self._lib.sfm_ba_get_structure(self._h, iptr(pt_ptr), iptr(cam_idx) if m else None, dptr(uv) if m else None))
+        return pt_ptr, cam_idx, uv
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1100,3 +1148,26 @@ class TrackStore:
         out = np.zeros(self.n_keys(view), dtype=np.int32)
         check(self._lib.sfm_track_copy_row(self._h, int(view), int(row), iptr(out) if out.size else None))
         return out
+
+    def set_normalised(self, view, uv):
+        """The normalised coordinates ((2, n): ``geometry.normalise_pixels`` of ALL keys) the observation list gathers
+        from (sfm_obs_set_normalised); again whenever the view's intrinsic matrix changes."""
+        uv = np.asarray(uv, dtype=np.float64).reshape(2, -1)
+        u, v = np.ascontiguousarray(uv[0]), np.ascontiguousarray(uv[1])
+        check(self._lib.sfm_obs_set_normalised(self._h, int(view), u.shape[0], dptr(u) if u.size else None, dptr(v) if v.size else None))
+
+    def build_observations(self, n_views, n_pts):
+        """Build the bundle adjustment's observation list of the first ``n_views`` views and ``n_pts`` points on the device
+        (sfm_obs_build: ``observations.build_observations`` of the views' own rows); returns M."""
+        m = ctypes.c_int64()
+        check(self._lib.sfm_obs_build(self._h, int(n_views), int(n_pts), ctypes.byref(m)))
+        return int(m.value)
+
+    def observations(self):
+        """(pt_ptr (N+1,), cam_idx (M,), key_idx (M,), uv (2, M)) of the last ``build_observations``."""
+        n, m = self.info(TRACK_INFO_OBS_PTS), self.info(TRACK_INFO_N_OBS)
+        pt_ptr, cam, key = np.zeros(n + 1, dtype=np.int32), np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
+        uv = np.zeros((2, m))
+        check(self._lib.sfm_obs_copy(self._h, iptr(pt_ptr), iptr(cam) if m else None, iptr(key) if m else None,
+                                                    dptr(uv) if m else None))
+        return pt_ptr, cam, key, uv

@@ -31,7 +31,7 @@ import pickle
 import numpy as np
 
 from . import matching, native
-from .geometry import (pack_cameras, quaternion_to_rotation_unchecked, quaternions_to_rotations)
+from .geometry import (normalise_pixels, pack_cameras, quaternion_to_rotation_unchecked, quaternions_to_rotations)
 from .observations import KeyCache, ObservationTracker, build_observations, gather_normalised_keys
 from .q13 import det_branch_fires, reference_winner
 from .sampling import sample_indices
@@ -344,6 +344,7 @@ class _ResidentScene:
         self.rots_written = None  # (V, 3, 3) / (V, 3): the poses of the last write-back (what view.rot / .loc hold if untouched)
         self.locs_written = None
         self.n_views_before = 0
+        self.from_device = False  # the structure came from the tracker's device tables (ba_device_tracks): the host picture above is not kept
         self.retired_bytes = 0    # upload bytes of problems this scene has replaced
 
     def close(self):
@@ -379,12 +380,24 @@ class HipBaMixin:
     ``ba_release()`` (or hand the view a new list) for the edit to reach the device.  The track tables of a
     ``HipDeviceKeyTracker`` follow the same rule the other way round: ``track_list[i].table`` is a host picture of the device
     table, and a write into it is not propagated to the device (``HipDeviceKeyTrack``).
-    ``ba_upload_bytes`` reports the PCIe bytes spent so far; ``ba_release()`` frees the device copy."""
+    ``ba_upload_bytes`` reports the PCIe bytes spent so far; ``ba_release()`` frees the device copy.
+
+    ``ba_device_tracks = True`` (off by default; needs ``ba_resident`` and a ``HipDeviceKeyTracker`` as ``self.key_tracker``,
+    anything else raises ``TypeError``) builds the observation list where the tracks already are: no ``track_list[v].table``
+    is read, nothing is diffed or gathered on the host.  Each call makes sure the tracker's store holds every view's
+    normalised key coordinates (computed on the host from the coordinates the tracker uploaded, once per view and again when
+    ``view.k`` changes), has the device build the list (``TrackStore.build_observations``) and compare it with the resident
+    structure (``BaProblem.sync_tracks``).  Then the DEVICE tables are the truth: a host-side replacement of
+    ``track_list[v].table`` (its setter) is not seen.  The observation list is the same as the host path's in every case,
+    but ``ba_last_action`` may be ``"append"`` or ``"reuse"`` where the host path conservatively says ``"create"``:
+    ``ObservationTracker.diff`` rebuilds on a second key for an observed point and on key index 0 even when the list does
+    not change, the device compares the lists themselves."""
 
     ba_quirk_flags = native.QUIRKS_REFERENCE
     ba_verbose = True          # the reference prints unconditionally (ba:418-439)
     ba_resident = True         # keep the problem on the device between calls (False: one sfm_ba_solve per call)
     ba_last_action = None      # "create" | "append" | "reuse" | "solve": what the last call did (diagnostics / tests)
+    ba_device_tracks = False   # build the observation list from a HipDeviceKeyTracker's device tables (class docstring)
 
     def ba_release(self):
         scene = self.__dict__.pop("_hip_scene", None)
@@ -409,8 +422,10 @@ class HipBaMixin:
             scene = self.__dict__["_hip_scene"] = _ResidentScene()
         view_num = len(views)
         n_old = scene.n_views_before = scene.n_views
+        if self.ba_device_tracks:
+            return self._ba_sync_device_tracks(scene, views, tri_num, n_same, new_cams, init_tri_pts)
         rows = [self.key_tracker.track_list[v].table[v, :] for v in range(view_num)]
-        same_intrinsics = scene.prob is not None and view_num >= n_old and all(
+        same_intrinsics = scene.prob is not None and not scene.from_device and view_num >= n_old and all(
             np.array_equal(views[v].k, scene.ks[v]) for v in range(n_old))
         grown = scene.tracker.diff(rows, tri_num) if same_intrinsics else None
         if grown is not None:
@@ -436,12 +451,70 @@ class HipBaMixin:
             scene.pts_written = None
             scene.rots_written = scene.locs_written = None
             self.ba_last_action = "create"
+        scene.from_device = False
         scene.ks = [np.array(v.k, dtype=np.float64, copy=True) for v in views]
         scene.n_views = view_num
         scene.n_pts = tri_num
         return scene
 
+    def _ba_check_device_tracks(self):
+        if not isinstance(self.key_tracker, HipDeviceKeyTracker):
+            raise TypeError("ba_device_tracks needs a HipDeviceKeyTracker as key_tracker, not {}".format(
+                type(self.key_tracker).__name__))
+        if not self.ba_resident:
+            raise TypeError("ba_device_tracks needs ba_resident")
+
+    def _ba_sync_device_tracks(self, scene, views, tri_num, n_same, new_cams, init_tri_pts):
+        """``_ba_sync_structure`` with ``ba_device_tracks``: the tracker's store builds the list, the device compares it with
+        the resident structure (class docstring)."""
+        kt = self.key_tracker
+        store = kt._store
+        view_num, n_old = len(views), scene.n_views
+        if store is None or store.n_views < view_num:
+            raise native.SfmHipError("ba_device_tracks: the device store holds %s views, the scene %d"
+                                     % ("no" if store is None else store.n_views, view_num))
+        norm = kt.__dict__.get("_norm_ks")                    # (store, per view: the k its normalised table was made with)
+        if norm is None or norm[0] is not store:
+            norm = kt.__dict__["_norm_ks"] = (store, [])
+        ks = norm[1]
+        for v in range(view_num):                             # ba:339-342 for all keys of a view, once per (view, k)
+            k = np.asarray(views[v].k, dtype=np.float64)
+            if v >= len(ks):
+                ks.extend([None] * (v + 1 - len(ks)))
+            if ks[v] is None or not np.array_equal(ks[v], k):
+                store.set_normalised(v, normalise_pixels(kt._xy[v].T, k))
+                ks[v] = k.copy()
+        store.build_observations(view_num, tri_num)           # ba:309
+        action = native.SYNC_REPLACED
+        if scene.prob is not None and view_num >= n_old and tri_num >= scene.n_pts:
+            try:
+                cams_app = new_cams[n_old - n_same:] if n_same <= n_old else pack_cameras(
+                    np.stack([np.asarray(v.rot, dtype=np.float64) for v in views[n_old:]]),
+                    np.stack([np.asarray(v.loc, dtype=np.float64).reshape(3) for v in views[n_old:]]))
+                action, _n_new = scene.prob.sync_tracks(store, cams_app, init_tri_pts[:, scene.n_pts:tri_num])
+            except Exception:
+                self.ba_release()
+                raise
+        if action == native.SYNC_REUSE:
+            self.ba_last_action = "reuse"
+        elif action == native.SYNC_GROWN:
+            self.ba_last_action = "append"
+        else:
+            scene.close()
+            scene.prob = native.BaProblem.from_tracks(store)
+            scene.pts_written = None
+            scene.rots_written = scene.locs_written = None
+            self.ba_last_action = "create"
+        scene.from_device = True
+        if scene.tracker.rows:
+            scene.tracker = ObservationTracker()              # the host picture is not kept on this path
+        scene.n_views = view_num
+        scene.n_pts = tri_num
+        return scene
+
     def execute_bundle_adjustment(self):
+        if self.ba_device_tracks:
+            self._ba_check_device_tracks()
         views = self.view_processor.view_list
         tri_pts = self.tri_processor.tri_pts
         view_num = len(views)
