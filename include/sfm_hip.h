@@ -364,6 +364,48 @@ int sfm_ba_flush(sfm_ba_problem* p);
  * sfm_ba_append / sfm_ba_destroy. */
 int sfm_ba_points_ptr(sfm_ba_problem* p, void** d_px, void** d_py, void** d_pz, int* n_pts);
 int sfm_ba_stream(sfm_ba_problem* p, void** hip_stream);
+
+/* ---- triangulation and structure-only refinement over ragged multi-view tracks ------------------------------------
+ * A point owns the observations [pt_ptr[i], pt_ptr[i+1]) of a CSR (cam_idx[M], uv[2][M] SoA, in the coordinates of
+ * projs[n_views][3][4]) and is solved from exactly those views:
+ *   SFM_TRACKS_LINEAR     TriangulationProcessor.linear_triangulate over the track (rows per observation: u, then v);
+ *   SFM_TRACKS_NONLINEAR  `iters` steps X[0:3] -= inv(sum Jx^T Jx + lambda I) sum Jx^T (f - b) over the track
+ *                         (TriangulationProcessor.nonlinear_triangulate = the point half of a bundle-adjustment
+ *                         iteration with the cameras held), from X_init, or from the DLT result when both bits are set.
+ * Row W of X is read, used in the projection and carried unchanged.  `group` lanes share a point (1, 4, 8, 16, 32, 64;
+ * 0 = chosen from n_pts, M and the longest track): a point's result depends on its own track, its input and the group
+ * width only -- not on the other points of the call, the grid or timing.  iters = 0 with SFM_TRACKS_NONLINEAR is a
+ * pure evaluation (points come out as they went in).  An empty track is a no-op; a track of one observation is
+ * refined (the damping makes it solvable) but not solved linearly.
+ * cost[2][n_pts] (optional): sum |f - b|^2 over the track at the input point (row 0) and at the output point (row 1).
+ * status[n_pts] (optional): a mask of the SFM_TRACK_* bits below.
+ * The CSR is validated on the device (pt_ptr[0] == 0, non-decreasing, pt_ptr[n_pts] == M, cam_idx in range); a failure
+ * returns SFM_E_SHAPE, sfm_last_error names the index, nothing is written.  The _dev form takes device pointers,
+ * waits once for that verdict and then only enqueues on hip_stream. */
+#define SFM_TRACKS_LINEAR    1   /* DLT from the track; needs >= 2 observations */
+#define SFM_TRACKS_NONLINEAR 2   /* damped Gauss-Newton from X (or from the DLT result when both bits are set) */
+#define SFM_TRACK_TOO_FEW    1   /* the linear pass was requested and the track has fewer than 2 observations: the point keeps its
+                                    input for that pass ((0, 0, 0, 1) when there is no X_init) */
+#define SFM_TRACK_NONFINITE  2   /* a non-finite value or a zero determinant turned up: the point is written back as it came in */
+#define SFM_TRACK_BEHIND     4   /* at the output point s[2] <= 0 for at least one observation (informational) */
+int sfm_tri_tracks(int n_pts, int n_views, int64_t M, const int* pt_ptr, const int* cam_idx,
+                   const double* uv /*[2][M]*/, const double* projs /*[n_views][3][4]*/,
+                   int mode, double lambda, int iters, int group,
+                   const double* X_init /*[4][n_pts], may be NULL when mode has LINEAR*/,
+                   double* X_out /*[4][n_pts]*/, double* cost /*[2][n_pts] or NULL*/, int* status /*[n_pts] or NULL*/);
+int sfm_tri_tracks_dev(int n_pts, int n_views, int64_t M, const int* d_pt_ptr, const int* d_cam_idx,
+                       const double* d_uv, const double* d_projs, int mode, double lambda, int iters, int group,
+                       const double* d_X_init, double* d_X_out /* may equal d_X_init */, double* d_cost, int* d_status,
+                       void* hip_stream);
+/* The group width `group` = 0 stands for, from the three quantities it may depend on (host only; the rule is DESIGN.md section 16). */
+int sfm_tri_tracks_auto_group(int n_pts, int64_t M, int max_track);
+/* The same on the resident scene, in place: observations and points (W = 1) are the problem's, the projections are
+ * [R(q)^T | -R(q)^T C] of the prepared cameras the linearisation reads, so cost row 0 summed over the points is the
+ * bundle adjustment's cost at the same state.  Completes a deferred back substitution first; cameras and their prepared
+ * form are untouched; the points are treated as by sfm_ba_set_points (the cost history restarts).  Runs on the problem's
+ * stream and uploads nothing.  cost / status are HOST arrays ([2][N], [N]) or NULL.  An empty problem returns SFM_OK. */
+int sfm_ba_refine_points(sfm_ba_problem* p, int mode, double lambda, int iters, int group,
+                         double* cost /*host [2][N] or NULL*/, int* status /*host [N] or NULL*/);
 /* DEVICE pointer + element count of the contiguous reduced buffer (doubles).  It holds [S | rhs] between sfm_ba_linearize_reduce and
  * sfm_ba_solve_update (what the caller all-reduces); the factorisation overwrites it, and sfm_ba_iterate on one GPU may never form S
  * in it at all (SFM_INFO_REDUCE_IN_SOLVE) -- use sfm_ba_reduced_system to look at S. */

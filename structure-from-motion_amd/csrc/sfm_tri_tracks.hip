@@ -1,0 +1,472 @@
+// sfm_tri_tracks.hip — triangulation and structure-only refinement over RAGGED multi-view tracks (gfx950).
+//
+// The rectangular kernels of sfm_core.hip take uv[n_views][2][m]: every point seen in every view.  Here a point owns
+// a CSR row of observations (pt_ptr / cam_idx / u / v, the layout of the resident bundle-adjustment scene and of
+// sfm_obs_build) and is solved from exactly those:
+//   linear     TriangulationProcessor.linear_triangulate (triangulation_processor.py:91-157) over the point's views,
+//   nonlinear  TriangulationProcessor.nonlinear_triangulate (triangulation_processor.py:160-234) over the point's
+//              views = the point half of BaProcessor.__execute_bundle_adjustment with delta_p = 0
+//              (ba_processor.py:333, 355-359, 405):  X -= inv(sum Jx^T Jx + lambda I) sum Jx^T (f - b).
+// A group of G lanes owns a point; lane l takes observations l, l + G, ... in track order, the nine normal-equation
+// sums go through group_sum<G>, every lane of the group then holds the same bits and solves the 3x3 redundantly.
+// No atomics, no LDS accumulation: a point's result is a function of its track, its input and G alone.
+#include <climits>
+
+#include "sfm_ba.h"
+#include "sfm_dlt.h"
+
+namespace sfm {
+
+// first failure of the CSR check: info[0] = code, info[1] = index, info[2] = longest track
+enum { kTrkPtr0 = 1, kTrkMonotone = 2, kTrkEnd = 3, kTrkCam = 4 };
+
+__global__ void tracks_check_kernel(int n_pts, int n_views, long long M, const int* __restrict__ pt_ptr,
+                                    const int* __restrict__ cam_idx, int* __restrict__ info) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pts) return;
+  if (p == 0 && pt_ptr[0] != 0) report_status(info, kTrkPtr0, 0);
+  if (p == n_pts - 1 && pt_ptr[n_pts] != M) report_status(info, kTrkEnd, n_pts);
+  const int beg = pt_ptr[p], end = pt_ptr[p + 1];
+  if (beg < 0 || end < beg || end > M) { report_status(info, kTrkMonotone, p); return; }
+  for (int o = beg; o < end; ++o) {
+    const int c = cam_idx[o];
+    if (c < 0 || c >= n_views) { report_status(info, kTrkCam, o); break; }
+  }
+  atomicMax(&info[2], end - beg);
+}
+
+// [R^T | t] of every prepared camera as a row-major 3x4 projection (ba_processor.py:328)
+__global__ void tracks_proj_from_prep_kernel(int V, const CamPrep* __restrict__ prep, double* __restrict__ projs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 12 * V) return;
+  const CamPrep& c = prep[i / 12];
+  const int r = (i % 12) / 4, k = i % 4;
+  projs[i] = k < 3 ? c.R[3 * k + r] : c.t[r];
+}
+
+struct TrackArgs {
+  int n_pts, n_views;
+  const int* pt_ptr;
+  const int* cam_idx;
+  const double* u;
+  const double* v;
+  const double* projs;
+  const double* xin[4];     // rows X, Y, Z, W of the input points; a null W row stands for W = 1
+  double* xout[4];          // may equal xin; a null W row is not written
+  double lambda;
+  int iters;
+  double* cost;             // [2][n_pts] or null
+  int* status;              // [n_pts] or null
+  int status_or;            // 1: OR into what the linear pass left in status, 0: overwrite
+  int proj_in_lds;          // re-reading variant: stage the projections in LDS
+};
+
+// ---------------------------------------------------------------------------------------------
+// Linear pass: one thread per point, the track's rows streamed through the Givens QR in the row order of
+// tri_linear_kernel (per observation the u-row, then the v-row).  (Compiled with the default contraction, as
+// tri_linear_kernel is: the same expressions give the same instructions.)
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void tri_tracks_linear_kernel(TrackArgs a) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.n_pts) return;
+  const int beg = a.pt_ptr[p], end = a.pt_ptr[p + 1];
+  double x[4] = {0, 0, 0, 1};
+  if (a.xin[0]) {
+    x[0] = a.xin[0][p]; x[1] = a.xin[1][p]; x[2] = a.xin[2][p];
+    x[3] = a.xin[3] ? a.xin[3][p] : 1.0;
+  }
+  int flags = 0;
+  if (end - beg < 2) {
+    flags = SFM_TRACK_TOO_FEW;
+  } else {
+    double R[4][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    for (int o = beg; o < end; ++o) {
+      const double* P = a.projs + 12 * (size_t)a.cam_idx[o];
+      const double u = a.u[o], w = a.v[o];
+      dlt_add_row(R, u * P[8] - P[0], u * P[9] - P[1], u * P[10] - P[2], u * P[11] - P[3]);    // tri:145
+      dlt_add_row(R, w * P[8] - P[4], w * P[9] - P[5], w * P[10] - P[6], w * P[11] - P[7]);    // tri:146
+    }
+    double y[4];
+    dlt_null_vector(R, y);
+    if (isfinite(y[0]) && isfinite(y[1]) && isfinite(y[2]) && isfinite(y[3])) {
+      x[0] = y[0]; x[1] = y[1]; x[2] = y[2]; x[3] = y[3];
+    } else {
+      flags = SFM_TRACK_NONFINITE;
+    }
+  }
+  a.xout[0][p] = x[0]; a.xout[1][p] = x[1]; a.xout[2][p] = x[2];
+  if (a.xout[3]) a.xout[3][p] = x[3];
+  if (a.status) a.status[p] = flags;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Nonlinear pass.  Everything below is compiled WITHOUT automatic contraction and spells its FMAs out: the cached and
+// the re-reading instantiations then execute the same operations per observation, so a point's bits do not depend on
+// which of them the longest track of a call selects.
+// ---------------------------------------------------------------------------------------------
+#pragma clang fp contract(off)
+
+struct TrackSums { double a00, a10, a11, a20, a21, a22, b0, b1, b2, c; };
+
+__device__ __forceinline__ void track_project(const double* P, double x0, double x1, double x2, double x3, double* s) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    s[r] = __builtin_fma(P[4 * r + 3], x3, __builtin_fma(P[4 * r + 2], x2, __builtin_fma(P[4 * r + 1], x1, P[4 * r] * x0)));
+}
+
+// One observation of the linearisation: tri_nonlinear_kernel's `view` (tri:209-228, 261-269) plus the squared residual.
+// 97 flops (FMA = 2, v_rcp_f64 = 1): projection 21, reciprocal 7, iz^2 1, Jacobian 24, residual 4, sums 36, cost 4.
+__device__ __forceinline__ void track_view(const double* P, double ku, double kv, double x0, double x1, double x2, double x3,
+                                           TrackSums& S) {
+  double s[3], j[6];
+  track_project(P, x0, x1, x2, x3, s);
+  const double iz = rcp_nr(s[2]), iz2 = iz * iz;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    j[c] = __builtin_fma(-s[0], P[8 + c], s[2] * P[c]) * iz2;
+    j[3 + c] = __builtin_fma(-s[1], P[8 + c], s[2] * P[4 + c]) * iz2;
+  }
+  const double eu = __builtin_fma(s[0], iz, -ku);
+  const double ev = __builtin_fma(s[1], iz, -kv);
+  S.a00 = __builtin_fma(j[3], j[3], __builtin_fma(j[0], j[0], S.a00));
+  S.a10 = __builtin_fma(j[4], j[3], __builtin_fma(j[1], j[0], S.a10));
+  S.a11 = __builtin_fma(j[4], j[4], __builtin_fma(j[1], j[1], S.a11));
+  S.a20 = __builtin_fma(j[5], j[3], __builtin_fma(j[2], j[0], S.a20));
+  S.a21 = __builtin_fma(j[5], j[4], __builtin_fma(j[2], j[1], S.a21));
+  S.a22 = __builtin_fma(j[5], j[5], __builtin_fma(j[2], j[2], S.a22));
+  S.b0 = __builtin_fma(j[3], ev, __builtin_fma(j[0], eu, S.b0));
+  S.b1 = __builtin_fma(j[4], ev, __builtin_fma(j[1], eu, S.b1));
+  S.b2 = __builtin_fma(j[5], ev, __builtin_fma(j[2], eu, S.b2));
+  S.c = __builtin_fma(ev, ev, __builtin_fma(eu, eu, S.c));
+}
+
+// The residual alone (the evaluation after the last iteration): the same eu / ev as track_view, and s[2] <= 0.
+__device__ __forceinline__ void track_residual(const double* P, double ku, double kv, double x0, double x1, double x2,
+                                               double x3, double& c, double& behind) {
+  double s[3];
+  track_project(P, x0, x1, x2, x3, s);
+  const double iz = rcp_nr(s[2]);
+  const double eu = __builtin_fma(s[0], iz, -ku);
+  const double ev = __builtin_fma(s[1], iz, -kv);
+  c = __builtin_fma(ev, ev, __builtin_fma(eu, eu, c));
+  if (s[2] <= 0.0) behind += 1.0;
+}
+
+template <int G>
+__device__ __forceinline__ double track_gsum(double v) {
+  if constexpr (G == 1) return v;
+  else return group_sum<G>(v);
+}
+
+constexpr int kTrkLdsViews = 512;     // projections staged in LDS by the re-reading variant up to here (48 KB)
+
+// NC > 0: every lane keeps its (up to NC = 2, 4 or 6) observations -- u, v and the twelve projection entries -- in registers
+// for all iterations; the host selects the smallest NC with G * NC >= the longest track of the call.  (A slot is skipped
+// by a branch: computing every slot and selecting at the accumulation, to let the scheduler interleave the slots of a
+// lane, measured 20 % slower.)  NC == 0: any length, observations
+// re-read per iteration, projections from LDS (or through L2 beyond kTrkLdsViews cameras).
+template <int G, int NC>
+__global__ __launch_bounds__(256) void tri_tracks_nonlinear_kernel(TrackArgs a) {
+  extern __shared__ double lds_proj[];
+  if (NC == 0 && a.proj_in_lds) {
+    for (int i = threadIdx.x; i < a.n_views * 12; i += blockDim.x) lds_proj[i] = a.projs[i];
+    __syncthreads();
+  }
+  const double* P_all = (NC == 0 && a.proj_in_lds) ? lds_proj : a.projs;
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int p = (int)(t / G), lane = (int)(threadIdx.x % G);
+  if (p >= a.n_pts) return;               // whole groups leave together
+  const int beg = a.pt_ptr[p], end = a.pt_ptr[p + 1];
+  const double in0 = a.xin[0][p], in1 = a.xin[1][p], in2 = a.xin[2][p];
+  const double x3 = a.xin[3] ? a.xin[3][p] : 1.0;
+  double x0 = in0, x1 = in1, x2 = in2;
+  const bool eval = a.cost != nullptr || a.status != nullptr;
+  double cost0 = 0, cost1 = 0, behind = 0;
+  int flags = 0;
+
+  constexpr int NR = NC > 0 ? NC : 1;
+  double ku[NR], kv[NR], kP[NR][12];
+  if (NC > 0) {
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const int o = beg + lane + k * G;
+      ku[k] = 0; kv[k] = 0;
+#pragma unroll
+      for (int i = 0; i < 12; ++i) kP[k][i] = 0;
+      if (o < end) {
+        ku[k] = a.u[o]; kv[k] = a.v[o];
+        const double* P = a.projs + 12 * (size_t)a.cam_idx[o];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) kP[k][i] = P[i];
+      }
+    }
+  }
+
+  if (end > beg) {
+    for (int it = 0;; ++it) {
+      const bool last = it >= a.iters;
+      if (last && !eval) break;
+      TrackSums S = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+      double nb = 0;
+      if (NC > 0) {
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+          if (beg + lane + k * G < end) {
+            if (last) track_residual(kP[k], ku[k], kv[k], x0, x1, x2, x3, S.c, nb);
+            else track_view(kP[k], ku[k], kv[k], x0, x1, x2, x3, S);
+          }
+        }
+      } else {
+        for (int o = beg + lane; o < end; o += G) {
+          const double* P = P_all + 12 * (size_t)a.cam_idx[o];
+          if (last) track_residual(P, a.u[o], a.v[o], x0, x1, x2, x3, S.c, nb);
+          else track_view(P, a.u[o], a.v[o], x0, x1, x2, x3, S);
+        }
+      }
+      if (last) {
+        cost1 = track_gsum<G>(S.c);
+        behind = track_gsum<G>(nb);
+        if (it == 0) cost0 = cost1;
+        break;
+      }
+      if (it == 0 && eval) cost0 = track_gsum<G>(S.c);
+      const double a00 = track_gsum<G>(S.a00) + a.lambda, a10 = track_gsum<G>(S.a10), a11 = track_gsum<G>(S.a11) + a.lambda;
+      const double a20 = track_gsum<G>(S.a20), a21 = track_gsum<G>(S.a21), a22 = track_gsum<G>(S.a22) + a.lambda;
+      const double b0 = track_gsum<G>(S.b0), b1 = track_gsum<G>(S.b1), b2 = track_gsum<G>(S.b2);
+      // symmetric 3x3 inverse by adjugate (np.linalg.inv in the reference, tri:227)
+      const double c00 = a11 * a22 - a21 * a21;
+      const double c10 = a20 * a21 - a10 * a22;
+      const double c20 = a10 * a21 - a20 * a11;
+      const double det = a00 * c00 + a10 * c10 + a20 * c20;
+      const double id = rcp_nr(det);
+      const double c11 = a00 * a22 - a20 * a20;
+      const double c21 = a10 * a20 - a00 * a21;
+      const double c22 = a00 * a11 - a10 * a10;
+      const double d0 = (c00 * b0 + c10 * b1 + c20 * b2) * id;
+      const double d1 = (c10 * b0 + c11 * b1 + c21 * b2) * id;
+      const double d2 = (c20 * b0 + c21 * b1 + c22 * b2) * id;
+      if (det == 0.0 || !isfinite(d0) || !isfinite(d1) || !isfinite(d2)) {      // the same bits on every lane of the group
+        flags |= SFM_TRACK_NONFINITE;
+        x0 = in0; x1 = in1; x2 = in2;
+        it = a.iters - 1;                  // straight to the evaluation of the point as it came in
+        continue;
+      }
+      x0 -= d0; x1 -= d1; x2 -= d2;
+    }
+    if (eval && !(isfinite(cost0) && isfinite(cost1))) flags |= SFM_TRACK_NONFINITE;
+    if (behind > 0.0) flags |= SFM_TRACK_BEHIND;
+  }
+
+  if (lane != 0) return;
+  a.xout[0][p] = x0; a.xout[1][p] = x1; a.xout[2][p] = x2;
+  if (a.xout[3]) a.xout[3][p] = x3;
+  if (a.cost) { a.cost[p] = cost0; a.cost[(size_t)a.n_pts + p] = cost1; }
+  if (a.status) a.status[p] = a.status_or ? (a.status[p] | flags) : flags;
+}
+
+template <int G>
+static void launch_tracks_g(const TrackArgs& a, int nc, hipStream_t s) {
+  const long long threads = (long long)a.n_pts * G;
+  const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  if (nc == 2) tri_tracks_nonlinear_kernel<G, 2><<<grid, block, 0, s>>>(a);
+  else if (nc == 4) tri_tracks_nonlinear_kernel<G, 4><<<grid, block, 0, s>>>(a);
+  else if (nc == 6) tri_tracks_nonlinear_kernel<G, 6><<<grid, block, 0, s>>>(a);
+  else tri_tracks_nonlinear_kernel<G, 0><<<grid, block, a.proj_in_lds ? sizeof(double) * 12 * (size_t)a.n_views : 0, s>>>(a);
+}
+
+static bool tracks_group_ok(int g) { return g == 0 || g == 1 || g == 4 || g == 8 || g == 16 || g == 32 || g == 64; }
+
+// Automatic group width from n_pts, M and the longest track: the narrowest group whose lanes can
+// keep the longest track in registers (6 observations each), widened while the call is too small to give every SIMD
+// two waves and the wider group is still no wider than the longest track.
+static int tracks_pick_group(int n_pts, long long M, int max_track) {
+  (void)M;
+  static const int widths[6] = {1, 4, 8, 16, 32, 64};
+  int i = 0;
+  while (i < 5 && 6 * widths[i] < max_track) ++i;
+  const long long want_waves = 2LL * 4 * ctx().num_cus;
+  while (i < 5 && (long long)n_pts * widths[i] / 64 < want_waves && widths[i + 1] <= max_track) ++i;
+  return widths[i];
+}
+
+// Enqueue the requested passes on s.  The CSR has been validated; max_track is its longest track.
+static int tracks_enqueue(TrackArgs a, int mode, int group, long long M, int max_track, hipStream_t s) {
+  if (a.n_pts <= 0) return SFM_OK;
+  if (mode & SFM_TRACKS_LINEAR) {
+    tri_tracks_linear_kernel<<<(a.n_pts + 255) / 256, 256, 0, s>>>(a);
+    SFM_HIP(hipGetLastError());
+    for (int r = 0; r < 4; ++r) a.xin[r] = a.xout[r];      // the nonlinear pass starts from the DLT result
+    a.status_or = 1;
+  }
+  if (mode & SFM_TRACKS_NONLINEAR) {
+    const int g = group ? group : tracks_pick_group(a.n_pts, M, max_track);
+    const int nc = max_track <= 2 * g ? 2 : (max_track <= 4 * g ? 4 : (max_track <= 6 * g ? 6 : 0));
+    a.proj_in_lds = a.n_views <= kTrkLdsViews;
+    switch (g) {
+      case 1: launch_tracks_g<1>(a, nc, s); break;
+      case 4: launch_tracks_g<4>(a, nc, s); break;
+      case 8: launch_tracks_g<8>(a, nc, s); break;
+      case 16: launch_tracks_g<16>(a, nc, s); break;
+      case 32: launch_tracks_g<32>(a, nc, s); break;
+      default: launch_tracks_g<64>(a, nc, s); break;
+    }
+    SFM_HIP(hipGetLastError());
+  }
+  return SFM_OK;
+}
+
+static int tracks_check_args(const char* who, int n_pts, int n_views, long long M, int mode, int iters, int group) {
+  if (n_pts < 0 || n_views < 1 || M < 0 || M > INT_MAX || iters < 0) {
+    set_error("%s: bad sizes n_pts=%d n_views=%d M=%lld iters=%d", who, n_pts, n_views, M, iters);
+    return SFM_E_SHAPE;
+  }
+  if (mode < 1 || mode > (SFM_TRACKS_LINEAR | SFM_TRACKS_NONLINEAR)) { set_error("%s: bad mode %d", who, mode); return SFM_E_SHAPE; }
+  if (!tracks_group_ok(group)) { set_error("%s: group %d is not one of 0, 1, 4, 8, 16, 32, 64", who, group); return SFM_E_SHAPE; }
+  return SFM_OK;
+}
+
+// Validate the CSR on the device (the way ba_structure_kernel does) and wait for the verdict.
+static int tracks_validate(const char* who, int n_pts, int n_views, long long M, const int* d_pt_ptr, const int* d_cam_idx,
+                           int* max_track, hipStream_t s) {
+  DevBuf<int> dInfo;
+  SFM_TRY(dInfo.alloc(4, s));
+  SFM_HIP(hipMemsetAsync(dInfo.p, 0, 4 * sizeof(int), s));
+  tracks_check_kernel<<<(n_pts + 255) / 256, 256, 0, s>>>(n_pts, n_views, M, d_pt_ptr, d_cam_idx, dInfo.p);
+  SFM_HIP(hipGetLastError());
+  int info[4] = {0, 0, 0, 0};
+  SFM_TRY(dInfo.download(info, 4, s));
+  SFM_TRY(stream_sync(s));
+  *max_track = info[2];
+  switch (info[0]) {
+    case 0: return SFM_OK;
+    case kTrkPtr0: set_error("%s: pt_ptr[0] is not 0", who); break;
+    case kTrkMonotone: set_error("%s: pt_ptr not monotone at point %d", who, info[1]); break;
+    case kTrkEnd: set_error("%s: pt_ptr[%d] is not M = %lld", who, info[1], M); break;
+    default: set_error("%s: cam_idx[%d] out of range", who, info[1]); break;
+  }
+  return SFM_E_SHAPE;
+}
+
+static TrackArgs tracks_args(int n_pts, int n_views, long long M, const int* pt_ptr, const int* cam_idx, const double* uv,
+                             const double* projs, double lambda, int iters, const double* X_init, double* X_out, double* cost,
+                             int* status) {
+  TrackArgs a = {};
+  a.n_pts = n_pts; a.n_views = n_views;
+  a.pt_ptr = pt_ptr; a.cam_idx = cam_idx;
+  a.u = uv; a.v = uv + M;
+  a.projs = projs;
+  for (int r = 0; r < 4; ++r) {
+    a.xin[r] = X_init ? X_init + (size_t)r * n_pts : nullptr;
+    a.xout[r] = X_out + (size_t)r * n_pts;
+  }
+  a.lambda = lambda; a.iters = iters;
+  a.cost = cost; a.status = status;
+  return a;
+}
+
+}  // namespace sfm
+
+using namespace sfm;
+
+extern "C" {
+
+int sfm_tri_tracks_auto_group(int n_pts, int64_t M, int max_track) { return tracks_pick_group(n_pts, M, max_track); }
+
+int sfm_tri_tracks_dev(int n_pts, int n_views, int64_t M, const int* d_pt_ptr, const int* d_cam_idx, const double* d_uv,
+                       const double* d_projs, int mode, double lambda, int iters, int group, const double* d_X_init,
+                       double* d_X_out, double* d_cost, int* d_status, void* hip_stream) {
+  SFM_TRY(ensure_init());
+  SFM_TRY(tracks_check_args("sfm_tri_tracks_dev", n_pts, n_views, M, mode, iters, group));
+  if (!(mode & SFM_TRACKS_LINEAR) && d_X_init == nullptr && n_pts > 0) {
+    set_error("sfm_tri_tracks_dev: X_init is required without SFM_TRACKS_LINEAR");
+    return SFM_E_SHAPE;
+  }
+  if (n_pts == 0) return SFM_OK;
+  if (!d_pt_ptr || !d_projs || !d_X_out || (M > 0 && (!d_cam_idx || !d_uv))) {
+    set_error("sfm_tri_tracks_dev: null device pointer");
+    return SFM_E_SHAPE;
+  }
+  hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx().stream;
+  int max_track = 0;
+  SFM_TRY(tracks_validate("sfm_tri_tracks_dev", n_pts, n_views, M, d_pt_ptr, d_cam_idx, &max_track, s));
+  const TrackArgs a = tracks_args(n_pts, n_views, M, d_pt_ptr, d_cam_idx, d_uv, d_projs, lambda, iters, d_X_init, d_X_out,
+                                  d_cost, d_status);
+  return tracks_enqueue(a, mode, group, M, max_track, s);
+}
+
+int sfm_tri_tracks(int n_pts, int n_views, int64_t M, const int* pt_ptr, const int* cam_idx, const double* uv,
+                   const double* projs, int mode, double lambda, int iters, int group, const double* X_init, double* X_out,
+                   double* cost, int* status) {
+  SFM_TRY(ensure_init());
+  SFM_TRY(tracks_check_args("sfm_tri_tracks", n_pts, n_views, M, mode, iters, group));
+  if (!(mode & SFM_TRACKS_LINEAR) && X_init == nullptr && n_pts > 0) {
+    set_error("sfm_tri_tracks: X_init is required without SFM_TRACKS_LINEAR");
+    return SFM_E_SHAPE;
+  }
+  if (n_pts == 0) return SFM_OK;
+  if (!pt_ptr || !projs || !X_out || (M > 0 && (!cam_idx || !uv))) { set_error("sfm_tri_tracks: null pointer"); return SFM_E_SHAPE; }
+  hipStream_t s = ctx().stream;
+  DevBuf<int> dPtr, dCam, dSt;
+  DevBuf<double> dUV, dP, dX, dO, dC;
+  SFM_TRY(dPtr.upload(pt_ptr, (size_t)n_pts + 1, s));
+  SFM_TRY(dCam.upload(cam_idx, (size_t)M, s));
+  SFM_TRY(dUV.upload(uv, 2 * (size_t)M, s));
+  SFM_TRY(dP.upload(projs, 12 * (size_t)n_views, s));
+  if (X_init) SFM_TRY(dX.upload(X_init, 4 * (size_t)n_pts, s));
+  SFM_TRY(dO.alloc(4 * (size_t)n_pts, s));
+  if (cost) SFM_TRY(dC.alloc(2 * (size_t)n_pts, s));
+  if (status) SFM_TRY(dSt.alloc((size_t)n_pts, s));
+  int max_track = 0;
+  SFM_TRY(tracks_validate("sfm_tri_tracks", n_pts, n_views, M, dPtr.p, dCam.p, &max_track, s));
+  const TrackArgs a = tracks_args(n_pts, n_views, M, dPtr.p, dCam.p, dUV.p, dP.p, lambda, iters, X_init ? dX.p : nullptr, dO.p,
+                                  cost ? dC.p : nullptr, status ? dSt.p : nullptr);
+  SFM_TRY(tracks_enqueue(a, mode, group, M, max_track, s));
+  SFM_TRY(dO.download(X_out, 4 * (size_t)n_pts, s));
+  if (cost) SFM_TRY(dC.download(cost, 2 * (size_t)n_pts, s));
+  if (status) SFM_TRY(dSt.download(status, (size_t)n_pts, s));
+  return stream_sync(s);
+}
+
+int sfm_ba_refine_points(sfm_ba_problem* p, int mode, double lambda, int iters, int group, double* cost, int* status) {
+  if (p == nullptr || p->magic != kBaMagic) {
+    set_error("invalid bundle-adjustment problem handle");
+    return SFM_E_HANDLE;
+  }
+  BaDev& d = p->dev;
+  SFM_TRY(tracks_check_args("sfm_ba_refine_points", d.N, d.V > 0 ? d.V : 1, d.M, mode, iters, group));
+  SFM_TRY(ba_flush(p));                                  // a deferred back substitution still owes the points its update
+  if (d.N == 0 || d.M == 0) return SFM_OK;
+  hipStream_t s = p->stream;
+  if (!p->prep_valid) SFM_TRY(ba_enqueue_prep(p));       // the expanded cameras the linearisation reads
+  DevBuf<double> dP, dC;
+  DevBuf<int> dSt;
+  SFM_TRY(dP.alloc(12 * (size_t)d.V, s));
+  tracks_proj_from_prep_kernel<<<(12 * d.V + 255) / 256, 256, 0, s>>>(d.V, d.prep[p->cur], dP.p);
+  SFM_HIP(hipGetLastError());
+  if (cost) SFM_TRY(dC.alloc(2 * (size_t)d.N, s));
+  if (status) SFM_TRY(dSt.alloc((size_t)d.N, s));
+  TrackArgs a = {};
+  a.n_pts = d.N; a.n_views = d.V;
+  a.pt_ptr = d.pt_ptr; a.cam_idx = d.cam_idx; a.u = d.u; a.v = d.v;
+  a.projs = dP.p;
+  a.xin[0] = d.px; a.xin[1] = d.py; a.xin[2] = d.pz; a.xin[3] = nullptr;      // W = 1
+  a.xout[0] = d.px; a.xout[1] = d.py; a.xout[2] = d.pz; a.xout[3] = nullptr;
+  a.lambda = lambda; a.iters = iters;
+  a.cost = cost ? dC.p : nullptr; a.status = status ? dSt.p : nullptr;
+  SFM_TRY(tracks_enqueue(a, mode, group, d.M, p->max_track, s));
+  // new points start a new cost history, as sfm_ba_set_points does
+  SFM_HIP(hipMemsetAsync(d.cost, 0, kStatSlots * sizeof(double), s));
+  SFM_HIP(hipMemsetAsync(d.iter_count, 0, sizeof(int), s));
+  int st[2] = {0, 0};
+  SFM_HIP(hipMemcpyAsync(st, d.status, sizeof(st), hipMemcpyDeviceToHost, s));
+  if (cost) SFM_TRY(dC.download(cost, 2 * (size_t)d.N, s));
+  if (status) SFM_TRY(dSt.download(status, (size_t)d.N, s));
+  SFM_TRY(stream_sync(s));
+  if (st[0] != SFM_OK) {
+    set_error("sfm_ba_refine_points: camera %d is invalid (status %d)", st[1], st[0]);
+    return st[0];
+  }
+  return SFM_OK;
+}
+
+}  // extern "C"

@@ -33,6 +33,9 @@ TRACK_INFO_N_VIEWS, TRACK_INFO_N_KEYS, TRACK_INFO_N_ROWS, TRACK_INFO_UPLOAD_BYTE
 TRACK_INFO_OBS_VIEWS, TRACK_INFO_OBS_PTS, TRACK_INFO_N_OBS = 6, 7, 8
 TRACK_OK, TRACK_NO_SECOND, TRACK_ZERO_SECOND, TRACK_BAD_TRAIN = 0, 1, 2, 3
 SYNC_REUSE, SYNC_GROWN, SYNC_REPLACED = 0, 1, 2
+TRACKS_LINEAR, TRACKS_NONLINEAR = 1, 2
+TRACK_TOO_FEW, TRACK_NONFINITE, TRACK_BEHIND = 1, 2, 4
+TRACK_GROUPS = (0, 1, 4, 8, 16, 32, 64)
 
 # every symbol include/sfm_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -61,6 +64,7 @@ EXPORTS = (
     "sfm_track_constructed", "sfm_track_unconstructed", "sfm_track_copy_table", "sfm_track_copy_row",
     "sfm_obs_set_normalised", "sfm_obs_build", "sfm_obs_copy",
     "sfm_ba_create_from_tracks", "sfm_ba_sync_tracks", "sfm_ba_get_structure",
+    "sfm_tri_tracks", "sfm_tri_tracks_dev", "sfm_ba_refine_points", "sfm_tri_tracks_auto_group",
 )
 
 _lib = None
@@ -192,6 +196,10 @@ def load():
     lib.sfm_ba_create_from_tracks.argtypes = [vp, ctypes.POINTER(vp)]
     lib.sfm_ba_sync_tracks.argtypes = [vp, vp, ci, _dp, ci, _dp, _ip, ctypes.POINTER(ctypes.c_int64)]
     lib.sfm_ba_get_structure.argtypes = [vp, _ip, _ip, _dp]
+    lib.sfm_tri_tracks.argtypes = [ci, ci, ctypes.c_int64, _ip, _ip, _dp, _dp, ci, ctypes.c_double, ci, ci, _dp, _dp, _dp, _ip]
+    lib.sfm_tri_tracks_dev.argtypes = [ci, ci, ctypes.c_int64, vp, vp, vp, vp, ci, ctypes.c_double, ci, ci, vp, vp, vp, vp, vp]
+    lib.sfm_ba_refine_points.argtypes = [vp, ci, ctypes.c_double, ci, ci, _dp, _ip]
+    lib.sfm_tri_tracks_auto_group.argtypes = [ci, ctypes.c_int64, ci]
     _lib = lib
     return lib
 
@@ -370,6 +378,68 @@ def triangulate(projs, uv, lam, iters):
     out = np.empty((4, m))
     check(load().sfm_triangulate(m, nv, dptr(projs), dptr(uv), float(lam), int(iters), dptr(out)))
     return out
+
+
+def _tracks_mode_group(mode, iters, group):
+    mode, iters, group = int(mode), int(iters), int(group)
+    if mode not in (TRACKS_LINEAR, TRACKS_NONLINEAR, TRACKS_LINEAR | TRACKS_NONLINEAR):
+        raise ValueError("mode must be TRACKS_LINEAR, TRACKS_NONLINEAR or both, got %d" % mode)
+    if group not in TRACK_GROUPS:
+        raise ValueError("group must be one of %s, got %d" % (TRACK_GROUPS, group))
+    if iters < 0:
+        raise ValueError("iters must be >= 0")
+    return mode, iters, group
+
+
+def check_tracks(pt_ptr, cam_idx, uv, projs, x_init, mode, iters, group):
+    """Shapes and dtypes of a ``tri_tracks`` call, without a device: returns the converted arrays or raises ValueError."""
+    mode, iters, group = _tracks_mode_group(mode, iters, group)
+    for name, arr in (("pt_ptr", pt_ptr), ("cam_idx", cam_idx)):
+        if not np.issubdtype(np.asarray(arr).dtype, np.integer):
+            raise ValueError("%s must be an integer array" % name)
+    pt_ptr = i32(pt_ptr); cam_idx = i32(cam_idx); uv = f64(uv); projs = f64(projs)
+    if pt_ptr.ndim != 1 or pt_ptr.shape[0] < 1 or cam_idx.ndim != 1:
+        raise ValueError("pt_ptr must be (n_pts + 1,) and cam_idx (M,)")
+    n_pts, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
+    if uv.shape != (2, n_obs):
+        raise ValueError("uv must be (2, M) with M = %d, got %s" % (n_obs, uv.shape))
+    if projs.ndim != 3 or projs.shape[0] < 1 or projs.shape[1:] != (3, 4):
+        raise ValueError("projs must be (n_views, 3, 4), got %s" % (projs.shape,))
+    if pt_ptr[0] != 0 or pt_ptr[-1] != n_obs:
+        raise ValueError("pt_ptr must start at 0 and end at M = %d, got %d .. %d" % (n_obs, pt_ptr[0], pt_ptr[-1]))
+    if x_init is None:
+        if not mode & TRACKS_LINEAR:
+            raise ValueError("X_init is required without TRACKS_LINEAR")
+    else:
+        x_init = f64(x_init)
+        if x_init.shape != (4, n_pts):
+            raise ValueError("X_init must be (4, n_pts) with n_pts = %d, got %s" % (n_pts, x_init.shape))
+    return pt_ptr, cam_idx, uv, projs, x_init, mode, iters, group
+
+
+def tri_tracks(pt_ptr, cam_idx, uv, projs, X_init=None, mode=TRACKS_NONLINEAR, lam=0.5, iters=100, group=0):
+    """Triangulate / refine every point from its own track (sfm_tri_tracks): pt_ptr (n+1,), cam_idx (M,), uv (2, M),
+    projs (V, 3, 4), X_init (4, n) or None with TRACKS_LINEAR -> (X (4, n), cost (2, n), status (n,) of TRACK_* bits)."""
+    pt_ptr, cam_idx, uv, projs, x_init, mode, iters, group = check_tracks(pt_ptr, cam_idx, uv, projs, X_init, mode, iters, group)
+    n_pts, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
+    out = np.zeros((4, n_pts)); cost = np.zeros((2, n_pts)); status = np.zeros(n_pts, dtype=np.int32)
+    check(load().sfm_tri_tracks(n_pts, projs.shape[0], n_obs, iptr(pt_ptr), iptr(cam_idx) if n_obs else None,
+                                dptr(uv) if n_obs else None, dptr(projs), mode, float(lam), iters, group,
+                                dptr(x_init) if x_init is not None else None, dptr(out), dptr(cost), iptr(status)))
+    return out, cost, status
+
+
+def tracks_auto_group(n_pts, n_obs, max_track):
+    """The lane-group width ``group=0`` selects for a call of these sizes (sfm_tri_tracks_auto_group; host only)."""
+    return int(load().sfm_tri_tracks_auto_group(int(n_pts), int(n_obs), int(max_track)))
+
+
+def tri_tracks_dev(n_pts, n_views, n_obs, d_pt_ptr, d_cam_idx, d_uv, d_projs, mode, lam, iters, group, d_x_init, d_x_out,
+                   d_cost=0, d_status=0, stream=0):
+    mode, iters, group = _tracks_mode_group(mode, iters, group)
+    check(load().sfm_tri_tracks_dev(int(n_pts), int(n_views), int(n_obs), _vp(d_pt_ptr), _vp(d_cam_idx), _vp(d_uv), _vp(d_projs),
+                                    mode, float(lam), iters, group, _vp(d_x_init), _vp(d_x_out), _vp(d_cost), _vp(d_status),
+                                    _vp(stream)))
 
 
 def pnp_nonlinear(uv_pix, pts_h, intrinsic, rot0, loc0, lam, iters, quirks=QUIRKS_REFERENCE):
@@ -771,6 +841,18 @@ class BaProblem:
         self.n_cams += cams_new.shape[0]
         self.n_pts += pts_new.shape[1]
         self.n_obs += obs_cam.shape[0]
+
+    def refine_points(self, lam, iters, mode=TRACKS_NONLINEAR, group=0, want_outputs=True):
+        """Structure-only refinement of the resident points, cameras held (sfm_ba_refine_points): returns
+        (cost (2, N), status (N,)) as ``tri_tracks`` does; ``want_outputs=False`` downloads neither and returns None."""
+        mode, iters, group = _tracks_mode_group(mode, iters, group)
+        n = self.info(INFO_N_PTS)
+        if not want_outputs:
+            check(self._lib.sfm_ba_refine_points(self._h, mode, float(lam), iters, group, None, None))
+            return None
+        cost = np.zeros((2, n)); status = np.zeros(n, dtype=np.int32)
+        check(self._lib.sfm_ba_refine_points(self._h, mode, float(lam), iters, group, dptr(cost), iptr(status)))
+        return cost, status
 
     def points_ptr(self):
         """Device pointers (px, py, pz) of the resident points and their count (sfm_ba_points_ptr)."""

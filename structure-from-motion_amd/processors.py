@@ -85,6 +85,20 @@ class HipTriangulationMixin:
         uv, projs_arr = self._pack_views(projs, matched_pairs)
         return native.triangulate(projs_arr, uv, damping_factor, iteration)
 
+    def triangulate_tracks(self, projs, pt_ptr, cam_idx, uv, init_3d_pts=None, damping_factor=None, iteration=None):
+        """Every point from its OWN views (no reference counterpart: the reference triangulates rectangular batches only).
+        Point i owns observations ``pt_ptr[i]:pt_ptr[i+1]`` of ``cam_idx`` (index into ``projs``) / ``uv`` (2, M), in the
+        coordinates of ``projs``.  Linear then nonlinear when ``init_3d_pts`` is None, else nonlinear from it; returns the
+        (4, n) points.  Per-point cost and status are ``native.tri_tracks``'s."""
+        if not damping_factor:
+            damping_factor = self.damping_factor
+        if not iteration:
+            iteration = self.iteration
+        projs_arr = np.stack([np.asarray(p, dtype=np.float64).reshape(3, 4) for p in projs])
+        mode = native.TRACKS_NONLINEAR if init_3d_pts is not None else native.TRACKS_LINEAR | native.TRACKS_NONLINEAR
+        out, _cost, _status = native.tri_tracks(pt_ptr, cam_idx, uv, projs_arr, init_3d_pts, mode, damping_factor, iteration)
+        return out
+
     @staticmethod
     def _pack_views(projs, matched_pairs):
         num_views = len(matched_pairs)
@@ -346,6 +360,7 @@ class _ResidentScene:
         self.n_views_before = 0
         self.from_device = False  # the structure came from the tracker's device tables (ba_device_tracks): the host picture above is not kept
         self.retired_bytes = 0    # upload bytes of problems this scene has replaced
+        self.cams_synced = False  # the device cameras are the views' poses as the last update left them (no iteration since)
 
     def close(self):
         if self.prob is not None:
@@ -512,6 +527,77 @@ class HipBaMixin:
         scene.n_pts = tri_num
         return scene
 
+    def _ba_update_resident(self, views, init_rots, init_locs, init_tri_pts):
+        """Bring the resident scene up to the caller's views, track tables and points (structure, cameras, points), uploading
+        only what is new or changed; returns it.  On a failure the resident copy is dropped."""
+        view_num, tri_num = len(views), init_tri_pts.shape[1]
+        scene = self.__dict__.get("_hip_scene")
+        # cameras the caller did not touch since the last write-back: their quaternion q(R(q)) (ba:285-288 after
+        # ba:412) is re-derived on the device; only changed or new views are packed on the host and uploaded
+        n_same = 0
+        if scene is not None and scene.prob is not None and scene.rots_written is not None:
+            n_old = min(scene.rots_written.shape[0], view_num)
+            if np.array_equal(init_rots[:n_old], scene.rots_written[:n_old]) and np.array_equal(init_locs[:n_old], scene.locs_written[:n_old]):
+                n_same = n_old
+        new_cams = pack_cameras(init_rots[n_same:], init_locs[n_same:]) if n_same < view_num else np.zeros((0, 7))
+        scene = self._ba_sync_structure(views, tri_num, n_same, new_cams, init_tri_pts)
+        prob = scene.prob
+        try:
+            if self.ba_last_action == "create":
+                prob.set_cameras(pack_cameras(init_rots, init_locs) if n_same else new_cams)
+                prob.set_points(0, init_tri_pts)
+            else:
+                if n_same == view_num or (self.ba_last_action == "append" and n_same == scene.n_views_before):
+                    if not scene.cams_synced:                     # (refine_structure has left them re-derived already)
+                        prob.rederive_quaternions(0, n_same)      # appended cameras went up with sfm_ba_append
+                else:
+                    cams_all = pack_cameras(init_rots, init_locs) if n_same else new_cams
+                    prob.set_cameras(cams_all)
+                # points the caller did not touch since the last write-back are already on the device (bit for
+                # bit what get_state returned); appended points went up with sfm_ba_append
+                done = 0 if scene.pts_written is None else min(scene.pts_written.shape[1], tri_num)
+                if scene.pts_written is None:
+                    prob.set_points(0, init_tri_pts)          # no record of what the device holds: upload everything
+                elif done and not np.array_equal(init_tri_pts[:, :done], scene.pts_written[:, :done]):
+                    prob.set_points(0, init_tri_pts[:, :done])
+        except Exception:
+            self.ba_release()
+            raise
+        scene.cams_synced = True
+        return scene
+
+    def refine_structure(self, damping_factor=None, iteration=None, relinearize=False):
+        """Structure-only refinement of the resident scene: every point from all its observations with the cameras held
+        (``BaProblem.refine_points``), after the scene has been brought up to date exactly as ``execute_bundle_adjustment``
+        does.  ``relinearize`` runs the DLT over each track first.  Writes ``tri_processor.tri_pts[0:3]`` in place, leaves
+        the views alone and returns ``(cost (2, N), status (N,))``.  It is triangulation: falsy ``damping_factor`` /
+        ``iteration`` fall back to ``tri_processor``'s.  Needs ``ba_resident``; nothing in ``process()`` calls it."""
+        if not self.ba_resident:
+            raise TypeError("refine_structure needs ba_resident")
+        if self.ba_device_tracks:
+            self._ba_check_device_tracks()
+        if not damping_factor:
+            damping_factor = self.tri_processor.damping_factor
+        if not iteration:
+            iteration = self.tri_processor.iteration
+        views = self.view_processor.view_list
+        tri_pts = self.tri_processor.tri_pts
+        init_rots = np.stack([np.asarray(v.rot, dtype=np.float64) for v in views])
+        init_locs = np.stack([np.asarray(v.loc, dtype=np.float64).reshape(3) for v in views])
+        init_tri_pts = np.ascontiguousarray(tri_pts[0:3, :], dtype=np.float64)
+        scene = self._ba_update_resident(views, init_rots, init_locs, init_tri_pts)
+        mode = native.TRACKS_NONLINEAR | (native.TRACKS_LINEAR if relinearize else 0)
+        try:
+            cost, status = scene.prob.refine_points(damping_factor, iteration, mode)
+            _cams, pts = scene.prob.get_state()
+        except Exception:
+            self.ba_release()
+            raise
+        scene.pts_written = pts
+        scene.rots_written, scene.locs_written = init_rots, init_locs      # the poses the device cameras were brought up to
+        tri_pts[0:3, :] = pts
+        return cost, status
+
     def execute_bundle_adjustment(self):
         if self.ba_device_tracks:
             self._ba_check_device_tracks()
@@ -524,34 +610,10 @@ class HipBaMixin:
         init_tri_pts = np.ascontiguousarray(tri_pts[0:3, :], dtype=np.float64)                          # ba:292-294
 
         if self.ba_resident:
-            scene = self.__dict__.get("_hip_scene")
-            # cameras the caller did not touch since the last write-back: their quaternion q(R(q)) (ba:285-288 after
-            # ba:412) is re-derived on the device; only changed or new views are packed on the host and uploaded
-            n_same = 0
-            if scene is not None and scene.prob is not None and scene.rots_written is not None:
-                n_old = min(scene.rots_written.shape[0], view_num)
-                if np.array_equal(init_rots[:n_old], scene.rots_written[:n_old]) and np.array_equal(init_locs[:n_old], scene.locs_written[:n_old]):
-                    n_same = n_old
-            new_cams = pack_cameras(init_rots[n_same:], init_locs[n_same:]) if n_same < view_num else np.zeros((0, 7))
-            scene = self._ba_sync_structure(views, tri_num, n_same, new_cams, init_tri_pts)
+            scene = self._ba_update_resident(views, init_rots, init_locs, init_tri_pts)
             prob = scene.prob
             try:
-                if self.ba_last_action == "create":
-                    prob.set_cameras(pack_cameras(init_rots, init_locs) if n_same else new_cams)
-                    prob.set_points(0, init_tri_pts)
-                else:
-                    if n_same == view_num or (self.ba_last_action == "append" and n_same == scene.n_views_before):
-                        prob.rederive_quaternions(0, n_same)          # appended cameras went up with sfm_ba_append
-                    else:
-                        cams_all = pack_cameras(init_rots, init_locs) if n_same else new_cams
-                        prob.set_cameras(cams_all)
-                    # points the caller did not touch since the last write-back are already on the device (bit for
-                    # bit what get_state returned); appended points went up with sfm_ba_append
-                    done = 0 if scene.pts_written is None else min(scene.pts_written.shape[1], tri_num)
-                    if scene.pts_written is None:
-                        prob.set_points(0, init_tri_pts)          # no record of what the device holds: upload everything
-                    elif done and not np.array_equal(init_tri_pts[:, :done], scene.pts_written[:, :done]):
-                        prob.set_points(0, init_tri_pts[:, :done])
+                scene.cams_synced = False
                 prob.iterate(self.damping_factor, self.iteration, self.ba_quirk_flags)
                 cams, pts, rots = prob.get_state_rot()                                             # ba:412 (validated on the device)
             except Exception:
