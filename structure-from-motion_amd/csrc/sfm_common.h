@@ -54,6 +54,9 @@ struct PendingWork { bool dirty = false; hipStream_t stream = nullptr; };
 PendingWork& pending_work();
 int stream_sync(hipStream_t s);
 
+// The split-PnP workspaces (sfm_core.hip) live until sfm_shutdown, which releases them before the pool.
+void pnp_split_release();
+
 // RAII device buffer for the host-pointer convenience entry points.
 template <typename T>
 struct DevBuf {

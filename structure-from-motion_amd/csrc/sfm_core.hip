@@ -1,300 +1,17 @@
-// sfm_core.hip — library context + unit-level hooks + the per-point nonlinear triangulation kernel
-// and the per-view nonlinear PnP kernel (gfx950).
+// sfm_core.hip — unit-level hooks + the triangulation kernels (per-point DLT and nonlinear refinement) and the PnP
+// kernels (six-point RANSAC hypotheses, per-view nonlinear refinement) with their entry points (gfx950).  The library
+// context and the device-memory pool are in sfm_runtime.hip.
 //
 //   tri_nonlinear_kernel  <-> TriangulationProcessor.nonlinear_triangulate (triangulation_processor.py:160-234)
 //   pnp_nonlinear_kernel  <-> CamposeProcessor.nonlinear_estimate_cam_pose_pnp (campose_processor.py:308-459)
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <unordered_map>
 #include <vector>
 
 #include "sfm_common.h"
 #include "sfm_dlt.h"
 
 namespace sfm {
-
-// ---------------------------------------------------------------------------------------------
-// context
-// ---------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-
-Context& ctx() {
-  static Context c;
-  return c;
-}
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-int hip_fail(hipError_t e, const char* what, int line) {
-  set_error("HIP error '%s' in %s (line %d)", hipGetErrorString(e), what, line);
-  return SFM_E_HIP;
-}
-
-PendingWork& pending_work() {
-  static thread_local PendingWork w;
-  return w;
-}
-
-int stream_sync(hipStream_t s) {
-  SFM_HIP(hipStreamSynchronize(s));
-  PendingWork& w = pending_work();
-  if (w.stream == s || w.stream == nullptr) w.dirty = false;
-  return SFM_OK;
-}
-
-int ensure_init() {
-  if (ctx().inited) return SFM_OK;
-  return sfm_init(0);
-}
-
-// ---------------------------------------------------------------------------------------------
-// device-memory pool (see sfm_common.h)
-//
-// Three process-wide modes, chosen by the environment at first use:
-//   default            blocks rounded up to a power of two, cached per size class.  NO slack behind a buffer: a read past
-//                      the end is not made harmless by construction (SFM_POOL_SLACK=<bytes> adds that many bytes behind
-//                      every block -- a field switch for a suspected stray read, never set by the tests).
-//   SFM_POOL_REDZONE=1 every buffer between two 4 KB zones of 0xA5, checked when it returns to the pool: an out-of-bounds
-//                      WRITE aborts with a message.
-//   SFM_POOL_GUARD=1   every buffer is its own virtual-memory mapping (hipMemAddressReserve / hipMemCreate / hipMemMap)
-//                      that ENDS (to 16 bytes) where the buffer ends, followed by a reserved, never mapped granule: an
-//                      out-of-bounds READ or write past the end faults at the access instead of landing in a neighbour.
-//                      No caching (every free unmaps).  For one test pass on the GPU box.
-// ---------------------------------------------------------------------------------------------
-namespace {
-struct Block { void* base; size_t size; size_t bytes; hipMemGenericAllocationHandle_t handle; size_t mapped; };
-struct Pool {
-  std::mutex mu;
-  std::unordered_map<void*, Block> live;                  // pointer handed out -> its block
-  std::unordered_map<size_t, std::vector<void*>> free_by_size;   // rounded size -> cached block bases
-  size_t cached_bytes = 0;
-  long long guard_allocs = 0;
-  size_t guard_reserved = 0;      // address space guard mode has reserved (never returned)
-};
-Pool& pool() {
-  static Pool p;
-  return p;
-}
-size_t round_up_pow2(size_t n) {
-  size_t r = 256;
-  while (r < n) r <<= 1;
-  return r;
-}
-constexpr size_t kPoolCap = (size_t)2 << 30;
-constexpr size_t kRedZone = 4096;
-bool env_is_one(const char* name) {
-  const char* e = std::getenv(name);
-  return e && e[0] == '1';
-}
-bool redzone_on() {
-  static const bool on = env_is_one("SFM_POOL_REDZONE");
-  return on;
-}
-bool guard_on() {
-  static const bool on = env_is_one("SFM_POOL_GUARD");
-  return on;
-}
-size_t slack_bytes() {
-  static const size_t n = [] { const char* e = std::getenv("SFM_POOL_SLACK"); return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)0; }();
-  return n;
-}
-void redzone_fill(const Block& b, void* user) {
-  char* base = static_cast<char*>(b.base);
-  char* end = static_cast<char*>(user) + b.bytes;
-  (void)hipMemset(base, 0xA5, kRedZone);
-  (void)hipMemset(end, 0xA5, (size_t)(base + b.size - end));
-}
-void redzone_check(const Block& b, void* user) {
-  (void)hipDeviceSynchronize();
-  char* base = static_cast<char*>(b.base);
-  char* end = static_cast<char*>(user) + b.bytes;
-  const size_t tail = (size_t)(base + b.size - end);
-  std::vector<unsigned char> h(std::max(kRedZone, tail));
-  auto scan = [&](const char* what, const char* dev, size_t n) {
-    (void)hipMemcpy(h.data(), dev, n, hipMemcpyDeviceToHost);
-    for (size_t i = 0; i < n; ++i)
-      if (h[i] != 0xA5) {
-        std::fprintf(stderr, "sfm pool red zone: a kernel wrote %s a %zu-byte buffer (offset %zu of the zone)\n", what, b.bytes, i);
-        std::abort();
-      }
-  };
-  scan("BEFORE", base, kRedZone);
-  scan("PAST THE END OF", end, tail);
-}
-
-// ---- guard mode --------------------------------------------------------------------------------
-size_t guard_granularity(int device) {
-  static size_t g = 0;
-  if (g) return g;
-  hipMemAllocationProp prop{};
-  prop.type = hipMemAllocationTypePinned;
-  prop.location.type = hipMemLocationTypeDevice;
-  prop.location.id = device;
-  size_t gran = 0;
-  if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityMinimum) != hipSuccess || gran == 0) gran = (size_t)2 << 20;
-  g = gran;
-  return g;
-}
-hipError_t guard_alloc(void** ptr, size_t bytes, Block* out) {
-  const int device = ctx().device < 0 ? 0 : ctx().device;
-  const size_t gran = guard_granularity(device);
-  const size_t need = (std::max<size_t>(bytes, 1) + 15) & ~(size_t)15;      // vector loads are at most 16 bytes wide
-  const size_t mapped = (need + gran - 1) / gran * gran;
-  void* base = nullptr;
-  hipError_t e = hipMemAddressReserve(&base, mapped + gran, gran, nullptr, 0);      // + one granule that is never mapped
-  if (e != hipSuccess) return e;
-  hipMemAllocationProp prop{};
-  prop.type = hipMemAllocationTypePinned;
-  prop.location.type = hipMemLocationTypeDevice;
-  prop.location.id = device;
-  hipMemGenericAllocationHandle_t h{};
-  e = hipMemCreate(&h, mapped, &prop, 0);
-  if (e != hipSuccess) { (void)hipMemAddressFree(base, mapped + gran); return e; }
-  e = hipMemMap(base, mapped, 0, h, 0);
-  if (e != hipSuccess) { (void)hipMemRelease(h); (void)hipMemAddressFree(base, mapped + gran); return e; }
-  hipMemAccessDesc acc{};
-  acc.location.type = hipMemLocationTypeDevice;
-  acc.location.id = device;
-  acc.flags = hipMemAccessFlagsProtReadWrite;
-  e = hipMemSetAccess(base, mapped, &acc, 1);
-  if (e != hipSuccess) { (void)hipMemUnmap(base, mapped); (void)hipMemRelease(h); (void)hipMemAddressFree(base, mapped + gran); return e; }
-  *ptr = static_cast<char*>(base) + (mapped - need);      // the buffer ends where the mapping ends
-  *out = Block{base, mapped + gran, bytes, h, mapped};
-  return hipSuccess;
-}
-void guard_free(const Block& b) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemUnmap(b.base, b.mapped);
-  (void)hipMemRelease(b.handle);
-  // The address range stays RESERVED for the life of the process: hipMemAddressFree followed by a new reservation hands
-  // the same addresses out again, and on this stack (ROCm 7.2, MI355X) the device then kept reading through stale
-  // translations -- 85 of 200 upload / kernel / download round trips came back wrong and BA results varied from run to run
-  // (profiles/r3/guard_mode_diagnostic.txt); with every range used once the same runs are exact.  A never-reused range also
-  // turns a use-after-free into a fault.  The suite reserves a few hundred GB of the 47-bit address space this way.
-}
-}  // namespace
-
-hipError_t pool_alloc(void** ptr, size_t bytes) {
-  Pool& P = pool();
-  if (bytes > ((size_t)1 << 40)) return hipErrorOutOfMemory;      // a size computed from a negative count: fail, do not loop in round_up_pow2
-  if (guard_on()) {
-    // guard mode never hands an address range out twice (guard_free), i.e. it leaks address space by design: it is a TEST
-    // mode.  A long-lived process must not run into the end of the 47-bit space unannounced: stop at 16 TB.
-    if (P.guard_reserved + bytes > ((size_t)16 << 40)) {
-      std::fprintf(stderr, "sfm pool guard mode: %zu GB of address space reserved and never reused; SFM_POOL_GUARD is a test mode, not for long-lived processes\n",
-                   P.guard_reserved >> 30);
-      std::abort();
-    }
-    P.guard_reserved += bytes + (64 << 10);
-    Block b{};
-    const hipError_t e = guard_alloc(ptr, bytes, &b);
-    if (e != hipSuccess) {
-      std::fprintf(stderr, "sfm pool guard mode: the virtual-memory API failed (%s); SFM_POOL_GUARD cannot be honoured on this stack\n", hipGetErrorString(e));
-      std::abort();      // a test pass that silently ran unguarded would claim what it did not check
-    }
-    std::lock_guard<std::mutex> g(P.mu);
-    P.live[*ptr] = b;
-    ++P.guard_allocs;
-    return hipSuccess;
-  }
-  const bool rz = redzone_on();
-  // size class = the request rounded up to a power of two up to 64 MB, to the next multiple of 2 MB above (VERDICT r3 item 8:
-  // the 169 MB Zd of C3 took a 256 MB class, 3.7 GB of C4 took 4 GB; large buffers are few and long-lived, so a fine class
-  // costs no reuse); red zones / optional slack come on top of the class, so a request that already is a class size does
-  // not grow
-  constexpr size_t kFineAbove = (size_t)64 << 20, kFineStep = (size_t)2 << 20;
-  const size_t cls = bytes <= kFineAbove ? round_up_pow2(bytes) : (bytes + kFineStep - 1) / kFineStep * kFineStep;
-  const size_t sz = cls + (rz ? 2 * kRedZone : slack_bytes());
-  void* base = nullptr;
-  {
-    std::lock_guard<std::mutex> g(P.mu);
-    auto it = P.free_by_size.find(sz);
-    if (it != P.free_by_size.end() && !it->second.empty()) {
-      base = it->second.back();
-      it->second.pop_back();
-      P.cached_bytes -= sz;
-    }
-  }
-  if (base == nullptr) {
-    hipError_t e = hipMalloc(&base, sz);
-    if (e != hipSuccess) {               // out of memory: drop the cache and retry once
-      pool_release_all();
-      e = hipMalloc(&base, sz);
-    }
-    if (e != hipSuccess) return e;
-  }
-  *ptr = rz ? static_cast<char*>(base) + kRedZone : base;
-  const Block b{base, sz, bytes, {}, 0};
-  if (rz) redzone_fill(b, *ptr);
-  std::lock_guard<std::mutex> g(P.mu);
-  P.live[*ptr] = b;
-  return hipSuccess;
-}
-
-void pool_free(void* ptr) {
-  if (ptr == nullptr) return;
-  Pool& P = pool();
-  Block b{};
-  {
-    std::lock_guard<std::mutex> g(P.mu);
-    auto it = P.live.find(ptr);
-    if (it == P.live.end()) { (void)hipFree(ptr); return; }     // not ours (defensive)
-    b = it->second;
-    P.live.erase(it);
-  }
-  if (b.mapped) { guard_free(b); return; }
-  if (redzone_on()) redzone_check(b, ptr);
-  {
-    std::lock_guard<std::mutex> g(P.mu);
-    if (P.cached_bytes + b.size <= kPoolCap) {
-      P.free_by_size[b.size].push_back(b.base);
-      P.cached_bytes += b.size;
-      return;
-    }
-  }
-  (void)hipFree(b.base);
-}
-
-void pool_release_all() {
-  Pool& P = pool();
-  std::lock_guard<std::mutex> g(P.mu);
-  for (auto& kv : P.free_by_size)
-    for (void* q : kv.second) (void)hipFree(q);
-  P.free_by_size.clear();
-  P.cached_bytes = 0;
-}
-
-// Diagnostics of the pool mode (sfm_pool_mode): bit 0 red zones, bit 1 guard mappings; *tail_slack = bytes between the
-// end of a probe buffer of `probe_bytes` and the end of what is mapped behind it (guard mode: < 16).
-int pool_mode_probe(size_t probe_bytes, long long* tail_slack, long long* guard_allocs) {
-  int mode = (redzone_on() ? 1 : 0) | (guard_on() ? 2 : 0);
-  if (tail_slack) {
-    *tail_slack = -1;
-    if (ctx().inited) {
-      void* q = nullptr;
-      if (pool_alloc(&q, probe_bytes) == hipSuccess) {
-        Pool& P = pool();
-        {
-          std::lock_guard<std::mutex> g(P.mu);
-          const Block& b = P.live[q];
-          const char* end_mapped = static_cast<char*>(b.base) + (b.mapped ? b.mapped : b.size);
-          *tail_slack = (long long)(end_mapped - (static_cast<char*>(q) + probe_bytes));
-        }
-        pool_free(q);
-      }
-    }
-  }
-  if (guard_allocs) *guard_allocs = pool().guard_allocs;
-  return mode;
-}
 
 // ---------------------------------------------------------------------------------------------
 // unit-level kernels
@@ -358,6 +75,8 @@ __global__ void jac_pt_kernel(int n, int n_views, const double* projs, const dou
 // uv / X arrays are SoA so consecutive lanes read consecutive doubles.
 // ---------------------------------------------------------------------------------------------
 constexpr int kTriLdsViews = 512;
+// dynamic LDS of both triangulation kernels: the projections, when the kernels' own `in_lds` test stages them
+static size_t tri_lds_bytes(int n_views) { return n_views <= kTriLdsViews ? sizeof(double) * 12 * n_views : 0; }
 
 // NV > 0: the view count is a compile-time constant (2..4, the pipeline's case is 2) and the point's keys stay
 // in registers for all iterations -- re-reading them made the kernel L2/HBM-bound (4.8 GB for 10^6 points x 3
@@ -481,6 +200,35 @@ __global__ __launch_bounds__(256) void tri_linear_kernel(int m, int n_views, con
   Xout[(size_t)m + p] = x[1];
   Xout[2 * (size_t)m + p] = x[2];
   Xout[3 * (size_t)m + p] = x[3];
+}
+
+// What the six triangulation entry points enqueue on device arrays.  d_X_in == nullptr: the DLT result (tri:85) lands in
+// d_X_out and is refined there -- a thread reads and writes only its own point.  iters < 0: DLT only.
+static int tri_enqueue(int m, int n_views, const double* d_projs, const double* d_uv, const double* d_X_in, double lambda, int iters,
+                       double* d_X_out, hipStream_t s) {
+  const size_t lds = tri_lds_bytes(n_views);
+  if (d_X_in == nullptr) {
+    tri_linear_kernel<<<(m + 255) / 256, 256, lds, s>>>(m, n_views, d_projs, d_uv, d_X_out);
+    d_X_in = d_X_out;
+  }
+  if (iters >= 0) launch_tri_nonlinear(m, n_views, d_projs, d_uv, d_X_in, lambda, iters, d_X_out, lds, s);      // tri:86
+  SFM_HIP(hipGetLastError());
+  return SFM_OK;
+}
+
+// The host-array forms, after their own size checks: upload, tri_enqueue, download, wait.  X_in == nullptr: DLT first.
+static int tri_host(int m, int n_views, const double* projs, const double* uv, const double* X_in, double lambda, int iters,
+                    double* X_out) {
+  hipStream_t s = ctx().stream;
+  DevBuf<double> dP, dUV, dX, dO;
+  SFM_TRY(dP.upload(projs, 12 * (size_t)n_views, s));
+  SFM_TRY(dUV.upload(uv, 2 * (size_t)n_views * m, s));
+  if (X_in) SFM_TRY(dX.upload(X_in, 4 * (size_t)m, s));
+  SFM_TRY(dO.alloc(4 * (size_t)m));
+  SFM_TRY(tri_enqueue(m, n_views, dP.p, dUV.p, dX.p, lambda, iters, dO.p, s));
+  SFM_TRY(dO.download(X_out, 4 * (size_t)m, s));
+  SFM_TRY(stream_sync(s));
+  return SFM_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1008,7 +756,7 @@ static int pnp_split_workspace(hipStream_t s, int n_views, int kmax, PnpSplitWs*
   out->xch = e->xch; out->ctr = e->ctr; out->kmax = kmax;
   return SFM_OK;
 }
-static void pnp_split_release() {
+void pnp_split_release() {
   for (auto& c : pnp_split_cache()) { if (c.xch) pool_free(c.xch); if (c.ctr) pool_free(c.ctr); }
   pnp_split_cache().clear();
 }
@@ -1091,6 +839,56 @@ static int first_bad(const std::vector<int>& st) {
   return SFM_OK;
 }
 
+// ---- the hypothesis stage of the four PnP RANSAC entry points ----------------------------------------------------
+static int pnp_check_samples(const char* who, int n, int n_hyp, const int* samples) {
+  if (n < 6 || n_hyp < 1) { set_error("%s: need n >= 6 points and n_hyp >= 1 (n=%d n_hyp=%d)", who, n, n_hyp); return SFM_E_SHAPE; }
+  for (int i = 0; i < 6 * n_hyp; ++i)
+    if (samples[i] < 0 || samples[i] >= n) { set_error("%s: sample index %d out of range", who, samples[i]); return SFM_E_SHAPE; }
+  return SFM_OK;
+}
+
+// What the stage leaves on the device: poses [n_hyp][9] / [n_hyp][3], projections [n_hyp][12] and inlier counts [n_hyp];
+// with both_signs the projections and counts of the poses (R, -C) follow behind those of (R, C).
+struct PnpHypotheses {
+  DevBuf<double> R, C, P;
+  DevBuf<int> samples, counts;
+};
+
+// pnp_six_point_kernel + pnp_score_kernel (one scoring launch over all projections) on a view that is on the device
+static int pnp_hypotheses(int n, const double* d_uv, const double* d_X, const double* d_K, int n_hyp, const int* samples,
+                          double threshold, bool both_signs, PnpHypotheses& h, hipStream_t s) {
+  const size_t sets = both_signs ? 2 : 1;
+  SFM_TRY(h.samples.upload(samples, 6 * (size_t)n_hyp, s));
+  SFM_TRY(h.R.alloc(9 * (size_t)n_hyp)); SFM_TRY(h.C.alloc(3 * (size_t)n_hyp)); SFM_TRY(h.P.alloc(sets * 12 * n_hyp));
+  SFM_TRY(h.counts.alloc(sets * n_hyp));
+  pnp_six_point_kernel<<<n_hyp, 64, 0, s>>>(n_hyp, n, h.samples.p, d_uv, d_X, d_K, h.R.p, h.C.p, h.P.p,
+                                            both_signs ? h.P.p + 12 * (size_t)n_hyp : nullptr);
+  pnp_score_kernel<<<(int)sets * n_hyp, 256, 0, s>>>(n, h.P.p, d_uv, d_X, threshold, h.counts.p);
+  SFM_HIP(hipGetLastError());
+  return SFM_OK;
+}
+
+// every pose and count of the stage to the host (counts_neg: null unless both signs were scored), then wait
+static int pnp_hypotheses_download(const PnpHypotheses& h, int n_hyp, double* R_out, double* C_out, int* counts, int* counts_neg,
+                                   hipStream_t s) {
+  SFM_TRY(h.R.download(R_out, 9 * (size_t)n_hyp, s)); SFM_TRY(h.C.download(C_out, 3 * (size_t)n_hyp, s));
+  SFM_HIP(hipMemcpyAsync(counts, h.counts.p, sizeof(int) * n_hyp, hipMemcpyDeviceToHost, s));
+  if (counts_neg) SFM_HIP(hipMemcpyAsync(counts_neg, h.counts.p + n_hyp, sizeof(int) * n_hyp, hipMemcpyDeviceToHost, s));
+  SFM_TRY(stream_sync(s));
+  return SFM_OK;
+}
+
+// proj = K @ [R^T | R^T @ -C]  (campose:538), 12 doubles: formed on the host side of the library, scored on the device
+static void pose_projection(const double K[9], const double R[9], const double C[3], double P[12]) {
+  double rt[12];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) rt[4 * i + j] = R[3 * j + i];
+    rt[4 * i + 3] = R[0 + i] * -C[0] + R[3 + i] * -C[1] + R[6 + i] * -C[2];
+  }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 4; ++j) P[4 * i + j] = K[3 * i] * rt[j] + K[3 * i + 1] * rt[4 + j] + K[3 * i + 2] * rt[8 + j];
+}
+
 }  // namespace sfm
 
 using namespace sfm;
@@ -1099,78 +897,6 @@ using namespace sfm;
 // C-ABI
 // =============================================================================================
 extern "C" {
-
-int sfm_version(void) { return 101; }
-
-const char* sfm_last_error(void) { return g_err; }
-
-int sfm_init(int device) {
-  int count = 0;
-  hipError_t e = hipGetDeviceCount(&count);
-  if (e != hipSuccess || count <= 0) {
-    set_error("no HIP device visible (%s)", e == hipSuccess ? "count = 0" : hipGetErrorString(e));
-    return SFM_E_NO_DEVICE;
-  }
-  if (device < 0 || device >= count) {
-    set_error("device %d out of range (0..%d)", device, count - 1);
-    return SFM_E_NO_DEVICE;
-  }
-  Context& c = ctx();
-  if (c.inited && c.device == device) return SFM_OK;
-  if (c.inited) sfm_shutdown();
-  SFM_HIP(hipSetDevice(device));
-  hipDeviceProp_t prop;
-  SFM_HIP(hipGetDeviceProperties(&prop, device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-    set_error("device %d is %s; this library ships gfx950 (MI355X) code objects only", device, prop.gcnArchName);
-    return SFM_E_NO_DEVICE;
-  }
-  c.num_cus = prop.multiProcessorCount;
-  SFM_HIP(hipStreamCreateWithFlags(&c.own, hipStreamNonBlocking));
-  c.stream = c.own;
-  c.device = device;
-  c.inited = true;
-  return SFM_OK;
-}
-
-int sfm_shutdown(void) {
-  Context& c = ctx();
-  if (!c.inited) return SFM_OK;
-  (void)hipStreamSynchronize(c.stream);
-  if (c.stream != c.own) (void)hipStreamSynchronize(c.own);
-  (void)hipDeviceSynchronize();      // the split-PnP workspaces belong to callers' streams
-  pnp_split_release();
-  pool_release_all();
-  if (c.own) (void)hipStreamDestroy(c.own);
-  c = Context();
-  return SFM_OK;
-}
-
-int sfm_set_stream(void* hip_stream) {
-  SFM_TRY(ensure_init());
-  Context& c = ctx();
-  // the library's own stream lives from sfm_init to sfm_shutdown, so a problem that captured it as its default
-  // (sfm_ba_create) never holds a dangling handle; an installed stream stays the caller's
-  SFM_HIP(hipStreamSynchronize(c.stream));
-  c.stream = hip_stream == nullptr ? c.own : reinterpret_cast<hipStream_t>(hip_stream);
-  return SFM_OK;
-}
-
-int sfm_synchronize(void) {
-  SFM_TRY(ensure_init());
-  SFM_TRY(stream_sync(ctx().stream));
-  return SFM_OK;
-}
-
-int sfm_pool_redzone_active(void) { return redzone_on() ? 1 : 0; }
-
-int sfm_pool_mode(int64_t probe_bytes, int64_t* tail_slack, int64_t* guard_allocs) {
-  long long slack = -1, allocs = 0;
-  const int mode = pool_mode_probe(probe_bytes > 0 ? (size_t)probe_bytes : 1, tail_slack ? &slack : nullptr, &allocs);
-  if (tail_slack) *tail_slack = slack;
-  if (guard_allocs) *guard_allocs = allocs;
-  return mode;
-}
 
 int sfm_quat_to_rot(int n, const double* q, double* R, int* status) {
   SFM_TRY(ensure_init());
@@ -1242,10 +968,7 @@ int sfm_tri_nonlinear_dev(int m, int n_views, const double* d_projs, const doubl
   }
   if (m == 0) return SFM_OK;
   if (!d_projs || !d_uv || !d_X_in || !d_X_out) { set_error("sfm_tri_nonlinear_dev: null device pointer"); return SFM_E_SHAPE; }
-  const size_t lds = n_views <= kTriLdsViews ? sizeof(double) * 12 * n_views : 0;
-  launch_tri_nonlinear(m, n_views, d_projs, d_uv, d_X_in, lambda, iters, d_X_out, lds, pick_stream(hip_stream));
-  SFM_HIP(hipGetLastError());
-  return SFM_OK;
+  return tri_enqueue(m, n_views, d_projs, d_uv, d_X_in, lambda, iters, d_X_out, pick_stream(hip_stream));
 }
 
 int sfm_tri_linear_dev(int m, int n_views, const double* d_projs, const double* d_uv, double* d_X_out, void* hip_stream) {
@@ -1253,10 +976,7 @@ int sfm_tri_linear_dev(int m, int n_views, const double* d_projs, const double* 
   if (m < 0 || n_views < 1) { set_error("sfm_tri_linear_dev: bad sizes m=%d n_views=%d", m, n_views); return SFM_E_SHAPE; }
   if (m == 0) return SFM_OK;
   if (!d_projs || !d_uv || !d_X_out) { set_error("sfm_tri_linear_dev: null device pointer"); return SFM_E_SHAPE; }
-  const size_t lds = n_views <= kTriLdsViews ? sizeof(double) * 12 * n_views : 0;
-  tri_linear_kernel<<<(m + 255) / 256, 256, lds, pick_stream(hip_stream)>>>(m, n_views, d_projs, d_uv, d_X_out);
-  SFM_HIP(hipGetLastError());
-  return SFM_OK;
+  return tri_enqueue(m, n_views, d_projs, d_uv, nullptr, 0.0, -1, d_X_out, pick_stream(hip_stream));
 }
 
 int sfm_triangulate_dev(int m, int n_views, const double* d_projs, const double* d_uv, double lambda, int iters,
@@ -1268,13 +988,7 @@ int sfm_triangulate_dev(int m, int n_views, const double* d_projs, const double*
   }
   if (m == 0) return SFM_OK;
   if (!d_projs || !d_uv || !d_X_out) { set_error("sfm_triangulate_dev: null device pointer"); return SFM_E_SHAPE; }
-  hipStream_t s = pick_stream(hip_stream);
-  const size_t lds = n_views <= kTriLdsViews ? sizeof(double) * 12 * n_views : 0;
-  // the DLT result lands in X_out and is refined in place: a thread reads and writes only its own point
-  tri_linear_kernel<<<(m + 255) / 256, 256, lds, s>>>(m, n_views, d_projs, d_uv, d_X_out);            // tri:85
-  launch_tri_nonlinear(m, n_views, d_projs, d_uv, d_X_out, lambda, iters, d_X_out, lds, s);           // tri:86
-  SFM_HIP(hipGetLastError());
-  return SFM_OK;
+  return tri_enqueue(m, n_views, d_projs, d_uv, nullptr, lambda, iters, d_X_out, pick_stream(hip_stream));
 }
 
 int sfm_pnp_nonlinear_batch_dev(int n_views, const int* d_offsets, int total, const double* d_uv_pix, const double* d_X,
@@ -1326,35 +1040,14 @@ int sfm_tri_nonlinear(int m, int n_views, const double* projs, const double* uv,
     return SFM_E_SHAPE;
   }
   if (m == 0) return SFM_OK;
-  hipStream_t s = ctx().stream;
-  DevBuf<double> dP, dUV, dX, dO;
-  SFM_TRY(dP.upload(projs, 12 * (size_t)n_views, s));
-  SFM_TRY(dUV.upload(uv, 2 * (size_t)n_views * m, s));
-  SFM_TRY(dX.upload(X_in, 4 * (size_t)m, s));
-  SFM_TRY(dO.alloc(4 * (size_t)m));
-  const size_t lds = n_views <= kTriLdsViews ? sizeof(double) * 12 * n_views : 0;
-  launch_tri_nonlinear(m, n_views, dP.p, dUV.p, dX.p, lambda, iters, dO.p, lds, s);
-  SFM_HIP(hipGetLastError());
-  SFM_TRY(dO.download(X_out, 4 * (size_t)m, s));
-  SFM_TRY(stream_sync(s));
-  return SFM_OK;
+  return tri_host(m, n_views, projs, uv, X_in, lambda, iters, X_out);
 }
 
 int sfm_tri_linear(int m, int n_views, const double* projs, const double* uv, double* X_out) {
   SFM_TRY(ensure_init());
   if (m < 0 || n_views < 1) { set_error("sfm_tri_linear: bad sizes m=%d n_views=%d", m, n_views); return SFM_E_SHAPE; }
   if (m == 0) return SFM_OK;
-  hipStream_t s = ctx().stream;
-  DevBuf<double> dP, dUV, dO;
-  SFM_TRY(dP.upload(projs, 12 * (size_t)n_views, s));
-  SFM_TRY(dUV.upload(uv, 2 * (size_t)n_views * m, s));
-  SFM_TRY(dO.alloc(4 * (size_t)m));
-  const size_t lds = n_views <= kTriLdsViews ? sizeof(double) * 12 * n_views : 0;
-  tri_linear_kernel<<<(m + 255) / 256, 256, lds, s>>>(m, n_views, dP.p, dUV.p, dO.p);
-  SFM_HIP(hipGetLastError());
-  SFM_TRY(dO.download(X_out, 4 * (size_t)m, s));
-  SFM_TRY(stream_sync(s));
-  return SFM_OK;
+  return tri_host(m, n_views, projs, uv, nullptr, 0.0, -1, X_out);
 }
 
 int sfm_triangulate(int m, int n_views, const double* projs, const double* uv, double lambda, int iters, double* X_out) {
@@ -1364,61 +1057,35 @@ int sfm_triangulate(int m, int n_views, const double* projs, const double* uv, d
     return SFM_E_SHAPE;
   }
   if (m == 0) return SFM_OK;
-  hipStream_t s = ctx().stream;
-  DevBuf<double> dP, dUV, dL, dO;
-  SFM_TRY(dP.upload(projs, 12 * (size_t)n_views, s));
-  SFM_TRY(dUV.upload(uv, 2 * (size_t)n_views * m, s));
-  SFM_TRY(dL.alloc(4 * (size_t)m)); SFM_TRY(dO.alloc(4 * (size_t)m));
-  const size_t lds = n_views <= kTriLdsViews ? sizeof(double) * 12 * n_views : 0;
-  tri_linear_kernel<<<(m + 255) / 256, 256, lds, s>>>(m, n_views, dP.p, dUV.p, dL.p);          // tri:85
-  launch_tri_nonlinear(m, n_views, dP.p, dUV.p, dL.p, lambda, iters, dO.p, lds, s);   // tri:86
-  SFM_HIP(hipGetLastError());
-  SFM_TRY(dO.download(X_out, 4 * (size_t)m, s));
-  SFM_TRY(stream_sync(s));
-  return SFM_OK;
+  return tri_host(m, n_views, projs, uv, nullptr, lambda, iters, X_out);
 }
 
 int sfm_pnp_six_point_hypotheses(int n, const double* uv_pix, const double* X, const double K[9], int n_hyp,
                                  const int* samples, double threshold, double* R_out, double* C_out, int* counts) {
   SFM_TRY(ensure_init());
-  if (n < 6 || n_hyp < 1) { set_error("sfm_pnp_six_point_hypotheses: need n >= 6 points and n_hyp >= 1 (n=%d n_hyp=%d)", n, n_hyp); return SFM_E_SHAPE; }
-  for (int i = 0; i < 6 * n_hyp; ++i)
-    if (samples[i] < 0 || samples[i] >= n) { set_error("sfm_pnp_six_point_hypotheses: sample index %d out of range", samples[i]); return SFM_E_SHAPE; }
+  SFM_TRY(pnp_check_samples("sfm_pnp_six_point_hypotheses", n, n_hyp, samples));
   hipStream_t s = ctx().stream;
-  DevBuf<double> dUV, dX, dK, dR, dC, dP;
-  DevBuf<int> dS, dCnt;
+  DevBuf<double> dUV, dX, dK;
+  PnpHypotheses hyp;
   SFM_TRY(dUV.upload(uv_pix, 3 * (size_t)n, s)); SFM_TRY(dX.upload(X, 4 * (size_t)n, s)); SFM_TRY(dK.upload(K, 9, s));
-  SFM_TRY(dS.upload(samples, 6 * (size_t)n_hyp, s));
-  SFM_TRY(dR.alloc(9 * (size_t)n_hyp)); SFM_TRY(dC.alloc(3 * (size_t)n_hyp)); SFM_TRY(dP.alloc(12 * (size_t)n_hyp));
-  SFM_TRY(dCnt.alloc(n_hyp));
-  pnp_six_point_kernel<<<n_hyp, 64, 0, s>>>(n_hyp, n, dS.p, dUV.p, dX.p, dK.p, dR.p, dC.p, dP.p, nullptr);
-  pnp_score_kernel<<<n_hyp, 256, 0, s>>>(n, dP.p, dUV.p, dX.p, threshold, dCnt.p);
-  SFM_HIP(hipGetLastError());
-  SFM_TRY(dR.download(R_out, 9 * (size_t)n_hyp, s)); SFM_TRY(dC.download(C_out, 3 * (size_t)n_hyp, s));
-  SFM_TRY(dCnt.download(counts, n_hyp, s));
-  SFM_TRY(stream_sync(s));
-  return SFM_OK;
+  SFM_TRY(pnp_hypotheses(n, dUV.p, dX.p, dK.p, n_hyp, samples, threshold, false, hyp, s));
+  return pnp_hypotheses_download(hyp, n_hyp, R_out, C_out, counts, nullptr, s);
 }
 
 int sfm_pnp_linear_ransac(int n, const double* uv_pix, const double* X, const double K[9], int n_hyp, const int* samples,
                           double threshold, double R_out[9], double C_out[3], int* inlier_mask, int* n_inliers,
                           int* best_hypothesis) {
   SFM_TRY(ensure_init());
-  if (n < 6 || n_hyp < 1) { set_error("sfm_pnp_linear_ransac: need n >= 6 points and n_hyp >= 1 (n=%d n_hyp=%d)", n, n_hyp); return SFM_E_SHAPE; }
-  for (int i = 0; i < 6 * n_hyp; ++i)
-    if (samples[i] < 0 || samples[i] >= n) { set_error("sfm_pnp_linear_ransac: sample index %d out of range", samples[i]); return SFM_E_SHAPE; }
+  SFM_TRY(pnp_check_samples("sfm_pnp_linear_ransac", n, n_hyp, samples));
   hipStream_t s = ctx().stream;
-  DevBuf<double> dUV, dX, dK, dR, dC, dP;
-  DevBuf<int> dS, dCnt, dMask;
+  DevBuf<double> dUV, dX, dK;
+  DevBuf<int> dMask;
+  PnpHypotheses hyp;
   SFM_TRY(dUV.upload(uv_pix, 3 * (size_t)n, s)); SFM_TRY(dX.upload(X, 4 * (size_t)n, s)); SFM_TRY(dK.upload(K, 9, s));
-  SFM_TRY(dS.upload(samples, 6 * (size_t)n_hyp, s));
-  SFM_TRY(dR.alloc(9 * (size_t)n_hyp)); SFM_TRY(dC.alloc(3 * (size_t)n_hyp)); SFM_TRY(dP.alloc(12 * (size_t)n_hyp));
-  SFM_TRY(dCnt.alloc(n_hyp)); SFM_TRY(dMask.alloc(n));
-  pnp_six_point_kernel<<<n_hyp, 64, 0, s>>>(n_hyp, n, dS.p, dUV.p, dX.p, dK.p, dR.p, dC.p, dP.p, nullptr);
-  pnp_score_kernel<<<n_hyp, 256, 0, s>>>(n, dP.p, dUV.p, dX.p, threshold, dCnt.p);
-  SFM_HIP(hipGetLastError());
+  SFM_TRY(pnp_hypotheses(n, dUV.p, dX.p, dK.p, n_hyp, samples, threshold, false, hyp, s));
+  SFM_TRY(dMask.alloc(n));
   std::vector<int> counts(n_hyp);
-  SFM_TRY(dCnt.download(counts.data(), n_hyp, s));
+  SFM_TRY(hyp.counts.download(counts.data(), n_hyp, s));
   SFM_TRY(stream_sync(s));
   // the reference keeps the FIRST hypothesis with a strictly larger count, starting from 0 inliers / identity
   // pose (campose:524-560)
@@ -1434,11 +1101,11 @@ int sfm_pnp_linear_ransac(int n, const double* uv_pix, const double* X, const do
     for (int i = 0; i < n; ++i) inlier_mask[i] = 0;
     return SFM_OK;
   }
-  pnp_inlier_mask_kernel<<<(n + 255) / 256, 256, 0, s>>>(n, dP.p + 12 * (size_t)best, dUV.p, dX.p, threshold, dMask.p);
+  pnp_inlier_mask_kernel<<<(n + 255) / 256, 256, 0, s>>>(n, hyp.P.p + 12 * (size_t)best, dUV.p, dX.p, threshold, dMask.p);
   SFM_HIP(hipGetLastError());
   SFM_TRY(dMask.download(inlier_mask, n, s));
-  SFM_HIP(hipMemcpyAsync(R_out, dR.p + 9 * (size_t)best, 9 * sizeof(double), hipMemcpyDeviceToHost, s));
-  SFM_HIP(hipMemcpyAsync(C_out, dC.p + 3 * (size_t)best, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  SFM_HIP(hipMemcpyAsync(R_out, hyp.R.p + 9 * (size_t)best, 9 * sizeof(double), hipMemcpyDeviceToHost, s));
+  SFM_HIP(hipMemcpyAsync(C_out, hyp.C.p + 3 * (size_t)best, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
   SFM_TRY(stream_sync(s));
   return SFM_OK;
 }
@@ -1446,39 +1113,21 @@ int sfm_pnp_linear_ransac(int n, const double* uv_pix, const double* X, const do
 int sfm_pnp_ransac_evaluate(int n, const double* uv_pix, const double* X, const double K[9], int n_hyp, const int* samples,
                             double threshold, double* R_out, double* C_out, int* counts, int* counts_neg) {
   SFM_TRY(ensure_init());
-  if (n < 6 || n_hyp < 1) { set_error("sfm_pnp_ransac_evaluate: need n >= 6 points and n_hyp >= 1 (n=%d n_hyp=%d)", n, n_hyp); return SFM_E_SHAPE; }
-  for (int i = 0; i < 6 * n_hyp; ++i)
-    if (samples[i] < 0 || samples[i] >= n) { set_error("sfm_pnp_ransac_evaluate: sample index %d out of range", samples[i]); return SFM_E_SHAPE; }
+  SFM_TRY(pnp_check_samples("sfm_pnp_ransac_evaluate", n, n_hyp, samples));
   hipStream_t s = ctx().stream;
-  DevBuf<double> dUV, dX, dK, dR, dC, dP;
-  DevBuf<int> dS, dCnt;
+  DevBuf<double> dUV, dX, dK;
+  PnpHypotheses hyp;
   SFM_TRY(dUV.upload(uv_pix, 3 * (size_t)n, s)); SFM_TRY(dX.upload(X, 4 * (size_t)n, s)); SFM_TRY(dK.upload(K, 9, s));
-  SFM_TRY(dS.upload(samples, 6 * (size_t)n_hyp, s));
-  SFM_TRY(dR.alloc(9 * (size_t)n_hyp)); SFM_TRY(dC.alloc(3 * (size_t)n_hyp)); SFM_TRY(dP.alloc(24 * (size_t)n_hyp));
-  SFM_TRY(dCnt.alloc(2 * (size_t)n_hyp));
-  // projections of the pose (R, C) in the first n_hyp blocks, of (R, -C) behind them; one scoring launch over both
-  pnp_six_point_kernel<<<n_hyp, 64, 0, s>>>(n_hyp, n, dS.p, dUV.p, dX.p, dK.p, dR.p, dC.p, dP.p, dP.p + 12 * (size_t)n_hyp);
-  pnp_score_kernel<<<2 * n_hyp, 256, 0, s>>>(n, dP.p, dUV.p, dX.p, threshold, dCnt.p);
-  SFM_HIP(hipGetLastError());
-  SFM_TRY(dR.download(R_out, 9 * (size_t)n_hyp, s)); SFM_TRY(dC.download(C_out, 3 * (size_t)n_hyp, s));
-  SFM_HIP(hipMemcpyAsync(counts, dCnt.p, sizeof(int) * n_hyp, hipMemcpyDeviceToHost, s));
-  SFM_HIP(hipMemcpyAsync(counts_neg, dCnt.p + n_hyp, sizeof(int) * n_hyp, hipMemcpyDeviceToHost, s));
-  SFM_TRY(stream_sync(s));
-  return SFM_OK;
+  SFM_TRY(pnp_hypotheses(n, dUV.p, dX.p, dK.p, n_hyp, samples, threshold, true, hyp, s));
+  return pnp_hypotheses_download(hyp, n_hyp, R_out, C_out, counts, counts_neg, s);
 }
 
 int sfm_pnp_inlier_mask(int n, const double* uv_pix, const double* X, const double K[9], const double R[9], const double C[3],
                         double threshold, int* inlier_mask, int* n_inliers) {
   SFM_TRY(ensure_init());
   if (n < 1) { set_error("sfm_pnp_inlier_mask: n < 1"); return SFM_E_SHAPE; }
-  // proj = K @ [R^T | R^T @ -C]  (campose:538), 12 doubles: formed on the host side of the library, scored on the device
-  double rt[12], P[12];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) rt[4 * i + j] = R[3 * j + i];
-    rt[4 * i + 3] = R[0 + i] * -C[0] + R[3 + i] * -C[1] + R[6 + i] * -C[2];
-  }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 4; ++j) P[4 * i + j] = K[3 * i] * rt[j] + K[3 * i + 1] * rt[4 + j] + K[3 * i + 2] * rt[8 + j];
+  double P[12];
+  pose_projection(K, R, C, P);
   hipStream_t s = ctx().stream;
   DevBuf<double> dUV, dX, dP;
   DevBuf<int> dMask;
@@ -1523,9 +1172,7 @@ int sfm_pnp_ransac_begin(int n, const double* uv_pix, const double* X, const dou
   SFM_TRY(ensure_init());
   if (out == nullptr) { set_error("sfm_pnp_ransac_begin: out is null"); return SFM_E_SHAPE; }
   *out = nullptr;
-  if (n < 6 || n_hyp < 1) { set_error("sfm_pnp_ransac_begin: need n >= 6 points and n_hyp >= 1 (n=%d n_hyp=%d)", n, n_hyp); return SFM_E_SHAPE; }
-  for (int i = 0; i < 6 * n_hyp; ++i)
-    if (samples[i] < 0 || samples[i] >= n) { set_error("sfm_pnp_ransac_begin: sample index %d out of range", samples[i]); return SFM_E_SHAPE; }
+  SFM_TRY(pnp_check_samples("sfm_pnp_ransac_begin", n, n_hyp, samples));
   hipStream_t s = ctx().stream;
   sfm_pnp_session* ses = new sfm_pnp_session{kPnpSessionMagic, n, nullptr, nullptr, nullptr, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
   for (int i = 0; i < 9; ++i) ses->K[i] = K[i];
@@ -1540,19 +1187,9 @@ int sfm_pnp_ransac_begin(int n, const double* uv_pix, const double* X, const dou
     SFM_HIP(hipMemcpyAsync(ses->dUV, uv_pix, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, s));
     SFM_HIP(hipMemcpyAsync(ses->dX, X, sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, s));
     SFM_HIP(hipMemcpyAsync(ses->dK, K, sizeof(double) * 9, hipMemcpyHostToDevice, s));
-    DevBuf<double> dR, dC, dP;
-    DevBuf<int> dS, dCnt;
-    SFM_TRY(dS.upload(samples, 6 * (size_t)n_hyp, s));
-    SFM_TRY(dR.alloc(9 * (size_t)n_hyp)); SFM_TRY(dC.alloc(3 * (size_t)n_hyp)); SFM_TRY(dP.alloc(24 * (size_t)n_hyp));
-    SFM_TRY(dCnt.alloc(2 * (size_t)n_hyp));
-    pnp_six_point_kernel<<<n_hyp, 64, 0, s>>>(n_hyp, n, dS.p, ses->dUV, ses->dX, ses->dK, dR.p, dC.p, dP.p, dP.p + 12 * (size_t)n_hyp);
-    pnp_score_kernel<<<2 * n_hyp, 256, 0, s>>>(n, dP.p, ses->dUV, ses->dX, threshold, dCnt.p);
-    SFM_HIP(hipGetLastError());
-    SFM_TRY(dR.download(R_out, 9 * (size_t)n_hyp, s)); SFM_TRY(dC.download(C_out, 3 * (size_t)n_hyp, s));
-    SFM_HIP(hipMemcpyAsync(counts, dCnt.p, sizeof(int) * n_hyp, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(counts_neg, dCnt.p + n_hyp, sizeof(int) * n_hyp, hipMemcpyDeviceToHost, s));
-    SFM_TRY(stream_sync(s));
-    return SFM_OK;
+    PnpHypotheses hyp;
+    SFM_TRY(pnp_hypotheses(n, ses->dUV, ses->dX, ses->dK, n_hyp, samples, threshold, true, hyp, s));
+    return pnp_hypotheses_download(hyp, n_hyp, R_out, C_out, counts, counts_neg, s);
   };
   const int st = run();
   if (st != SFM_OK) return fail(st);
@@ -1566,16 +1203,9 @@ int sfm_pnp_ransac_finish(sfm_pnp_session* ses, const double R[9], const double 
   if (ses == nullptr || ses->magic != kPnpSessionMagic) { set_error("sfm_pnp_ransac_finish: invalid session handle"); return SFM_E_HANDLE; }
   if (iters < 0) { set_error("sfm_pnp_ransac_finish: iters < 0"); return SFM_E_SHAPE; }
   const int n = ses->n;
-  // proj = K @ [R^T | R^T @ -C]  (campose:538) of the chosen pose
-  const double* Kh = ses->K;
   hipStream_t s = ctx().stream;
-  double rt[12], P[12];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) rt[4 * i + j] = R[3 * j + i];
-    rt[4 * i + 3] = R[0 + i] * -C[0] + R[3 + i] * -C[1] + R[6 + i] * -C[2];
-  }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 4; ++j) P[4 * i + j] = Kh[3 * i] * rt[j] + Kh[3 * i + 1] * rt[4 + j] + Kh[3 * i + 2] * rt[8 + j];
+  double P[12];
+  pose_projection(ses->K, R, C, P);      // of the chosen pose
   auto run = [&]() -> int {
     DevBuf<double> dP, dUVc, dXc, dR0, dC0, dR, dC;
     DevBuf<int> dMask, dPos, dOff, dSt;

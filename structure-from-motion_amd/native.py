@@ -1,5 +1,6 @@
 """ctypes binding of the C-ABI in include/sfm_hip.h (libsfm_hip.so, gfx950).
 
+Every C signature is written once, in the ``SIGNATURES`` table below; ``load()`` applies it and ``EXPORTS`` is its keys.
 There is no CPU fallback: ``load()`` raises if the library is missing, and every compute call
 raises if no MI355X is visible.  Status codes map back to the exceptions the reference raises
 (``ValueError`` for bad shapes / invalid rotations, utils.py:43-51, 93-95).
@@ -37,39 +38,138 @@ TRACKS_LINEAR, TRACKS_NONLINEAR = 1, 2
 TRACK_TOO_FEW, TRACK_NONFINITE, TRACK_BEHIND = 1, 2, 4
 TRACK_GROUPS = (0, 1, 4, 8, 16, 32, 64)
 
-# every symbol include/sfm_hip.h declares (checked by tests/test_abi.py)
-EXPORTS = (
-    "sfm_version", "sfm_init", "sfm_shutdown", "sfm_set_stream", "sfm_synchronize", "sfm_last_error",
-    "sfm_quat_to_rot", "sfm_rot_to_quat", "sfm_jac_cam", "sfm_jac_pt",
-    "sfm_tri_nonlinear", "sfm_tri_linear", "sfm_triangulate", "sfm_pnp_nonlinear", "sfm_pnp_nonlinear_batch",
-    "sfm_pnp_linear_ransac", "sfm_pnp_six_point_hypotheses", "sfm_pnp_ransac_evaluate", "sfm_pnp_inlier_mask",
-    "sfm_pnp_ransac_begin", "sfm_pnp_ransac_finish", "sfm_pnp_session_destroy",
-    "sfm_comm_available", "sfm_comm_unique_id", "sfm_comm_create", "sfm_comm_destroy", "sfm_ba_set_comm",
-    "sfm_fundamental_ransac", "sfm_fundamental_eight_point", "sfm_essential_from_fundamental", "sfm_pose_candidates",
-    "sfm_cheirality",
-    "sfm_ba_solve", "sfm_ba_create", "sfm_ba_destroy", "sfm_ba_set_option", "sfm_ba_set_state",
-    "sfm_ba_set_stream", "sfm_ba_info", "sfm_ba_set_cameras", "sfm_ba_set_points", "sfm_ba_get_stats", "sfm_ba_flush",
-    "sfm_pool_redzone_active", "sfm_ba_iterate", "sfm_ba_get_state", "sfm_ba_append", "sfm_ba_kernel_time", "sfm_ba_reset_timing", "sfm_ba_debug_stamps",
-    "sfm_ba_linearize_reduce", "sfm_ba_solve_update", "sfm_ba_reduced_buffer",
-    "sfm_ba_bind_reduced_buffer", "sfm_ba_residual_jacobian", "sfm_ba_reduced_system",
-    "sfm_pool_mode", "sfm_tri_nonlinear_dev", "sfm_tri_linear_dev", "sfm_triangulate_dev", "sfm_pnp_nonlinear_batch_dev",
-    "sfm_gather_points_dev", "sfm_ba_points_ptr", "sfm_ba_stream", "sfm_ba_event_overhead",
-    "sfm_ba_get_state_rot", "sfm_ba_rederive_quaternions", "sfm_ba_flow_tasks", "sfm_ba_flow_tasks_deferred",
-    "sfm_desc_create", "sfm_desc_destroy", "sfm_desc_info", "sfm_match", "sfm_match_dev",
-    "sfm_sift_detect", "sfm_sift_result_info", "sfm_sift_result_level_shape", "sfm_sift_result_copy",
-    "sfm_sift_result_copy_pre", "sfm_sift_result_copy_level", "sfm_sift_result_destroy", "sfm_sift_blur_kernel",
-    "sfm_track_create", "sfm_track_destroy", "sfm_track_info", "sfm_track_add_view", "sfm_track_drop_last_view",
-    "sfm_track_match_dedup_dev", "sfm_track_extend_dev", "sfm_track_match_views", "sfm_track_extend_status",
-    "sfm_track_kept_copy", "sfm_track_write_kept", "sfm_track_pairs_dev", "sfm_track_pairs", "sfm_track_update_usage",
-    "sfm_track_constructed", "sfm_track_unconstructed", "sfm_track_copy_table", "sfm_track_copy_row",
-    "sfm_obs_set_normalised", "sfm_obs_build", "sfm_obs_copy",
-    "sfm_ba_create_from_tracks", "sfm_ba_sync_tracks", "sfm_ba_get_structure",
-    "sfm_tri_tracks", "sfm_tri_tracks_dev", "sfm_ba_refine_points", "sfm_tri_tracks_auto_group",
-)
-
 _lib = None
-_dp = ctypes.POINTER(ctypes.c_double)
-_ip = ctypes.POINTER(ctypes.c_int)
+vp, ci, cd, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int64
+_dp = ctypes.POINTER(cd)
+_ip = ctypes.POINTER(ci)
+fp = ctypes.POINTER(ctypes.c_float)
+_lp = ctypes.POINTER(i64)
+_pp = ctypes.POINTER(vp)
+
+
+# sfm_sift_params of the SIFT detection below (the signature table names it)
+class SiftParams(ctypes.Structure):
+    _fields_ = [("n_octave_layers", ctypes.c_int), ("contrast_threshold", ctypes.c_double),
+                ("edge_threshold", ctypes.c_double), ("sigma", ctypes.c_double), ("keep_pyramid", ctypes.c_int),
+                ("stream", ctypes.c_void_p)]
+
+
+# The one place a C signature is written down on this side: every symbol include/sfm_hip.h declares -> its argument types
+# (tests/test_abi_and_host.py compares names and argument counts with the header).  load() applies the table; every
+# function returns int except sfm_last_error.
+SIGNATURES = {
+    "sfm_version": [],
+    "sfm_init": [ci],
+    "sfm_shutdown": [],
+    "sfm_set_stream": [vp],
+    "sfm_synchronize": [],
+    "sfm_last_error": [],
+    "sfm_quat_to_rot": [ci, _dp, _dp, _ip],
+    "sfm_rot_to_quat": [ci, _dp, _dp, _ip],
+    "sfm_jac_cam": [ci, _dp, _dp, _dp, ci, _dp, _ip],
+    "sfm_jac_pt": [ci, ci, _dp, _dp, _dp],
+    "sfm_tri_nonlinear": [ci, ci, _dp, _dp, _dp, cd, ci, _dp],
+    "sfm_tri_linear": [ci, ci, _dp, _dp, _dp],
+    "sfm_triangulate": [ci, ci, _dp, _dp, cd, ci, _dp],
+    "sfm_pnp_nonlinear": [ci, _dp, _dp, _dp, _dp, _dp, cd, ci, ci, _dp, _dp],
+    "sfm_pnp_nonlinear_batch": [ci, _ip, ci, _dp, _dp, _dp, _dp, _dp, cd, ci, ci, _dp, _dp, _ip],
+    "sfm_pnp_linear_ransac": [ci, _dp, _dp, _dp, ci, _ip, cd, _dp, _dp, _ip, _ip, _ip],
+    "sfm_pnp_six_point_hypotheses": [ci, _dp, _dp, _dp, ci, _ip, cd, _dp, _dp, _ip],
+    "sfm_pnp_ransac_evaluate": [ci, _dp, _dp, _dp, ci, _ip, cd, _dp, _dp, _ip, _ip],
+    "sfm_pnp_inlier_mask": [ci, _dp, _dp, _dp, _dp, _dp, cd, _ip, _ip],
+    "sfm_pnp_ransac_begin": [ci, _dp, _dp, _dp, ci, _ip, cd, _dp, _dp, _ip, _ip, _pp],
+    "sfm_pnp_ransac_finish": [vp, _dp, _dp, cd, cd, ci, ci, _ip, _ip, _dp, _dp],
+    "sfm_pnp_session_destroy": [vp],
+    "sfm_comm_available": [],
+    "sfm_comm_unique_id": [ctypes.c_char_p],
+    "sfm_comm_create": [ci, ci, ctypes.c_char_p, _pp],
+    "sfm_comm_destroy": [vp],
+    "sfm_ba_set_comm": [vp, vp],
+    "sfm_fundamental_ransac": [ci, _dp, _dp, ci, _ip, cd, _dp, _ip, _ip, _ip],
+    "sfm_fundamental_eight_point": [ci, _dp, ci, _ip, _dp, _ip],
+    "sfm_essential_from_fundamental": [_dp, _dp, _dp, _dp],
+    "sfm_pose_candidates": [_dp, _dp, _dp],
+    "sfm_cheirality": [ci, ci, _dp, _dp, _dp, _ip, _ip, _ip],
+    "sfm_ba_solve": [ci, ci, i64, _ip, _ip, _dp, _dp, _dp, cd, ci, ci],
+    "sfm_ba_create": [ci, ci, i64, _ip, _ip, _dp, _pp],
+    "sfm_ba_destroy": [vp],
+    "sfm_ba_set_option": [vp, ci, ci],
+    "sfm_ba_set_state": [vp, _dp, _dp],
+    "sfm_ba_set_stream": [vp, vp],
+    "sfm_ba_info": [vp, ci, _lp],
+    "sfm_ba_set_cameras": [vp, _dp],
+    "sfm_ba_set_points": [vp, ci, ci, _dp],
+    "sfm_ba_get_stats": [vp, _dp, ci, _ip],
+    "sfm_ba_flush": [vp],
+    "sfm_pool_redzone_active": [],
+    "sfm_ba_iterate": [vp, cd, ci, ci],
+    "sfm_ba_get_state": [vp, _dp, _dp],
+    "sfm_ba_append": [vp, ci, _dp, ci, _dp, i64, _ip, _ip, _dp],
+    "sfm_ba_kernel_time": [vp, ci, _dp, _ip],
+    "sfm_ba_reset_timing": [vp],
+    "sfm_ba_debug_stamps": [vp, ctypes.POINTER(ctypes.c_uint64), ci],
+    "sfm_ba_linearize_reduce": [vp, cd, ci],
+    "sfm_ba_solve_update": [vp, cd, ci],
+    "sfm_ba_reduced_buffer": [vp, _pp, _lp, _ip],
+    "sfm_ba_bind_reduced_buffer": [vp, vp, i64],
+    "sfm_ba_residual_jacobian": [ci, ci, i64, _ip, _ip, _dp, _dp, _dp, ci, _dp, _dp, _dp],
+    "sfm_ba_reduced_system": [ci, ci, i64, _ip, _ip, _dp, _dp, _dp, cd, ci, ci, _dp, _dp],
+    "sfm_pool_mode": [i64, _lp, _lp],
+    "sfm_tri_nonlinear_dev": [ci, ci, vp, vp, vp, cd, ci, vp, vp],
+    "sfm_tri_linear_dev": [ci, ci, vp, vp, vp, vp],
+    "sfm_triangulate_dev": [ci, ci, vp, vp, cd, ci, vp, vp],
+    "sfm_pnp_nonlinear_batch_dev": [ci, vp, ci, vp, vp, vp, vp, vp, cd, ci, ci, vp, vp, vp, ci, vp],
+    "sfm_gather_points_dev": [ci, vp, vp, vp, vp, vp, vp],
+    "sfm_ba_points_ptr": [vp, _pp, _pp, _pp, _ip],
+    "sfm_ba_stream": [vp, _pp],
+    "sfm_ba_event_overhead": [vp, ci, _dp],
+    "sfm_ba_get_state_rot": [vp, _dp, _dp, _dp],
+    "sfm_ba_rederive_quaternions": [vp, ci, ci],
+    "sfm_ba_flow_tasks": [ci, _ip, ci],
+    "sfm_ba_flow_tasks_deferred": [ci, _ip, ci],
+    "sfm_desc_create": [ci, ci, ci, ci, vp, _pp],
+    "sfm_desc_destroy": [vp],
+    "sfm_desc_info": [vp, ci, _lp],
+    "sfm_match": [vp, ci, _pp, ci, _ip, fp, _ip, fp, ctypes.POINTER(ctypes.c_uint8)],
+    "sfm_match_dev": [vp, ci, _pp, ci, vp, vp, vp, vp, vp, vp],
+    "sfm_sift_detect": [vp, ci, ci, ci, i64, ctypes.POINTER(SiftParams), _pp],
+    "sfm_sift_result_info": [vp, ci, _lp],
+    "sfm_sift_result_level_shape": [vp, ci, _ip, _ip],
+    "sfm_sift_result_copy": [vp, fp, fp, fp, fp, fp, _ip, fp],
+    "sfm_sift_result_copy_pre": [vp, fp, fp, fp, fp, _ip],
+    "sfm_sift_result_copy_level": [vp, ci, ci, ci, fp],
+    "sfm_sift_result_destroy": [vp],
+    "sfm_sift_blur_kernel": [cd, ci, fp, _ip],
+    "sfm_track_create": [_pp],
+    "sfm_track_destroy": [vp],
+    "sfm_track_info": [vp, ci, ci, _lp],
+    "sfm_track_add_view": [vp, ci, _dp, _dp, _ip],
+    "sfm_track_drop_last_view": [vp],
+    "sfm_track_match_dedup_dev": [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp],
+    "sfm_track_extend_dev": [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp],
+    "sfm_track_match_views": [vp, ci, vp, ci, _pp, ci, ci, vp],
+    "sfm_track_extend_status": [vp, ci, _ip, _ip, _ip],
+    "sfm_track_kept_copy": [vp, ci, _ip, _ip],
+    "sfm_track_write_kept": [vp, ci, ci, vp],
+    "sfm_track_pairs_dev": [vp, ci, ci, vp, vp, vp, vp, vp, vp],
+    "sfm_track_pairs": [vp, ci, ci, _ip, _ip, _ip, _dp, _dp],
+    "sfm_track_update_usage": [vp, ci, ci, _ip, _ip],
+    "sfm_track_constructed": [vp, ci, _ip, _ip, _ip],
+    "sfm_track_unconstructed": [vp, ci, _ip, _ip],
+    "sfm_track_copy_table": [vp, ci, _ip],
+    "sfm_track_copy_row": [vp, ci, ci, _ip],
+    "sfm_obs_set_normalised": [vp, ci, ci, _dp, _dp],
+    "sfm_obs_build": [vp, ci, ci, _lp],
+    "sfm_obs_copy": [vp, _ip, _ip, _ip, _dp],
+    "sfm_ba_create_from_tracks": [vp, _pp],
+    "sfm_ba_sync_tracks": [vp, vp, ci, _dp, ci, _dp, _ip, _lp],
+    "sfm_ba_get_structure": [vp, _ip, _ip, _dp],
+    "sfm_tri_tracks": [ci, ci, i64, _ip, _ip, _dp, _dp, ci, cd, ci, ci, _dp, _dp, _dp, _ip],
+    "sfm_tri_tracks_dev": [ci, ci, i64, vp, vp, vp, vp, ci, cd, ci, ci, vp, vp, vp, vp, vp],
+    "sfm_ba_refine_points": [vp, ci, cd, ci, ci, _dp, _ip],
+    "sfm_tri_tracks_auto_group": [ci, i64, ci],
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 class SfmHipError(RuntimeError):
@@ -94,112 +194,10 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    lib.sfm_last_error.restype = ctypes.c_char_p
-    lib.sfm_set_stream.argtypes = [ctypes.c_void_p]
-    for name in EXPORTS:
+    for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)
-        if name != "sfm_last_error":
-            fn.restype = ctypes.c_int
-    lib.sfm_ba_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _ip, _ip, _dp,
-                                  ctypes.POINTER(ctypes.c_void_p)]
-    for name in ("sfm_ba_destroy",):
-        getattr(lib, name).argtypes = [ctypes.c_void_p]
-    lib.sfm_ba_set_option.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-    lib.sfm_ba_set_state.argtypes = [ctypes.c_void_p, _dp, _dp]
-    lib.sfm_ba_set_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.sfm_ba_info.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
-    lib.sfm_ba_set_cameras.argtypes = [ctypes.c_void_p, _dp]
-    lib.sfm_ba_set_points.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _dp]
-    lib.sfm_ba_append.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp, ctypes.c_int, _dp, ctypes.c_int64, _ip, _ip, _dp]
-    lib.sfm_ba_get_state.argtypes = [ctypes.c_void_p, _dp, _dp]
-    lib.sfm_ba_iterate.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int]
-    lib.sfm_ba_linearize_reduce.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_int]
-    lib.sfm_ba_solve_update.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_int]
-    lib.sfm_ba_flush.argtypes = [ctypes.c_void_p]
-    lib.sfm_ba_kernel_time.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp, _ip]
-    lib.sfm_ba_reset_timing.argtypes = [ctypes.c_void_p]
-    lib.sfm_ba_reduced_buffer.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
-                                          ctypes.POINTER(ctypes.c_int64), _ip]
-    lib.sfm_ba_bind_reduced_buffer.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
-    lib.sfm_ba_solve.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _ip, _ip, _dp, _dp, _dp,
-                                 ctypes.c_double, ctypes.c_int, ctypes.c_int]
-    lib.sfm_ba_residual_jacobian.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _ip, _ip, _dp, _dp, _dp,
-                                             ctypes.c_int, _dp, _dp, _dp]
-    lib.sfm_ba_reduced_system.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _ip, _ip, _dp, _dp, _dp,
-                                          ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp]
-    lib.sfm_tri_nonlinear.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, ctypes.c_int, _dp]
-    lib.sfm_tri_linear.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp]
-    lib.sfm_triangulate.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_int, _dp]
-    lib.sfm_pnp_nonlinear.argtypes = [ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.c_int,
-                                      ctypes.c_int, _dp, _dp]
-    lib.sfm_pnp_nonlinear_batch.argtypes = [ctypes.c_int, _ip, ctypes.c_int, _dp, _dp, _dp, _dp, _dp,
-                                            ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip]
-    lib.sfm_quat_to_rot.argtypes = [ctypes.c_int, _dp, _dp, _ip]
-    lib.sfm_rot_to_quat.argtypes = [ctypes.c_int, _dp, _dp, _ip]
-    lib.sfm_jac_cam.argtypes = [ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _dp, _ip]
-    lib.sfm_jac_pt.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp]
-    lib.sfm_fundamental_eight_point.argtypes = [ctypes.c_int, _dp, ctypes.c_int, _ip, _dp, _ip]
-    lib.sfm_essential_from_fundamental.argtypes = [_dp, _dp, _dp, _dp]
-    lib.sfm_pose_candidates.argtypes = [_dp, _dp, _dp]
-    lib.sfm_cheirality.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _ip, _ip, _ip]
-    vp = ctypes.c_void_p
-    lib.sfm_pool_mode.argtypes = [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
-    lib.sfm_tri_nonlinear_dev.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_double, ctypes.c_int, vp, vp]
-    lib.sfm_tri_linear_dev.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
-    lib.sfm_triangulate_dev.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_double, ctypes.c_int, vp, vp]
-    lib.sfm_pnp_nonlinear_batch_dev.argtypes = [ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_int,
-                                                ctypes.c_int, vp, vp, vp, ctypes.c_int, vp]
-    lib.sfm_gather_points_dev.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp]
-    lib.sfm_ba_points_ptr.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), _ip]
-    lib.sfm_ba_stream.argtypes = [vp, ctypes.POINTER(vp)]
-    lib.sfm_ba_event_overhead.argtypes = [vp, ctypes.c_int, _dp]
-    lib.sfm_ba_get_state_rot.argtypes = [vp, _dp, _dp, _dp]
-    lib.sfm_ba_rederive_quaternions.argtypes = [vp, ctypes.c_int, ctypes.c_int]
-    lib.sfm_desc_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp)]
-    lib.sfm_desc_destroy.argtypes = [vp]
-    lib.sfm_desc_info.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
-    lib.sfm_match.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, _ip, ctypes.POINTER(ctypes.c_float), _ip,
-                              ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8)]
-    lib.sfm_match_dev.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, vp, vp, vp, vp, vp, vp]
-    fp = ctypes.POINTER(ctypes.c_float)
-    lib.sfm_sift_detect.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
-                                    ctypes.POINTER(SiftParams), ctypes.POINTER(vp)]
-    lib.sfm_sift_result_info.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
-    lib.sfm_sift_result_level_shape.argtypes = [vp, ctypes.c_int, _ip, _ip]
-    lib.sfm_sift_result_copy.argtypes = [vp, fp, fp, fp, fp, fp, _ip, fp]
-    lib.sfm_sift_result_copy_pre.argtypes = [vp, fp, fp, fp, fp, _ip]
-    lib.sfm_sift_result_copy_level.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp]
-    lib.sfm_sift_result_destroy.argtypes = [vp]
-    lib.sfm_sift_blur_kernel.argtypes = [ctypes.c_double, ctypes.c_int, fp, _ip]
-    ci = ctypes.c_int
-    lib.sfm_track_create.argtypes = [ctypes.POINTER(vp)]
-    lib.sfm_track_destroy.argtypes = [vp]
-    lib.sfm_track_info.argtypes = [vp, ci, ci, ctypes.POINTER(ctypes.c_int64)]
-    lib.sfm_track_add_view.argtypes = [vp, ci, _dp, _dp, _ip]
-    lib.sfm_track_drop_last_view.argtypes = [vp]
-    lib.sfm_track_match_dedup_dev.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
-    lib.sfm_track_extend_dev.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
-    lib.sfm_track_match_views.argtypes = [vp, ci, vp, ci, ctypes.POINTER(vp), ci, ci, vp]
-    lib.sfm_track_extend_status.argtypes = [vp, ci, _ip, _ip, _ip]
-    lib.sfm_track_kept_copy.argtypes = [vp, ci, _ip, _ip]
-    lib.sfm_track_write_kept.argtypes = [vp, ci, ci, vp]
-    lib.sfm_track_pairs_dev.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp]
-    lib.sfm_track_pairs.argtypes = [vp, ci, ci, _ip, _ip, _ip, _dp, _dp]
-    lib.sfm_track_update_usage.argtypes = [vp, ci, ci, _ip, _ip]
-    lib.sfm_track_constructed.argtypes = [vp, ci, _ip, _ip, _ip]
-    lib.sfm_track_unconstructed.argtypes = [vp, ci, _ip, _ip]
-    lib.sfm_track_copy_table.argtypes = [vp, ci, _ip]
-    lib.sfm_track_copy_row.argtypes = [vp, ci, ci, _ip]
-    lib.sfm_obs_set_normalised.argtypes = [vp, ci, ci, _dp, _dp]
-    lib.sfm_obs_build.argtypes = [vp, ci, ci, ctypes.POINTER(ctypes.c_int64)]
-    lib.sfm_obs_copy.argtypes = [vp, _ip, _ip, _ip, _dp]
-    lib.sfm_ba_create_from_tracks.argtypes = [vp, ctypes.POINTER(vp)]
-    lib.sfm_ba_sync_tracks.argtypes = [vp, vp, ci, _dp, ci, _dp, _ip, ctypes.POINTER(ctypes.c_int64)]
-    lib.sfm_ba_get_structure.argtypes = [vp, _ip, _ip, _dp]
-    lib.sfm_tri_tracks.argtypes = [ci, ci, ctypes.c_int64, _ip, _ip, _dp, _dp, ci, ctypes.c_double, ci, ci, _dp, _dp, _dp, _ip]
-    lib.sfm_tri_tracks_dev.argtypes = [ci, ci, ctypes.c_int64, vp, vp, vp, vp, ci, ctypes.c_double, ci, ci, vp, vp, vp, vp, vp]
-    lib.sfm_ba_refine_points.argtypes = [vp, ci, ctypes.c_double, ci, ci, _dp, _ip]
-    lib.sfm_tri_tracks_auto_group.argtypes = [ci, ctypes.c_int64, ci]
+        fn.argtypes = argtypes
+        fn.restype = ctypes.c_char_p if name == "sfm_last_error" else ci
     _lib = lib
     return lib
 
@@ -258,7 +256,6 @@ def flow_tasks(nbk):
     """Task table of the data-flow reduced solve for nbk block columns (host only; no device call): (n, 4) int32 rows
     {type, row, column, sort key} in the order the workgroups take them."""
     lib = load()
-    lib.sfm_ba_flow_tasks.argtypes = [ctypes.c_int, _ip, ctypes.c_int]
     n = lib.sfm_ba_flow_tasks(int(nbk), None, 0)
     out = np.zeros((max(n, 1), 4), dtype=np.int32)
     if n > 0:
@@ -270,7 +267,6 @@ def flow_tasks_deferred(n_cams):
     """Task table of the data-flow solve for n_cams cameras when the split-K reduce rides in its launch (host only): rows
     {type, row, column, key}; type 5 = camera sums (camera, part), 6 = rows 8q..8q+7 (q = key & 3) of block (row, column) of S."""
     lib = load()
-    lib.sfm_ba_flow_tasks_deferred.argtypes = [ctypes.c_int, _ip, ctypes.c_int]
     n = lib.sfm_ba_flow_tasks_deferred(int(n_cams), None, 0)
     out = np.zeros((max(n, 1), 4), dtype=np.int32)
     if n > 0:
@@ -460,12 +456,9 @@ def pnp_linear_ransac(uv_pix, pts_h, intrinsic, samples, threshold, as_array=Fal
     rot = np.empty((3, 3)); loc = np.empty(3)
     mask = np.empty(n, dtype=np.int32)
     cnt = ctypes.c_int(); best = ctypes.c_int()
-    lib = load()
-    lib.sfm_pnp_linear_ransac.argtypes = [ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _ip, ctypes.c_double, _dp, _dp,
-                                          _ip, _ip, _ip]
-    check(lib.sfm_pnp_linear_ransac(n, dptr(uv_pix), dptr(pts_h), dptr(intrinsic), n_hyp, iptr(samples),
-                                    float(threshold), dptr(rot), dptr(loc), iptr(mask), ctypes.byref(cnt),
-                                    ctypes.byref(best)))
+    check(load().sfm_pnp_linear_ransac(n, dptr(uv_pix), dptr(pts_h), dptr(intrinsic), n_hyp, iptr(samples),
+                                       float(threshold), dptr(rot), dptr(loc), iptr(mask), ctypes.byref(cnt),
+                                       ctypes.byref(best)))
     idx = np.flatnonzero(mask)
     return rot, loc.reshape(3, 1), (idx if as_array else idx.tolist()), best.value
 
@@ -478,9 +471,7 @@ def comm_available():
 def comm_unique_id():
     """128 opaque bytes identifying a new RCCL communicator (rank 0 calls this and hands them to the other ranks)."""
     buf = ctypes.create_string_buffer(128)
-    lib = load()
-    lib.sfm_comm_unique_id.argtypes = [ctypes.c_char_p]
-    check(lib.sfm_comm_unique_id(buf))
+    check(load().sfm_comm_unique_id(buf))
     return buf.raw
 
 
@@ -492,13 +483,11 @@ class Comm:
             raise ValueError("unique_id must be the 128 bytes of comm_unique_id()")
         self._lib = load()
         self._h = ctypes.c_void_p()
-        self._lib.sfm_comm_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
         check(self._lib.sfm_comm_create(int(world_size), int(rank), bytes(unique_id), ctypes.byref(self._h)))
         self.world_size, self.rank = int(world_size), int(rank)
 
     def close(self):
         if self._h:
-            self._lib.sfm_comm_destroy.argtypes = [ctypes.c_void_p]
             check(self._lib.sfm_comm_destroy(self._h))      # refused (SfmHipError) while a problem still holds it
             self._h = ctypes.c_void_p()
 
@@ -516,10 +505,8 @@ def pnp_ransac_evaluate(uv_pix, pts_h, intrinsic, samples, threshold):
     n, n_hyp = uv_pix.shape[1], samples.shape[0]
     rot = np.empty((n_hyp, 3, 3)); loc = np.empty((n_hyp, 3))
     cnt = np.empty(n_hyp, dtype=np.int32); cnt_neg = np.empty(n_hyp, dtype=np.int32)
-    lib = load()
-    lib.sfm_pnp_ransac_evaluate.argtypes = [ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _ip, ctypes.c_double, _dp, _dp, _ip, _ip]
-    check(lib.sfm_pnp_ransac_evaluate(n, dptr(uv_pix), dptr(pts_h), dptr(intrinsic), n_hyp, iptr(samples),
-                                      float(threshold), dptr(rot), dptr(loc), iptr(cnt), iptr(cnt_neg)))
+    check(load().sfm_pnp_ransac_evaluate(n, dptr(uv_pix), dptr(pts_h), dptr(intrinsic), n_hyp, iptr(samples),
+                                         float(threshold), dptr(rot), dptr(loc), iptr(cnt), iptr(cnt_neg)))
     return rot, loc, cnt, cnt_neg
 
 
@@ -532,11 +519,8 @@ def pnp_ransac_begin(uv_pix, pts_h, intrinsic, samples, threshold):
     rot = np.empty((n_hyp, 3, 3)); loc = np.empty((n_hyp, 3))
     cnt = np.empty(n_hyp, dtype=np.int32); cnt_neg = np.empty(n_hyp, dtype=np.int32)
     handle = ctypes.c_void_p()
-    lib = load()
-    lib.sfm_pnp_ransac_begin.argtypes = [ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _ip, ctypes.c_double, _dp, _dp, _ip, _ip,
-                                         ctypes.POINTER(ctypes.c_void_p)]
-    check(lib.sfm_pnp_ransac_begin(n, dptr(uv_pix), dptr(pts_h), dptr(intrinsic), n_hyp, iptr(samples), float(threshold),
-                                   dptr(rot), dptr(loc), iptr(cnt), iptr(cnt_neg), ctypes.byref(handle)))
+    check(load().sfm_pnp_ransac_begin(n, dptr(uv_pix), dptr(pts_h), dptr(intrinsic), n_hyp, iptr(samples), float(threshold),
+                                      dptr(rot), dptr(loc), iptr(cnt), iptr(cnt_neg), ctypes.byref(handle)))
     return (handle, n), rot, loc, cnt, cnt_neg
 
 
@@ -548,19 +532,14 @@ def pnp_ransac_finish(session, rot, loc, threshold, lam, iters, quirks=QUIRKS_RE
     mask = np.empty(n, dtype=np.int32)
     cnt = ctypes.c_int()
     r_out = np.empty((3, 3)); c_out = np.empty(3)
-    lib = load()
-    lib.sfm_pnp_ransac_finish.argtypes = [ctypes.c_void_p, _dp, _dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
-                                          _ip, _ip, _dp, _dp]
-    check(lib.sfm_pnp_ransac_finish(handle, dptr(rot), dptr(loc), float(threshold), float(lam), int(iters), int(quirks),
-                                    iptr(mask), ctypes.byref(cnt), dptr(r_out), dptr(c_out)))
+    check(load().sfm_pnp_ransac_finish(handle, dptr(rot), dptr(loc), float(threshold), float(lam), int(iters), int(quirks),
+                                       iptr(mask), ctypes.byref(cnt), dptr(r_out), dptr(c_out)))
     return np.flatnonzero(mask), r_out, c_out.reshape(3, 1)
 
 
 def pnp_session_destroy(session):
     handle, _n = session
-    lib = load()
-    lib.sfm_pnp_session_destroy.argtypes = [ctypes.c_void_p]
-    check(lib.sfm_pnp_session_destroy(handle))
+    check(load().sfm_pnp_session_destroy(handle))
 
 
 def pnp_inlier_mask(uv_pix, pts_h, intrinsic, rot, loc, threshold, as_array=False):
@@ -569,10 +548,8 @@ def pnp_inlier_mask(uv_pix, pts_h, intrinsic, rot, loc, threshold, as_array=Fals
     n = uv_pix.shape[1]
     mask = np.empty(n, dtype=np.int32)
     cnt = ctypes.c_int()
-    lib = load()
-    lib.sfm_pnp_inlier_mask.argtypes = [ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_double, _ip, _ip]
-    check(lib.sfm_pnp_inlier_mask(n, dptr(uv_pix), dptr(pts_h), dptr(intrinsic), dptr(rot), dptr(loc), float(threshold),
-                                  iptr(mask), ctypes.byref(cnt)))
+    check(load().sfm_pnp_inlier_mask(n, dptr(uv_pix), dptr(pts_h), dptr(intrinsic), dptr(rot), dptr(loc), float(threshold),
+                                     iptr(mask), ctypes.byref(cnt)))
     idx = np.flatnonzero(mask)
     return idx if as_array else idx.tolist()
 
@@ -583,10 +560,8 @@ def pnp_six_point_hypotheses(uv_pix, pts_h, intrinsic, samples, threshold):
     samples = i32(samples).reshape(-1, 6)
     n, n_hyp = uv_pix.shape[1], samples.shape[0]
     rot = np.empty((n_hyp, 3, 3)); loc = np.empty((n_hyp, 3)); cnt = np.empty(n_hyp, dtype=np.int32)
-    lib = load()
-    lib.sfm_pnp_six_point_hypotheses.argtypes = [ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _ip, ctypes.c_double, _dp, _dp, _ip]
-    check(lib.sfm_pnp_six_point_hypotheses(n, dptr(uv_pix), dptr(pts_h), dptr(intrinsic), n_hyp, iptr(samples),
-                                           float(threshold), dptr(rot), dptr(loc), iptr(cnt)))
+    check(load().sfm_pnp_six_point_hypotheses(n, dptr(uv_pix), dptr(pts_h), dptr(intrinsic), n_hyp, iptr(samples),
+                                              float(threshold), dptr(rot), dptr(loc), iptr(cnt)))
     return rot, loc, cnt
 
 
@@ -600,10 +575,8 @@ def fundamental_ransac(left, right, samples, threshold, return_count=False):
     samples = i32(samples if samples is not None and n != 8 else np.arange(8)).reshape(-1, 8)
     fund = np.empty((3, 3)); mask = np.empty(max(n, 1), dtype=np.int32)
     cnt = ctypes.c_int(); best = ctypes.c_int()
-    lib = load()
-    lib.sfm_fundamental_ransac.argtypes = [ctypes.c_int, _dp, _dp, ctypes.c_int, _ip, ctypes.c_double, _dp, _ip, _ip, _ip]
-    check(lib.sfm_fundamental_ransac(n, dptr(left), dptr(right), samples.shape[0], iptr(samples), float(threshold),
-                                     dptr(fund), iptr(mask), ctypes.byref(cnt), ctypes.byref(best)))
+    check(load().sfm_fundamental_ransac(n, dptr(left), dptr(right), samples.shape[0], iptr(samples), float(threshold),
+                                        dptr(fund), iptr(mask), ctypes.byref(cnt), ctypes.byref(best)))
     inliers = None if best.value < 0 else np.flatnonzero(mask[:n]).tolist()
     if return_count:
         return fund, inliers, best.value, cnt.value
@@ -801,7 +774,6 @@ class BaProblem:
     def set_comm(self, comm):
         """Attach a library-owned RCCL communicator (``Comm``) or detach it (None): ``iterate`` then all-reduces the
         packed [S | rhs] buffer itself, once per iteration, on the problem's stream (sfm_ba_set_comm)."""
-        self._lib.sfm_ba_set_comm.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         check(self._lib.sfm_ba_set_comm(self._h, comm._h if comm is not None else None))
         self._comm = comm                      # keep it alive as long as it is attached
 
@@ -809,7 +781,6 @@ class BaProblem:
         """Per-iteration cost sum |b - f|^2 (normalised image coordinates) at the start of every iteration run since
         the state was last uploaded -- no state download needed (sfm_ba_get_stats)."""
         out = np.empty(max_iters); n = ctypes.c_int()
-        self._lib.sfm_ba_get_stats.argtypes = [ctypes.c_void_p, _dp, ctypes.c_int, _ip]
         check(self._lib.sfm_ba_get_stats(self._h, dptr(out), int(max_iters), ctypes.byref(n)))
         return out[:n.value].copy()
 
@@ -891,7 +862,6 @@ class BaProblem:
 
     def debug_stamps(self, n=1024):
         out = np.zeros(n, dtype=np.uint64)
-        self._lib.sfm_ba_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
         check(self._lib.sfm_ba_debug_stamps(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n))
         return out
 
@@ -959,16 +929,14 @@ def match(query, refs, mode=MATCH_KNN2):
     Returns (best_idx, best_dist, second_idx, second_dist, mutual), each (len(refs), query.n): int32 / float32 /
     int32 / float32 / bool.  Order (distance, train index); a missing neighbour is index -1, distance inf; ``mutual``
     is only computed in MATCH_MUTUAL (all False otherwise)."""
-    lib = load()
     refs = list(refs)
     nr, nq = len(refs), query.n
     bi = np.empty((nr, nq), dtype=np.int32); si = np.empty((nr, nq), dtype=np.int32)
     bd = np.empty((nr, nq), dtype=np.float32); sd = np.empty((nr, nq), dtype=np.float32)
     mu = np.zeros((nr, nq), dtype=np.uint8)
     handles = (ctypes.c_void_p * max(nr, 1))(*[r._h for r in refs])
-    fp = ctypes.POINTER(ctypes.c_float)
-    check(lib.sfm_match(query._h, nr, handles, int(mode), iptr(bi), bd.ctypes.data_as(fp), iptr(si), sd.ctypes.data_as(fp),
-                        mu.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+    check(load().sfm_match(query._h, nr, handles, int(mode), iptr(bi), bd.ctypes.data_as(fp), iptr(si), sd.ctypes.data_as(fp),
+                           mu.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
     return bi, bd, si, sd, mu.astype(bool)
 
 
@@ -981,12 +949,6 @@ def match_dev(query, refs, mode, d_best_idx, d_best_dist, d_second_idx, d_second
 
 
 # ---- SIFT detection (ViewProcessor.__extract_keys, view_processor.py:199-202) ------------------------------------
-class SiftParams(ctypes.Structure):
-    _fields_ = [("n_octave_layers", ctypes.c_int), ("contrast_threshold", ctypes.c_double),
-                ("edge_threshold", ctypes.c_double), ("sigma", ctypes.c_double), ("keep_pyramid", ctypes.c_int),
-                ("stream", ctypes.c_void_p)]
-
-
 def _sift_image(img):
     a = np.asarray(img)
     if a.dtype != np.uint8 or a.size == 0 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)):
@@ -1052,7 +1014,6 @@ class SiftResult:
         out = {k: np.zeros(n, dtype=np.float32) for k in ("x", "y", "size", "angle", "response")}
         out["octave"] = np.zeros(n, dtype=np.int32)
         out["descriptors"] = np.zeros((n, 128), dtype=np.float32)
-        fp = ctypes.POINTER(ctypes.c_float)
         check(self._lib.sfm_sift_result_copy(self._h, *[out[k].ctypes.data_as(fp) for k in ("x", "y", "size", "angle", "response")],
                                               iptr(out["octave"]), out["descriptors"].ctypes.data_as(fp)))
         return out
@@ -1062,7 +1023,6 @@ class SiftResult:
         n = self.info(SIFT_INFO_N_PRE)
         out = {k: np.zeros(n, dtype=np.float32) for k in ("x", "y", "size", "response")}
         out["octave"] = np.zeros(n, dtype=np.int32)
-        fp = ctypes.POINTER(ctypes.c_float)
         check(self._lib.sfm_sift_result_copy_pre(self._h, *[out[k].ctypes.data_as(fp) for k in ("x", "y", "size", "response")],
                                                  iptr(out["octave"])))
         return out

@@ -1,6 +1,7 @@
 """CPU-side checks: the C-ABI library builds/loads and exports every symbol the header declares,
 fails loudly without a GPU, and the host logic (observation adapter, geometry helpers, scene
 generator) behaves like the reference.  No GPU compute here."""
+import ctypes
 import os
 import re
 
@@ -25,6 +26,31 @@ def test_library_loads_and_exports_everything(sfm):
     for name in sfm.native.EXPORTS:
         assert hasattr(lib, name), name
     assert lib.sfm_version() >= 100
+
+
+def test_signature_table_matches_the_header(sfm, monkeypatch):
+    """native.SIGNATURES is the only place a C signature is written in Python: its keys are EXPORTS, load() alone sets
+    argtypes on every symbol, and every argtypes list is as long as the header's parameter list."""
+    native = sfm.native
+    if not os.path.exists(native.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    assert tuple(native.SIGNATURES) == native.EXPORTS and len(set(native.EXPORTS)) == len(native.EXPORTS)
+    text = open(os.path.join(REPO, "include", "sfm_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    declared = {}
+    for name, params in re.findall(r"\b(sfm_[a-z0-9_]+)\s*\(([^()]*)\)", text):
+        params = params.strip()
+        declared[name] = 0 if params in ("", "void") else params.count(",") + 1
+    assert set(declared) == set(native.EXPORTS)
+    monkeypatch.setattr(native, "_lib", None)      # a fresh CDLL: no wrapper has been called on its function objects
+    lib = native.load()
+    for name, n_params in declared.items():
+        argtypes = getattr(lib, name).argtypes
+        assert argtypes is not None, "%s: load() set no argtypes" % name
+        assert len(argtypes) == n_params, "%s: header declares %d parameters, argtypes has %d" % (name, n_params, len(argtypes))
+    assert lib.sfm_last_error.restype is ctypes.c_char_p
 
 
 def test_no_cpu_fallback_without_gpu(sfm):

@@ -180,6 +180,53 @@ def test_pnp_ransac_session_equals_the_separate_calls(hip, sfm, n):
         hip.pnp_ransac_begin(uv[:, :5], x[:, :5], K, samples[:, :] % 5, 8.0)      # fewer than six points
 
 
+@pytest.mark.parametrize("n,n_hyp", [(6, 1), (257, 5)])
+def test_pnp_hypothesis_stage_is_one_body_behind_four_entry_points(hip, sfm, n, n_hyp):
+    """The four PnP RANSAC entry points share one hypothesis stage and the six triangulation entry points one enqueue
+    function; what the session test above leaves open, bit for bit (six points is the minimum, 257 is one past the 256
+    threads of pnp_score_kernel): pnp_six_point_hypotheses = pnp_ransac_evaluate; pnp_linear_ransac = the first strictly
+    largest count of pnp_ransac_evaluate, that row's pose and pnp_inlier_mask of it (-1, the identity and no inlier when
+    no count is positive); every entry point names itself when it rejects its input."""
+    rng = np.random.default_rng(300 + n)
+    sc = sfm.scenes.make_scene(2, n, 1.0, seed=90 + n, pixel_noise=0.4)
+    K = sc.intrinsic
+    uv = np.vstack((sc.uv_pix[:, sc.cam_idx == 1], np.ones((1, n))))
+    bad = rng.choice(n, n // 5, replace=False)
+    uv[0:2, bad] += rng.uniform(20, 150, (2, bad.size)) * rng.choice([-1, 1], (2, bad.size))
+    x = np.vstack((sc.pts_true, np.ones((1, n))))
+    samples = np.array([rng.choice(n, 6, replace=False) for _ in range(n_hyp)], dtype=np.int32)
+    for threshold in (8.0, 0.0):                       # 0.0: nothing is an inlier, the no-winner branch
+        rots, locs, cnt, _cneg = hip.pnp_ransac_evaluate(uv, x, K, samples, threshold)
+        r6, l6, c6 = hip.pnp_six_point_hypotheses(uv, x, K, samples, threshold)
+        assert np.array_equal(r6, rots) and np.array_equal(l6, locs) and np.array_equal(c6, cnt)
+        want = int(np.argmax(cnt)) if cnt.max() > 0 else -1       # argmax: the first index of the largest count
+        r, c, inl, best = hip.pnp_linear_ransac(uv, x, K, samples, threshold, as_array=True)
+        assert best == want and (threshold > 0 or want < 0)
+        if want >= 0:
+            assert np.array_equal(r, rots[want]) and np.array_equal(c, locs[want].reshape(3, 1))
+            assert np.array_equal(inl, hip.pnp_inlier_mask(uv, x, K, rots[want], locs[want], threshold, as_array=True))
+            assert inl.size == cnt[want]
+        else:
+            assert np.array_equal(r, np.eye(3)) and np.array_equal(c, np.zeros((3, 1))) and inl.size == 0
+    past = samples.copy()
+    past[-1, 5] = n                                    # one past the last point
+    for fn in (hip.pnp_six_point_hypotheses, hip.pnp_linear_ransac, hip.pnp_ransac_evaluate, hip.pnp_ransac_begin):
+        with pytest.raises(ValueError, match=r"^sfm_%s: sample index %d out of range$" % (fn.__name__, n)):
+            fn(uv, x, K, past, 8.0)
+    projs = np.stack([K @ np.hstack((rot.T, rot.T @ -loc)) for rot, loc in
+                      ((sfm.geometry.quaternion_to_rotation(q[3:7]), q[0:3].reshape(3, 1)) for q in sc.cams_true)])
+    uv2 = np.stack([sc.uv_pix[:, sc.cam_idx == v] for v in range(2)])
+    none = (np.zeros((0, 3, 4)), np.zeros((0, 2, n)))
+    with pytest.raises(ValueError, match=r"^sfm_tri_linear: bad sizes"):
+        hip.tri_linear(*none)
+    for args in ((projs, uv2, x, 0.5, -1), (*none, x, 0.5, 3)):
+        with pytest.raises(ValueError, match=r"^sfm_tri_nonlinear: bad sizes"):
+            hip.tri_nonlinear(*args)
+    for args in ((projs, uv2, 0.5, -1), (*none, 0.5, 3)):
+        with pytest.raises(ValueError, match=r"^sfm_triangulate: bad sizes"):
+            hip.triangulate(*args)
+
+
 def test_incremental_sfm_loop(hip, sfm, oracle):
     """Synthetic stand-in for BASELINE config 5 (the upenn BMPs need SIFT): views arrive one by one;
     each new view is posed by nonlinear PnP on the points known so far, new points are triangulated

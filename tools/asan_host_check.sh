@@ -12,8 +12,8 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -munsafe-fp-atomics -fsanitize=address,undefined -fno-gpu-sanitize -shared-libsan"
 cd "$repo/structure-from-motion_amd/csrc"
 pids=()
-for f in sfm_core sfm_ba sfm_ba_solve sfm_ba_host sfm_ba_schur sfm_ba_schur_rows sfm_epipolar sfm_comm; do
-  $HIPCC $FLAGS -c $f.hip -o "$out/$f.o" & pids+=($!)
+for f in $(make -s print-srcs); do      # the Makefile's own source list
+  $HIPCC $FLAGS -c $f -o "$out/${f%.hip}.o" & pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -fno-gpu-sanitize -shared-libsan "$out"/*.o -ldl -o "$out/libsfm_hip.so"
