@@ -194,13 +194,15 @@ struct KernelTimer {
 
 constexpr unsigned kBaMagic = 0x5F3BA001u;
 
-}  // namespace sfm
-
-struct sfm_ba_problem {
-  unsigned magic = sfm::kBaMagic;
-  sfm::BaDev dev;
-  hipStream_t stream = nullptr;   // every copy and kernel of this problem goes here (sfm_ba_set_stream)
-  long long upload_bytes = 0;     // host -> device bytes moved on behalf of this handle (SFM_INFO_UPLOAD_BYTES)
+// Everything of a problem that is sized or planned by (V, N, M).  A growth (sfm_ba_append, sfm_ba_sync_tracks) builds a
+// new scene and swaps it in whole (ba_adopt_grown); its defaults are the state of a scene nothing has run on yet.
+// A scene-sized device buffer is declared here and allocated with scene_alloc, which records it in `owned`: that
+// record is what ba_scene_free releases, there is no other list to keep.
+struct BaScene {
+  BaDev dev;                 // (dev.debug and dev.stamps mirror the handle: ba_mirror_handle)
+  double* own_red = nullptr; // library-owned reduced buffer (dev.red may point to a caller's tensor, which no scene owns)
+  int max_track = 0;         // longest track (observations of one point)
+  // run state
   int cur = 0;               // which prep slot holds the cameras of the current state
   bool prep_valid = false;
   int lin_rows = 0;          // rows of lin_ws the last ba_linearize wrote (0: it used global atomics)
@@ -209,24 +211,16 @@ struct sfm_ba_problem {
   bool backsub_pending = false;   // the reduced solve ran, its back substitution waits for the next launch (ba_flush)
   double pending_lambda = 0;      // ... with these parameters
   int pending_quirks = 0;
-  int max_track = 0;         // longest track (observations of one point)
-  int schur_mode = SFM_SCHUR_AUTO;
-  int quirks = SFM_QUIRKS_REFERENCE;   // of the linearisation in flight
-  int debug = 0;             // SFM_OPT_DEBUG: profiling ablations (results are wrong when set)
-  int deterministic = 0;     // SFM_OPT_DETERMINISTIC: fixed summation order everywhere (bitwise repeatable results)
-  int timing = 0;            // bitmask over SFM_K_* of the kernel classes bracketed by hipEvents
-  int timing_stride = 1;     // ... every stride-th time they run (an event pair costs ~11 us of stream bubbles on this stack)
-  double* own_red = nullptr; // library-owned reduced buffer (dev.red may point to a caller's tensor)
-  sfm_comm* comm = nullptr;  // library-owned RCCL communicator (sfm_ba_set_comm): the iterations all-reduce [S | rhs] themselves
-  // Schur-product plan (sfm_ba_schur.hip)
-  void* schur_ws = nullptr;      // [chunks][tiles][128][128] split-K partial tiles
-  const void* flow_tasks_red = nullptr;  // task table of the data-flow solve with the reduce deferred into it (sfm_ba_solve.hip)
-  int flow_ntasks_red = 0;
-  double* flow_camsum = nullptr; // [4][35 V] partial camera sums of the deferred reduce
   bool last_reduce_deferred = false;   // what the last ba_enqueue_schur decided (SFM_INFO_REDUCE_IN_SOLVE; survives the solve and graph replays)
   bool reduce_deferred = false;  // the last ba_enqueue_schur left its slabs unsummed: the next solve is the data-flow launch with FlowRed
+  // Schur-product plan (sfm_ba_schur.hip)
+  void* schur_ws = nullptr;      // [chunks][tiles][128][128] split-K partial tiles
   int* schur_blk_ptr = nullptr;  // [N][nblk + 1] first observation of a point in each 18-camera block (sparse path)
   bool schur_mfma_ok = false;
+  // data-flow solve with the reduce deferred into it (sfm_ba_solve.hip); the task tables live as long as the process
+  const void* flow_tasks_red = nullptr;
+  int flow_ntasks_red = 0;
+  double* flow_camsum = nullptr; // [4][35 V] partial camera sums of the deferred reduce
   // row-panel sparse product (sfm_ba_schur_rows.hip): camera-major observation list and work split, built on first use
   bool rows_built = false, rows_ok = false;
   int* cam_ptr = nullptr;                  // [V+1] device
@@ -239,6 +233,34 @@ struct sfm_ba_problem {
   void* rows_ws = nullptr;                 // [rows_wgs][7 R][tpr] split-K panels
   int rows_R = 0, rows_tpr = 0, rows_wgs = 0, rows_groups = 0;
   int rows_tpl = 0, rows_cp = 7;          // LDS row pitch and camera pitch of the panel (experiment: 8)
+  std::vector<void*> owned;                // every pool buffer allocated on behalf of this scene (scene_alloc)
+};
+
+// `bytes` of pool memory for a buffer of the scene, recorded in sc.owned (sfm_ba_host.hip)
+int scene_alloc_bytes(BaScene& sc, void** ptr, size_t bytes);
+template <typename T>
+int scene_alloc(BaScene& sc, T*& ptr, size_t count) {
+  void* q = nullptr;
+  SFM_TRY(scene_alloc_bytes(sc, &q, sizeof(T) * count));
+  ptr = static_cast<T*>(q);
+  return SFM_OK;
+}
+
+}  // namespace sfm
+
+// The handle: what survives a growth (identity, stream, options, communicator, graphs, timers, diagnostics) + one scene.
+struct sfm_ba_problem : sfm::BaScene {
+  unsigned magic = sfm::kBaMagic;
+  hipStream_t stream = nullptr;   // every copy and kernel of this problem goes here (sfm_ba_set_stream)
+  long long upload_bytes = 0;     // host -> device bytes moved on behalf of this handle (SFM_INFO_UPLOAD_BYTES)
+  int schur_mode = SFM_SCHUR_AUTO;
+  int quirks = SFM_QUIRKS_REFERENCE;   // of the linearisation in flight
+  int debug = 0;             // SFM_OPT_DEBUG: profiling ablations (results are wrong when set)
+  int deterministic = 0;     // SFM_OPT_DETERMINISTIC: fixed summation order everywhere (bitwise repeatable results)
+  int timing = 0;            // bitmask over SFM_K_* of the kernel classes bracketed by hipEvents
+  int timing_stride = 1;     // ... every stride-th time they run (an event pair costs ~11 us of stream bubbles on this stack)
+  sfm_comm* comm = nullptr;  // library-owned RCCL communicator (sfm_ba_set_comm): the iterations all-reduce [S | rhs] themselves
+  unsigned long long* stamps = nullptr;   // [1024] diagnostic shader-clock stamps, allocated when SFM_OPT_DEBUG bit 8 is first set
   // SFM_OPT_GRAPH: the steady-state iteration body (fused linearise + Schur + reduce + solve) captured once per
   // camera-slot parity and replayed by sfm_ba_iterate; dropped whenever an option, the stream, the reduced buffer or
   // the structure changes
@@ -251,11 +273,11 @@ struct sfm_ba_problem {
 };
 
 namespace sfm {
-int ba_schur_plan(sfm_ba_problem* p);
+int ba_schur_plan(BaScene& sc);      // plans of both Schur products, their workspace and block offsets
 int ba_rows_enqueue_build(sfm_ba_problem* p);
 int ba_rows_plan(sfm_ba_problem* p);
 int ba_rows_enqueue(sfm_ba_problem* p, hipStream_t s);
-int ba_enqueue_structure(sfm_ba_problem* p);      // validate the CSR, fill obs_pt / per-point block offsets / longest track (device)
+int ba_enqueue_structure(BaScene& sc, hipStream_t s);      // validate the CSR, fill obs_pt / per-point block offsets / longest track (device)
 int ba_schur_prepare_dense(sfm_ba_problem* p, hipStream_t s);
 int ba_enqueue_schur(sfm_ba_problem* p, hipStream_t s, bool allow_defer);
 SchurPlan ba_schur_dense_plan(const sfm_ba_problem* p);
@@ -271,7 +293,7 @@ void ba_graph_drop(sfm_ba_problem* p); // forget the captured iteration bodies
 int ba_enqueue_iterations(sfm_ba_problem* p, double lambda, int iters, int quirks);
 bool ba_can_fuse(const sfm_ba_problem* p);
 int ba_enqueue_reduced_solve(sfm_ba_problem* p, double lambda);      // sfm_ba_solve.hip: factor, solve, update cameras
-int ba_flow_setup(sfm_ba_problem* p);      // sfm_ba_solve.hip: flag words and task table of the data-flow solve (2 <= nbk <= kFlowMaxNbk)
+int ba_flow_setup(BaScene& sc, hipStream_t s);      // sfm_ba_solve.hip: flag words and task table of the data-flow solve (2 <= nbk <= kFlowMaxNbk)
 int comm_all_reduce_f64(sfm_comm* comm, double* buf, size_t count, hipStream_t s);      // sfm_comm.hip
 int comm_attach(sfm_comm* comm, int delta);      // a problem takes (+1) / gives back (-1) its hold on a communicator
 void ba_enqueue_residual_jacobian(sfm_ba_problem* p, int quirks, double* r, double* Jp, double* Jx);

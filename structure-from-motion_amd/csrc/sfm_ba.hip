@@ -507,7 +507,7 @@ int ba_enqueue_linearize_reduce(sfm_ba_problem* p, double lambda, int quirks, bo
   const bool dense_z = ba_schur_uses_mfma(p);
   if (dense_z) SFM_TRY(ba_schur_prepare_dense(p, s));
   if (!dense_z && d.Z == nullptr && d.M > 0) {     // sparse-product path: Z as AoS [M][21] (168 B/obs)
-    SFM_HIP(pool_alloc(reinterpret_cast<void**>(&p->dev.Z), sizeof(double) * 21 * (size_t)d.M));
+    SFM_TRY(scene_alloc(*p, p->dev.Z, 21 * (size_t)d.M));
   }
   const size_t lds_acc = sizeof(double) * (size_t)d.V * 35;
   const int mode = lds <= 64 * 1024 ? 2 : (lds_acc <= 64 * 1024 ? 1 : 0);

@@ -193,25 +193,24 @@ static const char* status_name(int st) {
   }
 }
 
-// Enqueue the structure kernel (all index arrays of p->dev must be on the device already).
-int ba_enqueue_structure(sfm_ba_problem* p) {
-  const BaDev& d = p->dev;
-  hipStream_t s = p->stream;
+// Enqueue the structure kernel (all index arrays of sc.dev must be on the device already).
+int ba_enqueue_structure(BaScene& sc, hipStream_t s) {
+  const BaDev& d = sc.dev;
   SFM_HIP(hipMemsetAsync(d.sinfo, 0, 4 * sizeof(int), s));
   if (d.N > 0) {
     const int nblk = (d.V + kSchurCB - 1) / kSchurCB;
-    ba_structure_kernel<<<(d.N + 255) / 256, 256, 0, s>>>(d.V, d.N, d.M, d.pt_ptr, d.cam_idx, d.obs_pt, p->schur_blk_ptr, nblk, d.sinfo);
+    ba_structure_kernel<<<(d.N + 255) / 256, 256, 0, s>>>(d.V, d.N, d.M, d.pt_ptr, d.cam_idx, d.obs_pt, sc.schur_blk_ptr, nblk, d.sinfo);
     SFM_HIP(hipGetLastError());
   }
   return SFM_OK;
 }
 
 // Wait for the structure kernel and turn its verdict into a status / message.  `who` names the entry point.
-static int ba_finish_structure(sfm_ba_problem* p, const char* who) {
+static int ba_finish_structure(BaScene& sc, hipStream_t s, const char* who) {
   int info[4] = {0, 0, 0, 0};
-  SFM_HIP(hipMemcpyAsync(info, p->dev.sinfo, sizeof(info), hipMemcpyDeviceToHost, p->stream));
-  SFM_TRY(stream_sync(p->stream));
-  p->max_track = info[2];
+  SFM_HIP(hipMemcpyAsync(info, sc.dev.sinfo, sizeof(info), hipMemcpyDeviceToHost, s));
+  SFM_TRY(stream_sync(s));
+  sc.max_track = info[2];
   switch (info[0]) {
     case 0: return SFM_OK;
     case 1: set_error("%s: pt_ptr not monotone at point %d", who, info[1]); break;
@@ -223,46 +222,56 @@ static int ba_finish_structure(sfm_ba_problem* p, const char* who) {
   return SFM_E_SHAPE;
 }
 
-// Allocate a problem of the given sizes on `stream` (nothing uploaded, no structure yet).
-static int ba_alloc_problem(int V, int N, long long M, hipStream_t stream, sfm_ba_problem** out) {
-  sfm_ba_problem* p = new sfm_ba_problem();
-  p->stream = stream;
-  BaDev& d = p->dev;
+int scene_alloc_bytes(BaScene& sc, void** ptr, size_t bytes) {
+  const hipError_t e = pool_alloc(ptr, std::max<size_t>(1, bytes));
+  if (e != hipSuccess) return hip_fail(e, "hipMalloc of a scene buffer", __LINE__);
+  sc.owned.push_back(*ptr);
+  return SFM_OK;
+}
+
+// Give back everything the scene owns, once nothing on `stream` uses it any more, and leave a scene of defaults.  Not
+// the scene's: the task tables of the data-flow solve (one per device for the life of the process) and a reduced
+// buffer the caller bound.
+static void ba_scene_free(BaScene& sc, hipStream_t stream) {
+  if (!sc.owned.empty() && ctx().inited && stream) (void)hipStreamSynchronize(stream);      // (empty: a new handle's, nothing ran on it)
+  for (void* q : sc.owned) pool_free(q);
+  sc = BaScene();
+}
+
+// The buffers and plans of a scene of the given sizes (nothing uploaded, no structure yet); the caller frees it on failure.
+static int ba_scene_alloc(BaScene& sc, int V, int N, long long M, hipStream_t stream) {
+  sc.owned.reserve(40);
+  BaDev& d = sc.dev;
   d.V = V; d.N = N; d.M = M; d.P = 7 * V;
   d.nbk = (d.P + kNB - 1) / kNB;
-  auto fail = [&](int st) { sfm_ba_destroy(p); return st; };
-#define BA_ALLOC(ptr, count) do { hipError_t e_ = pool_alloc(reinterpret_cast<void**>(&(ptr)), sizeof(*(ptr)) * std::max<size_t>(1, (count))); \
-    if (e_ != hipSuccess) return fail(hip_fail(e_, "hipMalloc " #ptr, __LINE__)); } while (0)
-  BA_ALLOC(d.pt_ptr, (size_t)N + 1);
-  BA_ALLOC(d.cam_idx, (size_t)M);
-  BA_ALLOC(d.obs_pt, (size_t)M);
-  BA_ALLOC(d.u, (size_t)M);
-  BA_ALLOC(d.v, (size_t)M);
-  BA_ALLOC(d.cams, (size_t)V * 7);
-  BA_ALLOC(d.px, (size_t)N); BA_ALLOC(d.py, (size_t)N); BA_ALLOC(d.pz, (size_t)N);
-  BA_ALLOC(d.prep[0], (size_t)V); BA_ALLOC(d.prep[1], (size_t)V);
-  BA_ALLOC(d.lin_ws, (sizeof(double) * V * 35 <= 64 * 1024) ? (size_t)kLinGridPerCu * ctx().num_cus * V * 35 : 1);
-  BA_ALLOC(p->own_red, red_size(d.nbk));
-  BA_ALLOC(d.delta, (size_t)d.nbk * kNB);
-  BA_ALLOC(d.ldiag, (size_t)((d.P + 31) / 32) * 32 * 32);
-  BA_ALLOC(d.xinv, d.nbk <= kInvRowsMaxNbk ? red_rhs_off(d.nbk) : 1);      // beyond that the back substitution runs block row by block row
-  BA_ALLOC(d.sync_ctr, 1);
-  BA_ALLOC(d.status, 2);
-  BA_ALLOC(d.sinfo, 4);
-  BA_ALLOC(d.cost, kStatSlots);
-  BA_ALLOC(d.cost_ws, (size_t)kLinGridPerCu * ctx().num_cus);
-  BA_ALLOC(d.iter_count, 1);
-#undef BA_ALLOC
-  d.red = p->own_red;
-  if (hipMemsetAsync(d.status, 0, 2 * sizeof(int), stream) != hipSuccess) return fail(SFM_E_HIP);
-  if (hipMemsetAsync(d.cost, 0, kStatSlots * sizeof(double), stream) != hipSuccess) return fail(SFM_E_HIP);
-  if (hipMemsetAsync(d.iter_count, 0, sizeof(int), stream) != hipSuccess) return fail(SFM_E_HIP);
-  if (hipMemsetAsync(d.sync_ctr, 0, sizeof(int), stream) != hipSuccess) return fail(SFM_E_HIP);
-  if (hipMemsetAsync(d.delta, 0, sizeof(double) * d.nbk * kNB, stream) != hipSuccess) return fail(SFM_E_HIP);
-  { const int st_plan = ba_schur_plan(p); if (st_plan != SFM_OK) return fail(st_plan); }
-  { const int st_flow = ba_flow_setup(p); if (st_flow != SFM_OK) return fail(st_flow); }
-  *out = p;
-  return SFM_OK;
+  const size_t lin_wgs = (size_t)kLinGridPerCu * ctx().num_cus;
+  SFM_TRY(scene_alloc(sc, d.pt_ptr, (size_t)N + 1));
+  SFM_TRY(scene_alloc(sc, d.cam_idx, (size_t)M));
+  SFM_TRY(scene_alloc(sc, d.obs_pt, (size_t)M));
+  SFM_TRY(scene_alloc(sc, d.u, (size_t)M));
+  SFM_TRY(scene_alloc(sc, d.v, (size_t)M));
+  SFM_TRY(scene_alloc(sc, d.cams, (size_t)V * 7));
+  SFM_TRY(scene_alloc(sc, d.px, (size_t)N)); SFM_TRY(scene_alloc(sc, d.py, (size_t)N)); SFM_TRY(scene_alloc(sc, d.pz, (size_t)N));
+  SFM_TRY(scene_alloc(sc, d.prep[0], (size_t)V)); SFM_TRY(scene_alloc(sc, d.prep[1], (size_t)V));
+  SFM_TRY(scene_alloc(sc, d.lin_ws, (sizeof(double) * V * 35 <= 64 * 1024) ? lin_wgs * V * 35 : 1));
+  SFM_TRY(scene_alloc(sc, sc.own_red, red_size(d.nbk)));
+  SFM_TRY(scene_alloc(sc, d.delta, (size_t)d.nbk * kNB));
+  SFM_TRY(scene_alloc(sc, d.ldiag, (size_t)((d.P + 31) / 32) * 32 * 32));
+  SFM_TRY(scene_alloc(sc, d.xinv, d.nbk <= kInvRowsMaxNbk ? red_rhs_off(d.nbk) : 1));      // beyond that the back substitution runs block row by block row
+  SFM_TRY(scene_alloc(sc, d.sync_ctr, 1));
+  SFM_TRY(scene_alloc(sc, d.status, 2));
+  SFM_TRY(scene_alloc(sc, d.sinfo, 4));
+  SFM_TRY(scene_alloc(sc, d.cost, kStatSlots));
+  SFM_TRY(scene_alloc(sc, d.cost_ws, lin_wgs));
+  SFM_TRY(scene_alloc(sc, d.iter_count, 1));
+  d.red = sc.own_red;
+  SFM_HIP(hipMemsetAsync(d.status, 0, 2 * sizeof(int), stream));
+  SFM_HIP(hipMemsetAsync(d.cost, 0, kStatSlots * sizeof(double), stream));
+  SFM_HIP(hipMemsetAsync(d.iter_count, 0, sizeof(int), stream));
+  SFM_HIP(hipMemsetAsync(d.sync_ctr, 0, sizeof(int), stream));
+  SFM_HIP(hipMemsetAsync(d.delta, 0, sizeof(double) * d.nbk * kNB, stream));
+  SFM_TRY(ba_schur_plan(sc));
+  return ba_flow_setup(sc, stream);
 }
 
 // A new state starts a new cost history (sfm_ba_get_stats).
@@ -279,40 +288,79 @@ static int ba_upload(sfm_ba_problem* p, void* dst, const void* src, size_t bytes
   return SFM_OK;
 }
 
-// p takes over the structure and state of q, a problem of the grown scene built on p's stream, and q leaves with p's old
-// buffers (sfm_ba_append, sfm_ba_sync_tracks).
-static int ba_adopt_grown(sfm_ba_problem* p, sfm_ba_problem* q, int n_new_cams) {
-  // the handle keeps its identity, options, stream and counters; the old buffers leave with q
-  q->schur_mode = p->schur_mode; q->debug = p->debug; q->timing = p->timing; q->quirks = p->quirks;
-  q->dev.debug = p->debug;
-  q->deterministic = p->deterministic && q->schur_mfma_ok && sizeof(double) * (size_t)q->dev.V * 35 <= 64 * 1024;
-  const bool had_external_red = p->dev.red != p->own_red;
-  ba_graph_drop(p);
-  std::swap(p->dev, q->dev);
-  std::swap(p->own_red, q->own_red);
-  std::swap(p->schur_ws, q->schur_ws);
-  std::swap(p->flow_tasks_red, q->flow_tasks_red); std::swap(p->flow_ntasks_red, q->flow_ntasks_red); std::swap(p->flow_camsum, q->flow_camsum);
-  p->reduce_deferred = false; p->last_reduce_deferred = false;
-  std::swap(p->schur_blk_ptr, q->schur_blk_ptr);
-  std::swap(p->schur_mfma_ok, q->schur_mfma_ok);
-  std::swap(p->rows_built, q->rows_built); std::swap(p->rows_ok, q->rows_ok);
-  std::swap(p->cam_ptr, q->cam_ptr); std::swap(p->cam_ent, q->cam_ent); std::swap(p->cam_pairs, q->cam_pairs);
-  std::swap(p->rows_table, q->rows_table); std::swap(p->rows_first, q->rows_first); std::swap(p->rows_ws, q->rows_ws);
-  std::swap(p->rows_R, q->rows_R); std::swap(p->rows_tpr, q->rows_tpr); std::swap(p->rows_wgs, q->rows_wgs);
-  std::swap(p->rows_groups, q->rows_groups); std::swap(p->rows_tpl, q->rows_tpl); std::swap(p->rows_cp, q->rows_cp);
-  std::swap(p->max_track, q->max_track);
-  // deterministic mode holds for the grown scene only while the dense product fits and the camera accumulators stay in
-  // LDS (V <= 234): beyond that the handle falls back to the default path instead of mixing the two reduce kernels
-  p->deterministic = q->deterministic;
+// The two fields of the kernel argument that belong to the handle: after create, SFM_OPT_DEBUG and every adoption.
+static void ba_mirror_handle(sfm_ba_problem* p) {
+  p->dev.debug = p->debug;
+  p->dev.stamps = p->stamps;
+}
+
+// Why the scene cannot run with a fixed summation order, or null: deterministic mode needs the atomic-free dense product
+// (Zd resident) and the LDS camera accumulators of ba_linearize.
+static const char* ba_deterministic_obstacle(const BaScene& sc) {
+  if (!sc.schur_mfma_ok) return "deterministic mode needs the dense Schur product, which does not fit this scene";
+  if (sizeof(double) * (size_t)sc.dev.V * 35 > 64 * 1024) return "deterministic mode supports at most 234 cameras";
+  return nullptr;
+}
+
+// p takes over `sc`, a checked scene built on p's stream, and what it held before is freed: the handle keeps its
+// identity, options, stream, counters and stamp buffer (sfm_ba_create*, sfm_ba_append, sfm_ba_sync_tracks).
+static int ba_adopt_grown(sfm_ba_problem* p, BaScene& sc, int n_new_cams) {
   // an externally bound reduced buffer has the wrong size when cameras were added: the library's own buffer takes
   // over and the caller binds a new one (sfm_ba_reduced_buffer reports the new size); with the camera count
   // unchanged the binding survives
-  if (had_external_red && n_new_cams == 0) p->dev.red = q->dev.red;
-  else p->dev.red = p->own_red;
-  q->dev.red = q->own_red;
-  p->cur = 0; p->prep_valid = false; p->red_clean = false; p->lin_rows = 0;
-  std::swap(p->dev.stamps, q->dev.stamps);      // the diagnostic stamp buffer stays with the handle
-  return sfm_ba_destroy(q);
+  double* const bound_red = (p->dev.red != p->own_red && n_new_cams == 0) ? p->dev.red : nullptr;
+  ba_graph_drop(p);
+  std::swap(static_cast<BaScene&>(*p), sc);
+  ba_mirror_handle(p);
+  // deterministic mode holds for the grown scene only while the dense product fits and the camera accumulators stay in
+  // LDS (V <= 234): beyond that the handle falls back to the default path instead of mixing the two reduce kernels
+  if (ba_deterministic_obstacle(*p)) p->deterministic = 0;
+  if (bound_red) p->dev.red = bound_red;
+  ba_scene_free(sc, p->stream);
+  return SFM_OK;
+}
+
+// One growth: a scene of the given sizes on p's stream, `fill` enqueues its structure and state, the structure kernel
+// checks it (synchronising: the caller's arrays are free again), and p adopts it.  On any failure the stream is drained, the
+// new scene freed and p left as it was.  `fill` keeps its temporaries outside, so that they outlive the check.
+template <typename Fill>
+static int ba_grow(sfm_ba_problem* p, int V, int N, long long M, int n_new_cams, const char* who, Fill&& fill) {
+  hipStream_t s = p->stream;
+  BaScene sc;
+  int st = ba_scene_alloc(sc, V, N, M, s);
+  if (st == SFM_OK) st = fill(sc.dev);
+  if (st == SFM_OK) st = ba_enqueue_structure(sc, s);
+  if (st == SFM_OK) st = ba_finish_structure(sc, s, who);
+  if (st != SFM_OK) { (void)hipStreamSynchronize(s); ba_scene_free(sc, s); return st; }
+  return ba_adopt_grown(p, sc, n_new_cams);
+}
+
+// The store's list IS the (point, camera)-sorted list of a scene of its sizes: taken over device to device.
+static int ba_fill_from_tracks(const BaDev& e, const TrackObservations& t, hipStream_t s) {
+  const size_t m = (size_t)t.n_obs;
+  SFM_HIP(hipMemcpyAsync(e.pt_ptr, t.pt_ptr, sizeof(int) * ((size_t)t.n_pts + 1), hipMemcpyDeviceToDevice, s));
+  if (m > 0) {
+    SFM_HIP(hipMemcpyAsync(e.cam_idx, t.cam_idx, sizeof(int) * m, hipMemcpyDeviceToDevice, s));
+    SFM_HIP(hipMemcpyAsync(e.u, t.u, sizeof(double) * m, hipMemcpyDeviceToDevice, s));
+    SFM_HIP(hipMemcpyAsync(e.v, t.v, sizeof(double) * m, hipMemcpyDeviceToDevice, s));
+  }
+  return SFM_OK;
+}
+
+// State of a grown scene e: p's cameras / points stay on the device, the new ones are uploaded behind them.
+static int ba_carry_state(sfm_ba_problem* p, const BaDev& e, const double* cams_new, const double* pts_new) {
+  const BaDev& d = p->dev;
+  hipStream_t s = p->stream;
+  const int n_new_cams = e.V - d.V, n_new_pts = e.N - d.N;
+  SFM_HIP(hipMemcpyAsync(e.cams, d.cams, sizeof(double) * 7 * d.V, hipMemcpyDeviceToDevice, s));
+  SFM_TRY(ba_upload(p, e.cams + 7 * (size_t)d.V, cams_new, sizeof(double) * 7 * n_new_cams));
+  double* dst[3] = {e.px, e.py, e.pz};
+  const double* old[3] = {d.px, d.py, d.pz};
+  for (int k = 0; k < 3; ++k) {
+    if (d.N > 0) SFM_HIP(hipMemcpyAsync(dst[k], old[k], sizeof(double) * d.N, hipMemcpyDeviceToDevice, s));
+    SFM_TRY(ba_upload(p, dst[k] + d.N, pts_new + (size_t)k * n_new_pts, sizeof(double) * n_new_pts));
+  }
+  return SFM_OK;
 }
 
 }  // namespace sfm
@@ -333,17 +381,16 @@ int sfm_ba_create(int V, int N, int64_t M, const int* pt_ptr, const int* cam_idx
   if (N == 0 && M > 0) { set_error("sfm_ba_create: %lld observations but no point", (long long)M); return SFM_E_SHAPE; }
   if (M > 0 && uv_norm == nullptr) { set_error("sfm_ba_create: uv_norm is null"); return SFM_E_SHAPE; }
   if (N > 0 && (pt_ptr[0] != 0 || pt_ptr[N] != M)) { set_error("sfm_ba_create: pt_ptr must span [0, M]"); return SFM_E_SHAPE; }
-  sfm_ba_problem* p = nullptr;
-  SFM_TRY(ba_alloc_problem(V, N, M, ctx().stream, &p));
-  BaDev& d = p->dev;
+  sfm_ba_problem* p = new sfm_ba_problem();
+  p->stream = ctx().stream;
   const int zero_ptr = 0;
-  int st = N > 0 ? ba_upload(p, d.pt_ptr, pt_ptr, sizeof(int) * ((size_t)N + 1)) : ba_upload(p, d.pt_ptr, &zero_ptr, sizeof(int));
-  if (st == SFM_OK) st = ba_upload(p, d.cam_idx, cam_idx, sizeof(int) * (size_t)M);
-  if (st == SFM_OK) st = ba_upload(p, d.u, uv_norm, sizeof(double) * (size_t)M);
-  if (st == SFM_OK) st = ba_upload(p, d.v, uv_norm + M, sizeof(double) * (size_t)M);
-  if (st == SFM_OK) st = ba_enqueue_structure(p);
-  if (st == SFM_OK) st = ba_finish_structure(p, "sfm_ba_create");      // synchronises: the caller's arrays are free again
-  if (st != SFM_OK) { (void)hipStreamSynchronize(p->stream); sfm_ba_destroy(p); return st; }
+  const int st = ba_grow(p, V, N, M, 0, "sfm_ba_create", [&](const BaDev& d) -> int {
+    SFM_TRY(N > 0 ? ba_upload(p, d.pt_ptr, pt_ptr, sizeof(int) * ((size_t)N + 1)) : ba_upload(p, d.pt_ptr, &zero_ptr, sizeof(int)));
+    SFM_TRY(ba_upload(p, d.cam_idx, cam_idx, sizeof(int) * (size_t)M));
+    SFM_TRY(ba_upload(p, d.u, uv_norm, sizeof(double) * (size_t)M));
+    return ba_upload(p, d.v, uv_norm + M, sizeof(double) * (size_t)M);
+  });
+  if (st != SFM_OK) { sfm_ba_destroy(p); return st; }
   *out = p;
   return SFM_OK;
 }
@@ -351,14 +398,10 @@ int sfm_ba_create(int V, int N, int64_t M, const int* pt_ptr, const int* cam_idx
 int sfm_ba_destroy(sfm_ba_problem* p) {
   if (p == nullptr) return SFM_OK;
   if (p->magic != kBaMagic) { set_error("sfm_ba_destroy: invalid handle"); return SFM_E_HANDLE; }
-  if (ctx().inited && p->stream) (void)hipStreamSynchronize(p->stream);
-  if (p->comm) { (void)comm_attach(p->comm, -1); p->comm = nullptr; }
+  ba_scene_free(*p, p->stream);      // waits for the stream before anything returns to the pool
+  pool_free(p->stamps);
   ba_graph_drop(p);
-  BaDev& d = p->dev;
-  void* ptrs[] = {d.pt_ptr, d.cam_idx, d.obs_pt, d.u, d.v, d.cams, d.px, d.py, d.pz, d.prep[0], d.prep[1],
-                  d.Z, d.Zd, d.lin_ws, d.stamps, p->own_red, d.delta, d.ldiag, d.xinv, d.sync_ctr, d.flow, d.status, d.sinfo, d.cost, d.cost_ws, d.iter_count,
-                  p->schur_ws, p->flow_camsum, p->schur_blk_ptr, p->cam_ptr, p->cam_ent, p->cam_pairs, p->rows_table, p->rows_first, p->rows_ws};
-  for (void* q : ptrs) if (q) pool_free(q);
+  if (p->comm) { (void)comm_attach(p->comm, -1); p->comm = nullptr; }
   for (auto& t : p->timers)
     for (auto& e : t.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   p->magic = 0;
@@ -390,11 +433,11 @@ int sfm_ba_set_option(sfm_ba_problem* p, int option, int value) {
     case SFM_OPT_DEBUG:
       SFM_TRY(ba_flush(p));
       p->debug = value;
-      p->dev.debug = value;
-      if ((value & 8) && p->dev.stamps == nullptr) {
-        SFM_HIP(pool_alloc(reinterpret_cast<void**>(&p->dev.stamps), sizeof(unsigned long long) * 1024));
-        SFM_HIP(hipMemset(p->dev.stamps, 0, sizeof(unsigned long long) * 1024));
+      if ((value & 8) && p->stamps == nullptr) {
+        SFM_HIP(pool_alloc(reinterpret_cast<void**>(&p->stamps), sizeof(unsigned long long) * 1024));
+        SFM_HIP(hipMemset(p->stamps, 0, sizeof(unsigned long long) * 1024));
       }
+      ba_mirror_handle(p);
       return SFM_OK;
     case SFM_OPT_TIMING:
       p->timing = value;   // bit k set = time kernel class k
@@ -405,11 +448,7 @@ int sfm_ba_set_option(sfm_ba_problem* p, int option, int value) {
       return SFM_OK;
     case SFM_OPT_DETERMINISTIC:
       SFM_TRY(ba_flush(p));
-      if (value != 0) {
-        // needs the atomic-free dense product (Zd resident) and the LDS camera accumulators of ba_linearize
-        if (!p->schur_mfma_ok) { set_error("deterministic mode needs the dense Schur product, which does not fit this scene"); return SFM_E_SHAPE; }
-        if (sizeof(double) * (size_t)p->dev.V * 35 > 64 * 1024) { set_error("deterministic mode supports at most 234 cameras"); return SFM_E_SHAPE; }
-      }
+      if (const char* why = value != 0 ? ba_deterministic_obstacle(*p) : nullptr) { set_error("%s", why); return SFM_E_SHAPE; }
       p->deterministic = value != 0;
       return SFM_OK;
     default:
@@ -593,13 +632,10 @@ int sfm_ba_append(sfm_ba_problem* p, int n_new_cams, const double* cams_new, int
   if (M2 > 0x7fffffffLL) { set_error("sfm_ba_append: too many observations"); return SFM_E_SHAPE; }
   if (N2 == 0 && M2 > 0) { set_error("sfm_ba_append: observations but no point"); return SFM_E_SHAPE; }
   hipStream_t s = p->stream;
-  sfm_ba_problem* q = nullptr;
-  SFM_TRY(ba_alloc_problem(V2, N2, M2, s, &q));
-  BaDev& e = q->dev;
-  auto run = [&]() -> int {
+  DevBuf<int> dcam, dpt, cnt, nstart, fill, norder;
+  DevBuf<double> duv;
+  return ba_grow(p, V2, N2, M2, n_new_cams, "sfm_ba_append", [&](const BaDev& e) -> int {
     // only the NEW data crosses PCIe; it is accounted to the surviving handle
-    DevBuf<int> dcam, dpt, cnt, nstart, fill, norder;
-    DevBuf<double> duv;
     const size_t n = (size_t)n_new_obs;
     SFM_TRY(dcam.upload(obs_cam, n, s)); SFM_TRY(dpt.upload(obs_pt, n, s)); SFM_TRY(duv.upload(uv_norm, 2 * n, s));
     p->upload_bytes += (long long)(n * (2 * sizeof(int) + 2 * sizeof(double)));
@@ -623,21 +659,8 @@ int sfm_ba_append(sfm_ba_problem* p, int n_new_cams, const double* cams_new, int
     if (N2 > 0) ba_append_merge_kernel<<<(N2 + 255) / 256, 256, 0, s>>>(d.N, N2, d.pt_ptr, d.cam_idx, d.u, d.v, e.pt_ptr, nstart.p, norder.p,
                                                                         dcam.p, duv.p, duv.p + n, e.cam_idx, e.u, e.v);
     SFM_HIP(hipGetLastError());
-    // state: old cameras / points stay on the device, the new ones are uploaded behind them
-    SFM_HIP(hipMemcpyAsync(e.cams, d.cams, sizeof(double) * 7 * d.V, hipMemcpyDeviceToDevice, s));
-    SFM_TRY(ba_upload(p, e.cams + 7 * (size_t)d.V, cams_new, sizeof(double) * 7 * n_new_cams));
-    double* dst[3] = {e.px, e.py, e.pz};
-    const double* old[3] = {d.px, d.py, d.pz};
-    for (int k = 0; k < 3; ++k) {
-      if (d.N > 0) SFM_HIP(hipMemcpyAsync(dst[k], old[k], sizeof(double) * d.N, hipMemcpyDeviceToDevice, s));
-      SFM_TRY(ba_upload(p, dst[k] + d.N, pts_new + (size_t)k * n_new_pts, sizeof(double) * n_new_pts));
-    }
-    SFM_TRY(ba_enqueue_structure(q));
-    return ba_finish_structure(q, "sfm_ba_append");
-  };
-  const int st = run();
-  if (st != SFM_OK) { (void)hipStreamSynchronize(s); sfm_ba_destroy(q); return st; }
-  return ba_adopt_grown(p, q, n_new_cams);
+    return ba_carry_state(p, e, cams_new, pts_new);
+  });
 }
 
 int sfm_ba_create_from_tracks(sfm_track_store* store, sfm_ba_problem** out) {
@@ -647,22 +670,12 @@ int sfm_ba_create_from_tracks(sfm_track_store* store, sfm_ba_problem** out) {
   TrackObservations t;
   SFM_TRY(track_observations(store, "sfm_ba_create_from_tracks", &t));      // waits for the store's pending work
   if (t.n_views < 1) { set_error("sfm_ba_create_from_tracks: the list was built for %d views", t.n_views); return SFM_E_SHAPE; }
-  sfm_ba_problem* p = nullptr;
-  SFM_TRY(ba_alloc_problem(t.n_views, t.n_pts, t.n_obs, ctx().stream, &p));
-  BaDev& d = p->dev;
-  const size_t m = (size_t)t.n_obs;
-  auto run = [&]() -> int {
-    SFM_HIP(hipMemcpyAsync(d.pt_ptr, t.pt_ptr, sizeof(int) * ((size_t)t.n_pts + 1), hipMemcpyDeviceToDevice, p->stream));
-    if (m > 0) {
-      SFM_HIP(hipMemcpyAsync(d.cam_idx, t.cam_idx, sizeof(int) * m, hipMemcpyDeviceToDevice, p->stream));
-      SFM_HIP(hipMemcpyAsync(d.u, t.u, sizeof(double) * m, hipMemcpyDeviceToDevice, p->stream));
-      SFM_HIP(hipMemcpyAsync(d.v, t.v, sizeof(double) * m, hipMemcpyDeviceToDevice, p->stream));
-    }
-    SFM_TRY(ba_enqueue_structure(p));
-    return ba_finish_structure(p, "sfm_ba_create_from_tracks");      // synchronises: the store may build its next list
-  };
-  const int st = run();
-  if (st != SFM_OK) { (void)hipStreamSynchronize(p->stream); sfm_ba_destroy(p); return st; }
+  sfm_ba_problem* p = new sfm_ba_problem();
+  p->stream = ctx().stream;
+  // (the check synchronises: the store may build its next list)
+  const int st = ba_grow(p, t.n_views, t.n_pts, t.n_obs, 0, "sfm_ba_create_from_tracks",
+                         [&](const BaDev& d) -> int { return ba_fill_from_tracks(d, t, p->stream); });
+  if (st != SFM_OK) { sfm_ba_destroy(p); return st; }
   *out = p;
   return SFM_OK;
 }
@@ -693,36 +706,13 @@ int sfm_ba_sync_tracks(sfm_ba_problem* p, sfm_track_store* store, int n_new_cams
   }
   // every resident track is part of its new track: with the same sizes all round nothing was added either
   if (t.n_views == d.V && t.n_pts == d.N && t.n_obs == d.M) { *action = SFM_SYNC_REUSE; return SFM_OK; }
-  const int V = d.V, N = d.N;
-  const long long M = d.M;
-  const size_t m2 = (size_t)t.n_obs;
-  sfm_ba_problem* q = nullptr;
-  SFM_TRY(ba_alloc_problem(t.n_views, t.n_pts, t.n_obs, s, &q));
-  BaDev& e = q->dev;
-  const long long uploaded = p->upload_bytes;
-  auto run = [&]() -> int {
-    // the store's list IS the merged (point, camera)-sorted list: adopt it, device to device
-    SFM_HIP(hipMemcpyAsync(e.pt_ptr, t.pt_ptr, sizeof(int) * ((size_t)t.n_pts + 1), hipMemcpyDeviceToDevice, s));
-    if (m2 > 0) {
-      SFM_HIP(hipMemcpyAsync(e.cam_idx, t.cam_idx, sizeof(int) * m2, hipMemcpyDeviceToDevice, s));
-      SFM_HIP(hipMemcpyAsync(e.u, t.u, sizeof(double) * m2, hipMemcpyDeviceToDevice, s));
-      SFM_HIP(hipMemcpyAsync(e.v, t.v, sizeof(double) * m2, hipMemcpyDeviceToDevice, s));
-    }
-    // state: old cameras / points stay on the device, the new ones are uploaded behind them
-    SFM_HIP(hipMemcpyAsync(e.cams, d.cams, sizeof(double) * 7 * V, hipMemcpyDeviceToDevice, s));
-    SFM_TRY(ba_upload(p, e.cams + 7 * (size_t)V, cams_new, sizeof(double) * 7 * n_new_cams));
-    double* dst[3] = {e.px, e.py, e.pz};
-    const double* old[3] = {d.px, d.py, d.pz};
-    for (int k = 0; k < 3; ++k) {
-      if (N > 0) SFM_HIP(hipMemcpyAsync(dst[k], old[k], sizeof(double) * N, hipMemcpyDeviceToDevice, s));
-      SFM_TRY(ba_upload(p, dst[k] + N, pts_new + (size_t)k * n_new_pts, sizeof(double) * n_new_pts));
-    }
-    SFM_TRY(ba_enqueue_structure(q));
-    return ba_finish_structure(q, "sfm_ba_sync_tracks");
-  };
-  const int st = run();
-  if (st != SFM_OK) { (void)hipStreamSynchronize(s); p->upload_bytes = uploaded; sfm_ba_destroy(q); return st; }
-  SFM_TRY(ba_adopt_grown(p, q, n_new_cams));
+  const long long M = d.M, uploaded = p->upload_bytes;
+  // the store's list IS the merged (point, camera)-sorted list: adopt it
+  const int st = ba_grow(p, t.n_views, t.n_pts, t.n_obs, n_new_cams, "sfm_ba_sync_tracks", [&](const BaDev& e) -> int {
+    SFM_TRY(ba_fill_from_tracks(e, t, s));
+    return ba_carry_state(p, e, cams_new, pts_new);
+  });
+  if (st != SFM_OK) { p->upload_bytes = uploaded; return st; }
   *action = SFM_SYNC_GROWN;
   if (n_new_obs) *n_new_obs = (int64_t)(t.n_obs - M);
   return SFM_OK;
@@ -834,9 +824,9 @@ int sfm_ba_event_overhead(sfm_ba_problem* p, int n, double* avg_ms) {
 
 int sfm_ba_debug_stamps(sfm_ba_problem* p, unsigned long long* out, int n) {
   SFM_TRY(check_problem(p));
-  if (p->dev.stamps == nullptr || n < 0 || n > 1024) { set_error("debug stamps not enabled (SFM_OPT_DEBUG bit 8)"); return SFM_E_SHAPE; }
+  if (p->stamps == nullptr || n < 0 || n > 1024) { set_error("debug stamps not enabled (SFM_OPT_DEBUG bit 8)"); return SFM_E_SHAPE; }
   SFM_HIP(hipStreamSynchronize(p->stream));
-  SFM_HIP(hipMemcpy(out, p->dev.stamps, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+  SFM_HIP(hipMemcpy(out, p->stamps, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
   return SFM_OK;
 }
 

@@ -544,8 +544,8 @@ static SchurPlan make_pairs_plan(const BaDev& d) {
 // Plans of both products: block offsets of every point (sparse path), shape of Zd and chunking of its rows
 // (dense path), and the split-K slab workspace both share.  Zd itself is allocated (and zero-filled) on first
 // use by ba_schur_prepare_dense.
-int ba_schur_plan(sfm_ba_problem* p) {
-  BaDev& d = p->dev;
+int ba_schur_plan(BaScene& sc) {
+  BaDev& d = sc.dev;
   d.zp = schur_dense_width(d.V);
   d.zrows = ((3 * d.N + KSL - 1) / KSL) * KSL;
   const SchurPlan pl = make_plan(d);
@@ -557,11 +557,11 @@ int ba_schur_plan(sfm_ba_problem* p) {
   const size_t zd_bytes = sizeof(double) * ((size_t)d.zrows * d.zp + RB);
   // the dense path is only ever chosen when it is cheaper than the pair path; do not reserve
   // tens of gigabytes for scenes that will never take it
-  p->schur_mfma_ok = d.N > 0 && ws_dense + zd_bytes <= ((size_t)32 << 30);
-  SFM_HIP(pool_alloc(&p->schur_ws, std::max(p->schur_mfma_ok ? ws_dense : 0, ws_pairs)));
+  sc.schur_mfma_ok = d.N > 0 && ws_dense + zd_bytes <= ((size_t)32 << 30);
+  SFM_TRY(scene_alloc_bytes(sc, &sc.schur_ws, std::max(sc.schur_mfma_ok ? ws_dense : 0, ws_pairs)));
   // per-point block offsets blk_ptr[p][b] = first observation of point p whose camera is >= 18 b (b = nblk: the
   // end of the track); filled on the device by ba_structure_kernel
-  SFM_HIP(pool_alloc(reinterpret_cast<void**>(&p->schur_blk_ptr), sizeof(int) * (size_t)std::max(1, d.N) * (pp.nblk + 1)));
+  SFM_TRY(scene_alloc(sc, sc.schur_blk_ptr, (size_t)std::max(1, d.N) * (pp.nblk + 1)));
   // once per device (every sfm_ba_create / sfm_ba_append plans a problem: the per-view loop of the reference appends after every
   // registered view); a process that re-initialises the library on another device sets them again
   static int attr_device = -1;
@@ -582,7 +582,7 @@ int ba_schur_prepare_dense(sfm_ba_problem* p, hipStream_t s) {
   // block reads up to 128 - 16 ra_last columns into the NEXT row of Zd -- values that only feed strips nobody computes --
   // and, for the last row, that far past it
   const size_t zd_bytes = sizeof(double) * ((size_t)d.zrows * d.zp + RB);
-  SFM_HIP(pool_alloc(reinterpret_cast<void**>(&d.Zd), zd_bytes));
+  SFM_TRY(scene_alloc(*p, d.Zd, zd_bytes / sizeof(double)));
   SFM_HIP(hipMemsetAsync(d.Zd, 0, zd_bytes, s));
   return SFM_OK;
 }

@@ -173,9 +173,9 @@ __global__ __launch_bounds__(256) void ba_schur_rows_reduce_kernel(BaDev d, cons
 int ba_rows_enqueue_build(sfm_ba_problem* p) {
   const BaDev& d = p->dev;
   hipStream_t s = p->stream;
-  SFM_HIP(pool_alloc(reinterpret_cast<void**>(&p->cam_ptr), sizeof(int) * ((size_t)d.V + 1)));
-  SFM_HIP(pool_alloc(reinterpret_cast<void**>(&p->cam_ent), sizeof(int4) * std::max<size_t>(1, (size_t)d.M)));
-  SFM_HIP(pool_alloc(reinterpret_cast<void**>(&p->cam_pairs), sizeof(unsigned long long) * (size_t)d.V));
+  SFM_TRY(scene_alloc(*p, p->cam_ptr, (size_t)d.V + 1));
+  SFM_TRY(scene_alloc_bytes(*p, &p->cam_ent, sizeof(int4) * std::max<size_t>(1, (size_t)d.M)));
+  SFM_TRY(scene_alloc(*p, p->cam_pairs, (size_t)d.V));
   DevBuf<int> cnt, fill;
   SFM_TRY(cnt.alloc((size_t)d.V, s)); SFM_TRY(fill.alloc((size_t)d.V, s));
   SFM_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * d.V, s));
@@ -239,9 +239,9 @@ int ba_rows_plan(sfm_ba_problem* p) {
   first[G] = (int)table.size();
   const size_t ws_bytes = sizeof(double) * table.size() * (size_t)7 * R * tpr;
   if (ws_bytes > ((size_t)8 << 30)) return SFM_OK;
-  SFM_HIP(pool_alloc(reinterpret_cast<void**>(&p->rows_table), sizeof(RowsWg) * table.size()));
-  SFM_HIP(pool_alloc(reinterpret_cast<void**>(&p->rows_first), sizeof(int) * first.size()));
-  SFM_HIP(pool_alloc(&p->rows_ws, ws_bytes));
+  SFM_TRY(scene_alloc_bytes(*p, &p->rows_table, sizeof(RowsWg) * table.size()));
+  SFM_TRY(scene_alloc(*p, p->rows_first, first.size()));
+  SFM_TRY(scene_alloc_bytes(*p, &p->rows_ws, ws_bytes));
   SFM_HIP(hipMemcpyAsync(p->rows_table, table.data(), sizeof(RowsWg) * table.size(), hipMemcpyHostToDevice, p->stream));
   SFM_HIP(hipMemcpyAsync(p->rows_first, first.data(), sizeof(int) * first.size(), hipMemcpyHostToDevice, p->stream));
   SFM_TRY(stream_sync(p->stream));

@@ -779,17 +779,17 @@ static int flow_task_table(int key, int nbk, int V, const void** table, int* nta
   return SFM_OK;
 }
 
-int ba_flow_setup(sfm_ba_problem* p) {
-  BaDev& d = p->dev;
+int ba_flow_setup(BaScene& sc, hipStream_t s) {
+  BaDev& d = sc.dev;
   if (d.nbk < 2 || d.nbk > kFlowMaxNbk) return SFM_OK;
   // field switch: SFM_FLOW_SOLVE=0 keeps every problem on the column-step launches (what SFM_OPT_DEBUG bit 1024 does per handle)
   static const bool enabled = [] { const char* e = getenv("SFM_FLOW_SOLVE"); return !(e && atoi(e) == 0); }();
   if (!enabled) return SFM_OK;
   SFM_TRY(flow_task_table(d.nbk, d.nbk, 0, &d.flow_tasks, &d.flow_ntasks));
-  SFM_TRY(flow_task_table(1000 + d.V, d.nbk, d.V, &p->flow_tasks_red, &p->flow_ntasks_red));
-  SFM_HIP(pool_alloc(reinterpret_cast<void**>(&d.flow), sizeof(unsigned) * flow_words(d.nbk)));
-  SFM_HIP(hipMemsetAsync(d.flow, 0, sizeof(unsigned) * flow_words(d.nbk), p->stream));
-  SFM_HIP(pool_alloc(reinterpret_cast<void**>(&p->flow_camsum), sizeof(double) * 4 * 35 * (size_t)d.V));
+  SFM_TRY(flow_task_table(1000 + d.V, d.nbk, d.V, &sc.flow_tasks_red, &sc.flow_ntasks_red));
+  SFM_TRY(scene_alloc(sc, d.flow, flow_words(d.nbk)));
+  SFM_HIP(hipMemsetAsync(d.flow, 0, sizeof(unsigned) * flow_words(d.nbk), s));
+  SFM_TRY(scene_alloc(sc, sc.flow_camsum, 4 * 35 * (size_t)d.V));
   static int attr_device = -1;
   if (attr_device != ctx().device) {
     SFM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_chol_flow_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFlowLdsBytes));

@@ -107,6 +107,100 @@ def test_append_rejects_bad_input(hip, sfm):
         assert np.array_equal(cams, sc.cams_init) and np.array_equal(pts, sc.pts_init)
 
 
+def _identity_options(hip, prob, stream, timing):
+    """What a handle must keep through a growth: dense product, fixed summation order, the linearise timer, its stream."""
+    prob.set_option(hip.OPT_SCHUR, hip.SCHUR_MFMA)
+    prob.set_option(hip.OPT_DETERMINISTIC, 1)
+    if timing:
+        prob.set_option(hip.OPT_TIMING, 1 << hip.K_LINEARIZE)
+    prob.set_stream(stream.cuda_stream)
+
+
+# 4 -> 7 cameras: one block column becomes two; 8 -> 10: P = 56 -> 70 leaves the single-workgroup solve for the data-flow
+# launch, whose flag words and camera sums exist only in the grown scene.  With SFM_OPT_GRAPH the brackets of SFM_OPT_TIMING
+# are left out (they switch the graphs off) and the iterations are six: one eager, two captures, then replays.
+@pytest.mark.parametrize("v0,n0,v1,n1,graph", [(4, 250, 7, 400, 0), (8, 200, 10, 300, 0), (8, 200, 10, 300, 1)])
+def test_grown_handle_keeps_its_identity(hip, sfm, v0, n0, v1, n1, graph):
+    import torch
+    sc = sfm.scenes.make_scene(v1, n1, 0.7, seed=17)
+    uvn = sfm.geometry.normalise_pixels(sc.uv_pix, sc.intrinsic)
+    keep, ptr0 = _subset(sc, v0, n0)
+    stream = torch.cuda.Stream()
+    iters = 6 if graph else 2
+    with hip.BaProblem(v0, ptr0, sc.cam_idx[keep], uvn[:, keep]) as prob:
+        _identity_options(hip, prob, stream, timing=not graph)
+        prob.set_option(hip.OPT_GRAPH, graph)
+        prob.set_state(sc.cams_init[:v0], sc.pts_init[:, :n0])
+        prob.iterate(5.0, iters)
+        assert prob.stream_ptr() == stream.cuda_stream
+        new = np.flatnonzero(~keep)
+        prob.append(sc.cams_init[v0:], sc.pts_init[:, n0:], sc.cam_idx[new], sc.pt_idx[new], uvn[:, new])
+        assert prob.info(hip.INFO_REDUCE_IN_SOLVE) == 0
+        assert prob.stream_ptr() == stream.cuda_stream
+        cams_b, pts_b = prob.get_state()
+        launches = prob.kernel_time(hip.K_LINEARIZE)[1]
+        replays = prob.info(hip.INFO_GRAPH_REPLAYS)
+        assert (launches > 0) == (not graph) and (replays > 0) == bool(graph)
+        prob.iterate(5.0, iters)
+        if graph:
+            assert prob.info(hip.INFO_GRAPH_REPLAYS) > replays      # captured anew for the grown scene, then replayed
+        else:
+            assert prob.kernel_time(hip.K_LINEARIZE)[1] > launches
+        cams_c, pts_c = prob.get_state()
+    with hip.BaProblem(sc.n_cams, sc.pt_ptr, sc.cam_idx, uvn) as fresh:
+        _identity_options(hip, fresh, stream, timing=not graph)      # eager in both variants
+        fresh.set_state(cams_b, pts_b)
+        fresh.iterate(5.0, iters)
+        cams_f, pts_f = fresh.get_state()
+    assert np.array_equal(cams_c, cams_f) and np.array_equal(pts_c, pts_f)
+    assert not np.array_equal(cams_c, cams_b)
+
+
+def test_grown_handle_keeps_its_stamp_buffer(hip, sfm):
+    sc = sfm.scenes.make_scene(7, 400, 0.7, seed=17)
+    uvn = sfm.geometry.normalise_pixels(sc.uv_pix, sc.intrinsic)
+    v0, n0 = 4, 250
+    keep, ptr0 = _subset(sc, v0, n0)
+    with hip.BaProblem(v0, ptr0, sc.cam_idx[keep], uvn[:, keep]) as prob:
+        prob.set_option(hip.OPT_DEBUG, 8)
+        prob.set_state(sc.cams_init[:v0], sc.pts_init[:, :n0])
+        new = np.flatnonzero(~keep)
+        prob.append(sc.cams_init[v0:], sc.pts_init[:, n0:], sc.cam_idx[new], sc.pt_idx[new], uvn[:, new])
+        prob.iterate(5.0, 1)
+        assert prob.debug_stamps().shape == (1024,)
+        prob.set_option(hip.OPT_DEBUG, 0)
+        prob.set_option(hip.OPT_DEBUG, 8)
+        prob.iterate(5.0, 1)
+        assert prob.debug_stamps().shape == (1024,)
+        assert np.all(np.isfinite(prob.get_state()[0]))
+
+
+def test_failed_growth_leaves_the_handle_usable(hip, sfm):
+    sc = sfm.scenes.make_scene(3, 40, 1.0, seed=2)
+    uvn = sfm.geometry.normalise_pixels(sc.uv_pix, sc.intrinsic)
+    states = []
+    for reject in (True, False):
+        with hip.BaProblem(sc.n_cams, sc.pt_ptr, sc.cam_idx, uvn) as prob:
+            prob.set_option(hip.OPT_SCHUR, hip.SCHUR_MFMA)
+            prob.set_option(hip.OPT_DETERMINISTIC, 1)
+            prob.set_state(sc.cams_init, sc.pts_init)
+            if reject:
+                with pytest.raises(ValueError, match="already observed"):
+                    prob.append(np.zeros((0, 7)), np.zeros((3, 0)), [1], [5], np.zeros((2, 1)))
+                assert (prob.n_cams, prob.n_pts, prob.n_obs) == (sc.n_cams, sc.n_pts, sc.cam_idx.shape[0])
+            prob.iterate(5.0, 2)
+            states.append(prob.get_state())
+            if reject:
+                # a valid growth afterwards: a second point where point 0 is, seen by all three cameras at point 0's keys
+                first = np.arange(sc.pt_ptr[0], sc.pt_ptr[1])
+                prob.append(np.zeros((0, 7)), sc.pts_init[:, :1], sc.cam_idx[first], np.full(first.shape[0], sc.n_pts), uvn[:, first])
+                assert (prob.info(hip.INFO_N_PTS), prob.info(hip.INFO_N_OBS)) == (sc.n_pts + 1, sc.cam_idx.shape[0] + first.shape[0])
+                prob.iterate(5.0, 2)
+                cams, pts = prob.get_state()
+                assert np.all(np.isfinite(cams)) and np.all(np.isfinite(pts)) and not np.array_equal(cams, states[0][0])
+    assert np.array_equal(states[0][0], states[1][0]) and np.array_equal(states[0][1], states[1][1])
+
+
 @pytest.mark.parametrize("shape", [(50, 4000, 0.6, "mfma"), (200, 3000, 0.15, "pairs"), (40, 2500, 0.3, "auto")])
 def test_two_rank_emulation_on_one_gpu_equals_single_problem(hip, sfm, shape):
     """The multi-GPU decomposition on the real HIP path: two point shards as two resident problems on one GPU,

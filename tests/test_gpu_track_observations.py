@@ -342,6 +342,45 @@ def test_synced_problem_solves_like_a_host_built_one(sfm, hip, capsys):
         case.close()
 
 
+def test_synced_handle_keeps_its_identity(sfm, hip):
+    """One SYNC_GROWN step behind a handle with options set: it keeps its stream, its linearise timer goes on counting, and
+    with the fixed summation order it ends on the bits of a host-built problem of the grown scene with the same options."""
+    import torch
+
+    def options(prob, stream):
+        prob.set_option(hip.OPT_SCHUR, hip.SCHUR_MFMA)
+        prob.set_option(hip.OPT_DETERMINISTIC, 1)
+        prob.set_option(hip.OPT_TIMING, 1 << hip.K_LINEARIZE)
+        prob.set_stream(stream.cuda_stream)
+
+    case = SyncCase(sfm, hip)
+    try:
+        stream = torch.cuda.Stream()
+        case.create()
+        prob = case.prob
+        options(prob, stream)
+        prob.iterate(5.0, 2)
+        assert case.grow()[0] == hip.SYNC_GROWN
+        assert prob.info(hip.INFO_REDUCE_IN_SOLVE) == 0
+        assert prob.stream_ptr() == stream.cuda_stream
+        cams_b, pts_b = prob.get_state()
+        launches = prob.kernel_time(hip.K_LINEARIZE)[1]
+        assert launches > 0
+        prob.iterate(5.0, 2)
+        assert prob.kernel_time(hip.K_LINEARIZE)[1] > launches
+        cams_c, pts_c = prob.get_state()
+        with case.host_problem(4, N1) as fresh:
+            options(fresh, stream)
+            fresh.set_state(cams_b, pts_b)
+            fresh.iterate(5.0, 2)
+            cams_f, pts_f = fresh.get_state()
+        np.testing.assert_array_equal(bits(cams_c), bits(cams_f))
+        np.testing.assert_array_equal(bits(pts_c), bits(pts_f))
+        assert not np.array_equal(cams_c, cams_b)
+    finally:
+        case.close()
+
+
 # ---- 5 ----------------------------------------------------------------------------------------------------------
 class LoopView:
     def __init__(self, rot, loc, k, xy, key_pts, descriptors):
