@@ -406,6 +406,49 @@ int sfm_tri_tracks_auto_group(int n_pts, int64_t M, int max_track);
  * stream and uploads nothing.  cost / status are HOST arrays ([2][N], [N]) or NULL.  An empty problem returns SFM_OK. */
 int sfm_ba_refine_points(sfm_ba_problem* p, int mode, double lambda, int iters, int group,
                          double* cost /*host [2][N] or NULL*/, int* status /*host [N] or NULL*/);
+
+/* ---- screening and culling of the resident scene's observations ----------------------------------------------------
+ * Judges every observation of the resident CSR at the current state and every point by what is left of its track.  For
+ * observation o of point p in camera c, with s = [R(q)^T | t]_c (X_p, 1) of the prepared cameras the linearisation reads
+ * (the projection of sfm_ba_refine_points, so err2 summed over a track is its cost row 0 when cam_scale is NULL):
+ *   depth[o] = s[2],   err2[o] = cam_scale[c]^2 ((s0/s2 - u)^2 + (s1/s2 - v)^2)      (cam_scale NULL: 1)
+ * and obs_flags[o] is a mask of SFM_OBS_*.  The observations with none of HIGH_ERROR, BEHIND, NONFINITE are the point's
+ * survivors: n_keep of them, and min_cos[p] = the minimum over survivor pairs i < j of r_i . r_j, r_i = (C_i - X) / |C_i - X|
+ * (1.0 with fewer than two).  pt_flags[p] is a mask of SFM_PT_*; a point with TOO_FEW or LOW_ANGLE is dropped: its survivors
+ * get SFM_OBS_POINT, so obs_flags[o] == 0 marks exactly the observations that remain.
+ *   max_err2 = +inf switches the error test off, cos_min_angle >= 1 the angle test; min_obs >= 0.  A NaN or negative
+ *   max_err2, cos_min_angle < -1 (or NaN), min_obs < 0 or a bad group return SFM_E_SHAPE and launch nothing.
+ * `group` lanes share a point (1, 4, 8, 16, 32, 64; 0 = sfm_tri_tracks_auto_group of the scene): no output depends on it,
+ * on the other points or on timing -- err2 and depth come from one lane, min_cos is a minimum, the counts are integers.
+ * summary[8] (counted on the device): observations before, observations kept, HIGH_ERROR, BEHIND, NONFINITE, observations
+ * dropped with their point, points dropped for TOO_FEW, points dropped for LOW_ANGLE.
+ * sfm_ba_screen completes a deferred back substitution first, prepares the cameras if they are not, runs on the
+ * problem's stream, uploads only cam_scale and changes nothing in the problem (state, cost history, captured graphs).
+ * sfm_ba_cull screens in the same way and then removes what failed: if nothing is dropped the problem is untouched (no
+ * allocation, graphs kept, summary[1] == summary[0]); otherwise a scene of (V, N, M') is built on the device (the kept
+ * cam_idx / u / v scattered in their old order, cameras and points copied bit for bit, nothing uploaded) and adopted as
+ * by sfm_ba_append: options, stream, communicator and a bound reduced buffer survive, the cost history restarts, graphs
+ * are dropped.  Point and camera indices are stable: a dropped point keeps its slot with an empty track (and stops
+ * moving), a camera may be left without observations, M' = 0 is legal.  The outputs describe the scene BEFORE the cull.
+ * With a communicator attached the cull is local to this rank's points: no collective.  All output arrays are HOST
+ * arrays or NULL.  Blocking. */
+#define SFM_OBS_HIGH_ERROR 1   /* err2 > max_err2 */
+#define SFM_OBS_BEHIND     2   /* s[2] <= 0 */
+#define SFM_OBS_NONFINITE  4   /* err2 is not finite (HIGH_ERROR is then not set) */
+#define SFM_OBS_POINT      8   /* none of the above, but the point was dropped */
+#define SFM_PT_TOO_FEW     1   /* the track was not empty and n_keep < min_obs */
+#define SFM_PT_LOW_ANGLE   2   /* n_keep >= 2, cos_min_angle < 1 and min_cos > cos_min_angle */
+#define SFM_PT_EMPTY       4   /* the track was already empty (informational, not a drop) */
+int sfm_ba_screen(sfm_ba_problem* p, double max_err2, double cos_min_angle, int min_obs, int group,
+                  const double* cam_scale /*host [V] or NULL*/,
+                  double* err2 /*host [M] or NULL*/, double* depth /*host [M] or NULL*/,
+                  unsigned char* obs_flags /*host [M] or NULL*/, double* min_cos /*host [N] or NULL*/,
+                  int* pt_flags /*host [N] or NULL*/, int64_t* summary /*[8] or NULL*/);
+int sfm_ba_cull(sfm_ba_problem* p, double max_err2, double cos_min_angle, int min_obs, int group,
+                const double* cam_scale /*host [V] or NULL*/,
+                double* err2 /*host [M] or NULL*/, double* depth /*host [M] or NULL*/,
+                unsigned char* obs_flags /*host [M] or NULL*/, double* min_cos /*host [N] or NULL*/,
+                int* pt_flags /*host [N] or NULL*/, int64_t* summary /*[8] or NULL*/);
 /* DEVICE pointer + element count of the contiguous reduced buffer (doubles).  It holds [S | rhs] between sfm_ba_linearize_reduce and
  * sfm_ba_solve_update (what the caller all-reduces); the factorisation overwrites it, and sfm_ba_iterate on one GPU may never form S
  * in it at all (SFM_INFO_REDUCE_IN_SOLVE) -- use sfm_ba_reduced_system to look at S. */

@@ -273,6 +273,19 @@ struct sfm_ba_problem : sfm::BaScene {
 };
 
 namespace sfm {
+// Device side of one screening (sfm_ba_screen.hip): the outputs before they are downloaded; a cull scatters by `flags`
+// and `new_ptr` (the exclusive scan of `keep`), kept = M'.
+struct ScreenWork {
+  DevBuf<double> scale, err2, depth, min_cos;
+  DevBuf<unsigned char> flags;
+  DevBuf<int> pt_flags, keep, new_ptr;
+  DevBuf<unsigned long long> summary;
+  long long kept = 0;
+};
+int ba_screen_run(sfm_ba_problem* p, const char* who, double max_err2, double cos_min_angle, int min_obs, int group,
+                  const double* cam_scale, double* err2, double* depth, unsigned char* obs_flags, double* min_cos,
+                  int* pt_flags, int64_t* summary, ScreenWork& w);
+int ba_cull_enqueue_scatter(const BaDev& d, const BaDev& e, const ScreenWork& w, hipStream_t s);
 int ba_schur_plan(BaScene& sc);      // plans of both Schur products, their workspace and block offsets
 int ba_rows_enqueue_build(sfm_ba_problem* p);
 int ba_rows_plan(sfm_ba_problem* p);

@@ -663,6 +663,27 @@ int sfm_ba_append(sfm_ba_problem* p, int n_new_cams, const double* cams_new, int
   });
 }
 
+// The shrinking twin of sfm_ba_append: screen (sfm_ba_screen.hip), and if anything fails, a scene of (V, N, M') filled on
+// the device -- the kept observations scattered to their new offsets, cameras and points copied as they are.
+int sfm_ba_cull(sfm_ba_problem* p, double max_err2, double cos_min_angle, int min_obs, int group, const double* cam_scale,
+                double* err2, double* depth, unsigned char* obs_flags, double* min_cos, int* pt_flags, int64_t* summary) {
+  SFM_TRY(check_problem(p));
+  ScreenWork w;
+  SFM_TRY(ba_screen_run(p, "sfm_ba_cull", max_err2, cos_min_angle, min_obs, group, cam_scale, err2, depth, obs_flags, min_cos,
+                        pt_flags, summary, w));
+  const BaDev& d = p->dev;
+  if (w.kept == d.M) return SFM_OK;      // nothing dropped: the scene, its cost history and its graphs stay
+  hipStream_t s = p->stream;
+  return ba_grow(p, d.V, d.N, w.kept, 0, "sfm_ba_cull", [&](const BaDev& e) -> int {
+    SFM_TRY(ba_cull_enqueue_scatter(d, e, w, s));
+    SFM_HIP(hipMemcpyAsync(e.cams, d.cams, sizeof(double) * 7 * d.V, hipMemcpyDeviceToDevice, s));
+    double* dst[3] = {e.px, e.py, e.pz};
+    const double* old[3] = {d.px, d.py, d.pz};
+    for (int k = 0; k < 3; ++k) SFM_HIP(hipMemcpyAsync(dst[k], old[k], sizeof(double) * d.N, hipMemcpyDeviceToDevice, s));
+    return SFM_OK;
+  });
+}
+
 int sfm_ba_create_from_tracks(sfm_track_store* store, sfm_ba_problem** out) {
   SFM_TRY(ensure_init());
   if (out == nullptr) { set_error("sfm_ba_create_from_tracks: out is null"); return SFM_E_SHAPE; }

@@ -37,6 +37,10 @@ SYNC_REUSE, SYNC_GROWN, SYNC_REPLACED = 0, 1, 2
 TRACKS_LINEAR, TRACKS_NONLINEAR = 1, 2
 TRACK_TOO_FEW, TRACK_NONFINITE, TRACK_BEHIND = 1, 2, 4
 TRACK_GROUPS = (0, 1, 4, 8, 16, 32, 64)
+OBS_HIGH_ERROR, OBS_BEHIND, OBS_NONFINITE, OBS_POINT = 1, 2, 4, 8
+PT_TOO_FEW, PT_LOW_ANGLE, PT_EMPTY = 1, 2, 4
+SCREEN_SUMMARY = ("obs_before", "obs_kept", "high_error", "behind", "nonfinite", "obs_dropped_with_point", "pts_too_few",
+                  "pts_low_angle")
 
 _lib = None
 vp, ci, cd, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int64
@@ -168,6 +172,8 @@ SIGNATURES = {
     "sfm_tri_tracks_dev": [ci, ci, i64, vp, vp, vp, vp, ci, cd, ci, ci, vp, vp, vp, vp, vp],
     "sfm_ba_refine_points": [vp, ci, cd, ci, ci, _dp, _ip],
     "sfm_tri_tracks_auto_group": [ci, i64, ci],
+    "sfm_ba_screen": [vp, cd, cd, ci, ci, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _lp],
+    "sfm_ba_cull": [vp, cd, cd, ci, ci, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _lp],
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -411,6 +417,26 @@ def check_tracks(pt_ptr, cam_idx, uv, projs, x_init, mode, iters, group):
         if x_init.shape != (4, n_pts):
             raise ValueError("X_init must be (4, n_pts) with n_pts = %d, got %s" % (n_pts, x_init.shape))
     return pt_ptr, cam_idx, uv, projs, x_init, mode, iters, group
+
+
+def check_screen(n_cams, max_err2, cos_min_angle, min_obs, cam_scale, group=0):
+    """Arguments of a ``BaProblem.screen`` / ``cull`` call, without a device: returns them converted or raises ValueError."""
+    max_err2, cos_min_angle = float(max_err2), float(cos_min_angle)
+    if not max_err2 >= 0.0:
+        raise ValueError("max_err2 must be >= 0 (inf switches the test off), got %r" % max_err2)
+    if not cos_min_angle >= -1.0:
+        raise ValueError("cos_min_angle must be >= -1 (>= 1 switches the test off), got %r" % cos_min_angle)
+    if int(min_obs) != min_obs or min_obs < 0:
+        raise ValueError("min_obs must be an integer >= 0, got %r" % (min_obs,))
+    if int(group) not in TRACK_GROUPS:
+        raise ValueError("group must be one of %s, got %r" % (TRACK_GROUPS, group))
+    if cam_scale is not None:
+        cam_scale = f64(cam_scale)
+        if cam_scale.shape != (int(n_cams),):
+            raise ValueError("cam_scale must be (n_cams,) with n_cams = %d, got %s" % (n_cams, cam_scale.shape))
+        if not np.all(np.isfinite(cam_scale)):
+            raise ValueError("cam_scale must be finite")
+    return max_err2, cos_min_angle, int(min_obs), cam_scale, int(group)
 
 
 def tri_tracks(pt_ptr, cam_idx, uv, projs, X_init=None, mode=TRACKS_NONLINEAR, lam=0.5, iters=100, group=0):
@@ -706,11 +732,14 @@ class BaProblem:
             self._read_sizes()
         return action.value, int(n_new.value)
 
-    def structure(self):
-        """(pt_ptr (N+1,), cam_idx (M,), uv_norm (2, M)): the resident observation list (sfm_ba_get_structure)."""
+    def structure(self, want_uv=True):
+        """(pt_ptr (N+1,), cam_idx (M,), uv_norm (2, M)): the resident observation list (sfm_ba_get_structure);
+        ``want_uv=False`` leaves the keys on the device and returns None in their place."""
         n, m = self.info(INFO_N_PTS), self.info(INFO_N_OBS)
-        pt_ptr, cam_idx, uv = np.zeros(n + 1, dtype=np.int32), np.zeros(m, dtype=np.int32), np.zeros((2, m))
-        check(self._lib.sfm_ba_get_structure(self._h, iptr(pt_ptr), iptr(cam_idx) if m else None, dptr(uv) if m else None))
+        pt_ptr, cam_idx = np.zeros(n + 1, dtype=np.int32), np.zeros(m, dtype=np.int32)
+        uv = np.zeros((2, m)) if want_uv else None
+        check(self._lib.sfm_ba_get_structure(self._h, iptr(pt_ptr), iptr(cam_idx) if m else None,
+                                             dptr(uv) if m and want_uv else None))
         return pt_ptr, cam_idx, uv
 
     def close(self):
@@ -824,6 +853,39 @@ class BaProblem:
         cost = np.zeros((2, n)); status = np.zeros(n, dtype=np.int32)
         check(self._lib.sfm_ba_refine_points(self._h, mode, float(lam), iters, group, dptr(cost), iptr(status)))
         return cost, status
+
+    def _screen(self, name, max_err2, cos_min_angle, min_obs, cam_scale, want_outputs, group):
+        from types import SimpleNamespace
+        max_err2, cos_min_angle, min_obs, cam_scale, group = check_screen(self.n_cams, max_err2, cos_min_angle, min_obs,
+                                                                          cam_scale, group)
+        n, m = self.info(INFO_N_PTS), self.info(INFO_N_OBS)
+        summary = np.zeros(8, dtype=np.int64)
+        out = SimpleNamespace(err2=None, depth=None, obs_flags=None, min_cos=None, pt_flags=None, summary=summary)
+        if want_outputs:
+            out.err2, out.depth, out.obs_flags = np.zeros(m), np.zeros(m), np.zeros(m, dtype=np.uint8)
+            out.min_cos, out.pt_flags = np.ones(n), np.zeros(n, dtype=np.int32)
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        check(getattr(self._lib, name)(self._h, max_err2, cos_min_angle, min_obs, group,
+                                         dptr(cam_scale) if cam_scale is not None else None,
+                                         dptr(out.err2) if want_outputs else None, dptr(out.depth) if want_outputs else None,
+                                         out.obs_flags.ctypes.data_as(u8) if want_outputs else None,
+                                         dptr(out.min_cos) if want_outputs else None,
+                                         iptr(out.pt_flags) if want_outputs else None, summary.ctypes.data_as(_lp)))
+        return out
+
+    def screen(self, max_err2=float("inf"), cos_min_angle=1.0, min_obs=2, cam_scale=None, want_outputs=True, group=0):
+        """Judge every observation and point of the resident scene at its current state (sfm_ba_screen) without changing
+        anything: returns a namespace with ``err2`` (M,), ``depth`` (M,), ``obs_flags`` (M,) uint8 of ``OBS_*`` bits,
+        ``min_cos`` (N,), ``pt_flags`` (N,) of ``PT_*`` bits and ``summary`` (8,) int64 in the order of ``SCREEN_SUMMARY``.
+        ``cam_scale`` (V,) multiplies a camera's residuals (None: 1); ``want_outputs=False`` downloads the summary only."""
+        return self._screen("sfm_ba_screen", max_err2, cos_min_angle, min_obs, cam_scale, want_outputs, group)
+
+    def cull(self, max_err2=float("inf"), cos_min_angle=1.0, min_obs=2, cam_scale=None, want_outputs=True, group=0):
+        """``screen``, then remove what failed from the resident scene on the device (sfm_ba_cull): the report describes the
+        scene before the cull, ``obs_flags == 0`` marks what remains.  Cameras, points and their indices are unchanged."""
+        out = self._screen("sfm_ba_cull", max_err2, cos_min_angle, min_obs, cam_scale, want_outputs, group)
+        self.n_obs = self.info(INFO_N_OBS)
+        return out
 
     def points_ptr(self):
         """Device pointers (px, py, pz) of the resident points and their count (sfm_ba_points_ptr)."""

@@ -60,6 +60,25 @@ def build_observations(self_rows, n_pts):
     return pt_ptr, cam_idx.astype(np.int32), pt_idx.astype(np.int32), key_idx.astype(np.int32)
 
 
+def remove_pairs(observations, pt_gone, cam_gone):
+    """``build_observations``' output (pt_ptr, cam_idx, pt_idx, key_idx) without the given (point, camera) pairs: the list a
+    resident scene is rebuilt from after ``HipBaMixin.filter_structure`` has removed observations.  Pairs the list does not
+    hold are ignored; the order of what stays is unchanged."""
+    pt_ptr, cam_idx, pt_idx, key_idx = observations
+    pt_gone = np.asarray(pt_gone, dtype=np.int64).ravel()
+    cam_gone = np.asarray(cam_gone, dtype=np.int64).ravel()
+    if pt_gone.shape[0] != cam_gone.shape[0]:
+        raise ValueError("remove_pairs: %d points but %d cameras" % (pt_gone.shape[0], cam_gone.shape[0]))
+    if pt_gone.size == 0 or cam_idx.size == 0:
+        return observations
+    n_cams = int(max(cam_idx.max(), cam_gone.max())) + 1
+    keep = ~np.isin(pt_idx.astype(np.int64) * n_cams + cam_idx, pt_gone * n_cams + cam_gone)
+    n_pts = pt_ptr.shape[0] - 1
+    new_ptr = np.zeros(n_pts + 1, dtype=np.int32)
+    np.cumsum(np.bincount(pt_idx[keep], minlength=n_pts), out=new_ptr[1:])
+    return new_ptr, cam_idx[keep], pt_idx[keep], key_idx[keep]
+
+
 def gather_normalised_keys(views, cam_idx, key_idx):
     """uv_norm (2, M): ``inv(view.k) @ [u, v, 1]`` divided by its third component, per observation
     (ba_processor.py:339-342).  ``views[c].key_pts[k].pt`` is the pixel key."""

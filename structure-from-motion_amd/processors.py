@@ -32,7 +32,7 @@ import numpy as np
 
 from . import matching, native
 from .geometry import (normalise_pixels, pack_cameras, quaternion_to_rotation_unchecked, quaternions_to_rotations)
-from .observations import KeyCache, ObservationTracker, build_observations, gather_normalised_keys
+from .observations import KeyCache, ObservationTracker, build_observations, gather_normalised_keys, remove_pairs
 from .q13 import det_branch_fires, reference_winner
 from .sampling import sample_indices
 
@@ -361,6 +361,9 @@ class _ResidentScene:
         self.from_device = False  # the structure came from the tracker's device tables (ba_device_tracks): the host picture above is not kept
         self.retired_bytes = 0    # upload bytes of problems this scene has replaced
         self.cams_synced = False  # the device cameras are the views' poses as the last update left them (no iteration since)
+        # (point, camera) pairs filter_structure has removed: the tracker keeps the uncut picture, a rebuild leaves them out
+        self.culled_pt = np.empty(0, dtype=np.int64)
+        self.culled_cam = np.empty(0, dtype=np.int64)
 
     def close(self):
         if self.prob is not None:
@@ -460,7 +463,8 @@ class HipBaMixin:
             self.ba_last_action = "append"
         else:
             scene.close()
-            pt_ptr, cam_idx, _pt_idx, key_idx = scene.tracker.reset(rows, tri_num)             # ba:309
+            pt_ptr, cam_idx, _pt_idx, key_idx = remove_pairs(scene.tracker.reset(rows, tri_num),                # ba:309
+                                                             scene.culled_pt, scene.culled_cam)
             uv_norm = scene.keys.gather_normalised(views, cam_idx, key_idx)
             scene.prob = native.BaProblem(view_num, pt_ptr, cam_idx, uv_norm)
             scene.pts_written = None
@@ -597,6 +601,82 @@ class HipBaMixin:
         scene.rots_written, scene.locs_written = init_rots, init_locs      # the poses the device cameras were brought up to
         tri_pts[0:3, :] = pts
         return cost, status
+
+    def _ba_screen_scene(self, who, max_reproj_px, min_angle_deg, min_obs):
+        """The resident scene brought up to date as ``refine_structure`` does, and the native arguments of a screening:
+        (scene, max_err2, cos_min_angle, cam_scale)."""
+        if not self.ba_resident:
+            raise TypeError("{} needs ba_resident".format(who))
+        if max_reproj_px is not None and not float(max_reproj_px) >= 0.0:
+            raise ValueError("max_reproj_px must be >= 0 or None, got {!r}".format(max_reproj_px))
+        if min_angle_deg is not None and not 0.0 <= float(min_angle_deg) <= 180.0:
+            raise ValueError("min_angle_deg must be in [0, 180] or None, got {!r}".format(min_angle_deg))
+        max_err2 = float("inf") if max_reproj_px is None else float(max_reproj_px) ** 2
+        cos_min_angle = 1.0 if min_angle_deg is None else math.cos(math.radians(float(min_angle_deg)))
+        native.check_screen(0, max_err2, cos_min_angle, min_obs, None)      # before anything reaches the device
+        views = self.view_processor.view_list
+        init_rots = np.stack([np.asarray(v.rot, dtype=np.float64) for v in views])
+        init_locs = np.stack([np.asarray(v.loc, dtype=np.float64).reshape(3) for v in views])
+        init_tri_pts = np.ascontiguousarray(self.tri_processor.tri_pts[0:3, :], dtype=np.float64)
+        scene = self._ba_update_resident(views, init_rots, init_locs, init_tri_pts)
+        # what the device holds now, so that the next call uploads nothing again (as refine_structure records it)
+        scene.pts_written = init_tri_pts.copy()
+        scene.rots_written, scene.locs_written = init_rots, init_locs
+        cam_scale = np.array([math.sqrt(abs(float(v.k[0, 0]) * float(v.k[1, 1]))) for v in views])
+        return scene, max_err2, cos_min_angle, cam_scale
+
+    @staticmethod
+    def _ba_screen_report(report):
+        report.err_px = np.sqrt(report.err2)
+        report.min_angle_deg = np.degrees(np.arccos(np.clip(report.min_cos, -1.0, 1.0)))
+        return report
+
+    def screen_structure(self, max_reproj_px=None, min_angle_deg=None, min_obs=2):
+        """Judge the resident scene without changing it (``BaProblem.screen``), after it has been brought up to date exactly
+        as ``refine_structure`` does: reprojection error and depth per observation, surviving observations and widest
+        triangulation angle per point.  Returns the native report (``err2``, ``depth``, ``obs_flags``, ``min_cos``,
+        ``pt_flags``, ``summary``; observations in the order of ``prob.structure()``) with ``err_px = sqrt(err2)`` and
+        ``min_angle_deg`` added.  ``None`` switches a test off.
+
+        The pixel threshold scales the normalised residual of view v by ``sqrt(|k[0, 0] k[1, 1]|)``: exact for square pixels
+        without skew; for the UPENN intrinsics the test scenes use, the two focal lengths differ from it by 7e-6 relative.
+        Neither the device state nor ``tri_pts``, the views or the track tables change.  Needs ``ba_resident``; nothing in
+        ``process()`` calls it."""
+        if self.ba_device_tracks:
+            self._ba_check_device_tracks()
+        scene, max_err2, cos_min_angle, cam_scale = self._ba_screen_scene("screen_structure", max_reproj_px, min_angle_deg, min_obs)
+        try:
+            return self._ba_screen_report(scene.prob.screen(max_err2, cos_min_angle, min_obs, cam_scale))
+        except Exception:
+            self.ba_release()
+            raise
+
+    def filter_structure(self, max_reproj_px=4.0, min_angle_deg=1.5, min_obs=2):
+        """``screen_structure``, then remove what failed from the resident scene on the device (``BaProblem.cull``): the
+        observations whose reprojection error exceeds ``max_reproj_px`` or that lie behind their camera, and the points
+        left with fewer than ``min_obs`` observations or with no pair of rays ``min_angle_deg`` apart.  Returns the report,
+        which describes the scene before the cull (``obs_flags == 0`` marks what remains).
+
+        ``tri_pts``, the views and the track tables stay as they are -- the reference's object model has no removed
+        observation; a point that lost its track keeps its index and simply stops moving.  The removed (point, camera)
+        pairs are remembered with the resident scene: later growth appends to the culled scene, a later rebuild leaves
+        the pairs out, ``ba_release()`` forgets them.  Not available with ``ba_device_tracks`` (the device-built list
+        would differ from the culled scene and replace it).  Needs ``ba_resident``; nothing in ``process()`` calls it."""
+        if self.ba_device_tracks:
+            raise TypeError("filter_structure does not support ba_device_tracks")
+        scene, max_err2, cos_min_angle, cam_scale = self._ba_screen_scene("filter_structure", max_reproj_px, min_angle_deg, min_obs)
+        try:
+            pt_ptr, cam_idx, _uv = scene.prob.structure(want_uv=False)
+            report = scene.prob.cull(max_err2, cos_min_angle, min_obs, cam_scale)
+        except Exception:
+            self.ba_release()
+            raise
+        gone = np.flatnonzero(report.obs_flags)
+        if gone.size:
+            pt_of = np.repeat(np.arange(pt_ptr.shape[0] - 1, dtype=np.int64), np.diff(pt_ptr))
+            scene.culled_pt = np.concatenate((scene.culled_pt, pt_of[gone]))
+            scene.culled_cam = np.concatenate((scene.culled_cam, cam_idx[gone].astype(np.int64)))
+        return self._ba_screen_report(report)
 
     def execute_bundle_adjustment(self):
         if self.ba_device_tracks:
