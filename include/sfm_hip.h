@@ -80,6 +80,11 @@ extern "C" {
                                  * ~6 us stream bubbles on this stack, so a measurement that must not disturb what it measures samples */
 #define SFM_OPT_TIMING       2  /* bitmask (1 << SFM_K_x): bracket those kernel classes with hipEvents */
 
+/* ---- robust loss of the resident bundle adjustment (sfm_ba_set_loss) -------------------------- */
+#define SFM_LOSS_NONE    0  /* plain sum of squares, as the reference (ba_processor.py:376) */
+#define SFM_LOSS_HUBER   1  /* rho(s) = s for s <= 1, else 2 sqrt(s) - 1;  w(s) = 1 for s <= 1, else 1 / sqrt(s) */
+#define SFM_LOSS_CAUCHY  2  /* rho(s) = log1p(s);  w(s) = 1 / (1 + s) */
+
 /* ---- items of sfm_ba_info -------------------------------------------------------------------------- */
 #define SFM_INFO_SCHUR_KERNEL  1  /* SFM_SCHUR_PAIRS / SFM_SCHUR_MFMA / SFM_SCHUR_ROWS: the product kernel the next iteration launches
                                    * (asking builds the row-panel product's work split if that is the candidate, so the answer is
@@ -304,6 +309,27 @@ int sfm_ba_iterate(sfm_ba_problem* p, double lambda, int iters, int quirks);
  * set_cameras / set_points / append start a new history; at most 256 iterations are kept).  sqrt(cost / M) is the RMS
  * residual; in a sharded run every rank reports its own observations.  Synchronises. */
 int sfm_ba_get_stats(sfm_ba_problem* p, double* cost /*[max_iters]*/, int max_iters, int* n_iters);
+/* Robust loss inside the linearisation.  With e_o = |b - f|^2 of observation o (normalised image coordinates) and
+ * s_o = e_o / delta^2, the iterations minimise delta^2 sum_o rho(s_o) instead of sum_o e_o: every iteration is the same
+ * damped Gauss-Newton step on the reweighted problem (IRLS: r, Jp, Jx of an observation are scaled by sqrt(w(s_o)) at the
+ * linearisation point; no second-order correction), in sfm_ba_iterate, in the split sfm_ba_linearize_reduce /
+ * sfm_ba_solve_update and with a communicator alike.  lambda, the quirks, the Schur products, the reduced solve and the
+ * camera update only ever see weighted blocks.  While a loss is set sfm_ba_get_stats reports delta^2 sum rho(s).
+ *   delta is in normalised units (pixels / focal scale), finite and > 0; it is ignored for SFM_LOSS_NONE.  A bad kind or
+ *   delta returns SFM_E_SHAPE and leaves the problem as it was.
+ *   The call completes a deferred back substitution with the OLD loss, drops captured graphs and restarts the cost
+ *   history (as sfm_ba_set_points does); it uploads nothing.  The loss belongs to the handle: it survives sfm_ba_append,
+ *   sfm_ba_cull and sfm_ba_sync_tracks like the options.  With SFM_LOSS_NONE (the default) the iterations launch the very
+ *   kernels they launched before this call existed.
+ * Plain least squares regardless of this setting: sfm_ba_solve, sfm_ba_refine_points, sfm_ba_screen / sfm_ba_cull's
+ * errors, and the PnP and triangulation solvers. */
+int sfm_ba_set_loss(sfm_ba_problem* p, int kind, double delta);
+int sfm_ba_get_loss(sfm_ba_problem* p, int* kind, double* delta);
+/* Parity hook: s_o, w(s_o), rho(s_o) of every observation at the current state, in the resident (point, camera) order, from
+ * the device function the iteration kernels weight with.  With SFM_LOSS_NONE: s = e, w = 1, rho = e.  Completes a deferred
+ * back substitution and expands the cameras if needed; changes nothing else.  Synchronises. */
+int sfm_ba_loss_terms(sfm_ba_problem* p, double* s /*host [M] or NULL*/, double* w /*host [M] or NULL*/,
+                      double* rho /*host [M] or NULL*/);
 /* Synchronise, copy the state back, and report the first device-side failure (bad rotation ...). */
 int sfm_ba_get_state(sfm_ba_problem* p, double* cams, double* pts);
 /* sfm_ba_get_state plus R(q) of every camera (what ba_processor.py:412 computes from the refined quaternions with
@@ -485,6 +511,11 @@ int sfm_ba_reduced_system(int V, int N, int64_t M, const int* pt_ptr, const int*
                           const double* uv_norm, const double* cams, const double* pts,
                           double lambda, int quirks, int schur_mode,
                           double* S /*[7V][7V]*/, double* rhs /*[7V]*/);
+/* sfm_ba_reduced_system of the reweighted problem (sfm_ba_set_loss(kind, delta) before the linearisation). */
+int sfm_ba_reduced_system_loss(int V, int N, int64_t M, const int* pt_ptr, const int* cam_idx,
+                               const double* uv_norm, const double* cams, const double* pts,
+                               double lambda, int quirks, int schur_mode, int loss_kind, double loss_delta,
+                               double* S /*[7V][7V]*/, double* rhs /*[7V]*/);
 
 /* ---- descriptor matching: KeyTracker.__extend_list (key_tracker.py:213-317) ------------------------------------
  * cv2.BFMatcher.knnMatch / .match of the new view's descriptors against every earlier view (key_tracker.py:248-263),

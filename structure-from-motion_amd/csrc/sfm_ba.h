@@ -259,6 +259,8 @@ struct sfm_ba_problem : sfm::BaScene {
   int deterministic = 0;     // SFM_OPT_DETERMINISTIC: fixed summation order everywhere (bitwise repeatable results)
   int timing = 0;            // bitmask over SFM_K_* of the kernel classes bracketed by hipEvents
   int timing_stride = 1;     // ... every stride-th time they run (an event pair costs ~11 us of stream bubbles on this stack)
+  int loss_kind = SFM_LOSS_NONE;  // sfm_ba_set_loss: which instantiation of ba_linearize / ba_backsub an iteration launches
+  double loss_delta = 1.0;        // ... and its scale, in normalised units (unused without a loss)
   sfm_comm* comm = nullptr;  // library-owned RCCL communicator (sfm_ba_set_comm): the iterations all-reduce [S | rhs] themselves
   unsigned long long* stamps = nullptr;   // [1024] diagnostic shader-clock stamps, allocated when SFM_OPT_DEBUG bit 8 is first set
   // SFM_OPT_GRAPH: the steady-state iteration body (fused linearise + Schur + reduce + solve) captured once per
@@ -310,5 +312,6 @@ int ba_flow_setup(BaScene& sc, hipStream_t s);      // sfm_ba_solve.hip: flag wo
 int comm_all_reduce_f64(sfm_comm* comm, double* buf, size_t count, hipStream_t s);      // sfm_comm.hip
 int comm_attach(sfm_comm* comm, int delta);      // a problem takes (+1) / gives back (-1) its hold on a communicator
 void ba_enqueue_residual_jacobian(sfm_ba_problem* p, int quirks, double* r, double* Jp, double* Jx);
+void ba_enqueue_loss_terms(sfm_ba_problem* p, int quirks, double* s, double* w, double* rho);
 void ba_enqueue_symmetrize(sfm_ba_problem* p, double lambda, double* S_out, double* rhs_out);
 }  // namespace sfm

@@ -56,6 +56,42 @@ __device__ __forceinline__ void load_cam(CamPrep& dst, const CamPrep* src) {
   for (int k = 0; k < 19; ++k) d[k] = s[k];
 }
 
+// Robust loss (sfm_ba_set_loss) as a compile-time switch: LOSS = SFM_LOSS_NONE instantiates exactly the plain least-squares
+// kernels (LossArg<0> is empty, obs_terms_loss<0> is obs_terms).  With a loss every observation's r, Jp, Jx are scaled
+// by sqrt(w(s)), s = |b - f|^2 / delta^2 at the linearisation point: one IRLS step, no second-order correction.
+template <int LOSS> struct LossArg { double inv_d2, d2; };      // 1 / delta^2, delta^2
+template <> struct LossArg<SFM_LOSS_NONE> {};
+
+// s -> w, sqrt(w), rho.  Huber: s <= 1 is the quadratic zone (w = 1 exactly, no reciprocal square root of 0);
+// a NaN s fails the comparison and comes out as NaN weights, as a NaN residual does without a loss.
+template <int LOSS>
+__device__ __forceinline__ void loss_eval(double s, double& w, double& sw, double& rho) {
+  if (LOSS == SFM_LOSS_HUBER) {
+    if (s <= 1.0) { w = 1.0; sw = 1.0; rho = s; }
+    else { const double q = sqrt(s); w = 1.0 / q; sw = 1.0 / sqrt(q); rho = 2.0 * q - 1.0; }
+  } else {
+    const double t = 1.0 + s;
+    w = 1.0 / t; sw = 1.0 / sqrt(t); rho = log1p(s);
+  }
+}
+
+// obs_terms, reweighted; rho_d2 = delta^2 rho(s), this observation's share of the robust cost.
+template <int LOSS>
+__device__ __forceinline__ void obs_terms_loss(const CamPrep& c, double X, double Y, double Z, double u, double v, int quirks,
+                                               const LossArg<LOSS>& la, double* r, double* Jp, double* Jx, double& rho_d2) {
+  obs_terms(c, X, Y, Z, u, v, quirks, r, Jp, Jx);
+  if constexpr (LOSS != SFM_LOSS_NONE) {
+    double w, sw, rho;
+    loss_eval<LOSS>((r[0] * r[0] + r[1] * r[1]) * la.inv_d2, w, sw, rho);
+    rho_d2 = la.d2 * rho;
+    r[0] *= sw; r[1] *= sw;
+#pragma unroll
+    for (int k = 0; k < 14; ++k) Jp[k] *= sw;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) Jx[k] *= sw;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // ba_linearize: G lanes per point (G = power of two <= 64 chosen from the mean track length).
 // LDS_MODE 2: [V][19] prepared cameras + [V][35] camera-side accumulators in LDS (V <= 151);
@@ -69,8 +105,10 @@ __device__ __forceinline__ void load_cam(CamPrep& dst, const CamPrep* src) {
 // ---------------------------------------------------------------------------------------------
 // THREADS = 64 (one wave per workgroup) is the deterministic variant: the camera accumulators in LDS then receive
 // their ds_add_f64 from a single instruction stream, in program order.
-template <int G, int LDS_MODE, bool DENSE_Z, bool FUSED, int THREADS = 256>
-__global__ __launch_bounds__(THREADS) void ba_linearize_kernel(BaDev d, int cur, double lambda, int quirks) {
+// LOSS: robust loss of the linearisation AND of the fused back substitution (which recomputes the weights at the old state,
+// i.e. the weights the previous linearisation used); its delta rides in the trailing argument, empty without a loss.
+template <int G, int LDS_MODE, bool DENSE_Z, bool FUSED, int THREADS = 256, int LOSS = SFM_LOSS_NONE>
+__global__ __launch_bounds__(THREADS) void ba_linearize_kernel(BaDev d, int cur, double lambda, int quirks, LossArg<LOSS> la) {
   static_assert(!FUSED || LDS_MODE == 2, "the fused kernel keeps both camera sets in LDS");
   extern __shared__ double lds[];
   unsigned long long* stamp = (d.stamps && blockIdx.x == 0 && threadIdx.x == 0) ? d.stamps + 192 : nullptr;
@@ -105,7 +143,7 @@ __global__ __launch_bounds__(THREADS) void ba_linearize_kernel(BaDev d, int cur,
   const int grp = threadIdx.x / G;
   double* S = d.red;
   double* rhs = d.red + red_rhs_off(d.nbk);
-  double cost = 0.0;                           // sum |b - f|^2 of this lane's observations (sfm_ba_get_stats)
+  double cost = 0.0;                           // sum |b - f|^2 (LOSS: delta^2 rho) of this lane's observations (sfm_ba_get_stats)
 
   for (int p0 = blockIdx.x * GPB; p0 < d.N; p0 += gridDim.x * GPB) {
     const int p = p0 + grp;
@@ -117,6 +155,7 @@ __global__ __launch_bounds__(THREADS) void ba_linearize_kernel(BaDev d, int cur,
     }
     const bool single = (end - beg) <= G;       // the whole track fits the lane group: every lane keeps its observation
     double r[2], Jp[14], Jx[6];
+    double rho = 0;                             // delta^2 rho(s) of the lane's observation (LOSS only)
     int cam = 0;
     double uo = 0, vo = 0;
     const int o1 = beg + lane_g;
@@ -127,7 +166,7 @@ __global__ __launch_bounds__(THREADS) void ba_linearize_kernel(BaDev d, int cur,
         if (!single) { cam = d.cam_idx[o]; uo = d.u[o]; vo = d.v[o]; }
         CamPrep c;
         load_cam(c, reinterpret_cast<const CamPrep*>(lds_old) + cam);
-        obs_terms(c, X, Y, Z, uo, vo, quirks, r, Jp, Jx);
+        obs_terms_loss<LOSS>(c, X, Y, Z, uo, vo, quirks, la, r, Jp, Jx, rho);
         const double* dp = lds_delta + 7 * cam;
         double e0 = r[0], e1 = r[1];               // r - Jp dp
 #pragma unroll
@@ -160,7 +199,7 @@ __global__ __launch_bounds__(THREADS) void ba_linearize_kernel(BaDev d, int cur,
       if (!single) { cam = d.cam_idx[o]; uo = d.u[o]; vo = d.v[o]; }
       CamPrep c;
       load_cam(c, PREP_LDS ? reinterpret_cast<const CamPrep*>(lds_prep) + cam : gprep + cam);
-      obs_terms(c, X, Y, Z, uo, vo, quirks, r, Jp, Jx);
+      obs_terms_loss<LOSS>(c, X, Y, Z, uo, vo, quirks, la, r, Jp, Jx, rho);
       v6[0] += Jx[0] * Jx[0] + Jx[3] * Jx[3];
       v6[1] += Jx[1] * Jx[0] + Jx[4] * Jx[3];
       v6[2] += Jx[1] * Jx[1] + Jx[4] * Jx[4];
@@ -192,7 +231,7 @@ __global__ __launch_bounds__(THREADS) void ba_linearize_kernel(BaDev d, int cur,
         cam = d.cam_idx[o];
         CamPrep c;
         load_cam(c, PREP_LDS ? reinterpret_cast<const CamPrep*>(lds_prep) + cam : gprep + cam);
-        obs_terms(c, X, Y, Z, d.u[o], d.v[o], quirks, r, Jp, Jx);
+        obs_terms_loss<LOSS>(c, X, Y, Z, d.u[o], d.v[o], quirks, la, r, Jp, Jx, rho);
       }
       double acc[35];
       {
@@ -233,7 +272,8 @@ __global__ __launch_bounds__(THREADS) void ba_linearize_kernel(BaDev d, int cur,
           zo[20] = zz[20];
         }
       }
-      cost += r[0] * r[0] + r[1] * r[1];
+      if constexpr (LOSS == SFM_LOSS_NONE) cost += r[0] * r[0] + r[1] * r[1];
+      else cost += rho;                        // r is weighted here: the robust cost comes from the unweighted residual
       // rhs_c -= W V^-1 g = Jp^T (Jx h) with h = V^-1 g: folded into the residual, e = r - Jx h
       const double e0 = r[0] - (Jx[0] * h0 + Jx[1] * h1 + Jx[2] * h2);
       const double e1 = r[1] - (Jx[3] * h0 + Jx[4] * h1 + Jx[5] * h2);
@@ -293,8 +333,8 @@ __global__ __launch_bounds__(THREADS) void ba_linearize_kernel(BaDev d, int cur,
 // ba_backsub: dX_p = V_p^-1 (g_p - sum_o W_o^T dp_c), recomputing the linearisation at the
 // iteration's starting state (prep[cur] and the not-yet-updated points).
 // ---------------------------------------------------------------------------------------------
-template <int G, bool CAMS_IN_LDS>
-__global__ __launch_bounds__(256) void ba_backsub_kernel(BaDev d, int cur, double lambda, int quirks) {
+template <int G, bool CAMS_IN_LDS, int LOSS = SFM_LOSS_NONE>
+__global__ __launch_bounds__(256) void ba_backsub_kernel(BaDev d, int cur, double lambda, int quirks, LossArg<LOSS> la) {
   extern __shared__ double lds[];
   double* lds_prep = lds;                      // V * 19
   double* lds_delta = lds + (size_t)d.V * 19;  // V * 7
@@ -327,8 +367,8 @@ __global__ __launch_bounds__(256) void ba_backsub_kernel(BaDev d, int cur, doubl
       const int cam = d.cam_idx[o];
       CamPrep c;
       load_cam(c, CAMS_IN_LDS ? reinterpret_cast<const CamPrep*>(lds_prep) + cam : gprep + cam);
-      double r[2], Jp[14], Jx[6];
-      obs_terms(c, X, Y, Z, d.u[o], d.v[o], quirks, r, Jp, Jx);
+      double r[2], Jp[14], Jx[6], rho;
+      obs_terms_loss<LOSS>(c, X, Y, Z, d.u[o], d.v[o], quirks, la, r, Jp, Jx, rho);
       const double* dp = CAMS_IN_LDS ? lds_delta + 7 * cam : d.delta + 7 * cam;
       double e0 = r[0], e1 = r[1];               // r - Jp dp
 #pragma unroll
@@ -375,6 +415,28 @@ __global__ void ba_residual_jacobian_kernel(BaDev d, int cur, int quirks, const 
   for (int k = 0; k < 6; ++k) Jx_out[6 * o + k] = Jx[k];
 }
 
+// Parity hook: s, w, rho of every observation at the current state (thread per observation), from the device function the
+// iteration kernels weight with.  Without a loss: s = |b - f|^2, w = 1, rho = s.  Any output may be null.
+template <int LOSS>
+__global__ void ba_loss_terms_kernel(BaDev d, int cur, int quirks, LossArg<LOSS> la, double* __restrict__ s_out,
+                                     double* __restrict__ w_out, double* __restrict__ rho_out) {
+  const long long o = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (o >= d.M) return;
+  const int p = d.obs_pt[o];
+  CamPrep c;
+  load_cam(c, d.prep[cur] + d.cam_idx[o]);
+  double r[2], Jp[14], Jx[6];
+  obs_terms(c, d.px[p], d.py[p], d.pz[p], d.u[o], d.v[o], quirks, r, Jp, Jx);
+  double s = r[0] * r[0] + r[1] * r[1], w = 1.0, sw = 1.0, rho = s;
+  if constexpr (LOSS != SFM_LOSS_NONE) {
+    s *= la.inv_d2;
+    loss_eval<LOSS>(s, w, sw, rho);
+  }
+  if (s_out) s_out[o] = s;
+  if (w_out) w_out[o] = w;
+  if (rho_out) rho_out[o] = rho;
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -386,38 +448,65 @@ static int pick_group(const sfm_ba_problem* p) {
   return g;
 }
 
+template <int LOSS>
+static LossArg<LOSS> loss_arg(const sfm_ba_problem* p) {
+  if constexpr (LOSS == SFM_LOSS_NONE) return {};
+  else { const double d2 = p->loss_delta * p->loss_delta; return {1.0 / d2, d2}; }
+}
+
 // `cur` = prep slot of the cameras to linearise at (FUSED: the back substitution uses the other slot)
-template <int LDS, bool WZ, bool FUSED = false>
-static void launch_linearize(const sfm_ba_problem* p, int cur, int g, int grid, size_t lds, hipStream_t s, double lambda, int quirks) {
+template <int LDS, bool WZ, bool FUSED, int LOSS>
+static void launch_linearize_loss(const sfm_ba_problem* p, int cur, int g, int grid, size_t lds, hipStream_t s, double lambda, int quirks) {
   const BaDev& d = p->dev;
+  const LossArg<LOSS> la = loss_arg<LOSS>(p);
   if (p->deterministic) {      // one wave per workgroup (ordered LDS accumulation)
     switch (g) {
-      case 4: ba_linearize_kernel<4, LDS, WZ, FUSED, 64><<<grid, 64, lds, s>>>(d, cur, lambda, quirks); break;
-      case 8: ba_linearize_kernel<8, LDS, WZ, FUSED, 64><<<grid, 64, lds, s>>>(d, cur, lambda, quirks); break;
-      case 16: ba_linearize_kernel<16, LDS, WZ, FUSED, 64><<<grid, 64, lds, s>>>(d, cur, lambda, quirks); break;
-      case 32: ba_linearize_kernel<32, LDS, WZ, FUSED, 64><<<grid, 64, lds, s>>>(d, cur, lambda, quirks); break;
-      default: ba_linearize_kernel<64, LDS, WZ, FUSED, 64><<<grid, 64, lds, s>>>(d, cur, lambda, quirks); break;
+      case 4: ba_linearize_kernel<4, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la); break;
+      case 8: ba_linearize_kernel<8, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la); break;
+      case 16: ba_linearize_kernel<16, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la); break;
+      case 32: ba_linearize_kernel<32, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la); break;
+      default: ba_linearize_kernel<64, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la); break;
     }
     return;
   }
   switch (g) {
-    case 4: ba_linearize_kernel<4, LDS, WZ, FUSED><<<grid, 256, lds, s>>>(d, cur, lambda, quirks); break;
-    case 8: ba_linearize_kernel<8, LDS, WZ, FUSED><<<grid, 256, lds, s>>>(d, cur, lambda, quirks); break;
-    case 16: ba_linearize_kernel<16, LDS, WZ, FUSED><<<grid, 256, lds, s>>>(d, cur, lambda, quirks); break;
-    case 32: ba_linearize_kernel<32, LDS, WZ, FUSED><<<grid, 256, lds, s>>>(d, cur, lambda, quirks); break;
-    default: ba_linearize_kernel<64, LDS, WZ, FUSED><<<grid, 256, lds, s>>>(d, cur, lambda, quirks); break;
+    case 4: ba_linearize_kernel<4, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la); break;
+    case 8: ba_linearize_kernel<8, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la); break;
+    case 16: ba_linearize_kernel<16, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la); break;
+    case 32: ba_linearize_kernel<32, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la); break;
+    default: ba_linearize_kernel<64, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la); break;
+  }
+}
+
+// the problem's loss picks the instantiation; without one it is the plain kernel
+template <int LDS, bool WZ, bool FUSED = false>
+static void launch_linearize(const sfm_ba_problem* p, int cur, int g, int grid, size_t lds, hipStream_t s, double lambda, int quirks) {
+  switch (p->loss_kind) {
+    case SFM_LOSS_HUBER: launch_linearize_loss<LDS, WZ, FUSED, SFM_LOSS_HUBER>(p, cur, g, grid, lds, s, lambda, quirks); break;
+    case SFM_LOSS_CAUCHY: launch_linearize_loss<LDS, WZ, FUSED, SFM_LOSS_CAUCHY>(p, cur, g, grid, lds, s, lambda, quirks); break;
+    default: launch_linearize_loss<LDS, WZ, FUSED, SFM_LOSS_NONE>(p, cur, g, grid, lds, s, lambda, quirks); break;
+  }
+}
+
+template <bool LDS, int LOSS>
+static void launch_backsub_loss(const sfm_ba_problem* p, int g, int grid, size_t lds, hipStream_t s, double lambda, int quirks) {
+  const BaDev& d = p->dev;
+  const LossArg<LOSS> la = loss_arg<LOSS>(p);
+  switch (g) {
+    case 4: ba_backsub_kernel<4, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la); break;
+    case 8: ba_backsub_kernel<8, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la); break;
+    case 16: ba_backsub_kernel<16, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la); break;
+    case 32: ba_backsub_kernel<32, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la); break;
+    default: ba_backsub_kernel<64, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la); break;
   }
 }
 
 template <bool LDS>
 static void launch_backsub(const sfm_ba_problem* p, int g, int grid, size_t lds, hipStream_t s, double lambda, int quirks) {
-  const BaDev& d = p->dev;
-  switch (g) {
-    case 4: ba_backsub_kernel<4, LDS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks); break;
-    case 8: ba_backsub_kernel<8, LDS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks); break;
-    case 16: ba_backsub_kernel<16, LDS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks); break;
-    case 32: ba_backsub_kernel<32, LDS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks); break;
-    default: ba_backsub_kernel<64, LDS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks); break;
+  switch (p->loss_kind) {
+    case SFM_LOSS_HUBER: launch_backsub_loss<LDS, SFM_LOSS_HUBER>(p, g, grid, lds, s, lambda, quirks); break;
+    case SFM_LOSS_CAUCHY: launch_backsub_loss<LDS, SFM_LOSS_CAUCHY>(p, g, grid, lds, s, lambda, quirks); break;
+    default: launch_backsub_loss<LDS, SFM_LOSS_NONE>(p, g, grid, lds, s, lambda, quirks); break;
   }
 }
 
@@ -615,6 +704,18 @@ int ba_enqueue_iterations(sfm_ba_problem* p, double lambda, int iters, int quirk
 void ba_enqueue_residual_jacobian(sfm_ba_problem* p, int quirks, double* r, double* Jp, double* Jx) {
   const BaDev& d = p->dev;
   ba_residual_jacobian_kernel<<<(unsigned)((d.M + 255) / 256), 256, 0, p->stream>>>(d, p->cur, quirks, d.obs_pt, r, Jp, Jx);
+}
+
+
+// parity hook (sfm_ba_loss_terms): device outputs of length M, any of them null
+void ba_enqueue_loss_terms(sfm_ba_problem* p, int quirks, double* s_out, double* w_out, double* rho_out) {
+  const BaDev& d = p->dev;
+  const unsigned grid = (unsigned)((d.M + 255) / 256);
+  switch (p->loss_kind) {
+    case SFM_LOSS_HUBER: ba_loss_terms_kernel<SFM_LOSS_HUBER><<<grid, 256, 0, p->stream>>>(d, p->cur, quirks, loss_arg<SFM_LOSS_HUBER>(p), s_out, w_out, rho_out); break;
+    case SFM_LOSS_CAUCHY: ba_loss_terms_kernel<SFM_LOSS_CAUCHY><<<grid, 256, 0, p->stream>>>(d, p->cur, quirks, loss_arg<SFM_LOSS_CAUCHY>(p), s_out, w_out, rho_out); break;
+    default: ba_loss_terms_kernel<SFM_LOSS_NONE><<<grid, 256, 0, p->stream>>>(d, p->cur, quirks, loss_arg<SFM_LOSS_NONE>(p), s_out, w_out, rho_out); break;
+  }
 }
 
 }  // namespace sfm

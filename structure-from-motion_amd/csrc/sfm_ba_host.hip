@@ -538,6 +538,44 @@ int sfm_ba_set_state(sfm_ba_problem* p, const double* cams, const double* pts) {
   return SFM_OK;
 }
 
+int sfm_ba_set_loss(sfm_ba_problem* p, int kind, double delta) {
+  SFM_TRY(check_problem(p));
+  if (kind != SFM_LOSS_NONE && kind != SFM_LOSS_HUBER && kind != SFM_LOSS_CAUCHY) { set_error("sfm_ba_set_loss: unknown loss %d", kind); return SFM_E_SHAPE; }
+  if (kind != SFM_LOSS_NONE && !(delta > 0 && delta <= 1.7976931348623157e308)) { set_error("sfm_ba_set_loss: delta must be finite and > 0"); return SFM_E_SHAPE; }
+  SFM_TRY(ba_flush(p));        // the pending step was solved for the old loss: its back substitution takes the old weights
+  ba_graph_drop(p);            // the captured bodies hold the old instantiation and its delta
+  SFM_TRY(ba_reset_stats(p));  // the cost changes meaning
+  p->loss_kind = kind;
+  if (kind != SFM_LOSS_NONE) p->loss_delta = delta;
+  return SFM_OK;
+}
+
+int sfm_ba_get_loss(sfm_ba_problem* p, int* kind, double* delta) {
+  SFM_TRY(check_problem(p));
+  if (kind) *kind = p->loss_kind;
+  if (delta) *delta = p->loss_delta;
+  return SFM_OK;
+}
+
+int sfm_ba_loss_terms(sfm_ba_problem* p, double* s, double* w, double* rho) {
+  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_flush(p));
+  if (!p->prep_valid) SFM_TRY(ba_enqueue_prep(p));
+  const size_t m = (size_t)p->dev.M;
+  if (m == 0) return stream_sync(p->stream);
+  hipStream_t st = p->stream;
+  DevBuf<double> ds, dw, drho;
+  if (s) SFM_TRY(ds.alloc(m, st));
+  if (w) SFM_TRY(dw.alloc(m, st));
+  if (rho) SFM_TRY(drho.alloc(m, st));
+  ba_enqueue_loss_terms(p, p->quirks, s ? ds.p : nullptr, w ? dw.p : nullptr, rho ? drho.p : nullptr);
+  SFM_HIP(hipGetLastError());
+  if (s) SFM_TRY(ds.download(s, m, st));
+  if (w) SFM_TRY(dw.download(w, m, st));
+  if (rho) SFM_TRY(drho.download(rho, m, st));
+  return stream_sync(st);
+}
+
 int sfm_ba_get_stats(sfm_ba_problem* p, double* cost, int max_iters, int* n_iters) {
   SFM_TRY(check_problem(p));
   if (max_iters < 0 || (max_iters > 0 && cost == nullptr)) { set_error("sfm_ba_get_stats: bad output buffer"); return SFM_E_SHAPE; }
@@ -897,10 +935,17 @@ int sfm_ba_residual_jacobian(int V, int N, int64_t M, const int* pt_ptr, const i
 int sfm_ba_reduced_system(int V, int N, int64_t M, const int* pt_ptr, const int* cam_idx, const double* uv_norm,
                           const double* cams, const double* pts, double lambda, int quirks, int schur_mode, double* S,
                           double* rhs) {
+  return sfm_ba_reduced_system_loss(V, N, M, pt_ptr, cam_idx, uv_norm, cams, pts, lambda, quirks, schur_mode, SFM_LOSS_NONE, 0.0, S, rhs);
+}
+
+int sfm_ba_reduced_system_loss(int V, int N, int64_t M, const int* pt_ptr, const int* cam_idx, const double* uv_norm,
+                               const double* cams, const double* pts, double lambda, int quirks, int schur_mode,
+                               int loss_kind, double loss_delta, double* S, double* rhs) {
   sfm_ba_problem* p = nullptr;
   SFM_TRY(sfm_ba_create(V, N, M, pt_ptr, cam_idx, uv_norm, &p));
   auto run = [&]() -> int {
     SFM_TRY(sfm_ba_set_option(p, SFM_OPT_SCHUR, schur_mode));
+    SFM_TRY(sfm_ba_set_loss(p, loss_kind, loss_delta));
     SFM_TRY(sfm_ba_set_state(p, cams, pts));
     SFM_TRY(ba_enqueue_linearize_reduce(p, lambda, quirks));
     hipStream_t s = p->stream;

@@ -39,6 +39,8 @@ TRACK_TOO_FEW, TRACK_NONFINITE, TRACK_BEHIND = 1, 2, 4
 TRACK_GROUPS = (0, 1, 4, 8, 16, 32, 64)
 OBS_HIGH_ERROR, OBS_BEHIND, OBS_NONFINITE, OBS_POINT = 1, 2, 4, 8
 PT_TOO_FEW, PT_LOW_ANGLE, PT_EMPTY = 1, 2, 4
+LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2
+LOSS_NAMES = {"none": LOSS_NONE, "huber": LOSS_HUBER, "cauchy": LOSS_CAUCHY}
 SCREEN_SUMMARY = ("obs_before", "obs_kept", "high_error", "behind", "nonfinite", "obs_dropped_with_point", "pts_too_few",
                   "pts_low_angle")
 
@@ -174,6 +176,10 @@ SIGNATURES = {
     "sfm_tri_tracks_auto_group": [ci, i64, ci],
     "sfm_ba_screen": [vp, cd, cd, ci, ci, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _lp],
     "sfm_ba_cull": [vp, cd, cd, ci, ci, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _lp],
+    "sfm_ba_set_loss": [vp, ci, cd],
+    "sfm_ba_get_loss": [vp, _ip, _dp],
+    "sfm_ba_loss_terms": [vp, _dp, _dp, _dp],
+    "sfm_ba_reduced_system_loss": [ci, ci, i64, _ip, _ip, _dp, _dp, _dp, cd, ci, ci, ci, cd, _dp, _dp],
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -439,6 +445,25 @@ def check_screen(n_cams, max_err2, cos_min_angle, min_obs, cam_scale, group=0):
     return max_err2, cos_min_angle, int(min_obs), cam_scale, int(group)
 
 
+def check_loss(kind, delta):
+    """Arguments of a ``BaProblem.set_loss`` call, without a device: returns ``(kind, delta)`` converted or raises ValueError.
+    ``kind`` is ``LOSS_NONE`` / ``LOSS_HUBER`` / ``LOSS_CAUCHY`` or its name; ``delta`` (normalised units) must be finite and
+    > 0 unless the kind is ``LOSS_NONE``, which ignores it."""
+    if isinstance(kind, str):
+        if kind.lower() not in LOSS_NAMES:
+            raise ValueError("loss must be one of %s, got %r" % (sorted(LOSS_NAMES), kind))
+        kind = LOSS_NAMES[kind.lower()]
+    if isinstance(kind, bool) or int(kind) != kind or int(kind) not in (LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY):
+        raise ValueError("loss kind must be LOSS_NONE, LOSS_HUBER or LOSS_CAUCHY, got %r" % (kind,))
+    kind = int(kind)
+    if kind == LOSS_NONE:
+        return kind, 1.0
+    delta = float(delta)
+    if not (np.isfinite(delta) and delta > 0.0):
+        raise ValueError("loss delta must be finite and > 0, got %r" % delta)
+    return kind, delta
+
+
 def tri_tracks(pt_ptr, cam_idx, uv, projs, X_init=None, mode=TRACKS_NONLINEAR, lam=0.5, iters=100, group=0):
     """Triangulate / refine every point from its own track (sfm_tri_tracks): pt_ptr (n+1,), cam_idx (M,), uv (2, M),
     projs (V, 3, 4), X_init (4, n) or None with TRACKS_LINEAR -> (X (4, n), cost (2, n), status (n,) of TRACK_* bits)."""
@@ -666,10 +691,16 @@ def ba_residual_jacobian(n_cams, pt_ptr, cam_idx, uv_norm, cams, pts, quirks=QUI
 
 
 def ba_reduced_system(n_cams, pt_ptr, cam_idx, uv_norm, cams, pts, lam, quirks=QUIRKS_REFERENCE,
-                      schur_mode=SCHUR_AUTO):
+                      schur_mode=SCHUR_AUTO, loss=None):
+    """S, rhs of one linearisation; ``loss=(kind, delta)`` reweights it as ``BaProblem.set_loss`` does."""
     pt_ptr = i32(pt_ptr); cam_idx = i32(cam_idx); uv_norm = f64(uv_norm); cams = f64(cams); pts = f64(pts)
     n, m = pt_ptr.shape[0] - 1, cam_idx.shape[0]
     s = np.empty((7 * n_cams, 7 * n_cams)); rhs = np.empty(7 * n_cams)
+    if loss is not None:
+        kind, delta = check_loss(*loss)
+        check(load().sfm_ba_reduced_system_loss(n_cams, n, m, iptr(pt_ptr), iptr(cam_idx), dptr(uv_norm), dptr(cams),
+                                                dptr(pts), float(lam), quirks, schur_mode, kind, delta, dptr(s), dptr(rhs)))
+        return s, rhs
     check(load().sfm_ba_reduced_system(n_cams, n, m, iptr(pt_ptr), iptr(cam_idx), dptr(uv_norm), dptr(cams),
                                        dptr(pts), float(lam), quirks, schur_mode, dptr(s), dptr(rhs)))
     return s, rhs
@@ -807,11 +838,32 @@ class BaProblem:
         self._comm = comm                      # keep it alive as long as it is attached
 
     def get_stats(self, max_iters=256):
-        """Per-iteration cost sum |b - f|^2 (normalised image coordinates) at the start of every iteration run since
-        the state was last uploaded -- no state download needed (sfm_ba_get_stats)."""
+        """Per-iteration cost sum |b - f|^2 (normalised image coordinates; delta^2 sum rho(s) while a loss is set) at the
+        start of every iteration run since the state was last uploaded -- no state download needed (sfm_ba_get_stats)."""
         out = np.empty(max_iters); n = ctypes.c_int()
         check(self._lib.sfm_ba_get_stats(self._h, dptr(out), int(max_iters), ctypes.byref(n)))
         return out[:n.value].copy()
+
+    def set_loss(self, kind, delta=1.0):
+        """Robust loss of the iterations (sfm_ba_set_loss): ``LOSS_NONE`` / ``LOSS_HUBER`` / ``LOSS_CAUCHY`` (or its name)
+        with scale ``delta`` in normalised units.  Completes a pending step with the old loss, restarts the cost history,
+        uploads nothing; survives ``append``, ``cull`` and ``sync_tracks``."""
+        kind, delta = check_loss(kind, delta)
+        check(self._lib.sfm_ba_set_loss(self._h, kind, delta))
+
+    def loss(self):
+        """(kind, delta) as set by ``set_loss`` (sfm_ba_get_loss)."""
+        kind, delta = ctypes.c_int(), ctypes.c_double()
+        check(self._lib.sfm_ba_get_loss(self._h, ctypes.byref(kind), ctypes.byref(delta)))
+        return int(kind.value), float(delta.value)
+
+    def loss_terms(self):
+        """(s, w, rho), each (M,): every observation's scaled squared residual, weight and loss value at the current state
+        (sfm_ba_loss_terms); without a loss s = |b - f|^2, w = 1, rho = s."""
+        m = self.info(INFO_N_OBS)
+        s, w, rho = np.zeros(m), np.zeros(m), np.zeros(m)
+        check(self._lib.sfm_ba_loss_terms(self._h, dptr(s), dptr(w), dptr(rho)))
+        return s, w, rho
 
     def get_state(self):
         cams = np.empty((self.n_cams, 7)); pts = np.empty((3, self.n_pts))

@@ -364,6 +364,8 @@ class _ResidentScene:
         # (point, camera) pairs filter_structure has removed: the tracker keeps the uncut picture, a rebuild leaves them out
         self.culled_pt = np.empty(0, dtype=np.int64)
         self.culled_cam = np.empty(0, dtype=np.int64)
+        self.loss_prob = None     # the problem ba_loss was last applied to, and what was applied (None: never, it runs plain)
+        self.loss_applied = None
 
     def close(self):
         if self.prob is not None:
@@ -416,6 +418,44 @@ class HipBaMixin:
     ba_resident = True         # keep the problem on the device between calls (False: one sfm_ba_solve per call)
     ba_last_action = None      # "create" | "append" | "reuse" | "solve": what the last call did (diagnostics / tests)
     ba_device_tracks = False   # build the observation list from a HipDeviceKeyTracker's device tables (class docstring)
+    ba_loss = None             # None | ("huber", px) | ("cauchy", px): robust loss of the resident adjustment (ba_loss_native)
+
+    def ba_loss_native(self):
+        """``ba_loss`` as the native ``(kind, delta)`` or None, without touching the device.  The pixel scale becomes
+        delta = px / sqrt(|k[0, 0] k[1, 1]|) in the normalised coordinates the adjustment works in; a problem has ONE delta,
+        so views whose focal scales differ by more than 1e-12 relative raise ``ValueError``, as does a malformed setting.
+        ``BaProblem.set_loss`` has the semantics; it needs ``ba_resident`` (the one-shot ``sfm_ba_solve`` is plain least
+        squares).  Applied whenever the resident problem is created or replaced and when the attribute changes; the
+        default None never calls ``set_loss``.  Nothing in ``process()`` sets it."""
+        if self.ba_loss is None:
+            return None
+        try:
+            name, px = self.ba_loss
+        except (TypeError, ValueError):
+            raise ValueError("ba_loss must be None or (\"huber\" | \"cauchy\", pixels), got {!r}".format(self.ba_loss))
+        if not isinstance(name, str) or name.lower() not in ("huber", "cauchy"):
+            raise ValueError("ba_loss must name \"huber\" or \"cauchy\", got {!r}".format(name))
+        if not self.ba_resident:
+            raise TypeError("ba_loss needs ba_resident")
+        kind, px = native.check_loss(name, px)
+        scales = np.array([math.sqrt(abs(float(v.k[0, 0]) * float(v.k[1, 1]))) for v in self.view_processor.view_list])
+        if scales.size == 0 or not np.all(np.isfinite(scales)) or not np.all(scales > 0.0):
+            raise ValueError("ba_loss needs views with finite, non-zero focal scales")
+        if np.max(np.abs(scales - scales[0])) > 1e-12 * scales[0]:
+            raise ValueError("ba_loss needs one focal scale for all views (one delta per problem), got {} .. {}".format(
+                scales.min(), scales.max()))
+        return native.check_loss(kind, px / scales[0])
+
+    def _ba_apply_loss(self, scene, loss):
+        """Make the resident problem's loss what ``ba_loss`` asks for (``loss`` = ``ba_loss_native()``): one ``set_loss`` when
+        the problem is new or the setting changed, none while a problem has only ever run plain."""
+        applied = scene.loss_applied if scene.loss_prob is scene.prob else None
+        if loss != applied:
+            if loss is None:
+                scene.prob.set_loss(native.LOSS_NONE)
+            else:
+                scene.prob.set_loss(*loss)
+        scene.loss_prob, scene.loss_applied = scene.prob, loss
 
     def ba_release(self):
         scene = self.__dict__.pop("_hip_scene", None)
@@ -544,9 +584,11 @@ class HipBaMixin:
             if np.array_equal(init_rots[:n_old], scene.rots_written[:n_old]) and np.array_equal(init_locs[:n_old], scene.locs_written[:n_old]):
                 n_same = n_old
         new_cams = pack_cameras(init_rots[n_same:], init_locs[n_same:]) if n_same < view_num else np.zeros((0, 7))
+        loss = self.ba_loss_native()          # (raises before anything reaches the device)
         scene = self._ba_sync_structure(views, tri_num, n_same, new_cams, init_tri_pts)
         prob = scene.prob
         try:
+            self._ba_apply_loss(scene, loss)
             if self.ba_last_action == "create":
                 prob.set_cameras(pack_cameras(init_rots, init_locs) if n_same else new_cams)
                 prob.set_points(0, init_tri_pts)
@@ -681,6 +723,7 @@ class HipBaMixin:
     def execute_bundle_adjustment(self):
         if self.ba_device_tracks:
             self._ba_check_device_tracks()
+        self.ba_loss_native()                         # a bad ba_loss (or one without ba_resident) stops here, before anything is read
         views = self.view_processor.view_list
         tri_pts = self.tri_processor.tri_pts
         view_num = len(views)
