@@ -460,22 +460,14 @@ static void launch_linearize_loss(const sfm_ba_problem* p, int cur, int g, int g
   const BaDev& d = p->dev;
   const LossArg<LOSS> la = loss_arg<LOSS>(p);
   if (p->deterministic) {      // one wave per workgroup (ordered LDS accumulation)
-    switch (g) {
-      case 4: ba_linearize_kernel<4, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la); break;
-      case 8: ba_linearize_kernel<8, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la); break;
-      case 16: ba_linearize_kernel<16, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la); break;
-      case 32: ba_linearize_kernel<32, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la); break;
-      default: ba_linearize_kernel<64, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la); break;
-    }
+    dispatch_group<4>(g, [&](auto G) {
+      ba_linearize_kernel<decltype(G)::value, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la);
+    });
     return;
   }
-  switch (g) {
-    case 4: ba_linearize_kernel<4, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la); break;
-    case 8: ba_linearize_kernel<8, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la); break;
-    case 16: ba_linearize_kernel<16, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la); break;
-    case 32: ba_linearize_kernel<32, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la); break;
-    default: ba_linearize_kernel<64, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la); break;
-  }
+  dispatch_group<4>(g, [&](auto G) {
+    ba_linearize_kernel<decltype(G)::value, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la);
+  });
 }
 
 // the problem's loss picks the instantiation; without one it is the plain kernel
@@ -492,13 +484,9 @@ template <bool LDS, int LOSS>
 static void launch_backsub_loss(const sfm_ba_problem* p, int g, int grid, size_t lds, hipStream_t s, double lambda, int quirks) {
   const BaDev& d = p->dev;
   const LossArg<LOSS> la = loss_arg<LOSS>(p);
-  switch (g) {
-    case 4: ba_backsub_kernel<4, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la); break;
-    case 8: ba_backsub_kernel<8, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la); break;
-    case 16: ba_backsub_kernel<16, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la); break;
-    case 32: ba_backsub_kernel<32, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la); break;
-    default: ba_backsub_kernel<64, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la); break;
-  }
+  dispatch_group<4>(g, [&](auto G) {
+    ba_backsub_kernel<decltype(G)::value, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la);
+  });
 }
 
 template <bool LDS>

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "sfm_ba.h"
+#include "sfm_scan.h"
 
 namespace sfm {
 
@@ -21,10 +22,6 @@ namespace sfm {
 // sinfo[0] = first failure code (1 pt_ptr not monotone, 2 camera out of range, 3 cameras of a track not strictly
 // increasing), sinfo[1] = its index (point, observation, point), sinfo[2] = longest track.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void structure_fail(int* sinfo, int code, int index) {
-  if (atomicCAS(&sinfo[0], 0, code) == 0) sinfo[1] = index;
-}
-
 __global__ void ba_structure_kernel(int V, int N, long long M, const int* __restrict__ pt_ptr,
                                     const int* __restrict__ cam_idx, int* __restrict__ obs_pt,
                                     int* __restrict__ blk_ptr, int nblk, int* __restrict__ sinfo) {
@@ -33,15 +30,15 @@ __global__ void ba_structure_kernel(int V, int N, long long M, const int* __rest
   const int beg = pt_ptr[p], end = pt_ptr[p + 1];
   int* row = blk_ptr + (size_t)p * (nblk + 1);
   if (beg < 0 || end < beg || end > M) {
-    structure_fail(sinfo, 1, p);
+    report_status(sinfo, 1, p);
     for (int b = 0; b <= nblk; ++b) row[b] = 0;
     return;
   }
   int prev = -1, b = 0;
   for (int o = beg; o < end; ++o) {
     const int c = cam_idx[o];
-    if (c < 0 || c >= V) { structure_fail(sinfo, 2, o); continue; }
-    if (c <= prev) structure_fail(sinfo, 3, p);
+    if (c < 0 || c >= V) { report_status(sinfo, 2, o); continue; }
+    if (c <= prev) report_status(sinfo, 3, p);
     prev = c;
     obs_pt[o] = p;
     while (b < nblk && c >= b * kSchurCB) row[b++] = o;      // first observation whose camera is >= 18 b
@@ -64,42 +61,22 @@ __global__ void ba_append_count_kernel(long long n, int V2, int N2, const int* _
   const long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (k >= n) return;
   const int c = obs_cam[k], q = obs_pt[k];
-  if (c < 0 || c >= V2 || q < 0 || q >= N2) { structure_fail(sinfo, 4, (int)k); return; }
+  if (c < 0 || c >= V2 || q < 0 || q >= N2) { report_status(sinfo, 4, (int)k); return; }
   atomicAdd(&cnt[q], 1);
 }
 
-// exclusive prefix sums of two integer sequences in one pass, one 1024-thread workgroup
-__global__ __launch_bounds__(1024) void ba_append_scan_kernel(int N, int N2, const int* __restrict__ old_ptr,
-                                                              const int* __restrict__ cnt, int* __restrict__ new_ptr,
-                                                              int* __restrict__ nstart) {
-  __shared__ int wsum[2][16];
-  __shared__ int carry[2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < 2) carry[tid] = 0;
-  __syncthreads();
-  for (int base = 0; base < N2; base += 1024) {
-    const int q = base + tid;
-    int a = 0, b = 0;
-    if (q < N2) {
-      b = cnt[q];
-      a = b + (q < N ? old_ptr[q + 1] - old_ptr[q] : 0);
-    }
-    int sa = a, sb = b;                              // inclusive scan inside the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int ta = __shfl_up(sa, off, 64), tb = __shfl_up(sb, off, 64);
-      if (lane >= off) { sa += ta; sb += tb; }
-    }
-    if (lane == 63) { wsum[0][wave] = sa; wsum[1][wave] = sb; }
-    __syncthreads();
-    int oa = carry[0], ob = carry[1];
-    for (int w = 0; w < wave; ++w) { oa += wsum[0][w]; ob += wsum[1][w]; }
-    if (q < N2) { new_ptr[q] = oa + sa - a; nstart[q] = ob + sb - b; }
-    __syncthreads();
-    if (tid == 1023) { carry[0] = oa + sa; carry[1] = ob + sb; }
-    __syncthreads();
-  }
-  if (tid == 0) { new_ptr[N2] = carry[0]; nstart[N2] = carry[1]; }
+// exclusive prefix sums of two integer sequences in one pass (one workgroup): old track length + cnt, and cnt
+__global__ __launch_bounds__(kScanBlock) void ba_append_scan_kernel(int N, int N2, const int* __restrict__ old_ptr,
+                                                                    const int* __restrict__ cnt, int* __restrict__ new_ptr,
+                                                                    int* __restrict__ nstart) {
+  block_exclusive_scan<2>(
+      N2,
+      [&](int q, int (&a)[2]) {
+        a[1] = cnt[q];
+        a[0] = a[1] + (q < N ? old_ptr[q + 1] - old_ptr[q] : 0);
+      },
+      [&](int q, const int (&e)[2]) { new_ptr[q] = e[0]; nstart[q] = e[1]; },
+      [&](const int (&t)[2]) { new_ptr[N2] = t[0]; nstart[N2] = t[1]; });
 }
 
 __global__ void ba_append_bucket_kernel(long long n, const int* __restrict__ obs_pt, const int* __restrict__ nstart,
@@ -692,7 +669,7 @@ int sfm_ba_append(sfm_ba_problem* p, int n_new_cams, const double* cams_new, int
         return SFM_E_SHAPE;
       }
     }
-    ba_append_scan_kernel<<<1, 1024, 0, s>>>(d.N, N2, d.pt_ptr, cnt.p, e.pt_ptr, nstart.p);
+    ba_append_scan_kernel<<<1, kScanBlock, 0, s>>>(d.N, N2, d.pt_ptr, cnt.p, e.pt_ptr, nstart.p);
     if (n > 0) ba_append_bucket_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((long long)n, dpt.p, nstart.p, fill.p, norder.p);
     if (N2 > 0) ba_append_merge_kernel<<<(N2 + 255) / 256, 256, 0, s>>>(d.N, N2, d.pt_ptr, d.cam_idx, d.u, d.v, e.pt_ptr, nstart.p, norder.p,
                                                                         dcam.p, duv.p, duv.p + n, e.cam_idx, e.u, e.v);

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "sfm_ba.h"
+#include "sfm_scan.h"
 
 namespace sfm {
 
@@ -34,28 +35,10 @@ __global__ void ba_cam_major_count_kernel(long long M, const int* __restrict__ c
   atomicAdd(&pairs[c], (unsigned long long)(o - pt_ptr[obs_pt[o]] + 1));      // camera pairs this observation owns
 }
 
-__global__ __launch_bounds__(1024) void ba_cam_major_scan_kernel(int V, const int* __restrict__ cnt, int* __restrict__ cam_ptr) {
-  __shared__ int wsum[16];
-  __shared__ int carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < V; base += 1024) {
-    const int q = base + tid;
-    const int a = q < V ? cnt[q] : 0;
-    int sa = a;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(sa, off, 64); if (lane >= off) sa += t; }
-    if (lane == 63) wsum[wave] = sa;
-    __syncthreads();
-    int o = carry;
-    for (int w = 0; w < wave; ++w) o += wsum[w];
-    if (q < V) cam_ptr[q] = o + sa - a;
-    __syncthreads();
-    if (tid == 1023) carry = o + sa;
-    __syncthreads();
-  }
-  if (tid == 0) cam_ptr[V] = carry;
+__global__ __launch_bounds__(kScanBlock) void ba_cam_major_scan_kernel(int V, const int* __restrict__ cnt, int* __restrict__ cam_ptr) {
+  block_exclusive_scan<1>(
+      V, [&](int q, int (&a)[1]) { a[0] = cnt[q]; }, [&](int q, const int (&e)[1]) { cam_ptr[q] = e[0]; },
+      [&](const int (&t)[1]) { cam_ptr[V] = t[0]; });
 }
 
 // entry of the camera-major list: everything a visit needs about its A-observation in ONE 16-byte load (the chain
@@ -182,7 +165,7 @@ int ba_rows_enqueue_build(sfm_ba_problem* p) {
   SFM_HIP(hipMemsetAsync(fill.p, 0, sizeof(int) * d.V, s));
   SFM_HIP(hipMemsetAsync(p->cam_pairs, 0, sizeof(unsigned long long) * d.V, s));
   if (d.M > 0) ba_cam_major_count_kernel<<<(unsigned)((d.M + 255) / 256), 256, 0, s>>>(d.M, d.cam_idx, d.obs_pt, d.pt_ptr, cnt.p, p->cam_pairs);
-  ba_cam_major_scan_kernel<<<1, 1024, 0, s>>>(d.V, cnt.p, p->cam_ptr);
+  ba_cam_major_scan_kernel<<<1, kScanBlock, 0, s>>>(d.V, cnt.p, p->cam_ptr);
   if (d.M > 0) ba_cam_major_fill_kernel<<<(unsigned)((d.M + 255) / 256), 256, 0, s>>>(d.M, d.cam_idx, d.obs_pt, d.pt_ptr, p->cam_ptr, fill.p,
                                                                                        static_cast<int4*>(p->cam_ent));
   SFM_HIP(hipGetLastError());

@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "sfm_ba.h"
+#include "sfm_scan.h"
 
 namespace sfm {
 
@@ -70,28 +71,6 @@ __device__ __forceinline__ void screen_obs(const CamPrep& c, double scale, doubl
   e.r[2] = d2 * inv;
 }
 
-template <int G>
-__device__ __forceinline__ int screen_gsum(int v) {
-#pragma unroll
-  for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-template <int G>
-__device__ __forceinline__ double screen_gmin(double v) {
-#pragma unroll
-  for (int off = G / 2; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-// The lanes of a group sit in one wave and run in lockstep; this keeps the compiler from moving an LDS access of one
-// lane across the point where another lane's access has to be complete.
-__device__ __forceinline__ void screen_group_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // A track of up to kScrSlots * G observations has its rays staged by the evaluation pass itself and every lane reads
 // its own rays back from the tile.  A longer one is staged tile by tile, and a lane forms the rays of its own
 // observations again for every tile (the fallback: any length, nothing held per observation).
@@ -124,8 +103,8 @@ __global__ __launch_bounds__(kScrBlock) void ba_screen_kernel(ScreenArgs a) {
       w[0] = e.r[0]; w[1] = e.r[1]; w[2] = e.r[2];
     }
   }
-  nk = screen_gsum<G>(nk);
-  screen_group_sync();
+  nk = group_sum<G>(nk);
+  group_lds_sync();
 
   double mc = 1.0;
   if (nk >= 2) {
@@ -138,7 +117,7 @@ __global__ __launch_bounds__(kScrBlock) void ba_screen_kernel(ScreenArgs a) {
           double* w = tile + 3 * (o - tb);
           w[0] = e.r[0]; w[1] = e.r[1]; w[2] = e.r[2];
         }
-        screen_group_sync();
+        group_lds_sync();
       }
       for (int i = beg + lane; i < end; i += G) {
         double r0, r1, r2;
@@ -158,10 +137,10 @@ __global__ __launch_bounds__(kScrBlock) void ba_screen_kernel(ScreenArgs a) {
           mc = fmin(mc, __builtin_fma(r2, w[2], __builtin_fma(r1, w[1], r0 * q0)));
         }
       }
-      if (!one) screen_group_sync();
+      if (!one) group_lds_sync();
     }
   }
-  mc = screen_gmin<G>(mc);
+  mc = group_min<G>(mc);
 
   int pf = 0;
   if (end == beg) {
@@ -175,9 +154,9 @@ __global__ __launch_bounds__(kScrBlock) void ba_screen_kernel(ScreenArgs a) {
     for (int o = beg + lane; o < end; o += G)      // the lane's own stores, read back
       if (a.obs_flags[o] == 0) a.obs_flags[o] = SFM_OBS_POINT;
   }
-  n_high = screen_gsum<G>(n_high);
-  n_behind = screen_gsum<G>(n_behind);
-  n_nonfinite = screen_gsum<G>(n_nonfinite);
+  n_high = group_sum<G>(n_high);
+  n_behind = group_sum<G>(n_behind);
+  n_nonfinite = group_sum<G>(n_nonfinite);
   if (lane != 0) return;
   a.min_cos[p] = mc;
   a.pt_flags[p] = pf;
@@ -192,38 +171,16 @@ __global__ __launch_bounds__(kScrBlock) void ba_screen_kernel(ScreenArgs a) {
 
 #pragma clang fp contract(on)
 
-// Exclusive prefix sum of the kept counts, one 1024-thread workgroup (the scan of ba_append_scan_kernel over one sequence);
-// summary[0] = observations before, summary[1] = observations kept.
-__global__ __launch_bounds__(1024) void ba_cull_scan_kernel(int N, const int* __restrict__ old_ptr, const int* __restrict__ keep,
-                                                            int* __restrict__ new_ptr, unsigned long long* __restrict__ summary) {
-  __shared__ int wsum[16];
-  __shared__ int carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < N; base += 1024) {
-    const int q = base + tid;
-    const int a = q < N ? keep[q] : 0;
-    int sa = a;                                      // inclusive scan inside the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int ta = __shfl_up(sa, off, 64);
-      if (lane >= off) sa += ta;
-    }
-    if (lane == 63) wsum[wave] = sa;
-    __syncthreads();
-    int oa = carry;
-    for (int w = 0; w < wave; ++w) oa += wsum[w];
-    if (q < N) new_ptr[q] = oa + sa - a;
-    __syncthreads();
-    if (tid == 1023) carry = oa + sa;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    new_ptr[N] = carry;
-    summary[0] = (unsigned long long)old_ptr[N];
-    summary[1] = (unsigned long long)carry;
-  }
+// Exclusive prefix sum of the kept counts (one workgroup); summary[0] = observations before, summary[1] = observations kept.
+__global__ __launch_bounds__(kScanBlock) void ba_cull_scan_kernel(int N, const int* __restrict__ old_ptr, const int* __restrict__ keep,
+                                                                  int* __restrict__ new_ptr, unsigned long long* __restrict__ summary) {
+  block_exclusive_scan<1>(
+      N, [&](int q, int (&a)[1]) { a[0] = keep[q]; }, [&](int q, const int (&e)[1]) { new_ptr[q] = e[0]; },
+      [&](const int (&t)[1]) {
+        new_ptr[N] = t[0];
+        summary[0] = (unsigned long long)old_ptr[N];
+        summary[1] = (unsigned long long)t[0];
+      });
 }
 
 // One thread per point: the observations whose flags are clear, in their old order, to the new offsets.
@@ -245,8 +202,6 @@ __global__ void ba_cull_scatter_kernel(int N, const int* __restrict__ old_ptr, c
   }
 }
 
-static bool screen_group_ok(int g) { return g == 0 || g == 1 || g == 4 || g == 8 || g == 16 || g == 32 || g == 64; }
-
 template <int G>
 static void launch_screen(const ScreenArgs& a, hipStream_t s) {
   const long long threads = (long long)a.N * G;
@@ -257,8 +212,7 @@ int ba_screen_check_args(const char* who, double max_err2, double cos_min_angle,
   if (!(max_err2 >= 0.0)) { set_error("%s: max_err2 = %g must be >= 0 (+inf switches the test off)", who, max_err2); return SFM_E_SHAPE; }
   if (!(cos_min_angle >= -1.0)) { set_error("%s: cos_min_angle = %g must be >= -1 (>= 1 switches the test off)", who, cos_min_angle); return SFM_E_SHAPE; }
   if (min_obs < 0) { set_error("%s: min_obs = %d must be >= 0", who, min_obs); return SFM_E_SHAPE; }
-  if (!screen_group_ok(group)) { set_error("%s: group %d is not one of 0, 1, 4, 8, 16, 32, 64", who, group); return SFM_E_SHAPE; }
-  return SFM_OK;
+  return group_width_check(who, group);
 }
 
 // Screen p's scene at its current state: enqueue, download what the caller asked for, wait.  The per-observation flags
@@ -293,16 +247,10 @@ int ba_screen_run(sfm_ba_problem* p, const char* who, double max_err2, double co
   a.err2 = w.err2.p; a.depth = w.depth.p; a.obs_flags = w.flags.p;
   a.min_cos = w.min_cos.p; a.pt_flags = w.pt_flags.p; a.keep = w.keep.p;
   a.summary = w.summary.p;
-  switch (group ? group : sfm_tri_tracks_auto_group(d.N, d.M, p->max_track)) {
-    case 1: launch_screen<1>(a, s); break;
-    case 4: launch_screen<4>(a, s); break;
-    case 8: launch_screen<8>(a, s); break;
-    case 16: launch_screen<16>(a, s); break;
-    case 32: launch_screen<32>(a, s); break;
-    default: launch_screen<64>(a, s); break;
-  }
+  dispatch_group<1>(group ? group : sfm_tri_tracks_auto_group(d.N, d.M, p->max_track),
+                    [&](auto G) { launch_screen<decltype(G)::value>(a, s); });
   SFM_HIP(hipGetLastError());
-  ba_cull_scan_kernel<<<1, 1024, 0, s>>>(d.N, d.pt_ptr, w.keep.p, w.new_ptr.p, w.summary.p);
+  ba_cull_scan_kernel<<<1, kScanBlock, 0, s>>>(d.N, d.pt_ptr, w.keep.p, w.new_ptr.p, w.summary.p);
   SFM_HIP(hipGetLastError());
   unsigned long long sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int st[2] = {0, 0};

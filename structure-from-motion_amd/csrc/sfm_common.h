@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/sfm_hip.h"
 #include "sfm_math.h"
@@ -117,12 +118,15 @@ __device__ __forceinline__ double dpp_f64(double v) {
   return __hiloint2double(hi, lo);
 }
 
-// Sum over aligned groups of G lanes (G = 4, 8, 16, 32, 64); every lane of the group gets the sum.
+// ---- lane groups: G adjacent lanes of a wave that own one point ("Shared primitives") ----
+// Sum over aligned groups of G lanes (G = 1, 4, 8, 16, 32, 64); every lane of the group gets the sum.
 // Up to 16 lanes stay on DPP: xor-1, xor-2 inside quads, then i <-> 7-i inside half rows, then
 // i <-> 15-i inside rows (mirrors pair each partial sum with a disjoint one, so four steps cover a row);
 // only the 32- and 64-lane steps go through ds_bpermute.
 template <int G>
 __device__ __forceinline__ double group_sum(double v) {
+  static_assert(G == 1 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64, "not a lane-group width");
+  if constexpr (G == 1) return v;
   v += dpp_f64<0xB1>(v);                       // quad_perm [1,0,3,2]
   v += dpp_f64<0x4E>(v);                       // quad_perm [2,3,0,1]
   if (G >= 8) v += dpp_f64<0x141>(v);          // row_half_mirror
@@ -130,6 +134,55 @@ __device__ __forceinline__ double group_sum(double v) {
   if (G >= 32) v += __shfl_xor(v, 16, 64);
   if (G >= 64) v += __shfl_xor(v, 32, 64);
   return v;
+}
+
+// Integer sum and double minimum over the same groups, by plain butterflies: both are order-independent, so the result
+// does not depend on G.
+template <int G>
+__device__ __forceinline__ int group_sum(int v) {
+#pragma unroll
+  for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <int G>
+__device__ __forceinline__ double group_min(double v) {
+#pragma unroll
+  for (int off = G / 2; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// The lanes of a group sit in one wave and run in lockstep; this keeps the compiler from moving an LDS access of one
+// lane across the point where another lane's access has to be complete.
+__device__ __forceinline__ void group_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Host side of the lane groups: the widths an entry point accepts (0 = automatic), and the step from a run-time width
+// to a template argument: f(std::integral_constant<int, G>()) for g = G >= MinG, the 64-lane instantiation for anything
+// else.  MinG = 4: the bundle-adjustment kernels, which have no one-lane form; MinG = 1: tracks and screening.
+inline bool group_width_ok(int g) { return g == 0 || g == 1 || g == 4 || g == 8 || g == 16 || g == 32 || g == 64; }
+
+inline int group_width_check(const char* who, int g) {
+  if (group_width_ok(g)) return SFM_OK;
+  set_error("%s: group %d is not one of 0, 1, 4, 8, 16, 32, 64", who, g);
+  return SFM_E_SHAPE;
+}
+
+template <int MinG, class F>
+inline void dispatch_group(int g, F&& f) {
+  if constexpr (MinG <= 1) {
+    if (g == 1) return f(std::integral_constant<int, 1>());
+  }
+  switch (g) {
+    case 4: return f(std::integral_constant<int, 4>());
+    case 8: return f(std::integral_constant<int, 8>());
+    case 16: return f(std::integral_constant<int, 16>());
+    case 32: return f(std::integral_constant<int, 32>());
+    default: return f(std::integral_constant<int, 64>());
+  }
 }
 
 // Row totals of MANY values at once (the 35 normal-equation sums of the PnP kernel): a halving fold instead of N

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "sfm_common.h"
+#include "sfm_scan.h"
 #include "sfm_dlt.h"
 
 namespace sfm {
@@ -688,28 +689,10 @@ __global__ void pnp_inlier_mask_kernel(int n, const double* __restrict__ proj, c
 // Stable compaction of the inlier columns (campose_processor.py:236-237: key_2d_pts[:, inlier_indices], tri_3d_pts[:, inlier_indices]
 // with the indices ascending): one workgroup scans the mask, then every inlier column goes to its rank.  The compacted arrays
 // keep the row pitch n of the originals (only the first m columns are written); offsets = {0, m} for the nonlinear kernel.
-__global__ __launch_bounds__(1024) void pnp_mask_scan_kernel(int n, const int* __restrict__ mask, int* __restrict__ pos, int* __restrict__ offsets) {
-  __shared__ int wsum[16];
-  __shared__ int carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + tid;
-    const int a = i < n ? (mask[i] != 0) : 0;
-    int sa = a;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(sa, off, 64); if (lane >= off) sa += t; }
-    if (lane == 63) wsum[wave] = sa;
-    __syncthreads();
-    int o = carry;
-    for (int w = 0; w < wave; ++w) o += wsum[w];
-    if (i < n) pos[i] = o + sa - a;
-    __syncthreads();
-    if (tid == 1023) carry = o + sa;
-    __syncthreads();
-  }
-  if (tid == 0) { offsets[0] = 0; offsets[1] = carry; }
+__global__ __launch_bounds__(kScanBlock) void pnp_mask_scan_kernel(int n, const int* __restrict__ mask, int* __restrict__ pos, int* __restrict__ offsets) {
+  block_exclusive_scan<1>(
+      n, [&](int i, int (&a)[1]) { a[0] = mask[i] != 0; }, [&](int i, const int (&e)[1]) { pos[i] = e[0]; },
+      [&](const int (&t)[1]) { offsets[0] = 0; offsets[1] = t[0]; });
 }
 
 __global__ void pnp_compact_kernel(int n, const int* __restrict__ mask, const int* __restrict__ pos, const double* __restrict__ uv_pix,
@@ -1213,7 +1196,7 @@ int sfm_pnp_ransac_finish(sfm_pnp_session* ses, const double R[9], const double 
     SFM_TRY(dMask.alloc(n)); SFM_TRY(dPos.alloc(n)); SFM_TRY(dOff.alloc(2)); SFM_TRY(dSt.alloc(1));
     SFM_TRY(dUVc.alloc(3 * (size_t)n)); SFM_TRY(dXc.alloc(4 * (size_t)n)); SFM_TRY(dR.alloc(9)); SFM_TRY(dC.alloc(3));
     pnp_inlier_mask_kernel<<<(n + 255) / 256, 256, 0, s>>>(n, dP.p, ses->dUV, ses->dX, threshold, dMask.p);
-    pnp_mask_scan_kernel<<<1, 1024, 0, s>>>(n, dMask.p, dPos.p, dOff.p);
+    pnp_mask_scan_kernel<<<1, kScanBlock, 0, s>>>(n, dMask.p, dPos.p, dOff.p);
     pnp_compact_kernel<<<(n + 255) / 256, 256, 0, s>>>(n, dMask.p, dPos.p, ses->dUV, ses->dX, dUVc.p, dXc.p);
     SFM_HIP(hipGetLastError());
     int off[2] = {0, 0};

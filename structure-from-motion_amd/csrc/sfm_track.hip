@@ -35,13 +35,14 @@
 #include <vector>
 
 #include "sfm_common.h"
+#include "sfm_scan.h"
 
 // the ratio test must be the plain division followed by the comparison
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int TB = 1024;            // threads of the single-workgroup kernels
+constexpr int TB = sfm::kScanBlock; // threads of the single-workgroup kernels
 constexpr int WAVES = TB / 64;
 constexpr int ROWS_SPARE = 16;      // rows a table is allocated with beyond what it needs
 constexpr double RATIO = 0.7;       // key_tracker.py:10
@@ -310,32 +311,11 @@ __global__ void obs_count_kernel(int n_views, int n_pts, const int* __restrict__
   cnt[p] = c;
 }
 
-// exclusive prefix sum, one workgroup: inclusive scan inside a wave, wave totals through LDS, a running carry per chunk
+// ptr = exclusive prefix sum of cnt, ptr[n] = the total (one workgroup)
 __global__ __launch_bounds__(TB) void obs_scan_kernel(int n, const int* __restrict__ cnt, int* __restrict__ ptr) {
-  __shared__ int wsum[WAVES];
-  __shared__ int carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += TB) {
-    const int q = base + tid;
-    const int a = q < n ? cnt[q] : 0;
-    int sa = a;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int t = __shfl_up(sa, off, 64);
-      if (lane >= off) sa += t;
-    }
-    if (lane == 63) wsum[wave] = sa;
-    __syncthreads();
-    int o = carry;
-    for (int w = 0; w < wave; ++w) o += wsum[w];
-    if (q < n) ptr[q] = o + sa - a;
-    __syncthreads();
-    if (tid == TB - 1) carry = o + sa;
-    __syncthreads();
-  }
-  if (tid == 0) ptr[n] = carry;
+  sfm::block_exclusive_scan<1>(
+      n, [&](int q, int (&a)[1]) { a[0] = cnt[q]; }, [&](int q, const int (&e)[1]) { ptr[q] = e[0]; },
+      [&](const int (&t)[1]) { ptr[n] = t[0]; });
 }
 
 __global__ void obs_fill_kernel(const ViewDesc* __restrict__ views, int n_views, int n_pts, const int* __restrict__ min_key,

@@ -152,12 +152,6 @@ __device__ __forceinline__ void track_residual(const double* P, double ku, doubl
   if (s[2] <= 0.0) behind += 1.0;
 }
 
-template <int G>
-__device__ __forceinline__ double track_gsum(double v) {
-  if constexpr (G == 1) return v;
-  else return group_sum<G>(v);
-}
-
 constexpr int kTrkLdsViews = 512;     // projections staged in LDS by the re-reading variant up to here (48 KB)
 
 // NC > 0: every lane keeps its (up to NC = 2, 4 or 6) observations -- u, v and the twelve projection entries -- in registers
@@ -224,15 +218,15 @@ __global__ __launch_bounds__(256) void tri_tracks_nonlinear_kernel(TrackArgs a) 
         }
       }
       if (last) {
-        cost1 = track_gsum<G>(S.c);
-        behind = track_gsum<G>(nb);
+        cost1 = group_sum<G>(S.c);
+        behind = group_sum<G>(nb);
         if (it == 0) cost0 = cost1;
         break;
       }
-      if (it == 0 && eval) cost0 = track_gsum<G>(S.c);
-      const double a00 = track_gsum<G>(S.a00) + a.lambda, a10 = track_gsum<G>(S.a10), a11 = track_gsum<G>(S.a11) + a.lambda;
-      const double a20 = track_gsum<G>(S.a20), a21 = track_gsum<G>(S.a21), a22 = track_gsum<G>(S.a22) + a.lambda;
-      const double b0 = track_gsum<G>(S.b0), b1 = track_gsum<G>(S.b1), b2 = track_gsum<G>(S.b2);
+      if (it == 0 && eval) cost0 = group_sum<G>(S.c);
+      const double a00 = group_sum<G>(S.a00) + a.lambda, a10 = group_sum<G>(S.a10), a11 = group_sum<G>(S.a11) + a.lambda;
+      const double a20 = group_sum<G>(S.a20), a21 = group_sum<G>(S.a21), a22 = group_sum<G>(S.a22) + a.lambda;
+      const double b0 = group_sum<G>(S.b0), b1 = group_sum<G>(S.b1), b2 = group_sum<G>(S.b2);
       // symmetric 3x3 inverse by adjugate (np.linalg.inv in the reference, tri:227)
       const double c00 = a11 * a22 - a21 * a21;
       const double c10 = a20 * a21 - a10 * a22;
@@ -274,8 +268,6 @@ static void launch_tracks_g(const TrackArgs& a, int nc, hipStream_t s) {
   else tri_tracks_nonlinear_kernel<G, 0><<<grid, block, a.proj_in_lds ? sizeof(double) * 12 * (size_t)a.n_views : 0, s>>>(a);
 }
 
-static bool tracks_group_ok(int g) { return g == 0 || g == 1 || g == 4 || g == 8 || g == 16 || g == 32 || g == 64; }
-
 // Automatic group width from n_pts, M and the longest track: the narrowest group whose lanes can
 // keep the longest track in registers (6 observations each), widened while the call is too small to give every SIMD
 // two waves and the wider group is still no wider than the longest track.
@@ -302,14 +294,7 @@ static int tracks_enqueue(TrackArgs a, int mode, int group, long long M, int max
     const int g = group ? group : tracks_pick_group(a.n_pts, M, max_track);
     const int nc = max_track <= 2 * g ? 2 : (max_track <= 4 * g ? 4 : (max_track <= 6 * g ? 6 : 0));
     a.proj_in_lds = a.n_views <= kTrkLdsViews;
-    switch (g) {
-      case 1: launch_tracks_g<1>(a, nc, s); break;
-      case 4: launch_tracks_g<4>(a, nc, s); break;
-      case 8: launch_tracks_g<8>(a, nc, s); break;
-      case 16: launch_tracks_g<16>(a, nc, s); break;
-      case 32: launch_tracks_g<32>(a, nc, s); break;
-      default: launch_tracks_g<64>(a, nc, s); break;
-    }
+    dispatch_group<1>(g, [&](auto G) { launch_tracks_g<decltype(G)::value>(a, nc, s); });
     SFM_HIP(hipGetLastError());
   }
   return SFM_OK;
@@ -321,8 +306,7 @@ static int tracks_check_args(const char* who, int n_pts, int n_views, long long 
     return SFM_E_SHAPE;
   }
   if (mode < 1 || mode > (SFM_TRACKS_LINEAR | SFM_TRACKS_NONLINEAR)) { set_error("%s: bad mode %d", who, mode); return SFM_E_SHAPE; }
-  if (!tracks_group_ok(group)) { set_error("%s: group %d is not one of 0, 1, 4, 8, 16, 32, 64", who, group); return SFM_E_SHAPE; }
-  return SFM_OK;
+  return group_width_check(who, group);
 }
 
 // Validate the CSR on the device (the way ba_structure_kernel does) and wait for the verdict.
