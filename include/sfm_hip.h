@@ -67,7 +67,7 @@ extern "C" {
                               * contribution (many cameras at low visibility: BASELINE config 4) */
 
 #define SFM_OPT_SCHUR        1
-#define SFM_OPT_DEBUG        3  /* profiling ablations of the Schur kernel (1 no MFMA, 4 no staging DMA: results are wrong when set; 8 = record clock stamps; 16 = keep ba_backsub and ba_linearize as separate launches, 64 = block column steps even for P <= 56 (no single-launch small-system solve), 256 = single-launch solve up to P = 64 instead of 56, 512 = block-row back substitution instead of dp = L^-T y with the inverse carried through the column steps, 128 = never pick the row-panel sparse product, 1024 = the column steps of the reduced solve as separate launches (ba_chol_step) where the single data-flow launch would run (9 to 237 cameras), 2048 = dp = X y and the camera update as their own launch (ba_inv_apply) behind the data-flow launch, 4096 = its tasks dealt by workgroup index instead of taken by ticket (A/B only: needs every workgroup of the launch resident): results unchanged; the environment variable SFM_FLOW_SOLVE=0 selects the column-step launches (bit 1024) for every handle of the process; 8192 = test of the data-flow launch's bounded waits: one hand-over is never announced, every wait gives up after 20 000 polls and the solve reports SFM_E_HIP; 16384 = the split-K reduce of the dense product always as its own launch (sfm_ba_iterate on one GPU otherwise leaves it to the first tasks of the data-flow launch: same sums in a fixed order) */
+#define SFM_OPT_DEBUG        3  /* profiling ablations of the Schur kernel (1 no MFMA, 4 no staging DMA: results are wrong when set; 8 = record clock stamps; 16 = keep ba_backsub and ba_linearize as separate launches, 64 = block column steps even for P <= 56 (no single-launch small-system solve), 256 = single-launch solve up to P = 64 instead of 56, 512 = block-row back substitution instead of dp = L^-T y with the inverse carried through the column steps, 128 = never pick the row-panel sparse product, 1024 = the column steps of the reduced solve as separate launches (ba_chol_step) where the single data-flow launch would run (9 to 237 cameras), 2048 = dp = X y and the camera update as their own launch (ba_inv_apply) behind the data-flow launch, 4096 = its tasks dealt by workgroup index instead of taken by ticket (A/B only: needs every workgroup of the launch resident): results unchanged; the environment variable SFM_FLOW_SOLVE=0 selects the column-step launches (bit 1024) for every handle of the process; 8192 = test of the data-flow launch's bounded waits: one hand-over is never announced, every wait gives up after 20 000 polls and the solve reports SFM_E_HIP; 16384 = the split-K reduce of the dense product always as its own launch (sfm_ba_iterate on one GPU otherwise leaves it to the first tasks of the data-flow launch: same sums in a fixed order); 32768 = sfm_ba_refine_cameras works on cameras of size class 3 with the launches of class 4 (A/B only: same slice order) */
 #define SFM_OPT_DETERMINISTIC 4 /* 1: fixed summation order everywhere -- one wave per ba_linearize workgroup (ordered LDS accumulation), the
                                  * atomic-free dense Schur product, a single-writer split-K / camera-accumulator reduce.  Two runs from the
                                  * same state then agree bit for bit (the default path agrees to ~1e-13).  Needs the dense product to fit
@@ -322,7 +322,7 @@ int sfm_ba_get_stats(sfm_ba_problem* p, double* cost /*[max_iters]*/, int max_it
  *   sfm_ba_cull and sfm_ba_sync_tracks like the options.  With SFM_LOSS_NONE (the default) the iterations launch the very
  *   kernels they launched before this call existed.
  * Plain least squares regardless of this setting: sfm_ba_solve, sfm_ba_refine_points, sfm_ba_screen / sfm_ba_cull's
- * errors, and the PnP and triangulation solvers. */
+ * errors, and the PnP and triangulation solvers.  sfm_ba_refine_cameras uses it when its use_loss argument says so. */
 int sfm_ba_set_loss(sfm_ba_problem* p, int kind, double delta);
 int sfm_ba_get_loss(sfm_ba_problem* p, int* kind, double* delta);
 /* Parity hook: s_o, w(s_o), rho(s_o) of every observation at the current state, in the resident (point, camera) order, from
@@ -432,6 +432,42 @@ int sfm_tri_tracks_auto_group(int n_pts, int64_t M, int max_track);
  * stream and uploads nothing.  cost / status are HOST arrays ([2][N], [N]) or NULL.  An empty problem returns SFM_OK. */
 int sfm_ba_refine_points(sfm_ba_problem* p, int mode, double lambda, int iters, int group,
                          double* cost /*host [2][N] or NULL*/, int* status /*host [N] or NULL*/);
+
+/* ---- motion-only refinement of the resident scene: every camera from its own observations, the points held ----------
+ * The other half of sfm_ba_refine_points.  For every camera c with cam_mask[c] != 0 and at least one observation, `iters`
+ * times: r_o = b - f and Jp_o (2x7 with respect to [C, q]) of the camera's observations exactly as one linearisation of the
+ * bundle adjustment forms them (R(q), t and q^ = q(R(q)) of the prepared camera, the Q2 bit of `quirks` honoured, the Q1
+ * bit ignored); with use_loss = 1 and a loss on the handle both are scaled by sqrt(w(s_o)) as the iterations scale them;
+ *   U = sum Jp^T Jp,  g = sum Jp^T r,  dp = inv(U + lambda I) g,  cam += dp,  q /= |q|      (ba_processor.py:382-392 without
+ * the point blocks), then R(q), its checks and q^ for the next pass.  iters = 0 is a pure evaluation: the cameras come out
+ * bit for bit as they went in.
+ *   cost[0][c] / cost[1][c]: the camera's share of the minimised cost (sum e_o, or delta^2 sum rho(s_o) with the loss) at
+ *   the input / output camera; row 0 summed over the cameras is what sfm_ba_get_stats reports for an iteration linearised at
+ *   that state.  A held, empty or NONFINITE camera reports its row 0 in both rows (0 for an empty one).
+ *   status[c]: a mask of the SFM_CAM_* bits below.
+ * Determinism: a camera's result bits depend on its own observations (in ascending point order), its own state, the points
+ * it sees, lambda, iters, quirks and the loss -- not on the other cameras, the mask, the grid or timing.  The 35 sums are
+ * formed per slice of consecutive observations and added in slice order; how a camera of n_obs observations is worked on is
+ * a function of n_obs alone, reported by the _plan call: size class 0 = empty, 1 / 2 = one workgroup runs all iterations in
+ * one launch with the observations in registers, 3 = the same with the observations read again in every pass, 4 = two
+ * launches per pass.
+ * Completes a deferred back substitution first and prepares the cameras if they are not; an INPUT camera that fails the
+ * rotation checks returns its status, names the camera and leaves the state as it was.  Afterwards the cameras are treated
+ * as by sfm_ba_set_cameras: the cost history restarts, captured graphs stay, the prepared form is rebuilt before the next
+ * linearisation.  Points, observations, options and the loss are untouched.  Only cam_mask is uploaded.  Runs on the
+ * problem's stream; blocking.  iters < 0, a NaN or negative lambda, use_loss outside {0, 1} or an attached communicator
+ * (the points are sharded: the replicas would diverge) return SFM_E_SHAPE and launch nothing.  An empty problem or one
+ * without observations returns SFM_OK.  cost / status are HOST arrays or NULL. */
+#define SFM_CAM_EMPTY      1   /* the camera has no observation: untouched (informational) */
+#define SFM_CAM_NONFINITE  2   /* a non-finite value turned up, or the updated camera failed the rotation checks of
+                                  cam_prepare: the camera is written back as it came in */
+#define SFM_CAM_BEHIND     4   /* at the output camera s[2] <= 0 for at least one of its observations (informational) */
+#define SFM_CAM_HELD       8   /* cam_mask[c] == 0: untouched */
+int sfm_ba_refine_cameras(sfm_ba_problem* p, double lambda, int iters, int quirks, int use_loss,
+                          const unsigned char* cam_mask /*host [V] or NULL = every camera*/,
+                          double* cost /*host [2][V] or NULL*/, int* status /*host [V] or NULL*/);
+/* host only, needs no device: how a camera of n_obs observations is worked on (any output may be NULL) */
+int sfm_ba_refine_cameras_plan(int64_t n_obs, int* n_slices, int* slice_obs, int* size_class);
 
 /* ---- screening and culling of the resident scene's observations ----------------------------------------------------
  * Judges every observation of the resident CSR at the current state and every point by what is left of its track.  For

@@ -233,6 +233,12 @@ struct BaScene {
   void* rows_ws = nullptr;                 // [rows_wgs][7 R][tpr] split-K panels
   int rows_R = 0, rows_tpr = 0, rows_wgs = 0, rows_groups = 0;
   int rows_tpl = 0, rows_cp = 7;          // LDS row pitch and camera pitch of the panel (experiment: 8)
+  // motion-only refinement (sfm_ba_motion.hip): the STABLE camera-major list, built on first use -- cam_ent above is
+  // filled through atomicAdd and has no fixed order inside a camera
+  bool motion_built = false;
+  int* mo_ptr = nullptr;                   // [V+1] device: first entry of every camera
+  int* mo_obs = nullptr;                   // [M] device: observation indices grouped by camera, ascending (= by point) inside one
+  std::vector<int> h_mo_ptr;               // host copy of mo_ptr: the launches are planned from the observation counts
   std::vector<void*> owned;                // every pool buffer allocated on behalf of this scene (scene_alloc)
 };
 

@@ -1,0 +1,527 @@
+// sfm_ba_motion.hip — motion-only refinement of the resident scene: every camera from its own observations, points held
+// (sfm_ba_refine_cameras; gfx950).
+//
+// The camera half of a bundle-adjustment iteration (ba_processor.py:382-392) with the point blocks dropped: per camera
+//   U = sum Jp^T Jp (7x7),  g = sum Jp^T r,  dp = (U + lambda I)^-1 g,  cam += dp,  q /= |q|,  R(q), checks, q^ = q(R(q))
+// over the camera's observations, r and Jp exactly those of ba_linearize (obs_terms_loss, sfm_ba_terms.h), optionally
+// reweighted by the handle's robust loss.  Nothing couples two cameras, so there is no Schur complement and no reduced solve.
+//
+//   mo_count / mo_chunk_scan / mo_ptr_scan / mo_fill   the STABLE camera-major list (mo_ptr, mo_obs), once per scene:
+//                          counts per (chunk of observations, camera), a scan over the chunks of every camera, a scan over
+//                          the cameras, and one wave per chunk that hands out the slots in observation order
+//   ba_motion_resident<T>  one workgroup per camera of up to 256 (T = 64) or 1 024 (T = 256) observations: the observations
+//                          stay in registers, all iterations run in one launch, every thread solves the same 7x7;
+//                          STREAM: up to 16 384 observations, read again in every pass, 1 024 at a time
+//   ba_motion_partial      cameras beyond 16 384 observations, one launch per pass: a workgroup sums 1 024 consecutive
+//                          observations into 16 slice vectors
+//   ba_motion_finish       ... and one wave per such camera adds the slice vectors in order, solves, updates, prepares
+//
+// Fixed summation order: a lane accumulates four consecutive observations, a 16-lane row folds to the 36 sums
+// (U lower 28 | g 7 | cost) of a SLICE of 64 consecutive observations, slices are added in ascending order.  Which kernel
+// a camera takes depends on its own observation count only (sfm_ba_refine_cameras_plan), so its result bits do not depend
+// on the other cameras, the mask, the grid or timing.  There is no floating-point atomic in this file.
+#include <algorithm>
+#include <vector>
+
+#include "sfm_ba.h"
+#include "sfm_ba_terms.h"
+#include "sfm_scan.h"
+
+namespace sfm {
+
+constexpr int kMoSlice = 64;         // observations per slice = 16 lanes x kMoPerLane
+constexpr int kMoPerLane = 4;        // consecutive observations a lane keeps in registers
+constexpr int kMoWaveObs = 256;      // size class 1: one wave
+constexpr int kMoBlockObs = 1024;    // size class 2: four waves; the larger classes work through 1 024 observations at a time
+constexpr int kMoStreamObs = 16384;  // size class 3: one workgroup streams the camera's observations in every pass; beyond it
+                                     // (class 4) a pass is spread over one workgroup per 1 024 observations and a second launch
+constexpr int kMoSums = 36;          // U lower triangle (28) | g (7) | cost share
+constexpr int kMoDone = 1 << 30;     // internal status bit of the multi-launch path: the camera needs no further pass
+
+// ---------------------------------------------------------------------------------------------
+// The stable list.  The resident observations are sorted by (point, camera), so ascending observation index inside a
+// camera IS ascending point.
+// ---------------------------------------------------------------------------------------------
+__global__ void mo_count_kernel(long long M, int V, int chunk_obs, const int* __restrict__ cam_idx, int* __restrict__ table) {
+  const long long o = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (o >= M) return;
+  atomicAdd(&table[(size_t)(o / chunk_obs) * V + cam_idx[o]], 1);      // integer: the counts do not depend on the order
+}
+
+// per camera: counts of its chunks -> their exclusive prefix (the chunk's first slot inside the camera), and the total
+__global__ void mo_chunk_scan_kernel(int V, int nchunks, int* __restrict__ table, int* __restrict__ cnt) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= V) return;
+  int off = 0;
+  for (int k = 0; k < nchunks; ++k) {
+    const int t = table[(size_t)k * V + c];
+    table[(size_t)k * V + c] = off;
+    off += t;
+  }
+  cnt[c] = off;
+}
+
+__global__ __launch_bounds__(kScanBlock) void mo_ptr_scan_kernel(int V, const int* __restrict__ cnt, int* __restrict__ ptr) {
+  block_exclusive_scan<1>(
+      V, [&](int q, int (&a)[1]) { a[0] = cnt[q]; }, [&](int q, const int (&e)[1]) { ptr[q] = e[0]; },
+      [&](const int (&t)[1]) { ptr[V] = t[0]; });
+}
+
+// One wave per chunk, 64 observations at a time: a lane's slot is the chunk's running offset of its camera (fetched and
+// advanced by the first lane of that camera, the only writer of the chunk's table row) plus the number of lower lanes with
+// the same camera.
+__global__ __launch_bounds__(64) void mo_fill_kernel(long long M, int V, int chunk_obs, const int* __restrict__ cam_idx,
+                                                     const int* __restrict__ ptr, int* __restrict__ table, int* __restrict__ list) {
+  const int lane = threadIdx.x;
+  const long long o0 = (long long)blockIdx.x * chunk_obs, o1 = min(M, o0 + chunk_obs);
+  int* row = table + (size_t)blockIdx.x * V;
+  for (long long ob = o0; ob < o1; ob += 64) {
+    const long long o = ob + lane;
+    const bool live = o < o1;
+    const int c = live ? cam_idx[o] : -1 - lane;          // idle lanes: cameras of their own
+    int rank = 0, total = 0, lead = lane;
+    for (int j = 63; j >= 0; --j) {
+      const int cj = __shfl(c, j, 64);
+      if (cj == c) { ++total; lead = j; if (j < lane) ++rank; }
+    }
+    int first = 0;
+    if (live && rank == 0) first = atomicAdd(&row[c], total);
+    first = __shfl(first, lead, 64);
+    if (live) list[ptr[c] + first + rank] = (int)o;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The iteration
+// ---------------------------------------------------------------------------------------------
+struct MoArgs {
+  int V;
+  const int* ptr;               // [V+1] stable list
+  const int* obs;               // [M]
+  const unsigned char* mask;    // [V] or null
+  double lambda;
+  int iters, quirks;
+  double* cost;                 // [2][V]
+  int* status;                  // [V]
+};
+
+struct MoObs { double u, v, X, Y, Z; };
+
+// entry i of the camera's list (observation by index, its point through obs_pt)
+__device__ __forceinline__ void mo_load(const BaDev& d, const int* __restrict__ list, int i, MoObs& ob) {
+  const int o = list[i];
+  const int p = d.obs_pt[o];
+  ob.u = d.u[o]; ob.v = d.v[o];
+  ob.X = d.px[p]; ob.Y = d.py[p]; ob.Z = d.pz[p];
+}
+
+// one observation into the 36 sums; behind: s[2] <= 0 at this camera
+template <int LOSS>
+__device__ __forceinline__ void mo_accumulate(const CamPrep& c, const MoObs& ob, int quirks, const LossArg<LOSS>& la,
+                                              double (&acc)[kMoSums], int& behind) {
+  double r[2], Jp[14], Jx[6], rho = 0;
+  obs_terms_loss<LOSS>(c, ob.X, ob.Y, ob.Z, ob.u, ob.v, quirks, la, r, Jp, Jx, rho);
+  if constexpr (LOSS == SFM_LOSS_NONE) rho = r[0] * r[0] + r[1] * r[1];
+  double s[3];
+  project_cam(c, ob.X, ob.Y, ob.Z, 1.0, s);
+  behind |= s[2] <= 0.0 ? 1 : 0;
+  int k = 0;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+#pragma unroll
+    for (int j = 0; j <= i; ++j) { acc[k] += Jp[i] * Jp[j] + Jp[7 + i] * Jp[7 + j]; ++k; }
+  }
+#pragma unroll
+  for (int i = 0; i < 7; ++i) acc[28 + i] += Jp[i] * r[0] + Jp[7 + i] * r[1];
+  acc[35] += rho;
+}
+
+// which three of the 36 sums a lane holds after mo_fold_row
+__device__ __forceinline__ void mo_fold_own(int lane, int (&own)[3]) {
+  int i36[kMoSums], i18[18], i9[9], i5[5];
+#pragma unroll
+  for (int k = 0; k < kMoSums; ++k) i36[k] = k;
+  fold_index(i36, i18, (lane & 8) != 0);
+  fold_index(i18, i9, (lane & 4) != 0);
+  fold_index(i9, i5, (lane & 2) != 0);
+  fold_index(i5, own, (lane & 1) != 0);
+}
+
+// the 36 totals of a 16-lane row (one slice) -> row[36] in LDS (fold_half, sfm_common.h)
+__device__ __forceinline__ void mo_fold_row(const double (&acc)[kMoSums], const int (&own)[3], int lane, double* row) {
+  double f18[18], f9[9], f5[5], f3[3];
+  fold_half<0x140>(acc, f18, (lane & 8) != 0);
+  fold_half<0x141>(f18, f9, (lane & 4) != 0);
+  fold_half<0x4E>(f9, f5, (lane & 2) != 0);
+  fold_half<0xB1>(f5, f3, (lane & 1) != 0);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) row[own[j]] = f3[j];
+}
+
+// 0.0 when every one of the n values is finite, NaN otherwise
+__device__ __forceinline__ double mo_finite_probe(const double* v, int n) {
+  double chk = 0;
+  for (int k = 0; k < n; ++k) chk += v[k] * 0.0;
+  return chk;
+}
+
+// The serial part, carried out by every thread on the same sums: dp = (U + lambda I)^-1 g, cam += dp, q /= |q|, and the next
+// prepared camera.  The quaternion was normalised two lines up, so the determinant / inverse test of the rotation cannot
+// fire (cam_prepare_dev<false>, sfm_common.h); false: a non-finite camera or qw ~ 0.
+__device__ __forceinline__ bool mo_step(const double* sums, double lambda, double (&params)[7], CamPrep& c) {
+  double a[28], b[7];
+#pragma unroll
+  for (int k = 0; k < 28; ++k) a[k] = sums[k];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    a[i * (i + 1) / 2 + i] += lambda;
+    b[i] = sums[28 + i];
+  }
+  solve7_spd(a, b);
+#pragma unroll
+  for (int i = 0; i < 7; ++i) params[i] += b[i];
+  const double inq = rsqrt_nr(params[3] * params[3] + params[4] * params[4] + params[5] * params[5] + params[6] * params[6]);
+#pragma unroll
+  for (int i = 3; i < 7; ++i) params[i] *= inq;
+  const double chk = mo_finite_probe(params, 7);
+  const int st = cam_prepare_dev<false>(params, &c);
+  return st == SFM_OK && chk == 0.0;
+}
+
+// One workgroup per camera of n_lo .. n_hi observations (the other size classes' launches skip it).  THREADS = 64 serves
+// up to 256 observations, THREADS = 256 up to 1 024: a lane's four consecutive observations and their points stay in
+// registers over all iterations.  STREAM (THREADS = 256): the camera is worked through in blocks of 1 024 observations,
+// read again in every pass (they stay in L2), the 36 running totals carried from block to block by the threads that add
+// the row partials -- the slices are still added in ascending order.  Pass `it` linearises at the current camera; pass 0
+// yields cost row 0, the pass after the last update yields cost row 1 and SFM_CAM_BEHIND.  A held or empty camera stops
+// after pass 0.
+template <int THREADS, bool STREAM, int LOSS>
+__global__ __launch_bounds__(THREADS) void ba_motion_resident_kernel(BaDev d, int cur, MoArgs a, int n_lo, int n_hi, LossArg<LOSS> la) {
+  static_assert(!STREAM || THREADS * kMoPerLane == kMoBlockObs, "a streamed block is one round of the workgroup");
+  constexpr int ROWS = THREADS / 16;
+  __shared__ double red[ROWS][kMoSums];
+  __shared__ double sums[kMoSums];
+  const int cam = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int base = a.ptr[cam], n = a.ptr[cam + 1] - base;
+  if (n < n_lo || n > n_hi) return;
+  const bool held = a.mask != nullptr && a.mask[cam] == 0;
+  const int my_iters = (held || n == 0) ? 0 : a.iters;
+  MoObs ob[kMoPerLane];
+  if (!STREAM) {
+#pragma unroll
+    for (int k = 0; k < kMoPerLane; ++k)
+      if (kMoPerLane * tid + k < n) mo_load(d, a.obs + base, kMoPerLane * tid + k, ob[k]);
+  }
+  const int n_blocks = STREAM ? (n + kMoBlockObs - 1) / kMoBlockObs : 1;
+  int own[3];
+  mo_fold_own(lane, own);
+  CamPrep c;
+  load_cam(c, d.prep[cur] + cam);
+  double params[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) params[k] = d.cams[7 * (size_t)cam + k];
+  int flags = (held ? SFM_CAM_HELD : 0) | (n == 0 ? SFM_CAM_EMPTY : 0);
+  double cost0 = 0, cost1 = 0;
+  for (int it = 0;; ++it) {
+    int behind = 0, any_behind = 0;
+    double run = 0;                                           // threads 0 .. 35: the running total of their sum
+    for (int blk = 0; blk < n_blocks; ++blk) {
+      double acc[kMoSums];
+#pragma unroll
+      for (int k = 0; k < kMoSums; ++k) acc[k] = 0;
+#pragma unroll
+      for (int k = 0; k < kMoPerLane; ++k) {
+        const int i = blk * kMoBlockObs + kMoPerLane * tid + k;
+        if (i < n) {
+          if (STREAM) mo_load(d, a.obs + base, i, ob[k]);
+          mo_accumulate<LOSS>(c, ob[k], a.quirks, la, acc, behind);
+        }
+      }
+      mo_fold_row(acc, own, lane, red[tid >> 4]);
+      const bool last = blk == n_blocks - 1;                  // (uniform over the workgroup)
+      if (last) any_behind = __syncthreads_or(behind);
+      else __syncthreads();
+      if (tid < kMoSums) {
+        double t = blk == 0 ? red[0][tid] : run + red[0][tid];
+#pragma unroll
+        for (int w = 1; w < ROWS; ++w) t += red[w][tid];      // slice order; the rows beyond the camera's slices hold zeros
+        run = t;
+        if (last) sums[tid] = t;
+      }
+      __syncthreads();                                        // sums complete / red free for the next block
+    }
+    // from here on every thread holds the same values: the branches are uniform
+    const double chk = mo_finite_probe(sums, kMoSums);
+    if (it == 0) cost0 = sums[35];
+    if (!(chk == 0.0)) { flags |= SFM_CAM_NONFINITE; cost1 = cost0; break; }
+    if (it == my_iters) {
+      cost1 = sums[35];
+      if (any_behind) flags |= SFM_CAM_BEHIND;
+      break;
+    }
+    if (!mo_step(sums, a.lambda, params, c)) { flags |= SFM_CAM_NONFINITE; cost1 = cost0; break; }
+    // (the next pass writes red after this pass' last read of it, and sums only behind its first barrier)
+  }
+  if (tid == 0) {
+    if (my_iters > 0 && !(flags & SFM_CAM_NONFINITE)) {
+#pragma unroll
+      for (int k = 0; k < 7; ++k) d.cams[7 * (size_t)cam + k] = params[k];
+    }
+    a.cost[cam] = cost0;
+    a.cost[(size_t)a.V + cam] = cost1;
+    a.status[cam] = flags;
+  }
+}
+
+// first workspace row of a camera whose list starts at `base`: camera k has at most n_k / 64 + 1 slices, so the rows of
+// the cameras before it end at or before base / 64 + cam (no scan needed; the workspace has M / 64 + V + 1 rows)
+__device__ __forceinline__ size_t mo_ws_row(int base, int cam) { return (size_t)(base / kMoSlice) + cam; }
+
+// Cameras of more than n_min observations, one pass: workgroup (camera, block) sums observations [1024 block, +1024) of the
+// camera's list at the prepared camera prep[cur] into one 36-vector per slice.
+template <int LOSS>
+__global__ __launch_bounds__(256) void ba_motion_partial_kernel(BaDev d, int cur, MoArgs a, int n_min, double* __restrict__ ws,
+                                                                int* __restrict__ behind_flag, LossArg<LOSS> la) {
+  __shared__ double red[16][kMoSums];
+  const int cam = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const int base = a.ptr[cam], n = a.ptr[cam + 1] - base;
+  if (n <= n_min || (long long)blk * kMoBlockObs >= n) return;
+  if (a.status[cam] & kMoDone) return;
+  int own[3];
+  mo_fold_own(lane, own);
+  CamPrep c;
+  load_cam(c, d.prep[cur] + cam);
+  double acc[kMoSums];
+#pragma unroll
+  for (int k = 0; k < kMoSums; ++k) acc[k] = 0;
+  int behind = 0;
+#pragma unroll
+  for (int k = 0; k < kMoPerLane; ++k) {
+    const int i = blk * kMoBlockObs + kMoPerLane * tid + k;
+    if (i < n) {
+      MoObs ob;
+      mo_load(d, a.obs + base, i, ob);
+      mo_accumulate<LOSS>(c, ob, a.quirks, la, acc, behind);
+    }
+  }
+  mo_fold_row(acc, own, lane, red[tid >> 4]);
+  const int any_behind = __syncthreads_or(behind);
+  if (any_behind && tid == 0) atomicOr(&behind_flag[cam], 1);
+  const int n_slices = (n + kMoSlice - 1) / kMoSlice;
+  const int rows = min(16, n_slices - blk * 16);
+  double* dst = ws + (mo_ws_row(base, cam) + (size_t)blk * 16) * kMoSums;
+  const double* src = &red[0][0];
+  for (int i = tid; i < rows * kMoSums; i += 256) dst[i] = src[i];
+}
+
+// ... and its second half, one wave per camera: the slice vectors added in slice order, then what ba_motion_resident does
+// with the sums of pass `it`.  The camera and its prepared form travel through d.cams / d.prep[cur] between the passes;
+// cams_in restores a camera that turns non-finite.
+__global__ __launch_bounds__(64) void ba_motion_finish_kernel(BaDev d, int cur, MoArgs a, int n_min, const double* __restrict__ ws,
+                                                              int* __restrict__ behind_flag, const double* __restrict__ cams_in, int it) {
+  __shared__ double sums[kMoSums];
+  const int cam = blockIdx.x, tid = threadIdx.x;
+  const int base = a.ptr[cam], n = a.ptr[cam + 1] - base;
+  if (n <= n_min) return;
+  if (a.status[cam] & kMoDone) return;
+  const int n_slices = (n + kMoSlice - 1) / kMoSlice;
+  if (tid < kMoSums) {
+    const double* part = ws + mo_ws_row(base, cam) * kMoSums + tid;
+    double t = part[0];
+    for (int s = 1; s < n_slices; ++s) t += part[(size_t)s * kMoSums];
+    sums[tid] = t;
+  }
+  __syncthreads();
+  const bool held = a.mask != nullptr && a.mask[cam] == 0;
+  const int my_iters = held ? 0 : a.iters;
+  const int flags = held ? SFM_CAM_HELD : 0;
+  const double chk = mo_finite_probe(sums, kMoSums);
+  const double cost0 = it == 0 ? sums[35] : a.cost[cam];
+  bool ok = chk == 0.0;
+  if (ok && it == my_iters) {
+    if (tid == 0) {
+      if (it == 0) a.cost[cam] = cost0;
+      a.cost[(size_t)a.V + cam] = sums[35];
+      a.status[cam] = flags | (behind_flag[cam] ? SFM_CAM_BEHIND : 0) | kMoDone;
+      behind_flag[cam] = 0;
+    }
+    return;
+  }
+  double params[7];
+  CamPrep c;
+  if (ok) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k) params[k] = d.cams[7 * (size_t)cam + k];
+    ok = mo_step(sums, a.lambda, params, c);
+  }
+  if (tid != 0) return;
+  behind_flag[cam] = 0;
+  if (it == 0) a.cost[cam] = cost0;
+  if (ok) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k) d.cams[7 * (size_t)cam + k] = params[k];
+    d.prep[cur][cam] = c;
+  } else {
+    for (int k = 0; k < 7; ++k) d.cams[7 * (size_t)cam + k] = cams_in[7 * (size_t)cam + k];
+    a.cost[(size_t)a.V + cam] = cost0;
+    a.status[cam] = flags | SFM_CAM_NONFINITE | kMoDone;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+static int mo_size_class(long long n) {
+  return n <= 0 ? 0 : (n <= kMoWaveObs ? 1 : (n <= kMoBlockObs ? 2 : (n <= kMoStreamObs ? 3 : 4)));
+}
+
+// The stable list of the scene, built once (a grown or culled scene is a new BaScene and starts without one).
+static int mo_build_list(sfm_ba_problem* p) {
+  if (p->motion_built) return SFM_OK;
+  const BaDev& d = p->dev;
+  hipStream_t s = p->stream;
+  const int V = d.V;
+  const long long M = d.M;
+  SFM_TRY(scene_alloc(*p, p->mo_ptr, (size_t)V + 1));
+  SFM_TRY(scene_alloc(*p, p->mo_obs, (size_t)M));
+  // at most 1 024 chunks of at least 1 024 observations: the count table stays within 1 024 V integers
+  const int chunk_obs = (int)std::max<long long>(1024, ((M + 1023) / 1024 + 63) / 64 * 64);
+  const int nchunks = (int)((M + chunk_obs - 1) / chunk_obs);
+  DevBuf<int> table, cnt;
+  SFM_TRY(table.alloc((size_t)nchunks * V, s));
+  SFM_TRY(cnt.alloc((size_t)V, s));
+  SFM_HIP(hipMemsetAsync(table.p, 0, sizeof(int) * (size_t)nchunks * V, s));
+  mo_count_kernel<<<(unsigned)((M + 255) / 256), 256, 0, s>>>(M, V, chunk_obs, d.cam_idx, table.p);
+  mo_chunk_scan_kernel<<<(V + 255) / 256, 256, 0, s>>>(V, nchunks, table.p, cnt.p);
+  mo_ptr_scan_kernel<<<1, kScanBlock, 0, s>>>(V, cnt.p, p->mo_ptr);
+  mo_fill_kernel<<<nchunks, 64, 0, s>>>(M, V, chunk_obs, d.cam_idx, p->mo_ptr, table.p, p->mo_obs);
+  SFM_HIP(hipGetLastError());
+  p->h_mo_ptr.assign((size_t)V + 1, 0);
+  SFM_HIP(hipMemcpyAsync(p->h_mo_ptr.data(), p->mo_ptr, sizeof(int) * ((size_t)V + 1), hipMemcpyDeviceToHost, s));
+  SFM_TRY(stream_sync(s));
+  p->motion_built = true;
+  return SFM_OK;
+}
+
+// SFM_OPT_DEBUG bit 32768 (measurement only): cameras of size class 3 take class 4's launches
+template <int LOSS>
+static int mo_enqueue(sfm_ba_problem* p, const MoArgs& a, const int (&n_class)[5], int max_obs, DevBuf<double>& ws,
+                      DevBuf<int>& behind, DevBuf<double>& cams_in) {
+  const BaDev& d = p->dev;
+  hipStream_t s = p->stream;
+  const LossArg<LOSS> la = loss_arg<LOSS>(p);
+  const bool stream3 = !(p->debug & 32768);
+  const int n_min = stream3 ? kMoStreamObs : kMoBlockObs;      // the multi-launch path takes the cameras beyond it
+  if (n_class[0] + n_class[1] > 0)
+    ba_motion_resident_kernel<64, false, LOSS><<<d.V, 64, 0, s>>>(d, p->cur, a, 0, kMoWaveObs, la);
+  if (n_class[2] > 0)
+    ba_motion_resident_kernel<256, false, LOSS><<<d.V, 256, 0, s>>>(d, p->cur, a, kMoWaveObs + 1, kMoBlockObs, la);
+  if (n_class[3] > 0 && stream3)
+    ba_motion_resident_kernel<256, true, LOSS><<<d.V, 256, 0, s>>>(d, p->cur, a, kMoBlockObs + 1, kMoStreamObs, la);
+  if (n_class[4] > 0 || (n_class[3] > 0 && !stream3)) {
+    SFM_TRY(ws.alloc(((size_t)d.M / kMoSlice + d.V + 1) * kMoSums, s));
+    SFM_TRY(behind.alloc((size_t)d.V, s));
+    SFM_TRY(cams_in.alloc(7 * (size_t)d.V, s));
+    SFM_HIP(hipMemsetAsync(behind.p, 0, sizeof(int) * (size_t)d.V, s));
+    SFM_HIP(hipMemcpyAsync(cams_in.p, d.cams, sizeof(double) * 7 * d.V, hipMemcpyDeviceToDevice, s));
+    const dim3 grid((unsigned)d.V, (unsigned)((max_obs + kMoBlockObs - 1) / kMoBlockObs));
+    for (int it = 0; it <= a.iters; ++it) {
+      ba_motion_partial_kernel<LOSS><<<grid, 256, 0, s>>>(d, p->cur, a, n_min, ws.p, behind.p, la);
+      ba_motion_finish_kernel<<<d.V, 64, 0, s>>>(d, p->cur, a, n_min, ws.p, behind.p, cams_in.p, it);
+    }
+  }
+  SFM_HIP(hipGetLastError());
+  return SFM_OK;
+}
+
+}  // namespace sfm
+
+using namespace sfm;
+
+extern "C" {
+
+int sfm_ba_refine_cameras_plan(int64_t n_obs, int* n_slices, int* slice_obs, int* size_class) {
+  if (n_obs < 0) { set_error("sfm_ba_refine_cameras_plan: n_obs < 0"); return SFM_E_SHAPE; }
+  if (n_slices) *n_slices = (int)((n_obs + kMoSlice - 1) / kMoSlice);
+  if (slice_obs) *slice_obs = kMoSlice;
+  if (size_class) *size_class = mo_size_class(n_obs);
+  return SFM_OK;
+}
+
+int sfm_ba_refine_cameras(sfm_ba_problem* p, double lambda, int iters, int quirks, int use_loss, const unsigned char* cam_mask,
+                          double* cost, int* status) {
+  if (p == nullptr || p->magic != kBaMagic) {
+    set_error("invalid bundle-adjustment problem handle");
+    return SFM_E_HANDLE;
+  }
+  if (iters < 0) { set_error("sfm_ba_refine_cameras: iters < 0"); return SFM_E_SHAPE; }
+  if (!(lambda >= 0)) { set_error("sfm_ba_refine_cameras: lambda must be >= 0"); return SFM_E_SHAPE; }
+  if (use_loss != 0 && use_loss != 1) { set_error("sfm_ba_refine_cameras: use_loss must be 0 or 1"); return SFM_E_SHAPE; }
+  if (p->comm) {
+    set_error("sfm_ba_refine_cameras: not with a communicator attached (the points are sharded; the replicas would diverge)");
+    return SFM_E_SHAPE;
+  }
+  BaDev& d = p->dev;
+  const int V = d.V;
+  SFM_TRY(ba_flush(p));                                  // a deferred back substitution still owes the points its update
+  if (d.N == 0 || d.M == 0) {                            // nothing to fit: every camera is empty
+    for (int c = 0; c < V; ++c) {
+      if (cost) cost[c] = cost[(size_t)V + c] = 0.0;
+      if (status) status[c] = SFM_CAM_EMPTY | ((cam_mask && cam_mask[c] == 0) ? SFM_CAM_HELD : 0);
+    }
+    return SFM_OK;
+  }
+  hipStream_t s = p->stream;
+  if (!p->prep_valid) SFM_TRY(ba_enqueue_prep(p));       // the expanded cameras the linearisation reads
+  {
+    int st[2] = {0, 0};
+    SFM_HIP(hipMemcpyAsync(st, d.status, sizeof(st), hipMemcpyDeviceToHost, s));
+    SFM_TRY(stream_sync(s));
+    if (st[0] != SFM_OK) {
+      set_error("sfm_ba_refine_cameras: camera %d is invalid (status %d)", st[1], st[0]);
+      return st[0];
+    }
+  }
+  SFM_TRY(mo_build_list(p));
+  int n_class[5] = {0, 0, 0, 0, 0}, max_obs = 0;
+  for (int c = 0; c < V; ++c) {
+    const int n = p->h_mo_ptr[c + 1] - p->h_mo_ptr[c];
+    ++n_class[mo_size_class(n)];
+    max_obs = std::max(max_obs, n);
+  }
+  if ((max_obs + kMoBlockObs - 1) / kMoBlockObs > 65535) {
+    set_error("sfm_ba_refine_cameras: a camera of %d observations is beyond the launch grid", max_obs);
+    return SFM_E_SHAPE;
+  }
+  DevBuf<unsigned char> dmask;
+  DevBuf<double> dcost, ws, cams_in;
+  DevBuf<int> dstat, behind;
+  if (cam_mask) {
+    SFM_TRY(dmask.upload(cam_mask, (size_t)V, s));
+    p->upload_bytes += V;
+  }
+  SFM_TRY(dcost.alloc(2 * (size_t)V, s));
+  SFM_TRY(dstat.alloc((size_t)V, s));
+  SFM_HIP(hipMemsetAsync(dstat.p, 0, sizeof(int) * (size_t)V, s));
+  MoArgs a = {};
+  a.V = V; a.ptr = p->mo_ptr; a.obs = p->mo_obs; a.mask = cam_mask ? dmask.p : nullptr;
+  a.lambda = lambda; a.iters = iters; a.quirks = quirks;
+  a.cost = dcost.p; a.status = dstat.p;
+  switch (use_loss ? p->loss_kind : SFM_LOSS_NONE) {
+    case SFM_LOSS_HUBER: SFM_TRY(mo_enqueue<SFM_LOSS_HUBER>(p, a, n_class, max_obs, ws, behind, cams_in)); break;
+    case SFM_LOSS_CAUCHY: SFM_TRY(mo_enqueue<SFM_LOSS_CAUCHY>(p, a, n_class, max_obs, ws, behind, cams_in)); break;
+    default: SFM_TRY(mo_enqueue<SFM_LOSS_NONE>(p, a, n_class, max_obs, ws, behind, cams_in)); break;
+  }
+  // new cameras start a new cost history and need a new expansion, as after sfm_ba_set_cameras
+  SFM_HIP(hipMemsetAsync(d.cost, 0, kStatSlots * sizeof(double), s));
+  SFM_HIP(hipMemsetAsync(d.iter_count, 0, sizeof(int), s));
+  p->prep_valid = false;
+  if (cost) SFM_TRY(dcost.download(cost, 2 * (size_t)V, s));
+  if (status) SFM_TRY(dstat.download(status, (size_t)V, s));
+  SFM_TRY(stream_sync(s));
+  if (status)
+    for (int c = 0; c < V; ++c) status[c] &= ~kMoDone;
+  return SFM_OK;
+}
+
+}  // extern "C"

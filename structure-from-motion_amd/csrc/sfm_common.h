@@ -239,6 +239,42 @@ __device__ __forceinline__ void chol3_inv_fast(const double* a, double* li) {
 
 __device__ __forceinline__ double wave_sum(double v) { return group_sum<64>(v); }
 
+// (J^T J + lambda I) x = b for the 7x7 SPD normal equations, lower triangle packed row-wise (a[i(i+1)/2 + j]).
+// Fully unrolled Cholesky in registers (no pivoting needed for an SPD matrix; the reference inverts with LU,
+// campose:409 -- same solution to rounding).  a is destroyed, b becomes the solution.
+__device__ __forceinline__ void solve7_spd(double (&a)[28], double (&b)[7]) {
+  double inv[7];
+#pragma unroll
+  for (int j = 0; j < 7; ++j) {
+    double d = a[j * (j + 1) / 2 + j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) d -= a[j * (j + 1) / 2 + k] * a[j * (j + 1) / 2 + k];
+    inv[j] = rsqrt_nr(d);
+    a[j * (j + 1) / 2 + j] = d * inv[j];
+#pragma unroll
+    for (int i = j + 1; i < 7; ++i) {
+      double v = a[i * (i + 1) / 2 + j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) v -= a[i * (i + 1) / 2 + k] * a[j * (j + 1) / 2 + k];
+      a[i * (i + 1) / 2 + j] = v * inv[j];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {          // L y = b
+    double v = b[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) v -= a[i * (i + 1) / 2 + k] * b[k];
+    b[i] = v * inv[i];
+  }
+#pragma unroll
+  for (int i = 6; i >= 0; --i) {         // L^T x = y
+    double v = b[i];
+#pragma unroll
+    for (int k = i + 1; k < 7; ++k) v -= a[k * (k + 1) / 2 + i] * b[k];
+    b[i] = v * inv[i];
+  }
+}
+
 // One-sided Jacobi on the columns of B (N x N, row-major B[row][col]): on return the columns of B are
 // mutually orthogonal (B_out = B_in V, column c = sigma_c u_c) and V holds the right singular vectors as
 // columns.  Column order is whatever the sweeps leave; callers pick columns by norm.

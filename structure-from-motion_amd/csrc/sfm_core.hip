@@ -239,43 +239,8 @@ static int tri_host(int m, int n_views, const double* projs, const double* uv, c
 // re-normalises the quaternion and rebuilds R(q) for the next iteration.
 // Quirk Q1 (default): the reference stores each point's 2 rows at [pt : pt+2], so only the u-row of
 // every point and the v-row of the LAST point survive (campose_processor.py:404-405).
+// The 7x7 solve is solve7_spd (sfm_common.h), shared with the motion-only refinement (sfm_ba_motion.hip).
 // ---------------------------------------------------------------------------------------------
-// (J^T J + lambda I) x = b for the 7x7 SPD normal equations, lower triangle packed row-wise (a[i(i+1)/2 + j]).
-// Fully unrolled Cholesky in registers (no pivoting needed for an SPD matrix; the reference inverts with LU,
-// campose:409 -- same solution to rounding).  a is destroyed, b becomes the solution.
-__device__ __forceinline__ void solve7_spd(double (&a)[28], double (&b)[7]) {
-  double inv[7];
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    double d = a[j * (j + 1) / 2 + j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) d -= a[j * (j + 1) / 2 + k] * a[j * (j + 1) / 2 + k];
-    inv[j] = rsqrt_nr(d);
-    a[j * (j + 1) / 2 + j] = d * inv[j];
-#pragma unroll
-    for (int i = j + 1; i < 7; ++i) {
-      double v = a[i * (i + 1) / 2 + j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v -= a[i * (i + 1) / 2 + k] * a[j * (j + 1) / 2 + k];
-      a[i * (i + 1) / 2 + j] = v * inv[j];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {          // L y = b
-    double v = b[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v -= a[i * (i + 1) / 2 + k] * b[k];
-    b[i] = v * inv[i];
-  }
-#pragma unroll
-  for (int i = 6; i >= 0; --i) {         // L^T x = y
-    double v = b[i];
-#pragma unroll
-    for (int k = i + 1; k < 7; ++k) v -= a[k * (k + 1) / 2 + i] * b[k];
-    b[i] = v * inv[i];
-  }
-}
-
 // One workgroup per view.  The view's points (and their normalised keys, a constant of the problem) stay in
 // registers across all iterations when the view has at most 256 * PNP_CACHE points; per iteration every thread
 // linearises its points (35 accumulators), a DPP wave reduction + a 35-thread sum over the 4 waves gives the

@@ -40,6 +40,7 @@ TRACK_GROUPS = (0, 1, 4, 8, 16, 32, 64)
 OBS_HIGH_ERROR, OBS_BEHIND, OBS_NONFINITE, OBS_POINT = 1, 2, 4, 8
 PT_TOO_FEW, PT_LOW_ANGLE, PT_EMPTY = 1, 2, 4
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2
+CAM_EMPTY, CAM_NONFINITE, CAM_BEHIND, CAM_HELD = 1, 2, 4, 8
 LOSS_NAMES = {"none": LOSS_NONE, "huber": LOSS_HUBER, "cauchy": LOSS_CAUCHY}
 SCREEN_SUMMARY = ("obs_before", "obs_kept", "high_error", "behind", "nonfinite", "obs_dropped_with_point", "pts_too_few",
                   "pts_low_angle")
@@ -180,6 +181,8 @@ SIGNATURES = {
     "sfm_ba_get_loss": [vp, _ip, _dp],
     "sfm_ba_loss_terms": [vp, _dp, _dp, _dp],
     "sfm_ba_reduced_system_loss": [ci, ci, i64, _ip, _ip, _dp, _dp, _dp, cd, ci, ci, ci, cd, _dp, _dp],
+    "sfm_ba_refine_cameras": [vp, cd, ci, ci, ci, ctypes.POINTER(ctypes.c_uint8), _dp, _ip],
+    "sfm_ba_refine_cameras_plan": [i64, _ip, _ip, _ip],
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -716,6 +719,15 @@ def ba_solve(n_cams, pt_ptr, cam_idx, uv_norm, cams, pts, lam, iters, quirks=QUI
     return cams, pts
 
 
+def refine_cameras_plan(n_obs):
+    """How ``BaProblem.refine_cameras`` works on a camera of ``n_obs`` observations (sfm_ba_refine_cameras_plan; host only):
+    ``(n_slices, slice_obs, size_class)`` -- the sums are formed per slice of ``slice_obs`` consecutive observations and
+    added in slice order; size class 0 = empty, 1 / 2 / 3 = one launch for all iterations, 4 = two launches per pass."""
+    a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(load().sfm_ba_refine_cameras_plan(int(n_obs), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return int(a.value), int(b.value), int(c.value)
+
+
 class BaProblem:
     """Device-resident BA problem (sfm_ba_create ... sfm_ba_destroy)."""
 
@@ -904,6 +916,23 @@ class BaProblem:
             return None
         cost = np.zeros((2, n)); status = np.zeros(n, dtype=np.int32)
         check(self._lib.sfm_ba_refine_points(self._h, mode, float(lam), iters, group, dptr(cost), iptr(status)))
+        return cost, status
+
+    def refine_cameras(self, lam, iters, quirks=QUIRKS_REFERENCE, use_loss=False, mask=None, want_cost=False, want_status=False):
+        """Motion-only refinement of the resident cameras, points held (sfm_ba_refine_cameras): ``iters`` damped steps per
+        camera over its own observations, reweighted by the problem's loss when ``use_loss``.  ``mask`` (V,): cameras with
+        a zero entry are held (None: every camera moves).  Returns ``(cost (2, V) or None, status (V,) of CAM_* bits or
+        None)`` as ``want_cost`` / ``want_status`` ask."""
+        v = self.info(INFO_N_CAMS)
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).ravel()
+            if mask.shape[0] != v:
+                raise ValueError("mask must have one entry per camera (%d), got %d" % (v, mask.shape[0]))
+        cost = np.zeros((2, v)) if want_cost else None
+        status = np.zeros(v, dtype=np.int32) if want_status else None
+        check(self._lib.sfm_ba_refine_cameras(self._h, float(lam), int(iters), int(quirks), int(use_loss),
+                                              mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if mask is not None else None,
+                                              dptr(cost) if want_cost else None, iptr(status) if want_status else None))
         return cost, status
 
     def _screen(self, name, max_err2, cos_min_angle, min_obs, cam_scale, want_outputs, group):

@@ -644,6 +644,49 @@ class HipBaMixin:
         tri_pts[0:3, :] = pts
         return cost, status
 
+    def refine_motion(self, iters=None, views=None, use_loss=True, damping_factor=None):
+        """Motion-only refinement of the resident scene: every camera from all its resident observations with the points
+        held (``BaProblem.refine_cameras``), after the scene has been brought up to date exactly as
+        ``execute_bundle_adjustment`` does.  ``views``: the indices of the views to refine (None: all; the others are held
+        through the mask).  ``use_loss``: reweight by ``ba_loss`` when one is set.  Falsy ``iters`` / ``damping_factor``
+        fall back to ``self.iteration`` / ``self.damping_factor``.  Writes the poses back through ``view.update_cam_pose``
+        as ``execute_bundle_adjustment`` does, leaves ``tri_pts`` alone and returns ``(cost (2, V), status (V,))``.
+        Needs ``ba_resident``; nothing in ``process()`` calls it."""
+        if not self.ba_resident:
+            raise TypeError("refine_motion needs ba_resident")
+        if self.ba_device_tracks:
+            self._ba_check_device_tracks()
+        if not damping_factor:
+            damping_factor = self.damping_factor
+        if not iters:
+            iters = self.iteration
+        view_list = self.view_processor.view_list
+        view_num = len(view_list)
+        mask = None
+        if views is not None:
+            idx = np.asarray(list(views), dtype=np.int64).ravel()
+            if idx.size and (idx.min() < 0 or idx.max() >= view_num):
+                raise ValueError("refine_motion: view index outside the {} views".format(view_num))
+            mask = np.zeros(view_num, dtype=np.uint8)
+            mask[idx] = 1
+        init_rots = np.stack([np.asarray(v.rot, dtype=np.float64) for v in view_list])
+        init_locs = np.stack([np.asarray(v.loc, dtype=np.float64).reshape(3) for v in view_list])
+        init_tri_pts = np.ascontiguousarray(self.tri_processor.tri_pts[0:3, :], dtype=np.float64)
+        scene = self._ba_update_resident(view_list, init_rots, init_locs, init_tri_pts)
+        try:
+            scene.cams_synced = False
+            cost, status = scene.prob.refine_cameras(damping_factor, iters, self.ba_quirk_flags, bool(use_loss), mask,
+                                                     want_cost=True, want_status=True)
+            cams, pts, rots = scene.prob.get_state_rot()
+        except Exception:
+            self.ba_release()
+            raise
+        scene.pts_written = pts                        # (the points did not move: bit for bit what the device was given)
+        scene.rots_written, scene.locs_written = rots, cams[:, 0:3].copy()
+        for view_idx in range(view_num):
+            view_list[view_idx].update_cam_pose(rots[view_idx].copy(), cams[view_idx, 0:3].reshape(3, 1).copy())
+        return cost, status
+
     def _ba_screen_scene(self, who, max_reproj_px, min_angle_deg, min_obs):
         """The resident scene brought up to date as ``refine_structure`` does, and the native arguments of a screening:
         (scene, max_err2, cos_min_angle, cam_scale)."""
