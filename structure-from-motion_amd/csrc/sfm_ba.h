@@ -15,6 +15,7 @@ constexpr int kSchurRB = 128;
 constexpr int kSchurMaxChunks = 128;  // split-K slabs of the dense product's tile when it is the only one (up to 18 cameras)
 constexpr int kSchurKSL = 16;    // Z rows per LDS slab; the row count of Zd is padded to a multiple of it
 constexpr int kInvRowsMaxNbk = 52;  // block columns up to which the column steps carry the identity rows (X = L^-T; sfm_ba_solve.hip)
+constexpr size_t kRowsLdsBudget = 156 * 1024;   // LDS of the row-panel product's panel (sfm_ba_schur_rows.hip)
 constexpr int kLinGridPerCu = 3; // ba_linearize workgroups per CU (132 VGPRs -> 3 waves/SIMD; forcing 4 measured 10 % slower)
 
 // ---------------------------------------------------------------------------------------------
@@ -185,6 +186,11 @@ __host__ __device__ inline SchurTileRef plan_locate(const SchurPlan& pl, int w) 
   return SchurTileRef{0, 0, 0, 0, 0};
 }
 
+// Row-panel product: row pitch (doubles) of a panel with the natural camera pitch of 7, and whether the block row of one
+// camera fits the LDS budget at that pitch (up to 407 cameras) -- beyond it the 18-camera tile kernel takes over.
+inline int rows_pitch7(int V) { return ((7 * V + 1) / 2) * 2; }
+inline bool ba_rows_fits(int V) { return (size_t)7 * rows_pitch7(V) * sizeof(double) <= kRowsLdsBudget; }
+
 struct KernelTimer {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
   int used = 0;
@@ -221,24 +227,21 @@ struct BaScene {
   const void* flow_tasks_red = nullptr;
   int flow_ntasks_red = 0;
   double* flow_camsum = nullptr; // [4][35 V] partial camera sums of the deferred reduce
-  // row-panel sparse product (sfm_ba_schur_rows.hip): camera-major observation list and work split, built on first use
+  // camera-major observation list, built on first use by either of its users (ba_cam_list_ensure, sfm_ba_host.hip)
+  bool cam_list_built = false;
+  int* cam_ptr = nullptr;                  // [V+1] device: first entry of every camera
+  int* cam_obs = nullptr;                  // [M] device: observation indices grouped by camera, ascending (= by point) inside one
+  std::vector<int> h_cam_ptr;              // host copy of cam_ptr: both users plan their launches from the observation counts
+  // row-panel sparse product (sfm_ba_schur_rows.hip): its entries and work split, built on first use (ba_rows_ensure)
   bool rows_built = false, rows_ok = false;
-  int* cam_ptr = nullptr;                  // [V+1] device
-  void* cam_ent = nullptr;                 // [M] device int4: the observations grouped by camera (observation, first of its track, camera, k_B)
+  void* cam_ent = nullptr;                 // [M] device int4, entry e = observation cam_obs[e]: (observation, first of its track, camera, k_B)
   unsigned long long* cam_pairs = nullptr; // [V] device: camera pairs the observations of a camera own
-  std::vector<int> h_cam_ptr;
   std::vector<unsigned long long> h_cam_pairs;
   void* rows_table = nullptr;              // [rows_wgs] workgroup -> (camera group, observation range)
   int* rows_first = nullptr;               // [groups+1] first workgroup of every camera group
   void* rows_ws = nullptr;                 // [rows_wgs][7 R][tpr] split-K panels
   int rows_R = 0, rows_tpr = 0, rows_wgs = 0, rows_groups = 0;
   int rows_tpl = 0, rows_cp = 7;          // LDS row pitch and camera pitch of the panel (experiment: 8)
-  // motion-only refinement (sfm_ba_motion.hip): the STABLE camera-major list, built on first use -- cam_ent above is
-  // filled through atomicAdd and has no fixed order inside a camera
-  bool motion_built = false;
-  int* mo_ptr = nullptr;                   // [V+1] device: first entry of every camera
-  int* mo_obs = nullptr;                   // [M] device: observation indices grouped by camera, ascending (= by point) inside one
-  std::vector<int> h_mo_ptr;               // host copy of mo_ptr: the launches are planned from the observation counts
   std::vector<void*> owned;                // every pool buffer allocated on behalf of this scene (scene_alloc)
 };
 
@@ -295,8 +298,8 @@ int ba_screen_run(sfm_ba_problem* p, const char* who, double max_err2, double co
                   int* pt_flags, int64_t* summary, ScreenWork& w);
 int ba_cull_enqueue_scatter(const BaDev& d, const BaDev& e, const ScreenWork& w, hipStream_t s);
 int ba_schur_plan(BaScene& sc);      // plans of both Schur products, their workspace and block offsets
-int ba_rows_enqueue_build(sfm_ba_problem* p);
-int ba_rows_plan(sfm_ba_problem* p);
+int ba_cam_list_ensure(sfm_ba_problem* p);      // sfm_ba_host.hip: the scene's camera-major list, built once (M > 0)
+int ba_rows_ensure(sfm_ba_problem* p);          // ... and on it the row-panel product's entries and work split (sets rows_ok)
 int ba_rows_enqueue(sfm_ba_problem* p, hipStream_t s);
 int ba_enqueue_structure(BaScene& sc, hipStream_t s);      // validate the CSR, fill obs_pt / per-point block offsets / longest track (device)
 int ba_schur_prepare_dense(sfm_ba_problem* p, hipStream_t s);

@@ -6,7 +6,8 @@
 //
 // Everything that scales with the scene is built ON THE DEVICE: the host uploads the caller's CSR as it is
 // (one copy per array) and ba_structure_kernel validates it, derives obs_pt, the per-point 18-camera block
-// offsets of the sparse Schur product and the longest track; sfm_ba_append uploads only the NEW cameras,
+// offsets of the sparse Schur product and the longest track (and, on first use, the ba_cam_list_* chain the
+// camera-major list of the row-panel product and the motion-only refinement); sfm_ba_append uploads only the NEW cameras,
 // points and observations and merges them into the (point, camera)-sorted list with a count / scan /
 // bucket / merge kernel chain.  The host never loops over observations.
 #include <algorithm>
@@ -45,6 +46,63 @@ __global__ void ba_structure_kernel(int V, int N, long long M, const int* __rest
   }
   while (b <= nblk) row[b++] = end;
   atomicMax(&sinfo[2], end - beg);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The camera-major observation list (cam_ptr, cam_obs), once per scene.  The resident observations are sorted by
+// (point, camera), so ascending observation index inside a camera IS ascending point: the order is fixed.
+//   count       per observation: counts per (chunk of observations, camera)
+//   chunk_scan  per camera: a scan over its chunks
+//   ptr_scan    one workgroup: a scan over the cameras
+//   fill        one wave per chunk hands out the slots in observation order
+// ---------------------------------------------------------------------------------------------
+__global__ void ba_cam_list_count_kernel(long long M, int V, int chunk_obs, const int* __restrict__ cam_idx, int* __restrict__ table) {
+  const long long o = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (o >= M) return;
+  atomicAdd(&table[(size_t)(o / chunk_obs) * V + cam_idx[o]], 1);      // integer: the counts do not depend on the order
+}
+
+// per camera: counts of its chunks -> their exclusive prefix (the chunk's first slot inside the camera), and the total
+__global__ void ba_cam_list_chunk_scan_kernel(int V, int nchunks, int* __restrict__ table, int* __restrict__ cnt) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= V) return;
+  int off = 0;
+  for (int k = 0; k < nchunks; ++k) {
+    const int t = table[(size_t)k * V + c];
+    table[(size_t)k * V + c] = off;
+    off += t;
+  }
+  cnt[c] = off;
+}
+
+__global__ __launch_bounds__(kScanBlock) void ba_cam_list_ptr_scan_kernel(int V, const int* __restrict__ cnt, int* __restrict__ ptr) {
+  block_exclusive_scan<1>(
+      V, [&](int q, int (&a)[1]) { a[0] = cnt[q]; }, [&](int q, const int (&e)[1]) { ptr[q] = e[0]; },
+      [&](const int (&t)[1]) { ptr[V] = t[0]; });
+}
+
+// One wave per chunk, 64 observations at a time: a lane's slot is the chunk's running offset of its camera (fetched and
+// advanced by the first lane of that camera, the only writer of the chunk's table row) plus the number of lower lanes with
+// the same camera.
+__global__ __launch_bounds__(64) void ba_cam_list_fill_kernel(long long M, int V, int chunk_obs, const int* __restrict__ cam_idx,
+                                                              const int* __restrict__ ptr, int* __restrict__ table, int* __restrict__ list) {
+  const int lane = threadIdx.x;
+  const long long o0 = (long long)blockIdx.x * chunk_obs, o1 = min(M, o0 + chunk_obs);
+  int* row = table + (size_t)blockIdx.x * V;
+  for (long long ob = o0; ob < o1; ob += 64) {
+    const long long o = ob + lane;
+    const bool live = o < o1;
+    const int c = live ? cam_idx[o] : -1 - lane;          // idle lanes: cameras of their own
+    int rank = 0, total = 0, lead = lane;
+    for (int j = 63; j >= 0; --j) {
+      const int cj = __shfl(c, j, 64);
+      if (cj == c) { ++total; lead = j; if (j < lane) ++rank; }
+    }
+    int first = 0;
+    if (live && rank == 0) first = atomicAdd(&row[c], total);
+    first = __shfl(first, lead, 64);
+    if (live) list[ptr[c] + first + rank] = (int)o;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -197,6 +255,35 @@ static int ba_finish_structure(BaScene& sc, hipStream_t s, const char* who) {
     default: set_error("%s: observation %d (camera, point) out of range", who, info[1]); break;
   }
   return SFM_E_SHAPE;
+}
+
+// The scene's camera-major list, built on first use by the row-panel product or the motion-only refinement (a grown or
+// culled scene is a new BaScene and starts without one).  Needs M > 0; blocks once for the host copy of cam_ptr.
+int ba_cam_list_ensure(sfm_ba_problem* p) {
+  if (p->cam_list_built) return SFM_OK;
+  const BaDev& d = p->dev;
+  hipStream_t s = p->stream;
+  const int V = d.V;
+  const long long M = d.M;
+  SFM_TRY(scene_alloc(*p, p->cam_ptr, (size_t)V + 1));
+  SFM_TRY(scene_alloc(*p, p->cam_obs, (size_t)M));
+  // at most 1 024 chunks of at least 1 024 observations: the count table stays within 1 024 V integers
+  const int chunk_obs = (int)std::max<long long>(1024, ((M + 1023) / 1024 + 63) / 64 * 64);
+  const int nchunks = (int)((M + chunk_obs - 1) / chunk_obs);
+  DevBuf<int> table, cnt;
+  SFM_TRY(table.alloc((size_t)nchunks * V, s));
+  SFM_TRY(cnt.alloc((size_t)V, s));
+  SFM_HIP(hipMemsetAsync(table.p, 0, sizeof(int) * (size_t)nchunks * V, s));
+  ba_cam_list_count_kernel<<<(unsigned)((M + 255) / 256), 256, 0, s>>>(M, V, chunk_obs, d.cam_idx, table.p);
+  ba_cam_list_chunk_scan_kernel<<<(V + 255) / 256, 256, 0, s>>>(V, nchunks, table.p, cnt.p);
+  ba_cam_list_ptr_scan_kernel<<<1, kScanBlock, 0, s>>>(V, cnt.p, p->cam_ptr);
+  ba_cam_list_fill_kernel<<<nchunks, 64, 0, s>>>(M, V, chunk_obs, d.cam_idx, p->cam_ptr, table.p, p->cam_obs);
+  SFM_HIP(hipGetLastError());
+  p->h_cam_ptr.assign((size_t)V + 1, 0);
+  SFM_HIP(hipMemcpyAsync(p->h_cam_ptr.data(), p->cam_ptr, sizeof(int) * ((size_t)V + 1), hipMemcpyDeviceToHost, s));
+  SFM_TRY(stream_sync(s));
+  p->cam_list_built = true;
+  return SFM_OK;
 }
 
 int scene_alloc_bytes(BaScene& sc, void** ptr, size_t bytes) {
@@ -443,12 +530,8 @@ int sfm_ba_info(sfm_ba_problem* p, int what, int64_t* value) {
       // which decide whether it can run at all -- build them now rather than answer "rows" and then launch "pairs"
       int choice = ba_schur_choice(p);
       if (choice == SFM_SCHUR_ROWS && p->dev.M > 0 && p->dev.N > 0) {
-        if (!p->rows_built) {
-          SFM_TRY(ba_flush(p));
-          SFM_TRY(ba_rows_enqueue_build(p));
-          SFM_TRY(ba_rows_plan(p));
-          p->rows_built = true;
-        }
+        if (!p->rows_built) SFM_TRY(ba_flush(p));
+        SFM_TRY(ba_rows_ensure(p));
         if (!p->rows_ok) choice = SFM_SCHUR_PAIRS;
       }
       *value = choice;

@@ -6,9 +6,8 @@
 // over the camera's observations, r and Jp exactly those of ba_linearize (obs_terms_loss, sfm_ba_terms.h), optionally
 // reweighted by the handle's robust loss.  Nothing couples two cameras, so there is no Schur complement and no reduced solve.
 //
-//   mo_count / mo_chunk_scan / mo_ptr_scan / mo_fill   the STABLE camera-major list (mo_ptr, mo_obs), once per scene:
-//                          counts per (chunk of observations, camera), a scan over the chunks of every camera, a scan over
-//                          the cameras, and one wave per chunk that hands out the slots in observation order
+//   ba_cam_list_ensure     the scene's camera-major list (BaScene::cam_ptr, cam_obs; sfm_ba_host.hip), shared with the
+//                          row-panel Schur product: ascending observation (= ascending point) inside a camera
 //   ba_motion_resident<T>  one workgroup per camera of up to 256 (T = 64) or 1 024 (T = 256) observations: the observations
 //                          stay in registers, all iterations run in one launch, every thread solves the same 7x7;
 //                          STREAM: up to 16 384 observations, read again in every pass, 1 024 at a time
@@ -25,7 +24,6 @@
 
 #include "sfm_ba.h"
 #include "sfm_ba_terms.h"
-#include "sfm_scan.h"
 
 namespace sfm {
 
@@ -39,64 +37,11 @@ constexpr int kMoSums = 36;          // U lower triangle (28) | g (7) | cost sha
 constexpr int kMoDone = 1 << 30;     // internal status bit of the multi-launch path: the camera needs no further pass
 
 // ---------------------------------------------------------------------------------------------
-// The stable list.  The resident observations are sorted by (point, camera), so ascending observation index inside a
-// camera IS ascending point.
-// ---------------------------------------------------------------------------------------------
-__global__ void mo_count_kernel(long long M, int V, int chunk_obs, const int* __restrict__ cam_idx, int* __restrict__ table) {
-  const long long o = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (o >= M) return;
-  atomicAdd(&table[(size_t)(o / chunk_obs) * V + cam_idx[o]], 1);      // integer: the counts do not depend on the order
-}
-
-// per camera: counts of its chunks -> their exclusive prefix (the chunk's first slot inside the camera), and the total
-__global__ void mo_chunk_scan_kernel(int V, int nchunks, int* __restrict__ table, int* __restrict__ cnt) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= V) return;
-  int off = 0;
-  for (int k = 0; k < nchunks; ++k) {
-    const int t = table[(size_t)k * V + c];
-    table[(size_t)k * V + c] = off;
-    off += t;
-  }
-  cnt[c] = off;
-}
-
-__global__ __launch_bounds__(kScanBlock) void mo_ptr_scan_kernel(int V, const int* __restrict__ cnt, int* __restrict__ ptr) {
-  block_exclusive_scan<1>(
-      V, [&](int q, int (&a)[1]) { a[0] = cnt[q]; }, [&](int q, const int (&e)[1]) { ptr[q] = e[0]; },
-      [&](const int (&t)[1]) { ptr[V] = t[0]; });
-}
-
-// One wave per chunk, 64 observations at a time: a lane's slot is the chunk's running offset of its camera (fetched and
-// advanced by the first lane of that camera, the only writer of the chunk's table row) plus the number of lower lanes with
-// the same camera.
-__global__ __launch_bounds__(64) void mo_fill_kernel(long long M, int V, int chunk_obs, const int* __restrict__ cam_idx,
-                                                     const int* __restrict__ ptr, int* __restrict__ table, int* __restrict__ list) {
-  const int lane = threadIdx.x;
-  const long long o0 = (long long)blockIdx.x * chunk_obs, o1 = min(M, o0 + chunk_obs);
-  int* row = table + (size_t)blockIdx.x * V;
-  for (long long ob = o0; ob < o1; ob += 64) {
-    const long long o = ob + lane;
-    const bool live = o < o1;
-    const int c = live ? cam_idx[o] : -1 - lane;          // idle lanes: cameras of their own
-    int rank = 0, total = 0, lead = lane;
-    for (int j = 63; j >= 0; --j) {
-      const int cj = __shfl(c, j, 64);
-      if (cj == c) { ++total; lead = j; if (j < lane) ++rank; }
-    }
-    int first = 0;
-    if (live && rank == 0) first = atomicAdd(&row[c], total);
-    first = __shfl(first, lead, 64);
-    if (live) list[ptr[c] + first + rank] = (int)o;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // The iteration
 // ---------------------------------------------------------------------------------------------
 struct MoArgs {
   int V;
-  const int* ptr;               // [V+1] stable list
+  const int* ptr;               // [V+1] the scene's camera-major list
   const int* obs;               // [M]
   const unsigned char* mask;    // [V] or null
   double lambda;
@@ -375,34 +320,6 @@ static int mo_size_class(long long n) {
   return n <= 0 ? 0 : (n <= kMoWaveObs ? 1 : (n <= kMoBlockObs ? 2 : (n <= kMoStreamObs ? 3 : 4)));
 }
 
-// The stable list of the scene, built once (a grown or culled scene is a new BaScene and starts without one).
-static int mo_build_list(sfm_ba_problem* p) {
-  if (p->motion_built) return SFM_OK;
-  const BaDev& d = p->dev;
-  hipStream_t s = p->stream;
-  const int V = d.V;
-  const long long M = d.M;
-  SFM_TRY(scene_alloc(*p, p->mo_ptr, (size_t)V + 1));
-  SFM_TRY(scene_alloc(*p, p->mo_obs, (size_t)M));
-  // at most 1 024 chunks of at least 1 024 observations: the count table stays within 1 024 V integers
-  const int chunk_obs = (int)std::max<long long>(1024, ((M + 1023) / 1024 + 63) / 64 * 64);
-  const int nchunks = (int)((M + chunk_obs - 1) / chunk_obs);
-  DevBuf<int> table, cnt;
-  SFM_TRY(table.alloc((size_t)nchunks * V, s));
-  SFM_TRY(cnt.alloc((size_t)V, s));
-  SFM_HIP(hipMemsetAsync(table.p, 0, sizeof(int) * (size_t)nchunks * V, s));
-  mo_count_kernel<<<(unsigned)((M + 255) / 256), 256, 0, s>>>(M, V, chunk_obs, d.cam_idx, table.p);
-  mo_chunk_scan_kernel<<<(V + 255) / 256, 256, 0, s>>>(V, nchunks, table.p, cnt.p);
-  mo_ptr_scan_kernel<<<1, kScanBlock, 0, s>>>(V, cnt.p, p->mo_ptr);
-  mo_fill_kernel<<<nchunks, 64, 0, s>>>(M, V, chunk_obs, d.cam_idx, p->mo_ptr, table.p, p->mo_obs);
-  SFM_HIP(hipGetLastError());
-  p->h_mo_ptr.assign((size_t)V + 1, 0);
-  SFM_HIP(hipMemcpyAsync(p->h_mo_ptr.data(), p->mo_ptr, sizeof(int) * ((size_t)V + 1), hipMemcpyDeviceToHost, s));
-  SFM_TRY(stream_sync(s));
-  p->motion_built = true;
-  return SFM_OK;
-}
-
 // SFM_OPT_DEBUG bit 32768 (measurement only): cameras of size class 3 take class 4's launches
 template <int LOSS>
 static int mo_enqueue(sfm_ba_problem* p, const MoArgs& a, const int (&n_class)[5], int max_obs, DevBuf<double>& ws,
@@ -482,10 +399,10 @@ int sfm_ba_refine_cameras(sfm_ba_problem* p, double lambda, int iters, int quirk
       return st[0];
     }
   }
-  SFM_TRY(mo_build_list(p));
+  SFM_TRY(ba_cam_list_ensure(p));
   int n_class[5] = {0, 0, 0, 0, 0}, max_obs = 0;
   for (int c = 0; c < V; ++c) {
-    const int n = p->h_mo_ptr[c + 1] - p->h_mo_ptr[c];
+    const int n = p->h_cam_ptr[c + 1] - p->h_cam_ptr[c];
     ++n_class[mo_size_class(n)];
     max_obs = std::max(max_obs, n);
   }
@@ -504,7 +421,7 @@ int sfm_ba_refine_cameras(sfm_ba_problem* p, double lambda, int iters, int quirk
   SFM_TRY(dstat.alloc((size_t)V, s));
   SFM_HIP(hipMemsetAsync(dstat.p, 0, sizeof(int) * (size_t)V, s));
   MoArgs a = {};
-  a.V = V; a.ptr = p->mo_ptr; a.obs = p->mo_obs; a.mask = cam_mask ? dmask.p : nullptr;
+  a.V = V; a.ptr = p->cam_ptr; a.obs = p->cam_obs; a.mask = cam_mask ? dmask.p : nullptr;
   a.lambda = lambda; a.iters = iters; a.quirks = quirks;
   a.cost = dcost.p; a.status = dstat.p;
   switch (use_loss ? p->loss_kind : SFM_LOSS_NONE) {

@@ -600,8 +600,7 @@ int ba_schur_prepare_dense(sfm_ba_problem* p, hipStream_t s) {
 int ba_schur_choice(const sfm_ba_problem* p) {
   const BaDev& d = p->dev;
   if (p->deterministic && p->schur_mfma_ok) return SFM_SCHUR_MFMA;       // the sparse products accumulate with unordered LDS atomics
-  const bool rows_possible = !(p->debug & 128) && (size_t)7 * (((7 * d.V + 1) / 2) * 2) * sizeof(double) <= ((size_t)156 << 10) &&
-                             !(p->rows_built && !p->rows_ok);
+  const bool rows_possible = !(p->debug & 128) && ba_rows_fits(d.V) && !(p->rows_built && !p->rows_ok);
   if (p->schur_mode == SFM_SCHUR_MFMA && p->schur_mfma_ok) return SFM_SCHUR_MFMA;
   if (p->schur_mode == SFM_SCHUR_PAIRS) return SFM_SCHUR_PAIRS;
   if (p->schur_mode == SFM_SCHUR_ROWS) return rows_possible ? SFM_SCHUR_ROWS : SFM_SCHUR_PAIRS;
@@ -635,11 +634,7 @@ int ba_enqueue_schur(sfm_ba_problem* p, hipStream_t s, bool allow_defer) {
   SchurPlan pl;
   int choice = ba_schur_choice(p);
   if (choice == SFM_SCHUR_ROWS) {            // camera-major list and work split on first use (blocking once)
-    if (!p->rows_built) {
-      SFM_TRY(ba_rows_enqueue_build(p));
-      SFM_TRY(ba_rows_plan(p));
-      p->rows_built = true;
-    }
+    SFM_TRY(ba_rows_ensure(p));
     if (!p->rows_ok) choice = SFM_SCHUR_PAIRS;
   }
   if (choice == SFM_SCHUR_MFMA) {

@@ -7,7 +7,7 @@
 // and the observations of a point are sorted by camera, so those b are the contiguous range [pt_ptr[p], a] -- no
 // search, no empty visits.  A workgroup owns a group of R cameras (R = as many block rows of S as fit in LDS: 7R rows
 // x 7V columns of doubles, R = 2 at V = 200, 7 at V = 50) and a chunk of that group's observations (from the
-// camera-major observation list built once on the device, ba_cam_major_*); its 16 waves take one observation each:
+// scene's camera-major observation list, BaScene::cam_obs, as 16-byte entries); its 16 waves take one observation each:
 // the 21 values of Z_a arrive through the scalar data cache as SGPR operands, lanes = (b, column j) hold Z_b -- nine
 // B-observations per lane round, and a point seen by 30 cameras fills most of the 64 lanes where the 18x18-camera
 // tiles of the first sparse kernel kept 19 busy -- and every product is one ds_add_f64 into the panel.  Panels go to
@@ -16,41 +16,24 @@
 #include <vector>
 
 #include "sfm_ba.h"
-#include "sfm_scan.h"
 
 namespace sfm {
 
 constexpr int ROWS_WAVES = 16;
 constexpr int ROWS_THREADS = 64 * ROWS_WAVES;
-constexpr size_t kRowsLdsBudget = 156 * 1024;
 
-// ---- camera-major observation list (static structure, built at create / append) ------------------------------
-__global__ void ba_cam_major_count_kernel(long long M, const int* __restrict__ cam_idx, const int* __restrict__ obs_pt,
-                                          const int* __restrict__ pt_ptr, int* __restrict__ cnt,
-                                          unsigned long long* __restrict__ pairs) {
-  const long long o = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (o >= M) return;
-  const int c = cam_idx[o];
-  atomicAdd(&cnt[c], 1);
-  atomicAdd(&pairs[c], (unsigned long long)(o - pt_ptr[obs_pt[o]] + 1));      // camera pairs this observation owns
-}
-
-__global__ __launch_bounds__(kScanBlock) void ba_cam_major_scan_kernel(int V, const int* __restrict__ cnt, int* __restrict__ cam_ptr) {
-  block_exclusive_scan<1>(
-      V, [&](int q, int (&a)[1]) { a[0] = cnt[q]; }, [&](int q, const int (&e)[1]) { cam_ptr[q] = e[0]; },
-      [&](const int (&t)[1]) { cam_ptr[V] = t[0]; });
-}
-
-// entry of the camera-major list: everything a visit needs about its A-observation in ONE 16-byte load (the chain
-// cam_obs -> obs_pt -> pt_ptr of dependent loads cost three L2 round trips per visit: 410 us at the C4 share)
-__global__ void ba_cam_major_fill_kernel(long long M, const int* __restrict__ cam_idx, const int* __restrict__ obs_pt,
-                                         const int* __restrict__ pt_ptr, const int* __restrict__ cam_ptr,
-                                         int* __restrict__ fill, int4* __restrict__ cam_ent) {
-  const long long o = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (o >= M) return;
-  const int c = cam_idx[o];
-  const int b0 = pt_ptr[obs_pt[o]];
-  cam_ent[cam_ptr[c] + atomicAdd(&fill[c], 1)] = int4{(int)o, b0, c, (int)o - b0 + 1};      // observation, first of its track, camera, k_B
+// ---- entries: the scene's camera-major list (cam_obs, ascending inside a camera) expanded for the product ------
+// Everything a visit needs about its A-observation in ONE 16-byte load (the chain cam_obs -> obs_pt -> pt_ptr of
+// dependent loads cost three L2 round trips per visit: 410 us at the C4 share), and the camera pairs a camera's
+// observations own (integer atomic: the sums do not depend on the order).
+__global__ void ba_rows_entries_kernel(long long M, const int* __restrict__ cam_obs, const int* __restrict__ cam_idx,
+                                       const int* __restrict__ obs_pt, const int* __restrict__ pt_ptr,
+                                       int4* __restrict__ cam_ent, unsigned long long* __restrict__ pairs) {
+  const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (e >= M) return;
+  const int o = cam_obs[e], c = cam_idx[o], b0 = pt_ptr[obs_pt[o]];
+  cam_ent[e] = int4{o, b0, c, o - b0 + 1};      // observation, first of its track, camera, k_B
+  atomicAdd(&pairs[c], (unsigned long long)(o - b0 + 1));
 }
 
 // ---- the product ---------------------------------------------------------------------------------------------
@@ -151,39 +134,28 @@ __global__ __launch_bounds__(256) void ba_schur_rows_reduce_kernel(BaDev d, cons
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------
-// Camera-major list of the problem's observations (cam_ptr / cam_obs on the device, per-camera counts and pair
-// counts on the host for the work split).  Enqueued behind the structure kernel; ba_rows_finish reads it back.
-int ba_rows_enqueue_build(sfm_ba_problem* p) {
+// The entries and the per-camera pair counts (on the host too, for the work split), from the scene's list.
+static int ba_rows_build_entries(sfm_ba_problem* p) {
   const BaDev& d = p->dev;
   hipStream_t s = p->stream;
-  SFM_TRY(scene_alloc(*p, p->cam_ptr, (size_t)d.V + 1));
-  SFM_TRY(scene_alloc_bytes(*p, &p->cam_ent, sizeof(int4) * std::max<size_t>(1, (size_t)d.M)));
+  SFM_TRY(scene_alloc_bytes(*p, &p->cam_ent, sizeof(int4) * (size_t)d.M));
   SFM_TRY(scene_alloc(*p, p->cam_pairs, (size_t)d.V));
-  DevBuf<int> cnt, fill;
-  SFM_TRY(cnt.alloc((size_t)d.V, s)); SFM_TRY(fill.alloc((size_t)d.V, s));
-  SFM_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * d.V, s));
-  SFM_HIP(hipMemsetAsync(fill.p, 0, sizeof(int) * d.V, s));
   SFM_HIP(hipMemsetAsync(p->cam_pairs, 0, sizeof(unsigned long long) * d.V, s));
-  if (d.M > 0) ba_cam_major_count_kernel<<<(unsigned)((d.M + 255) / 256), 256, 0, s>>>(d.M, d.cam_idx, d.obs_pt, d.pt_ptr, cnt.p, p->cam_pairs);
-  ba_cam_major_scan_kernel<<<1, kScanBlock, 0, s>>>(d.V, cnt.p, p->cam_ptr);
-  if (d.M > 0) ba_cam_major_fill_kernel<<<(unsigned)((d.M + 255) / 256), 256, 0, s>>>(d.M, d.cam_idx, d.obs_pt, d.pt_ptr, p->cam_ptr, fill.p,
-                                                                                       static_cast<int4*>(p->cam_ent));
+  ba_rows_entries_kernel<<<(unsigned)((d.M + 255) / 256), 256, 0, s>>>(d.M, p->cam_obs, d.cam_idx, d.obs_pt, d.pt_ptr,
+                                                                      static_cast<int4*>(p->cam_ent), p->cam_pairs);
   SFM_HIP(hipGetLastError());
-  p->h_cam_ptr.assign((size_t)d.V + 1, 0);
   p->h_cam_pairs.assign((size_t)d.V, 0);
-  SFM_HIP(hipMemcpyAsync(p->h_cam_ptr.data(), p->cam_ptr, sizeof(int) * ((size_t)d.V + 1), hipMemcpyDeviceToHost, s));
   SFM_HIP(hipMemcpyAsync(p->h_cam_pairs.data(), p->cam_pairs, sizeof(unsigned long long) * (size_t)d.V, hipMemcpyDeviceToHost, s));
-  SFM_TRY(stream_sync(s));            // cnt / fill go back to the pool; the host copies are complete
-  return SFM_OK;
+  return stream_sync(s);
 }
 
 // Work split: R cameras per group (LDS), chunks per group in proportion to the camera pairs it owns, about two
 // workgroups per CU in total (one is resident per CU).  Uploads the workgroup table.
-int ba_rows_plan(sfm_ba_problem* p) {
+static int ba_rows_plan(sfm_ba_problem* p) {
   const BaDev& d = p->dev;
   p->rows_ok = false;
-  if (d.M == 0 || d.N == 0) return SFM_OK;
-  const int tpr = ((7 * d.V + 1) / 2) * 2;
+  if (!ba_rows_fits(d.V)) return SFM_OK;    // not one camera's block row: the 18-camera tile kernel takes over
+  const int tpr = rows_pitch7(d.V);
   // Camera pitch of the LDS panel.  A lane round adds 9 x 7 columns of one panel row; with the natural pitch of 7 the nine
   // 7-wide groups of a sparse track sit at random offsets of the 32 bank pairs (worst bank pair 4.1 lanes on average at 15 %
   // visibility, ideal 2), with a pitch of 8 they fall into four classes (3.7).  Measured (profiles/r4/ab_rows_pitch.txt,
@@ -194,10 +166,9 @@ int ba_rows_plan(sfm_ba_problem* p) {
   static const int forced = [] { const char* e = getenv("SFM_ROWS_PITCH8"); return e ? (atoi(e) == 1 ? 8 : 7) : 0; }();
   const double visibility = (double)d.M / ((double)d.N * (double)d.V);
   int cp = forced ? forced : (visibility <= 0.25 ? 8 : 7);
-  if (cp == 8 && kRowsLdsBudget / ((size_t)7 * 8 * d.V * sizeof(double)) < 1) cp = 7;      // 349 ... 398 cameras: one camera still fits with pitch 7
+  if (cp == 8 && kRowsLdsBudget / ((size_t)7 * 8 * d.V * sizeof(double)) < 1) cp = 7;      // 357 ... 407 cameras: one camera still fits with pitch 7
   const int tpl = cp == 7 ? tpr : 8 * d.V;
   const int R = (int)std::min<size_t>((size_t)d.V, kRowsLdsBudget / ((size_t)7 * tpl * sizeof(double)));
-  if (R < 1) return SFM_OK;                 // more than ~2800 cameras: the 18-camera tile kernel takes over
   const int G = (d.V + R - 1) / R;
   double total = 0;
   for (int c = 0; c < d.V; ++c) total += (double)p->h_cam_pairs[c] + 4.0 * (p->h_cam_ptr[c + 1] - p->h_cam_ptr[c]);
@@ -233,6 +204,16 @@ int ba_rows_plan(sfm_ba_problem* p) {
   p->rows_R = R; p->rows_tpr = tpr; p->rows_wgs = (int)table.size(); p->rows_groups = G;
   p->rows_tpl = tpl; p->rows_cp = cp;
   p->rows_ok = true;
+  return SFM_OK;
+}
+
+// The scene's list, the entries and the work split on the product's first use (blocking once); rows_ok says whether it can run.
+int ba_rows_ensure(sfm_ba_problem* p) {
+  if (p->rows_built) return SFM_OK;
+  SFM_TRY(ba_cam_list_ensure(p));
+  SFM_TRY(ba_rows_build_entries(p));
+  SFM_TRY(ba_rows_plan(p));
+  p->rows_built = true;
   return SFM_OK;
 }
 

@@ -6,8 +6,8 @@ Sizes: 1, 63, 64, 65 are the edges of a wave, 1023 and 1024 those of the 1024-el
 a one-element tail, 2049 two carries.  The scan is integer arithmetic: every comparison is exact, against values computed
 with NumPy.  Six or seven cameras and tracks of one to four observations keep every case well under a second.
 
-The camera-major list of the row-panel Schur product (ba_cam_major_scan_kernel) scans per camera; its single-chunk path
-is covered by the "rows"-mode tests, its multi-chunk path is the shared body exercised here."""
+The scene's camera-major list (ba_cam_list_ptr_scan_kernel) scans per camera; its single-chunk path is covered by the
+"rows"-mode and refine_cameras tests, its multi-chunk path is the shared body exercised here."""
 import ctypes
 
 import numpy as np
