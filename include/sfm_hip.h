@@ -469,6 +469,55 @@ int sfm_ba_refine_cameras(sfm_ba_problem* p, double lambda, int iters, int quirk
 /* host only, needs no device: how a camera of n_obs observations is worked on (any output may be NULL) */
 int sfm_ba_refine_cameras_plan(int64_t n_obs, int* n_slices, int* slice_obs, int* size_class);
 
+/* ---- covariance of the resident scene: per-camera and per-point blocks ---------------------------------------------
+ * How well the current state is determined.  With H = J^T J + lambda I = [A B; B^T D] of one linearisation at the current
+ * state (r, Jp, Jx exactly as the iterations form them, the Q2 bit of `quirks` honoured; with use_loss = 1 and a loss on
+ * the handle scaled by sqrt(w(s_o)) as the iterations scale them), A = U + lambda I, D = V + lambda I, Y_o = W_o D_p^-1:
+ *   cam_cov[c]  = the 7x7 diagonal block of inv(S_ff), S = A - B D^-1 B^T, row-major, in the [C, q] parametrisation
+ *   pt_cov[p]   = D_p^-1 + sum over o, o' in track(p) of Y_o^T Sigma_{c(o) c(o')} Y_o'     as (xx, xy, xz, yy, yz, zz)
+ *   *sigma0_sq  = cost / (2 M - 7 V_free - 3 N_observed), cost the linearisation's sum (the robust cost with the loss);
+ *                 0 when the denominator is not positive
+ * The covariances are NOT scaled by sigma0^2.  The gauge is fixed by holding cameras: cam_mask[c] == 0 holds camera c (the
+ * convention of sfm_ba_refine_cameras), which removes its rows and columns from S -- S_ff is the Schur complement of the
+ * problem in which those cameras are constants.  A held camera's block is zero and it adds nothing to a point's sum; a
+ * point seen only by held cameras gets D_p^-1; a mask that holds every camera is valid.  With nothing held the seven
+ * gauge directions of S have the eigenvalue lambda exactly, so the result says nothing about the data.
+ *   cam_status[c]: SFM_COV_CAM_HELD; SFM_COV_CAM_PIVOT on the camera at which the factorisation of S_ff met a pivot that
+ *   is not positive (not above 1e-9 x the row's diagonal entry of S: rounding noise; a positive definite system whose
+ *   pivots fall below that, nothing held with a lambda nine orders below the diagonal of S for instance, is refused too).  Then the call returns SFM_E_SINGULAR,
+ *   cam_cov / pt_cov / pt_status / sigma0_sq are untouched and nothing non-finite is produced.  That is what holding fewer than two
+ *   cameras with lambda = 0 gives (the scale, or the whole gauge, is free).
+ *   pt_status[p]: SFM_COV_PT_EMPTY (no observation: zeros), SFM_COV_PT_SINGULAR (D_p is not positive definite, one
+ *   observation with lambda = 0 for instance: zeros, and the point's observations are left out of S altogether, U
+ *   included.  For one observation that is the limit lambda -> 0: Jx (Jx^T Jx + lambda I)^-1 Jx^T -> I_2, the observation
+ *   says nothing about its camera; for a longer track whose D_p is singular it errs on the large side).  Such a point
+ *   still counts in sigma0_sq, whose formula is the one above on the whole scene.
+ * `group` lanes share a point in the point kernel (1, 4, 8, 16, 32, 64; 0 = automatic); tracks longer than 64 take one
+ * workgroup per point.  Determinism: no floating-point atomic anywhere; two calls return the same bits, and pt_cov[p] does
+ * not depend on `group`.  The inverse is a dense FP64 Cholesky in 64 x 64 blocks (sfm_ba_covariance_plan), for every V.
+ * Completes a deferred back substitution first and prepares the cameras if they are not; an INPUT camera that fails the
+ * rotation checks returns its status and names the camera.  Works in buffers of its own: state, loss, options, cost
+ * history, captured graphs and every buffer of the iterations are untouched, so `iterate; covariance; iterate` ends in the
+ * bits of `iterate; iterate`.  Only cam_mask is uploaded.  Runs on the problem's stream; blocking.  A NaN or negative
+ * lambda, use_loss outside {0, 1}, a bad group or an attached communicator (the points are sharded: Sigma_ff would need
+ * the all-reduced S) return SFM_E_SHAPE and launch nothing.  All output arrays are HOST arrays or NULL. */
+#define SFM_E_SINGULAR     -10  /* sfm_ba_covariance: the free cameras' system is not positive definite */
+#define SFM_COV_CAM_HELD     8  /* cam_mask[c] == 0: the block is zero (= SFM_CAM_HELD) */
+#define SFM_COV_CAM_PIVOT   16  /* the first camera with a pivot that is not positive */
+#define SFM_COV_PT_EMPTY     4  /* the point has no observation (= SFM_PT_EMPTY) */
+#define SFM_COV_PT_SINGULAR  8  /* D_p is not positive definite */
+int sfm_ba_covariance(sfm_ba_problem* p, double lambda, int quirks, int use_loss,
+                      const unsigned char* cam_mask /*host [V] or NULL = every camera free*/, int group,
+                      double* cam_cov /*host [V][49] or NULL*/, double* pt_cov /*host [N][6] or NULL*/,
+                      int* cam_status /*host [V] or NULL*/, int* pt_status /*host [N] or NULL*/, double* sigma0_sq /*or NULL*/);
+/* host only, needs no device: block size of the dense inverse, its block count and kernel launches for n_cams cameras, and
+ * the longest track a lane group takes (any output may be NULL) */
+int sfm_ba_covariance_plan(int n_cams, int* block, int* n_blocks, int* n_launches, int* group_max_track);
+/* Device time (ms, hipEvents) of the four phases of the last sfm_ba_covariance on this handle -- per-point terms, S, the
+ * inverse (with its one status read-back), the point kernels -- if any SFM_OPT_TIMING bit was set during that call; zeros
+ * otherwise and for a phase that did not run.  Measurement only: the events cost stream bubbles. */
+int sfm_ba_covariance_times(sfm_ba_problem* p, double* ms /*[4]*/);
+
 /* ---- screening and culling of the resident scene's observations ----------------------------------------------------
  * Judges every observation of the resident CSR at the current state and every point by what is left of its track.  For
  * observation o of point p in camera c, with s = [R(q)^T | t]_c (X_p, 1) of the prepared cameras the linearisation reads

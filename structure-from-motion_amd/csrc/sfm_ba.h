@@ -281,6 +281,7 @@ struct sfm_ba_problem : sfm::BaScene {
   int graph_quirks = 0;
   long long graph_replays = 0;    // SFM_INFO_GRAPH_REPLAYS
   sfm::KernelTimer timers[SFM_K_COUNT];
+  float cov_ms[4] = {0, 0, 0, 0};   // phases of the last sfm_ba_covariance under SFM_OPT_TIMING (sfm_ba_covariance_times)
 };
 
 namespace sfm {

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("SFM_HIP_LIBRARY") or os.path.join(_HERE, "libsfm_hip.
 
 OK = 0
 E_SHAPE, E_BAD_ROTATION, E_QW_ZERO, E_SQRT_DOMAIN, E_HIP, E_NO_DEVICE, E_HANDLE, E_RANK, E_RCCL = -1, -2, -3, -4, -5, -6, -7, -8, -9
+E_SINGULAR = -10
 Q1_PNP_ROW_OVERLAP, Q2_LOC_JAC_SIGN, QUIRKS_REFERENCE = 1, 2, 3
 SCHUR_AUTO, SCHUR_PAIRS, SCHUR_MFMA, SCHUR_ROWS = 0, 1, 2, 3
 OPT_SCHUR, OPT_TIMING, OPT_DEBUG, OPT_DETERMINISTIC, OPT_GRAPH, OPT_TIMING_STRIDE = 1, 2, 3, 4, 5, 6
@@ -41,6 +42,7 @@ OBS_HIGH_ERROR, OBS_BEHIND, OBS_NONFINITE, OBS_POINT = 1, 2, 4, 8
 PT_TOO_FEW, PT_LOW_ANGLE, PT_EMPTY = 1, 2, 4
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2
 CAM_EMPTY, CAM_NONFINITE, CAM_BEHIND, CAM_HELD = 1, 2, 4, 8
+COV_CAM_HELD, COV_CAM_PIVOT, COV_PT_EMPTY, COV_PT_SINGULAR = 8, 16, 4, 8
 LOSS_NAMES = {"none": LOSS_NONE, "huber": LOSS_HUBER, "cauchy": LOSS_CAUCHY}
 SCREEN_SUMMARY = ("obs_before", "obs_kept", "high_error", "behind", "nonfinite", "obs_dropped_with_point", "pts_too_few",
                   "pts_low_angle")
@@ -183,6 +185,9 @@ SIGNATURES = {
     "sfm_ba_reduced_system_loss": [ci, ci, i64, _ip, _ip, _dp, _dp, _dp, cd, ci, ci, ci, cd, _dp, _dp],
     "sfm_ba_refine_cameras": [vp, cd, ci, ci, ci, ctypes.POINTER(ctypes.c_uint8), _dp, _ip],
     "sfm_ba_refine_cameras_plan": [i64, _ip, _ip, _ip],
+    "sfm_ba_covariance": [vp, cd, ci, ci, ctypes.POINTER(ctypes.c_uint8), ci, _dp, _dp, _ip, _ip, _dp],
+    "sfm_ba_covariance_plan": [ci, _ip, _ip, _ip, _ip],
+    "sfm_ba_covariance_times": [vp, _dp],
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -728,6 +733,20 @@ def refine_cameras_plan(n_obs):
     return int(a.value), int(b.value), int(c.value)
 
 
+def covariance_plan(n_cams):
+    """How ``BaProblem.covariance`` inverts the camera system of ``n_cams`` cameras (sfm_ba_covariance_plan; host only):
+    ``(block size, blocks per side, kernel launches of the inverse, longest track a lane group takes)``."""
+    a, b, c, d = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(load().sfm_ba_covariance_plan(int(n_cams), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+    return a.value, b.value, c.value, d.value
+
+
+def sym3(packed):
+    """(N, 6) packed (xx, xy, xz, yy, yz, zz) -> (N, 3, 3) symmetric blocks."""
+    packed = np.asarray(packed)
+    return packed[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
+
+
 class BaProblem:
     """Device-resident BA problem (sfm_ba_create ... sfm_ba_destroy)."""
 
@@ -934,6 +953,46 @@ class BaProblem:
                                               mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if mask is not None else None,
                                               dptr(cost) if want_cost else None, iptr(status) if want_status else None))
         return cost, status
+
+    def covariance(self, lam, quirks=QUIRKS_REFERENCE, use_loss=False, mask=None, group=0, want_cameras=True, want_points=True):
+        """Covariance blocks of the resident scene at its current state (sfm_ba_covariance), the cameras with a zero
+        ``mask`` entry held (None: every camera free, which needs ``lam > 0`` and says little: hold at least two).
+        Returns a namespace: ``cam_cov`` (V, 7, 7) or None, ``pt_cov`` (N, 6) packed (xx, xy, xz, yy, yz, zz) or None
+        (``sym3`` expands it), ``cam_status`` (V,) of ``COV_CAM_*`` bits, ``pt_status`` (N,) of ``COV_PT_*`` bits,
+        ``sigma0_sq``, and ``pivot_camera``: None, or the camera at which the free cameras' system turned out not to be
+        positive definite -- then the covariances are None and ``sigma0_sq`` is NaN.  Nothing is scaled by ``sigma0_sq``."""
+        from types import SimpleNamespace
+        v, n = self.info(INFO_N_CAMS), self.info(INFO_N_PTS)
+        if group not in TRACK_GROUPS:
+            raise ValueError("group must be one of %s, got %r" % (TRACK_GROUPS, group))
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).ravel()
+            if mask.shape[0] != v:
+                raise ValueError("mask must have one entry per camera (%d), got %d" % (v, mask.shape[0]))
+        out = SimpleNamespace(cam_cov=np.zeros((v, 7, 7)) if want_cameras else None,
+                              pt_cov=np.zeros((n, 6)) if want_points else None,
+                              cam_status=np.zeros(v, dtype=np.int32), pt_status=np.zeros(n, dtype=np.int32),
+                              sigma0_sq=float("nan"), pivot_camera=None)
+        s0 = ctypes.c_double(float("nan"))
+        st = self._lib.sfm_ba_covariance(self._h, float(lam), int(quirks), int(bool(use_loss)),
+                                         mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if mask is not None else None,
+                                         int(group), dptr(out.cam_cov) if want_cameras else None,
+                                         dptr(out.pt_cov) if want_points else None, iptr(out.cam_status), iptr(out.pt_status),
+                                         ctypes.byref(s0))
+        if st == E_SINGULAR:
+            out.pivot_camera = int(np.flatnonzero(out.cam_status & COV_CAM_PIVOT)[0])
+            out.cam_cov = out.pt_cov = None
+            return out
+        check(st)
+        out.sigma0_sq = s0.value
+        return out
+
+    def covariance_times(self):
+        """Device milliseconds of the last ``covariance`` call's phases (terms, S, inverse, points) when an ``OPT_TIMING``
+        bit was set during it (sfm_ba_covariance_times); zeros otherwise."""
+        ms = np.zeros(4)
+        check(self._lib.sfm_ba_covariance_times(self._h, dptr(ms)))
+        return ms
 
     def _screen(self, name, max_err2, cos_min_angle, min_obs, cam_scale, want_outputs, group):
         from types import SimpleNamespace

@@ -763,6 +763,39 @@ class HipBaMixin:
             scene.culled_cam = np.concatenate((scene.culled_cam, cam_idx[gone].astype(np.int64)))
         return self._ba_screen_report(report)
 
+    def structure_uncertainty(self, hold=(0, 1), scaled=True, use_loss=True, damping_factor=0.0):
+        """How well the resident scene is determined (``BaProblem.covariance``), after it has been brought up to date exactly
+        as ``screen_structure`` does.  ``hold``: the views whose poses fix the gauge -- by default the first two registered
+        views, the pair whose relative pose the two-view initialisation fixes; with fewer than two held and no damping the
+        system is singular and a ``ValueError`` names the view at which that showed.  Returns a namespace with
+        ``cam_sigma`` (V,): standard deviation of a view's centre, sqrt(trace of the centre's 3x3), 0 for a held view;
+        ``pt_sigma`` (N,): sqrt(trace Sigma_pp), 0 for a point without observations; both in world units, multiplied by
+        ``sigma0`` when ``scaled`` (normalised image units otherwise cancel only for a unit-variance residual);
+        ``sigma0`` (normalised image units), and the native report as ``cov``.  ``use_loss``: weight by ``ba_loss`` when one
+        is set.  Nothing on the device, in ``tri_pts`` or in the views changes.  Needs ``ba_resident``."""
+        if self.ba_device_tracks:
+            self._ba_check_device_tracks()
+        from types import SimpleNamespace
+        views = self.view_processor.view_list
+        idx = np.asarray(list(hold), dtype=np.int64).ravel()
+        if idx.size and (idx.min() < 0 or idx.max() >= len(views)):
+            raise ValueError("structure_uncertainty: held view outside the {} views".format(len(views)))
+        scene, _e, _c, _s = self._ba_screen_scene("structure_uncertainty", None, None, 0)
+        mask = np.ones(len(views), dtype=np.uint8)
+        mask[idx] = 0
+        try:
+            cov = scene.prob.covariance(float(damping_factor), self.ba_quirk_flags, bool(use_loss), mask)
+        except Exception:
+            self.ba_release()
+            raise
+        if cov.pivot_camera is not None:
+            raise ValueError("structure_uncertainty: the system is singular at view {} (hold at least two views)".format(cov.pivot_camera))
+        sigma0 = math.sqrt(max(cov.sigma0_sq, 0.0))
+        scale = sigma0 if scaled else 1.0
+        cam_var = np.maximum(cov.cam_cov[:, 0, 0] + cov.cam_cov[:, 1, 1] + cov.cam_cov[:, 2, 2], 0.0)
+        pt_var = np.maximum(cov.pt_cov[:, 0] + cov.pt_cov[:, 3] + cov.pt_cov[:, 5], 0.0)
+        return SimpleNamespace(cam_sigma=scale * np.sqrt(cam_var), pt_sigma=scale * np.sqrt(pt_var), sigma0=sigma0, cov=cov)
+
     def execute_bundle_adjustment(self):
         if self.ba_device_tracks:
             self._ba_check_device_tracks()
