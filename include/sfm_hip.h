@@ -100,6 +100,8 @@ extern "C" {
 #define SFM_INFO_GRAPH_REPLAYS 7  /* iterations sfm_ba_iterate carried out as hipGraph replays (SFM_OPT_GRAPH) */
 #define SFM_INFO_REDUCE_IN_SOLVE 8 /* 1 if the last iteration sfm_ba_iterate enqueued left the split-K reduce of the dense product to the
                                    * data-flow solve's launch (no ba_schur_reduce launch: one GPU, 37 to 237 cameras, not deterministic), else 0 */
+#define SFM_INFO_PCG_HELD_POINTS 9 /* points whose D_p was not positive definite or not finite in the last outer iteration of
+                                   * sfm_ba_iterate_pcg: they were held for that iteration (arises only at lambda = 0) */
 
 /* ---- kernel ids for sfm_ba_kernel_time ------------------------------------------------------- */
 #define SFM_K_PREP       0
@@ -501,7 +503,7 @@ int sfm_ba_refine_cameras_plan(int64_t n_obs, int* n_slices, int* slice_obs, int
  * bits of `iterate; iterate`.  Only cam_mask is uploaded.  Runs on the problem's stream; blocking.  A NaN or negative
  * lambda, use_loss outside {0, 1}, a bad group or an attached communicator (the points are sharded: Sigma_ff would need
  * the all-reduced S) return SFM_E_SHAPE and launch nothing.  All output arrays are HOST arrays or NULL. */
-#define SFM_E_SINGULAR     -10  /* sfm_ba_covariance: the free cameras' system is not positive definite */
+#define SFM_E_SINGULAR     -10  /* sfm_ba_covariance: the free cameras' system is not positive definite; sfm_ba_iterate_pcg: a diagonal block is not */
 #define SFM_COV_CAM_HELD     8  /* cam_mask[c] == 0: the block is zero (= SFM_CAM_HELD) */
 #define SFM_COV_CAM_PIVOT   16  /* the first camera with a pivot that is not positive */
 #define SFM_COV_PT_EMPTY     4  /* the point has no observation (= SFM_PT_EMPTY) */
@@ -517,6 +519,42 @@ int sfm_ba_covariance_plan(int n_cams, int* block, int* n_blocks, int* n_launche
  * inverse (with its one status read-back), the point kernels -- if any SFM_OPT_TIMING bit was set during that call; zeros
  * otherwise and for a phase that did not run.  Measurement only: the events cost stream bubbles. */
 int sfm_ba_covariance_times(sfm_ba_problem* p, double* ms /*[4]*/);
+
+/* ---- matrix-free bundle adjustment of the resident scene: PCG on the reduced camera system, cameras can be held -----
+ * `iters` outer iterations, each one iteration of sfm_ba_iterate with the solve replaced: S dp = rhs is solved by
+ * conjugate gradients preconditioned with the diagonal 7x7 blocks of S (block Jacobi), and S is never formed -- q = S p is
+ * two passes over the observations (by point, then by camera through the camera-major list).  r, Jp, Jx of every
+ * observation are those of the iterations (the handle's loss applies, the Q2 bit of `quirks` is honoured).
+ *   cam_mask[c] == 0 holds camera c (the convention of sfm_ba_refine_cameras): it has no unknowns, its seven doubles are
+ *   never written; NULL = every camera free.  A mask that holds every camera is valid (the points still move).
+ *   CG starts from x = 0 and stops when r^T M^-1 r <= cg_tol^2 r0^T M^-1 r0, or after cg_max_iters iterations
+ *   (0: min(7 V_free, 1000)); the step found so far is then applied (SFM_PCG_MAX_ITERS).  p^T S p <= 0 or a non-finite
+ *   scalar is SFM_PCG_BREAKDOWN: nothing of that outer iteration is applied and the loop stops.
+ *   A point whose D_p is not positive definite or not finite is held for that iteration (SFM_INFO_PCG_HELD_POINTS); a point
+ *   with no observation is untouched.  A free camera whose diagonal block does not factor (a pivot not above 1e-9 of its
+ *   diagonal entry, as in sfm_ba_covariance; an empty free camera at lambda = 0 is the case) ends the call with
+ *   SFM_E_SINGULAR: *bad_camera names it (the lowest such camera), and state and outputs are as they were before the call.
+ *   Per outer iteration i < *iters_done: cost[i] the minimised cost at its linearisation, cg_iters[i], cg_rel[i] =
+ *   sqrt(r^T M^-1 r / r0^T M^-1 r0) at exit, cg_status[i].  All outputs are HOST arrays or NULL.
+ * `group` lanes share a point in the point kernels (1, 4, 8, 16, 32, 64; 0 = automatic, from the mean track length); lanes
+ * stride over longer tracks.  Determinism: no floating-point atomic; the bits depend on the scene, the arguments and
+ * `group` only.  The updated cameras are normalised and checked as the iterations check them (same error codes).
+ * Completes a deferred back substitution first and prepares the cameras if they are not.  Works in buffers of its own:
+ * nothing an iteration owns is touched.  Afterwards the state is treated as by sfm_ba_set_state without the upload: the
+ * cost history restarts, the prepared cameras are rebuilt before the next linearisation.  Only the mask is uploaded.  Runs
+ * on the problem's stream; blocking.  iters < 0, cg_tol outside (0, 1), cg_max_iters < 0, a bad group, a negative or
+ * non-finite lambda or an attached communicator return SFM_E_SHAPE and launch nothing; iters = 0 does nothing. */
+#define SFM_PCG_CONVERGED  0
+#define SFM_PCG_MAX_ITERS  1   /* cg_max_iters reached; the step found so far was applied */
+#define SFM_PCG_BREAKDOWN  2   /* p^T S p <= 0 or a non-finite scalar: nothing of this outer iteration was applied, the loop stopped */
+int sfm_ba_iterate_pcg(sfm_ba_problem* p, double lambda, int iters, int quirks,
+                       const unsigned char* cam_mask /*host [V] or NULL*/, double cg_tol, int cg_max_iters, int group,
+                       int* iters_done, double* cost /*host [iters] or NULL*/, int* cg_iters /*host [iters] or NULL*/,
+                       double* cg_rel /*host [iters] or NULL*/, int* cg_status /*host [iters] or NULL*/, int* bad_camera /*or NULL*/);
+/* Milliseconds of the last sfm_ba_iterate_pcg on this handle, summed over its outer iterations: linearisation, camera
+ * blocks, CG loop (with its flag reads), back substitution and camera update -- device time by hipEvents, zeros unless an
+ * SFM_OPT_TIMING bit was set during the call -- and [4] the whole call by the host's clock (always). */
+int sfm_ba_pcg_times(sfm_ba_problem* p, double* ms /*[5]*/);
 
 /* ---- screening and culling of the resident scene's observations ----------------------------------------------------
  * Judges every observation of the resident CSR at the current state and every point by what is left of its track.  For

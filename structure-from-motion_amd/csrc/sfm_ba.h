@@ -282,6 +282,8 @@ struct sfm_ba_problem : sfm::BaScene {
   long long graph_replays = 0;    // SFM_INFO_GRAPH_REPLAYS
   sfm::KernelTimer timers[SFM_K_COUNT];
   float cov_ms[4] = {0, 0, 0, 0};   // phases of the last sfm_ba_covariance under SFM_OPT_TIMING (sfm_ba_covariance_times)
+  float pcg_ms[5] = {0, 0, 0, 0, 0};   // parts of the last sfm_ba_iterate_pcg (sfm_ba_pcg_times); [4], the whole call, is host time
+  int pcg_held_points = 0;          // points the last outer iteration of sfm_ba_iterate_pcg held (SFM_INFO_PCG_HELD_POINTS)
 };
 
 namespace sfm {

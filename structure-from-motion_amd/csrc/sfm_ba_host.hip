@@ -544,6 +544,7 @@ int sfm_ba_info(sfm_ba_problem* p, int what, int64_t* value) {
     case SFM_INFO_MAX_TRACK: *value = p->max_track; return SFM_OK;
     case SFM_INFO_GRAPH_REPLAYS: *value = p->graph_replays; return SFM_OK;
     case SFM_INFO_REDUCE_IN_SOLVE: *value = p->last_reduce_deferred ? 1 : 0; return SFM_OK;
+    case SFM_INFO_PCG_HELD_POINTS: *value = p->pcg_held_points; return SFM_OK;
     default: set_error("sfm_ba_info: unknown item %d", what); return SFM_E_SHAPE;
   }
 }

@@ -25,6 +25,8 @@ K_PREP, K_LINEARIZE, K_SCHUR, K_SOLVE, K_BACKSUB, K_REDUCE, K_COUNT = 0, 1, 2, 3
 KERNEL_NAMES = ("prep", "linearize", "schur", "solve", "backsub", "reduce")
 INFO_SCHUR_KERNEL, INFO_UPLOAD_BYTES, INFO_N_CAMS, INFO_N_PTS, INFO_N_OBS, INFO_MAX_TRACK, INFO_GRAPH_REPLAYS = 1, 2, 3, 4, 5, 6, 7
 INFO_REDUCE_IN_SOLVE = 8
+INFO_PCG_HELD_POINTS = 9
+PCG_CONVERGED, PCG_MAX_ITERS, PCG_BREAKDOWN = 0, 1, 2
 MATCH_L2, MATCH_HAMMING = 0, 1
 MATCH_KNN2, MATCH_NN1, MATCH_MUTUAL = 0, 1, 2
 DESC_U8, DESC_F32 = 0, 1
@@ -188,12 +190,22 @@ SIGNATURES = {
     "sfm_ba_covariance": [vp, cd, ci, ci, ctypes.POINTER(ctypes.c_uint8), ci, _dp, _dp, _ip, _ip, _dp],
     "sfm_ba_covariance_plan": [ci, _ip, _ip, _ip, _ip],
     "sfm_ba_covariance_times": [vp, _dp],
+    "sfm_ba_iterate_pcg": [vp, cd, ci, ci, ctypes.POINTER(ctypes.c_uint8), cd, ci, ci, _ip, _dp, _ip, _dp, _ip, _ip],
+    "sfm_ba_pcg_times": [vp, _dp],
 }
 EXPORTS = tuple(SIGNATURES)
 
 
 class SfmHipError(RuntimeError):
     """HIP / device / handle failures (no reference counterpart)."""
+
+
+class SfmSingularError(SfmHipError):
+    """SFM_E_SINGULAR: a system that has to be positive definite is not; ``camera`` names where it was found."""
+
+    def __init__(self, message, camera=None):
+        super().__init__(message)
+        self.camera = camera
 
 
 def load():
@@ -470,6 +482,27 @@ def check_loss(kind, delta):
     if not (np.isfinite(delta) and delta > 0.0):
         raise ValueError("loss delta must be finite and > 0, got %r" % delta)
     return kind, delta
+
+
+def check_pcg(n_cams, lam, iters, mask=None, tol=1e-10, max_cg=0, group=0):
+    """Arguments of a ``BaProblem.iterate_pcg`` call, without a device: returns ``(lam, iters, mask, tol, max_cg, group)``
+    converted (``mask`` as uint8 (n_cams,) or None) or raises ValueError -- the rules of sfm_ba_iterate_pcg."""
+    lam, tol = float(lam), float(tol)
+    if not (np.isfinite(lam) and lam >= 0.0):
+        raise ValueError("lam must be finite and >= 0, got %r" % lam)
+    if isinstance(iters, bool) or int(iters) != iters or iters < 0:
+        raise ValueError("iters must be an integer >= 0, got %r" % (iters,))
+    if not (0.0 < tol < 1.0):
+        raise ValueError("tol must lie in (0, 1), got %r" % tol)
+    if isinstance(max_cg, bool) or int(max_cg) != max_cg or max_cg < 0:
+        raise ValueError("max_cg must be an integer >= 0 (0: min(7 V_free, 1000)), got %r" % (max_cg,))
+    if isinstance(group, bool) or group not in TRACK_GROUPS:
+        raise ValueError("group must be one of %s, got %r" % (TRACK_GROUPS, group))
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).ravel()
+        if mask.shape[0] != int(n_cams):
+            raise ValueError("mask must have one entry per camera (%d), got %d" % (n_cams, mask.shape[0]))
+    return lam, int(iters), mask, tol, int(max_cg), int(group)
 
 
 def tri_tracks(pt_ptr, cam_idx, uv, projs, X_init=None, mode=TRACKS_NONLINEAR, lam=0.5, iters=100, group=0):
@@ -992,6 +1025,38 @@ class BaProblem:
         bit was set during it (sfm_ba_covariance_times); zeros otherwise."""
         ms = np.zeros(4)
         check(self._lib.sfm_ba_covariance_times(self._h, dptr(ms)))
+        return ms
+
+    def iterate_pcg(self, lam, iters, quirks=QUIRKS_REFERENCE, mask=None, tol=1e-10, max_cg=0, group=0):
+        """``iters`` bundle-adjustment iterations with the reduced camera system solved matrix-free by block-Jacobi PCG
+        (sfm_ba_iterate_pcg); cameras with a zero ``mask`` entry are held (None: every camera moves).  ``tol`` is the
+        relative tolerance on the preconditioned residual, ``max_cg`` the CG iteration limit (0: min(7 V_free, 1000)).
+        Returns a namespace: ``iters_done``, and per outer iteration ``cost``, ``cg_iters``, ``cg_rel``, ``cg_status``
+        (``PCG_CONVERGED`` / ``PCG_MAX_ITERS`` / ``PCG_BREAKDOWN``).  Raises ``SfmSingularError`` (``.camera``) when a free
+        camera's diagonal block does not factor; the state is then as it was."""
+        from types import SimpleNamespace
+        lam, iters, mask, tol, max_cg, group = check_pcg(self.info(INFO_N_CAMS), lam, iters, mask, tol, max_cg, group)
+        n = max(iters, 1)
+        cost, rel = np.zeros(n), np.zeros(n)
+        cg, status = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        done, bad = ctypes.c_int(0), ctypes.c_int(-1)
+        st = self._lib.sfm_ba_iterate_pcg(self._h, lam, iters, int(quirks),
+                                          mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if mask is not None else None,
+                                          tol, max_cg, group, ctypes.byref(done), dptr(cost), iptr(cg), dptr(rel), iptr(status),
+                                          ctypes.byref(bad))
+        if st == E_SINGULAR:
+            raise SfmSingularError(last_error(), int(bad.value))
+        check(st)
+        k = int(done.value)
+        return SimpleNamespace(iters_done=k, cost=cost[:k].copy(), cg_iters=cg[:k].copy(), cg_rel=rel[:k].copy(),
+                               cg_status=status[:k].copy())
+
+    def pcg_times(self):
+        """Milliseconds of the last ``iterate_pcg`` call, summed over its outer iterations: (linearise, camera blocks, CG
+        loop, back substitution, whole call).  The first four are device times and zeros unless an ``OPT_TIMING`` bit was
+        set during the call; the last is the host's clock (sfm_ba_pcg_times)."""
+        ms = np.zeros(5)
+        check(self._lib.sfm_ba_pcg_times(self._h, dptr(ms)))
         return ms
 
     def _screen(self, name, max_err2, cos_min_angle, min_obs, cam_scale, want_outputs, group):

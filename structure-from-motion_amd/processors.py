@@ -419,6 +419,11 @@ class HipBaMixin:
     ba_last_action = None      # "create" | "append" | "reuse" | "solve": what the last call did (diagnostics / tests)
     ba_device_tracks = False   # build the observation list from a HipDeviceKeyTracker's device tables (class docstring)
     ba_loss = None             # None | ("huber", px) | ("cauchy", px): robust loss of the resident adjustment (ba_loss_native)
+    ba_solver = "dense"        # "dense": sfm_ba_iterate, S formed and factored | "pcg": sfm_ba_iterate_pcg, matrix-free (ba_pcg_native)
+    ba_hold_views = None       # view indices held by the "pcg" solver (their rot / loc are left alone), None: every view moves
+    ba_pcg_tol = 1e-10         # relative tolerance of the preconditioned residual
+    ba_pcg_max_iters = 0       # CG iteration limit, 0: min(7 free views, 1000)
+    ba_pcg_last = None         # the result object of the last iterate_pcg call (iters_done, cost, cg_iters, cg_rel, cg_status)
 
     def ba_loss_native(self):
         """``ba_loss`` as the native ``(kind, delta)`` or None, without touching the device.  The pixel scale becomes
@@ -445,6 +450,29 @@ class HipBaMixin:
             raise ValueError("ba_loss needs one focal scale for all views (one delta per problem), got {} .. {}".format(
                 scales.min(), scales.max()))
         return native.check_loss(kind, px / scales[0])
+
+    def ba_pcg_native(self, view_num=None):
+        """``ba_solver`` and ``ba_hold_views`` checked without touching the device or the views: None for the dense solver,
+        else a one-element tuple with the mask (uint8 (view_num,), 1 = free; None when nothing is held or ``view_num`` is
+        None).  ``ba_hold_views`` with the dense solver (``sfm_ba_iterate`` cannot hold a camera) and ``"pcg"`` without
+        ``ba_resident`` raise ``TypeError``; a bad tolerance, limit or view index raises ``ValueError``."""
+        if self.ba_solver not in ("dense", "pcg"):
+            raise ValueError("ba_solver must be \"dense\" or \"pcg\", got {!r}".format(self.ba_solver))
+        if self.ba_solver == "dense":
+            if self.ba_hold_views is not None:
+                raise TypeError("ba_hold_views needs ba_solver = \"pcg\" (the dense solver cannot hold a view)")
+            return None
+        if not self.ba_resident:
+            raise TypeError("ba_solver = \"pcg\" needs ba_resident")
+        native.check_pcg(0, self.damping_factor, self.iteration, None, self.ba_pcg_tol, self.ba_pcg_max_iters)
+        if self.ba_hold_views is None or view_num is None:
+            return (None,)
+        idx = np.asarray(list(self.ba_hold_views), dtype=np.int64).ravel()
+        if idx.size and (idx.min() < 0 or idx.max() >= view_num):
+            raise ValueError("ba_hold_views: view index outside the {} views".format(view_num))
+        mask = np.ones(view_num, dtype=np.uint8)
+        mask[idx] = 0
+        return (mask,)
 
     def _ba_apply_loss(self, scene, loss):
         """Make the resident problem's loss what ``ba_loss`` asks for (``loss`` = ``ba_loss_native()``): one ``set_loss`` when
@@ -800,7 +828,10 @@ class HipBaMixin:
         if self.ba_device_tracks:
             self._ba_check_device_tracks()
         self.ba_loss_native()                         # a bad ba_loss (or one without ba_resident) stops here, before anything is read
+        self.ba_pcg_native()                          # ... as does ba_hold_views with the dense solver, or "pcg" without ba_resident
         views = self.view_processor.view_list
+        pcg = self.ba_pcg_native(len(views))
+        held = np.zeros(len(views), dtype=bool) if pcg is None or pcg[0] is None else pcg[0] == 0
         tri_pts = self.tri_processor.tri_pts
         view_num = len(views)
         tri_num = tri_pts.shape[1]
@@ -813,7 +844,11 @@ class HipBaMixin:
             prob = scene.prob
             try:
                 scene.cams_synced = False
-                prob.iterate(self.damping_factor, self.iteration, self.ba_quirk_flags)
+                if pcg is None:
+                    prob.iterate(self.damping_factor, self.iteration, self.ba_quirk_flags)
+                else:
+                    self.ba_pcg_last = prob.iterate_pcg(self.damping_factor, self.iteration, self.ba_quirk_flags, pcg[0],
+                                                        self.ba_pcg_tol, self.ba_pcg_max_iters)
                 cams, pts, rots = prob.get_state_rot()                                             # ba:412 (validated on the device)
             except Exception:
                 # the device state has advanced (or is invalid: a bad rotation) while tri_pts / the views keep the old
@@ -823,6 +858,11 @@ class HipBaMixin:
                 raise
             scene.pts_written = pts
             scene.rots_written, scene.locs_written = rots, cams[:, 0:3].copy()
+            if held.any():
+                # a held view keeps its rot / loc; the device holds the quaternion packed from them, not q(R(q)) of a
+                # written pose, so the next call packs and uploads the cameras again instead of re-deriving them
+                scene.rots_written = rots.copy()
+                scene.rots_written[held] = np.nan
         else:
             init_cam_poses = pack_cameras(init_rots, init_locs)
             rows = [self.key_tracker.track_list[v].table[v, :] for v in range(view_num)]
@@ -834,7 +874,8 @@ class HipBaMixin:
             self.ba_last_action = "solve"
 
         for view_idx in range(view_num):                                                       # ba:409-413
-            views[view_idx].update_cam_pose(rots[view_idx].copy(), cams[view_idx, 0:3].reshape(3, 1).copy())
+            if not held[view_idx]:
+                views[view_idx].update_cam_pose(rots[view_idx].copy(), cams[view_idx, 0:3].reshape(3, 1).copy())
         tri_pts[0:3, :] = pts                                                                  # ba:415-416
 
         if self.ba_verbose:                                                                    # ba:418-439
