@@ -198,6 +198,30 @@ struct KernelTimer {
   bool open = false;     // the current bracket is a sampled one
 };
 
+// hipEvents between the phases of one call (SFM_OPT_TIMING, any bit): mark() records the next one, phase i runs from
+// mark i to mark i + 1.  Not timed: no event is ever created.
+struct PhaseEvents {
+  explicit PhaseEvents(bool timed_) : timed(timed_) {}
+  PhaseEvents(const PhaseEvents&) = delete;
+  ~PhaseEvents() { for (hipEvent_t x : ev) (void)hipEventDestroy(x); }
+  int mark(hipStream_t s) {
+    if (!timed) return SFM_OK;
+    hipEvent_t x;
+    SFM_HIP(hipEventCreate(&x));
+    ev.push_back(x);
+    SFM_HIP(hipEventRecord(x, s));
+    return SFM_OK;
+  }
+  int marks() const { return (int)ev.size(); }
+  float elapsed_ms(int i) const {      // 0 when either mark is missing or the runtime refuses
+    float t = 0.f;
+    if (i < 0 || i + 1 >= marks() || hipEventElapsedTime(&t, ev[i], ev[i + 1]) != hipSuccess) return 0.f;
+    return t;
+  }
+  const bool timed;
+  std::vector<hipEvent_t> ev;
+};
+
 constexpr unsigned kBaMagic = 0x5F3BA001u;
 
 // Everything of a problem that is sized or planned by (V, N, M).  A growth (sfm_ba_append, sfm_ba_sync_tracks) builds a
@@ -300,6 +324,17 @@ int ba_screen_run(sfm_ba_problem* p, const char* who, double max_err2, double co
                   const double* cam_scale, double* err2, double* depth, unsigned char* obs_flags, double* min_cos,
                   int* pt_flags, int64_t* summary, ScreenWork& w);
 int ba_cull_enqueue_scatter(const BaDev& d, const BaDev& e, const ScreenWork& w, hipStream_t s);
+// What an operation on the resident scene is given (sfm_ba_host.hip; DESIGN.md, "What an operation on the resident scene
+// is given").  `who` names the entry point in the message.
+int ba_check_handle(const sfm_ba_problem* p);
+int ba_refuse_comm(const sfm_ba_problem* p, const char* who, const char* why);      // "<who>: not with a communicator attached (<why>)"
+// download d.status behind whatever the caller has enqueued, wait for the stream, and fail with
+// "<who>: camera %d is invalid<when> (status %d)" on a camera that did not pass its checks
+int ba_sync_cam_status(sfm_ba_problem* p, const char* who, const char* when);
+int ba_prepared_cameras(sfm_ba_problem* p, const char* who);   // the expanded cameras the linearisation reads, checked (blocks)
+int ba_reset_stats(sfm_ba_problem* p);      // a new state starts a new cost history (sfm_ba_get_stats)
+int ba_state_changed(sfm_ba_problem* p);    // ... and new cameras need a new expansion, as after sfm_ba_set_cameras
+void ba_free_cameras(const unsigned char* cam_mask, int V, int* v_free, int* first_free);      // null mask: all free; none: -1
 int ba_schur_plan(BaScene& sc);      // plans of both Schur products, their workspace and block offsets
 int ba_cam_list_ensure(sfm_ba_problem* p);      // sfm_ba_host.hip: the scene's camera-major list, built once (M > 0)
 int ba_rows_ensure(sfm_ba_problem* p);          // ... and on it the row-panel product's entries and work split (sets rows_ok)

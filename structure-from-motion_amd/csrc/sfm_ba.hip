@@ -394,48 +394,33 @@ static int pick_group(const sfm_ba_problem* p) {
   return g;
 }
 
-// `cur` = prep slot of the cameras to linearise at (FUSED: the back substitution uses the other slot)
-template <int LDS, bool WZ, bool FUSED, int LOSS>
-static void launch_linearize_loss(const sfm_ba_problem* p, int cur, int g, int grid, size_t lds, hipStream_t s, double lambda, int quirks) {
-  const BaDev& d = p->dev;
-  const LossArg<LOSS> la = loss_arg<LOSS>(p);
-  if (p->deterministic) {      // one wave per workgroup (ordered LDS accumulation)
-    dispatch_group<4>(g, [&](auto G) {
-      ba_linearize_kernel<decltype(G)::value, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la);
-    });
-    return;
-  }
-  dispatch_group<4>(g, [&](auto G) {
-    ba_linearize_kernel<decltype(G)::value, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la);
-  });
-}
-
-// the problem's loss picks the instantiation; without one it is the plain kernel
+// `cur` = prep slot of the cameras to linearise at (FUSED: the back substitution uses the other slot).  The problem's loss
+// picks the instantiation; without one it is the plain kernel.
 template <int LDS, bool WZ, bool FUSED = false>
 static void launch_linearize(const sfm_ba_problem* p, int cur, int g, int grid, size_t lds, hipStream_t s, double lambda, int quirks) {
-  switch (p->loss_kind) {
-    case SFM_LOSS_HUBER: launch_linearize_loss<LDS, WZ, FUSED, SFM_LOSS_HUBER>(p, cur, g, grid, lds, s, lambda, quirks); break;
-    case SFM_LOSS_CAUCHY: launch_linearize_loss<LDS, WZ, FUSED, SFM_LOSS_CAUCHY>(p, cur, g, grid, lds, s, lambda, quirks); break;
-    default: launch_linearize_loss<LDS, WZ, FUSED, SFM_LOSS_NONE>(p, cur, g, grid, lds, s, lambda, quirks); break;
-  }
-}
-
-template <bool LDS, int LOSS>
-static void launch_backsub_loss(const sfm_ba_problem* p, int g, int grid, size_t lds, hipStream_t s, double lambda, int quirks) {
   const BaDev& d = p->dev;
-  const LossArg<LOSS> la = loss_arg<LOSS>(p);
-  dispatch_group<4>(g, [&](auto G) {
-    ba_backsub_kernel<decltype(G)::value, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la);
+  dispatch_loss(p->loss_kind, [&](auto L) {
+    constexpr int LOSS = decltype(L)::value;
+    const LossArg<LOSS> la = loss_arg<LOSS>(p);
+    dispatch_group<4>(g, [&](auto G) {
+      if (p->deterministic)      // one wave per workgroup (ordered LDS accumulation)
+        ba_linearize_kernel<decltype(G)::value, LDS, WZ, FUSED, 64, LOSS><<<grid, 64, lds, s>>>(d, cur, lambda, quirks, la);
+      else
+        ba_linearize_kernel<decltype(G)::value, LDS, WZ, FUSED, 256, LOSS><<<grid, 256, lds, s>>>(d, cur, lambda, quirks, la);
+    });
   });
 }
 
 template <bool LDS>
 static void launch_backsub(const sfm_ba_problem* p, int g, int grid, size_t lds, hipStream_t s, double lambda, int quirks) {
-  switch (p->loss_kind) {
-    case SFM_LOSS_HUBER: launch_backsub_loss<LDS, SFM_LOSS_HUBER>(p, g, grid, lds, s, lambda, quirks); break;
-    case SFM_LOSS_CAUCHY: launch_backsub_loss<LDS, SFM_LOSS_CAUCHY>(p, g, grid, lds, s, lambda, quirks); break;
-    default: launch_backsub_loss<LDS, SFM_LOSS_NONE>(p, g, grid, lds, s, lambda, quirks); break;
-  }
+  const BaDev& d = p->dev;
+  dispatch_loss(p->loss_kind, [&](auto L) {
+    constexpr int LOSS = decltype(L)::value;
+    const LossArg<LOSS> la = loss_arg<LOSS>(p);
+    dispatch_group<4>(g, [&](auto G) {
+      ba_backsub_kernel<decltype(G)::value, LDS, LOSS><<<grid, 256, lds, s>>>(d, p->cur, lambda, quirks, la);
+    });
+  });
 }
 
 void ba_tick(sfm_ba_problem* p, int kid, bool begin, hipStream_t s) {
@@ -639,11 +624,10 @@ void ba_enqueue_residual_jacobian(sfm_ba_problem* p, int quirks, double* r, doub
 void ba_enqueue_loss_terms(sfm_ba_problem* p, int quirks, double* s_out, double* w_out, double* rho_out) {
   const BaDev& d = p->dev;
   const unsigned grid = (unsigned)((d.M + 255) / 256);
-  switch (p->loss_kind) {
-    case SFM_LOSS_HUBER: ba_loss_terms_kernel<SFM_LOSS_HUBER><<<grid, 256, 0, p->stream>>>(d, p->cur, quirks, loss_arg<SFM_LOSS_HUBER>(p), s_out, w_out, rho_out); break;
-    case SFM_LOSS_CAUCHY: ba_loss_terms_kernel<SFM_LOSS_CAUCHY><<<grid, 256, 0, p->stream>>>(d, p->cur, quirks, loss_arg<SFM_LOSS_CAUCHY>(p), s_out, w_out, rho_out); break;
-    default: ba_loss_terms_kernel<SFM_LOSS_NONE><<<grid, 256, 0, p->stream>>>(d, p->cur, quirks, loss_arg<SFM_LOSS_NONE>(p), s_out, w_out, rho_out); break;
-  }
+  dispatch_loss(p->loss_kind, [&](auto L) {
+    constexpr int LOSS = decltype(L)::value;
+    ba_loss_terms_kernel<LOSS><<<grid, 256, 0, p->stream>>>(d, p->cur, quirks, loss_arg<LOSS>(p), s_out, w_out, rho_out);
+  });
 }
 
 }  // namespace sfm

@@ -16,7 +16,7 @@
 //   cov_trinv_row       X = L^-1, one launch per block row
 //   cov_product         Sigma = X^T X, both triangles, held and padding rows zeroed
 //   cov_points<G>       the hot path: G lanes per point (tracks up to 64), cov_points_block beyond
-//   cov_reduce          cost and observed-point count, one workgroup, fixed order
+//   ba_point_cost_reduce  cost and observed-point count, one workgroup, fixed order (sfm_ba_terms.h)
 //
 // Fixed summation order everywhere, no floating-point atomic: every element of S, L, X and Sigma is summed by one thread
 // in ascending k; a point's six sums are the leaves of ONE balanced binary tree over 64 row slots whatever the group
@@ -93,32 +93,22 @@ __global__ void cov_point_terms_kernel(BaDev d, int cur, double lambda, int quir
     if (ok) {
       const double l11 = sqrt(d1), l21 = (a21 - l20 * l10) / l11;
       const double d2 = a22 - l20 * l20 - l21 * l21;
-      ok = d2 > 1e-14 * a22;      // a rank-2 block (one observation, lambda = 0) leaves rounding noise here
+      ok = d2 > kPtPivotTol * a22;
       if (ok) {
         const double l22 = sqrt(d2);
         const double i00 = 1.0 / l00, i11 = 1.0 / l11, i22 = 1.0 / l22;
         const double i10 = -l10 * i00 * i11;
         const double i21 = -l21 * i11 * i22;
-        const double i20 = -(l20 * i00 + l21 * i10) * i22;
-        di[0] = i00 * i00 + i10 * i10 + i20 * i20;
-        di[1] = i10 * i11 + i20 * i21;
-        di[2] = i20 * i22;
-        di[3] = i11 * i11 + i21 * i21;
-        di[4] = i21 * i22;
-        di[5] = i22 * i22;
+        const double li[6] = {i00, i10, i11, -(l20 * i00 + l21 * i10) * i22, i21, i22};
+        sym3_from_li(li, di);
       }
     }
   }
   if (!ok && end > beg) st |= SFM_COV_PT_SINGULAR;
-  ok = ok && isfinite(di[0] + di[1] + di[2] + di[3] + di[4] + di[5]);
-  if (!ok) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) di[k] = 0;
-  }
+  ok = sym3_finite_or_zero(ok, di);
 #pragma unroll
   for (int k = 0; k < 6; ++k) Dinv[6 * (size_t)p + k] = di[k];
   pt_status[p] = st;
-  const double dm[3][3] = {{di[0], di[1], di[2]}, {di[1], di[3], di[4]}, {di[2], di[4], di[5]}};
   for (int o = beg; o < end; ++o) {
     CamPrep c;
     load_cam(c, d.prep[cur] + d.cam_idx[o]);
@@ -128,35 +118,14 @@ __global__ void cov_point_terms_kernel(BaDev d, int cur, double lambda, int quir
     double* y = Y + 21 * (size_t)o;
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
-      double wi[3];
+      double wi[3], yi[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) wi[k] = ok ? Jp[i] * Jx[k] + Jp[7 + i] * Jx[3 + k] : 0.0;
+      sym3_apply(di, wi, yi);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        w[3 * i + k] = wi[k];
-        y[3 * i + k] = wi[0] * dm[0][k] + wi[1] * dm[1][k] + wi[2] * dm[2][k];
-      }
+      for (int k = 0; k < 3; ++k) { w[3 * i + k] = wi[k]; y[3 * i + k] = yi[k]; }
     }
   }
-}
-
-// cost = sum of the per-point shares, n_observed = points with a track: one workgroup, thread t sums points t, t + 256, ...
-// in ascending order, then a fixed tree
-__global__ __launch_bounds__(256) void cov_reduce_kernel(int N, const double* __restrict__ cost_pt, const int* __restrict__ pt_ptr,
-                                                         double* __restrict__ out) {
-  __shared__ double sc[256];
-  __shared__ int sn[256];
-  const int t = threadIdx.x;
-  double c = 0;
-  int n = 0;
-  for (int p = t; p < N; p += 256) { c += cost_pt[p]; n += pt_ptr[p + 1] > pt_ptr[p]; }
-  sc[t] = c; sn[t] = n;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if (t < s) { sc[t] += sc[t + s]; sn[t] += sn[t + s]; }
-    __syncthreads();
-  }
-  if (t == 0) { out[0] = sc[0]; out[1] = (double)sn[0]; }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -581,14 +550,10 @@ __global__ __launch_bounds__(256) void cov_points_block_kernel(CovPtArgs a) {
 // The group width `group` = 0 stands for: the narrowest that gives a mean track one slot pair per lane, widened while the
 // scene would otherwise leave the device short of waves.
 static int cov_pick_group(int n_pts, long long M, int max_track) {
-  static const int widths[6] = {1, 4, 8, 16, 32, 64};
   const long long mean = n_pts > 0 ? (M + n_pts - 1) / n_pts : 1;
   const int top = std::min(max_track, kCovGroupMax);
-  int i = 0;
-  while (i < 5 && 2 * widths[i] < std::min<long long>(mean + 1, top + 1)) ++i;
-  const long long want_waves = 2LL * 4 * ctx().num_cus;
-  while (i < 5 && (long long)n_pts * widths[i] / 64 < want_waves && widths[i + 1] <= top + 1) ++i;
-  return widths[i];
+  const int i = narrowest_group([&](int w) { return 2 * w >= std::min<long long>(mean + 1, top + 1); });
+  return kGroupWidths[widen_for_waves(i, n_pts, top + 1)];
 }
 
 template <int G>
@@ -606,20 +571,24 @@ struct CovWork {
   DevBuf<int> pt_status, status;
 };
 
-template <int LOSS>
-static int cov_enqueue_terms(sfm_ba_problem* p, double lambda, int quirks, CovWork& w, int Pp, bool want_s, hipEvent_t mark) {
-  const BaDev& d = p->dev;
-  hipStream_t s = p->stream;
-  const LossArg<LOSS> la = loss_arg<LOSS>(p);
-  cov_point_terms_kernel<LOSS><<<(d.N + 127) / 128, 128, 0, s>>>(d, p->cur, lambda, quirks, la, w.Dinv.p, w.W.p, w.Y.p, w.cost_pt.p,
-                                                                 w.pt_status.p);
-  cov_reduce_kernel<<<1, 256, 0, s>>>(d.N, w.cost_pt.p, d.pt_ptr, w.red.p);
-  if (mark) SFM_HIP(hipEventRecord(mark, s));
-  if (want_s)
-    cov_build_s_kernel<LOSS><<<(unsigned)((long long)d.V * (d.V + 1) / 2), 256, 0, s>>>(d, p->cur, lambda, quirks, la, p->cam_ptr, p->cam_obs,
-                                                                                    w.mask.p, w.W.p, w.Y.p, w.pt_status.p, w.S.p, Pp);
-  SFM_HIP(hipGetLastError());
-  return SFM_OK;
+// the per-point terms and the cost (a mark of `ev` behind them), then S if it is wanted
+static int cov_enqueue_terms(sfm_ba_problem* p, double lambda, int quirks, int loss_kind, CovWork& w, int Pp, bool want_s,
+                             PhaseEvents& ev) {
+  return dispatch_loss(loss_kind, [&](auto L) -> int {
+    constexpr int LOSS = decltype(L)::value;
+    const BaDev& d = p->dev;
+    hipStream_t s = p->stream;
+    const LossArg<LOSS> la = loss_arg<LOSS>(p);
+    cov_point_terms_kernel<LOSS><<<(d.N + 127) / 128, 128, 0, s>>>(d, p->cur, lambda, quirks, la, w.Dinv.p, w.W.p, w.Y.p, w.cost_pt.p,
+                                                                   w.pt_status.p);
+    ba_point_cost_reduce_kernel<<<1, 256, 0, s>>>(d.N, w.cost_pt.p, d.pt_ptr, w.red.p);
+    SFM_TRY(ev.mark(s));
+    if (want_s)
+      cov_build_s_kernel<LOSS><<<(unsigned)((long long)d.V * (d.V + 1) / 2), 256, 0, s>>>(d, p->cur, lambda, quirks, la, p->cam_ptr, p->cam_obs,
+                                                                                      w.mask.p, w.W.p, w.Y.p, w.pt_status.p, w.S.p, Pp);
+    SFM_HIP(hipGetLastError());
+    return SFM_OK;
+  });
 }
 
 // S (in w.S, cleared, rows set) -> Sigma in w.S; *fail_row >= 0: the first row whose pivot was not positive
@@ -671,10 +640,7 @@ int sfm_ba_covariance_plan(int n_cams, int* block, int* n_blocks, int* n_launche
 }
 
 int sfm_ba_covariance_times(sfm_ba_problem* p, double* ms) {
-  if (p == nullptr || p->magic != kBaMagic) {
-    set_error("invalid bundle-adjustment problem handle");
-    return SFM_E_HANDLE;
-  }
+  SFM_TRY(ba_check_handle(p));
   if (ms == nullptr) { set_error("sfm_ba_covariance_times: ms is null"); return SFM_E_SHAPE; }
   for (int k = 0; k < 4; ++k) ms[k] = p->cov_ms[k];
   return SFM_OK;
@@ -682,37 +648,18 @@ int sfm_ba_covariance_times(sfm_ba_problem* p, double* ms) {
 
 int sfm_ba_covariance(sfm_ba_problem* p, double lambda, int quirks, int use_loss, const unsigned char* cam_mask, int group,
                       double* cam_cov, double* pt_cov, int* cam_status, int* pt_status, double* sigma0_sq) {
-  if (p == nullptr || p->magic != kBaMagic) {
-    set_error("invalid bundle-adjustment problem handle");
-    return SFM_E_HANDLE;
-  }
+  SFM_TRY(ba_check_handle(p));
   if (!(lambda >= 0)) { set_error("sfm_ba_covariance: lambda must be >= 0"); return SFM_E_SHAPE; }
   if (use_loss != 0 && use_loss != 1) { set_error("sfm_ba_covariance: use_loss must be 0 or 1"); return SFM_E_SHAPE; }
   SFM_TRY(group_width_check("sfm_ba_covariance", group));
-  if (p->comm) {
-    set_error("sfm_ba_covariance: not with a communicator attached (the points are sharded; Sigma_ff needs the all-reduced S)");
-    return SFM_E_SHAPE;
-  }
+  SFM_TRY(ba_refuse_comm(p, "sfm_ba_covariance", "the points are sharded; Sigma_ff needs the all-reduced S"));
   const BaDev& d = p->dev;
   const int V = d.V, N = d.N;
   SFM_TRY(ba_flush(p));                                  // a deferred back substitution still owes the points its update
   hipStream_t s = p->stream;
-  if (!p->prep_valid) SFM_TRY(ba_enqueue_prep(p));       // the expanded cameras the linearisation reads
-  {
-    int st[2] = {0, 0};
-    SFM_HIP(hipMemcpyAsync(st, d.status, sizeof(st), hipMemcpyDeviceToHost, s));
-    SFM_TRY(stream_sync(s));
-    if (st[0] != SFM_OK) {
-      set_error("sfm_ba_covariance: camera %d is invalid (status %d)", st[1], st[0]);
-      return st[0];
-    }
-  }
+  SFM_TRY(ba_prepared_cameras(p, "sfm_ba_covariance"));
   int v_free = 0, first_free = -1;
-  for (int c = 0; c < V; ++c) {
-    const bool fr = cam_mask == nullptr || cam_mask[c] != 0;
-    v_free += fr;
-    if (fr && first_free < 0) first_free = c;
-  }
+  ba_free_cameras(cam_mask, V, &v_free, &first_free);
   if (cam_status)
     for (int c = 0; c < V; ++c) cam_status[c] = (cam_mask && cam_mask[c] == 0) ? SFM_COV_CAM_HELD : 0;
   if (N == 0 || d.M == 0) {                              // nothing is observed: S_ff = lambda I, every point is empty
@@ -736,11 +683,8 @@ int sfm_ba_covariance(sfm_ba_problem* p, double lambda, int quirks, int use_loss
   const int P = 7 * V, Pp = (P + kCovNB - 1) / kCovNB * kCovNB;
   const size_t n = (size_t)N, m = (size_t)d.M;
   CovWork w;
-  // SFM_OPT_TIMING (any bit): hipEvents around the four phases, read back by sfm_ba_covariance_times
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  const bool timed = p->timing != 0;
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 5; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } guard{ev};
-  if (timed) for (int k = 0; k < 5; ++k) SFM_HIP(hipEventCreate(&ev[k]));
+  // SFM_OPT_TIMING (any bit): marks around the four phases, read back by sfm_ba_covariance_times
+  PhaseEvents ev(p->timing != 0);
   for (int k = 0; k < 4; ++k) p->cov_ms[k] = 0.f;
   if (cam_mask) {
     SFM_TRY(w.mask.upload(cam_mask, (size_t)V, s));
@@ -757,19 +701,12 @@ int sfm_ba_covariance(sfm_ba_problem* p, double lambda, int quirks, int use_loss
     cov_rows_kernel<<<(Pp + 255) / 256, 256, 0, s>>>(P, Pp, w.mask.p, w.rowfree.p, w.S.p);
   }
   SFM_HIP(hipMemsetAsync(w.red.p, 0, 2 * sizeof(double), s));
-  if (timed) SFM_HIP(hipEventRecord(ev[0], s));
-  {
-    const bool build = want_sigma;
-    switch (use_loss ? p->loss_kind : SFM_LOSS_NONE) {
-      case SFM_LOSS_HUBER: SFM_TRY(cov_enqueue_terms<SFM_LOSS_HUBER>(p, lambda, quirks, w, Pp, build, ev[1])); break;
-      case SFM_LOSS_CAUCHY: SFM_TRY(cov_enqueue_terms<SFM_LOSS_CAUCHY>(p, lambda, quirks, w, Pp, build, ev[1])); break;
-      default: SFM_TRY(cov_enqueue_terms<SFM_LOSS_NONE>(p, lambda, quirks, w, Pp, build, ev[1])); break;
-    }
-  }
+  SFM_TRY(ev.mark(s));
+  SFM_TRY(cov_enqueue_terms(p, lambda, quirks, use_loss ? p->loss_kind : SFM_LOSS_NONE, w, Pp, want_sigma, ev));
   int fail_row = -1;
-  if (timed) SFM_HIP(hipEventRecord(ev[2], s));
+  SFM_TRY(ev.mark(s));
   if (want_sigma) SFM_TRY(cov_enqueue_inverse(s, w, Pp, &fail_row));
-  if (timed) SFM_HIP(hipEventRecord(ev[3], s));
+  SFM_TRY(ev.mark(s));
   if (fail_row >= 0) {
     SFM_TRY(stream_sync(s));
     const int cam = std::min(fail_row / 7, V - 1);
@@ -786,7 +723,7 @@ int sfm_ba_covariance(sfm_ba_problem* p, double lambda, int quirks, int use_loss
       dispatch_group<1>(g, [&](auto G) { launch_cov_points<decltype(G)::value>(a, s); });
       if (p->max_track > kCovGroupMax) cov_points_block_kernel<<<N, 256, 0, s>>>(a);
       SFM_HIP(hipGetLastError());
-      if (timed) SFM_HIP(hipEventRecord(ev[4], s));
+      SFM_TRY(ev.mark(s));
       SFM_TRY(w.pt_cov.download(pt_cov, 6 * n, s));
     } else {
       SFM_TRY(w.Dinv.download(pt_cov, 6 * n, s));
@@ -806,10 +743,7 @@ int sfm_ba_covariance(sfm_ba_problem* p, double lambda, int quirks, int use_loss
   double red[2] = {0, 0};
   SFM_TRY(w.red.download(red, 2, s));
   SFM_TRY(stream_sync(s));
-  if (timed) {
-    for (int k = 0; k < 4; ++k)
-      if (k < 3 || (pt_cov != nullptr && want_sigma)) (void)hipEventElapsedTime(&p->cov_ms[k], ev[k], ev[k + 1]);
-  }
+  for (int k = 0; k < 4; ++k) p->cov_ms[k] = ev.elapsed_ms(k);      // (the points' phase has its closing mark only when it ran)
   if (sigma0_sq) {
     const double dof = 2.0 * (double)d.M - 7.0 * v_free - 3.0 * red[1];
     *sigma0_sq = dof > 0 ? red[0] / dof : 0.0;

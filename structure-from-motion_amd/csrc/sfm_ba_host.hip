@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "sfm_ba.h"
+#include "sfm_ba_terms.h"
 #include "sfm_scan.h"
 
 namespace sfm {
@@ -211,12 +212,65 @@ __global__ void ba_gather_rot_kernel(int V, const CamPrep* __restrict__ prep, do
   rots[i] = prep[i / 9].R[i % 9];
 }
 
-static int check_problem(const sfm_ba_problem* p) {
+// cost (and, with pt_ptr, the observed-point count) of a per-point linearisation: sfm_ba_terms.h
+__global__ __launch_bounds__(256) void ba_point_cost_reduce_kernel(int N, const double* __restrict__ cost_pt, const int* __restrict__ pt_ptr,
+                                                                   double* __restrict__ out) {
+  __shared__ double sc[256];
+  __shared__ int sn[256];
+  const int t = threadIdx.x;
+  double c = 0;
+  int n = 0;
+  for (int p = t; p < N; p += 256) {
+    c += cost_pt[p];
+    if (pt_ptr != nullptr) n += pt_ptr[p + 1] > pt_ptr[p];
+  }
+  sc[t] = c; sn[t] = n;
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if (t < s) { sc[t] += sc[t + s]; sn[t] += sn[t + s]; }
+    __syncthreads();
+  }
+  if (t == 0) {
+    out[0] = sc[0];
+    if (pt_ptr != nullptr) out[1] = (double)sn[0];
+  }
+}
+
+int ba_check_handle(const sfm_ba_problem* p) {
   if (p == nullptr || p->magic != kBaMagic) {
     set_error("invalid bundle-adjustment problem handle");
     return SFM_E_HANDLE;
   }
   return SFM_OK;
+}
+
+int ba_refuse_comm(const sfm_ba_problem* p, const char* who, const char* why) {
+  if (p->comm == nullptr) return SFM_OK;
+  set_error("%s: not with a communicator attached (%s)", who, why);
+  return SFM_E_SHAPE;
+}
+
+int ba_sync_cam_status(sfm_ba_problem* p, const char* who, const char* when) {
+  int st[2] = {0, 0};
+  SFM_HIP(hipMemcpyAsync(st, p->dev.status, sizeof(st), hipMemcpyDeviceToHost, p->stream));
+  SFM_TRY(stream_sync(p->stream));
+  if (st[0] != SFM_OK) set_error("%s: camera %d is invalid%s (status %d)", who, st[1], when, st[0]);
+  return st[0];
+}
+
+int ba_prepared_cameras(sfm_ba_problem* p, const char* who) {
+  if (!p->prep_valid) SFM_TRY(ba_enqueue_prep(p));
+  return ba_sync_cam_status(p, who, "");
+}
+
+void ba_free_cameras(const unsigned char* cam_mask, int V, int* v_free, int* first_free) {
+  *v_free = 0;
+  *first_free = -1;
+  for (int c = 0; c < V; ++c) {
+    if (cam_mask != nullptr && cam_mask[c] == 0) continue;
+    if (*v_free == 0) *first_free = c;
+    ++*v_free;
+  }
 }
 
 static const char* status_name(int st) {
@@ -339,9 +393,15 @@ static int ba_scene_alloc(BaScene& sc, int V, int N, long long M, hipStream_t st
 }
 
 // A new state starts a new cost history (sfm_ba_get_stats).
-static int ba_reset_stats(sfm_ba_problem* p) {
+int ba_reset_stats(sfm_ba_problem* p) {
   SFM_HIP(hipMemsetAsync(p->dev.cost, 0, kStatSlots * sizeof(double), p->stream));
   SFM_HIP(hipMemsetAsync(p->dev.iter_count, 0, sizeof(int), p->stream));
+  return SFM_OK;
+}
+
+int ba_state_changed(sfm_ba_problem* p) {
+  SFM_TRY(ba_reset_stats(p));
+  p->prep_valid = false;
   return SFM_OK;
 }
 
@@ -474,7 +534,7 @@ int sfm_ba_destroy(sfm_ba_problem* p) {
 }
 
 int sfm_ba_set_stream(sfm_ba_problem* p, void* hip_stream) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   SFM_TRY(ba_flush(p));
   SFM_HIP(hipStreamSynchronize(p->stream));
   ba_graph_drop(p);
@@ -483,7 +543,7 @@ int sfm_ba_set_stream(sfm_ba_problem* p, void* hip_stream) {
 }
 
 int sfm_ba_set_option(sfm_ba_problem* p, int option, int value) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   ba_graph_drop(p);       // every option changes what an iteration launches
   switch (option) {
     case SFM_OPT_GRAPH:
@@ -522,7 +582,7 @@ int sfm_ba_set_option(sfm_ba_problem* p, int option, int value) {
 }
 
 int sfm_ba_info(sfm_ba_problem* p, int what, int64_t* value) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (value == nullptr) { set_error("sfm_ba_info: value is null"); return SFM_E_SHAPE; }
   switch (what) {
     case SFM_INFO_SCHUR_KERNEL: {
@@ -550,12 +610,12 @@ int sfm_ba_info(sfm_ba_problem* p, int what, int64_t* value) {
 }
 
 int sfm_ba_flush(sfm_ba_problem* p) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   return ba_flush(p);
 }
 
 int sfm_ba_set_cameras(sfm_ba_problem* p, const double* cams) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   SFM_TRY(ba_flush(p));
   BaDev& d = p->dev;
   SFM_TRY(ba_upload(p, d.cams, cams, sizeof(double) * 7 * d.V));
@@ -567,7 +627,7 @@ int sfm_ba_set_cameras(sfm_ba_problem* p, const double* cams) {
 }
 
 int sfm_ba_set_points(sfm_ba_problem* p, int first, int count, const double* pts) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   BaDev& d = p->dev;
   SFM_TRY(ba_flush(p));
   if (first < 0 || count < 0 || first + (long long)count > d.N) {
@@ -583,7 +643,7 @@ int sfm_ba_set_points(sfm_ba_problem* p, int first, int count, const double* pts
 }
 
 int sfm_ba_set_state(sfm_ba_problem* p, const double* cams, const double* pts) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   SFM_TRY(ba_flush(p));
   BaDev& d = p->dev;
   SFM_TRY(ba_upload(p, d.cams, cams, sizeof(double) * 7 * d.V));
@@ -600,7 +660,7 @@ int sfm_ba_set_state(sfm_ba_problem* p, const double* cams, const double* pts) {
 }
 
 int sfm_ba_set_loss(sfm_ba_problem* p, int kind, double delta) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (kind != SFM_LOSS_NONE && kind != SFM_LOSS_HUBER && kind != SFM_LOSS_CAUCHY) { set_error("sfm_ba_set_loss: unknown loss %d", kind); return SFM_E_SHAPE; }
   if (kind != SFM_LOSS_NONE && !(delta > 0 && delta <= 1.7976931348623157e308)) { set_error("sfm_ba_set_loss: delta must be finite and > 0"); return SFM_E_SHAPE; }
   SFM_TRY(ba_flush(p));        // the pending step was solved for the old loss: its back substitution takes the old weights
@@ -612,14 +672,14 @@ int sfm_ba_set_loss(sfm_ba_problem* p, int kind, double delta) {
 }
 
 int sfm_ba_get_loss(sfm_ba_problem* p, int* kind, double* delta) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (kind) *kind = p->loss_kind;
   if (delta) *delta = p->loss_delta;
   return SFM_OK;
 }
 
 int sfm_ba_loss_terms(sfm_ba_problem* p, double* s, double* w, double* rho) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   SFM_TRY(ba_flush(p));
   if (!p->prep_valid) SFM_TRY(ba_enqueue_prep(p));
   const size_t m = (size_t)p->dev.M;
@@ -638,7 +698,7 @@ int sfm_ba_loss_terms(sfm_ba_problem* p, double* s, double* w, double* rho) {
 }
 
 int sfm_ba_get_stats(sfm_ba_problem* p, double* cost, int max_iters, int* n_iters) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (max_iters < 0 || (max_iters > 0 && cost == nullptr)) { set_error("sfm_ba_get_stats: bad output buffer"); return SFM_E_SHAPE; }
   int done = 0;
   SFM_HIP(hipMemcpyAsync(&done, p->dev.iter_count, sizeof(int), hipMemcpyDeviceToHost, p->stream));
@@ -651,23 +711,23 @@ int sfm_ba_get_stats(sfm_ba_problem* p, double* cost, int max_iters, int* n_iter
 }
 
 int sfm_ba_linearize_reduce(sfm_ba_problem* p, double lambda, int quirks) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   return ba_enqueue_linearize_reduce(p, lambda, quirks);
 }
 
 int sfm_ba_solve_update(sfm_ba_problem* p, double lambda, int quirks) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   return ba_enqueue_solve_update(p, lambda, quirks);
 }
 
 int sfm_ba_iterate(sfm_ba_problem* p, double lambda, int iters, int quirks) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (iters < 0) { set_error("sfm_ba_iterate: iters < 0"); return SFM_E_SHAPE; }
   return ba_enqueue_iterations(p, lambda, iters, quirks);
 }
 
 int sfm_ba_get_state(sfm_ba_problem* p, double* cams, double* pts) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   SFM_TRY(ba_flush(p));
   hipStream_t s = p->stream;
   BaDev& d = p->dev;
@@ -689,7 +749,7 @@ int sfm_ba_get_state(sfm_ba_problem* p, double* cams, double* pts) {
 }
 
 int sfm_ba_rederive_quaternions(sfm_ba_problem* p, int first, int count) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   SFM_TRY(ba_flush(p));
   BaDev& d = p->dev;
   if (first < 0 || count < 0 || first + (long long)count > d.V) {
@@ -707,7 +767,7 @@ int sfm_ba_rederive_quaternions(sfm_ba_problem* p, int first, int count) {
 }
 
 int sfm_ba_get_state_rot(sfm_ba_problem* p, double* cams, double* pts, double* rots) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (rots == nullptr) return sfm_ba_get_state(p, cams, pts);
   SFM_TRY(ba_flush(p));
   if (!p->prep_valid) SFM_TRY(ba_enqueue_prep(p));
@@ -722,7 +782,7 @@ int sfm_ba_get_state_rot(sfm_ba_problem* p, double* cams, double* pts, double* r
 
 int sfm_ba_append(sfm_ba_problem* p, int n_new_cams, const double* cams_new, int n_new_pts, const double* pts_new,
                   int64_t n_new_obs, const int* obs_cam, const int* obs_pt, const double* uv_norm) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (n_new_cams < 0 || n_new_pts < 0 || n_new_obs < 0) { set_error("sfm_ba_append: negative count"); return SFM_E_SHAPE; }
   SFM_TRY(ba_flush(p));
   BaDev& d = p->dev;
@@ -766,7 +826,7 @@ int sfm_ba_append(sfm_ba_problem* p, int n_new_cams, const double* cams_new, int
 // the device -- the kept observations scattered to their new offsets, cameras and points copied as they are.
 int sfm_ba_cull(sfm_ba_problem* p, double max_err2, double cos_min_angle, int min_obs, int group, const double* cam_scale,
                 double* err2, double* depth, unsigned char* obs_flags, double* min_cos, int* pt_flags, int64_t* summary) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   ScreenWork w;
   SFM_TRY(ba_screen_run(p, "sfm_ba_cull", max_err2, cos_min_angle, min_obs, group, cam_scale, err2, depth, obs_flags, min_cos,
                         pt_flags, summary, w));
@@ -802,7 +862,7 @@ int sfm_ba_create_from_tracks(sfm_track_store* store, sfm_ba_problem** out) {
 
 int sfm_ba_sync_tracks(sfm_ba_problem* p, sfm_track_store* store, int n_new_cams, const double* cams_new, int n_new_pts,
                        const double* pts_new, int* action, int64_t* n_new_obs) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (action == nullptr) { set_error("sfm_ba_sync_tracks: action is null"); return SFM_E_SHAPE; }
   if ((n_new_cams > 0 && cams_new == nullptr) || (n_new_pts > 0 && pts_new == nullptr)) { set_error("sfm_ba_sync_tracks: new cameras or points are null"); return SFM_E_SHAPE; }
   TrackObservations t;
@@ -839,7 +899,7 @@ int sfm_ba_sync_tracks(sfm_ba_problem* p, sfm_track_store* store, int n_new_cams
 }
 
 int sfm_ba_get_structure(sfm_ba_problem* p, int* pt_ptr, int* cam_idx, double* uv_norm) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   const BaDev& d = p->dev;
   hipStream_t s = p->stream;
   const size_t m = (size_t)d.M;
@@ -853,7 +913,7 @@ int sfm_ba_get_structure(sfm_ba_problem* p, int* pt_ptr, int* cam_idx, double* u
 }
 
 int sfm_ba_points_ptr(sfm_ba_problem* p, void** d_px, void** d_py, void** d_pz, int* n_pts) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   SFM_TRY(ba_flush(p));           // the deferred back substitution still has to move the points
   if (d_px) *d_px = p->dev.px;
   if (d_py) *d_py = p->dev.py;
@@ -863,13 +923,13 @@ int sfm_ba_points_ptr(sfm_ba_problem* p, void** d_px, void** d_py, void** d_pz, 
 }
 
 int sfm_ba_stream(sfm_ba_problem* p, void** hip_stream) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (hip_stream) *hip_stream = p->stream;
   return SFM_OK;
 }
 
 int sfm_ba_reduced_buffer(sfm_ba_problem* p, void** device_ptr, int64_t* n_doubles, int* ld) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (device_ptr) *device_ptr = p->dev.red;
   if (n_doubles) *n_doubles = (int64_t)red_size(p->dev.nbk);
   if (ld) *ld = p->dev.nbk * kNB;
@@ -877,7 +937,7 @@ int sfm_ba_reduced_buffer(sfm_ba_problem* p, void** device_ptr, int64_t* n_doubl
 }
 
 int sfm_ba_bind_reduced_buffer(sfm_ba_problem* p, void* device_ptr, int64_t n_doubles) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   SFM_TRY(ba_flush(p));           // the deferred kernel clears the buffer that is bound now
   const int64_t need = (int64_t)red_size(p->dev.nbk);
   ba_graph_drop(p);
@@ -889,7 +949,7 @@ int sfm_ba_bind_reduced_buffer(sfm_ba_problem* p, void* device_ptr, int64_t n_do
 }
 
 int sfm_ba_set_comm(sfm_ba_problem* p, sfm_comm* comm) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   SFM_TRY(ba_flush(p));
   ba_graph_drop(p);          // a captured iteration body has no collective in it
   SFM_TRY(comm_attach(comm, +1));
@@ -899,7 +959,7 @@ int sfm_ba_set_comm(sfm_ba_problem* p, sfm_comm* comm) {
 }
 
 int sfm_ba_kernel_time(sfm_ba_problem* p, int kernel_id, double* total_ms, int* launches) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (kernel_id < 0 || kernel_id >= SFM_K_COUNT) { set_error("bad kernel id %d", kernel_id); return SFM_E_SHAPE; }
   SFM_HIP(hipStreamSynchronize(p->stream));
   KernelTimer& t = p->timers[kernel_id];
@@ -917,7 +977,7 @@ int sfm_ba_kernel_time(sfm_ba_problem* p, int kernel_id, double* total_ms, int* 
 namespace sfm { __global__ void ba_noop_kernel() {} }
 
 int sfm_ba_event_overhead(sfm_ba_problem* p, int n, double* avg_ms) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (n < 1 || avg_ms == nullptr) { set_error("sfm_ba_event_overhead: bad arguments"); return SFM_E_SHAPE; }
   hipStream_t s = p->stream;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev((size_t)n);
@@ -943,7 +1003,7 @@ int sfm_ba_event_overhead(sfm_ba_problem* p, int n, double* avg_ms) {
 }
 
 int sfm_ba_debug_stamps(sfm_ba_problem* p, unsigned long long* out, int n) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   if (p->stamps == nullptr || n < 0 || n > 1024) { set_error("debug stamps not enabled (SFM_OPT_DEBUG bit 8)"); return SFM_E_SHAPE; }
   SFM_HIP(hipStreamSynchronize(p->stream));
   SFM_HIP(hipMemcpy(out, p->stamps, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
@@ -951,7 +1011,7 @@ int sfm_ba_debug_stamps(sfm_ba_problem* p, unsigned long long* out, int n) {
 }
 
 int sfm_ba_reset_timing(sfm_ba_problem* p) {
-  SFM_TRY(check_problem(p));
+  SFM_TRY(ba_check_handle(p));
   SFM_HIP(hipStreamSynchronize(p->stream));
   for (auto& t : p->timers) { t.used = 0; t.calls = 0; t.open = false; }
   return SFM_OK;

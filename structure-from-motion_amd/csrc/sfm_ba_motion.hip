@@ -27,8 +27,7 @@
 
 namespace sfm {
 
-constexpr int kMoSlice = 64;         // observations per slice = 16 lanes x kMoPerLane
-constexpr int kMoPerLane = 4;        // consecutive observations a lane keeps in registers
+constexpr int kMoPerLane = 4;        // consecutive observations a lane keeps in registers: a slice (kCamSlice) is 16 lanes' worth
 constexpr int kMoWaveObs = 256;      // size class 1: one wave
 constexpr int kMoBlockObs = 1024;    // size class 2: four waves; the larger classes work through 1 024 observations at a time
 constexpr int kMoStreamObs = 16384;  // size class 3: one workgroup streams the camera's observations in every pass; beyond it
@@ -218,10 +217,6 @@ __global__ __launch_bounds__(THREADS) void ba_motion_resident_kernel(BaDev d, in
   }
 }
 
-// first workspace row of a camera whose list starts at `base`: camera k has at most n_k / 64 + 1 slices, so the rows of
-// the cameras before it end at or before base / 64 + cam (no scan needed; the workspace has M / 64 + V + 1 rows)
-__device__ __forceinline__ size_t mo_ws_row(int base, int cam) { return (size_t)(base / kMoSlice) + cam; }
-
 // Cameras of more than n_min observations, one pass: workgroup (camera, block) sums observations [1024 block, +1024) of the
 // camera's list at the prepared camera prep[cur] into one 36-vector per slice.
 template <int LOSS>
@@ -252,9 +247,9 @@ __global__ __launch_bounds__(256) void ba_motion_partial_kernel(BaDev d, int cur
   mo_fold_row(acc, own, lane, red[tid >> 4]);
   const int any_behind = __syncthreads_or(behind);
   if (any_behind && tid == 0) atomicOr(&behind_flag[cam], 1);
-  const int n_slices = (n + kMoSlice - 1) / kMoSlice;
+  const int n_slices = cam_slice_count(n);
   const int rows = min(16, n_slices - blk * 16);
-  double* dst = ws + (mo_ws_row(base, cam) + (size_t)blk * 16) * kMoSums;
+  double* dst = ws + (cam_slice_first_row(base, cam) + (size_t)blk * 16) * kMoSums;
   const double* src = &red[0][0];
   for (int i = tid; i < rows * kMoSums; i += 256) dst[i] = src[i];
 }
@@ -269,9 +264,9 @@ __global__ __launch_bounds__(64) void ba_motion_finish_kernel(BaDev d, int cur, 
   const int base = a.ptr[cam], n = a.ptr[cam + 1] - base;
   if (n <= n_min) return;
   if (a.status[cam] & kMoDone) return;
-  const int n_slices = (n + kMoSlice - 1) / kMoSlice;
+  const int n_slices = cam_slice_count(n);
   if (tid < kMoSums) {
-    const double* part = ws + mo_ws_row(base, cam) * kMoSums + tid;
+    const double* part = ws + cam_slice_first_row(base, cam) * kMoSums + tid;
     double t = part[0];
     for (int s = 1; s < n_slices; ++s) t += part[(size_t)s * kMoSums];
     sums[tid] = t;
@@ -321,34 +316,36 @@ static int mo_size_class(long long n) {
 }
 
 // SFM_OPT_DEBUG bit 32768 (measurement only): cameras of size class 3 take class 4's launches
-template <int LOSS>
-static int mo_enqueue(sfm_ba_problem* p, const MoArgs& a, const int (&n_class)[5], int max_obs, DevBuf<double>& ws,
+static int mo_enqueue(sfm_ba_problem* p, const MoArgs& a, int loss_kind, const int (&n_class)[5], int max_obs, DevBuf<double>& ws,
                       DevBuf<int>& behind, DevBuf<double>& cams_in) {
-  const BaDev& d = p->dev;
-  hipStream_t s = p->stream;
-  const LossArg<LOSS> la = loss_arg<LOSS>(p);
-  const bool stream3 = !(p->debug & 32768);
-  const int n_min = stream3 ? kMoStreamObs : kMoBlockObs;      // the multi-launch path takes the cameras beyond it
-  if (n_class[0] + n_class[1] > 0)
-    ba_motion_resident_kernel<64, false, LOSS><<<d.V, 64, 0, s>>>(d, p->cur, a, 0, kMoWaveObs, la);
-  if (n_class[2] > 0)
-    ba_motion_resident_kernel<256, false, LOSS><<<d.V, 256, 0, s>>>(d, p->cur, a, kMoWaveObs + 1, kMoBlockObs, la);
-  if (n_class[3] > 0 && stream3)
-    ba_motion_resident_kernel<256, true, LOSS><<<d.V, 256, 0, s>>>(d, p->cur, a, kMoBlockObs + 1, kMoStreamObs, la);
-  if (n_class[4] > 0 || (n_class[3] > 0 && !stream3)) {
-    SFM_TRY(ws.alloc(((size_t)d.M / kMoSlice + d.V + 1) * kMoSums, s));
-    SFM_TRY(behind.alloc((size_t)d.V, s));
-    SFM_TRY(cams_in.alloc(7 * (size_t)d.V, s));
-    SFM_HIP(hipMemsetAsync(behind.p, 0, sizeof(int) * (size_t)d.V, s));
-    SFM_HIP(hipMemcpyAsync(cams_in.p, d.cams, sizeof(double) * 7 * d.V, hipMemcpyDeviceToDevice, s));
-    const dim3 grid((unsigned)d.V, (unsigned)((max_obs + kMoBlockObs - 1) / kMoBlockObs));
-    for (int it = 0; it <= a.iters; ++it) {
-      ba_motion_partial_kernel<LOSS><<<grid, 256, 0, s>>>(d, p->cur, a, n_min, ws.p, behind.p, la);
-      ba_motion_finish_kernel<<<d.V, 64, 0, s>>>(d, p->cur, a, n_min, ws.p, behind.p, cams_in.p, it);
+  return dispatch_loss(loss_kind, [&](auto L) -> int {
+    constexpr int LOSS = decltype(L)::value;
+    const BaDev& d = p->dev;
+    hipStream_t s = p->stream;
+    const LossArg<LOSS> la = loss_arg<LOSS>(p);
+    const bool stream3 = !(p->debug & 32768);
+    const int n_min = stream3 ? kMoStreamObs : kMoBlockObs;      // the multi-launch path takes the cameras beyond it
+    if (n_class[0] + n_class[1] > 0)
+      ba_motion_resident_kernel<64, false, LOSS><<<d.V, 64, 0, s>>>(d, p->cur, a, 0, kMoWaveObs, la);
+    if (n_class[2] > 0)
+      ba_motion_resident_kernel<256, false, LOSS><<<d.V, 256, 0, s>>>(d, p->cur, a, kMoWaveObs + 1, kMoBlockObs, la);
+    if (n_class[3] > 0 && stream3)
+      ba_motion_resident_kernel<256, true, LOSS><<<d.V, 256, 0, s>>>(d, p->cur, a, kMoBlockObs + 1, kMoStreamObs, la);
+    if (n_class[4] > 0 || (n_class[3] > 0 && !stream3)) {
+      SFM_TRY(ws.alloc(cam_slice_rows(d.M, d.V) * kMoSums, s));
+      SFM_TRY(behind.alloc((size_t)d.V, s));
+      SFM_TRY(cams_in.alloc(7 * (size_t)d.V, s));
+      SFM_HIP(hipMemsetAsync(behind.p, 0, sizeof(int) * (size_t)d.V, s));
+      SFM_HIP(hipMemcpyAsync(cams_in.p, d.cams, sizeof(double) * 7 * d.V, hipMemcpyDeviceToDevice, s));
+      const dim3 grid((unsigned)d.V, (unsigned)((max_obs + kMoBlockObs - 1) / kMoBlockObs));
+      for (int it = 0; it <= a.iters; ++it) {
+        ba_motion_partial_kernel<LOSS><<<grid, 256, 0, s>>>(d, p->cur, a, n_min, ws.p, behind.p, la);
+        ba_motion_finish_kernel<<<d.V, 64, 0, s>>>(d, p->cur, a, n_min, ws.p, behind.p, cams_in.p, it);
+      }
     }
-  }
-  SFM_HIP(hipGetLastError());
-  return SFM_OK;
+    SFM_HIP(hipGetLastError());
+    return SFM_OK;
+  });
 }
 
 }  // namespace sfm
@@ -359,25 +356,19 @@ extern "C" {
 
 int sfm_ba_refine_cameras_plan(int64_t n_obs, int* n_slices, int* slice_obs, int* size_class) {
   if (n_obs < 0) { set_error("sfm_ba_refine_cameras_plan: n_obs < 0"); return SFM_E_SHAPE; }
-  if (n_slices) *n_slices = (int)((n_obs + kMoSlice - 1) / kMoSlice);
-  if (slice_obs) *slice_obs = kMoSlice;
+  if (n_slices) *n_slices = (int)cam_slice_count(n_obs);
+  if (slice_obs) *slice_obs = kCamSlice;
   if (size_class) *size_class = mo_size_class(n_obs);
   return SFM_OK;
 }
 
 int sfm_ba_refine_cameras(sfm_ba_problem* p, double lambda, int iters, int quirks, int use_loss, const unsigned char* cam_mask,
                           double* cost, int* status) {
-  if (p == nullptr || p->magic != kBaMagic) {
-    set_error("invalid bundle-adjustment problem handle");
-    return SFM_E_HANDLE;
-  }
+  SFM_TRY(ba_check_handle(p));
   if (iters < 0) { set_error("sfm_ba_refine_cameras: iters < 0"); return SFM_E_SHAPE; }
   if (!(lambda >= 0)) { set_error("sfm_ba_refine_cameras: lambda must be >= 0"); return SFM_E_SHAPE; }
   if (use_loss != 0 && use_loss != 1) { set_error("sfm_ba_refine_cameras: use_loss must be 0 or 1"); return SFM_E_SHAPE; }
-  if (p->comm) {
-    set_error("sfm_ba_refine_cameras: not with a communicator attached (the points are sharded; the replicas would diverge)");
-    return SFM_E_SHAPE;
-  }
+  SFM_TRY(ba_refuse_comm(p, "sfm_ba_refine_cameras", "the points are sharded; the replicas would diverge"));
   BaDev& d = p->dev;
   const int V = d.V;
   SFM_TRY(ba_flush(p));                                  // a deferred back substitution still owes the points its update
@@ -389,16 +380,7 @@ int sfm_ba_refine_cameras(sfm_ba_problem* p, double lambda, int iters, int quirk
     return SFM_OK;
   }
   hipStream_t s = p->stream;
-  if (!p->prep_valid) SFM_TRY(ba_enqueue_prep(p));       // the expanded cameras the linearisation reads
-  {
-    int st[2] = {0, 0};
-    SFM_HIP(hipMemcpyAsync(st, d.status, sizeof(st), hipMemcpyDeviceToHost, s));
-    SFM_TRY(stream_sync(s));
-    if (st[0] != SFM_OK) {
-      set_error("sfm_ba_refine_cameras: camera %d is invalid (status %d)", st[1], st[0]);
-      return st[0];
-    }
-  }
+  SFM_TRY(ba_prepared_cameras(p, "sfm_ba_refine_cameras"));
   SFM_TRY(ba_cam_list_ensure(p));
   int n_class[5] = {0, 0, 0, 0, 0}, max_obs = 0;
   for (int c = 0; c < V; ++c) {
@@ -424,15 +406,8 @@ int sfm_ba_refine_cameras(sfm_ba_problem* p, double lambda, int iters, int quirk
   a.V = V; a.ptr = p->cam_ptr; a.obs = p->cam_obs; a.mask = cam_mask ? dmask.p : nullptr;
   a.lambda = lambda; a.iters = iters; a.quirks = quirks;
   a.cost = dcost.p; a.status = dstat.p;
-  switch (use_loss ? p->loss_kind : SFM_LOSS_NONE) {
-    case SFM_LOSS_HUBER: SFM_TRY(mo_enqueue<SFM_LOSS_HUBER>(p, a, n_class, max_obs, ws, behind, cams_in)); break;
-    case SFM_LOSS_CAUCHY: SFM_TRY(mo_enqueue<SFM_LOSS_CAUCHY>(p, a, n_class, max_obs, ws, behind, cams_in)); break;
-    default: SFM_TRY(mo_enqueue<SFM_LOSS_NONE>(p, a, n_class, max_obs, ws, behind, cams_in)); break;
-  }
-  // new cameras start a new cost history and need a new expansion, as after sfm_ba_set_cameras
-  SFM_HIP(hipMemsetAsync(d.cost, 0, kStatSlots * sizeof(double), s));
-  SFM_HIP(hipMemsetAsync(d.iter_count, 0, sizeof(int), s));
-  p->prep_valid = false;
+  SFM_TRY(mo_enqueue(p, a, use_loss ? p->loss_kind : SFM_LOSS_NONE, n_class, max_obs, ws, behind, cams_in));
+  SFM_TRY(ba_state_changed(p));                          // new cameras
   if (cost) SFM_TRY(dcost.download(cost, 2 * (size_t)V, s));
   if (status) SFM_TRY(dstat.download(status, (size_t)V, s));
   SFM_TRY(stream_sync(s));

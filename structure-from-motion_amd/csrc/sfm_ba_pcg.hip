@@ -35,7 +35,6 @@
 
 namespace sfm {
 
-constexpr int kPcgSlice = 64;        // entries of the camera-major list per slice: one wave, one entry per lane
 constexpr int kPcgBlockSums = 35;    // S_cc lower triangle (28) | b (7)
 constexpr int kPcgJ = 20;            // doubles per observation of the stored Jacobians: Jp (2 x 7) | Jx (2 x 3)
 constexpr int kPcgVecThreads = 1024; // the one workgroup of the vector update: eight lanes per camera, 128 cameras a sweep
@@ -54,7 +53,7 @@ struct PcgState {
 struct PcgDev {
   int V, N;
   long long M;
-  int rows;                     // slices of the camera-major list, numbered as mo_ws_row does: M / 64 + V + 1 at the most
+  int rows;                     // slices of the camera-major list (kCamSlice entries: one wave, one per lane), cam_slice_rows(M, V)
   double lambda;
   const int* pt_ptr;
   const int* cam_idx;
@@ -78,8 +77,6 @@ struct PcgDev {
   PcgState* st;
 };
 
-__device__ __forceinline__ int pcg_first_row(const PcgDev& a, int cam) { return a.cam_ptr[cam] / kPcgSlice + cam; }
-
 // ---------------------------------------------------------------------------------------------
 // once per call: the camera of every slice
 // ---------------------------------------------------------------------------------------------
@@ -87,7 +84,7 @@ __global__ void pcg_rows_kernel(PcgDev a) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= a.V) return;
   const int n = a.cam_ptr[c + 1] - a.cam_ptr[c];
-  const int first = pcg_first_row(a, c), ns = (n + kPcgSlice - 1) / kPcgSlice;
+  const int first = (int)cam_slice_first_row(a.cam_ptr[c], c), ns = cam_slice_count(n);
   for (int s = 0; s < ns; ++s)
     if (first + s < a.rows) a.row_cam[first + s] = c;
 }
@@ -114,28 +111,11 @@ __device__ __forceinline__ bool pcg_point_inverse(const double* a, double* di) {
     const double i00 = rsqrt_nr(a[0]), l10 = a[1] * i00, l20 = a[3] * i00;
     const double i11 = rsqrt_nr(d1), l21 = (a[4] - l20 * l10) * i11;
     const double d2 = a[5] - l20 * l20 - l21 * l21;
-    ok = d2 > 1e-14 * a[5];      // a rank-2 block (one observation, lambda = 0) leaves rounding noise here
+    ok = d2 > kPtPivotTol * a[5];
     if (ok) chol3_inv_fast(a, li);
   }
-  // D^-1 = L^-T L^-1, li = (i00 i10 i11 i20 i21 i22)
-  di[0] = li[0] * li[0] + li[1] * li[1] + li[3] * li[3];
-  di[1] = li[1] * li[2] + li[3] * li[4];
-  di[2] = li[3] * li[5];
-  di[3] = li[2] * li[2] + li[4] * li[4];
-  di[4] = li[4] * li[5];
-  di[5] = li[5] * li[5];
-  ok = ok && isfinite(di[0] + di[1] + di[2] + di[3] + di[4] + di[5]);
-  if (!ok) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) di[k] = 0.0;
-  }
-  return ok;
-}
-
-__device__ __forceinline__ void pcg_sym3_apply(const double* di, const double* g, double* out) {
-  out[0] = di[0] * g[0] + di[1] * g[1] + di[2] * g[2];
-  out[1] = di[1] * g[0] + di[3] * g[1] + di[4] * g[2];
-  out[2] = di[2] * g[0] + di[4] * g[1] + di[5] * g[2];
+  sym3_from_li(li, di);
+  return sym3_finite_or_zero(ok, di);
 }
 
 template <int G, int LOSS>
@@ -190,7 +170,7 @@ __global__ __launch_bounds__(256) void pcg_linearize_kernel(BaDev d, int cur, Pc
   // dinv comes out packed (xx xy xz yy yz zz)
   const bool ok = pcg_point_inverse(li_order, dinv);
   double g[3];
-  pcg_sym3_apply(dinv, s + 6, g);                           // D^-1 ex
+  sym3_apply(dinv, s + 6, g);                               // D^-1 ex
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) a.Dinv[6 * (size_t)p + k] = dinv[k];
@@ -206,21 +186,6 @@ __global__ __launch_bounds__(256) void pcg_linearize_kernel(BaDev d, int cur, Pc
     e[0] -= jx[0] * g[0] + jx[1] * g[1] + jx[2] * g[2];
     e[1] -= jx[3] * g[0] + jx[4] * g[1] + jx[5] * g[2];
   }
-}
-
-// cost of the linearisation: thread t sums points t, t + 256, ... in ascending order, then a fixed tree
-__global__ __launch_bounds__(256) void pcg_cost_kernel(int N, const double* __restrict__ cost_pt, double* __restrict__ out) {
-  __shared__ double sc[256];
-  const int t = threadIdx.x;
-  double c = 0;
-  for (int p = t; p < N; p += 256) c += cost_pt[p];
-  sc[t] = c;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if (t < s) sc[t] += sc[t + s];
-    __syncthreads();
-  }
-  if (t == 0) *out = sc[0];
 }
 
 // pass one of q = S p
@@ -252,7 +217,7 @@ __global__ __launch_bounds__(256) void pcg_matvec_points_kernel(PcgDev a) {
   double di[6], tp[3];
 #pragma unroll
   for (int k = 0; k < 6; ++k) di[k] = a.Dinv[6 * (size_t)p + k];
-  pcg_sym3_apply(di, s, tp);
+  sym3_apply(di, s, tp);
   for (int o = beg + lane; o < end; o += G) {
     const double* jx = a.J + kPcgJ * (size_t)o + 14;
     double* v = a.v + 2 * (size_t)o;
@@ -290,7 +255,7 @@ __global__ __launch_bounds__(256) void pcg_backsub_kernel(BaDev d, PcgDev a) {
   for (int k = 0; k < 6; ++k) di[k] = a.Dinv[6 * (size_t)p + k];
 #pragma unroll
   for (int k = 0; k < 3; ++k) g[k] = a.ex[3 * (size_t)p + k] - s[k];
-  pcg_sym3_apply(di, g, dx);
+  sym3_apply(di, g, dx);
   d.px[p] += dx[0];
   d.py[p] += dx[1];
   d.pz[p] += dx[2];
@@ -304,7 +269,7 @@ __global__ __launch_bounds__(256) void pcg_blocks_kernel(PcgDev a) {
   if (row >= a.rows) return;
   const int cam = a.row_cam[row];
   if (cam < 0 || !a.freec[cam]) return;
-  const int e = a.cam_ptr[cam] + (row - pcg_first_row(a, cam)) * kPcgSlice + lane;
+  const int e = a.cam_ptr[cam] + (row - (int)cam_slice_first_row(a.cam_ptr[cam], cam)) * kCamSlice + lane;
   double acc[kPcgBlockSums];
 #pragma unroll
   for (int k = 0; k < kPcgBlockSums; ++k) acc[k] = 0.0;
@@ -322,7 +287,7 @@ __global__ __launch_bounds__(256) void pcg_blocks_kernel(PcgDev a) {
     for (int i = 0; i < 7; ++i) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) W[i][k] = j[i] * j[14 + k] + j[7 + i] * j[17 + k];
-      pcg_sym3_apply(di, W[i], Yw[i]);
+      sym3_apply(di, W[i], Yw[i]);
     }
     int k = 0;
 #pragma unroll
@@ -357,9 +322,9 @@ __global__ __launch_bounds__(64) void pcg_blocks_finish_kernel(PcgDev a) {
     if (tid < 7) a.b[7 * (size_t)cam + tid] = 0.0;
     return;
   }
-  const int n = a.cam_ptr[cam + 1] - a.cam_ptr[cam], ns = (n + kPcgSlice - 1) / kPcgSlice;
+  const int n = a.cam_ptr[cam + 1] - a.cam_ptr[cam], ns = cam_slice_count(n);
   if (tid < kPcgBlockSums) {
-    const double* part = a.ws + kPcgBlockSums * (size_t)pcg_first_row(a, cam) + tid;
+    const double* part = a.ws + kPcgBlockSums * cam_slice_first_row(a.cam_ptr[cam], cam) + tid;
     double t = 0.0;
     for (int s = 0; s < ns; ++s) t += part[(size_t)s * kPcgBlockSums];
     sums[tid] = t;
@@ -409,7 +374,7 @@ __global__ __launch_bounds__(256) void pcg_matvec_slices_kernel(PcgDev a) {
   if (row >= a.rows) return;
   const int cam = a.row_cam[row];
   if (cam < 0 || !a.freec[cam]) return;
-  const int e = a.cam_ptr[cam] + (row - pcg_first_row(a, cam)) * kPcgSlice + lane;
+  const int e = a.cam_ptr[cam] + (row - (int)cam_slice_first_row(a.cam_ptr[cam], cam)) * kCamSlice + lane;
   double acc[7] = {0, 0, 0, 0, 0, 0, 0};
   if (e < a.cam_ptr[cam + 1]) {
     const int o = a.cam_obs[e];
@@ -488,8 +453,8 @@ __global__ __launch_bounds__(kPcgVecThreads) void pcg_update_kernel(PcgDev a) {
   for (int c0 = 0; c0 < a.V; c0 += kPcgVecThreads / 8) {
     const int c = c0 + (threadIdx.x >> 3);
     if (c >= a.V || k >= 7 || !a.freec[c]) continue;
-    const int ns = (a.cam_ptr[c + 1] - a.cam_ptr[c] + kPcgSlice - 1) / kPcgSlice;
-    const double* wsp = a.ws + kPcgBlockSums * (size_t)pcg_first_row(a, c) + k;
+    const int ns = cam_slice_count(a.cam_ptr[c + 1] - a.cam_ptr[c]);
+    const double* wsp = a.ws + kPcgBlockSums * cam_slice_first_row(a.cam_ptr[c], c) + k;
     const size_t i = 7 * (size_t)c + k;
     const double pk = a.pv[i];
     double q = a.lambda * pk;
@@ -561,11 +526,8 @@ __global__ void pcg_update_cams_kernel(BaDev d, int cur, PcgDev a) {
 // ---------------------------------------------------------------------------------------------
 // `group` = 0: the narrowest width that gives every observation of a mean track a lane
 static int pcg_pick_group(int n_pts, long long M) {
-  static const int widths[6] = {1, 4, 8, 16, 32, 64};
   const long long mean = n_pts > 0 ? (M + n_pts - 1) / n_pts : 1;
-  int i = 0;
-  while (i < 5 && widths[i] < mean) ++i;
-  return widths[i];
+  return kGroupWidths[narrowest_group([&](int w) { return w >= mean; })];
 }
 
 struct PcgWork {
@@ -575,13 +537,15 @@ struct PcgWork {
   DevBuf<PcgState> st;
 };
 
-template <int LOSS>
 static void pcg_launch_linearize(sfm_ba_problem* p, const PcgDev& a, int g, int quirks) {
-  const LossArg<LOSS> la = loss_arg<LOSS>(p);
-  dispatch_group<1>(g, [&](auto G) {
-    constexpr int kG = decltype(G)::value;
-    const long long threads = (long long)a.N * kG;
-    pcg_linearize_kernel<kG, LOSS><<<(unsigned)((threads + 255) / 256), 256, 0, p->stream>>>(p->dev, p->cur, a, quirks, la);
+  dispatch_loss(p->loss_kind, [&](auto L) {
+    constexpr int LOSS = decltype(L)::value;
+    const LossArg<LOSS> la = loss_arg<LOSS>(p);
+    dispatch_group<1>(g, [&](auto G) {
+      constexpr int kG = decltype(G)::value;
+      const long long threads = (long long)a.N * kG;
+      pcg_linearize_kernel<kG, LOSS><<<(unsigned)((threads + 255) / 256), 256, 0, p->stream>>>(p->dev, p->cur, a, quirks, la);
+    });
   });
 }
 
@@ -608,10 +572,7 @@ using namespace sfm;
 extern "C" {
 
 int sfm_ba_pcg_times(sfm_ba_problem* p, double* ms) {
-  if (p == nullptr || p->magic != kBaMagic) {
-    set_error("invalid bundle-adjustment problem handle");
-    return SFM_E_HANDLE;
-  }
+  SFM_TRY(ba_check_handle(p));
   if (ms == nullptr) { set_error("sfm_ba_pcg_times: ms is null"); return SFM_E_SHAPE; }
   for (int k = 0; k < 5; ++k) ms[k] = p->pcg_ms[k];
   return SFM_OK;
@@ -620,19 +581,13 @@ int sfm_ba_pcg_times(sfm_ba_problem* p, double* ms) {
 int sfm_ba_iterate_pcg(sfm_ba_problem* p, double lambda, int iters, int quirks, const unsigned char* cam_mask, double cg_tol,
                        int cg_max_iters, int group, int* iters_done, double* cost, int* cg_iters, double* cg_rel, int* cg_status,
                        int* bad_camera) {
-  if (p == nullptr || p->magic != kBaMagic) {
-    set_error("invalid bundle-adjustment problem handle");
-    return SFM_E_HANDLE;
-  }
+  SFM_TRY(ba_check_handle(p));
   if (iters < 0) { set_error("sfm_ba_iterate_pcg: iters < 0"); return SFM_E_SHAPE; }
   if (!(lambda >= 0) || !std::isfinite(lambda)) { set_error("sfm_ba_iterate_pcg: lambda must be finite and >= 0"); return SFM_E_SHAPE; }
   if (!(cg_tol > 0 && cg_tol < 1)) { set_error("sfm_ba_iterate_pcg: cg_tol must lie in (0, 1)"); return SFM_E_SHAPE; }
   if (cg_max_iters < 0) { set_error("sfm_ba_iterate_pcg: cg_max_iters < 0"); return SFM_E_SHAPE; }
   SFM_TRY(group_width_check("sfm_ba_iterate_pcg", group));
-  if (p->comm) {
-    set_error("sfm_ba_iterate_pcg: not with a communicator attached (the points are sharded; the replicas would diverge)");
-    return SFM_E_SHAPE;
-  }
+  SFM_TRY(ba_refuse_comm(p, "sfm_ba_iterate_pcg", "the points are sharded; the replicas would diverge"));
   const auto wall0 = std::chrono::steady_clock::now();
   if (iters_done) *iters_done = 0;
   if (iters == 0) return SFM_OK;
@@ -640,23 +595,9 @@ int sfm_ba_iterate_pcg(sfm_ba_problem* p, double lambda, int iters, int quirks, 
   const int V = d.V, N = d.N;
   SFM_TRY(ba_flush(p));                                  // a deferred back substitution still owes the points its update
   hipStream_t s = p->stream;
-  if (!p->prep_valid) SFM_TRY(ba_enqueue_prep(p));       // the expanded cameras the linearisation reads
-  {
-    int st[2] = {0, 0};
-    SFM_HIP(hipMemcpyAsync(st, d.status, sizeof(st), hipMemcpyDeviceToHost, s));
-    SFM_TRY(stream_sync(s));
-    if (st[0] != SFM_OK) {
-      set_error("sfm_ba_iterate_pcg: camera %d is invalid (status %d)", st[1], st[0]);
-      return st[0];
-    }
-  }
+  SFM_TRY(ba_prepared_cameras(p, "sfm_ba_iterate_pcg"));
   int v_free = 0, first_free = -1;
-  std::vector<unsigned char> h_free((size_t)std::max(V, 1), 1);
-  for (int c = 0; c < V; ++c) {
-    h_free[c] = (cam_mask == nullptr || cam_mask[c] != 0) ? 1 : 0;
-    v_free += h_free[c];
-    if (h_free[c] && first_free < 0) first_free = c;
-  }
+  ba_free_cameras(cam_mask, V, &v_free, &first_free);
   const int max_cg = cg_max_iters > 0 ? cg_max_iters : std::min(7 * v_free, 1000);
   for (int k = 0; k < 5; ++k) p->pcg_ms[k] = 0.f;
   p->pcg_held_points = 0;
@@ -677,9 +618,11 @@ int sfm_ba_iterate_pcg(sfm_ba_problem* p, double lambda, int iters, int quirks, 
   }
   SFM_TRY(ba_cam_list_ensure(p));
   const size_t n = (size_t)N, m = (size_t)d.M, nv = (size_t)V;
-  const int rows = (int)(d.M / kPcgSlice) + V + 1;
+  const int rows = (int)cam_slice_rows(d.M, V);
   const int g = group ? group : pcg_pick_group(N, d.M);
   PcgWork w;
+  std::vector<unsigned char> h_free(nv, 1);              // the kernels' flags are 0 / 1 whatever the mask's non-zero values
+  for (int c = 0; cam_mask != nullptr && c < V; ++c) h_free[c] = cam_mask[c] != 0;
   SFM_TRY(w.freec.upload(h_free.data(), nv, s));
   p->upload_bytes += V;
   SFM_TRY(w.row_cam.alloc((size_t)rows, s));
@@ -707,41 +650,27 @@ int sfm_ba_iterate_pcg(sfm_ba_problem* p, double lambda, int iters, int quirks, 
   pcg_rows_kernel<<<(V + 255) / 256, 256, 0, s>>>(a);
   SFM_HIP(hipGetLastError());
   // SFM_OPT_TIMING (any bit): hipEvents around the four parts of every outer iteration, read back by sfm_ba_pcg_times
-  const bool timed = p->timing != 0;
-  struct EvList {
-    std::vector<hipEvent_t> e;
-    ~EvList() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
-  } ev;
-  auto mark = [&]() -> int {
-    if (!timed) return SFM_OK;
-    hipEvent_t x;
-    SFM_HIP(hipEventCreate(&x));
-    ev.e.push_back(x);
-    SFM_HIP(hipEventRecord(x, s));
-    return SFM_OK;
-  };
+  PhaseEvents ev(p->timing != 0);
   const unsigned row_grid = (unsigned)((rows + 3) / 4);
   const int cur = p->cur;
   std::vector<int> h_cg((size_t)iters, 0), h_status((size_t)iters, 0);
   std::vector<double> h_rel((size_t)iters, 0.0);
   int done_iters = 0, ret = SFM_OK, bad_cam = -1, held_pts = 0;
   for (int it = 0; it < iters; ++it) {
-    SFM_TRY(mark());
+    SFM_TRY(ev.mark(s));
     pcg_reset_kernel<<<1, 1, 0, s>>>(a, cg_tol * cg_tol, max_cg);
-    switch (p->loss_kind) {
-      case SFM_LOSS_HUBER: pcg_launch_linearize<SFM_LOSS_HUBER>(p, a, g, quirks); break;
-      case SFM_LOSS_CAUCHY: pcg_launch_linearize<SFM_LOSS_CAUCHY>(p, a, g, quirks); break;
-      default: pcg_launch_linearize<SFM_LOSS_NONE>(p, a, g, quirks); break;
-    }
-    pcg_cost_kernel<<<1, 256, 0, s>>>(N, a.cost_pt, w.cost.p + it);
-    SFM_TRY(mark());
+    pcg_launch_linearize(p, a, g, quirks);
+    ba_point_cost_reduce_kernel<<<1, 256, 0, s>>>(N, a.cost_pt, nullptr, w.cost.p + it);      // (out[0] only: out[1] is the next iteration's)
+    SFM_TRY(ev.mark(s));
     pcg_blocks_kernel<<<row_grid, 256, 0, s>>>(a);
     pcg_blocks_finish_kernel<<<V, 64, 0, s>>>(a);
     pcg_init_kernel<<<1, kPcgVecThreads, 0, s>>>(a);
     SFM_HIP(hipGetLastError());
-    SFM_TRY(mark());
+    SFM_TRY(ev.mark(s));
     PcgState hs = {};
-    int cam_st[2] = {0, 0};
+    int cam_ret = SFM_OK;
+    char when[48];
+    std::snprintf(when, sizeof(when), " after iteration %d", it);
     for (;;) {
       for (int k = 0; k < kPcgChunk; ++k) {
         pcg_launch_matvec_points(a, g, s);
@@ -750,34 +679,32 @@ int sfm_ba_iterate_pcg(sfm_ba_problem* p, double lambda, int iters, int quirks, 
       }
       SFM_HIP(hipGetLastError());
       SFM_HIP(hipMemcpyAsync(&hs, a.st, sizeof(hs), hipMemcpyDeviceToHost, s));
-      SFM_HIP(hipMemcpyAsync(cam_st, d.status, sizeof(cam_st), hipMemcpyDeviceToHost, s));
-      SFM_TRY(stream_sync(s));
-      if (hs.done || cam_st[0] != SFM_OK) break;
+      cam_ret = ba_sync_cam_status(p, "sfm_ba_iterate_pcg", when);      // (the previous update's cameras)
+      if (hs.done || cam_ret != SFM_OK) break;
     }
-    SFM_TRY(mark());
-    if (cam_st[0] != SFM_OK) {                           // the previous update produced a camera that fails its checks
-      set_error("sfm_ba_iterate_pcg: camera %d is invalid after iteration %d (status %d)", cam_st[1], it, cam_st[0]);
-      ret = cam_st[0];
-      SFM_TRY(mark());
+    SFM_TRY(ev.mark(s));
+    if (cam_ret != SFM_OK) {                             // the previous update produced a camera that fails its checks
+      ret = cam_ret;
+      SFM_TRY(ev.mark(s));
       break;
     }
     if (hs.status == kPcgSingular) {
       bad_cam = hs.bad_cam;
       ret = SFM_E_SINGULAR;
-      SFM_TRY(mark());
+      SFM_TRY(ev.mark(s));
       break;
     }
     held_pts = hs.bad_pts;
     h_cg[it] = hs.iters; h_rel[it] = hs.rel; h_status[it] = hs.status;
     done_iters = it + 1;
     if (hs.status == SFM_PCG_BREAKDOWN) {                // nothing of this outer iteration is applied
-      SFM_TRY(mark());
+      SFM_TRY(ev.mark(s));
       break;
     }
     pcg_launch_backsub(d, a, g, s);
     pcg_update_cams_kernel<<<(V + 63) / 64, 64, 0, s>>>(d, cur, a);
     SFM_HIP(hipGetLastError());
-    SFM_TRY(mark());
+    SFM_TRY(ev.mark(s));
   }
   if (ret == SFM_E_SINGULAR) {
     SFM_HIP(hipMemcpyAsync(d.cams, w.save_cams.p, sizeof(double) * 7 * nv, hipMemcpyDeviceToDevice, s));
@@ -790,18 +717,10 @@ int sfm_ba_iterate_pcg(sfm_ba_problem* p, double lambda, int iters, int quirks, 
     set_error("sfm_ba_iterate_pcg: the diagonal block of camera %d does not factor (hold it, or use lambda > 0)", bad_cam);
     return SFM_E_SINGULAR;
   }
-  // new cameras and points start a new cost history and need a new expansion, as after sfm_ba_refine_cameras
-  SFM_HIP(hipMemsetAsync(d.cost, 0, kStatSlots * sizeof(double), s));
-  SFM_HIP(hipMemsetAsync(d.iter_count, 0, sizeof(int), s));
-  p->prep_valid = false;
+  SFM_TRY(ba_state_changed(p));                          // new cameras and points
   if (cost && done_iters > 0) SFM_TRY(w.cost.download(cost, (size_t)done_iters, s));
-  int cam_st[2] = {0, 0};
-  SFM_HIP(hipMemcpyAsync(cam_st, d.status, sizeof(cam_st), hipMemcpyDeviceToHost, s));
-  SFM_TRY(stream_sync(s));
-  if (ret == SFM_OK && cam_st[0] != SFM_OK) {
-    set_error("sfm_ba_iterate_pcg: camera %d is invalid after the last iteration (status %d)", cam_st[1], cam_st[0]);
-    ret = cam_st[0];
-  }
+  if (ret == SFM_OK) ret = ba_sync_cam_status(p, "sfm_ba_iterate_pcg", " after the last iteration");
+  else SFM_TRY(stream_sync(s));                          // (its message stands)
   for (int it = 0; it < done_iters; ++it) {
     if (cg_iters) cg_iters[it] = h_cg[it];
     if (cg_rel) cg_rel[it] = h_rel[it];
@@ -809,14 +728,8 @@ int sfm_ba_iterate_pcg(sfm_ba_problem* p, double lambda, int iters, int quirks, 
   }
   if (iters_done) *iters_done = done_iters;
   p->pcg_held_points = held_pts;
-  if (timed) {
-    for (size_t k = 0; k + 4 < ev.e.size(); k += 5) {
-      for (int q = 0; q < 4; ++q) {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, ev.e[k + q], ev.e[k + q + 1]) == hipSuccess) p->pcg_ms[q] += t;
-      }
-    }
-  }
+  for (int k = 0; k + 4 < ev.marks(); k += 5)             // five marks per outer iteration
+    for (int q = 0; q < 4; ++q) p->pcg_ms[q] += ev.elapsed_ms(k + q);
   p->pcg_ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - wall0).count();
   return ret;
 }

@@ -253,19 +253,13 @@ int ba_screen_run(sfm_ba_problem* p, const char* who, double max_err2, double co
   ba_cull_scan_kernel<<<1, kScanBlock, 0, s>>>(d.N, d.pt_ptr, w.keep.p, w.new_ptr.p, w.summary.p);
   SFM_HIP(hipGetLastError());
   unsigned long long sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int st[2] = {0, 0};
   SFM_HIP(hipMemcpyAsync(sum, w.summary.p, sizeof(sum), hipMemcpyDeviceToHost, s));
-  SFM_HIP(hipMemcpyAsync(st, d.status, sizeof(st), hipMemcpyDeviceToHost, s));
   if (err2) SFM_TRY(w.err2.download(err2, m, s));
   if (depth) SFM_TRY(w.depth.download(depth, m, s));
   if (obs_flags) SFM_TRY(w.flags.download(obs_flags, m, s));
   if (min_cos) SFM_TRY(w.min_cos.download(min_cos, n, s));
   if (pt_flags) SFM_TRY(w.pt_flags.download(pt_flags, n, s));
-  SFM_TRY(stream_sync(s));
-  if (st[0] != SFM_OK) {
-    set_error("%s: camera %d is invalid (status %d)", who, st[1], st[0]);
-    return st[0];
-  }
+  SFM_TRY(ba_sync_cam_status(p, who, ""));
   if (summary) for (int k = 0; k < 8; ++k) summary[k] = (int64_t)sum[k];
   w.kept = (long long)sum[1];
   return SFM_OK;
@@ -288,10 +282,7 @@ extern "C" {
 
 int sfm_ba_screen(sfm_ba_problem* p, double max_err2, double cos_min_angle, int min_obs, int group, const double* cam_scale,
                   double* err2, double* depth, unsigned char* obs_flags, double* min_cos, int* pt_flags, int64_t* summary) {
-  if (p == nullptr || p->magic != kBaMagic) {
-    set_error("invalid bundle-adjustment problem handle");
-    return SFM_E_HANDLE;
-  }
+  SFM_TRY(ba_check_handle(p));
   ScreenWork w;
   return ba_screen_run(p, "sfm_ba_screen", max_err2, cos_min_angle, min_obs, group, cam_scale, err2, depth, obs_flags,
                        min_cos, pt_flags, summary, w);

@@ -171,6 +171,21 @@ inline int group_width_check(const char* who, int g) {
   return SFM_E_SHAPE;
 }
 
+// What `group` = 0 picks from: index of the narrowest width that satisfies `pred` (the widest if none does), and from
+// there wider while the call would leave the device short of waves (two per SIMD) and the next width is within `cap`.
+constexpr int kGroupWidths[6] = {1, 4, 8, 16, 32, 64};
+template <class Pred>
+inline int narrowest_group(Pred&& pred) {
+  int i = 0;
+  while (i < 5 && !pred(kGroupWidths[i])) ++i;
+  return i;
+}
+inline int widen_for_waves(int i, int n_pts, int cap) {
+  const long long want_waves = 2LL * 4 * ctx().num_cus;
+  while (i < 5 && (long long)n_pts * kGroupWidths[i] / 64 < want_waves && kGroupWidths[i + 1] <= cap) ++i;
+  return i;
+}
+
 template <int MinG, class F>
 inline void dispatch_group(int g, F&& f) {
   if constexpr (MinG <= 1) {

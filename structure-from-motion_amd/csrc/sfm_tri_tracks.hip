@@ -273,12 +273,8 @@ static void launch_tracks_g(const TrackArgs& a, int nc, hipStream_t s) {
 // two waves and the wider group is still no wider than the longest track.
 static int tracks_pick_group(int n_pts, long long M, int max_track) {
   (void)M;
-  static const int widths[6] = {1, 4, 8, 16, 32, 64};
-  int i = 0;
-  while (i < 5 && 6 * widths[i] < max_track) ++i;
-  const long long want_waves = 2LL * 4 * ctx().num_cus;
-  while (i < 5 && (long long)n_pts * widths[i] / 64 < want_waves && widths[i + 1] <= max_track) ++i;
-  return widths[i];
+  const int i = narrowest_group([&](int w) { return 6 * w >= max_track; });
+  return kGroupWidths[widen_for_waves(i, n_pts, max_track)];
 }
 
 // Enqueue the requested passes on s.  The CSR has been validated; max_track is its longest track.
@@ -412,10 +408,7 @@ int sfm_tri_tracks(int n_pts, int n_views, int64_t M, const int* pt_ptr, const i
 }
 
 int sfm_ba_refine_points(sfm_ba_problem* p, int mode, double lambda, int iters, int group, double* cost, int* status) {
-  if (p == nullptr || p->magic != kBaMagic) {
-    set_error("invalid bundle-adjustment problem handle");
-    return SFM_E_HANDLE;
-  }
+  SFM_TRY(ba_check_handle(p));
   BaDev& d = p->dev;
   SFM_TRY(tracks_check_args("sfm_ba_refine_points", d.N, d.V > 0 ? d.V : 1, d.M, mode, iters, group));
   SFM_TRY(ba_flush(p));                                  // a deferred back substitution still owes the points its update
@@ -438,19 +431,10 @@ int sfm_ba_refine_points(sfm_ba_problem* p, int mode, double lambda, int iters, 
   a.lambda = lambda; a.iters = iters;
   a.cost = cost ? dC.p : nullptr; a.status = status ? dSt.p : nullptr;
   SFM_TRY(tracks_enqueue(a, mode, group, d.M, p->max_track, s));
-  // new points start a new cost history, as sfm_ba_set_points does
-  SFM_HIP(hipMemsetAsync(d.cost, 0, kStatSlots * sizeof(double), s));
-  SFM_HIP(hipMemsetAsync(d.iter_count, 0, sizeof(int), s));
-  int st[2] = {0, 0};
-  SFM_HIP(hipMemcpyAsync(st, d.status, sizeof(st), hipMemcpyDeviceToHost, s));
+  SFM_TRY(ba_reset_stats(p));                            // new points, as after sfm_ba_set_points
   if (cost) SFM_TRY(dC.download(cost, 2 * (size_t)d.N, s));
   if (status) SFM_TRY(dSt.download(status, (size_t)d.N, s));
-  SFM_TRY(stream_sync(s));
-  if (st[0] != SFM_OK) {
-    set_error("sfm_ba_refine_points: camera %d is invalid (status %d)", st[1], st[0]);
-    return st[0];
-  }
-  return SFM_OK;
+  return ba_sync_cam_status(p, "sfm_ba_refine_points", "");
 }
 
 }  // extern "C"

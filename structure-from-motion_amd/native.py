@@ -408,6 +408,27 @@ def triangulate(projs, uv, lam, iters):
     return out
 
 
+def _check_group(group):
+    """``group`` as an int, or ValueError: one of TRACK_GROUPS, and not a bool."""
+    if isinstance(group, bool) or group not in TRACK_GROUPS:
+        raise ValueError("group must be one of %s, got %r" % (TRACK_GROUPS, group))
+    return int(group)
+
+
+def _cam_mask(mask, n_cams):
+    """A camera mask as a contiguous uint8 (n_cams,) array of 0 / 1 (None stays None), or ValueError."""
+    if mask is None:
+        return None
+    mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).ravel()
+    if mask.shape[0] != int(n_cams):
+        raise ValueError("mask must have one entry per camera (%d), got %d" % (n_cams, mask.shape[0]))
+    return mask
+
+
+def _u8ptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if a is not None else None
+
+
 def _tracks_mode_group(mode, iters, group):
     mode, iters, group = int(mode), int(iters), int(group)
     if mode not in (TRACKS_LINEAR, TRACKS_NONLINEAR, TRACKS_LINEAR | TRACKS_NONLINEAR):
@@ -454,15 +475,14 @@ def check_screen(n_cams, max_err2, cos_min_angle, min_obs, cam_scale, group=0):
         raise ValueError("cos_min_angle must be >= -1 (>= 1 switches the test off), got %r" % cos_min_angle)
     if int(min_obs) != min_obs or min_obs < 0:
         raise ValueError("min_obs must be an integer >= 0, got %r" % (min_obs,))
-    if int(group) not in TRACK_GROUPS:
-        raise ValueError("group must be one of %s, got %r" % (TRACK_GROUPS, group))
+    group = _check_group(group)
     if cam_scale is not None:
         cam_scale = f64(cam_scale)
         if cam_scale.shape != (int(n_cams),):
             raise ValueError("cam_scale must be (n_cams,) with n_cams = %d, got %s" % (n_cams, cam_scale.shape))
         if not np.all(np.isfinite(cam_scale)):
             raise ValueError("cam_scale must be finite")
-    return max_err2, cos_min_angle, int(min_obs), cam_scale, int(group)
+    return max_err2, cos_min_angle, int(min_obs), cam_scale, group
 
 
 def check_loss(kind, delta):
@@ -496,13 +516,7 @@ def check_pcg(n_cams, lam, iters, mask=None, tol=1e-10, max_cg=0, group=0):
         raise ValueError("tol must lie in (0, 1), got %r" % tol)
     if isinstance(max_cg, bool) or int(max_cg) != max_cg or max_cg < 0:
         raise ValueError("max_cg must be an integer >= 0 (0: min(7 V_free, 1000)), got %r" % (max_cg,))
-    if isinstance(group, bool) or group not in TRACK_GROUPS:
-        raise ValueError("group must be one of %s, got %r" % (TRACK_GROUPS, group))
-    if mask is not None:
-        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).ravel()
-        if mask.shape[0] != int(n_cams):
-            raise ValueError("mask must have one entry per camera (%d), got %d" % (n_cams, mask.shape[0]))
-    return lam, int(iters), mask, tol, int(max_cg), int(group)
+    return lam, int(iters), _cam_mask(mask, n_cams), tol, int(max_cg), _check_group(group)
 
 
 def tri_tracks(pt_ptr, cam_idx, uv, projs, X_init=None, mode=TRACKS_NONLINEAR, lam=0.5, iters=100, group=0):
@@ -976,14 +990,11 @@ class BaProblem:
         a zero entry are held (None: every camera moves).  Returns ``(cost (2, V) or None, status (V,) of CAM_* bits or
         None)`` as ``want_cost`` / ``want_status`` ask."""
         v = self.info(INFO_N_CAMS)
-        if mask is not None:
-            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).ravel()
-            if mask.shape[0] != v:
-                raise ValueError("mask must have one entry per camera (%d), got %d" % (v, mask.shape[0]))
+        mask = _cam_mask(mask, v)
         cost = np.zeros((2, v)) if want_cost else None
         status = np.zeros(v, dtype=np.int32) if want_status else None
         check(self._lib.sfm_ba_refine_cameras(self._h, float(lam), int(iters), int(quirks), int(use_loss),
-                                              mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if mask is not None else None,
+                                              _u8ptr(mask),
                                               dptr(cost) if want_cost else None, iptr(status) if want_status else None))
         return cost, status
 
@@ -996,20 +1007,15 @@ class BaProblem:
         positive definite -- then the covariances are None and ``sigma0_sq`` is NaN.  Nothing is scaled by ``sigma0_sq``."""
         from types import SimpleNamespace
         v, n = self.info(INFO_N_CAMS), self.info(INFO_N_PTS)
-        if group not in TRACK_GROUPS:
-            raise ValueError("group must be one of %s, got %r" % (TRACK_GROUPS, group))
-        if mask is not None:
-            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).ravel()
-            if mask.shape[0] != v:
-                raise ValueError("mask must have one entry per camera (%d), got %d" % (v, mask.shape[0]))
+        group, mask = _check_group(group), _cam_mask(mask, v)
         out = SimpleNamespace(cam_cov=np.zeros((v, 7, 7)) if want_cameras else None,
                               pt_cov=np.zeros((n, 6)) if want_points else None,
                               cam_status=np.zeros(v, dtype=np.int32), pt_status=np.zeros(n, dtype=np.int32),
                               sigma0_sq=float("nan"), pivot_camera=None)
         s0 = ctypes.c_double(float("nan"))
         st = self._lib.sfm_ba_covariance(self._h, float(lam), int(quirks), int(bool(use_loss)),
-                                         mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if mask is not None else None,
-                                         int(group), dptr(out.cam_cov) if want_cameras else None,
+                                         _u8ptr(mask),
+                                         group, dptr(out.cam_cov) if want_cameras else None,
                                          dptr(out.pt_cov) if want_points else None, iptr(out.cam_status), iptr(out.pt_status),
                                          ctypes.byref(s0))
         if st == E_SINGULAR:
@@ -1041,7 +1047,7 @@ class BaProblem:
         cg, status = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
         done, bad = ctypes.c_int(0), ctypes.c_int(-1)
         st = self._lib.sfm_ba_iterate_pcg(self._h, lam, iters, int(quirks),
-                                          mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if mask is not None else None,
+                                          _u8ptr(mask),
                                           tol, max_cg, group, ctypes.byref(done), dptr(cost), iptr(cg), dptr(rel), iptr(status),
                                           ctypes.byref(bad))
         if st == E_SINGULAR:
@@ -1069,11 +1075,10 @@ class BaProblem:
         if want_outputs:
             out.err2, out.depth, out.obs_flags = np.zeros(m), np.zeros(m), np.zeros(m, dtype=np.uint8)
             out.min_cos, out.pt_flags = np.ones(n), np.zeros(n, dtype=np.int32)
-        u8 = ctypes.POINTER(ctypes.c_uint8)
         check(getattr(self._lib, name)(self._h, max_err2, cos_min_angle, min_obs, group,
                                          dptr(cam_scale) if cam_scale is not None else None,
                                          dptr(out.err2) if want_outputs else None, dptr(out.depth) if want_outputs else None,
-                                         out.obs_flags.ctypes.data_as(u8) if want_outputs else None,
+                                         _u8ptr(out.obs_flags),
                                          dptr(out.min_cos) if want_outputs else None,
                                          iptr(out.pt_flags) if want_outputs else None, summary.ctypes.data_as(_lp)))
         return out
