@@ -556,6 +556,87 @@ int sfm_ba_iterate_pcg(sfm_ba_problem* p, double lambda, int iters, int quirks,
  * SFM_OPT_TIMING bit was set during the call -- and [4] the whole call by the host's clock (always). */
 int sfm_ba_pcg_times(sfm_ba_problem* p, double* ms /*[5]*/);
 
+/* ---- the cost of the resident scene ----------------------------------------------------------------------------------
+ * *cost = delta^2 sum rho(|b - f|^2 / delta^2) with the handle's loss, the plain sum |b - f|^2 without one, at the current
+ * state, from the prepared cameras the linearisation reads.  Residuals only: no Jacobian is formed or written.
+ * `group` lanes share a point (1, 4, 8, 16, 32, 64; 0 = the width sfm_ba_iterate_pcg picks); lane l adds observations
+ * l, l + group, ... of the track in ascending order, the group is a fixed tree, the points are added in a fixed order: no
+ * floating-point atomic, the bits depend on the scene, the state and `group` only.  The value agrees with the cost
+ * sfm_ba_iterate_pcg reports for the same state to rounding (1e-13 relative), not bit for bit.
+ * Completes a deferred back substitution first and prepares the cameras if they are not; changes nothing else on the
+ * handle (state, cost history, captured graphs): `iterate; cost; iterate` ends in the bits of `iterate; iterate`.  Uploads
+ * nothing.  Runs on the problem's stream; blocking.  A bad group, a null cost or an attached communicator (the points are
+ * sharded: the value would be one rank's share) return SFM_E_SHAPE and launch nothing; a scene without observations costs 0.  `quirks` is accepted for symmetry: no bit of it changes a residual. */
+int sfm_ba_cost(sfm_ba_problem* p, int quirks, int group, double* cost);
+
+/* ---- Levenberg-Marquardt control of the matrix-free bundle adjustment -------------------------------------------------
+ * sfm_ba_iterate_pcg with a damping that adapts, steps that are judged before they stand, and stopping rules: the rule
+ * of Madsen, Nielsen and Tingleff ("Methods for non-linear least squares problems", 2004, algorithm 3.16) with this
+ * project's lambda I damping.  F is always sfm_ba_cost of a state.
+ *   F = cost(state), lambda = lambda0, nu = 2; then at most max_trials trials, each:
+ *   1. one outer iteration of sfm_ba_iterate_pcg at lambda, from the linearisation through the CG loop (same kernels, same
+ *      order, the mask, the handle's loss, the Q2 bit of quirks, cg_tol, cg_max_iters);
+ *   2. grad_inf = max(|rhs|_inf over the free cameras, |ex|_inf over the points) of that linearisation: the gradient with
+ *      the points eliminated, zero exactly where the full gradient is; if gtol > 0 and grad_inf <= gtol: SFM_LM_STOP_GTOL,
+ *      nothing is solved;
+ *   3. cameras, prepared cameras and points are copied aside, and the step is applied as sfm_ba_iterate_pcg applies it
+ *      (back substitution, cams += x, q /= |q|, the prepared camera and its checks);
+ *   4. F_trial = cost(trial state);
+ *      predicted = |r|^2 - |r - J h|^2 of the linearisation (r, J scaled by sqrt(w) with a loss), h = (x on the cameras,
+ *      dx_p on the points) the step as applied before the normalisation, evaluated without a pass over the observations as
+ *        sum_p ex_p^T D_p^-1 ex_p + x.rhs + x.r_cg + lambda (|x|^2 + sum_p |dx_p|^2),   r_cg = rhs - S x of the CG loop;
+ *      step_norm = sqrt(|x|^2 + sum_p |dx_p|^2);  rho = (F - F_trial) / predicted;
+ *   5. accepted iff predicted > 0, F_trial is finite and rho > SFM_LM_MIN_GAIN.
+ *      accepted: the trial state stands; lambda = max(lambda_min, lambda max(1/3, 1 - (2 rho - 1)^3)), nu = 2;
+ *        SFM_LM_STOP_FTOL if ftol > 0 and F - F_trial <= ftol F; else SFM_LM_STOP_XTOL if xtol > 0 and
+ *        step_norm <= xtol (|state| + xtol), |state| the 2-norm of all 7 V + 3 N doubles of the state the trial started
+ *        from; then F = F_trial.
+ *      rejected: cameras, prepared cameras and points are copied back (device to device); lambda *= nu, nu *= 2;
+ *        SFM_LM_STOP_LAMBDA_MAX if lambda > lambda_max.  The next trial linearises anew at the restored state.
+ *   When the trials run out: SFM_LM_STOP_MAX_TRIALS.  A CG breakdown ends the call with SFM_LM_STOP_BREAKDOWN, a free
+ *   camera whose diagonal block does not factor with SFM_LM_STOP_SINGULAR and *bad_camera: nothing of that trial is
+ *   applied, and the call returns SFM_OK.  A trial camera that fails the checks of the iterations ends the call with their
+ *   error code, after the restore.  In every case the state on return is the last accepted one (the entry state if there
+ *   is none), *cost_out its cost, *lambda_out the damping the next trial would have used.
+ * The decision and the sums of steps 2 and 4 are made on the device (lm_sums, lm_decide: a lane's own terms in ascending
+ * order, a fixed tree per wave, the wave totals in order; no floating-point atomic); the host reads one sfm_lm_trial row
+ * and the next lambda per trial and does what it says.  log[i], i < *trials_done, is the row of trial i; a trial that
+ * ended in BREAKDOWN or SINGULAR has no row, one that ended in GTOL has a row with lambda, cost = cost_trial = F and
+ * grad_inf, the rest zero.  A scene without observations has cost 0 and runs no trial.  Determinism: the bits depend on
+ * the scene, the state, the options and `group` only.
+ * Works in buffers of its own and the PCG work buffers; nothing sfm_ba_iterate owns is touched.  Afterwards the handle is
+ * as after sfm_ba_iterate_pcg (the cost history restarts, the prepared cameras are rebuilt).  Only the mask is uploaded.
+ * Runs on the problem's stream; blocking.  Returns SFM_E_SHAPE and launches nothing for: a null opt; lambda_min, lambda0,
+ * lambda_max not finite, not positive or not in that order; a negative or NaN ftol, xtol or gtol; cg_tol outside (0, 1);
+ * cg_max_iters < 0; max_trials < 0; a bad group; an attached communicator.  max_trials = 0 reports the current cost and
+ * does nothing else.  Every output pointer may be NULL. */
+#define SFM_LM_MIN_GAIN 1e-3          /* a trial stands only if it realised more than this share of the predicted decrease */
+#define SFM_LM_STOP_MAX_TRIALS 0
+#define SFM_LM_STOP_FTOL       1
+#define SFM_LM_STOP_XTOL       2
+#define SFM_LM_STOP_GTOL       3
+#define SFM_LM_STOP_LAMBDA_MAX 4
+#define SFM_LM_STOP_BREAKDOWN  5
+#define SFM_LM_STOP_SINGULAR   6
+typedef struct sfm_lm_options {
+  double lambda0, lambda_min, lambda_max;   /* 0 < lambda_min <= lambda0 <= lambda_max, all finite */
+  double ftol, xtol, gtol;                  /* each >= 0; 0 switches that test off */
+  double cg_tol; int cg_max_iters;          /* as sfm_ba_iterate_pcg */
+  int max_trials;                           /* >= 0; linearise-solve-evaluate rounds, accepted or not */
+  int quirks, group;
+} sfm_lm_options;
+typedef struct sfm_lm_trial {
+  double lambda, cost, cost_trial, predicted, rho, step_norm, grad_inf, cg_rel;
+  int cg_iters, cg_status, accepted, reserved;
+} sfm_lm_trial;
+/* lambda0 5, lambda_min 1e-8, lambda_max 1e8, ftol 1e-8, xtol 0, gtol 0, cg_tol 1e-10, cg_max_iters 0, max_trials 50,
+ * quirks SFM_QUIRKS_REFERENCE, group 0; returns sizeof(sfm_lm_options) (0 for a null opt).  Host only. */
+int sfm_lm_options_default(sfm_lm_options* opt);
+int sfm_lm_trial_size(void);                /* sizeof(sfm_lm_trial); host only */
+int sfm_ba_minimize_pcg(sfm_ba_problem* p, const sfm_lm_options* opt, const unsigned char* cam_mask /*host [V] or NULL*/,
+                        sfm_lm_trial* log /*host [max_trials] or NULL*/, int* trials_done, int* accepted_steps,
+                        int* stop_reason, double* lambda_out, double* cost_out, int* bad_camera);
+
 /* ---- screening and culling of the resident scene's observations ----------------------------------------------------
  * Judges every observation of the resident CSR at the current state and every point by what is left of its track.  For
  * observation o of point p in camera c, with s = [R(q)^T | t]_c (X_p, 1) of the prepared cameras the linearisation reads

@@ -27,6 +27,9 @@ INFO_SCHUR_KERNEL, INFO_UPLOAD_BYTES, INFO_N_CAMS, INFO_N_PTS, INFO_N_OBS, INFO_
 INFO_REDUCE_IN_SOLVE = 8
 INFO_PCG_HELD_POINTS = 9
 PCG_CONVERGED, PCG_MAX_ITERS, PCG_BREAKDOWN = 0, 1, 2
+LM_STOP_MAX_TRIALS, LM_STOP_FTOL, LM_STOP_XTOL, LM_STOP_GTOL, LM_STOP_LAMBDA_MAX, LM_STOP_BREAKDOWN, LM_STOP_SINGULAR = 0, 1, 2, 3, 4, 5, 6
+LM_STOP_NAMES = ("max_trials", "ftol", "xtol", "gtol", "lambda_max", "breakdown", "singular")
+LM_MIN_GAIN = 1e-3
 MATCH_L2, MATCH_HAMMING = 0, 1
 MATCH_KNN2, MATCH_NN1, MATCH_MUTUAL = 0, 1, 2
 DESC_U8, DESC_F32 = 0, 1
@@ -63,6 +66,26 @@ class SiftParams(ctypes.Structure):
     _fields_ = [("n_octave_layers", ctypes.c_int), ("contrast_threshold", ctypes.c_double),
                 ("edge_threshold", ctypes.c_double), ("sigma", ctypes.c_double), ("keep_pyramid", ctypes.c_int),
                 ("stream", ctypes.c_void_p)]
+
+
+# sfm_lm_options / sfm_lm_trial of the controlled minimisation (sfm_ba_minimize_pcg)
+class LmOptions(ctypes.Structure):
+    _fields_ = [("lambda0", ctypes.c_double), ("lambda_min", ctypes.c_double), ("lambda_max", ctypes.c_double),
+                ("ftol", ctypes.c_double), ("xtol", ctypes.c_double), ("gtol", ctypes.c_double),
+                ("cg_tol", ctypes.c_double), ("cg_max_iters", ctypes.c_int), ("max_trials", ctypes.c_int),
+                ("quirks", ctypes.c_int), ("group", ctypes.c_int)]
+
+
+class LmTrial(ctypes.Structure):
+    _fields_ = [("lam", ctypes.c_double), ("cost", ctypes.c_double), ("cost_trial", ctypes.c_double),
+                ("predicted", ctypes.c_double), ("rho", ctypes.c_double), ("step_norm", ctypes.c_double),
+                ("grad_inf", ctypes.c_double), ("cg_rel", ctypes.c_double), ("cg_iters", ctypes.c_int),
+                ("cg_status", ctypes.c_int), ("accepted", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+LM_TRIAL_DTYPE = np.dtype([(name, np.float64 if t is ctypes.c_double else np.int32) for name, t in LmTrial._fields_])
+LM_DEFAULTS = dict(lambda0=5.0, lambda_min=1e-8, lambda_max=1e8, ftol=1e-8, xtol=0.0, gtol=0.0, cg_tol=1e-10, cg_max_iters=0,
+                   max_trials=50, quirks=QUIRKS_REFERENCE, group=0)
 
 
 # The one place a C signature is written down on this side: every symbol include/sfm_hip.h declares -> its argument types
@@ -192,6 +215,11 @@ SIGNATURES = {
     "sfm_ba_covariance_times": [vp, _dp],
     "sfm_ba_iterate_pcg": [vp, cd, ci, ci, ctypes.POINTER(ctypes.c_uint8), cd, ci, ci, _ip, _dp, _ip, _dp, _ip, _ip],
     "sfm_ba_pcg_times": [vp, _dp],
+    "sfm_ba_cost": [vp, ci, ci, _dp],
+    "sfm_lm_options_default": [ctypes.POINTER(LmOptions)],
+    "sfm_lm_trial_size": [],
+    "sfm_ba_minimize_pcg": [vp, ctypes.POINTER(LmOptions), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(LmTrial), _ip, _ip, _ip,
+                            _dp, _dp, _ip],
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -517,6 +545,39 @@ def check_pcg(n_cams, lam, iters, mask=None, tol=1e-10, max_cg=0, group=0):
     if isinstance(max_cg, bool) or int(max_cg) != max_cg or max_cg < 0:
         raise ValueError("max_cg must be an integer >= 0 (0: min(7 V_free, 1000)), got %r" % (max_cg,))
     return lam, int(iters), _cam_mask(mask, n_cams), tol, int(max_cg), _check_group(group)
+
+
+def _count(name, value):
+    try:
+        ok = not isinstance(value, bool) and int(value) == value and value >= 0
+    except (OverflowError, ValueError, TypeError):      # inf, nan, not a number
+        ok = False
+    if not ok:
+        raise ValueError("%s must be an integer >= 0, got %r" % (name, value))
+    return int(value)
+
+
+def check_lm(n_cams, mask=None, **options):
+    """Options of a ``BaProblem.minimize_pcg`` call, without a device: ``(LmOptions, mask)`` -- the defaults of
+    sfm_lm_options_default (``LM_DEFAULTS``) overridden by the keywords, ``mask`` as uint8 (n_cams,) or None -- or
+    ValueError for everything sfm_ba_minimize_pcg refuses."""
+    unknown = sorted(set(options) - set(LM_DEFAULTS))
+    if unknown:
+        raise ValueError("unknown option(s) %s; the options are %s" % (unknown, sorted(LM_DEFAULTS)))
+    o = dict(LM_DEFAULTS)
+    o.update(options)
+    lo, l0, hi = float(o["lambda_min"]), float(o["lambda0"]), float(o["lambda_max"])
+    if not (np.isfinite(lo) and np.isfinite(l0) and np.isfinite(hi) and 0.0 < lo <= l0 <= hi):
+        raise ValueError("0 < lambda_min <= lambda0 <= lambda_max, all finite, is required, got %r, %r, %r" % (lo, l0, hi))
+    for name in ("ftol", "xtol", "gtol"):
+        if not float(o[name]) >= 0.0:
+            raise ValueError("%s must be >= 0 (0 switches the test off), got %r" % (name, o[name]))
+    if not (0.0 < float(o["cg_tol"]) < 1.0):
+        raise ValueError("cg_tol must lie in (0, 1), got %r" % (o["cg_tol"],))
+    out = LmOptions(l0, lo, hi, float(o["ftol"]), float(o["xtol"]), float(o["gtol"]), float(o["cg_tol"]),
+                    _count("cg_max_iters", o["cg_max_iters"]), _count("max_trials", o["max_trials"]), int(o["quirks"]),
+                    _check_group(o["group"]))
+    return out, _cam_mask(mask, n_cams)
 
 
 def tri_tracks(pt_ptr, cam_idx, uv, projs, X_init=None, mode=TRACKS_NONLINEAR, lam=0.5, iters=100, group=0):
@@ -1056,6 +1117,33 @@ class BaProblem:
         k = int(done.value)
         return SimpleNamespace(iters_done=k, cost=cost[:k].copy(), cg_iters=cg[:k].copy(), cg_rel=rel[:k].copy(),
                                cg_status=status[:k].copy())
+
+    def cost(self, quirks=QUIRKS_REFERENCE, group=0):
+        """The minimised cost at the current state, computed on the device from residuals alone (sfm_ba_cost): the robust
+        cost while a loss is set.  Changes nothing on the problem."""
+        out = ctypes.c_double(0.0)
+        check(self._lib.sfm_ba_cost(self._h, int(quirks), _check_group(group), ctypes.byref(out)))
+        return float(out.value)
+
+    def minimize_pcg(self, mask=None, **options):
+        """Levenberg-Marquardt minimisation on the matrix-free route (sfm_ba_minimize_pcg): every trial is one outer
+        iteration of ``iterate_pcg`` whose step stands only if it lowered the cost by more than ``LM_MIN_GAIN`` of what the
+        linear model predicted; the damping adapts and the call stops by itself.  ``options`` are the fields of
+        ``LmOptions`` (``LM_DEFAULTS``); cameras with a zero ``mask`` entry are held.  Returns a namespace: ``trials``,
+        ``accepted``, ``stop`` (``LM_STOP_*``), ``lam`` (the damping the next trial would use), ``cost`` (of the state the
+        problem is left in: the last accepted one), ``bad_camera`` (``LM_STOP_SINGULAR``) and ``log``, a structured array
+        with the fields of ``LmTrial``, one row per trial."""
+        from types import SimpleNamespace
+        opt, mask = check_lm(self.info(INFO_N_CAMS), mask, **options)
+        log = (LmTrial * max(opt.max_trials, 1))()
+        trials, accepted, stop, bad = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(-1)
+        lam, cost = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        check(self._lib.sfm_ba_minimize_pcg(self._h, ctypes.byref(opt), _u8ptr(mask), log, ctypes.byref(trials),
+                                            ctypes.byref(accepted), ctypes.byref(stop), ctypes.byref(lam), ctypes.byref(cost),
+                                            ctypes.byref(bad)))
+        rows = np.frombuffer(log, dtype=LM_TRIAL_DTYPE)[:trials.value].copy()
+        return SimpleNamespace(trials=int(trials.value), accepted=int(accepted.value), stop=int(stop.value), lam=float(lam.value),
+                               cost=float(cost.value), bad_camera=int(bad.value), log=rows)
 
     def pcg_times(self):
         """Milliseconds of the last ``iterate_pcg`` call, summed over its outer iterations: (linearise, camera blocks, CG

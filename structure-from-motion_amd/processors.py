@@ -420,10 +420,15 @@ class HipBaMixin:
     ba_device_tracks = False   # build the observation list from a HipDeviceKeyTracker's device tables (class docstring)
     ba_loss = None             # None | ("huber", px) | ("cauchy", px): robust loss of the resident adjustment (ba_loss_native)
     ba_solver = "dense"        # "dense": sfm_ba_iterate, S formed and factored | "pcg": sfm_ba_iterate_pcg, matrix-free (ba_pcg_native)
-    ba_hold_views = None       # view indices held by the "pcg" solver (their rot / loc are left alone), None: every view moves
+                               # | "lm": sfm_ba_minimize_pcg, the matrix-free route under Levenberg-Marquardt control
+    ba_hold_views = None       # view indices held by the "pcg" / "lm" solvers (their rot / loc are left alone), None: every view moves
     ba_pcg_tol = 1e-10         # relative tolerance of the preconditioned residual
     ba_pcg_max_iters = 0       # CG iteration limit, 0: min(7 free views, 1000)
     ba_pcg_last = None         # the result object of the last iterate_pcg call (iters_done, cost, cg_iters, cg_rel, cg_status)
+    ba_lm_ftol = 1e-8          # "lm": stop when an accepted step lowers the cost by no more than this share of it (0: off)
+    ba_lm_xtol = 0.0           # "lm": stop when an accepted step is no longer than this share of the state's norm (0: off)
+    ba_lm_gtol = 0.0           # "lm": stop when the gradient's largest entry is no larger than this (0: off)
+    ba_lm_last = None          # the result object of the last minimize_pcg call (trials, accepted, stop, lam, cost, log)
 
     def ba_loss_native(self):
         """``ba_loss`` as the native ``(kind, delta)`` or None, without touching the device.  The pixel scale becomes
@@ -455,16 +460,21 @@ class HipBaMixin:
         """``ba_solver`` and ``ba_hold_views`` checked without touching the device or the views: None for the dense solver,
         else a one-element tuple with the mask (uint8 (view_num,), 1 = free; None when nothing is held or ``view_num`` is
         None).  ``ba_hold_views`` with the dense solver (``sfm_ba_iterate`` cannot hold a camera) and ``"pcg"`` without
-        ``ba_resident`` raise ``TypeError``; a bad tolerance, limit or view index raises ``ValueError``."""
-        if self.ba_solver not in ("dense", "pcg"):
-            raise ValueError("ba_solver must be \"dense\" or \"pcg\", got {!r}".format(self.ba_solver))
+        ``ba_resident`` raise ``TypeError``; a bad tolerance, limit or view index raises ``ValueError``.  ``"lm"`` follows the
+        rules of ``"pcg"``, with ``damping_factor`` as the first damping and ``iteration`` as the number of trials
+        (``ba_lm_options``)."""
+        if self.ba_solver not in ("dense", "pcg", "lm"):
+            raise ValueError("ba_solver must be \"dense\", \"pcg\" or \"lm\", got {!r}".format(self.ba_solver))
         if self.ba_solver == "dense":
             if self.ba_hold_views is not None:
-                raise TypeError("ba_hold_views needs ba_solver = \"pcg\" (the dense solver cannot hold a view)")
+                raise TypeError("ba_hold_views needs ba_solver = \"pcg\" or \"lm\" (the dense solver cannot hold a view)")
             return None
         if not self.ba_resident:
-            raise TypeError("ba_solver = \"pcg\" needs ba_resident")
-        native.check_pcg(0, self.damping_factor, self.iteration, None, self.ba_pcg_tol, self.ba_pcg_max_iters)
+            raise TypeError("ba_solver = \"{}\" needs ba_resident".format(self.ba_solver))
+        if self.ba_solver == "lm":
+            native.check_lm(0, None, **self.ba_lm_options())
+        else:
+            native.check_pcg(0, self.damping_factor, self.iteration, None, self.ba_pcg_tol, self.ba_pcg_max_iters)
         if self.ba_hold_views is None or view_num is None:
             return (None,)
         idx = np.asarray(list(self.ba_hold_views), dtype=np.int64).ravel()
@@ -473,6 +483,16 @@ class HipBaMixin:
         mask = np.ones(view_num, dtype=np.uint8)
         mask[idx] = 0
         return (mask,)
+
+    def ba_lm_options(self):
+        """The options ``ba_solver = "lm"`` hands to ``BaProblem.minimize_pcg``: ``damping_factor`` as ``lambda0`` (the
+        default bounds, widened where they would not hold it), ``iteration`` as ``max_trials``, the ``ba_lm_*`` tolerances
+        and the ``ba_pcg_*`` settings of the inner solve."""
+        lam0, dflt = float(self.damping_factor), native.LM_DEFAULTS
+        return dict(lambda0=lam0, lambda_min=min(dflt["lambda_min"], lam0) if lam0 > 0 else dflt["lambda_min"],
+                    lambda_max=max(dflt["lambda_max"], lam0), ftol=self.ba_lm_ftol, xtol=self.ba_lm_xtol, gtol=self.ba_lm_gtol,
+                    cg_tol=self.ba_pcg_tol, cg_max_iters=self.ba_pcg_max_iters, max_trials=self.iteration,
+                    quirks=self.ba_quirk_flags)
 
     def _ba_apply_loss(self, scene, loss):
         """Make the resident problem's loss what ``ba_loss`` asks for (``loss`` = ``ba_loss_native()``): one ``set_loss`` when
@@ -846,6 +866,8 @@ class HipBaMixin:
                 scene.cams_synced = False
                 if pcg is None:
                     prob.iterate(self.damping_factor, self.iteration, self.ba_quirk_flags)
+                elif self.ba_solver == "lm":
+                    self.ba_lm_last = prob.minimize_pcg(pcg[0], **self.ba_lm_options())
                 else:
                     self.ba_pcg_last = prob.iterate_pcg(self.damping_factor, self.iteration, self.ba_quirk_flags, pcg[0],
                                                         self.ba_pcg_tol, self.ba_pcg_max_iters)
