@@ -83,37 +83,48 @@ def _compare(ref, got, angle_tol, desc_tol, margin):
     return amax, dmax, excluded
 
 
-def _pyramid_equal(hip, img):
-    ref = S.detect(img, with_descriptors=False)
-    with hip.SiftResult(img, keep_pyramid=True) as r:
+def _pyramid_equal(hip, img, ref=None, **params):
+    """Every Gaussian and DoG level of the device equals the stand-in's bit for bit, for any sfm_sift_params values.
+    Returns (the device's refined list, the stand-in result, the device's final arrays with the pyramid kept)."""
+    if ref is None:
+        ref = S.detect(img, with_descriptors=False, **params)
+    with hip.SiftResult(img, keep_pyramid=True, **params) as r:
         assert r.n_octaves == len(ref["gauss"])
+        assert r.n_layers == params.get("n_octave_layers", 3)
         for o in range(r.n_octaves):
+            assert len(ref["gauss"][o]) == r.n_layers + 3 and len(ref["dog"][o]) == r.n_layers + 2
             for i, lev in enumerate(ref["gauss"][o]):
                 got = r.level(hip.SIFT_LEVEL_GAUSS, o, i)
                 assert got.shape == lev.shape and np.array_equal(got.view(np.uint32), lev.view(np.uint32)), ("gauss", o, i)
             for i, lev in enumerate(ref["dog"][o]):
                 got = r.level(hip.SIFT_LEVEL_DOG, o, i)
-                assert np.array_equal(got.view(np.uint32), lev.view(np.uint32)), ("dog", o, i)
-        return r.pre(), ref
+                assert got.shape == lev.shape and np.array_equal(got.view(np.uint32), lev.view(np.uint32)), ("dog", o, i)
+        return r.pre(), ref, r.arrays()
 
 
-@pytest.mark.parametrize("shape,channels,seed", [((64, 80), 1, 1), ((45, 67), 1, 2), ((57, 40), 3, 3), ((12, 30), 1, 4)])
-def test_pyramid_bit_exact_synthetic(hip, shape, channels, seed):
-    """Gray and BGR, even and odd sizes, and a 12-row image whose last octaves are narrower than the blur radius."""
-    _pyramid_equal(hip, texture(shape[0], shape[1], seed, channels))
-
-
-def test_pyramid_and_refined_keypoints_bit_exact_on_frame(hip, ref1):
-    pre, _ = _pyramid_equal(hip, frame(1))
-    want = ref1["pre"]
+def _refined_equal(pre, want):
+    """The refined keypoints before orientation: the same count, x, y, response and octave bit for bit (compared as
+    sorted lists), size within 1 float32 ulp (exp2 on both sides)."""
     assert len(pre["x"]) == len(want["x"])
     key = lambda d, size: sorted(zip(d["x"].view(np.uint32).tolist(), d["y"].view(np.uint32).tolist(),
                                      d["response"].view(np.uint32).tolist(), d["octave"].tolist(), size))
     a = key(pre, pre["size"].tolist())
     b = key(want, want["size"].tolist())
     assert [t[:4] for t in a] == [t[:4] for t in b]
-    for (_, _, _, _, sa), (_, _, _, _, sb) in zip(a, b):   # exp2 on both sides: 1 float32 ulp
+    for (_, _, _, _, sa), (_, _, _, _, sb) in zip(a, b):
         assert abs(np.float32(sa) - np.float32(sb)) <= np.spacing(np.float32(sb))
+
+
+@pytest.mark.parametrize("shape,channels,seed", [((64, 80), 1, 1), ((45, 67), 1, 2), ((57, 40), 3, 3), ((12, 30), 1, 4)])
+def test_pyramid_bit_exact_synthetic(hip, shape, channels, seed):
+    """Gray and BGR, even and odd sizes, and a 12-row image whose last octaves are narrower than the blur radius."""
+    pre, ref, _ = _pyramid_equal(hip, texture(shape[0], shape[1], seed, channels))
+    _refined_equal(pre, ref["pre"])
+
+
+def test_pyramid_and_refined_keypoints_bit_exact_on_frame(hip, ref1):
+    pre, _, _ = _pyramid_equal(hip, frame(1))
+    _refined_equal(pre, ref1["pre"])
 
 
 def test_blur_weights_equal_stand_in(hip):
@@ -163,11 +174,10 @@ def test_run_to_run_and_two_streams_identical(hip):
 
 
 def test_tiny_images(hip):
-    for shape in ((1, 1), (1, 40), (8, 8), (16, 16), (16, 9)):
-        img = texture(max(shape[0], 4), max(shape[1], 4), 7)[:shape[0], :shape[1]]
-        ref = S.detect(img)
-        got = hip.sift_detect(img)
-        assert len(got["x"]) == len(ref["x"])
+    """Zero octaves and one-pixel rows, each through the whole per-case comparison of the path tests."""
+    from _sift_cases import TINY_SHAPES, check_image, tiny_image
+    for shape in TINY_SHAPES:
+        check_image(hip, tiny_image(shape), label="tiny %dx%d" % shape)
 
 
 def test_bad_input_raises(hip):
