@@ -435,6 +435,70 @@ int sfm_tri_tracks_auto_group(int n_pts, int64_t M, int max_track);
 int sfm_ba_refine_points(sfm_ba_problem* p, int mode, double lambda, int iters, int group,
                          double* cost /*host [2][N] or NULL*/, int* status /*host [N] or NULL*/);
 
+/* ---- robust triangulation of ragged tracks: pair hypotheses, inlier refit -------------------------------------------
+ * sfm_tri_tracks solves a point by least squares over every observation of its track; one mismatched key then moves the
+ * point.  Here the consistent subset of the track is found first.  The CSR, uv and projs are sfm_tri_tracks'.  W = 1:
+ * with s = P_c (X, 1), err2 = cam_scale[c]^2 ((s0/s2 - u)^2 + (s1/s2 - v)^2) is sfm_ba_screen's quantity, and an
+ * observation is an INLIER of X iff s2 > 0, err2 is finite and err2 <= max_err2.  The rule, per track of n observations:
+ *   1. Hypotheses.  The P = n (n - 1) / 2 pairs (i < j) are numbered in lexicographic order.  The track has
+ *      H = min(P, max_hyp) hypotheses; hypothesis h is pair k = h when P <= max_hyp, else k = floor(h P / max_hyp) in
+ *      64-bit integers.  No random number anywhere.  max_hyp = 0 means 128; its range is 1 .. 65 536.
+ *   2. Its point.  The four rows a = u p3 - p1, a = v p3 - p2 of the two observations, solved inhomogeneously:
+ *      N = sum a[0:3] a[0:3]^T, g = -sum a[3] a[0:3], X = N^-1 g (3x3 adjugate).  A zero or non-finite determinant or a
+ *      non-finite X makes the hypothesis invalid.
+ *   3. Angle gate.  With r = (C - X) / |C - X| of the two generating cameras (C: the camera centre -- of the resident
+ *      cameras, or -M^-1 p4 of projs = [M | p4]) the hypothesis is invalid if r_i . r_j > cos_min_angle;
+ *      cos_min_angle >= 1 switches the gate off.  A non-finite r_i . r_j (X on a centre) is invalid either way.
+ *   4. Pair gate.  The hypothesis is invalid unless both generating observations are inliers of X.
+ *   5. Score, lexicographic: the inlier count over the whole track (an integer); then the smaller r_i . r_j of the
+ *      generating pair (the wider baseline); then the lower h.  None of the three depends on `group`, on the other points
+ *      of the call or on timing: one lane forms X and the cosine from the pair alone and counts in an integer.
+ *   6. Refit.  Step 2's solve over all inliers of the winner, then `iters` steps X -= inv(sum Jx^T Jx + lambda I)
+ *      sum Jx^T (f - b) over those inliers (sfm_tri_tracks' step), the mask fixed.  The refit stands iff every solve
+ *      succeeded, it is finite and its own inlier count over the whole track is at least the winner's; otherwise the
+ *      hypothesis point and its mask stand and SFM_RANSAC_KEPT_HYPOTHESIS is set.  obs_inlier / n_inliers describe the
+ *      point that stands.  A solved point comes out with W = 1.
+ *   7. With SFM_RANSAC_TOO_FEW or SFM_RANSAC_NO_MODEL the point comes out bit for bit as it went in (X_init, the
+ *      resident point, or (0, 0, 0, 1) without X_init), n_inliers = 0, best_hyp = -1, its obs_inlier entries are 0.
+ *   8. summary[6], counted on the device with integer atomics: points solved, points NO_MODEL, points TOO_FEW, points
+ *      KEPT_HYPOTHESIS, observations flagged inlier, observations of solved points flagged outlier.
+ * `group` lanes share a point (1, 4, 8, 16, 32, 64; 0 = sfm_tri_tracks_auto_group): best_hyp and the winner's count do
+ * not depend on it; the refit's sums do, so a point's bits depend on its track, its input, the options and the width.
+ * A NaN or negative max_err2, cos_min_angle < -1 or NaN, max_hyp outside 0 .. 65 536, iters < 0, a negative or NaN
+ * lambda or a bad group return SFM_E_SHAPE and launch nothing.  The CSR is validated as sfm_tri_tracks validates it (one
+ * read-back before anything is written).  cam_scale[n_views], X_init and every output but X_out may be NULL.
+ * The _dev form takes device pointers (d_summary: int64[6] on the device) and runs on hip_stream; d_X_out may equal
+ * d_X_init; it returns when the work is done (its work buffers go back to the pool). */
+#define SFM_RANSAC_TOO_FEW          1   /* the track has fewer than 2 observations */
+#define SFM_RANSAC_NO_MODEL         2   /* no valid hypothesis */
+#define SFM_RANSAC_KEPT_HYPOTHESIS  4   /* the refit did not stand: the point is the winning hypothesis itself */
+#define SFM_RANSAC_SAMPLED          8   /* P > max_hyp: not every pair was a hypothesis (informational) */
+int sfm_tri_tracks_ransac(int n_pts, int n_views, int64_t M, const int* pt_ptr, const int* cam_idx,
+                          const double* uv /*[2][M]*/, const double* projs /*[n_views][3][4]*/,
+                          const double* cam_scale /*[n_views] or NULL*/, double max_err2, double cos_min_angle, int max_hyp,
+                          double lambda, int iters, int group, const double* X_init /*[4][n_pts] or NULL*/,
+                          double* X_out /*[4][n_pts]*/, unsigned char* obs_inlier /*[M] or NULL*/,
+                          int* n_inliers /*[n_pts] or NULL*/, int* best_hyp /*[n_pts] or NULL*/,
+                          int* status /*[n_pts] or NULL*/, int64_t* summary /*[6] or NULL*/);
+int sfm_tri_tracks_ransac_dev(int n_pts, int n_views, int64_t M, const int* d_pt_ptr, const int* d_cam_idx,
+                              const double* d_uv, const double* d_projs, const double* d_cam_scale, double max_err2,
+                              double cos_min_angle, int max_hyp, double lambda, int iters, int group,
+                              const double* d_X_init, double* d_X_out /* may equal d_X_init */,
+                              unsigned char* d_obs_inlier, int* d_n_inliers, int* d_best_hyp, int* d_status,
+                              int64_t* d_summary, void* hip_stream);
+/* The same on the resident scene, in place, following sfm_ba_refine_points: observations and points (W = 1) are the
+ * problem's, projections and centres those of the prepared cameras.  Completes a deferred back substitution first; only
+ * points move (the cost history restarts); cameras, their prepared form, graphs and the structure are untouched.  With a
+ * communicator it is local to the rank's points, as the cull is.  sfm_ba_retriangulate(t) followed by sfm_ba_cull(t)
+ * removes what it flagged.  cam_scale and the outputs are HOST arrays or NULL.  An empty problem returns SFM_OK. */
+int sfm_ba_retriangulate(sfm_ba_problem* p, double max_err2, double cos_min_angle, int max_hyp, double lambda, int iters,
+                         int group, const double* cam_scale /*host [V] or NULL*/, unsigned char* obs_inlier /*host [M]*/,
+                         int* n_inliers /*host [N]*/, int* best_hyp /*host [N]*/, int* status /*host [N]*/,
+                         int64_t* summary /*[6]*/);
+/* Host only: the hypothesis count H of a track of n observations (0 for n < 2 or a max_hyp out of range) and, for
+ * 0 <= h < H, the pair (*i < *j) of hypothesis h. */
+int sfm_tri_ransac_pair(int n, int max_hyp, int h, int* i, int* j);
+
 /* ---- motion-only refinement of the resident scene: every camera from its own observations, the points held ----------
  * The other half of sfm_ba_refine_points.  For every camera c with cam_mask[c] != 0 and at least one observation, `iters`
  * times: r_o = b - f and Jp_o (2x7 with respect to [C, q]) of the camera's observations exactly as one linearisation of the

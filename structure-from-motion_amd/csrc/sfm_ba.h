@@ -324,6 +324,11 @@ int ba_screen_run(sfm_ba_problem* p, const char* who, double max_err2, double co
                   const double* cam_scale, double* err2, double* depth, unsigned char* obs_flags, double* min_cos,
                   int* pt_flags, int64_t* summary, ScreenWork& w);
 int ba_cull_enqueue_scatter(const BaDev& d, const BaDev& e, const ScreenWork& w, hipStream_t s);
+// Ragged tracks (sfm_tri_tracks.hip), for the robust triangulation (sfm_tri_ransac.hip): the CSR check with its one
+// read-back (max_track = the longest track), and [R^T | t] of the prepared cameras as row-major 3x4 projections.
+int tracks_validate(const char* who, int n_pts, int n_views, long long M, const int* d_pt_ptr, const int* d_cam_idx,
+                    int* max_track, hipStream_t s);
+int tracks_enqueue_proj_from_prep(int V, const CamPrep* prep, double* projs, hipStream_t s);
 // What an operation on the resident scene is given (sfm_ba_host.hip; DESIGN.md, "What an operation on the resident scene
 // is given").  `who` names the entry point in the message.
 int ba_check_handle(const sfm_ba_problem* p);

@@ -3,7 +3,7 @@
 // After an adjustment, every observation of the resident CSR is judged at the current state -- reprojection error,
 // depth -- and every point by what is left of its track -- number of surviving observations, widest angle between two
 // of their rays (sfm_hip.h, block "screening").  The residuals are the linearisation's: the projection is
-// [R(q)^T | t] of the prepared cameras, formed with the operations of sfm_tri_tracks.hip's track_project /
+// [R(q)^T | t] of the prepared cameras, formed with the operations of sfm_track_obs.h's track_project /
 // track_residual, so the sum of err2 over a track is sfm_ba_refine_points' cost row 0 of that point.
 //   screen   a group of G lanes owns a point, lane l takes observations l, l + G, ... in track order; one lane
 //            evaluates an observation and writes err2 / depth / flags, the group counts the survivors and takes the

@@ -44,6 +44,12 @@ __global__ void tracks_proj_from_prep_kernel(int V, const CamPrep* __restrict__ 
   projs[i] = k < 3 ? c.R[3 * k + r] : c.t[r];
 }
 
+int tracks_enqueue_proj_from_prep(int V, const CamPrep* prep, double* projs, hipStream_t s) {
+  tracks_proj_from_prep_kernel<<<(12 * V + 255) / 256, 256, 0, s>>>(V, prep, projs);
+  SFM_HIP(hipGetLastError());
+  return SFM_OK;
+}
+
 struct TrackArgs {
   int n_pts, n_views;
   const int* pt_ptr;
@@ -104,53 +110,11 @@ __global__ __launch_bounds__(256) void tri_tracks_linear_kernel(TrackArgs a) {
 // the re-reading instantiations then execute the same operations per observation, so a point's bits do not depend on
 // which of them the longest track of a call selects.
 // ---------------------------------------------------------------------------------------------
-#pragma clang fp contract(off)
+}  // namespace sfm
 
-struct TrackSums { double a00, a10, a11, a20, a21, a22, b0, b1, b2, c; };
+#include "sfm_track_obs.h"      // contraction is off from here on
 
-__device__ __forceinline__ void track_project(const double* P, double x0, double x1, double x2, double x3, double* s) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-    s[r] = __builtin_fma(P[4 * r + 3], x3, __builtin_fma(P[4 * r + 2], x2, __builtin_fma(P[4 * r + 1], x1, P[4 * r] * x0)));
-}
-
-// One observation of the linearisation: tri_nonlinear_kernel's `view` (tri:209-228, 261-269) plus the squared residual.
-// 97 flops (FMA = 2, v_rcp_f64 = 1): projection 21, reciprocal 7, iz^2 1, Jacobian 24, residual 4, sums 36, cost 4.
-__device__ __forceinline__ void track_view(const double* P, double ku, double kv, double x0, double x1, double x2, double x3,
-                                           TrackSums& S) {
-  double s[3], j[6];
-  track_project(P, x0, x1, x2, x3, s);
-  const double iz = rcp_nr(s[2]), iz2 = iz * iz;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    j[c] = __builtin_fma(-s[0], P[8 + c], s[2] * P[c]) * iz2;
-    j[3 + c] = __builtin_fma(-s[1], P[8 + c], s[2] * P[4 + c]) * iz2;
-  }
-  const double eu = __builtin_fma(s[0], iz, -ku);
-  const double ev = __builtin_fma(s[1], iz, -kv);
-  S.a00 = __builtin_fma(j[3], j[3], __builtin_fma(j[0], j[0], S.a00));
-  S.a10 = __builtin_fma(j[4], j[3], __builtin_fma(j[1], j[0], S.a10));
-  S.a11 = __builtin_fma(j[4], j[4], __builtin_fma(j[1], j[1], S.a11));
-  S.a20 = __builtin_fma(j[5], j[3], __builtin_fma(j[2], j[0], S.a20));
-  S.a21 = __builtin_fma(j[5], j[4], __builtin_fma(j[2], j[1], S.a21));
-  S.a22 = __builtin_fma(j[5], j[5], __builtin_fma(j[2], j[2], S.a22));
-  S.b0 = __builtin_fma(j[3], ev, __builtin_fma(j[0], eu, S.b0));
-  S.b1 = __builtin_fma(j[4], ev, __builtin_fma(j[1], eu, S.b1));
-  S.b2 = __builtin_fma(j[5], ev, __builtin_fma(j[2], eu, S.b2));
-  S.c = __builtin_fma(ev, ev, __builtin_fma(eu, eu, S.c));
-}
-
-// The residual alone (the evaluation after the last iteration): the same eu / ev as track_view, and s[2] <= 0.
-__device__ __forceinline__ void track_residual(const double* P, double ku, double kv, double x0, double x1, double x2,
-                                               double x3, double& c, double& behind) {
-  double s[3];
-  track_project(P, x0, x1, x2, x3, s);
-  const double iz = rcp_nr(s[2]);
-  const double eu = __builtin_fma(s[0], iz, -ku);
-  const double ev = __builtin_fma(s[1], iz, -kv);
-  c = __builtin_fma(ev, ev, __builtin_fma(eu, eu, c));
-  if (s[2] <= 0.0) behind += 1.0;
-}
+namespace sfm {
 
 constexpr int kTrkLdsViews = 512;     // projections staged in LDS by the re-reading variant up to here (48 KB)
 
@@ -227,19 +191,8 @@ __global__ __launch_bounds__(256) void tri_tracks_nonlinear_kernel(TrackArgs a) 
       const double a00 = group_sum<G>(S.a00) + a.lambda, a10 = group_sum<G>(S.a10), a11 = group_sum<G>(S.a11) + a.lambda;
       const double a20 = group_sum<G>(S.a20), a21 = group_sum<G>(S.a21), a22 = group_sum<G>(S.a22) + a.lambda;
       const double b0 = group_sum<G>(S.b0), b1 = group_sum<G>(S.b1), b2 = group_sum<G>(S.b2);
-      // symmetric 3x3 inverse by adjugate (np.linalg.inv in the reference, tri:227)
-      const double c00 = a11 * a22 - a21 * a21;
-      const double c10 = a20 * a21 - a10 * a22;
-      const double c20 = a10 * a21 - a20 * a11;
-      const double det = a00 * c00 + a10 * c10 + a20 * c20;
-      const double id = rcp_nr(det);
-      const double c11 = a00 * a22 - a20 * a20;
-      const double c21 = a10 * a20 - a00 * a21;
-      const double c22 = a00 * a11 - a10 * a10;
-      const double d0 = (c00 * b0 + c10 * b1 + c20 * b2) * id;
-      const double d1 = (c10 * b0 + c11 * b1 + c21 * b2) * id;
-      const double d2 = (c20 * b0 + c21 * b1 + c22 * b2) * id;
-      if (det == 0.0 || !isfinite(d0) || !isfinite(d1) || !isfinite(d2)) {      // the same bits on every lane of the group
+      double d0, d1, d2;
+      if (!track_solve3(a00, a10, a11, a20, a21, a22, b0, b1, b2, d0, d1, d2)) {      // the same bits on every lane of the group
         flags |= SFM_TRACK_NONFINITE;
         x0 = in0; x1 = in1; x2 = in2;
         it = a.iters - 1;                  // straight to the evaluation of the point as it came in
@@ -306,8 +259,8 @@ static int tracks_check_args(const char* who, int n_pts, int n_views, long long 
 }
 
 // Validate the CSR on the device (the way ba_structure_kernel does) and wait for the verdict.
-static int tracks_validate(const char* who, int n_pts, int n_views, long long M, const int* d_pt_ptr, const int* d_cam_idx,
-                           int* max_track, hipStream_t s) {
+int tracks_validate(const char* who, int n_pts, int n_views, long long M, const int* d_pt_ptr, const int* d_cam_idx,
+                    int* max_track, hipStream_t s) {
   DevBuf<int> dInfo;
   SFM_TRY(dInfo.alloc(4, s));
   SFM_HIP(hipMemsetAsync(dInfo.p, 0, 4 * sizeof(int), s));
@@ -418,8 +371,7 @@ int sfm_ba_refine_points(sfm_ba_problem* p, int mode, double lambda, int iters, 
   DevBuf<double> dP, dC;
   DevBuf<int> dSt;
   SFM_TRY(dP.alloc(12 * (size_t)d.V, s));
-  tracks_proj_from_prep_kernel<<<(12 * d.V + 255) / 256, 256, 0, s>>>(d.V, d.prep[p->cur], dP.p);
-  SFM_HIP(hipGetLastError());
+  SFM_TRY(tracks_enqueue_proj_from_prep(d.V, d.prep[p->cur], dP.p, s));
   if (cost) SFM_TRY(dC.alloc(2 * (size_t)d.N, s));
   if (status) SFM_TRY(dSt.alloc((size_t)d.N, s));
   TrackArgs a = {};

@@ -45,6 +45,9 @@ TRACK_TOO_FEW, TRACK_NONFINITE, TRACK_BEHIND = 1, 2, 4
 TRACK_GROUPS = (0, 1, 4, 8, 16, 32, 64)
 OBS_HIGH_ERROR, OBS_BEHIND, OBS_NONFINITE, OBS_POINT = 1, 2, 4, 8
 PT_TOO_FEW, PT_LOW_ANGLE, PT_EMPTY = 1, 2, 4
+RANSAC_TOO_FEW, RANSAC_NO_MODEL, RANSAC_KEPT_HYPOTHESIS, RANSAC_SAMPLED = 1, 2, 4, 8
+RANSAC_MAX_HYP, RANSAC_DEFAULT_HYP = 65536, 128
+RANSAC_SUMMARY = ("pts_solved", "pts_no_model", "pts_too_few", "pts_kept_hypothesis", "obs_inlier", "obs_outlier")
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2
 CAM_EMPTY, CAM_NONFINITE, CAM_BEHIND, CAM_HELD = 1, 2, 4, 8
 COV_CAM_HELD, COV_CAM_PIVOT, COV_PT_EMPTY, COV_PT_SINGULAR = 8, 16, 4, 8
@@ -202,6 +205,11 @@ SIGNATURES = {
     "sfm_tri_tracks_dev": [ci, ci, i64, vp, vp, vp, vp, ci, cd, ci, ci, vp, vp, vp, vp, vp],
     "sfm_ba_refine_points": [vp, ci, cd, ci, ci, _dp, _ip],
     "sfm_tri_tracks_auto_group": [ci, i64, ci],
+    "sfm_tri_tracks_ransac": [ci, ci, i64, _ip, _ip, _dp, _dp, _dp, cd, cd, ci, cd, ci, ci, _dp, _dp,
+                              ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
+    "sfm_tri_tracks_ransac_dev": [ci, ci, i64, vp, vp, vp, vp, vp, cd, cd, ci, cd, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp],
+    "sfm_ba_retriangulate": [vp, cd, cd, ci, cd, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
+    "sfm_tri_ransac_pair": [ci, ci, ci, _ip, _ip],
     "sfm_ba_screen": [vp, cd, cd, ci, ci, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _lp],
     "sfm_ba_cull": [vp, cd, cd, ci, ci, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _lp],
     "sfm_ba_set_loss": [vp, ci, cd],
@@ -513,6 +521,31 @@ def check_screen(n_cams, max_err2, cos_min_angle, min_obs, cam_scale, group=0):
     return max_err2, cos_min_angle, int(min_obs), cam_scale, group
 
 
+def check_ransac(n_cams, max_err2, cos_min_angle=1.0, max_hyp=0, lam=0.5, iters=3, cam_scale=None, group=0):
+    """Arguments of a ``tri_tracks_ransac`` / ``BaProblem.retriangulate`` call, without a device: returns
+    ``(max_err2, cos_min_angle, max_hyp, lam, iters, cam_scale, group)`` converted or raises ValueError -- everything
+    sfm_tri_tracks_ransac refuses."""
+    max_err2, cos_min_angle, lam = float(max_err2), float(cos_min_angle), float(lam)
+    if not max_err2 >= 0.0:
+        raise ValueError("max_err2 must be >= 0, got %r" % max_err2)
+    if not cos_min_angle >= -1.0:
+        raise ValueError("cos_min_angle must be >= -1 (>= 1 switches the gate off), got %r" % cos_min_angle)
+    max_hyp = _count("max_hyp", max_hyp)
+    if max_hyp > RANSAC_MAX_HYP:
+        raise ValueError("max_hyp must be in 1 .. %d (0 = %d), got %r" % (RANSAC_MAX_HYP, RANSAC_DEFAULT_HYP, max_hyp))
+    if not lam >= 0.0:
+        raise ValueError("lam must be >= 0, got %r" % lam)
+    iters = _count("iters", iters)
+    group = _check_group(group)
+    if cam_scale is not None:
+        cam_scale = f64(cam_scale)
+        if cam_scale.shape != (int(n_cams),):
+            raise ValueError("cam_scale must be (n_cams,) with n_cams = %d, got %s" % (n_cams, cam_scale.shape))
+        if not np.all(np.isfinite(cam_scale)):
+            raise ValueError("cam_scale must be finite")
+    return max_err2, cos_min_angle, max_hyp, lam, iters, cam_scale, group
+
+
 def check_loss(kind, delta):
     """Arguments of a ``BaProblem.set_loss`` call, without a device: returns ``(kind, delta)`` converted or raises ValueError.
     ``kind`` is ``LOSS_NONE`` / ``LOSS_HUBER`` / ``LOSS_CAUCHY`` or its name; ``delta`` (normalised units) must be finite and
@@ -603,6 +636,49 @@ def tri_tracks_dev(n_pts, n_views, n_obs, d_pt_ptr, d_cam_idx, d_uv, d_projs, mo
     check(load().sfm_tri_tracks_dev(int(n_pts), int(n_views), int(n_obs), _vp(d_pt_ptr), _vp(d_cam_idx), _vp(d_uv), _vp(d_projs),
                                     mode, float(lam), iters, group, _vp(d_x_init), _vp(d_x_out), _vp(d_cost), _vp(d_status),
                                     _vp(stream)))
+
+
+def tri_ransac_pair(n, max_hyp, h):
+    """``(H, i, j)``: the hypothesis count of a track of ``n`` observations and the pair of hypothesis ``h``
+    (sfm_tri_ransac_pair; host only).  ``i = j = -1`` when ``h`` is not in ``0 .. H - 1``."""
+    i, j = ctypes.c_int(-1), ctypes.c_int(-1)
+    count = int(load().sfm_tri_ransac_pair(int(n), int(max_hyp), int(h), ctypes.byref(i), ctypes.byref(j)))
+    return count, int(i.value), int(j.value)
+
+
+def tri_tracks_ransac(pt_ptr, cam_idx, uv, projs, max_err2, cos_min_angle=1.0, max_hyp=0, lam=0.5, iters=3, cam_scale=None,
+                      X_init=None, group=0):
+    """Robust triangulation of every point from its own track (sfm_tri_tracks_ransac): pair hypotheses scored by their
+    inlier count, then a refit over the winner's inliers.  Arrays as ``tri_tracks``; ``cam_scale`` (V,) multiplies a
+    view's residuals (None: 1).  Returns ``X (4, n), inlier (M,) uint8, n_inliers (n,), best_hyp (n,), status (n,) of
+    RANSAC_* bits, summary (6,) int64`` in the order of ``RANSAC_SUMMARY``."""
+    pt_ptr, cam_idx, uv, projs, x_init, _mode, _iters, _group = check_tracks(
+        pt_ptr, cam_idx, uv, projs, X_init, TRACKS_LINEAR | TRACKS_NONLINEAR, 0, 0)
+    max_err2, cos_min_angle, max_hyp, lam, iters, cam_scale, group = check_ransac(projs.shape[0], max_err2, cos_min_angle, max_hyp,
+                                                                                  lam, iters, cam_scale, group)
+    n_pts, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
+    out = np.zeros((4, n_pts)); inlier = np.zeros(n_obs, dtype=np.uint8)
+    n_in = np.zeros(n_pts, dtype=np.int32); best = np.zeros(n_pts, dtype=np.int32); status = np.zeros(n_pts, dtype=np.int32)
+    summary = np.zeros(6, dtype=np.int64)
+    check(load().sfm_tri_tracks_ransac(n_pts, projs.shape[0], n_obs, iptr(pt_ptr), iptr(cam_idx) if n_obs else None,
+                                       dptr(uv) if n_obs else None, dptr(projs), dptr(cam_scale) if cam_scale is not None else None,
+                                       max_err2, cos_min_angle, max_hyp, lam, iters, group,
+                                       dptr(x_init) if x_init is not None else None, dptr(out), _u8ptr(inlier), iptr(n_in),
+                                       iptr(best), iptr(status), summary.ctypes.data_as(_lp)))
+    return out, inlier, n_in, best, status, summary
+
+
+def tri_tracks_ransac_dev(n_pts, n_views, n_obs, d_pt_ptr, d_cam_idx, d_uv, d_projs, max_err2, cos_min_angle=1.0, max_hyp=0,
+                          lam=0.5, iters=3, group=0, d_cam_scale=0, d_x_init=0, d_x_out=0, d_inlier=0, d_n_inliers=0, d_best_hyp=0,
+                          d_status=0, d_summary=0, stream=0):
+    """``tri_tracks_ransac`` on device pointers and a caller's stream (sfm_tri_tracks_ransac_dev); ``d_x_out`` may equal
+    ``d_x_init``, optional arrays are 0."""
+    max_err2, cos_min_angle, max_hyp, lam, iters, _s, group = check_ransac(n_views, max_err2, cos_min_angle, max_hyp, lam, iters,
+                                                                           None, group)
+    check(load().sfm_tri_tracks_ransac_dev(int(n_pts), int(n_views), int(n_obs), _vp(d_pt_ptr), _vp(d_cam_idx), _vp(d_uv),
+                                           _vp(d_projs), _vp(d_cam_scale), max_err2, cos_min_angle, max_hyp, lam, iters, group,
+                                           _vp(d_x_init), _vp(d_x_out), _vp(d_inlier), _vp(d_n_inliers), _vp(d_best_hyp),
+                                           _vp(d_status), _vp(d_summary), _vp(stream)))
 
 
 def pnp_nonlinear(uv_pix, pts_h, intrinsic, rot0, loc0, lam, iters, quirks=QUIRKS_REFERENCE):
@@ -1044,6 +1120,28 @@ class BaProblem:
         cost = np.zeros((2, n)); status = np.zeros(n, dtype=np.int32)
         check(self._lib.sfm_ba_refine_points(self._h, mode, float(lam), iters, group, dptr(cost), iptr(status)))
         return cost, status
+
+    def retriangulate(self, max_err2, cos_min_angle=1.0, max_hyp=0, lam=0.5, iters=3, cam_scale=None, group=0, want_outputs=True):
+        """Robust re-triangulation of the resident points, cameras held (sfm_ba_retriangulate): every point from the
+        consistent subset of its own track, in place.  Returns a namespace with ``inlier`` (M,) uint8, ``n_inliers`` (N,),
+        ``best_hyp`` (N,), ``status`` (N,) of ``RANSAC_*`` bits and ``summary`` (6,) int64 in the order of
+        ``RANSAC_SUMMARY``; ``want_outputs=False`` downloads nothing and returns None."""
+        from types import SimpleNamespace
+        max_err2, cos_min_angle, max_hyp, lam, iters, cam_scale, group = check_ransac(self.n_cams, max_err2, cos_min_angle,
+                                                                                      max_hyp, lam, iters, cam_scale, group)
+        scale = dptr(cam_scale) if cam_scale is not None else None
+        if not want_outputs:
+            check(self._lib.sfm_ba_retriangulate(self._h, max_err2, cos_min_angle, max_hyp, lam, iters, group, scale,
+                                                 None, None, None, None, None))
+            return None
+        n, m = self.info(INFO_N_PTS), self.info(INFO_N_OBS)
+        out = SimpleNamespace(inlier=np.zeros(m, dtype=np.uint8), n_inliers=np.zeros(n, dtype=np.int32),
+                              best_hyp=np.zeros(n, dtype=np.int32), status=np.zeros(n, dtype=np.int32),
+                              summary=np.zeros(6, dtype=np.int64))
+        check(self._lib.sfm_ba_retriangulate(self._h, max_err2, cos_min_angle, max_hyp, lam, iters, group, scale,
+                                             _u8ptr(out.inlier), iptr(out.n_inliers), iptr(out.best_hyp), iptr(out.status),
+                                             out.summary.ctypes.data_as(_lp)))
+        return out
 
     def refine_cameras(self, lam, iters, quirks=QUIRKS_REFERENCE, use_loss=False, mask=None, want_cost=False, want_status=False):
         """Motion-only refinement of the resident cameras, points held (sfm_ba_refine_cameras): ``iters`` damped steps per

@@ -99,6 +99,27 @@ class HipTriangulationMixin:
         out, _cost, _status = native.tri_tracks(pt_ptr, cam_idx, uv, projs_arr, init_3d_pts, mode, damping_factor, iteration)
         return out
 
+    def triangulate_tracks_robust(self, projs, pt_ptr, cam_idx, uv, max_reproj, min_angle_deg=1.5, max_hyp=128, cam_scale=None,
+                                  init_3d_pts=None, damping_factor=None, iteration=3):
+        """``triangulate_tracks`` for tracks that may hold wrong observations (``native.tri_tracks_ransac``; no reference
+        counterpart): every pair of a track's observations (at most ``max_hyp``, evenly spaced) proposes a point, the
+        proposal with the most observations within ``max_reproj`` wins, and the point is refitted over those.
+        ``max_reproj`` is in the units of ``uv`` times ``cam_scale`` (V,); ``min_angle_deg`` is the smallest angle between
+        the two generating rays (None: no gate).  ``init_3d_pts`` (4, n) is what an unsolved point keeps.  Returns
+        ``(points (4, n), inlier (M,) bool, status (n,) of native.RANSAC_* bits)``."""
+        if not damping_factor:
+            damping_factor = self.damping_factor
+        if not float(max_reproj) >= 0.0:
+            raise ValueError("max_reproj must be >= 0, got {!r}".format(max_reproj))
+        if min_angle_deg is not None and not 0.0 <= float(min_angle_deg) <= 180.0:
+            raise ValueError("min_angle_deg must be in [0, 180] or None, got {!r}".format(min_angle_deg))
+        cos_min_angle = 1.0 if min_angle_deg is None else math.cos(math.radians(float(min_angle_deg)))
+        projs_arr = np.stack([np.asarray(p, dtype=np.float64).reshape(3, 4) for p in projs])
+        out, inlier, _n, _best, status, _summary = native.tri_tracks_ransac(
+            pt_ptr, cam_idx, uv, projs_arr, float(max_reproj) ** 2, cos_min_angle, max_hyp, damping_factor, iteration, cam_scale,
+            init_3d_pts)
+        return out, inlier.astype(bool), status
+
     @staticmethod
     def _pack_views(projs, matched_pairs):
         num_views = len(matched_pairs)
@@ -691,6 +712,33 @@ class HipBaMixin:
         scene.rots_written, scene.locs_written = init_rots, init_locs      # the poses the device cameras were brought up to
         tri_pts[0:3, :] = pts
         return cost, status
+
+    def retriangulate_structure(self, max_reproj_px=4.0, min_angle_deg=1.5, max_hyp=128, iteration=3, damping_factor=None):
+        """Robust re-triangulation of the resident scene (``BaProblem.retriangulate``), after it has been brought up to date
+        exactly as ``refine_structure`` does: every point from the consistent subset of its own track -- the pair of
+        observations whose point has the most observations within ``max_reproj_px`` (rays at least ``min_angle_deg`` apart;
+        at most ``max_hyp`` pairs per track), refitted over those.  Thresholds convert as ``screen_structure``'s.  Writes
+        ``tri_processor.tri_pts[0:3]`` in place, leaves the views and the track tables alone and returns the native report
+        (``inlier``, ``n_inliers``, ``best_hyp``, ``status``, ``summary``; observations in the order of
+        ``prob.structure()``).  A point without a model keeps its coordinates.  Falsy ``damping_factor`` falls back to
+        ``tri_processor``'s.  Needs ``ba_resident``; nothing in ``process()`` calls it."""
+        if self.ba_device_tracks:
+            self._ba_check_device_tracks()
+        if not damping_factor:
+            damping_factor = self.tri_processor.damping_factor
+        if max_reproj_px is None:
+            raise ValueError("retriangulate_structure needs max_reproj_px")
+        native.check_ransac(0, 0.0, 1.0, max_hyp, damping_factor, iteration)      # before anything reaches the device
+        scene, max_err2, cos_min_angle, cam_scale = self._ba_screen_scene("retriangulate_structure", max_reproj_px, min_angle_deg, 0)
+        try:
+            report = scene.prob.retriangulate(max_err2, cos_min_angle, max_hyp, damping_factor, iteration, cam_scale)
+            _cams, pts = scene.prob.get_state()
+        except Exception:
+            self.ba_release()
+            raise
+        scene.pts_written = pts
+        self.tri_processor.tri_pts[0:3, :] = pts
+        return report
 
     def refine_motion(self, iters=None, views=None, use_loss=True, damping_factor=None):
         """Motion-only refinement of the resident scene: every camera from all its resident observations with the points
