@@ -314,9 +314,11 @@ namespace sfm {
 // Device side of one screening (sfm_ba_screen.hip): the outputs before they are downloaded; a cull scatters by `flags`
 // and `new_ptr` (the exclusive scan of `keep`), kept = M'.
 struct ScreenWork {
-  DevBuf<double> scale, err2, depth, min_cos;
-  DevBuf<unsigned char> flags;
-  DevBuf<int> pt_flags, keep, new_ptr;
+  DevBuf<double> scale;
+  HostOut<double> err2, depth, min_cos;      // always allocated: the kernel writes all five, the cull reads flags
+  HostOut<unsigned char> flags;
+  HostOut<int> pt_flags;
+  DevBuf<int> keep, new_ptr;
   DevBuf<unsigned long long> summary;
   long long kept = 0;
 };
@@ -324,11 +326,30 @@ int ba_screen_run(sfm_ba_problem* p, const char* who, double max_err2, double co
                   const double* cam_scale, double* err2, double* depth, unsigned char* obs_flags, double* min_cos,
                   int* pt_flags, int64_t* summary, ScreenWork& w);
 int ba_cull_enqueue_scatter(const BaDev& d, const BaDev& e, const ScreenWork& w, hipStream_t s);
-// Ragged tracks (sfm_tri_tracks.hip), for the robust triangulation (sfm_tri_ransac.hip): the CSR check with its one
-// read-back (max_track = the longest track), and [R^T | t] of the prepared cameras as row-major 3x4 projections.
+// Ragged tracks (sfm_tri_tracks.hip), for the robust triangulation (sfm_tri_ransac.hip): "<who>: <what>" unless the
+// arrays a free form cannot do without are there, and the CSR check with its one read-back (max_track = the longest track).
+int tracks_check_ptrs(const char* who, const char* what, long long M, const void* pt_ptr, const void* cam_idx, const void* uv,
+                      const void* projs, const void* X_out);
 int tracks_validate(const char* who, int n_pts, int n_views, long long M, const int* d_pt_ptr, const int* d_cam_idx,
                     int* max_track, hipStream_t s);
-int tracks_enqueue_proj_from_prep(int V, const CamPrep* prep, double* projs, hipStream_t s);
+// A set of ragged tracks and the points they solve for: the leading member of the kernel arguments of both track files
+// ("Shared primitives").  All pointers are device pointers.
+struct TrackView {
+  int n_pts, n_views;
+  const int* pt_ptr;
+  const int* cam_idx;
+  const double* u;
+  const double* v;
+  const double* projs;      // [n_views][12]
+  const double* xin[4];     // rows X, Y, Z, W of the input points; a null W row stands for W = 1, null rows for (0, 0, 0, 1)
+  double* xout[4];          // may equal xin; a null W row is not written
+};
+// The free form: uv = [2][M], X_init (or null) and X_out = [4][n_pts].
+TrackView track_view_free(int n_pts, int n_views, long long M, const int* pt_ptr, const int* cam_idx, const double* uv,
+                          const double* projs, const double* X_init, double* X_out);
+// The resident scene, solved in place with W = 1: allocates `projs` (12 V doubles) and enqueues its fill from the
+// prepared cameras on p->stream.  The flush, the preparation of the cameras and the early returns are the caller's.
+int track_view_resident(sfm_ba_problem* p, DevBuf<double>& projs, TrackView* out);
 // What an operation on the resident scene is given (sfm_ba_host.hip; DESIGN.md, "What an operation on the resident scene
 // is given").  `who` names the entry point in the message.
 int ba_check_handle(const sfm_ba_problem* p);

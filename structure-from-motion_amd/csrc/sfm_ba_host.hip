@@ -685,15 +685,11 @@ int sfm_ba_loss_terms(sfm_ba_problem* p, double* s, double* w, double* rho) {
   const size_t m = (size_t)p->dev.M;
   if (m == 0) return stream_sync(p->stream);
   hipStream_t st = p->stream;
-  DevBuf<double> ds, dw, drho;
-  if (s) SFM_TRY(ds.alloc(m, st));
-  if (w) SFM_TRY(dw.alloc(m, st));
-  if (rho) SFM_TRY(drho.alloc(m, st));
-  ba_enqueue_loss_terms(p, p->quirks, s ? ds.p : nullptr, w ? dw.p : nullptr, rho ? drho.p : nullptr);
+  HostOut<double> os, ow, orho;
+  SFM_TRY(os.want(s, m, st)); SFM_TRY(ow.want(w, m, st)); SFM_TRY(orho.want(rho, m, st));
+  ba_enqueue_loss_terms(p, p->quirks, os.dev(), ow.dev(), orho.dev());
   SFM_HIP(hipGetLastError());
-  if (s) SFM_TRY(ds.download(s, m, st));
-  if (w) SFM_TRY(dw.download(w, m, st));
-  if (rho) SFM_TRY(drho.download(rho, m, st));
+  SFM_TRY(os.fetch(st)); SFM_TRY(ow.fetch(st)); SFM_TRY(orho.fetch(st));
   return stream_sync(st);
 }
 

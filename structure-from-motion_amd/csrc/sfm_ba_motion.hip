@@ -393,23 +393,23 @@ int sfm_ba_refine_cameras(sfm_ba_problem* p, double lambda, int iters, int quirk
     return SFM_E_SHAPE;
   }
   DevBuf<unsigned char> dmask;
-  DevBuf<double> dcost, ws, cams_in;
-  DevBuf<int> dstat, behind;
-  if (cam_mask) {
-    SFM_TRY(dmask.upload(cam_mask, (size_t)V, s));
-    p->upload_bytes += V;
-  }
-  SFM_TRY(dcost.alloc(2 * (size_t)V, s));
-  SFM_TRY(dstat.alloc((size_t)V, s));
-  SFM_HIP(hipMemsetAsync(dstat.p, 0, sizeof(int) * (size_t)V, s));
+  DevBuf<double> ws, cams_in;
+  DevBuf<int> behind;
+  HostOut<double> ocost;      // the kernels carry both through their iterations, wanted or not
+  HostOut<int> ostat;
+  SFM_TRY(dmask.upload_if(cam_mask, (size_t)V, s));
+  if (cam_mask) p->upload_bytes += V;
+  SFM_TRY(ocost.want(cost, 2 * (size_t)V, s, true));
+  SFM_TRY(ostat.want(status, (size_t)V, s, true));
+  SFM_HIP(hipMemsetAsync(ostat.dev(), 0, sizeof(int) * (size_t)V, s));
   MoArgs a = {};
-  a.V = V; a.ptr = p->cam_ptr; a.obs = p->cam_obs; a.mask = cam_mask ? dmask.p : nullptr;
+  a.V = V; a.ptr = p->cam_ptr; a.obs = p->cam_obs; a.mask = dmask.p;
   a.lambda = lambda; a.iters = iters; a.quirks = quirks;
-  a.cost = dcost.p; a.status = dstat.p;
+  a.cost = ocost.dev(); a.status = ostat.dev();
   SFM_TRY(mo_enqueue(p, a, use_loss ? p->loss_kind : SFM_LOSS_NONE, n_class, max_obs, ws, behind, cams_in));
   SFM_TRY(ba_state_changed(p));                          // new cameras
-  if (cost) SFM_TRY(dcost.download(cost, 2 * (size_t)V, s));
-  if (status) SFM_TRY(dstat.download(status, (size_t)V, s));
+  SFM_TRY(ocost.fetch(s));
+  SFM_TRY(ostat.fetch(s));
   SFM_TRY(stream_sync(s));
   if (status)
     for (int c = 0; c < V; ++c) status[c] &= ~kMoDone;

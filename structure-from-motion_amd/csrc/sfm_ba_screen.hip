@@ -229,12 +229,10 @@ int ba_screen_run(sfm_ba_problem* p, const char* who, double max_err2, double co
   if (d.N == 0) return SFM_OK;
   if (!p->prep_valid) SFM_TRY(ba_enqueue_prep(p));       // the expanded cameras the linearisation reads
   const size_t n = (size_t)d.N, m = (size_t)d.M;
-  if (cam_scale) {
-    SFM_TRY(w.scale.upload(cam_scale, (size_t)d.V, s));
-    p->upload_bytes += (long long)(sizeof(double) * d.V);
-  }
-  SFM_TRY(w.err2.alloc(m, s)); SFM_TRY(w.depth.alloc(m, s)); SFM_TRY(w.flags.alloc(m, s));
-  SFM_TRY(w.min_cos.alloc(n, s)); SFM_TRY(w.pt_flags.alloc(n, s)); SFM_TRY(w.keep.alloc(n, s));
+  SFM_TRY(w.scale.upload_if(cam_scale, (size_t)d.V, s));
+  if (cam_scale) p->upload_bytes += (long long)(sizeof(double) * d.V);
+  SFM_TRY(w.err2.want(err2, m, s, true)); SFM_TRY(w.depth.want(depth, m, s, true)); SFM_TRY(w.flags.want(obs_flags, m, s, true));
+  SFM_TRY(w.min_cos.want(min_cos, n, s, true)); SFM_TRY(w.pt_flags.want(pt_flags, n, s, true)); SFM_TRY(w.keep.alloc(n, s));
   SFM_TRY(w.new_ptr.alloc(n + 1, s)); SFM_TRY(w.summary.alloc(8, s));
   SFM_HIP(hipMemsetAsync(w.summary.p, 0, 8 * sizeof(unsigned long long), s));
   ScreenArgs a = {};
@@ -242,10 +240,10 @@ int ba_screen_run(sfm_ba_problem* p, const char* who, double max_err2, double co
   a.pt_ptr = d.pt_ptr; a.cam_idx = d.cam_idx; a.u = d.u; a.v = d.v;
   a.prep = d.prep[p->cur];
   a.px = d.px; a.py = d.py; a.pz = d.pz;
-  a.cam_scale = cam_scale ? w.scale.p : nullptr;
+  a.cam_scale = w.scale.p;
   a.max_err2 = max_err2; a.cos_min_angle = cos_min_angle; a.min_obs = min_obs;
-  a.err2 = w.err2.p; a.depth = w.depth.p; a.obs_flags = w.flags.p;
-  a.min_cos = w.min_cos.p; a.pt_flags = w.pt_flags.p; a.keep = w.keep.p;
+  a.err2 = w.err2.dev(); a.depth = w.depth.dev(); a.obs_flags = w.flags.dev();
+  a.min_cos = w.min_cos.dev(); a.pt_flags = w.pt_flags.dev(); a.keep = w.keep.p;
   a.summary = w.summary.p;
   dispatch_group<1>(group ? group : sfm_tri_tracks_auto_group(d.N, d.M, p->max_track),
                     [&](auto G) { launch_screen<decltype(G)::value>(a, s); });
@@ -254,11 +252,8 @@ int ba_screen_run(sfm_ba_problem* p, const char* who, double max_err2, double co
   SFM_HIP(hipGetLastError());
   unsigned long long sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   SFM_HIP(hipMemcpyAsync(sum, w.summary.p, sizeof(sum), hipMemcpyDeviceToHost, s));
-  if (err2) SFM_TRY(w.err2.download(err2, m, s));
-  if (depth) SFM_TRY(w.depth.download(depth, m, s));
-  if (obs_flags) SFM_TRY(w.flags.download(obs_flags, m, s));
-  if (min_cos) SFM_TRY(w.min_cos.download(min_cos, n, s));
-  if (pt_flags) SFM_TRY(w.pt_flags.download(pt_flags, n, s));
+  SFM_TRY(w.err2.fetch(s)); SFM_TRY(w.depth.fetch(s)); SFM_TRY(w.flags.fetch(s));
+  SFM_TRY(w.min_cos.fetch(s)); SFM_TRY(w.pt_flags.fetch(s));
   SFM_TRY(ba_sync_cam_status(p, who, ""));
   if (summary) for (int k = 0; k < 8; ++k) summary[k] = (int64_t)sum[k];
   w.kept = (long long)sum[1];
@@ -268,7 +263,7 @@ int ba_screen_run(sfm_ba_problem* p, const char* who, double max_err2, double co
 // Fill of the culled scene e from d: the kept observations and the new pt_ptr.
 int ba_cull_enqueue_scatter(const BaDev& d, const BaDev& e, const ScreenWork& w, hipStream_t s) {
   if (d.N <= 0) return SFM_OK;
-  ba_cull_scatter_kernel<<<(d.N + 255) / 256, 256, 0, s>>>(d.N, d.pt_ptr, d.cam_idx, d.u, d.v, w.flags.p, w.new_ptr.p,
+  ba_cull_scatter_kernel<<<(d.N + 255) / 256, 256, 0, s>>>(d.N, d.pt_ptr, d.cam_idx, d.u, d.v, w.flags.dev(), w.new_ptr.p,
                                                            e.pt_ptr, e.cam_idx, e.u, e.v);
   SFM_HIP(hipGetLastError());
   return SFM_OK;

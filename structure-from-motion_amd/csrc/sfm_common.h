@@ -84,10 +84,26 @@ struct DevBuf {
     if (count) SFM_HIP(hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, s));
     return SFM_OK;
   }
+  int upload_if(const T* host, size_t count, hipStream_t s) { return host ? upload(host, count, s) : SFM_OK; }      // an optional input: p stays null without one
   int download(T* host, size_t count, hipStream_t s) const {
     if (count) SFM_HIP(hipMemcpyAsync(host, p, count * sizeof(T), hipMemcpyDeviceToHost, s));
     return SFM_OK;
   }
+};
+
+// An optional output of a host-pointer entry point: a device buffer only when the caller asked for the array (or
+// `always`: the kernels write it whether or not anyone reads it back), null for the kernels otherwise, and the
+// download of exactly what was asked for.
+template <typename T>
+struct HostOut {
+  DevBuf<T> buf;
+  T* host = nullptr;
+  int want(T* h, size_t count, hipStream_t s, bool always = false) {
+    host = h;
+    return (h || always) ? buf.alloc(count, s) : SFM_OK;
+  }
+  T* dev() const { return buf.p; }
+  int fetch(hipStream_t s) const { return host ? buf.download(host, buf.n, s) : SFM_OK; }
 };
 
 // The observation list a track store built last (sfm_obs_build), for the bundle adjustment to read:

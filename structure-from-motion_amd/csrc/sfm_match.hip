@@ -548,21 +548,14 @@ int sfm_match(sfm_desc_set* query, int n_refs, sfm_desc_set* const* refs, int mo
   if (!query) return SFM_E_HANDLE;
   const size_t pairs = (size_t)(n_refs > 0 ? n_refs : 0) * (size_t)query->n;
   hipStream_t st = ctx().stream;
-  DevBuf<int> dbi, dsi;
-  DevBuf<float> dbd, dsd;
-  DevBuf<uint8_t> dm;
-  SFM_TRY(dbi.alloc(pairs, st)); SFM_TRY(dbd.alloc(pairs, st)); SFM_TRY(dsi.alloc(pairs, st)); SFM_TRY(dsd.alloc(pairs, st));
-  SFM_TRY(dm.alloc(pairs, st));
-  SFM_TRY(sfm_match_dev(query, n_refs, refs, mode, dbi.p, dbd.p, dsi.p, dsd.p, dm.p, st));
-  if (pairs) {
-    if (best_idx) SFM_TRY(dbi.download(best_idx, pairs, st));
-    if (best_dist) SFM_TRY(dbd.download(best_dist, pairs, st));
-    if (second_idx) SFM_TRY(dsi.download(second_idx, pairs, st));
-    if (second_dist) SFM_TRY(dsd.download(second_dist, pairs, st));
-    if (mutual) SFM_TRY(dm.download(mutual, pairs, st));
-  }
-  SFM_TRY(stream_sync(st));
-  return SFM_OK;
+  HostOut<int> obi, osi;
+  HostOut<float> obd, osd;
+  HostOut<uint8_t> om;
+  SFM_TRY(obi.want(best_idx, pairs, st)); SFM_TRY(obd.want(best_dist, pairs, st)); SFM_TRY(osi.want(second_idx, pairs, st));
+  SFM_TRY(osd.want(second_dist, pairs, st)); SFM_TRY(om.want(mutual, pairs, st));
+  SFM_TRY(sfm_match_dev(query, n_refs, refs, mode, obi.dev(), obd.dev(), osi.dev(), osd.dev(), om.dev(), st));
+  SFM_TRY(obi.fetch(st)); SFM_TRY(obd.fetch(st)); SFM_TRY(osi.fetch(st)); SFM_TRY(osd.fetch(st)); SFM_TRY(om.fetch(st));
+  return stream_sync(st);
 }
 
 }  // extern "C"

@@ -52,12 +52,7 @@ __host__ __device__ inline void ransac_pair_of(int n, long long k, int* i, int* 
 }
 
 struct RansacArgs {
-  int n_pts;
-  const int* pt_ptr;
-  const int* cam_idx;
-  const double* u;
-  const double* v;
-  const double* projs;          // [V][12]
+  TrackView t;                  // null input rows stand for (0, 0, 0, 1)
   const double* centres;        // camera c's centre at centres + centre_stride * c
   int centre_stride;
   const double* cam_scale;      // [V] or null (= 1)
@@ -65,8 +60,6 @@ struct RansacArgs {
   int max_hyp;
   double lambda;
   int iters;
-  const double* xin[4];         // rows X, Y, Z, W of the input points; null rows stand for (0, 0, 0, 1)
-  double* xout[4];              // may equal xin; a null W row is not written
   int* best_hyp;                // [n_pts] score -> refit, and an output
   int* hyp_count;               // [n_pts] score -> refit: the winner's inlier count
   double* hyp_x;                // [3][n_pts] score -> refit: the winner's point
@@ -114,10 +107,10 @@ __device__ __forceinline__ bool ransac_hypothesis(const RansacArgs& a, int beg, 
   int i, j;
   ransac_pair_of(n, ransac_pair_number(P, a.max_hyp, h), &i, &j);
   const int oi = beg + i, oj = beg + j;
-  const int ci = a.cam_idx[oi], cj = a.cam_idx[oj];
-  const double* Pi = a.projs + 12 * (size_t)ci;
-  const double* Pj = a.projs + 12 * (size_t)cj;
-  const double ui = a.u[oi], vi = a.v[oi], uj = a.u[oj], vj = a.v[oj];
+  const int ci = a.t.cam_idx[oi], cj = a.t.cam_idx[oj];
+  const double* Pi = a.t.projs + 12 * (size_t)ci;
+  const double* Pj = a.t.projs + 12 * (size_t)cj;
+  const double ui = a.t.u[oi], vi = a.t.v[oi], uj = a.t.u[oj], vj = a.t.v[oj];
   TrackSums S = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   ransac_rows(Pi, ui, vi, S);
   ransac_rows(Pj, uj, vj, S);
@@ -144,9 +137,9 @@ __global__ __launch_bounds__(kRanBlock) void tri_ransac_score_kernel(RansacArgs 
   __shared__ double tile_all[kRanBlock * kRanSlots * kRanObs];
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int p = (int)(t / G), lane = (int)(threadIdx.x % G);
-  if (p >= a.n_pts) return;               // whole groups leave together
+  if (p >= a.t.n_pts) return;               // whole groups leave together
   double* tile = tile_all + (size_t)(threadIdx.x - lane) * kRanSlots * kRanObs;      // kCap observations of this group
-  const int beg = a.pt_ptr[p], end = a.pt_ptr[p + 1], n = end - beg;
+  const int beg = a.t.pt_ptr[p], end = a.t.pt_ptr[p + 1], n = end - beg;
 
   int best_cnt = 0, best_h = -1;
   double best_cos = 2.0, b0 = 0, b1 = 0, b2 = 0;
@@ -163,10 +156,10 @@ __global__ __launch_bounds__(kRanBlock) void tri_ransac_score_kernel(RansacArgs 
         const int te = min(end, tb + kCap);
         if (!one || hb == 0) {
           for (int o = tb + lane; o < te; o += G) {
-            const int c = a.cam_idx[o];
-            const double* P12 = a.projs + 12 * (size_t)c;
+            const int c = a.t.cam_idx[o];
+            const double* P12 = a.t.projs + 12 * (size_t)c;
             double* w = tile + kRanObs * (o - tb);
-            w[0] = a.u[o]; w[1] = a.v[o];
+            w[0] = a.t.u[o]; w[1] = a.t.v[o];
 #pragma unroll
             for (int k = 0; k < 12; ++k) w[2 + k] = P12[k];
             w[14] = a.cam_scale ? a.cam_scale[c] : 1.0;
@@ -202,7 +195,7 @@ __global__ __launch_bounds__(kRanBlock) void tri_ransac_score_kernel(RansacArgs 
     if (better) { best_cnt = oc; best_cos = os; best_h = oh; }
   }
   if (best_h >= 0 && own_h == best_h) {      // the lane that formed the winner still holds its point
-    a.hyp_x[p] = b0; a.hyp_x[(size_t)a.n_pts + p] = b1; a.hyp_x[2 * (size_t)a.n_pts + p] = b2;
+    a.hyp_x[p] = b0; a.hyp_x[(size_t)a.t.n_pts + p] = b1; a.hyp_x[2 * (size_t)a.t.n_pts + p] = b2;
   }
   if (lane == 0) { a.best_hyp[p] = best_h; a.hyp_count[p] = best_cnt; }
 }
@@ -211,12 +204,12 @@ template <int G>
 __global__ __launch_bounds__(256) void tri_ransac_refit_kernel(RansacArgs a) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int p = (int)(t / G), lane = (int)(threadIdx.x % G);
-  if (p >= a.n_pts) return;               // whole groups leave together
-  const int beg = a.pt_ptr[p], end = a.pt_ptr[p + 1], n = end - beg;
+  if (p >= a.t.n_pts) return;               // whole groups leave together
+  const int beg = a.t.pt_ptr[p], end = a.t.pt_ptr[p + 1], n = end - beg;
   double x0 = 0, x1 = 0, x2 = 0, x3 = 1.0;
-  if (a.xin[0]) {
-    x0 = a.xin[0][p]; x1 = a.xin[1][p]; x2 = a.xin[2][p];
-    if (a.xin[3]) x3 = a.xin[3][p];
+  if (a.t.xin[0]) {
+    x0 = a.t.xin[0][p]; x1 = a.t.xin[1][p]; x2 = a.t.xin[2][p];
+    if (a.t.xin[3]) x3 = a.t.xin[3][p];
   }
   const int bh = a.best_hyp[p];
   int flags = n < 2 ? SFM_RANSAC_TOO_FEW : (bh < 0 ? SFM_RANSAC_NO_MODEL : 0);
@@ -224,7 +217,7 @@ __global__ __launch_bounds__(256) void tri_ransac_refit_kernel(RansacArgs a) {
   const bool solved = !(flags & (SFM_RANSAC_TOO_FEW | SFM_RANSAC_NO_MODEL));
 
   if (solved) {
-    const double h0 = a.hyp_x[p], h1 = a.hyp_x[(size_t)a.n_pts + p], h2 = a.hyp_x[2 * (size_t)a.n_pts + p];
+    const double h0 = a.hyp_x[p], h1 = a.hyp_x[(size_t)a.t.n_pts + p], h2 = a.hyp_x[2 * (size_t)a.t.n_pts + p];
     const int hc = a.hyp_count[p];
     // the inhomogeneous solve over the winner's inliers, then the damped steps with that mask
     double y0 = 0, y1 = 0, y2 = 0;
@@ -232,9 +225,9 @@ __global__ __launch_bounds__(256) void tri_ransac_refit_kernel(RansacArgs a) {
     for (int it = -1; ok && it < a.iters; ++it) {
       TrackSums S = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       for (int o = beg + lane; o < end; o += G) {
-        const int c = a.cam_idx[o];
-        const double* P = a.projs + 12 * (size_t)c;
-        const double ku = a.u[o], kv = a.v[o];
+        const int c = a.t.cam_idx[o];
+        const double* P = a.t.projs + 12 * (size_t)c;
+        const double ku = a.t.u[o], kv = a.t.v[o];
         if (!ransac_inlier(P, ku, kv, a.cam_scale ? a.cam_scale[c] : 1.0, h0, h1, h2, a.max_err2)) continue;
         if (it < 0) ransac_rows(P, ku, kv, S);
         else track_view(P, ku, kv, y0, y1, y2, 1.0, S);
@@ -252,8 +245,8 @@ __global__ __launch_bounds__(256) void tri_ransac_refit_kernel(RansacArgs a) {
     int rc = 0;
     if (ok) {
       for (int o = beg + lane; o < end; o += G) {
-        const int c = a.cam_idx[o];
-        rc += ransac_inlier(a.projs + 12 * (size_t)c, a.u[o], a.v[o], a.cam_scale ? a.cam_scale[c] : 1.0, y0, y1, y2, a.max_err2);
+        const int c = a.t.cam_idx[o];
+        rc += ransac_inlier(a.t.projs + 12 * (size_t)c, a.t.u[o], a.t.v[o], a.cam_scale ? a.cam_scale[c] : 1.0, y0, y1, y2, a.max_err2);
       }
       rc = group_sum<G>(rc);
     }
@@ -267,16 +260,16 @@ __global__ __launch_bounds__(256) void tri_ransac_refit_kernel(RansacArgs a) {
   for (int o = beg + lane; o < end; o += G) {
     bool in = false;
     if (solved) {
-      const int c = a.cam_idx[o];
-      in = ransac_inlier(a.projs + 12 * (size_t)c, a.u[o], a.v[o], a.cam_scale ? a.cam_scale[c] : 1.0, x0, x1, x2, a.max_err2);
+      const int c = a.t.cam_idx[o];
+      in = ransac_inlier(a.t.projs + 12 * (size_t)c, a.t.u[o], a.t.v[o], a.cam_scale ? a.cam_scale[c] : 1.0, x0, x1, x2, a.max_err2);
     }
     if (a.obs_inlier) a.obs_inlier[o] = in ? 1 : 0;
     nin += in;
   }
   nin = group_sum<G>(nin);
   if (lane != 0) return;
-  a.xout[0][p] = x0; a.xout[1][p] = x1; a.xout[2][p] = x2;
-  if (a.xout[3]) a.xout[3][p] = x3;
+  a.t.xout[0][p] = x0; a.t.xout[1][p] = x1; a.t.xout[2][p] = x2;
+  if (a.t.xout[3]) a.t.xout[3][p] = x3;
   if (a.n_inliers) a.n_inliers[p] = nin;
   if (a.status) a.status[p] = flags;
   if (solved) {
@@ -308,14 +301,10 @@ __global__ void tri_ransac_centres_kernel(int V, const double* __restrict__ proj
 
 template <int G>
 static void launch_ransac(const RansacArgs& a, hipStream_t s) {
-  const long long threads = (long long)a.n_pts * G;
+  const long long threads = (long long)a.t.n_pts * G;
   tri_ransac_score_kernel<G><<<dim3((unsigned)((threads + kRanBlock - 1) / kRanBlock)), dim3(kRanBlock), 0, s>>>(a);
   tri_ransac_refit_kernel<G><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(a);
 }
-
-// `group` = 0: tracks_pick_group's rule unchanged -- the narrowest group whose tile holds the
-// longest track, widened while the call is short of waves.
-static int ransac_pick_group(int n_pts, long long M, int max_track) { return sfm_tri_tracks_auto_group(n_pts, M, max_track); }
 
 static int ransac_check_args(const char* who, int n_pts, int n_views, long long M, double max_err2, double cos_min_angle,
                              int max_hyp, double lambda, int iters, int group) {
@@ -334,14 +323,15 @@ static int ransac_check_args(const char* who, int n_pts, int n_views, long long 
 // What a call keeps on the device besides the caller's arrays.
 struct RansacWork {
   DevBuf<int> best_hyp, hyp_count;
-  DevBuf<double> hyp_x;
+  DevBuf<double> hyp_x, centres;      // centres: the free form only
   DevBuf<unsigned long long> summary;
 };
 
 // Enqueue both kernels on s; the CSR has been validated, max_track is its longest track.  a.best_hyp / a.summary may be
-// null: the work buffers stand in.
+// null: the work buffers stand in.  `group` = 0: the rule of sfm_tri_tracks unchanged -- the
+// narrowest group whose tile holds the longest track, widened while the call is short of waves.
 static int ransac_enqueue(RansacArgs a, RansacWork& w, int group, long long M, int max_track, hipStream_t s) {
-  const size_t n = (size_t)a.n_pts;
+  const size_t n = (size_t)a.t.n_pts;
   if (a.max_hyp == 0) a.max_hyp = kRanDefaultHyp;
   if (!a.best_hyp) { SFM_TRY(w.best_hyp.alloc(n, s)); a.best_hyp = w.best_hyp.p; }
   if (!a.summary) { SFM_TRY(w.summary.alloc(6, s)); a.summary = w.summary.p; }
@@ -349,11 +339,32 @@ static int ransac_enqueue(RansacArgs a, RansacWork& w, int group, long long M, i
   SFM_TRY(w.hyp_x.alloc(3 * n, s));
   a.hyp_count = w.hyp_count.p; a.hyp_x = w.hyp_x.p;
   SFM_HIP(hipMemsetAsync(a.summary, 0, 6 * sizeof(unsigned long long), s));
-  if (a.n_pts <= 0) return SFM_OK;
-  const int g = group ? group : ransac_pick_group(a.n_pts, M, max_track);
+  if (a.t.n_pts <= 0) return SFM_OK;
+  const int g = group ? group : sfm_tri_tracks_auto_group(a.t.n_pts, M, max_track);
   dispatch_group<1>(g, [&](auto G) { launch_ransac<decltype(G)::value>(a, s); });
   SFM_HIP(hipGetLastError());
   return SFM_OK;
+}
+
+// The one body of sfm_tri_tracks_ransac and sfm_tri_tracks_ransac_dev: checked arguments and device pointers in
+// (n_pts > 0), the kernels enqueued on s out.  w lives until the caller has waited for s.
+static int ransac_run(const char* who, int n_pts, int n_views, long long M, const int* d_pt_ptr, const int* d_cam_idx,
+                      const double* d_uv, const double* d_projs, const double* d_cam_scale, double max_err2, double cos_min_angle,
+                      int max_hyp, double lambda, int iters, int group, const double* d_X_init, double* d_X_out,
+                      unsigned char* d_obs_inlier, int* d_n_inliers, int* d_best_hyp, int* d_status, int64_t* d_summary,
+                      RansacWork& w, hipStream_t s) {
+  int max_track = 0;
+  SFM_TRY(tracks_validate(who, n_pts, n_views, M, d_pt_ptr, d_cam_idx, &max_track, s));
+  SFM_TRY(w.centres.alloc(3 * (size_t)n_views, s));
+  tri_ransac_centres_kernel<<<(n_views + 255) / 256, 256, 0, s>>>(n_views, d_projs, w.centres.p);
+  SFM_HIP(hipGetLastError());
+  RansacArgs a = {};
+  a.t = track_view_free(n_pts, n_views, M, d_pt_ptr, d_cam_idx, d_uv, d_projs, d_X_init, d_X_out);
+  a.centres = w.centres.p; a.centre_stride = 3; a.cam_scale = d_cam_scale;
+  a.max_err2 = max_err2; a.cos_min_angle = cos_min_angle; a.max_hyp = max_hyp; a.lambda = lambda; a.iters = iters;
+  a.best_hyp = d_best_hyp; a.obs_inlier = d_obs_inlier; a.n_inliers = d_n_inliers; a.status = d_status;
+  a.summary = reinterpret_cast<unsigned long long*>(d_summary);
+  return ransac_enqueue(a, w, group, M, max_track, s);
 }
 
 }  // namespace sfm
@@ -384,26 +395,10 @@ int sfm_tri_tracks_ransac_dev(int n_pts, int n_views, int64_t M, const int* d_pt
     if (d_summary) SFM_HIP(hipMemsetAsync(d_summary, 0, 6 * sizeof(int64_t), s));
     return SFM_OK;
   }
-  if (!d_pt_ptr || !d_projs || !d_X_out || (M > 0 && (!d_cam_idx || !d_uv))) { set_error("%s: null device pointer", who); return SFM_E_SHAPE; }
-  int max_track = 0;
-  SFM_TRY(tracks_validate(who, n_pts, n_views, M, d_pt_ptr, d_cam_idx, &max_track, s));
-  DevBuf<double> dCen;
-  SFM_TRY(dCen.alloc(3 * (size_t)n_views, s));
-  tri_ransac_centres_kernel<<<(n_views + 255) / 256, 256, 0, s>>>(n_views, d_projs, dCen.p);
-  SFM_HIP(hipGetLastError());
-  RansacArgs a = {};
-  a.n_pts = n_pts;
-  a.pt_ptr = d_pt_ptr; a.cam_idx = d_cam_idx; a.u = d_uv; a.v = d_uv + M;
-  a.projs = d_projs; a.centres = dCen.p; a.centre_stride = 3; a.cam_scale = d_cam_scale;
-  a.max_err2 = max_err2; a.cos_min_angle = cos_min_angle; a.max_hyp = max_hyp; a.lambda = lambda; a.iters = iters;
-  for (int r = 0; r < 4; ++r) {
-    a.xin[r] = d_X_init ? d_X_init + (size_t)r * n_pts : nullptr;
-    a.xout[r] = d_X_out + (size_t)r * n_pts;
-  }
-  a.best_hyp = d_best_hyp; a.obs_inlier = d_obs_inlier; a.n_inliers = d_n_inliers; a.status = d_status;
-  a.summary = reinterpret_cast<unsigned long long*>(d_summary);
+  SFM_TRY(tracks_check_ptrs(who, "null device pointer", M, d_pt_ptr, d_cam_idx, d_uv, d_projs, d_X_out));
   RansacWork w;
-  SFM_TRY(ransac_enqueue(a, w, group, M, max_track, s));
+  SFM_TRY(ransac_run(who, n_pts, n_views, M, d_pt_ptr, d_cam_idx, d_uv, d_projs, d_cam_scale, max_err2, cos_min_angle, max_hyp,
+                     lambda, iters, group, d_X_init, d_X_out, d_obs_inlier, d_n_inliers, d_best_hyp, d_status, d_summary, w, s));
   return stream_sync(s);      // the work buffers go back to the pool with this call
 }
 
@@ -416,35 +411,28 @@ int sfm_tri_tracks_ransac(int n_pts, int n_views, int64_t M, const int* pt_ptr, 
   SFM_TRY(ransac_check_args(who, n_pts, n_views, M, max_err2, cos_min_angle, max_hyp, lambda, iters, group));
   if (summary) for (int k = 0; k < 6; ++k) summary[k] = 0;
   if (n_pts == 0) return SFM_OK;
-  if (!pt_ptr || !projs || !X_out || (M > 0 && (!cam_idx || !uv))) { set_error("%s: null pointer", who); return SFM_E_SHAPE; }
+  SFM_TRY(tracks_check_ptrs(who, "null pointer", M, pt_ptr, cam_idx, uv, projs, X_out));
   hipStream_t s = ctx().stream;
   const size_t n = (size_t)n_pts, m = (size_t)M;
-  DevBuf<int> dPtr, dCam, dNi, dBh, dSt;
-  DevBuf<double> dUV, dP, dSc, dX, dO;
-  DevBuf<unsigned char> dIn;
-  DevBuf<int64_t> dSum;
+  DevBuf<int> dPtr, dCam;
+  DevBuf<double> dUV, dP, dSc, dX;
+  HostOut<double> oX;
+  HostOut<unsigned char> oInlier;
+  HostOut<int> oCount, oBest, oStatus;
+  HostOut<int64_t> oSummary;
+  RansacWork w;
   SFM_TRY(dPtr.upload(pt_ptr, n + 1, s));
   SFM_TRY(dCam.upload(cam_idx, m, s));
   SFM_TRY(dUV.upload(uv, 2 * m, s));
   SFM_TRY(dP.upload(projs, 12 * (size_t)n_views, s));
-  if (cam_scale) SFM_TRY(dSc.upload(cam_scale, (size_t)n_views, s));
-  if (X_init) SFM_TRY(dX.upload(X_init, 4 * n, s));
-  SFM_TRY(dO.alloc(4 * n, s));
-  if (obs_inlier) SFM_TRY(dIn.alloc(m, s));
-  if (n_inliers) SFM_TRY(dNi.alloc(n, s));
-  if (best_hyp) SFM_TRY(dBh.alloc(n, s));
-  if (status) SFM_TRY(dSt.alloc(n, s));
-  if (summary) SFM_TRY(dSum.alloc(6, s));
-  SFM_TRY(sfm_tri_tracks_ransac_dev(n_pts, n_views, M, dPtr.p, dCam.p, dUV.p, dP.p, cam_scale ? dSc.p : nullptr, max_err2,
-                                    cos_min_angle, max_hyp, lambda, iters, group, X_init ? dX.p : nullptr, dO.p,
-                                    obs_inlier ? dIn.p : nullptr, n_inliers ? dNi.p : nullptr, best_hyp ? dBh.p : nullptr,
-                                    status ? dSt.p : nullptr, summary ? dSum.p : nullptr, s));
-  SFM_TRY(dO.download(X_out, 4 * n, s));
-  if (obs_inlier) SFM_TRY(dIn.download(obs_inlier, m, s));
-  if (n_inliers) SFM_TRY(dNi.download(n_inliers, n, s));
-  if (best_hyp) SFM_TRY(dBh.download(best_hyp, n, s));
-  if (status) SFM_TRY(dSt.download(status, n, s));
-  if (summary) SFM_TRY(dSum.download(summary, 6, s));
+  SFM_TRY(dSc.upload_if(cam_scale, (size_t)n_views, s));
+  SFM_TRY(dX.upload_if(X_init, 4 * n, s));
+  SFM_TRY(oX.want(X_out, 4 * n, s)); SFM_TRY(oInlier.want(obs_inlier, m, s)); SFM_TRY(oCount.want(n_inliers, n, s));
+  SFM_TRY(oBest.want(best_hyp, n, s)); SFM_TRY(oStatus.want(status, n, s)); SFM_TRY(oSummary.want(summary, 6, s));
+  SFM_TRY(ransac_run(who, n_pts, n_views, M, dPtr.p, dCam.p, dUV.p, dP.p, dSc.p, max_err2, cos_min_angle, max_hyp, lambda, iters,
+                     group, dX.p, oX.dev(), oInlier.dev(), oCount.dev(), oBest.dev(), oStatus.dev(), oSummary.dev(), w, s));
+  SFM_TRY(oX.fetch(s)); SFM_TRY(oInlier.fetch(s)); SFM_TRY(oCount.fetch(s));
+  SFM_TRY(oBest.fetch(s)); SFM_TRY(oStatus.fetch(s)); SFM_TRY(oSummary.fetch(s));
   return stream_sync(s);
 }
 
@@ -462,43 +450,30 @@ int sfm_ba_retriangulate(sfm_ba_problem* p, double max_err2, double cos_min_angl
   hipStream_t s = p->stream;
   const size_t n = (size_t)d.N, m = (size_t)d.M;
   DevBuf<double> dP, dSc;
-  DevBuf<int> dNi, dBh, dSt;
-  DevBuf<unsigned char> dIn;
+  HostOut<unsigned char> oInlier;
+  HostOut<int> oCount, oBest, oStatus;
   RansacWork w;
-  SFM_TRY(dP.alloc(12 * (size_t)d.V, s));
-  SFM_TRY(tracks_enqueue_proj_from_prep(d.V, d.prep[p->cur], dP.p, s));
-  if (cam_scale) {
-    SFM_TRY(dSc.upload(cam_scale, (size_t)d.V, s));
-    p->upload_bytes += (long long)(sizeof(double) * d.V);
-  }
-  if (obs_inlier) SFM_TRY(dIn.alloc(m, s));
-  if (n_inliers) SFM_TRY(dNi.alloc(n, s));
-  if (best_hyp) SFM_TRY(dBh.alloc(n, s));
-  if (status) SFM_TRY(dSt.alloc(n, s));
-  SFM_TRY(w.summary.alloc(6, s));
   RansacArgs a = {};
-  a.n_pts = d.N;
-  a.pt_ptr = d.pt_ptr; a.cam_idx = d.cam_idx; a.u = d.u; a.v = d.v;
-  a.projs = dP.p;
+  SFM_TRY(track_view_resident(p, dP, &a.t));
+  SFM_TRY(dSc.upload_if(cam_scale, (size_t)d.V, s));
+  if (cam_scale) p->upload_bytes += (long long)(sizeof(double) * d.V);
+  SFM_TRY(oInlier.want(obs_inlier, m, s)); SFM_TRY(oCount.want(n_inliers, n, s));
+  SFM_TRY(oBest.want(best_hyp, n, s)); SFM_TRY(oStatus.want(status, n, s));
+  SFM_TRY(w.summary.alloc(6, s));
   a.centres = d.prep[p->cur]->C; a.centre_stride = 19;      // the centres of the prepared cameras
-  a.cam_scale = cam_scale ? dSc.p : nullptr;
+  a.cam_scale = dSc.p;
   a.max_err2 = max_err2; a.cos_min_angle = cos_min_angle; a.max_hyp = max_hyp; a.lambda = lambda; a.iters = iters;
-  a.xin[0] = d.px; a.xin[1] = d.py; a.xin[2] = d.pz; a.xin[3] = nullptr;      // W = 1
-  a.xout[0] = d.px; a.xout[1] = d.py; a.xout[2] = d.pz; a.xout[3] = nullptr;
-  a.best_hyp = best_hyp ? dBh.p : nullptr; a.obs_inlier = obs_inlier ? dIn.p : nullptr;
-  a.n_inliers = n_inliers ? dNi.p : nullptr; a.status = status ? dSt.p : nullptr;
+  a.best_hyp = oBest.dev(); a.obs_inlier = oInlier.dev(); a.n_inliers = oCount.dev(); a.status = oStatus.dev();
   a.summary = w.summary.p;
   SFM_TRY(ransac_enqueue(a, w, group, d.M, p->max_track, s));
   SFM_TRY(ba_reset_stats(p));                            // new points, as after sfm_ba_set_points
   unsigned long long sum[6] = {0, 0, 0, 0, 0, 0};
-  SFM_HIP(hipMemcpyAsync(sum, w.summary.p, sizeof(sum), hipMemcpyDeviceToHost, s));
-  if (obs_inlier) SFM_TRY(dIn.download(obs_inlier, m, s));
-  if (n_inliers) SFM_TRY(dNi.download(n_inliers, n, s));
-  if (best_hyp) SFM_TRY(dBh.download(best_hyp, n, s));
-  if (status) SFM_TRY(dSt.download(status, n, s));
+  SFM_TRY(w.summary.download(sum, 6, s));
+  SFM_TRY(oInlier.fetch(s)); SFM_TRY(oCount.fetch(s)); SFM_TRY(oBest.fetch(s)); SFM_TRY(oStatus.fetch(s));
   SFM_TRY(stream_sync(s));
   if (summary) for (int k = 0; k < 6; ++k) summary[k] = (int64_t)sum[k];
   return SFM_OK;
 }
 
 }  // extern "C"
+

@@ -44,21 +44,8 @@ __global__ void tracks_proj_from_prep_kernel(int V, const CamPrep* __restrict__ 
   projs[i] = k < 3 ? c.R[3 * k + r] : c.t[r];
 }
 
-int tracks_enqueue_proj_from_prep(int V, const CamPrep* prep, double* projs, hipStream_t s) {
-  tracks_proj_from_prep_kernel<<<(12 * V + 255) / 256, 256, 0, s>>>(V, prep, projs);
-  SFM_HIP(hipGetLastError());
-  return SFM_OK;
-}
-
 struct TrackArgs {
-  int n_pts, n_views;
-  const int* pt_ptr;
-  const int* cam_idx;
-  const double* u;
-  const double* v;
-  const double* projs;
-  const double* xin[4];     // rows X, Y, Z, W of the input points; a null W row stands for W = 1
-  double* xout[4];          // may equal xin; a null W row is not written
+  TrackView t;
   double lambda;
   int iters;
   double* cost;             // [2][n_pts] or null
@@ -74,12 +61,12 @@ struct TrackArgs {
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tri_tracks_linear_kernel(TrackArgs a) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= a.n_pts) return;
-  const int beg = a.pt_ptr[p], end = a.pt_ptr[p + 1];
+  if (p >= a.t.n_pts) return;
+  const int beg = a.t.pt_ptr[p], end = a.t.pt_ptr[p + 1];
   double x[4] = {0, 0, 0, 1};
-  if (a.xin[0]) {
-    x[0] = a.xin[0][p]; x[1] = a.xin[1][p]; x[2] = a.xin[2][p];
-    x[3] = a.xin[3] ? a.xin[3][p] : 1.0;
+  if (a.t.xin[0]) {
+    x[0] = a.t.xin[0][p]; x[1] = a.t.xin[1][p]; x[2] = a.t.xin[2][p];
+    x[3] = a.t.xin[3] ? a.t.xin[3][p] : 1.0;
   }
   int flags = 0;
   if (end - beg < 2) {
@@ -87,8 +74,8 @@ __global__ __launch_bounds__(256) void tri_tracks_linear_kernel(TrackArgs a) {
   } else {
     double R[4][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
     for (int o = beg; o < end; ++o) {
-      const double* P = a.projs + 12 * (size_t)a.cam_idx[o];
-      const double u = a.u[o], w = a.v[o];
+      const double* P = a.t.projs + 12 * (size_t)a.t.cam_idx[o];
+      const double u = a.t.u[o], w = a.t.v[o];
       dlt_add_row(R, u * P[8] - P[0], u * P[9] - P[1], u * P[10] - P[2], u * P[11] - P[3]);    // tri:145
       dlt_add_row(R, w * P[8] - P[4], w * P[9] - P[5], w * P[10] - P[6], w * P[11] - P[7]);    // tri:146
     }
@@ -100,8 +87,8 @@ __global__ __launch_bounds__(256) void tri_tracks_linear_kernel(TrackArgs a) {
       flags = SFM_TRACK_NONFINITE;
     }
   }
-  a.xout[0][p] = x[0]; a.xout[1][p] = x[1]; a.xout[2][p] = x[2];
-  if (a.xout[3]) a.xout[3][p] = x[3];
+  a.t.xout[0][p] = x[0]; a.t.xout[1][p] = x[1]; a.t.xout[2][p] = x[2];
+  if (a.t.xout[3]) a.t.xout[3][p] = x[3];
   if (a.status) a.status[p] = flags;
 }
 
@@ -127,16 +114,16 @@ template <int G, int NC>
 __global__ __launch_bounds__(256) void tri_tracks_nonlinear_kernel(TrackArgs a) {
   extern __shared__ double lds_proj[];
   if (NC == 0 && a.proj_in_lds) {
-    for (int i = threadIdx.x; i < a.n_views * 12; i += blockDim.x) lds_proj[i] = a.projs[i];
+    for (int i = threadIdx.x; i < a.t.n_views * 12; i += blockDim.x) lds_proj[i] = a.t.projs[i];
     __syncthreads();
   }
-  const double* P_all = (NC == 0 && a.proj_in_lds) ? lds_proj : a.projs;
+  const double* P_all = (NC == 0 && a.proj_in_lds) ? lds_proj : a.t.projs;
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int p = (int)(t / G), lane = (int)(threadIdx.x % G);
-  if (p >= a.n_pts) return;               // whole groups leave together
-  const int beg = a.pt_ptr[p], end = a.pt_ptr[p + 1];
-  const double in0 = a.xin[0][p], in1 = a.xin[1][p], in2 = a.xin[2][p];
-  const double x3 = a.xin[3] ? a.xin[3][p] : 1.0;
+  if (p >= a.t.n_pts) return;               // whole groups leave together
+  const int beg = a.t.pt_ptr[p], end = a.t.pt_ptr[p + 1];
+  const double in0 = a.t.xin[0][p], in1 = a.t.xin[1][p], in2 = a.t.xin[2][p];
+  const double x3 = a.t.xin[3] ? a.t.xin[3][p] : 1.0;
   double x0 = in0, x1 = in1, x2 = in2;
   const bool eval = a.cost != nullptr || a.status != nullptr;
   double cost0 = 0, cost1 = 0, behind = 0;
@@ -152,8 +139,8 @@ __global__ __launch_bounds__(256) void tri_tracks_nonlinear_kernel(TrackArgs a) 
 #pragma unroll
       for (int i = 0; i < 12; ++i) kP[k][i] = 0;
       if (o < end) {
-        ku[k] = a.u[o]; kv[k] = a.v[o];
-        const double* P = a.projs + 12 * (size_t)a.cam_idx[o];
+        ku[k] = a.t.u[o]; kv[k] = a.t.v[o];
+        const double* P = a.t.projs + 12 * (size_t)a.t.cam_idx[o];
 #pragma unroll
         for (int i = 0; i < 12; ++i) kP[k][i] = P[i];
       }
@@ -176,9 +163,9 @@ __global__ __launch_bounds__(256) void tri_tracks_nonlinear_kernel(TrackArgs a) 
         }
       } else {
         for (int o = beg + lane; o < end; o += G) {
-          const double* P = P_all + 12 * (size_t)a.cam_idx[o];
-          if (last) track_residual(P, a.u[o], a.v[o], x0, x1, x2, x3, S.c, nb);
-          else track_view(P, a.u[o], a.v[o], x0, x1, x2, x3, S);
+          const double* P = P_all + 12 * (size_t)a.t.cam_idx[o];
+          if (last) track_residual(P, a.t.u[o], a.t.v[o], x0, x1, x2, x3, S.c, nb);
+          else track_view(P, a.t.u[o], a.t.v[o], x0, x1, x2, x3, S);
         }
       }
       if (last) {
@@ -205,20 +192,20 @@ __global__ __launch_bounds__(256) void tri_tracks_nonlinear_kernel(TrackArgs a) 
   }
 
   if (lane != 0) return;
-  a.xout[0][p] = x0; a.xout[1][p] = x1; a.xout[2][p] = x2;
-  if (a.xout[3]) a.xout[3][p] = x3;
-  if (a.cost) { a.cost[p] = cost0; a.cost[(size_t)a.n_pts + p] = cost1; }
+  a.t.xout[0][p] = x0; a.t.xout[1][p] = x1; a.t.xout[2][p] = x2;
+  if (a.t.xout[3]) a.t.xout[3][p] = x3;
+  if (a.cost) { a.cost[p] = cost0; a.cost[(size_t)a.t.n_pts + p] = cost1; }
   if (a.status) a.status[p] = a.status_or ? (a.status[p] | flags) : flags;
 }
 
 template <int G>
 static void launch_tracks_g(const TrackArgs& a, int nc, hipStream_t s) {
-  const long long threads = (long long)a.n_pts * G;
+  const long long threads = (long long)a.t.n_pts * G;
   const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
   if (nc == 2) tri_tracks_nonlinear_kernel<G, 2><<<grid, block, 0, s>>>(a);
   else if (nc == 4) tri_tracks_nonlinear_kernel<G, 4><<<grid, block, 0, s>>>(a);
   else if (nc == 6) tri_tracks_nonlinear_kernel<G, 6><<<grid, block, 0, s>>>(a);
-  else tri_tracks_nonlinear_kernel<G, 0><<<grid, block, a.proj_in_lds ? sizeof(double) * 12 * (size_t)a.n_views : 0, s>>>(a);
+  else tri_tracks_nonlinear_kernel<G, 0><<<grid, block, a.proj_in_lds ? sizeof(double) * 12 * (size_t)a.t.n_views : 0, s>>>(a);
 }
 
 // Automatic group width from n_pts, M and the longest track: the narrowest group whose lanes can
@@ -232,17 +219,17 @@ static int tracks_pick_group(int n_pts, long long M, int max_track) {
 
 // Enqueue the requested passes on s.  The CSR has been validated; max_track is its longest track.
 static int tracks_enqueue(TrackArgs a, int mode, int group, long long M, int max_track, hipStream_t s) {
-  if (a.n_pts <= 0) return SFM_OK;
+  if (a.t.n_pts <= 0) return SFM_OK;
   if (mode & SFM_TRACKS_LINEAR) {
-    tri_tracks_linear_kernel<<<(a.n_pts + 255) / 256, 256, 0, s>>>(a);
+    tri_tracks_linear_kernel<<<(a.t.n_pts + 255) / 256, 256, 0, s>>>(a);
     SFM_HIP(hipGetLastError());
-    for (int r = 0; r < 4; ++r) a.xin[r] = a.xout[r];      // the nonlinear pass starts from the DLT result
+    for (int r = 0; r < 4; ++r) a.t.xin[r] = a.t.xout[r];      // the nonlinear pass starts from the DLT result
     a.status_or = 1;
   }
   if (mode & SFM_TRACKS_NONLINEAR) {
-    const int g = group ? group : tracks_pick_group(a.n_pts, M, max_track);
+    const int g = group ? group : tracks_pick_group(a.t.n_pts, M, max_track);
     const int nc = max_track <= 2 * g ? 2 : (max_track <= 4 * g ? 4 : (max_track <= 6 * g ? 6 : 0));
-    a.proj_in_lds = a.n_views <= kTrkLdsViews;
+    a.proj_in_lds = a.t.n_views <= kTrkLdsViews;
     dispatch_group<1>(g, [&](auto G) { launch_tracks_g<decltype(G)::value>(a, nc, s); });
     SFM_HIP(hipGetLastError());
   }
@@ -280,21 +267,54 @@ int tracks_validate(const char* who, int n_pts, int n_views, long long M, const 
   return SFM_E_SHAPE;
 }
 
-static TrackArgs tracks_args(int n_pts, int n_views, long long M, const int* pt_ptr, const int* cam_idx, const double* uv,
-                             const double* projs, double lambda, int iters, const double* X_init, double* X_out, double* cost,
-                             int* status) {
-  TrackArgs a = {};
-  a.n_pts = n_pts; a.n_views = n_views;
-  a.pt_ptr = pt_ptr; a.cam_idx = cam_idx;
-  a.u = uv; a.v = uv + M;
-  a.projs = projs;
+TrackView track_view_free(int n_pts, int n_views, long long M, const int* pt_ptr, const int* cam_idx, const double* uv,
+                          const double* projs, const double* X_init, double* X_out) {
+  TrackView t = {n_pts, n_views, pt_ptr, cam_idx, uv, uv + M, projs, {}, {}};
   for (int r = 0; r < 4; ++r) {
-    a.xin[r] = X_init ? X_init + (size_t)r * n_pts : nullptr;
-    a.xout[r] = X_out + (size_t)r * n_pts;
+    t.xin[r] = X_init ? X_init + (size_t)r * n_pts : nullptr;
+    t.xout[r] = X_out + (size_t)r * n_pts;
   }
+  return t;
+}
+
+int track_view_resident(sfm_ba_problem* p, DevBuf<double>& projs, TrackView* out) {
+  const BaDev& d = p->dev;
+  SFM_TRY(projs.alloc(12 * (size_t)d.V, p->stream));
+  tracks_proj_from_prep_kernel<<<(12 * d.V + 255) / 256, 256, 0, p->stream>>>(d.V, d.prep[p->cur], projs.p);
+  SFM_HIP(hipGetLastError());
+  *out = TrackView{d.N, d.V, d.pt_ptr, d.cam_idx, d.u, d.v, projs.p, {d.px, d.py, d.pz, nullptr}, {d.px, d.py, d.pz, nullptr}};
+  return SFM_OK;
+}
+
+int tracks_check_ptrs(const char* who, const char* what, long long M, const void* pt_ptr, const void* cam_idx, const void* uv,
+                      const void* projs, const void* X_out) {
+  if (pt_ptr && projs && X_out && (M == 0 || (cam_idx && uv))) return SFM_OK;
+  set_error("%s: %s", who, what);
+  return SFM_E_SHAPE;
+}
+
+// The checks of both free forms, in their order; their pointers are the host's or the device's.
+static int tracks_check_free(const char* who, const char* null_what, int n_pts, int n_views, long long M, const void* pt_ptr,
+                             const void* cam_idx, const void* uv, const void* projs, int mode, int iters, int group,
+                             const void* X_init, const void* X_out) {
+  SFM_TRY(tracks_check_args(who, n_pts, n_views, M, mode, iters, group));
+  if (n_pts == 0) return SFM_OK;
+  if (!(mode & SFM_TRACKS_LINEAR) && X_init == nullptr) { set_error("%s: X_init is required without SFM_TRACKS_LINEAR", who); return SFM_E_SHAPE; }
+  return tracks_check_ptrs(who, null_what, M, pt_ptr, cam_idx, uv, projs, X_out);
+}
+
+// The one body of sfm_tri_tracks and sfm_tri_tracks_dev: checked arguments and device pointers in (n_pts > 0), the
+// kernels enqueued on s out.
+static int tracks_run(const char* who, int n_pts, int n_views, long long M, const int* d_pt_ptr, const int* d_cam_idx,
+                      const double* d_uv, const double* d_projs, int mode, double lambda, int iters, int group,
+                      const double* d_X_init, double* d_X_out, double* d_cost, int* d_status, hipStream_t s) {
+  int max_track = 0;
+  SFM_TRY(tracks_validate(who, n_pts, n_views, M, d_pt_ptr, d_cam_idx, &max_track, s));
+  TrackArgs a = {};
+  a.t = track_view_free(n_pts, n_views, M, d_pt_ptr, d_cam_idx, d_uv, d_projs, d_X_init, d_X_out);
   a.lambda = lambda; a.iters = iters;
-  a.cost = cost; a.status = status;
-  return a;
+  a.cost = d_cost; a.status = d_status;
+  return tracks_enqueue(a, mode, group, M, max_track, s);
 }
 
 }  // namespace sfm
@@ -308,55 +328,38 @@ int sfm_tri_tracks_auto_group(int n_pts, int64_t M, int max_track) { return trac
 int sfm_tri_tracks_dev(int n_pts, int n_views, int64_t M, const int* d_pt_ptr, const int* d_cam_idx, const double* d_uv,
                        const double* d_projs, int mode, double lambda, int iters, int group, const double* d_X_init,
                        double* d_X_out, double* d_cost, int* d_status, void* hip_stream) {
+  const char* who = "sfm_tri_tracks_dev";
   SFM_TRY(ensure_init());
-  SFM_TRY(tracks_check_args("sfm_tri_tracks_dev", n_pts, n_views, M, mode, iters, group));
-  if (!(mode & SFM_TRACKS_LINEAR) && d_X_init == nullptr && n_pts > 0) {
-    set_error("sfm_tri_tracks_dev: X_init is required without SFM_TRACKS_LINEAR");
-    return SFM_E_SHAPE;
-  }
+  SFM_TRY(tracks_check_free(who, "null device pointer", n_pts, n_views, M, d_pt_ptr, d_cam_idx, d_uv, d_projs, mode, iters, group,
+                            d_X_init, d_X_out));
   if (n_pts == 0) return SFM_OK;
-  if (!d_pt_ptr || !d_projs || !d_X_out || (M > 0 && (!d_cam_idx || !d_uv))) {
-    set_error("sfm_tri_tracks_dev: null device pointer");
-    return SFM_E_SHAPE;
-  }
   hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx().stream;
-  int max_track = 0;
-  SFM_TRY(tracks_validate("sfm_tri_tracks_dev", n_pts, n_views, M, d_pt_ptr, d_cam_idx, &max_track, s));
-  const TrackArgs a = tracks_args(n_pts, n_views, M, d_pt_ptr, d_cam_idx, d_uv, d_projs, lambda, iters, d_X_init, d_X_out,
-                                  d_cost, d_status);
-  return tracks_enqueue(a, mode, group, M, max_track, s);
+  return tracks_run(who, n_pts, n_views, M, d_pt_ptr, d_cam_idx, d_uv, d_projs, mode, lambda, iters, group, d_X_init, d_X_out,
+                    d_cost, d_status, s);
 }
 
 int sfm_tri_tracks(int n_pts, int n_views, int64_t M, const int* pt_ptr, const int* cam_idx, const double* uv,
                    const double* projs, int mode, double lambda, int iters, int group, const double* X_init, double* X_out,
                    double* cost, int* status) {
+  const char* who = "sfm_tri_tracks";
   SFM_TRY(ensure_init());
-  SFM_TRY(tracks_check_args("sfm_tri_tracks", n_pts, n_views, M, mode, iters, group));
-  if (!(mode & SFM_TRACKS_LINEAR) && X_init == nullptr && n_pts > 0) {
-    set_error("sfm_tri_tracks: X_init is required without SFM_TRACKS_LINEAR");
-    return SFM_E_SHAPE;
-  }
+  SFM_TRY(tracks_check_free(who, "null pointer", n_pts, n_views, M, pt_ptr, cam_idx, uv, projs, mode, iters, group, X_init, X_out));
   if (n_pts == 0) return SFM_OK;
-  if (!pt_ptr || !projs || !X_out || (M > 0 && (!cam_idx || !uv))) { set_error("sfm_tri_tracks: null pointer"); return SFM_E_SHAPE; }
   hipStream_t s = ctx().stream;
-  DevBuf<int> dPtr, dCam, dSt;
-  DevBuf<double> dUV, dP, dX, dO, dC;
-  SFM_TRY(dPtr.upload(pt_ptr, (size_t)n_pts + 1, s));
+  const size_t n = (size_t)n_pts;
+  DevBuf<int> dPtr, dCam;
+  DevBuf<double> dUV, dP, dX;
+  HostOut<double> oX, oCost;
+  HostOut<int> oStatus;
+  SFM_TRY(dPtr.upload(pt_ptr, n + 1, s));
   SFM_TRY(dCam.upload(cam_idx, (size_t)M, s));
   SFM_TRY(dUV.upload(uv, 2 * (size_t)M, s));
   SFM_TRY(dP.upload(projs, 12 * (size_t)n_views, s));
-  if (X_init) SFM_TRY(dX.upload(X_init, 4 * (size_t)n_pts, s));
-  SFM_TRY(dO.alloc(4 * (size_t)n_pts, s));
-  if (cost) SFM_TRY(dC.alloc(2 * (size_t)n_pts, s));
-  if (status) SFM_TRY(dSt.alloc((size_t)n_pts, s));
-  int max_track = 0;
-  SFM_TRY(tracks_validate("sfm_tri_tracks", n_pts, n_views, M, dPtr.p, dCam.p, &max_track, s));
-  const TrackArgs a = tracks_args(n_pts, n_views, M, dPtr.p, dCam.p, dUV.p, dP.p, lambda, iters, X_init ? dX.p : nullptr, dO.p,
-                                  cost ? dC.p : nullptr, status ? dSt.p : nullptr);
-  SFM_TRY(tracks_enqueue(a, mode, group, M, max_track, s));
-  SFM_TRY(dO.download(X_out, 4 * (size_t)n_pts, s));
-  if (cost) SFM_TRY(dC.download(cost, 2 * (size_t)n_pts, s));
-  if (status) SFM_TRY(dSt.download(status, (size_t)n_pts, s));
+  SFM_TRY(dX.upload_if(X_init, 4 * n, s));
+  SFM_TRY(oX.want(X_out, 4 * n, s)); SFM_TRY(oCost.want(cost, 2 * n, s)); SFM_TRY(oStatus.want(status, n, s));
+  SFM_TRY(tracks_run(who, n_pts, n_views, M, dPtr.p, dCam.p, dUV.p, dP.p, mode, lambda, iters, group, dX.p, oX.dev(),
+                     oCost.dev(), oStatus.dev(), s));
+  SFM_TRY(oX.fetch(s)); SFM_TRY(oCost.fetch(s)); SFM_TRY(oStatus.fetch(s));
   return stream_sync(s);
 }
 
@@ -368,24 +371,17 @@ int sfm_ba_refine_points(sfm_ba_problem* p, int mode, double lambda, int iters, 
   if (d.N == 0 || d.M == 0) return SFM_OK;
   hipStream_t s = p->stream;
   if (!p->prep_valid) SFM_TRY(ba_enqueue_prep(p));       // the expanded cameras the linearisation reads
-  DevBuf<double> dP, dC;
-  DevBuf<int> dSt;
-  SFM_TRY(dP.alloc(12 * (size_t)d.V, s));
-  SFM_TRY(tracks_enqueue_proj_from_prep(d.V, d.prep[p->cur], dP.p, s));
-  if (cost) SFM_TRY(dC.alloc(2 * (size_t)d.N, s));
-  if (status) SFM_TRY(dSt.alloc((size_t)d.N, s));
+  DevBuf<double> dP;
+  HostOut<double> oCost;
+  HostOut<int> oStatus;
   TrackArgs a = {};
-  a.n_pts = d.N; a.n_views = d.V;
-  a.pt_ptr = d.pt_ptr; a.cam_idx = d.cam_idx; a.u = d.u; a.v = d.v;
-  a.projs = dP.p;
-  a.xin[0] = d.px; a.xin[1] = d.py; a.xin[2] = d.pz; a.xin[3] = nullptr;      // W = 1
-  a.xout[0] = d.px; a.xout[1] = d.py; a.xout[2] = d.pz; a.xout[3] = nullptr;
+  SFM_TRY(track_view_resident(p, dP, &a.t));
+  SFM_TRY(oCost.want(cost, 2 * (size_t)d.N, s)); SFM_TRY(oStatus.want(status, (size_t)d.N, s));
   a.lambda = lambda; a.iters = iters;
-  a.cost = cost ? dC.p : nullptr; a.status = status ? dSt.p : nullptr;
+  a.cost = oCost.dev(); a.status = oStatus.dev();
   SFM_TRY(tracks_enqueue(a, mode, group, d.M, p->max_track, s));
   SFM_TRY(ba_reset_stats(p));                            // new points, as after sfm_ba_set_points
-  if (cost) SFM_TRY(dC.download(cost, 2 * (size_t)d.N, s));
-  if (status) SFM_TRY(dSt.download(status, (size_t)d.N, s));
+  SFM_TRY(oCost.fetch(s)); SFM_TRY(oStatus.fetch(s));
   return ba_sync_cam_status(p, "sfm_ba_refine_points", "");
 }
 

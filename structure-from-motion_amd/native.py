@@ -7,6 +7,7 @@ raises if no MI355X is visible.  Status codes map back to the exceptions the ref
 """
 import ctypes
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -301,11 +302,15 @@ def i32(a):
 
 
 def dptr(a):
-    return a.ctypes.data_as(_dp)
+    return a.ctypes.data_as(_dp) if a is not None else None      # None: an optional array the caller leaves out
 
 
 def iptr(a):
-    return a.ctypes.data_as(_ip)
+    return a.ctypes.data_as(_ip) if a is not None else None
+
+
+def _lptr(a):
+    return a.ctypes.data_as(_lp) if a is not None else None
 
 
 def init(device=0):
@@ -320,26 +325,24 @@ def synchronize():
     check(load().sfm_synchronize())
 
 
+def _task_table(fn, n):
+    rows = fn(int(n), None, 0)
+    out = np.zeros((max(rows, 1), 4), dtype=np.int32)
+    if rows > 0:
+        fn(int(n), iptr(out), rows)
+    return out[:rows]
+
+
 def flow_tasks(nbk):
     """Task table of the data-flow reduced solve for nbk block columns (host only; no device call): (n, 4) int32 rows
     {type, row, column, sort key} in the order the workgroups take them."""
-    lib = load()
-    n = lib.sfm_ba_flow_tasks(int(nbk), None, 0)
-    out = np.zeros((max(n, 1), 4), dtype=np.int32)
-    if n > 0:
-        lib.sfm_ba_flow_tasks(int(nbk), iptr(out), n)
-    return out[:n]
+    return _task_table(load().sfm_ba_flow_tasks, nbk)
 
 
 def flow_tasks_deferred(n_cams):
     """Task table of the data-flow solve for n_cams cameras when the split-K reduce rides in its launch (host only): rows
     {type, row, column, key}; type 5 = camera sums (camera, part), 6 = rows 8q..8q+7 (q = key & 3) of block (row, column) of S."""
-    lib = load()
-    n = lib.sfm_ba_flow_tasks_deferred(int(n_cams), None, 0)
-    out = np.zeros((max(n, 1), 4), dtype=np.int32)
-    if n > 0:
-        lib.sfm_ba_flow_tasks_deferred(int(n_cams), iptr(out), n)
-    return out[:n]
+    return _task_table(load().sfm_ba_flow_tasks_deferred, n_cams)
 
 
 def pool_redzone_active():
@@ -461,6 +464,18 @@ def _cam_mask(mask, n_cams):
     return mask
 
 
+def _check_cam_scale(cam_scale, n_cams):
+    """``cam_scale`` as a float64 (n_cams,) array of finite values (None stays None), or ValueError."""
+    if cam_scale is None:
+        return None
+    cam_scale = f64(cam_scale)
+    if cam_scale.shape != (int(n_cams),):
+        raise ValueError("cam_scale must be (n_cams,) with n_cams = %d, got %s" % (n_cams, cam_scale.shape))
+    if not np.all(np.isfinite(cam_scale)):
+        raise ValueError("cam_scale must be finite")
+    return cam_scale
+
+
 def _u8ptr(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if a is not None else None
 
@@ -512,13 +527,7 @@ def check_screen(n_cams, max_err2, cos_min_angle, min_obs, cam_scale, group=0):
     if int(min_obs) != min_obs or min_obs < 0:
         raise ValueError("min_obs must be an integer >= 0, got %r" % (min_obs,))
     group = _check_group(group)
-    if cam_scale is not None:
-        cam_scale = f64(cam_scale)
-        if cam_scale.shape != (int(n_cams),):
-            raise ValueError("cam_scale must be (n_cams,) with n_cams = %d, got %s" % (n_cams, cam_scale.shape))
-        if not np.all(np.isfinite(cam_scale)):
-            raise ValueError("cam_scale must be finite")
-    return max_err2, cos_min_angle, int(min_obs), cam_scale, group
+    return max_err2, cos_min_angle, int(min_obs), _check_cam_scale(cam_scale, n_cams), group
 
 
 def check_ransac(n_cams, max_err2, cos_min_angle=1.0, max_hyp=0, lam=0.5, iters=3, cam_scale=None, group=0):
@@ -537,13 +546,7 @@ def check_ransac(n_cams, max_err2, cos_min_angle=1.0, max_hyp=0, lam=0.5, iters=
         raise ValueError("lam must be >= 0, got %r" % lam)
     iters = _count("iters", iters)
     group = _check_group(group)
-    if cam_scale is not None:
-        cam_scale = f64(cam_scale)
-        if cam_scale.shape != (int(n_cams),):
-            raise ValueError("cam_scale must be (n_cams,) with n_cams = %d, got %s" % (n_cams, cam_scale.shape))
-        if not np.all(np.isfinite(cam_scale)):
-            raise ValueError("cam_scale must be finite")
-    return max_err2, cos_min_angle, max_hyp, lam, iters, cam_scale, group
+    return max_err2, cos_min_angle, max_hyp, lam, iters, _check_cam_scale(cam_scale, n_cams), group
 
 
 def check_loss(kind, delta):
@@ -619,9 +622,8 @@ def tri_tracks(pt_ptr, cam_idx, uv, projs, X_init=None, mode=TRACKS_NONLINEAR, l
     pt_ptr, cam_idx, uv, projs, x_init, mode, iters, group = check_tracks(pt_ptr, cam_idx, uv, projs, X_init, mode, iters, group)
     n_pts, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
     out = np.zeros((4, n_pts)); cost = np.zeros((2, n_pts)); status = np.zeros(n_pts, dtype=np.int32)
-    check(load().sfm_tri_tracks(n_pts, projs.shape[0], n_obs, iptr(pt_ptr), iptr(cam_idx) if n_obs else None,
-                                dptr(uv) if n_obs else None, dptr(projs), mode, float(lam), iters, group,
-                                dptr(x_init) if x_init is not None else None, dptr(out), dptr(cost), iptr(status)))
+    check(load().sfm_tri_tracks(n_pts, projs.shape[0], n_obs, iptr(pt_ptr), iptr(cam_idx), dptr(uv), dptr(projs), mode,
+                                float(lam), iters, group, dptr(x_init), dptr(out), dptr(cost), iptr(status)))
     return out, cost, status
 
 
@@ -646,6 +648,17 @@ def tri_ransac_pair(n, max_hyp, h):
     return count, int(i.value), int(j.value)
 
 
+def _ransac_outputs(n, m):
+    """The five output arrays of a robust triangulation of n points and m observations, as a namespace."""
+    return SimpleNamespace(inlier=np.zeros(m, dtype=np.uint8), n_inliers=np.zeros(n, dtype=np.int32),
+                           best_hyp=np.zeros(n, dtype=np.int32), status=np.zeros(n, dtype=np.int32),
+                           summary=np.zeros(6, dtype=np.int64))
+
+
+def _ransac_pointers(o):
+    return _u8ptr(o.inlier), iptr(o.n_inliers), iptr(o.best_hyp), iptr(o.status), _lptr(o.summary)
+
+
 def tri_tracks_ransac(pt_ptr, cam_idx, uv, projs, max_err2, cos_min_angle=1.0, max_hyp=0, lam=0.5, iters=3, cam_scale=None,
                       X_init=None, group=0):
     """Robust triangulation of every point from its own track (sfm_tri_tracks_ransac): pair hypotheses scored by their
@@ -657,15 +670,12 @@ def tri_tracks_ransac(pt_ptr, cam_idx, uv, projs, max_err2, cos_min_angle=1.0, m
     max_err2, cos_min_angle, max_hyp, lam, iters, cam_scale, group = check_ransac(projs.shape[0], max_err2, cos_min_angle, max_hyp,
                                                                                   lam, iters, cam_scale, group)
     n_pts, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
-    out = np.zeros((4, n_pts)); inlier = np.zeros(n_obs, dtype=np.uint8)
-    n_in = np.zeros(n_pts, dtype=np.int32); best = np.zeros(n_pts, dtype=np.int32); status = np.zeros(n_pts, dtype=np.int32)
-    summary = np.zeros(6, dtype=np.int64)
-    check(load().sfm_tri_tracks_ransac(n_pts, projs.shape[0], n_obs, iptr(pt_ptr), iptr(cam_idx) if n_obs else None,
-                                       dptr(uv) if n_obs else None, dptr(projs), dptr(cam_scale) if cam_scale is not None else None,
-                                       max_err2, cos_min_angle, max_hyp, lam, iters, group,
-                                       dptr(x_init) if x_init is not None else None, dptr(out), _u8ptr(inlier), iptr(n_in),
-                                       iptr(best), iptr(status), summary.ctypes.data_as(_lp)))
-    return out, inlier, n_in, best, status, summary
+    out = np.zeros((4, n_pts))
+    o = _ransac_outputs(n_pts, n_obs)
+    check(load().sfm_tri_tracks_ransac(n_pts, projs.shape[0], n_obs, iptr(pt_ptr), iptr(cam_idx), dptr(uv), dptr(projs),
+                                       dptr(cam_scale), max_err2, cos_min_angle, max_hyp, lam, iters, group, dptr(x_init),
+                                       dptr(out), *_ransac_pointers(o)))
+    return out, o.inlier, o.n_inliers, o.best_hyp, o.status, o.summary
 
 
 def tri_tracks_ransac_dev(n_pts, n_views, n_obs, d_pt_ptr, d_cam_idx, d_uv, d_projs, max_err2, cos_min_angle=1.0, max_hyp=0,
@@ -1126,21 +1136,11 @@ class BaProblem:
         consistent subset of its own track, in place.  Returns a namespace with ``inlier`` (M,) uint8, ``n_inliers`` (N,),
         ``best_hyp`` (N,), ``status`` (N,) of ``RANSAC_*`` bits and ``summary`` (6,) int64 in the order of
         ``RANSAC_SUMMARY``; ``want_outputs=False`` downloads nothing and returns None."""
-        from types import SimpleNamespace
         max_err2, cos_min_angle, max_hyp, lam, iters, cam_scale, group = check_ransac(self.n_cams, max_err2, cos_min_angle,
                                                                                       max_hyp, lam, iters, cam_scale, group)
-        scale = dptr(cam_scale) if cam_scale is not None else None
-        if not want_outputs:
-            check(self._lib.sfm_ba_retriangulate(self._h, max_err2, cos_min_angle, max_hyp, lam, iters, group, scale,
-                                                 None, None, None, None, None))
-            return None
-        n, m = self.info(INFO_N_PTS), self.info(INFO_N_OBS)
-        out = SimpleNamespace(inlier=np.zeros(m, dtype=np.uint8), n_inliers=np.zeros(n, dtype=np.int32),
-                              best_hyp=np.zeros(n, dtype=np.int32), status=np.zeros(n, dtype=np.int32),
-                              summary=np.zeros(6, dtype=np.int64))
-        check(self._lib.sfm_ba_retriangulate(self._h, max_err2, cos_min_angle, max_hyp, lam, iters, group, scale,
-                                             _u8ptr(out.inlier), iptr(out.n_inliers), iptr(out.best_hyp), iptr(out.status),
-                                             out.summary.ctypes.data_as(_lp)))
+        out = _ransac_outputs(self.info(INFO_N_PTS), self.info(INFO_N_OBS)) if want_outputs else None
+        check(self._lib.sfm_ba_retriangulate(self._h, max_err2, cos_min_angle, max_hyp, lam, iters, group, dptr(cam_scale),
+                                             *(_ransac_pointers(out) if want_outputs else (None,) * 5)))
         return out
 
     def refine_cameras(self, lam, iters, quirks=QUIRKS_REFERENCE, use_loss=False, mask=None, want_cost=False, want_status=False):
@@ -1153,8 +1153,7 @@ class BaProblem:
         cost = np.zeros((2, v)) if want_cost else None
         status = np.zeros(v, dtype=np.int32) if want_status else None
         check(self._lib.sfm_ba_refine_cameras(self._h, float(lam), int(iters), int(quirks), int(use_loss),
-                                              _u8ptr(mask),
-                                              dptr(cost) if want_cost else None, iptr(status) if want_status else None))
+                                              _u8ptr(mask), dptr(cost), iptr(status)))
         return cost, status
 
     def covariance(self, lam, quirks=QUIRKS_REFERENCE, use_loss=False, mask=None, group=0, want_cameras=True, want_points=True):
@@ -1164,7 +1163,6 @@ class BaProblem:
         (``sym3`` expands it), ``cam_status`` (V,) of ``COV_CAM_*`` bits, ``pt_status`` (N,) of ``COV_PT_*`` bits,
         ``sigma0_sq``, and ``pivot_camera``: None, or the camera at which the free cameras' system turned out not to be
         positive definite -- then the covariances are None and ``sigma0_sq`` is NaN.  Nothing is scaled by ``sigma0_sq``."""
-        from types import SimpleNamespace
         v, n = self.info(INFO_N_CAMS), self.info(INFO_N_PTS)
         group, mask = _check_group(group), _cam_mask(mask, v)
         out = SimpleNamespace(cam_cov=np.zeros((v, 7, 7)) if want_cameras else None,
@@ -1174,8 +1172,7 @@ class BaProblem:
         s0 = ctypes.c_double(float("nan"))
         st = self._lib.sfm_ba_covariance(self._h, float(lam), int(quirks), int(bool(use_loss)),
                                          _u8ptr(mask),
-                                         group, dptr(out.cam_cov) if want_cameras else None,
-                                         dptr(out.pt_cov) if want_points else None, iptr(out.cam_status), iptr(out.pt_status),
+                                         group, dptr(out.cam_cov), dptr(out.pt_cov), iptr(out.cam_status), iptr(out.pt_status),
                                          ctypes.byref(s0))
         if st == E_SINGULAR:
             out.pivot_camera = int(np.flatnonzero(out.cam_status & COV_CAM_PIVOT)[0])
@@ -1199,7 +1196,6 @@ class BaProblem:
         Returns a namespace: ``iters_done``, and per outer iteration ``cost``, ``cg_iters``, ``cg_rel``, ``cg_status``
         (``PCG_CONVERGED`` / ``PCG_MAX_ITERS`` / ``PCG_BREAKDOWN``).  Raises ``SfmSingularError`` (``.camera``) when a free
         camera's diagonal block does not factor; the state is then as it was."""
-        from types import SimpleNamespace
         lam, iters, mask, tol, max_cg, group = check_pcg(self.info(INFO_N_CAMS), lam, iters, mask, tol, max_cg, group)
         n = max(iters, 1)
         cost, rel = np.zeros(n), np.zeros(n)
@@ -1231,7 +1227,6 @@ class BaProblem:
         ``accepted``, ``stop`` (``LM_STOP_*``), ``lam`` (the damping the next trial would use), ``cost`` (of the state the
         problem is left in: the last accepted one), ``bad_camera`` (``LM_STOP_SINGULAR``) and ``log``, a structured array
         with the fields of ``LmTrial``, one row per trial."""
-        from types import SimpleNamespace
         opt, mask = check_lm(self.info(INFO_N_CAMS), mask, **options)
         log = (LmTrial * max(opt.max_trials, 1))()
         trials, accepted, stop, bad = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(-1)
@@ -1252,7 +1247,6 @@ class BaProblem:
         return ms
 
     def _screen(self, name, max_err2, cos_min_angle, min_obs, cam_scale, want_outputs, group):
-        from types import SimpleNamespace
         max_err2, cos_min_angle, min_obs, cam_scale, group = check_screen(self.n_cams, max_err2, cos_min_angle, min_obs,
                                                                           cam_scale, group)
         n, m = self.info(INFO_N_PTS), self.info(INFO_N_OBS)
@@ -1262,11 +1256,8 @@ class BaProblem:
             out.err2, out.depth, out.obs_flags = np.zeros(m), np.zeros(m), np.zeros(m, dtype=np.uint8)
             out.min_cos, out.pt_flags = np.ones(n), np.zeros(n, dtype=np.int32)
         check(getattr(self._lib, name)(self._h, max_err2, cos_min_angle, min_obs, group,
-                                         dptr(cam_scale) if cam_scale is not None else None,
-                                         dptr(out.err2) if want_outputs else None, dptr(out.depth) if want_outputs else None,
-                                         _u8ptr(out.obs_flags),
-                                         dptr(out.min_cos) if want_outputs else None,
-                                         iptr(out.pt_flags) if want_outputs else None, summary.ctypes.data_as(_lp)))
+                                         dptr(cam_scale), dptr(out.err2), dptr(out.depth), _u8ptr(out.obs_flags),
+                                         dptr(out.min_cos), iptr(out.pt_flags), _lptr(summary)))
         return out
 
     def screen(self, max_err2=float("inf"), cos_min_angle=1.0, min_obs=2, cam_scale=None, want_outputs=True, group=0):

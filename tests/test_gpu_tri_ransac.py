@@ -375,6 +375,62 @@ def test_dev_form_in_place_on_a_callers_stream(hip):
     assert same_bits(d_y.cpu().numpy(), run(hip, sc, 8)[0])
 
 
+# ---- 8 ------------------------------------------------------------------------------------------------------------
+def _subset_scene():
+    """14 cameras, 70 points, track lengths cycling through 0, 1, 2, 3, 5, 7, 13: an empty track, one too short, tracks a
+    lane keeps in registers and, at group 1, tracks beyond 6 G (the re-reading kernel, the tile-by-tile scoring)."""
+    rng = np.random.default_rng(105)
+    rots, C = rr._cameras(14, 120.0)
+    lengths = np.resize(np.array([0, 1, 2, 3, 5, 7, 13]), 70)
+    pts = rng.uniform(-rr.CUBE / 2.0, rr.CUBE / 2.0, (3, 70))
+    pt_ptr = np.concatenate(([0], np.cumsum(lengths)))
+    cam_idx = np.concatenate([np.sort(rng.choice(14, n, replace=False)) for n in lengths]).astype(np.int64)
+    return rr._finish(rots, C, pts, pt_ptr, cam_idx, rng, rng.random(cam_idx.shape[0]) < rr.BAD_SHARE)
+
+
+@pytest.mark.parametrize("group", [1, 8])
+def test_any_subset_of_the_outputs_gives_the_same_bytes(hip, group):
+    """Through the raw C calls: what a call computes does not depend on which optional outputs it was asked for."""
+    sc = _subset_scene()
+    lib = hip.load()
+    n, m = sc.n_pts, sc.cam_idx.shape[0]
+    projs = np.ascontiguousarray(sc.projs)
+    names = ("inlier", "n_inliers", "best_hyp", "status", "summary")
+
+    def ransac(wanted):
+        o = hip._ransac_outputs(n, m)
+        X = np.full((4, n), -7.25)
+        ptrs = [p if k in wanted else None for k, p in zip(names, hip._ransac_pointers(o))]
+        hip.check(lib.sfm_tri_tracks_ransac(n, 14, m, hip.iptr(sc.pt_ptr), hip.iptr(sc.cam_idx), hip.dptr(sc.uv), hip.dptr(projs),
+                                            hip.dptr(sc.cam_scale), rr.MAX_ERR2, rr.COS_MIN, 128, 0.5, 3, group, None, hip.dptr(X),
+                                            *ptrs))
+        return X, o
+
+    X_all, o_all = ransac(names)
+    assert o_all.summary[0] > 0 and o_all.summary[2] == 20 and o_all.inlier.any()      # the call did solve something
+    for wanted in [()] + [(k,) for k in names]:
+        X, o = ransac(wanted)
+        assert same_bits(X, X_all), wanted
+        for k in names:
+            got = getattr(o, k)
+            assert same_bits(got, getattr(o_all, k)) if k in wanted else not got.any(), (wanted, k)
+
+    def tracks(want_cost, want_status):
+        X = np.full((4, n), -7.25); cost = np.full((2, n), -7.25); status = np.full(n, -7, dtype=np.int32)
+        hip.check(lib.sfm_tri_tracks(n, 14, m, hip.iptr(sc.pt_ptr), hip.iptr(sc.cam_idx), hip.dptr(sc.uv), hip.dptr(projs),
+                                     hip.TRACKS_LINEAR | hip.TRACKS_NONLINEAR, 0.5, 5, group, None, hip.dptr(X),
+                                     hip.dptr(cost) if want_cost else None, hip.iptr(status) if want_status else None))
+        return X, cost, status
+
+    T_all = tracks(True, True)
+    assert np.all(T_all[0] != -7.25) and np.all(T_all[2] >= 0)
+    for want_cost, want_status in ((False, False), (True, False), (False, True)):
+        X, cost, status = tracks(want_cost, want_status)
+        assert same_bits(X, T_all[0]), (want_cost, want_status)
+        assert same_bits(cost, T_all[1]) if want_cost else np.all(cost == -7.25)
+        assert same_bits(status, T_all[2]) if want_status else np.all(status == -7)
+
+
 # ---- drop-in methods -----------------------------------------------------------------------------------------------------
 def test_triangulate_tracks_robust_equals_native(hip, sfm):
     sc, _ref = rr.scene_and_reference("proto1")

@@ -2,14 +2,15 @@
 """kernel_resources.py CSRC_DIR OUT.txt -- registers, scratch, occupancy and LDS of every kernel of the resident-scene files
 (sfm_ba_cov, sfm_ba_pcg, sfm_ba_motion, the linearise and backsub kernels of sfm_ba, the shared cost reduction), from
 -Rpass-analysis=kernel-resource-usage for gfx950; no GPU needed.  Run it on two checkouts and diff the tables
-(profiles/resident_ops/)."""
+(profiles/resident_ops/).  File names after OUT.txt replace that list: `... OUT.txt sfm_tri_ransac.hip` gives the table
+of the robust triangulation's kernels (profiles/track_ops/)."""
 import os
 import re
 import subprocess
 import sys
 
 csrc, out = sys.argv[1], sys.argv[2]
-FILES = ["sfm_ba_cov.hip", "sfm_ba_pcg.hip", "sfm_ba_motion.hip", "sfm_ba.hip", "sfm_ba_host.hip"]
+FILES = sys.argv[3:] or ["sfm_ba_cov.hip", "sfm_ba_pcg.hip", "sfm_ba_motion.hip", "sfm_ba.hip", "sfm_ba_host.hip"]
 KEEP_BA = ("ba_linearize_kernel", "ba_backsub_kernel")
 rows = []
 for f in FILES:
