@@ -535,6 +535,92 @@ int sfm_ba_refine_cameras(sfm_ba_problem* p, double lambda, int iters, int quirk
 /* host only, needs no device: how a camera of n_obs observations is worked on (any output may be NULL) */
 int sfm_ba_refine_cameras_plan(int64_t n_obs, int* n_slices, int* slice_obs, int* size_class);
 
+/* ---- robust resection of cameras: three-point hypotheses, inlier refit ---------------------------------------------
+ * sfm_ba_refine_cameras fits a camera by least squares over every observation it owns; a share of mismatched keys then
+ * moves the pose.  Here the consistent subset of a camera's observations is found first: the camera-side counterpart of
+ * the robust triangulation above.  A camera owns n observations: normalised keys u, v in the coordinates of the K-free
+ * projection [R(q)^T | -R(q)^T C], each with its point X; scale = cam_scale[c], or 1.  With s = R(q)^T X - R(q)^T C,
+ * err2 = scale^2 ((s0/s2 - u)^2 + (s1/s2 - v)^2) is sfm_ba_screen's quantity, and an observation is an INLIER of a pose
+ * iff s2 > 0, err2 is finite and err2 <= max_err2.  The rule, per camera:
+ *   1. n < 4: SFM_RESECT_TOO_FEW.
+ *   2. Hypotheses.  The T = n (n - 1) (n - 2) / 6 triples (i < j < l) are numbered in lexicographic order.  The camera has
+ *      H = min(T, max_hyp) hypotheses; hypothesis h is triple k = h when T <= max_hyp, else k = floor(h T / max_hyp) in
+ *      64-bit integers.  No random number anywhere.  max_hyp = 0 means 128; its range is 1 .. 65 536.  A camera of more
+ *      than 2^20 observations returns SFM_E_SHAPE naming the camera (T must fit 63 bits).
+ *   3. Poses of a triple.  Bearings f = (u, v, 1) / |(u, v, 1)|; a2 = |X_j - X_l|^2, b2 = |X_i - X_l|^2,
+ *      c2 = |X_i - X_j|^2; ca = f_j . f_l, cb = f_i . f_l, cg = f_i . f_j; depths s_j = x s_i, s_l = y s_i from Grunert's
+ *      quartic A4 y^4 + A3 y^3 + A2 y^2 + A1 y + A0 = 0 with p = (a2 - c2) / b2, q = (a2 + c2) / b2,
+ *        A4 = (p - 1)^2 - 4 (c2 / b2) ca^2
+ *        A3 = 4 (p (1 - p) cb - (1 - q) ca cg + 2 (c2 / b2) ca^2 cb)
+ *        A2 = 2 (p^2 - 1 + 2 p^2 cb^2 + 2 ((b2 - c2) / b2) ca^2 - 4 q ca cb cg + 2 ((b2 - a2) / b2) cg^2)
+ *        A1 = 4 (-p (1 + p) cb + 2 (a2 / b2) cg^2 cb - (1 - q) ca cg)
+ *        A0 = (1 + p)^2 - 4 (a2 / b2) cg^2
+ *        x = ((p - 1) y^2 - 2 p cb y + 1 + p) / (2 (cg - y ca)),   s_i = sqrt(b2 / (1 + y^2 - 2 y cb)).
+ *      Every real root with x, y, s_i > 0 gives a pose: R^T and t from the two right-handed frames spanned by
+ *      (P_j - P_i, (P_j - P_i) x (P_l - P_i)), once of the camera-frame points s f and once of the world points.  A
+ *      triple has at most four poses, numbered r = 0 .. 3 by ascending s_i.  Invalid: non-finite or zero a2, b2, c2, a
+ *      zero frame normal (collinear points), a zero or non-finite A4, a zero divisor, a non-finite pose, or a rotation
+ *      that sfm_rot_to_quat refuses (qw below 1e-6).  How the real roots are found is not part of the rule: a conjugate
+ *      pair whose imaginary part is below 1e-7 (1 + |real part|) counts as a double root, and every root is polished by two
+ *      Newton steps on the quartic; what one solver gets wrong is caught by step 4.
+ *   4. Triple gate.  A pose is invalid unless its three generating observations are inliers of it.
+ *   5. Score, lexicographic: the inlier count over all n observations (an integer); then the lower h; then the lower r.
+ *      A winner needs a count of at least 4 (a model that explains only its own three points explains nothing), otherwise
+ *      SFM_RESECT_NO_MODEL.  The count and the winner depend on nothing but the camera's own data.
+ *   6. Refit.  The winner becomes cam7 = [C, q] = [-R t, sfm_rot_to_quat(R)]; then `iters` steps of sfm_ba_refine_cameras'
+ *      update over the observations that are inliers of the winner's pose [R^T | t] (the mask fixed, no loss, the Q2 bit
+ *      of `quirks` honoured).  The refit stands iff every solve and every expansion of the camera succeeded, it is finite
+ *      and its own inlier count over all n is at least the winner's; otherwise the hypothesis camera stands and
+ *      SFM_RESECT_KEPT_HYPOTHESIS is set.  obs_inlier / n_inliers describe the camera that stands, EXPANDED as every
+ *      operation on a scene expands it and projected as sfm_ba_screen projects: on the resident scene sfm_ba_resect(t)
+ *      followed by sfm_ba_screen(t) shows HIGH_ERROR | BEHIND | NONFINITE exactly where obs_inlier == 0, for every solved
+ *      camera, by construction.
+ *   7. With SFM_RESECT_TOO_FEW or SFM_RESECT_NO_MODEL the camera comes out bit for bit as it went in (cams_init, the
+ *      resident camera, or (0, 0, 0, 1, 0, 0, 0) without cams_init), n_inliers = 0, best_hyp = -1, its obs_inlier entries are
+ *      0.  A held camera (cam_mask[c] == 0, resident form) is untouched and SFM_RESECT_HELD, but it is still judged at its
+ *      current expansion: obs_inlier and n_inliers are filled for it.
+ *   8. summary[6], counted on the device with integer atomics: cameras solved, cameras NO_MODEL, cameras TOO_FEW, cameras
+ *      KEPT_HYPOTHESIS, observations flagged inlier, observations of solved cameras flagged outlier.
+ * Determinism: no floating-point atomic; best_hyp and the counts are integers and do not depend on the grid or on
+ * timing; the refit's 36 sums are formed per slice of 64 consecutive observations and added in slice order, so a camera's
+ * bits depend on its own observations, their points and the options only.  A camera of any size takes the same path.
+ * Free form: view_ptr[n_views + 1] (HOST in both forms: the launches are planned from it) delimits the observations of a
+ * view in uv = [2][M] and X = [3][M] (the point of every observation).  A NaN or negative max_err2, max_hyp outside
+ * 0 .. 65 536, iters < 0, a negative or NaN lambda, or a view_ptr that does not start at 0, decreases or does not end at M
+ * return SFM_E_SHAPE and launch nothing.  cam_scale, cams_init and every output but cams_out may be NULL.  The _dev form
+ * takes device pointers (d_summary: int64[6] on the device) and runs on hip_stream; d_cams_out may equal d_cams_init; it
+ * returns when the work is done (its work buffers go back to the pool). */
+#define SFM_RESECT_TOO_FEW          1   /* the camera has fewer than 4 observations */
+#define SFM_RESECT_NO_MODEL         2   /* no valid pose with at least 4 inliers */
+#define SFM_RESECT_KEPT_HYPOTHESIS  4   /* the refit did not stand: the camera is the winning hypothesis itself */
+#define SFM_RESECT_SAMPLED          8   /* T > max_hyp: not every triple was a hypothesis (informational) */
+#define SFM_RESECT_HELD            16   /* cam_mask[c] == 0: untouched, judged only */
+int sfm_resect_ransac(int n_views, const int* view_ptr /*host [n_views+1]*/, int64_t M, const double* uv /*[2][M]*/,
+                      const double* X /*[3][M]*/, const double* cam_scale /*[n_views] or NULL*/, double max_err2,
+                      int max_hyp, double lambda, int iters, int quirks, const double* cams_init /*[n_views][7] or NULL*/,
+                      double* cams_out /*[n_views][7]*/, unsigned char* obs_inlier /*[M] or NULL*/,
+                      int* n_inliers /*[n_views] or NULL*/, int* best_hyp /*[n_views] or NULL*/,
+                      int* status /*[n_views] or NULL*/, int64_t* summary /*[6] or NULL*/);
+int sfm_resect_ransac_dev(int n_views, const int* view_ptr /*host [n_views+1]*/, int64_t M, const double* d_uv,
+                          const double* d_X, const double* d_cam_scale, double max_err2, int max_hyp, double lambda,
+                          int iters, int quirks, const double* d_cams_init, double* d_cams_out /* may equal d_cams_init */,
+                          unsigned char* d_obs_inlier, int* d_n_inliers, int* d_best_hyp, int* d_status,
+                          int64_t* d_summary, void* hip_stream);
+/* The same on the resident scene, in place, following sfm_ba_refine_cameras: a camera's observations are those of the
+ * scene's camera-major list (ascending point), its points the resident ones.  Completes a deferred back substitution
+ * first; only cameras move and they are treated as by sfm_ba_set_cameras (the cost history restarts, the prepared form is
+ * rebuilt); points, observations, options, the loss and captured graphs are untouched.  sfm_ba_resect(t) followed by
+ * sfm_ba_cull(t) removes the flagged observations of the solved cameras.  With a communicator attached it is refused
+ * (SFM_E_SHAPE).  cam_mask, cam_scale and the outputs are HOST arrays or NULL; obs_inlier is in the scene's observation
+ * order.  A problem without observations returns SFM_OK with every free camera TOO_FEW. */
+int sfm_ba_resect(sfm_ba_problem* p, double max_err2, int max_hyp, double lambda, int iters, int quirks,
+                  const unsigned char* cam_mask /*host [V] or NULL = every camera*/, const double* cam_scale /*host [V] or NULL*/,
+                  unsigned char* obs_inlier /*host [M]*/, int* n_inliers /*host [V]*/, int* best_hyp /*host [V]*/,
+                  int* status /*host [V]*/, int64_t* summary /*[6]*/);
+/* Host only, needs no device: the hypothesis count H of a camera of n observations (0 for n < 3, n > 2^20 or a max_hyp
+ * out of range) and, for 0 <= h < H, the triple (*i < *j < *l) of hypothesis h. */
+int sfm_resect_triple(int n, int max_hyp, int h, int* i, int* j, int* l);
+
 /* ---- covariance of the resident scene: per-camera and per-point blocks ---------------------------------------------
  * How well the current state is determined.  With H = J^T J + lambda I = [A B; B^T D] of one linearisation at the current
  * state (r, Jp, Jx exactly as the iterations form them, the Q2 bit of `quirks` honoured; with use_loss = 1 and a loss on

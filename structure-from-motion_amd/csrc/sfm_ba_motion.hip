@@ -24,15 +24,14 @@
 
 #include "sfm_ba.h"
 #include "sfm_ba_terms.h"
+#include "sfm_cam_fit.h"
 
 namespace sfm {
 
-constexpr int kMoPerLane = 4;        // consecutive observations a lane keeps in registers: a slice (kCamSlice) is 16 lanes' worth
 constexpr int kMoWaveObs = 256;      // size class 1: one wave
 constexpr int kMoBlockObs = 1024;    // size class 2: four waves; the larger classes work through 1 024 observations at a time
 constexpr int kMoStreamObs = 16384;  // size class 3: one workgroup streams the camera's observations in every pass; beyond it
                                      // (class 4) a pass is spread over one workgroup per 1 024 observations and a second launch
-constexpr int kMoSums = 36;          // U lower triangle (28) | g (7) | cost share
 constexpr int kMoDone = 1 << 30;     // internal status bit of the multi-launch path: the camera needs no further pass
 
 // ---------------------------------------------------------------------------------------------
@@ -49,7 +48,6 @@ struct MoArgs {
   int* status;                  // [V]
 };
 
-struct MoObs { double u, v, X, Y, Z; };
 
 // entry i of the camera's list (observation by index, its point through obs_pt)
 __device__ __forceinline__ void mo_load(const BaDev& d, const int* __restrict__ list, int i, MoObs& ob) {
@@ -57,79 +55,6 @@ __device__ __forceinline__ void mo_load(const BaDev& d, const int* __restrict__ 
   const int p = d.obs_pt[o];
   ob.u = d.u[o]; ob.v = d.v[o];
   ob.X = d.px[p]; ob.Y = d.py[p]; ob.Z = d.pz[p];
-}
-
-// one observation into the 36 sums; behind: s[2] <= 0 at this camera
-template <int LOSS>
-__device__ __forceinline__ void mo_accumulate(const CamPrep& c, const MoObs& ob, int quirks, const LossArg<LOSS>& la,
-                                              double (&acc)[kMoSums], int& behind) {
-  double r[2], Jp[14], Jx[6], rho = 0;
-  obs_terms_loss<LOSS>(c, ob.X, ob.Y, ob.Z, ob.u, ob.v, quirks, la, r, Jp, Jx, rho);
-  if constexpr (LOSS == SFM_LOSS_NONE) rho = r[0] * r[0] + r[1] * r[1];
-  double s[3];
-  project_cam(c, ob.X, ob.Y, ob.Z, 1.0, s);
-  behind |= s[2] <= 0.0 ? 1 : 0;
-  int k = 0;
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {
-#pragma unroll
-    for (int j = 0; j <= i; ++j) { acc[k] += Jp[i] * Jp[j] + Jp[7 + i] * Jp[7 + j]; ++k; }
-  }
-#pragma unroll
-  for (int i = 0; i < 7; ++i) acc[28 + i] += Jp[i] * r[0] + Jp[7 + i] * r[1];
-  acc[35] += rho;
-}
-
-// which three of the 36 sums a lane holds after mo_fold_row
-__device__ __forceinline__ void mo_fold_own(int lane, int (&own)[3]) {
-  int i36[kMoSums], i18[18], i9[9], i5[5];
-#pragma unroll
-  for (int k = 0; k < kMoSums; ++k) i36[k] = k;
-  fold_index(i36, i18, (lane & 8) != 0);
-  fold_index(i18, i9, (lane & 4) != 0);
-  fold_index(i9, i5, (lane & 2) != 0);
-  fold_index(i5, own, (lane & 1) != 0);
-}
-
-// the 36 totals of a 16-lane row (one slice) -> row[36] in LDS (fold_half, sfm_common.h)
-__device__ __forceinline__ void mo_fold_row(const double (&acc)[kMoSums], const int (&own)[3], int lane, double* row) {
-  double f18[18], f9[9], f5[5], f3[3];
-  fold_half<0x140>(acc, f18, (lane & 8) != 0);
-  fold_half<0x141>(f18, f9, (lane & 4) != 0);
-  fold_half<0x4E>(f9, f5, (lane & 2) != 0);
-  fold_half<0xB1>(f5, f3, (lane & 1) != 0);
-#pragma unroll
-  for (int j = 0; j < 3; ++j) row[own[j]] = f3[j];
-}
-
-// 0.0 when every one of the n values is finite, NaN otherwise
-__device__ __forceinline__ double mo_finite_probe(const double* v, int n) {
-  double chk = 0;
-  for (int k = 0; k < n; ++k) chk += v[k] * 0.0;
-  return chk;
-}
-
-// The serial part, carried out by every thread on the same sums: dp = (U + lambda I)^-1 g, cam += dp, q /= |q|, and the next
-// prepared camera.  The quaternion was normalised two lines up, so the determinant / inverse test of the rotation cannot
-// fire (cam_prepare_dev<false>, sfm_common.h); false: a non-finite camera or qw ~ 0.
-__device__ __forceinline__ bool mo_step(const double* sums, double lambda, double (&params)[7], CamPrep& c) {
-  double a[28], b[7];
-#pragma unroll
-  for (int k = 0; k < 28; ++k) a[k] = sums[k];
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    a[i * (i + 1) / 2 + i] += lambda;
-    b[i] = sums[28 + i];
-  }
-  solve7_spd(a, b);
-#pragma unroll
-  for (int i = 0; i < 7; ++i) params[i] += b[i];
-  const double inq = rsqrt_nr(params[3] * params[3] + params[4] * params[4] + params[5] * params[5] + params[6] * params[6]);
-#pragma unroll
-  for (int i = 3; i < 7; ++i) params[i] *= inq;
-  const double chk = mo_finite_probe(params, 7);
-  const int st = cam_prepare_dev<false>(params, &c);
-  return st == SFM_OK && chk == 0.0;
 }
 
 // One workgroup per camera of n_lo .. n_hi observations (the other size classes' launches skip it).  THREADS = 64 serves

@@ -130,4 +130,8 @@ __device__ __forceinline__ void sym3_apply(const double* di, const double* g, do
 __global__ void ba_point_cost_reduce_kernel(int N, const double* __restrict__ cost_pt, const int* __restrict__ pt_ptr,
                                             double* __restrict__ out);
 
+// cams [V][7] -> their expanded form, one thread per camera; status[2]: first failing code and its camera (cam_prepare).
+// (defined once, in sfm_ba.hip)
+__global__ void ba_cam_prep_kernel(int V, const double* __restrict__ cams, CamPrep* __restrict__ prep, int* __restrict__ status);
+
 }  // namespace sfm

@@ -18,6 +18,7 @@
 
 #include "sfm_ba.h"
 #include "sfm_track_obs.h"      // contraction is off from here on
+#include "sfm_hyp_number.h"
 
 namespace sfm {
 
@@ -28,28 +29,6 @@ constexpr int kRanMaxHyp = 65536;
 constexpr int kRanDefaultHyp = 128;
 
 static_assert(sizeof(CamPrep) == 19 * sizeof(double), "the centres of the prepared cameras are read with a stride of 19 doubles");
-
-// ---- the numbering of the hypotheses (host and device) ----
-__host__ __device__ inline long long ransac_pair_count(int n) { return (long long)n * (n - 1) / 2; }
-
-// Pair number of hypothesis h: h itself while every pair is a hypothesis, else floor(h P / max_hyp) -- split as
-// h (P / max_hyp) + floor(h (P % max_hyp) / max_hyp), which is the same integer and stays below 2^63.
-__host__ __device__ inline long long ransac_pair_number(long long P, int max_hyp, int h) {
-  if (P <= max_hyp) return h;
-  return (long long)h * (P / max_hyp) + (long long)h * (P % max_hyp) / max_hyp;
-}
-
-// Pair k of the n (n - 1) / 2 pairs (i < j) in lexicographic order: r (2 n - r - 1) / 2 pairs precede row r.  The square
-// root gives the row to within a few units (its argument exceeds 2^53 for long tracks); the two loops make it exact.
-__host__ __device__ inline void ransac_pair_of(int n, long long k, int* i, int* j) {
-  const double b = 2.0 * n - 1.0;
-  long long r = (long long)((b - sqrt(fmax(b * b - 8.0 * (double)k, 0.0))) * 0.5);
-  r = r < 0 ? 0 : (r > n - 2 ? n - 2 : r);
-  while (r > 0 && r * (2LL * n - r - 1) / 2 > k) --r;
-  while (r < n - 2 && (r + 1) * (2LL * n - r - 2) / 2 <= k) ++r;
-  *i = (int)r;
-  *j = (int)(r + 1 + (k - r * (2LL * n - r - 1) / 2));
-}
 
 struct RansacArgs {
   TrackView t;                  // null input rows stand for (0, 0, 0, 1)

@@ -49,6 +49,9 @@ PT_TOO_FEW, PT_LOW_ANGLE, PT_EMPTY = 1, 2, 4
 RANSAC_TOO_FEW, RANSAC_NO_MODEL, RANSAC_KEPT_HYPOTHESIS, RANSAC_SAMPLED = 1, 2, 4, 8
 RANSAC_MAX_HYP, RANSAC_DEFAULT_HYP = 65536, 128
 RANSAC_SUMMARY = ("pts_solved", "pts_no_model", "pts_too_few", "pts_kept_hypothesis", "obs_inlier", "obs_outlier")
+RESECT_TOO_FEW, RESECT_NO_MODEL, RESECT_KEPT_HYPOTHESIS, RESECT_SAMPLED, RESECT_HELD = 1, 2, 4, 8, 16
+RESECT_MAX_HYP, RESECT_DEFAULT_HYP, RESECT_MAX_OBS = 65536, 128, 1 << 20
+RESECT_SUMMARY = ("cams_solved", "cams_no_model", "cams_too_few", "cams_kept_hypothesis", "obs_inlier", "obs_outlier")
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2
 CAM_EMPTY, CAM_NONFINITE, CAM_BEHIND, CAM_HELD = 1, 2, 4, 8
 COV_CAM_HELD, COV_CAM_PIVOT, COV_PT_EMPTY, COV_PT_SINGULAR = 8, 16, 4, 8
@@ -219,6 +222,10 @@ SIGNATURES = {
     "sfm_ba_reduced_system_loss": [ci, ci, i64, _ip, _ip, _dp, _dp, _dp, cd, ci, ci, ci, cd, _dp, _dp],
     "sfm_ba_refine_cameras": [vp, cd, ci, ci, ci, ctypes.POINTER(ctypes.c_uint8), _dp, _ip],
     "sfm_ba_refine_cameras_plan": [i64, _ip, _ip, _ip],
+    "sfm_resect_ransac": [ci, _ip, i64, _dp, _dp, _dp, cd, ci, cd, ci, ci, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
+    "sfm_resect_ransac_dev": [ci, _ip, i64, vp, vp, vp, cd, ci, cd, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp],
+    "sfm_ba_resect": [vp, cd, ci, cd, ci, ci, ctypes.POINTER(ctypes.c_uint8), _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
+    "sfm_resect_triple": [ci, ci, ci, _ip, _ip, _ip],
     "sfm_ba_covariance": [vp, cd, ci, ci, ctypes.POINTER(ctypes.c_uint8), ci, _dp, _dp, _ip, _ip, _dp],
     "sfm_ba_covariance_plan": [ci, _ip, _ip, _ip, _ip],
     "sfm_ba_covariance_times": [vp, _dp],
@@ -549,6 +556,34 @@ def check_ransac(n_cams, max_err2, cos_min_angle=1.0, max_hyp=0, lam=0.5, iters=
     return max_err2, cos_min_angle, max_hyp, lam, iters, _check_cam_scale(cam_scale, n_cams), group
 
 
+def check_resect(n_cams, max_err2, max_hyp=0, lam=0.5, iters=3, mask=None, cam_scale=None):
+    """Arguments of a ``resect_ransac`` / ``BaProblem.resect`` call, without a device: returns
+    ``(max_err2, max_hyp, lam, iters, mask, cam_scale)`` converted or raises ValueError -- everything sfm_resect_ransac
+    refuses before it looks at the views."""
+    max_err2, lam = float(max_err2), float(lam)
+    if not max_err2 >= 0.0:
+        raise ValueError("max_err2 must be >= 0, got %r" % max_err2)
+    max_hyp = _count("max_hyp", max_hyp)
+    if max_hyp > RESECT_MAX_HYP:
+        raise ValueError("max_hyp must be in 1 .. %d (0 = %d), got %r" % (RESECT_MAX_HYP, RESECT_DEFAULT_HYP, max_hyp))
+    if not lam >= 0.0:
+        raise ValueError("lam must be >= 0, got %r" % lam)
+    iters = _count("iters", iters)
+    return max_err2, max_hyp, lam, iters, _cam_mask(mask, n_cams), _check_cam_scale(cam_scale, n_cams)
+
+
+def check_resect_views(view_ptr, uv, X):
+    """The free form's arrays, without a device: ``(view_ptr int32 (V + 1,), uv (2, M), X (3, M))`` converted or ValueError --
+    view_ptr must start at 0, not decrease and end at M."""
+    view_ptr = np.ascontiguousarray(view_ptr, dtype=np.int32).ravel()
+    uv, X = f64(uv), f64(X)
+    if uv.ndim != 2 or uv.shape[0] != 2 or X.ndim != 2 or X.shape != (3, uv.shape[1]):
+        raise ValueError("uv must be (2, M) and X (3, M), got %r and %r" % (uv.shape, X.shape))
+    if view_ptr.shape[0] < 1 or view_ptr[0] != 0 or view_ptr[-1] != uv.shape[1] or np.any(np.diff(view_ptr) < 0):
+        raise ValueError("view_ptr must start at 0, not decrease and end at M = %d" % uv.shape[1])
+    return view_ptr, uv, X
+
+
 def check_loss(kind, delta):
     """Arguments of a ``BaProblem.set_loss`` call, without a device: returns ``(kind, delta)`` converted or raises ValueError.
     ``kind`` is ``LOSS_NONE`` / ``LOSS_HUBER`` / ``LOSS_CAUCHY`` or its name; ``delta`` (normalised units) must be finite and
@@ -689,6 +724,46 @@ def tri_tracks_ransac_dev(n_pts, n_views, n_obs, d_pt_ptr, d_cam_idx, d_uv, d_pr
                                            _vp(d_projs), _vp(d_cam_scale), max_err2, cos_min_angle, max_hyp, lam, iters, group,
                                            _vp(d_x_init), _vp(d_x_out), _vp(d_inlier), _vp(d_n_inliers), _vp(d_best_hyp),
                                            _vp(d_status), _vp(d_summary), _vp(stream)))
+
+
+def resect_triple(n, max_hyp, h):
+    """``(H, i, j, l)``: the hypothesis count of a camera of ``n`` observations and the triple of hypothesis ``h``
+    (sfm_resect_triple; host only).  ``i = j = l = -1`` when ``h`` is not in ``0 .. H - 1``."""
+    i, j, l = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    count = int(load().sfm_resect_triple(int(n), int(max_hyp), int(h), ctypes.byref(i), ctypes.byref(j), ctypes.byref(l)))
+    return count, int(i.value), int(j.value), int(l.value)
+
+
+def resect_ransac(view_ptr, uv, X, max_err2, max_hyp=0, lam=0.5, iters=3, quirks=QUIRKS_REFERENCE, cam_scale=None, cams_init=None):
+    """Robust resection of every view from its own observations (sfm_resect_ransac): three-point hypotheses scored by
+    their inlier count, then a refit over the winner's inliers.  ``view_ptr`` (V + 1,) delimits the observations of a view
+    in ``uv`` (2, M) normalised keys and ``X`` (3, M) their points; ``cam_scale`` (V,) multiplies a view's residuals (None:
+    1); ``cams_init`` (V, 7) is what an unsolved view returns (None: the identity at the origin).  Returns ``cams (V, 7),
+    inlier (M,) uint8, n_inliers (V,), best_hyp (V,), status (V,) of RESECT_* bits, summary (6,) int64`` in the order of
+    ``RESECT_SUMMARY``."""
+    view_ptr, uv, X = check_resect_views(view_ptr, uv, X)
+    n_views, n_obs = view_ptr.shape[0] - 1, uv.shape[1]
+    max_err2, max_hyp, lam, iters, _mask, cam_scale = check_resect(n_views, max_err2, max_hyp, lam, iters, None, cam_scale)
+    if cams_init is not None:
+        cams_init = f64(cams_init)
+        if cams_init.shape != (n_views, 7):
+            raise ValueError("cams_init must be (%d, 7), got %r" % (n_views, cams_init.shape))
+    cams = np.zeros((n_views, 7))
+    o = _ransac_outputs(n_views, n_obs)
+    check(load().sfm_resect_ransac(n_views, iptr(view_ptr), n_obs, dptr(uv), dptr(X), dptr(cam_scale), max_err2, max_hyp, lam,
+                                   iters, int(quirks), dptr(cams_init), dptr(cams), *_ransac_pointers(o)))
+    return cams, o.inlier, o.n_inliers, o.best_hyp, o.status, o.summary
+
+
+def resect_ransac_dev(view_ptr, n_obs, d_uv, d_X, max_err2, max_hyp=0, lam=0.5, iters=3, quirks=QUIRKS_REFERENCE, d_cam_scale=0,
+                      d_cams_init=0, d_cams_out=0, d_inlier=0, d_n_inliers=0, d_best_hyp=0, d_status=0, d_summary=0, stream=0):
+    """``resect_ransac`` on device pointers and a caller's stream (sfm_resect_ransac_dev); ``view_ptr`` stays a host array,
+    ``d_cams_out`` may equal ``d_cams_init``, optional arrays are 0."""
+    view_ptr = np.ascontiguousarray(view_ptr, dtype=np.int32).ravel()
+    max_err2, max_hyp, lam, iters, _mask, _s = check_resect(view_ptr.shape[0] - 1, max_err2, max_hyp, lam, iters)
+    check(load().sfm_resect_ransac_dev(view_ptr.shape[0] - 1, iptr(view_ptr), int(n_obs), _vp(d_uv), _vp(d_X), _vp(d_cam_scale),
+                                       max_err2, max_hyp, lam, iters, int(quirks), _vp(d_cams_init), _vp(d_cams_out), _vp(d_inlier),
+                                       _vp(d_n_inliers), _vp(d_best_hyp), _vp(d_status), _vp(d_summary), _vp(stream)))
 
 
 def pnp_nonlinear(uv_pix, pts_h, intrinsic, rot0, loc0, lam, iters, quirks=QUIRKS_REFERENCE):
@@ -1141,6 +1216,19 @@ class BaProblem:
         out = _ransac_outputs(self.info(INFO_N_PTS), self.info(INFO_N_OBS)) if want_outputs else None
         check(self._lib.sfm_ba_retriangulate(self._h, max_err2, cos_min_angle, max_hyp, lam, iters, group, dptr(cam_scale),
                                              *(_ransac_pointers(out) if want_outputs else (None,) * 5)))
+        return out
+
+    def resect(self, max_err2, max_hyp=0, lam=0.5, iters=3, quirks=QUIRKS_REFERENCE, mask=None, cam_scale=None, want_outputs=True):
+        """Robust resection of the resident cameras, points held (sfm_ba_resect): every camera from the consistent subset
+        of its own observations, in place.  ``mask`` (V,): cameras with a zero entry are held and only judged.  Returns a
+        namespace with ``inlier`` (M,) uint8 in the scene's observation order, ``n_inliers`` (V,), ``best_hyp`` (V,),
+        ``status`` (V,) of ``RESECT_*`` bits and ``summary`` (6,) int64 in the order of ``RESECT_SUMMARY``;
+        ``want_outputs=False`` downloads nothing and returns None."""
+        v = self.info(INFO_N_CAMS)
+        max_err2, max_hyp, lam, iters, mask, cam_scale = check_resect(v, max_err2, max_hyp, lam, iters, mask, cam_scale)
+        out = _ransac_outputs(v, self.info(INFO_N_OBS)) if want_outputs else None
+        check(self._lib.sfm_ba_resect(self._h, max_err2, max_hyp, lam, iters, int(quirks), _u8ptr(mask), dptr(cam_scale),
+                                      *(_ransac_pointers(out) if want_outputs else (None,) * 5)))
         return out
 
     def refine_cameras(self, lam, iters, quirks=QUIRKS_REFERENCE, use_loss=False, mask=None, want_cost=False, want_status=False):

@@ -282,6 +282,36 @@ class HipCamposeMixin:
             ini_rot, ini_loc, damping_factor, iteration)
         return sel.tolist(), ref_rot, ref_loc          # a list is the reference's return type (campose:246)
 
+    def estimate_cam_pose_robust(self, key_2d_pts, tri_3d_pts, intrinsic_mat, max_reproj_px=4.0, max_hyp=128, iteration=None,
+                                 damping_factor=None):
+        """``estimate_cam_pose_pnp`` by calibrated three-point hypotheses (``native.resect_ransac``; no reference counterpart):
+        every triple of the view's correspondences (at most ``max_hyp``, evenly spaced, no random number) proposes up to four
+        poses, the pose with the most correspondences within ``max_reproj_px`` wins and is refitted over those.  The keys are
+        normalised with ``inv(K)``; the pixel threshold scales the normalised residual by ``sqrt(|k[0, 0] k[1, 1]|)`` as
+        ``screen_structure`` does.  Falsy ``iteration`` / ``damping_factor`` fall back to the processor's.  Returns what
+        ``estimate_cam_pose_pnp`` returns -- inlier indices (a list), rot, loc (3, 1) -- with the identity at the origin and
+        no inliers for a view without a model; ``resect_last`` keeps best_hyp, status and the summary."""
+        if not damping_factor:
+            damping_factor = self.damping_factor
+        if not iteration:
+            iteration = self.iteration
+        if not float(max_reproj_px) >= 0.0:
+            raise ValueError("max_reproj_px must be >= 0, got {!r}".format(max_reproj_px))
+        key_2d_pts, tri_3d_pts = np.asarray(key_2d_pts, dtype=np.float64), np.asarray(tri_3d_pts, dtype=np.float64)
+        if key_2d_pts.shape[1] != tri_3d_pts.shape[1]:
+            raise ValueError("key pts num - triangulated pts num : {} - {}".format(key_2d_pts.shape[1], tri_3d_pts.shape[1]))
+        num_pts = key_2d_pts.shape[1]
+        intrinsic = np.asarray(intrinsic_mat, dtype=np.float64)
+        uv = normalise_pixels(key_2d_pts, intrinsic)
+        pts = np.ascontiguousarray(tri_3d_pts[0:3, :] / tri_3d_pts[3:4, :]) if tri_3d_pts.shape[0] == 4 else tri_3d_pts
+        scale = math.sqrt(abs(float(intrinsic[0, 0]) * float(intrinsic[1, 1])))
+        cams, inlier, _n, best, status, summary = native.resect_ransac(
+            [0, num_pts], uv, pts, float(max_reproj_px) ** 2, max_hyp, damping_factor, iteration, self.quirk_flags,
+            np.array([scale]))
+        self.resect_last = {"hypothesis": int(best[0]), "status": int(status[0]), "summary": summary}
+        rot = quaternion_to_rotation_unchecked(cams[0, 3:7])
+        return np.flatnonzero(inlier).tolist(), rot, cams[0, 0:3].reshape(3, 1).copy()
+
     # ---- two-view initialisation (campose_processor.py:29-189) --------------------------------------------
     def extract_cam_pose_from_essential_mat(self, esse_mat):
         """(r1, r2, c1, c2) of campose_processor.py:29-100.  The set {r1, r2} x {c1, c2} is the reference's;
@@ -782,6 +812,47 @@ class HipBaMixin:
         for view_idx in range(view_num):
             view_list[view_idx].update_cam_pose(rots[view_idx].copy(), cams[view_idx, 0:3].reshape(3, 1).copy())
         return cost, status
+
+    def resect_motion(self, max_reproj_px=4.0, max_hyp=128, iteration=3, damping_factor=None, views=None):
+        """Robust resection of the resident cameras (``BaProblem.resect``), after the scene has been brought up to date
+        exactly as ``refine_motion`` does: every camera from the consistent subset of its own resident observations -- the
+        triple whose pose has the most observations within ``max_reproj_px`` (at most ``max_hyp`` triples per camera),
+        refitted over those, the points held.  ``views``: the indices of the views to resect (None: all; the others are held
+        and only judged).  The threshold converts as ``screen_structure``'s.  Writes the poses back through
+        ``view.update_cam_pose`` as ``refine_motion`` does, leaves ``tri_pts`` and the track tables alone and returns the
+        native report (``inlier`` in the order of ``prob.structure()``, ``n_inliers``, ``best_hyp``, ``status``, ``summary``).
+        A camera without a model keeps its pose.  Falsy ``damping_factor`` falls back to ``self.damping_factor``.  Needs
+        ``ba_resident``; nothing in ``process()`` calls it."""
+        if not self.ba_resident:
+            raise TypeError("resect_motion needs ba_resident")
+        if self.ba_device_tracks:
+            self._ba_check_device_tracks()
+        if not damping_factor:
+            damping_factor = self.damping_factor
+        if max_reproj_px is None:
+            raise ValueError("resect_motion needs max_reproj_px")
+        native.check_resect(0, 0.0, max_hyp, damping_factor, iteration)      # before anything reaches the device
+        view_list = self.view_processor.view_list
+        mask = None
+        if views is not None:
+            idx = np.asarray(list(views), dtype=np.int64).ravel()
+            if idx.size and (idx.min() < 0 or idx.max() >= len(view_list)):
+                raise ValueError("resect_motion: view index outside the {} views".format(len(view_list)))
+            mask = np.zeros(len(view_list), dtype=np.uint8)
+            mask[idx] = 1
+        scene, max_err2, _cos, cam_scale = self._ba_screen_scene("resect_motion", max_reproj_px, None, 0)
+        try:
+            scene.cams_synced = False
+            report = scene.prob.resect(max_err2, max_hyp, damping_factor, iteration, self.ba_quirk_flags, mask, cam_scale)
+            cams, pts, rots = scene.prob.get_state_rot()
+        except Exception:
+            self.ba_release()
+            raise
+        scene.pts_written = pts                        # (the points did not move: bit for bit what the device was given)
+        scene.rots_written, scene.locs_written = rots, cams[:, 0:3].copy()
+        for view_idx, view in enumerate(view_list):
+            view.update_cam_pose(rots[view_idx].copy(), cams[view_idx, 0:3].reshape(3, 1).copy())
+        return report
 
     def _ba_screen_scene(self, who, max_reproj_px, min_angle_deg, min_obs):
         """The resident scene brought up to date as ``refine_structure`` does, and the native arguments of a screening:
