@@ -350,6 +350,31 @@ TrackView track_view_free(int n_pts, int n_views, long long M, const int* pt_ptr
 // The resident scene, solved in place with W = 1: allocates `projs` (12 V doubles) and enqueues its fill from the
 // prepared cameras on p->stream.  The flush, the preparation of the cameras and the early returns are the caller's.
 int track_view_resident(sfm_ba_problem* p, DevBuf<double>& projs, TrackView* out);
+// The counterpart by camera: entry e of camera c, e in [ptr[c], ptr[c + 1]), is observation obs[e] (the entry itself
+// without a list), whose point is obs_pt[o] (the observation itself without one).  The leading member of the kernel
+// arguments of the motion-only refinement and the robust resection; cam_obs_load (sfm_cam_fit.h) reads an entry.
+struct CamObsView {
+  int V;
+  const int* ptr;           // [V + 1]
+  const int* obs;           // [M] or null
+  const int* obs_pt;        // [M] or null
+  const double* u;          // [M] by observation
+  const double* v;
+  const double* px;         // by point
+  const double* py;
+  const double* pz;
+  const double* cam_scale;  // [V] or null (= 1)
+};
+// The free form: contiguous observations uv = [2][M] with a point per observation, X = [3][M].
+inline CamObsView cam_obs_view_free(int n_views, const int* view_ptr, long long M, const double* uv, const double* X,
+                                    const double* cam_scale) {
+  return CamObsView{n_views, view_ptr, nullptr, nullptr, uv, uv + M, X, X + M, X + 2 * M, cam_scale};
+}
+// The resident scene: its camera-major list (ba_cam_list_ensure is the caller's) through obs_pt.
+inline CamObsView cam_obs_view_resident(const sfm_ba_problem* p, const double* cam_scale) {
+  const BaDev& d = p->dev;
+  return CamObsView{d.V, p->cam_ptr, p->cam_obs, d.obs_pt, d.u, d.v, d.px, d.py, d.pz, cam_scale};
+}
 // What an operation on the resident scene is given (sfm_ba_host.hip; DESIGN.md, "What an operation on the resident scene
 // is given").  `who` names the entry point in the message.
 int ba_check_handle(const sfm_ba_problem* p);

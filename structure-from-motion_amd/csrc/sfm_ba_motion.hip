@@ -23,7 +23,6 @@
 #include <vector>
 
 #include "sfm_ba.h"
-#include "sfm_ba_terms.h"
 #include "sfm_cam_fit.h"
 
 namespace sfm {
@@ -38,24 +37,15 @@ constexpr int kMoDone = 1 << 30;     // internal status bit of the multi-launch 
 // The iteration
 // ---------------------------------------------------------------------------------------------
 struct MoArgs {
-  int V;
-  const int* ptr;               // [V+1] the scene's camera-major list
-  const int* obs;               // [M]
+  CamObsView w;                 // the scene's camera-major list
   const unsigned char* mask;    // [V] or null
+  double* cams;                 // [V][7]
+  CamPrep* prep;                // [V] the prepared cameras of the current state
   double lambda;
   int iters, quirks;
   double* cost;                 // [2][V]
   int* status;                  // [V]
 };
-
-
-// entry i of the camera's list (observation by index, its point through obs_pt)
-__device__ __forceinline__ void mo_load(const BaDev& d, const int* __restrict__ list, int i, MoObs& ob) {
-  const int o = list[i];
-  const int p = d.obs_pt[o];
-  ob.u = d.u[o]; ob.v = d.v[o];
-  ob.X = d.px[p]; ob.Y = d.py[p]; ob.Z = d.pz[p];
-}
 
 // One workgroup per camera of n_lo .. n_hi observations (the other size classes' launches skip it).  THREADS = 64 serves
 // up to 256 observations, THREADS = 256 up to 1 024: a lane's four consecutive observations and their points stay in
@@ -65,13 +55,13 @@ __device__ __forceinline__ void mo_load(const BaDev& d, const int* __restrict__ 
 // yields cost row 0, the pass after the last update yields cost row 1 and SFM_CAM_BEHIND.  A held or empty camera stops
 // after pass 0.
 template <int THREADS, bool STREAM, int LOSS>
-__global__ __launch_bounds__(THREADS) void ba_motion_resident_kernel(BaDev d, int cur, MoArgs a, int n_lo, int n_hi, LossArg<LOSS> la) {
+__global__ __launch_bounds__(THREADS) void ba_motion_resident_kernel(MoArgs a, int n_lo, int n_hi, LossArg<LOSS> la) {
   static_assert(!STREAM || THREADS * kMoPerLane == kMoBlockObs, "a streamed block is one round of the workgroup");
   constexpr int ROWS = THREADS / 16;
   __shared__ double red[ROWS][kMoSums];
   __shared__ double sums[kMoSums];
   const int cam = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  const int base = a.ptr[cam], n = a.ptr[cam + 1] - base;
+  const int base = a.w.ptr[cam], n = a.w.ptr[cam + 1] - base;
   if (n < n_lo || n > n_hi) return;
   const bool held = a.mask != nullptr && a.mask[cam] == 0;
   const int my_iters = (held || n == 0) ? 0 : a.iters;
@@ -79,16 +69,16 @@ __global__ __launch_bounds__(THREADS) void ba_motion_resident_kernel(BaDev d, in
   if (!STREAM) {
 #pragma unroll
     for (int k = 0; k < kMoPerLane; ++k)
-      if (kMoPerLane * tid + k < n) mo_load(d, a.obs + base, kMoPerLane * tid + k, ob[k]);
+      if (kMoPerLane * tid + k < n) cam_obs_load(a.w, cam, base + kMoPerLane * tid + k, ob[k]);
   }
   const int n_blocks = STREAM ? (n + kMoBlockObs - 1) / kMoBlockObs : 1;
   int own[3];
   mo_fold_own(lane, own);
   CamPrep c;
-  load_cam(c, d.prep[cur] + cam);
+  load_cam(c, a.prep + cam);
   double params[7];
 #pragma unroll
-  for (int k = 0; k < 7; ++k) params[k] = d.cams[7 * (size_t)cam + k];
+  for (int k = 0; k < 7; ++k) params[k] = a.cams[7 * (size_t)cam + k];
   int flags = (held ? SFM_CAM_HELD : 0) | (n == 0 ? SFM_CAM_EMPTY : 0);
   double cost0 = 0, cost1 = 0;
   for (int it = 0;; ++it) {
@@ -102,7 +92,7 @@ __global__ __launch_bounds__(THREADS) void ba_motion_resident_kernel(BaDev d, in
       for (int k = 0; k < kMoPerLane; ++k) {
         const int i = blk * kMoBlockObs + kMoPerLane * tid + k;
         if (i < n) {
-          if (STREAM) mo_load(d, a.obs + base, i, ob[k]);
+          if (STREAM) cam_obs_load(a.w, cam, base + i, ob[k]);
           mo_accumulate<LOSS>(c, ob[k], a.quirks, la, acc, behind);
         }
       }
@@ -134,28 +124,28 @@ __global__ __launch_bounds__(THREADS) void ba_motion_resident_kernel(BaDev d, in
   if (tid == 0) {
     if (my_iters > 0 && !(flags & SFM_CAM_NONFINITE)) {
 #pragma unroll
-      for (int k = 0; k < 7; ++k) d.cams[7 * (size_t)cam + k] = params[k];
+      for (int k = 0; k < 7; ++k) a.cams[7 * (size_t)cam + k] = params[k];
     }
     a.cost[cam] = cost0;
-    a.cost[(size_t)a.V + cam] = cost1;
+    a.cost[(size_t)a.w.V + cam] = cost1;
     a.status[cam] = flags;
   }
 }
 
 // Cameras of more than n_min observations, one pass: workgroup (camera, block) sums observations [1024 block, +1024) of the
-// camera's list at the prepared camera prep[cur] into one 36-vector per slice.
+// camera's list at the prepared camera into one 36-vector per slice.
 template <int LOSS>
-__global__ __launch_bounds__(256) void ba_motion_partial_kernel(BaDev d, int cur, MoArgs a, int n_min, double* __restrict__ ws,
+__global__ __launch_bounds__(256) void ba_motion_partial_kernel(MoArgs a, int n_min, double* __restrict__ ws,
                                                                 int* __restrict__ behind_flag, LossArg<LOSS> la) {
   __shared__ double red[16][kMoSums];
   const int cam = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-  const int base = a.ptr[cam], n = a.ptr[cam + 1] - base;
+  const int base = a.w.ptr[cam], n = a.w.ptr[cam + 1] - base;
   if (n <= n_min || (long long)blk * kMoBlockObs >= n) return;
   if (a.status[cam] & kMoDone) return;
   int own[3];
   mo_fold_own(lane, own);
   CamPrep c;
-  load_cam(c, d.prep[cur] + cam);
+  load_cam(c, a.prep + cam);
   double acc[kMoSums];
 #pragma unroll
   for (int k = 0; k < kMoSums; ++k) acc[k] = 0;
@@ -165,7 +155,7 @@ __global__ __launch_bounds__(256) void ba_motion_partial_kernel(BaDev d, int cur
     const int i = blk * kMoBlockObs + kMoPerLane * tid + k;
     if (i < n) {
       MoObs ob;
-      mo_load(d, a.obs + base, i, ob);
+      cam_obs_load(a.w, cam, base + i, ob);
       mo_accumulate<LOSS>(c, ob, a.quirks, la, acc, behind);
     }
   }
@@ -180,13 +170,13 @@ __global__ __launch_bounds__(256) void ba_motion_partial_kernel(BaDev d, int cur
 }
 
 // ... and its second half, one wave per camera: the slice vectors added in slice order, then what ba_motion_resident does
-// with the sums of pass `it`.  The camera and its prepared form travel through d.cams / d.prep[cur] between the passes;
+// with the sums of pass `it`.  The camera and its prepared form travel through a.cams / a.prep between the passes;
 // cams_in restores a camera that turns non-finite.
-__global__ __launch_bounds__(64) void ba_motion_finish_kernel(BaDev d, int cur, MoArgs a, int n_min, const double* __restrict__ ws,
+__global__ __launch_bounds__(64) void ba_motion_finish_kernel(MoArgs a, int n_min, const double* __restrict__ ws,
                                                               int* __restrict__ behind_flag, const double* __restrict__ cams_in, int it) {
   __shared__ double sums[kMoSums];
   const int cam = blockIdx.x, tid = threadIdx.x;
-  const int base = a.ptr[cam], n = a.ptr[cam + 1] - base;
+  const int base = a.w.ptr[cam], n = a.w.ptr[cam + 1] - base;
   if (n <= n_min) return;
   if (a.status[cam] & kMoDone) return;
   const int n_slices = cam_slice_count(n);
@@ -206,7 +196,7 @@ __global__ __launch_bounds__(64) void ba_motion_finish_kernel(BaDev d, int cur, 
   if (ok && it == my_iters) {
     if (tid == 0) {
       if (it == 0) a.cost[cam] = cost0;
-      a.cost[(size_t)a.V + cam] = sums[35];
+      a.cost[(size_t)a.w.V + cam] = sums[35];
       a.status[cam] = flags | (behind_flag[cam] ? SFM_CAM_BEHIND : 0) | kMoDone;
       behind_flag[cam] = 0;
     }
@@ -216,7 +206,7 @@ __global__ __launch_bounds__(64) void ba_motion_finish_kernel(BaDev d, int cur, 
   CamPrep c;
   if (ok) {
 #pragma unroll
-    for (int k = 0; k < 7; ++k) params[k] = d.cams[7 * (size_t)cam + k];
+    for (int k = 0; k < 7; ++k) params[k] = a.cams[7 * (size_t)cam + k];
     ok = mo_step(sums, a.lambda, params, c);
   }
   if (tid != 0) return;
@@ -224,11 +214,11 @@ __global__ __launch_bounds__(64) void ba_motion_finish_kernel(BaDev d, int cur, 
   if (it == 0) a.cost[cam] = cost0;
   if (ok) {
 #pragma unroll
-    for (int k = 0; k < 7; ++k) d.cams[7 * (size_t)cam + k] = params[k];
-    d.prep[cur][cam] = c;
+    for (int k = 0; k < 7; ++k) a.cams[7 * (size_t)cam + k] = params[k];
+    a.prep[cam] = c;
   } else {
-    for (int k = 0; k < 7; ++k) d.cams[7 * (size_t)cam + k] = cams_in[7 * (size_t)cam + k];
-    a.cost[(size_t)a.V + cam] = cost0;
+    for (int k = 0; k < 7; ++k) a.cams[7 * (size_t)cam + k] = cams_in[7 * (size_t)cam + k];
+    a.cost[(size_t)a.w.V + cam] = cost0;
     a.status[cam] = flags | SFM_CAM_NONFINITE | kMoDone;
   }
 }
@@ -251,11 +241,11 @@ static int mo_enqueue(sfm_ba_problem* p, const MoArgs& a, int loss_kind, const i
     const bool stream3 = !(p->debug & 32768);
     const int n_min = stream3 ? kMoStreamObs : kMoBlockObs;      // the multi-launch path takes the cameras beyond it
     if (n_class[0] + n_class[1] > 0)
-      ba_motion_resident_kernel<64, false, LOSS><<<d.V, 64, 0, s>>>(d, p->cur, a, 0, kMoWaveObs, la);
+      ba_motion_resident_kernel<64, false, LOSS><<<d.V, 64, 0, s>>>(a, 0, kMoWaveObs, la);
     if (n_class[2] > 0)
-      ba_motion_resident_kernel<256, false, LOSS><<<d.V, 256, 0, s>>>(d, p->cur, a, kMoWaveObs + 1, kMoBlockObs, la);
+      ba_motion_resident_kernel<256, false, LOSS><<<d.V, 256, 0, s>>>(a, kMoWaveObs + 1, kMoBlockObs, la);
     if (n_class[3] > 0 && stream3)
-      ba_motion_resident_kernel<256, true, LOSS><<<d.V, 256, 0, s>>>(d, p->cur, a, kMoBlockObs + 1, kMoStreamObs, la);
+      ba_motion_resident_kernel<256, true, LOSS><<<d.V, 256, 0, s>>>(a, kMoBlockObs + 1, kMoStreamObs, la);
     if (n_class[4] > 0 || (n_class[3] > 0 && !stream3)) {
       SFM_TRY(ws.alloc(cam_slice_rows(d.M, d.V) * kMoSums, s));
       SFM_TRY(behind.alloc((size_t)d.V, s));
@@ -264,8 +254,8 @@ static int mo_enqueue(sfm_ba_problem* p, const MoArgs& a, int loss_kind, const i
       SFM_HIP(hipMemcpyAsync(cams_in.p, d.cams, sizeof(double) * 7 * d.V, hipMemcpyDeviceToDevice, s));
       const dim3 grid((unsigned)d.V, (unsigned)((max_obs + kMoBlockObs - 1) / kMoBlockObs));
       for (int it = 0; it <= a.iters; ++it) {
-        ba_motion_partial_kernel<LOSS><<<grid, 256, 0, s>>>(d, p->cur, a, n_min, ws.p, behind.p, la);
-        ba_motion_finish_kernel<<<d.V, 64, 0, s>>>(d, p->cur, a, n_min, ws.p, behind.p, cams_in.p, it);
+        ba_motion_partial_kernel<LOSS><<<grid, 256, 0, s>>>(a, n_min, ws.p, behind.p, la);
+        ba_motion_finish_kernel<<<d.V, 64, 0, s>>>(a, n_min, ws.p, behind.p, cams_in.p, it);
       }
     }
     SFM_HIP(hipGetLastError());
@@ -328,7 +318,7 @@ int sfm_ba_refine_cameras(sfm_ba_problem* p, double lambda, int iters, int quirk
   SFM_TRY(ostat.want(status, (size_t)V, s, true));
   SFM_HIP(hipMemsetAsync(ostat.dev(), 0, sizeof(int) * (size_t)V, s));
   MoArgs a = {};
-  a.V = V; a.ptr = p->cam_ptr; a.obs = p->cam_obs; a.mask = dmask.p;
+  a.w = cam_obs_view_resident(p, nullptr); a.mask = dmask.p; a.cams = d.cams; a.prep = d.prep[p->cur];
   a.lambda = lambda; a.iters = iters; a.quirks = quirks;
   a.cost = ocost.dev(); a.status = ostat.dev();
   SFM_TRY(mo_enqueue(p, a, use_loss ? p->loss_kind : SFM_LOSS_NONE, n_class, max_obs, ws, behind, cams_in));

@@ -3,8 +3,8 @@
 // After an adjustment, every observation of the resident CSR is judged at the current state -- reprojection error,
 // depth -- and every point by what is left of its track -- number of surviving observations, widest angle between two
 // of their rays (sfm_hip.h, block "screening").  The residuals are the linearisation's: the projection is
-// [R(q)^T | t] of the prepared cameras, formed with the operations of sfm_track_obs.h's track_project /
-// track_residual, so the sum of err2 over a track is sfm_ba_refine_points' cost row 0 of that point.
+// [R(q)^T | t] of the prepared cameras in track_project's operation order and the residual is track_residual's
+// (sfm_obs_test.h), so the sum of err2 over a track is sfm_ba_refine_points' cost row 0 of that point.
 //   screen   a group of G lanes owns a point, lane l takes observations l, l + G, ... in track order; one lane
 //            evaluates an observation and writes err2 / depth / flags, the group counts the survivors and takes the
 //            minimum of r_i . r_j over the surviving pairs with the rays staged in LDS
@@ -16,6 +16,7 @@
 
 #include "sfm_ba.h"
 #include "sfm_scan.h"
+#include "sfm_obs_test.h"      // contraction is off from here on
 
 namespace sfm {
 
@@ -44,23 +45,17 @@ struct ScreenArgs {
   unsigned long long* summary;  // [8]; slots 2..7 are counted here, 0 and 1 by the scan
 };
 
-// Everything below is compiled WITHOUT automatic contraction and spells its FMAs out: every instantiation executes the
-// same operations per observation.
-#pragma clang fp contract(off)
-
+// Everything below is compiled WITHOUT automatic contraction (sfm_obs_test.h) and spells its FMAs out: every instantiation
+// executes the same operations per observation.
 struct ScreenObs { double err2, depth, r[3]; int flags; };
 
-// One observation: s = [R^T | t] (X, 1) with track_project's operation order, the residual of track_residual, the unit
-// ray from the point to the camera centre.  r[0] is NaN for an observation that does not survive.
+// One observation: obs_project_cam and obs_err2 (sfm_obs_test.h), the flags that say why it does not pass, the unit ray
+// from the point to the camera centre.  r[0] is NaN for an observation that does not survive.
 __device__ __forceinline__ void screen_obs(const CamPrep& c, double scale, double ku, double kv, double x0, double x1, double x2,
                                            double max_err2, ScreenObs& e) {
   double s[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) s[r] = __builtin_fma(c.R[6 + r], x2, __builtin_fma(c.R[3 + r], x1, c.R[r] * x0)) + c.t[r];
-  const double iz = rcp_nr(s[2]);
-  const double eu = __builtin_fma(s[0], iz, -ku);
-  const double ev = __builtin_fma(s[1], iz, -kv);
-  e.err2 = (scale * scale) * __builtin_fma(ev, ev, eu * eu);
+  obs_project_cam(c, x0, x1, x2, s);
+  e.err2 = obs_err2(s, ku, kv, scale);
   e.depth = s[2];
   e.flags = !isfinite(e.err2) ? SFM_OBS_NONFINITE : (e.err2 > max_err2 ? SFM_OBS_HIGH_ERROR : 0);
   if (s[2] <= 0.0) e.flags |= SFM_OBS_BEHIND;

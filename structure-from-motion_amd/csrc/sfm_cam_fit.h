@@ -1,6 +1,10 @@
-// sfm_cam_fit.h -- one damped step of a camera over its own observations, the points held: the per-observation sums, their
-// fold to slices of 64 consecutive observations and the serial 7x7 step.  Shared as they are by the motion-only refinement
-// (sfm_ba_motion.hip) and the refit of the robust resection (sfm_resect.hip), which differ in which observations they pass.
+// sfm_cam_fit.h -- one damped step of a camera over its own observations, the points held: the loader of an entry of a
+// camera's list, the per-observation sums, their fold to slices of 64 consecutive observations and the serial 7x7 step.
+// Shared as they are by the motion-only refinement (sfm_ba_motion.hip) and the refit of the robust resection
+// (sfm_resect.hip), which differ in which observations they pass.  Compiled under the compiler's default contraction:
+// include it ahead of sfm_obs_test.h.  The loop of a workgroup over 1 024 entries stays written out in its three kernels:
+// under that contraction the operand order of their sums, and with it their bits, follows the shape of the code around
+// mo_accumulate.
 #pragma once
 
 #include "sfm_ba_terms.h"
@@ -11,6 +15,17 @@ constexpr int kMoPerLane = 4;        // consecutive observations a lane keeps in
 constexpr int kMoSums = 36;          // U lower triangle (28) | g (7) | cost share
 
 struct MoObs { double u, v, X, Y, Z; };
+
+// entry e of camera cam's list (CamObsView, sfm_ba.h); on request the camera's scale and the observation's index
+__device__ __forceinline__ void cam_obs_load(const CamObsView& w, int cam, int e, MoObs& ob, double* scale = nullptr,
+                                             int* index = nullptr) {
+  const int o = w.obs ? w.obs[e] : e;
+  const int p = w.obs_pt ? w.obs_pt[o] : o;
+  ob.u = w.u[o]; ob.v = w.v[o];
+  ob.X = w.px[p]; ob.Y = w.py[p]; ob.Z = w.pz[p];
+  if (scale) *scale = w.cam_scale ? w.cam_scale[cam] : 1.0;
+  if (index) *index = o;
+}
 
 // one observation into the 36 sums; behind: s[2] <= 0 at this camera
 template <int LOSS>

@@ -1,0 +1,44 @@
+// sfm_obs_test.h -- the reprojection test of one observation, once: the residual of a projected point s against the key
+// (u, v), its scaled square, the inlier predicate.  Whoever judges an observation (sfm_ba_screen, the robust triangulation
+// and resection, the residuals of the ragged-track kernels) projects by its own data layout (track_project for a 3x4 P,
+// rs_project_pose for [m | t], obs_project_cam for a prepared camera) and continues here: resect then screen, retriangulate
+// then cull, free and resident form agree on every decision because they execute the same function.
+//
+// Compiled WITHOUT automatic contraction, the FMAs spelled out.  The pragma is lexical and stays in force for the rest of
+// the translation unit: include this header outside any namespace and AFTER all code that keeps the compiler's default
+// contraction (sfm_ba_terms.h, sfm_cam_fit.h, tri_tracks_linear_kernel) -- a later `contract(on)` is not that default.
+#pragma once
+
+#include "sfm_common.h"
+
+#pragma clang fp contract(off)
+
+namespace sfm {
+
+// s = [R^T | t] (X, 1) of a prepared camera, in track_project's operation order
+__device__ __forceinline__ void obs_project_cam(const CamPrep& c, double X, double Y, double Z, double* s) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) s[r] = __builtin_fma(c.R[6 + r], Z, __builtin_fma(c.R[3 + r], Y, c.R[r] * X)) + c.t[r];
+}
+
+__device__ __forceinline__ double obs_inv_depth(const double* s) { return rcp_nr(s[2]); }
+
+// (eu, ev) = s[0:2] / s[2] - (u, v)
+__device__ __forceinline__ void obs_residual(const double* s, double u, double v, double& eu, double& ev) {
+  const double iz = obs_inv_depth(s);
+  eu = __builtin_fma(s[0], iz, -u);
+  ev = __builtin_fma(s[1], iz, -v);
+}
+
+__device__ __forceinline__ double obs_err2(const double* s, double u, double v, double scale) {
+  double eu, ev;
+  obs_residual(s, u, v, eu, ev);
+  return (scale * scale) * __builtin_fma(ev, ev, eu * eu);
+}
+
+// in front of the camera, finite, within the bound; no short circuit: a branch per observation would serialise a walk
+__device__ __forceinline__ bool obs_passes(const double* s, double err2, double max_err2) {
+  return (s[2] > 0.0) & isfinite(err2) & (err2 <= max_err2);
+}
+
+}  // namespace sfm

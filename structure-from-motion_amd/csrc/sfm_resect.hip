@@ -26,32 +26,16 @@
 #include "sfm_ba.h"
 #include "sfm_cam_fit.h"
 #include "sfm_hyp_number.h"
+#include "sfm_obs_test.h"      // contraction is off from here on
 
 namespace sfm {
 
-constexpr int kRsMaxHyp = 65536;
-constexpr int kRsDefaultHyp = 128;
-constexpr int kRsMinCount = 4;        // a winner explains at least one observation besides its own three
+constexpr int kRsMinCount = 4;       // a winner explains at least one observation besides its own three
 constexpr int kRsThreads = 256;
 constexpr int kRsBlockObs = kRsThreads * kMoPerLane;      // 1 024 observations per workgroup and round
 constexpr int kRsBatch = 64;          // hypotheses per LDS batch: 64 x 4 x 12 doubles = 24 576 bytes, six workgroups per CU
 constexpr int kRsPose = 12;           // R^T row-major (9) | t (3)
 constexpr double kRsRootImag = 1e-7;  // a conjugate pair whose imaginary part is below this (relative to 1 + |real|) counts as a double root
-
-// The observations of every camera: entry e of camera c, e in [ptr[c], ptr[c + 1]), is observation obs[e] (the entry
-// itself without a list), whose point is obs_pt[o] (the observation itself without one).  The counterpart of TrackView.
-struct CamObsView {
-  int V;
-  const int* ptr;           // [V + 1]
-  const int* obs;           // [M] or null
-  const int* obs_pt;        // [M] or null
-  const double* u;          // [M] by observation
-  const double* v;
-  const double* px;         // by point
-  const double* py;
-  const double* pz;
-  const double* cam_scale;  // [V] or null (= 1)
-};
 
 struct RsArgs {
   CamObsView w;
@@ -78,43 +62,24 @@ struct RsArgs {
   unsigned long long* summary;  // [6]
 };
 
-struct RsObs { MoObs o; double scale; int index; };
-
-__device__ __forceinline__ void rs_load(const CamObsView& w, int cam, int e, RsObs& ob) {
-  const int o = w.obs ? w.obs[e] : e;
-  const int p = w.obs_pt ? w.obs_pt[o] : o;
-  ob.index = o;
-  ob.o.u = w.u[o]; ob.o.v = w.v[o];
-  ob.o.X = w.px[p]; ob.o.Y = w.py[p]; ob.o.Z = w.pz[p];
-  ob.scale = w.cam_scale ? w.cam_scale[cam] : 1.0;
-}
-
-// Everything below is compiled WITHOUT automatic contraction and spells its FMAs out: the test of an observation executes
-// the same operations wherever it is instantiated, and they are sfm_ba_screen's.
-#pragma clang fp contract(off)
-
-// Is the observation an inlier of s = m X + t (m row-major)?  sfm_ba_screen's err2 and comparison; no short circuit.
-__device__ __forceinline__ bool rs_inlier_pose(const double* m, const double* t, const MoObs& o, double scale, double max_err2) {
-  double s[3];
+// Everything below is compiled WITHOUT automatic contraction and spells its FMAs out; the test of an observation is
+// sfm_obs_test.h's, the one sfm_ba_screen applies.
+// s = m X + t of a pose [m | t] (m row-major), in track_project's operation order
+__device__ __forceinline__ void rs_project_pose(const double* m, const double* t, const MoObs& o, double* s) {
 #pragma unroll
   for (int r = 0; r < 3; ++r) s[r] = __builtin_fma(m[3 * r + 2], o.Z, __builtin_fma(m[3 * r + 1], o.Y, m[3 * r] * o.X)) + t[r];
-  const double iz = rcp_nr(s[2]);
-  const double eu = __builtin_fma(s[0], iz, -o.u);
-  const double ev = __builtin_fma(s[1], iz, -o.v);
-  const double err2 = (scale * scale) * __builtin_fma(ev, ev, eu * eu);
-  return (s[2] > 0.0) & isfinite(err2) & (err2 <= max_err2);
 }
 
-// The same at a prepared camera: screen_obs' operations on R and t.
+// Is the observation an inlier of the pose / of the prepared camera?
+__device__ __forceinline__ bool rs_inlier_pose(const double* m, const double* t, const MoObs& o, double scale, double max_err2) {
+  double s[3];
+  rs_project_pose(m, t, o, s);
+  return obs_passes(s, obs_err2(s, o.u, o.v, scale), max_err2);
+}
 __device__ __forceinline__ bool rs_inlier_cam(const CamPrep& c, const MoObs& o, double scale, double max_err2) {
   double s[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) s[r] = __builtin_fma(c.R[6 + r], o.Z, __builtin_fma(c.R[3 + r], o.Y, c.R[r] * o.X)) + c.t[r];
-  const double iz = rcp_nr(s[2]);
-  const double eu = __builtin_fma(s[0], iz, -o.u);
-  const double ev = __builtin_fma(s[1], iz, -o.v);
-  const double err2 = (scale * scale) * __builtin_fma(ev, ev, eu * eu);
-  return (s[2] > 0.0) & isfinite(err2) & (err2 <= max_err2);
+  obs_project_cam(c, o.X, o.Y, o.Z, s);
+  return obs_passes(s, obs_err2(s, o.u, o.v, scale), max_err2);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -219,14 +184,14 @@ __global__ __launch_bounds__(kRsThreads) void resect_hyp_kernel(RsArgs a, int n_
   const long long T = triple_count(n);
   int idx[3];
   triple_of(n, ransac_pair_number(T, a.max_hyp, h), &idx[0], &idx[1], &idx[2]);
-  RsObs ob[3];
-  double f[3][3], X[3][3];
+  MoObs ob[3];
+  double scale = 1.0, f[3][3], X[3][3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    rs_load(a.w, cam, base + idx[k], ob[k]);
-    const double inv = 1.0 / sqrt(ob[k].o.u * ob[k].o.u + ob[k].o.v * ob[k].o.v + 1.0);
-    f[k][0] = ob[k].o.u * inv; f[k][1] = ob[k].o.v * inv; f[k][2] = inv;
-    X[k][0] = ob[k].o.X; X[k][1] = ob[k].o.Y; X[k][2] = ob[k].o.Z;
+    cam_obs_load(a.w, cam, base + idx[k], ob[k], &scale);
+    const double inv = 1.0 / sqrt(ob[k].u * ob[k].u + ob[k].v * ob[k].v + 1.0);
+    f[k][0] = ob[k].u * inv; f[k][1] = ob[k].v * inv; f[k][2] = inv;
+    X[k][0] = ob[k].X; X[k][1] = ob[k].Y; X[k][2] = ob[k].Z;
   }
   auto dist2 = [&](int i, int j) {
     const double d0 = X[i][0] - X[j][0], d1 = X[i][1] - X[j][1], d2 = X[i][2] - X[j][2];
@@ -289,8 +254,8 @@ __global__ __launch_bounds__(kRsThreads) void resect_hyp_kernel(RsArgs a, int n_
     }
     good = good && chk == 0.0 && rot_to_quat(rot, quat) == SFM_OK;
     // the triple gate
-    good = good && rs_inlier_pose(m, t, ob[0].o, ob[0].scale, a.max_err2) && rs_inlier_pose(m, t, ob[1].o, ob[1].scale, a.max_err2) &&
-           rs_inlier_pose(m, t, ob[2].o, ob[2].scale, a.max_err2);
+    good = good && rs_inlier_pose(m, t, ob[0], scale, a.max_err2) && rs_inlier_pose(m, t, ob[1], scale, a.max_err2) &&
+           rs_inlier_pose(m, t, ob[2], scale, a.max_err2);
     bits |= good ? 1 << k : 0;
 #pragma unroll
     for (int i = 0; i < 9; ++i) out[kRsPose * k + i] = m[i];
@@ -317,10 +282,8 @@ __global__ __launch_bounds__(kRsThreads) void resect_score_kernel(RsArgs a) {
 #pragma unroll
   for (int k = 0; k < kMoPerLane; ++k) {
     const int i = blk.y + kMoPerLane * tid + k;
-    RsObs r;
-    rs_load(a.w, cam, base + (i < n ? i : n - 1), r);
-    ob[k] = r.o;
-    sc[k] = i < n ? r.scale : __builtin_nan("");
+    cam_obs_load(a.w, cam, base + (i < n ? i : n - 1), ob[k], &sc[k]);
+    if (!(i < n)) sc[k] = __builtin_nan("");
   }
   for (int hb = 0; hb < H; hb += kRsBatch) {
     const int nb = min(kRsBatch, H - hb);
@@ -423,9 +386,10 @@ __global__ __launch_bounds__(kRsThreads) void resect_refit_kernel(RsArgs a) {
         for (int k = 0; k < kMoPerLane; ++k) {
           const int i = blk * kRsBlockObs + kMoPerLane * tid + k;
           if (i < n) {
-            RsObs ob;
-            rs_load(a.w, cam, base + i, ob);
-            if (rs_inlier_pose(wp, wp + 9, ob.o, ob.scale, a.max_err2)) mo_accumulate<SFM_LOSS_NONE>(c, ob.o, a.quirks, la, acc, behind);
+            MoObs ob;
+            double scale;
+            cam_obs_load(a.w, cam, base + i, ob, &scale);
+            if (rs_inlier_pose(wp, wp + 9, ob, scale, a.max_err2)) mo_accumulate<SFM_LOSS_NONE>(c, ob, a.quirks, la, acc, behind);
           }
         }
         mo_fold_row(acc, own, lane, red[tid >> 4]);
@@ -451,9 +415,10 @@ __global__ __launch_bounds__(kRsThreads) void resect_refit_kernel(RsArgs a) {
         for (int k = 0; k < kMoPerLane; ++k) {
           const int i = blk * kRsBlockObs + kMoPerLane * tid + k;
           if (i < n) {
-            RsObs ob;
-            rs_load(a.w, cam, base + i, ob);
-            mine += rs_inlier_cam(c, ob.o, ob.scale, a.max_err2);
+            MoObs ob;
+            double scale;
+            cam_obs_load(a.w, cam, base + i, ob, &scale);
+            mine += rs_inlier_cam(c, ob, scale, a.max_err2);
           }
         }
         rc += __syncthreads_count(mine & 1) + 2 * __syncthreads_count(mine & 2) + 4 * __syncthreads_count(mine & 4);
@@ -492,10 +457,12 @@ __global__ __launch_bounds__(kRsThreads) void resect_judge_kernel(RsArgs a) {
   load_cam(c, a.prep + cam);
   int nin = 0;
   for (int i = tid; i < n; i += kRsThreads) {
-    RsObs ob;
-    rs_load(a.w, cam, base + i, ob);
-    const bool in = judged & rs_inlier_cam(c, ob.o, ob.scale, a.max_err2);
-    if (a.obs_inlier) a.obs_inlier[ob.index] = in ? 1 : 0;
+    MoObs ob;
+    double scale;
+    int index;      // the observation: obs_inlier is by observation
+    cam_obs_load(a.w, cam, base + i, ob, &scale, &index);
+    const bool in = judged & rs_inlier_cam(c, ob, scale, a.max_err2);
+    if (a.obs_inlier) a.obs_inlier[index] = in ? 1 : 0;
     nin += in;
   }
 #pragma unroll
@@ -505,14 +472,7 @@ __global__ __launch_bounds__(kRsThreads) void resect_judge_kernel(RsArgs a) {
   if (tid != 0) return;
   nin = total;
   if (a.n_inliers) a.n_inliers[cam] = nin;
-  if (solved) {
-    atomicAdd(&a.summary[0], 1ULL);
-    if (flags & SFM_RESECT_KEPT_HYPOTHESIS) atomicAdd(&a.summary[3], 1ULL);
-    if (n - nin) atomicAdd(&a.summary[5], (unsigned long long)(n - nin));
-  } else if (!(flags & SFM_RESECT_HELD)) {
-    atomicAdd(&a.summary[(flags & SFM_RESECT_TOO_FEW) ? 2 : 1], 1ULL);
-  }
-  if (nin) atomicAdd(&a.summary[4], (unsigned long long)nin);
+  robust_summary_add(a.summary, solved, flags & SFM_RESECT_HELD, flags & SFM_RESECT_TOO_FEW, flags & SFM_RESECT_KEPT_HYPOTHESIS, n, nin);
 }
 
 #pragma clang fp contract(on)
@@ -520,14 +480,6 @@ __global__ __launch_bounds__(kRsThreads) void resect_judge_kernel(RsArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int resect_check_args(const char* who, double max_err2, int max_hyp, double lambda, int iters) {
-  if (!(max_err2 >= 0.0)) { set_error("%s: max_err2 = %g must be >= 0", who, max_err2); return SFM_E_SHAPE; }
-  if (max_hyp < 0 || max_hyp > kRsMaxHyp) { set_error("%s: max_hyp = %d must be in 1 .. %d (0 = %d)", who, max_hyp, kRsMaxHyp, kRsDefaultHyp); return SFM_E_SHAPE; }
-  if (iters < 0) { set_error("%s: iters = %d must be >= 0", who, iters); return SFM_E_SHAPE; }
-  if (!(lambda >= 0.0)) { set_error("%s: lambda = %g must be >= 0", who, lambda); return SFM_E_SHAPE; }
-  return SFM_OK;
-}
-
 // T = n (n - 1) (n - 2) / 6 must fit 63 bits
 static int resect_check_counts(const char* who, int V, const int* ptr) {
   for (int c = 0; c < V; ++c) {
@@ -564,7 +516,7 @@ struct ResectWork {
 // 2^20 observations) and the mask, from which the launches are planned.  a.best_hyp / a.status / a.summary may be null: the work buffers stand in.
 static int resect_enqueue(const char* who, RsArgs& a, ResectWork& w, const int* h_ptr, const unsigned char* h_mask, hipStream_t s) {
   const int V = a.w.V;
-  if (a.max_hyp == 0) a.max_hyp = kRsDefaultHyp;
+  if (a.max_hyp == 0) a.max_hyp = kHypDefault;
   std::vector<int> off((size_t)V + 1, 0);
   std::vector<int2> blocks;
   long long total = 0;
@@ -572,8 +524,7 @@ static int resect_enqueue(const char* who, RsArgs& a, ResectWork& w, const int* 
     const int n = h_ptr[c + 1] - h_ptr[c];
     off[c] = (int)total;
     if (n >= 4 && !(h_mask && h_mask[c] == 0)) {
-      const long long T = triple_count(n);
-      total += T < (long long)a.max_hyp ? T : a.max_hyp;
+      total += hyp_count(triple_count(n), a.max_hyp);
       for (int b = 0; b < n; b += kRsBlockObs) blocks.push_back(make_int2(c, b));
     }
     if (total > INT_MAX / (4 * kRsPose)) { set_error("%s: %lld hypotheses are beyond the workspace", who, total); return SFM_E_SHAPE; }
@@ -602,28 +553,18 @@ static int resect_enqueue(const char* who, RsArgs& a, ResectWork& w, const int* 
   return SFM_OK;
 }
 
-static int resect_enqueue_judge(const RsArgs& a, hipStream_t s) {
-  resect_judge_kernel<<<a.w.V, kRsThreads, 0, s>>>(a);
-  SFM_HIP(hipGetLastError());
-  return SFM_OK;
-}
-
 // The one body of sfm_resect_ransac and sfm_resect_ransac_dev: checked arguments and device pointers in (n_views > 0), the
 // kernels enqueued on s out.  w lives until the caller has waited for s.
 static int resect_run(const char* who, int n_views, const int* view_ptr, long long M, const double* d_uv, const double* d_X,
                       const double* d_cam_scale, double max_err2, int max_hyp, double lambda, int iters, int quirks,
-                      const double* d_cams_init, double* d_cams_out, unsigned char* d_obs_inlier, int* d_n_inliers, int* d_best_hyp,
-                      int* d_status, int64_t* d_summary, DevBuf<int>& d_ptr, ResectWork& w, hipStream_t s) {
+                      const double* d_cams_init, double* d_cams_out, const RobustPtrs& out, DevBuf<int>& d_ptr, ResectWork& w,
+                      hipStream_t s) {
   SFM_TRY(d_ptr.upload(view_ptr, (size_t)n_views + 1, s));
   RsArgs a = {};
-  a.w.V = n_views; a.w.ptr = d_ptr.p;
-  a.w.u = d_uv; a.w.v = d_uv + M;
-  a.w.px = d_X; a.w.py = d_X + M; a.w.pz = d_X + 2 * M;
-  a.w.cam_scale = d_cam_scale;
+  a.w = cam_obs_view_free(n_views, d_ptr.p, M, d_uv, d_X, d_cam_scale);
   a.max_err2 = max_err2; a.max_hyp = max_hyp; a.lambda = lambda; a.iters = iters; a.quirks = quirks;
   a.cams_in = d_cams_init; a.cams_out = d_cams_out;
-  a.best_hyp = d_best_hyp; a.status = d_status; a.obs_inlier = d_obs_inlier; a.n_inliers = d_n_inliers;
-  a.summary = reinterpret_cast<unsigned long long*>(d_summary);
+  out.into(a);
   SFM_TRY(resect_enqueue(who, a, w, view_ptr, nullptr, s));
   // the cameras that stand, expanded as every operation on a scene expands them (a camera that fails its checks there is
   // still projected with its R(q) and t)
@@ -633,7 +574,9 @@ static int resect_run(const char* who, int n_views, const int* view_ptr, long lo
   ba_cam_prep_kernel<<<(n_views + 63) / 64, 64, 0, s>>>(n_views, d_cams_out, w.prep.p, w.prep_status.p);
   SFM_HIP(hipGetLastError());
   a.prep = w.prep.p;
-  return resect_enqueue_judge(a, s);
+  resect_judge_kernel<<<n_views, kRsThreads, 0, s>>>(a);
+  SFM_HIP(hipGetLastError());
+  return SFM_OK;
 }
 
 }  // namespace sfm
@@ -643,10 +586,10 @@ using namespace sfm;
 extern "C" {
 
 int sfm_resect_triple(int n, int max_hyp, int h, int* i, int* j, int* l) {
-  if (max_hyp == 0) max_hyp = kRsDefaultHyp;
-  if (n < 3 || n > kTripleMaxObs || max_hyp < 1 || max_hyp > kRsMaxHyp) return 0;
+  if (max_hyp == 0) max_hyp = kHypDefault;
+  if (n < 3 || n > kTripleMaxObs || max_hyp < 1 || max_hyp > kHypMax) return 0;
   const long long T = triple_count(n);
-  const int H = T < (long long)max_hyp ? (int)T : max_hyp;
+  const int H = hyp_count(T, max_hyp);
   if (h >= 0 && h < H && i != nullptr && j != nullptr && l != nullptr) triple_of(n, ransac_pair_number(T, max_hyp, h), i, j, l);
   return H;
 }
@@ -657,7 +600,7 @@ int sfm_resect_ransac_dev(int n_views, const int* view_ptr, int64_t M, const dou
                           int* d_best_hyp, int* d_status, int64_t* d_summary, void* hip_stream) {
   const char* who = "sfm_resect_ransac_dev";
   SFM_TRY(ensure_init());
-  SFM_TRY(resect_check_args(who, max_err2, max_hyp, lambda, iters));
+  SFM_TRY(robust_check_args(who, max_err2, max_hyp, lambda, iters));
   SFM_TRY(resect_check_views(who, n_views, view_ptr, M));
   hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx().stream;
   if (n_views == 0) {
@@ -668,7 +611,7 @@ int sfm_resect_ransac_dev(int n_views, const int* view_ptr, int64_t M, const dou
   DevBuf<int> dPtr;
   ResectWork w;
   SFM_TRY(resect_run(who, n_views, view_ptr, M, d_uv, d_X, d_cam_scale, max_err2, max_hyp, lambda, iters, quirks, d_cams_init,
-                     d_cams_out, d_obs_inlier, d_n_inliers, d_best_hyp, d_status, d_summary, dPtr, w, s));
+                     d_cams_out, RobustPtrs{d_obs_inlier, d_n_inliers, d_best_hyp, d_status, d_summary}, dPtr, w, s));
   return stream_sync(s);      // the work buffers go back to the pool with this call
 }
 
@@ -677,9 +620,9 @@ int sfm_resect_ransac(int n_views, const int* view_ptr, int64_t M, const double*
                       unsigned char* obs_inlier, int* n_inliers, int* best_hyp, int* status, int64_t* summary) {
   const char* who = "sfm_resect_ransac";
   SFM_TRY(ensure_init());
-  SFM_TRY(resect_check_args(who, max_err2, max_hyp, lambda, iters));
+  SFM_TRY(robust_check_args(who, max_err2, max_hyp, lambda, iters));
   SFM_TRY(resect_check_views(who, n_views, view_ptr, M));
-  if (summary) for (int k = 0; k < 6; ++k) summary[k] = 0;
+  robust_summary_clear(summary);
   if (n_views == 0) return SFM_OK;
   if (cams_out == nullptr || (M > 0 && (uv == nullptr || X == nullptr))) { set_error("%s: null pointer", who); return SFM_E_SHAPE; }
   hipStream_t s = ctx().stream;
@@ -687,20 +630,18 @@ int sfm_resect_ransac(int n_views, const int* view_ptr, int64_t M, const double*
   DevBuf<int> dPtr;
   DevBuf<double> dUV, dX, dSc, dIn;
   HostOut<double> oCams;
-  HostOut<unsigned char> oInlier;
-  HostOut<int> oCount, oBest, oStatus;
-  HostOut<int64_t> oSummary;
+  RobustOut o;
   ResectWork w;
   SFM_TRY(dUV.upload(uv, 2 * m, s));
   SFM_TRY(dX.upload(X, 3 * m, s));
   SFM_TRY(dSc.upload_if(cam_scale, v, s));
   SFM_TRY(dIn.upload_if(cams_init, 7 * v, s));
-  SFM_TRY(oCams.want(cams_out, 7 * v, s)); SFM_TRY(oInlier.want(obs_inlier, m, s)); SFM_TRY(oCount.want(n_inliers, v, s));
-  SFM_TRY(oBest.want(best_hyp, v, s)); SFM_TRY(oStatus.want(status, v, s)); SFM_TRY(oSummary.want(summary, 6, s));
+  SFM_TRY(oCams.want(cams_out, 7 * v, s));
+  SFM_TRY(o.want(m, v, obs_inlier, n_inliers, best_hyp, status, summary, s));
   SFM_TRY(resect_run(who, n_views, view_ptr, M, dUV.p, dX.p, dSc.p, max_err2, max_hyp, lambda, iters, quirks, dIn.p, oCams.dev(),
-                     oInlier.dev(), oCount.dev(), oBest.dev(), oStatus.dev(), oSummary.dev(), dPtr, w, s));
-  SFM_TRY(oCams.fetch(s)); SFM_TRY(oInlier.fetch(s)); SFM_TRY(oCount.fetch(s));
-  SFM_TRY(oBest.fetch(s)); SFM_TRY(oStatus.fetch(s)); SFM_TRY(oSummary.fetch(s));
+                     o.dev(), dPtr, w, s));
+  SFM_TRY(oCams.fetch(s));
+  SFM_TRY(o.fetch(s));
   return stream_sync(s);
 }
 
@@ -708,12 +649,12 @@ int sfm_ba_resect(sfm_ba_problem* p, double max_err2, int max_hyp, double lambda
                   const double* cam_scale, unsigned char* obs_inlier, int* n_inliers, int* best_hyp, int* status, int64_t* summary) {
   const char* who = "sfm_ba_resect";
   SFM_TRY(ba_check_handle(p));
-  SFM_TRY(resect_check_args(who, max_err2, max_hyp, lambda, iters));
+  SFM_TRY(robust_check_args(who, max_err2, max_hyp, lambda, iters));
   SFM_TRY(ba_refuse_comm(p, who, "the points are sharded; the replicas would diverge"));
   BaDev& d = p->dev;
   const int V = d.V;
   SFM_TRY(ba_flush(p));                                  // a deferred back substitution still owes the points its update
-  if (summary) for (int k = 0; k < 6; ++k) summary[k] = 0;
+  robust_summary_clear(summary);
   if (d.N == 0 || d.M == 0) {                            // no observation anywhere: every camera that is not held has too few
     for (int c = 0; c < V; ++c) {
       const bool held = cam_mask && cam_mask[c] == 0;
@@ -733,35 +674,26 @@ int sfm_ba_resect(sfm_ba_problem* p, double max_err2, int max_hyp, double lambda
   const size_t v = (size_t)V, m = (size_t)d.M;
   DevBuf<unsigned char> dMask;
   DevBuf<double> dSc;
-  HostOut<unsigned char> oInlier;
-  HostOut<int> oCount, oBest, oStatus;
+  RobustOut o;
   ResectWork w;
   SFM_TRY(dMask.upload_if(cam_mask, v, s));
   SFM_TRY(dSc.upload_if(cam_scale, v, s));
   p->upload_bytes += (long long)((cam_mask ? v : 0) + (cam_scale ? sizeof(double) * v : 0));
-  SFM_TRY(oInlier.want(obs_inlier, m, s)); SFM_TRY(oCount.want(n_inliers, v, s));
-  SFM_TRY(oBest.want(best_hyp, v, s)); SFM_TRY(oStatus.want(status, v, s));
-  SFM_TRY(w.summary.alloc(6, s));
+  SFM_TRY(o.want(m, v, obs_inlier, n_inliers, best_hyp, status, summary, s));
   RsArgs a = {};
-  a.w.V = V; a.w.ptr = p->cam_ptr; a.w.obs = p->cam_obs; a.w.obs_pt = d.obs_pt;
-  a.w.u = d.u; a.w.v = d.v; a.w.px = d.px; a.w.py = d.py; a.w.pz = d.pz;
-  a.w.cam_scale = dSc.p;
+  a.w = cam_obs_view_resident(p, dSc.p);
   a.mask = dMask.p;
   a.max_err2 = max_err2; a.max_hyp = max_hyp; a.lambda = lambda; a.iters = iters; a.quirks = quirks;
   a.cams_in = d.cams; a.cams_out = d.cams;               // in place: only solved cameras are written
-  a.best_hyp = oBest.dev(); a.status = oStatus.dev(); a.obs_inlier = oInlier.dev(); a.n_inliers = oCount.dev();
-  a.summary = w.summary.p;
+  o.dev().into(a);
   SFM_TRY(resect_enqueue(who, a, w, p->h_cam_ptr.data(), cam_mask, s));
   if (v_free > 0) SFM_TRY(ba_enqueue_prep(p));           // the expansion sfm_ba_screen will read, of the cameras that stand
   a.prep = d.prep[p->cur];
-  SFM_TRY(resect_enqueue_judge(a, s));
+  resect_judge_kernel<<<V, kRsThreads, 0, s>>>(a);
+  SFM_HIP(hipGetLastError());
   SFM_TRY(ba_state_changed(p));                          // new cameras
-  unsigned long long sum[6] = {0, 0, 0, 0, 0, 0};
-  SFM_TRY(w.summary.download(sum, 6, s));
-  SFM_TRY(oInlier.fetch(s)); SFM_TRY(oCount.fetch(s)); SFM_TRY(oBest.fetch(s)); SFM_TRY(oStatus.fetch(s));
-  SFM_TRY(stream_sync(s));
-  if (summary) for (int k = 0; k < 6; ++k) summary[k] = (int64_t)sum[k];
-  return SFM_OK;
+  SFM_TRY(o.fetch(s));
+  return stream_sync(s);
 }
 
 }  // extern "C"

@@ -3,12 +3,10 @@
 // Everything here is compiled WITHOUT automatic contraction and spells its FMAs out: every kernel that includes it
 // executes the same operations per observation, so a point's bits do not depend on which instantiation serves it.
 // The pragma stays in force for the rest of the translation unit: include this header AFTER the code that is to keep the
-// default contraction (tri_tracks_linear_kernel), outside any namespace.
+// default contraction (tri_tracks_linear_kernel), outside any namespace.  The residual is sfm_obs_test.h's.
 #pragma once
 
-#include "sfm_common.h"
-
-#pragma clang fp contract(off)
+#include "sfm_obs_test.h"      // contraction is off from here on
 
 namespace sfm {
 
@@ -26,14 +24,14 @@ __device__ __forceinline__ void track_view(const double* P, double ku, double kv
                                            TrackSums& S) {
   double s[3], j[6];
   track_project(P, x0, x1, x2, x3, s);
-  const double iz = rcp_nr(s[2]), iz2 = iz * iz;
+  const double iz = obs_inv_depth(s), iz2 = iz * iz;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     j[c] = __builtin_fma(-s[0], P[8 + c], s[2] * P[c]) * iz2;
     j[3 + c] = __builtin_fma(-s[1], P[8 + c], s[2] * P[4 + c]) * iz2;
   }
-  const double eu = __builtin_fma(s[0], iz, -ku);
-  const double ev = __builtin_fma(s[1], iz, -kv);
+  double eu, ev;
+  obs_residual(s, ku, kv, eu, ev);      // (divides by the same reciprocal: it is formed once)
   S.a00 = __builtin_fma(j[3], j[3], __builtin_fma(j[0], j[0], S.a00));
   S.a10 = __builtin_fma(j[4], j[3], __builtin_fma(j[1], j[0], S.a10));
   S.a11 = __builtin_fma(j[4], j[4], __builtin_fma(j[1], j[1], S.a11));
@@ -51,9 +49,8 @@ __device__ __forceinline__ void track_residual(const double* P, double ku, doubl
                                                double x3, double& c, double& behind) {
   double s[3];
   track_project(P, x0, x1, x2, x3, s);
-  const double iz = rcp_nr(s[2]);
-  const double eu = __builtin_fma(s[0], iz, -ku);
-  const double ev = __builtin_fma(s[1], iz, -kv);
+  double eu, ev;
+  obs_residual(s, ku, kv, eu, ev);
   c = __builtin_fma(ev, ev, __builtin_fma(eu, eu, c));
   if (s[2] <= 0.0) behind += 1.0;
 }

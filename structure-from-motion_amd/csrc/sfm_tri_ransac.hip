@@ -25,8 +25,6 @@ namespace sfm {
 constexpr int kRanSlots = 6;        // observations per lane of the LDS tile: a track of up to 6 G observations is staged once
 constexpr int kRanObs = 15;         // doubles per staged observation: u, v, P[12], scale
 constexpr int kRanBlock = 64;       // 64 * 6 * 15 doubles = 46 080 bytes of LDS: three workgroups per CU (160 KB)
-constexpr int kRanMaxHyp = 65536;
-constexpr int kRanDefaultHyp = 128;
 
 static_assert(sizeof(CamPrep) == 19 * sizeof(double), "the centres of the prepared cameras are read with a stride of 19 doubles");
 
@@ -48,16 +46,12 @@ struct RansacArgs {
   unsigned long long* summary;  // [6]
 };
 
-// Is the observation an inlier of (x, 1)?  track_project / track_residual's operations and sfm_ba_screen's err2.
+// Is the observation an inlier of (x, 1)?  track_project, then the observation test (sfm_obs_test.h).
 __device__ __forceinline__ bool ransac_inlier(const double* P, double ku, double kv, double scale, double x0, double x1, double x2,
                                               double max_err2) {
   double s[3];
   track_project(P, x0, x1, x2, 1.0, s);
-  const double iz = rcp_nr(s[2]);
-  const double eu = __builtin_fma(s[0], iz, -ku);
-  const double ev = __builtin_fma(s[1], iz, -kv);
-  const double err2 = (scale * scale) * __builtin_fma(ev, ev, eu * eu);
-  return (s[2] > 0.0) & isfinite(err2) & (err2 <= max_err2);      // no short circuit: a branch per observation would serialise the walk
+  return obs_passes(s, obs_err2(s, ku, kv, scale), max_err2);
 }
 
 // The two rows a = u p3 - p1 and a = v p3 - p2 of an observation, added to N = sum a[0:3] a[0:3]^T and g = -sum a[3] a[0:3].
@@ -124,7 +118,7 @@ __global__ __launch_bounds__(kRanBlock) void tri_ransac_score_kernel(RansacArgs 
   double best_cos = 2.0, b0 = 0, b1 = 0, b2 = 0;
   if (n >= 2) {
     const long long P = ransac_pair_count(n);
-    const int H = P < (long long)a.max_hyp ? (int)P : a.max_hyp;
+    const int H = hyp_count(P, a.max_hyp);
     const bool one = n <= kCap;
     for (int hb = 0; hb < H; hb += G) {
       const int h = hb + lane;
@@ -251,14 +245,7 @@ __global__ __launch_bounds__(256) void tri_ransac_refit_kernel(RansacArgs a) {
   if (a.t.xout[3]) a.t.xout[3][p] = x3;
   if (a.n_inliers) a.n_inliers[p] = nin;
   if (a.status) a.status[p] = flags;
-  if (solved) {
-    atomicAdd(&a.summary[0], 1ULL);
-    if (flags & SFM_RANSAC_KEPT_HYPOTHESIS) atomicAdd(&a.summary[3], 1ULL);
-    if (nin) atomicAdd(&a.summary[4], (unsigned long long)nin);
-    if (n - nin) atomicAdd(&a.summary[5], (unsigned long long)(n - nin));
-  } else {
-    atomicAdd(&a.summary[(flags & SFM_RANSAC_TOO_FEW) ? 2 : 1], 1ULL);
-  }
+  robust_summary_add(a.summary, solved, false, flags & SFM_RANSAC_TOO_FEW, flags & SFM_RANSAC_KEPT_HYPOTHESIS, n, nin);
 }
 
 // C = -M^-1 p4 of every projection [M | p4] (the free form; the resident scene reads the centres of its cameras)
@@ -291,11 +278,8 @@ static int ransac_check_args(const char* who, int n_pts, int n_views, long long 
     set_error("%s: bad sizes n_pts=%d n_views=%d M=%lld", who, n_pts, n_views, M);
     return SFM_E_SHAPE;
   }
-  if (!(max_err2 >= 0.0)) { set_error("%s: max_err2 = %g must be >= 0", who, max_err2); return SFM_E_SHAPE; }
+  SFM_TRY(robust_check_args(who, max_err2, max_hyp, lambda, iters));
   if (!(cos_min_angle >= -1.0)) { set_error("%s: cos_min_angle = %g must be >= -1 (>= 1 switches the gate off)", who, cos_min_angle); return SFM_E_SHAPE; }
-  if (max_hyp < 0 || max_hyp > kRanMaxHyp) { set_error("%s: max_hyp = %d must be in 1 .. %d (0 = %d)", who, max_hyp, kRanMaxHyp, kRanDefaultHyp); return SFM_E_SHAPE; }
-  if (iters < 0) { set_error("%s: iters = %d must be >= 0", who, iters); return SFM_E_SHAPE; }
-  if (!(lambda >= 0.0)) { set_error("%s: lambda = %g must be >= 0", who, lambda); return SFM_E_SHAPE; }
   return group_width_check(who, group);
 }
 
@@ -311,7 +295,7 @@ struct RansacWork {
 // narrowest group whose tile holds the longest track, widened while the call is short of waves.
 static int ransac_enqueue(RansacArgs a, RansacWork& w, int group, long long M, int max_track, hipStream_t s) {
   const size_t n = (size_t)a.t.n_pts;
-  if (a.max_hyp == 0) a.max_hyp = kRanDefaultHyp;
+  if (a.max_hyp == 0) a.max_hyp = kHypDefault;
   if (!a.best_hyp) { SFM_TRY(w.best_hyp.alloc(n, s)); a.best_hyp = w.best_hyp.p; }
   if (!a.summary) { SFM_TRY(w.summary.alloc(6, s)); a.summary = w.summary.p; }
   SFM_TRY(w.hyp_count.alloc(n, s));
@@ -330,8 +314,7 @@ static int ransac_enqueue(RansacArgs a, RansacWork& w, int group, long long M, i
 static int ransac_run(const char* who, int n_pts, int n_views, long long M, const int* d_pt_ptr, const int* d_cam_idx,
                       const double* d_uv, const double* d_projs, const double* d_cam_scale, double max_err2, double cos_min_angle,
                       int max_hyp, double lambda, int iters, int group, const double* d_X_init, double* d_X_out,
-                      unsigned char* d_obs_inlier, int* d_n_inliers, int* d_best_hyp, int* d_status, int64_t* d_summary,
-                      RansacWork& w, hipStream_t s) {
+                      const RobustPtrs& out, RansacWork& w, hipStream_t s) {
   int max_track = 0;
   SFM_TRY(tracks_validate(who, n_pts, n_views, M, d_pt_ptr, d_cam_idx, &max_track, s));
   SFM_TRY(w.centres.alloc(3 * (size_t)n_views, s));
@@ -341,8 +324,7 @@ static int ransac_run(const char* who, int n_pts, int n_views, long long M, cons
   a.t = track_view_free(n_pts, n_views, M, d_pt_ptr, d_cam_idx, d_uv, d_projs, d_X_init, d_X_out);
   a.centres = w.centres.p; a.centre_stride = 3; a.cam_scale = d_cam_scale;
   a.max_err2 = max_err2; a.cos_min_angle = cos_min_angle; a.max_hyp = max_hyp; a.lambda = lambda; a.iters = iters;
-  a.best_hyp = d_best_hyp; a.obs_inlier = d_obs_inlier; a.n_inliers = d_n_inliers; a.status = d_status;
-  a.summary = reinterpret_cast<unsigned long long*>(d_summary);
+  out.into(a);
   return ransac_enqueue(a, w, group, M, max_track, s);
 }
 
@@ -353,10 +335,10 @@ using namespace sfm;
 extern "C" {
 
 int sfm_tri_ransac_pair(int n, int max_hyp, int h, int* i, int* j) {
-  if (max_hyp == 0) max_hyp = kRanDefaultHyp;
-  if (n < 2 || max_hyp < 1 || max_hyp > kRanMaxHyp) return 0;
+  if (max_hyp == 0) max_hyp = kHypDefault;
+  if (n < 2 || max_hyp < 1 || max_hyp > kHypMax) return 0;
   const long long P = ransac_pair_count(n);
-  const int H = P < (long long)max_hyp ? (int)P : max_hyp;
+  const int H = hyp_count(P, max_hyp);
   if (h >= 0 && h < H && i != nullptr && j != nullptr) ransac_pair_of(n, ransac_pair_number(P, max_hyp, h), i, j);
   return H;
 }
@@ -377,7 +359,8 @@ int sfm_tri_tracks_ransac_dev(int n_pts, int n_views, int64_t M, const int* d_pt
   SFM_TRY(tracks_check_ptrs(who, "null device pointer", M, d_pt_ptr, d_cam_idx, d_uv, d_projs, d_X_out));
   RansacWork w;
   SFM_TRY(ransac_run(who, n_pts, n_views, M, d_pt_ptr, d_cam_idx, d_uv, d_projs, d_cam_scale, max_err2, cos_min_angle, max_hyp,
-                     lambda, iters, group, d_X_init, d_X_out, d_obs_inlier, d_n_inliers, d_best_hyp, d_status, d_summary, w, s));
+                     lambda, iters, group, d_X_init, d_X_out, RobustPtrs{d_obs_inlier, d_n_inliers, d_best_hyp, d_status, d_summary},
+                     w, s));
   return stream_sync(s);      // the work buffers go back to the pool with this call
 }
 
@@ -388,7 +371,7 @@ int sfm_tri_tracks_ransac(int n_pts, int n_views, int64_t M, const int* pt_ptr, 
   const char* who = "sfm_tri_tracks_ransac";
   SFM_TRY(ensure_init());
   SFM_TRY(ransac_check_args(who, n_pts, n_views, M, max_err2, cos_min_angle, max_hyp, lambda, iters, group));
-  if (summary) for (int k = 0; k < 6; ++k) summary[k] = 0;
+  robust_summary_clear(summary);
   if (n_pts == 0) return SFM_OK;
   SFM_TRY(tracks_check_ptrs(who, "null pointer", M, pt_ptr, cam_idx, uv, projs, X_out));
   hipStream_t s = ctx().stream;
@@ -396,9 +379,7 @@ int sfm_tri_tracks_ransac(int n_pts, int n_views, int64_t M, const int* pt_ptr, 
   DevBuf<int> dPtr, dCam;
   DevBuf<double> dUV, dP, dSc, dX;
   HostOut<double> oX;
-  HostOut<unsigned char> oInlier;
-  HostOut<int> oCount, oBest, oStatus;
-  HostOut<int64_t> oSummary;
+  RobustOut o;
   RansacWork w;
   SFM_TRY(dPtr.upload(pt_ptr, n + 1, s));
   SFM_TRY(dCam.upload(cam_idx, m, s));
@@ -406,12 +387,12 @@ int sfm_tri_tracks_ransac(int n_pts, int n_views, int64_t M, const int* pt_ptr, 
   SFM_TRY(dP.upload(projs, 12 * (size_t)n_views, s));
   SFM_TRY(dSc.upload_if(cam_scale, (size_t)n_views, s));
   SFM_TRY(dX.upload_if(X_init, 4 * n, s));
-  SFM_TRY(oX.want(X_out, 4 * n, s)); SFM_TRY(oInlier.want(obs_inlier, m, s)); SFM_TRY(oCount.want(n_inliers, n, s));
-  SFM_TRY(oBest.want(best_hyp, n, s)); SFM_TRY(oStatus.want(status, n, s)); SFM_TRY(oSummary.want(summary, 6, s));
+  SFM_TRY(oX.want(X_out, 4 * n, s));
+  SFM_TRY(o.want(m, n, obs_inlier, n_inliers, best_hyp, status, summary, s));
   SFM_TRY(ransac_run(who, n_pts, n_views, M, dPtr.p, dCam.p, dUV.p, dP.p, dSc.p, max_err2, cos_min_angle, max_hyp, lambda, iters,
-                     group, dX.p, oX.dev(), oInlier.dev(), oCount.dev(), oBest.dev(), oStatus.dev(), oSummary.dev(), w, s));
-  SFM_TRY(oX.fetch(s)); SFM_TRY(oInlier.fetch(s)); SFM_TRY(oCount.fetch(s));
-  SFM_TRY(oBest.fetch(s)); SFM_TRY(oStatus.fetch(s)); SFM_TRY(oSummary.fetch(s));
+                     group, dX.p, oX.dev(), o.dev(), w, s));
+  SFM_TRY(oX.fetch(s));
+  SFM_TRY(o.fetch(s));
   return stream_sync(s);
 }
 
@@ -423,35 +404,27 @@ int sfm_ba_retriangulate(sfm_ba_problem* p, double max_err2, double cos_min_angl
   BaDev& d = p->dev;
   SFM_TRY(ransac_check_args(who, d.N, d.V > 0 ? d.V : 1, d.M, max_err2, cos_min_angle, max_hyp, lambda, iters, group));
   SFM_TRY(ba_flush(p));                                  // a deferred back substitution still owes the points its update
-  if (summary) for (int k = 0; k < 6; ++k) summary[k] = 0;
+  robust_summary_clear(summary);
   if (d.N == 0) return SFM_OK;
   SFM_TRY(ba_prepared_cameras(p, who));                  // the expanded cameras the linearisation reads
   hipStream_t s = p->stream;
   const size_t n = (size_t)d.N, m = (size_t)d.M;
   DevBuf<double> dP, dSc;
-  HostOut<unsigned char> oInlier;
-  HostOut<int> oCount, oBest, oStatus;
+  RobustOut o;
   RansacWork w;
   RansacArgs a = {};
   SFM_TRY(track_view_resident(p, dP, &a.t));
   SFM_TRY(dSc.upload_if(cam_scale, (size_t)d.V, s));
   if (cam_scale) p->upload_bytes += (long long)(sizeof(double) * d.V);
-  SFM_TRY(oInlier.want(obs_inlier, m, s)); SFM_TRY(oCount.want(n_inliers, n, s));
-  SFM_TRY(oBest.want(best_hyp, n, s)); SFM_TRY(oStatus.want(status, n, s));
-  SFM_TRY(w.summary.alloc(6, s));
+  SFM_TRY(o.want(m, n, obs_inlier, n_inliers, best_hyp, status, summary, s));
   a.centres = d.prep[p->cur]->C; a.centre_stride = 19;      // the centres of the prepared cameras
   a.cam_scale = dSc.p;
   a.max_err2 = max_err2; a.cos_min_angle = cos_min_angle; a.max_hyp = max_hyp; a.lambda = lambda; a.iters = iters;
-  a.best_hyp = oBest.dev(); a.obs_inlier = oInlier.dev(); a.n_inliers = oCount.dev(); a.status = oStatus.dev();
-  a.summary = w.summary.p;
+  o.dev().into(a);
   SFM_TRY(ransac_enqueue(a, w, group, d.M, p->max_track, s));
   SFM_TRY(ba_reset_stats(p));                            // new points, as after sfm_ba_set_points
-  unsigned long long sum[6] = {0, 0, 0, 0, 0, 0};
-  SFM_TRY(w.summary.download(sum, 6, s));
-  SFM_TRY(oInlier.fetch(s)); SFM_TRY(oCount.fetch(s)); SFM_TRY(oBest.fetch(s)); SFM_TRY(oStatus.fetch(s));
-  SFM_TRY(stream_sync(s));
-  if (summary) for (int k = 0; k < 6; ++k) summary[k] = (int64_t)sum[k];
-  return SFM_OK;
+  SFM_TRY(o.fetch(s));
+  return stream_sync(s);
 }
 
 }  // extern "C"
