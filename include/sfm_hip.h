@@ -621,6 +621,69 @@ int sfm_ba_resect(sfm_ba_problem* p, double max_err2, int max_hyp, double lambda
  * out of range) and, for 0 <= h < H, the triple (*i < *j < *l) of hypothesis h. */
 int sfm_resect_triple(int n, int max_hyp, int h, int* i, int* j, int* l);
 
+/* ---- robust two-view geometry: sampled eight-point hypotheses, inlier refit ----------------------------------------
+ * sfm_fundamental_ransac scores host-drawn samples by |x_r^T F x_l| on normalised coordinates (a residual without a unit),
+ * returns the best eight-point matrix as it is and handles one pair of views.  Here the consistent subset of the matches
+ * between two views is found, for a batch of sets in one call: the third robust estimator, next to the point
+ * (sfm_tri_tracks_ransac) and the camera (sfm_resect_ransac).  A call holds n_sets sets of matches; left and right are
+ * [2][M] pixel coordinates (the x row, then the y row); set s owns the matches set_ptr[s] .. set_ptr[s + 1] - 1, n of them.
+ * The rule, per set:
+ *   1. n < 9: SFM_TWOVIEW_TOO_FEW.
+ *   2. The test.  For a matrix F (row-major 3x3, pixel coordinates): a = F (x_l, y_l, 1)^T, b = F^T (x_r, y_r, 1)^T,
+ *      e = (x_r, y_r, 1) . a; the squared Sampson distance d2 = e^2 / (a0^2 + a1^2 + b0^2 + b1^2) is in pixels squared.  A
+ *      match is an INLIER of F iff d2 is finite and d2 <= max_err2.  One function (twoview_inlier, csrc/sfm_obs_test.h)
+ *      that every stage below calls.
+ *   3. Normalisation.  T = [s 0 -s mx; 0 s -s my; 0 0 1] per image over all n matches of the set: (mx, my) the centroid,
+ *      s = sqrt(2) / (mean distance from the centroid) (Hartley; the layout of epipolar_processor.py:97-137, whose scale
+ *      sqrt(2 n) / (sum of distances) differs from this by sqrt(n)).  If T_l or T_r is not finite (a NaN coordinate,
+ *      identical points) the set is SFM_TWOVIEW_NO_MODEL.
+ *   4. Hypotheses.  H = max_hyp (0 means 128; range 1 .. 65 536), whatever n.  Hypothesis h uses, for k = 0 .. 7, the match
+ *      lo_k + mix(8 h + k) mod (hi_k - lo_k) with lo_k = floor(k n / 8), hi_k = floor((k + 1) n / 8): one match of every
+ *      eighth of the set, so the eight indices are distinct and ascending.  mix is the splitmix64 finaliser in unsigned
+ *      64-bit arithmetic: z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *      z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31.  No random-number state and no floating point:
+ *      sfm_twoview_sample returns the same indices on any machine.
+ *   5. Matrix of a sample.  The eight-point solve of sfm_fundamental_eight_point on the normalised matches: the null
+ *      vector of the 8x9 design matrix (rows x1 x2, y1 x2, x2, x1 y2, y1 y2, y2, x1, y1, 1 with 1 = left, 2 = right), as
+ *      a 3x3 matrix projected to rank 2 (its two largest singular values kept; invalid unless sigma_1 > 3 eps sigma_0),
+ *      WITHOUT the division by f[2][2]; then F = T_r^T f T_l, scaled to Frobenius norm 1 with its entry of largest
+ *      magnitude positive (the lowest index on a tie).  Invalid if rank-deficient or not finite.  How the null vector is
+ *      found is not part of the rule.
+ *   6. Sample gate.  A hypothesis is invalid unless its own eight matches are inliers of it.
+ *   7. Score, lexicographic: the inlier count over all n matches (an integer); then the lower h.  A winner needs a count
+ *      of at least 9, otherwise SFM_TWOVIEW_NO_MODEL.
+ *   8. Refit, up to `iters` rounds.  The inlier mask of the standing matrix; the transforms of step 3 over those inliers
+ *      only; the 9x9 moment matrix A^T A of the inliers' design rows; its eigenvector of smallest eigenvalue, then rank-2
+ *      projection, de-normalisation and scaling as in step 5.  The round stands iff the result is valid and its inlier
+ *      count over all n is at least the standing count (it then becomes the standing matrix and count); otherwise the
+ *      rounds stop.  SFM_TWOVIEW_KEPT_HYPOTHESIS iff iters > 0 and no round stood.
+ *   9. Outputs, all optional but F_out.  F_out[n_sets][9]: the standing matrix, scaled as in step 5; nine zeros with
+ *      TOO_FEW or NO_MODEL.  obs_inlier[M], n_inliers, best_hyp (-1 without a model), status and summary[6] (sets solved,
+ *      sets NO_MODEL, sets TOO_FEW, sets KEPT_HYPOTHESIS, matches flagged inlier, matches of solved sets flagged outlier)
+ *      describe the standing matrix, judged once more by the function of step 2.
+ * Determinism: no floating-point atomic; the counts are integers; every floating-point sum over matches (the sums of the
+ * normalisation and the 45 moment sums) is formed per slice of 64 consecutive matches of the set and the slices are added
+ * in ascending order.  A set's bits depend on its own matches and the options only, never on the batch.
+ * set_ptr[n_sets + 1] is a HOST array in both forms (the launches are planned from it).  A NaN or negative max_err2,
+ * max_hyp outside 0 .. 65 536, iters < 0, or a set_ptr that does not start at 0, decreases or does not end at M return
+ * SFM_E_SHAPE and launch nothing.  The _dev form takes device pointers (d_summary: int64[6] on the device), runs on
+ * hip_stream and returns when the work is done (its work buffers go back to the pool). */
+#define SFM_TWOVIEW_TOO_FEW          1   /* the set has fewer than 9 matches */
+#define SFM_TWOVIEW_NO_MODEL         2   /* no valid hypothesis with at least 9 inliers, or no finite normalisation */
+#define SFM_TWOVIEW_KEPT_HYPOTHESIS  4   /* no refit round stood: the matrix is the winning hypothesis itself */
+int sfm_twoview_ransac(int n_sets, const int* set_ptr /*host [n_sets+1]*/, int64_t M, const double* left /*[2][M]*/,
+                       const double* right /*[2][M]*/, double max_err2, int max_hyp, int iters,
+                       double* F_out /*[n_sets][9]*/, unsigned char* obs_inlier /*[M] or NULL*/,
+                       int* n_inliers /*[n_sets] or NULL*/, int* best_hyp /*[n_sets] or NULL*/,
+                       int* status /*[n_sets] or NULL*/, int64_t* summary /*[6] or NULL*/);
+int sfm_twoview_ransac_dev(int n_sets, const int* set_ptr /*host [n_sets+1]*/, int64_t M, const double* d_left,
+                           const double* d_right, double max_err2, int max_hyp, int iters, double* d_F_out,
+                           unsigned char* d_obs_inlier, int* d_n_inliers, int* d_best_hyp, int* d_status,
+                           int64_t* d_summary, void* hip_stream);
+/* Host only, needs no device: the hypothesis count H of a set of n matches (0 for n < 9 or a max_hyp out of range) and,
+ * for 0 <= h < H, the eight ascending match indices of hypothesis h. */
+int sfm_twoview_sample(int n, int max_hyp, int h, int idx[8]);
+
 /* ---- covariance of the resident scene: per-camera and per-point blocks ---------------------------------------------
  * How well the current state is determined.  With H = J^T J + lambda I = [A B; B^T D] of one linearisation at the current
  * state (r, Jp, Jx exactly as the iterations form them, the Q2 bit of `quirks` honoured; with use_loss = 1 and a loss on
@@ -1020,6 +1083,12 @@ int sfm_track_pairs_dev(sfm_track_store* s, int ref, int que, int* d_count, int*
                         double* d_ref_pts, double* d_que_pts, void* hip_stream);
 int sfm_track_pairs(sfm_track_store* s, int ref, int que, int* n, int* r_idx, int* q_idx, double* ref_pts,
                     double* que_pts);
+/* The pairs of a track store's table[ref][que] (sfm_track_pairs_dev, into buffers of the pool) verified by
+ * sfm_twoview_ransac_dev as one set on the library's stream: *n pairs, r_idx[n], q_idx[n], inlier[n] (HOST arrays that hold
+ * the reference view's key count, or NULL), F_out[9], best_hyp and status of the set.  Only the count comes down between
+ * the two steps; the coordinates stay on the device. */
+int sfm_twoview_verify_pairs(sfm_track_store* s, int ref, int que, double max_err2, int max_hyp, int iters, int* n, int* r_idx,
+                           int* q_idx, unsigned char* inlier, double F_out[9], int* best_hyp, int* status);
 /* KeyTrack.update_usage: table[view][view, keys[i]] = tri[i] (host arrays).  A key given twice takes the LAST value,
  * as NumPy's fancy assignment does; a key outside [0, n) returns SFM_E_SHAPE and writes nothing. */
 int sfm_track_update_usage(sfm_track_store* s, int view, int n, const int* keys, const int* tri);

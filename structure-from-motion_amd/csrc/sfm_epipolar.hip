@@ -5,7 +5,7 @@
 //                            (epipolar_processor.py:97-137) -> pairs [n][4] and the two 3x3 transforms
 //   fund_eight_point_kernel  wave per hypothesis: 8x9 design matrix -> null vector by a wave-cooperative one-sided
 //                            Jacobi (9x9 with a zero row), rank-2 projection by a 3x3 Jacobi SVD, / f[2][2]
-//                            (epipolar:140-193)
+//                            (epipolar:140-193; the solve up to the projection is sfm_eight_point.h's)
 //   fund_score_kernel        workgroup per hypothesis: |x_r^T F x_l| < threshold over all pairs (epipolar:231-239)
 //   fund_finish_kernel       inlier mask of the winner + de-normalisation (epipolar:251-267)
 //   essential_kernel / pose_candidates_kernel   single-thread 3x3 algebra (epipolar:60-95, campose:29-100)
@@ -18,29 +18,9 @@
 #include <vector>
 
 #include "sfm_common.h"
+#include "sfm_eight_point.h"
 
 namespace sfm {
-
-// 3x3 SVD pieces: columns of B become sigma_c u_c, V the right singular vectors; ord[] sorts sigma descending.
-// B is first scaled by the power of two that brings max|B| into [1, 2): exact, so the result is that of 2^e B, whose
-// Jacobi sums al, be and al*be cannot overflow (they did from max|B| ~ 2^255) or lose bits to underflow (below ~2^-511).
-// sigma and the columns of B come out scaled by 2^e; every caller uses sigma only in ratios or as B / sigma.
-__device__ void svd3(double (&B)[3][3], double (&V)[3][3], double (&sig)[3], int (&ord)[3]) {
-  double mx = 0.0;
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) mx = fmax(mx, fabs(B[i][j]));        // fmax skips NaN, which stays NaN below
-  if (mx > 0.0 && mx <= 1.7976931348623157e308) {
-    const int e = -ilogb(mx);
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) B[i][j] = ldexp(B[i][j], e);
-  }
-  jacobi_right_vectors<3>(B, V, 40);
-  for (int c = 0; c < 3; ++c) sig[c] = sqrt(B[0][c] * B[0][c] + B[1][c] * B[1][c] + B[2][c] * B[2][c]);
-  ord[0] = 0; ord[1] = 1; ord[2] = 2;
-  for (int i = 0; i < 2; ++i)
-    for (int j = i + 1; j < 3; ++j)
-      if (sig[ord[j]] > sig[ord[i]]) { const int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
-}
 
 __global__ __launch_bounds__(256) void fund_normalize_kernel(int n, const double* __restrict__ left, const double* __restrict__ right,
                                                              double* __restrict__ pairs /*[n][4]*/, double* __restrict__ T /*[2][9]*/) {
@@ -81,8 +61,8 @@ __global__ __launch_bounds__(256) void fund_normalize_kernel(int n, const double
 }
 
 // epipolar_processor.py:140-193, one wave per hypothesis: lanes 0..7 hold the rows of the 8x9 design matrix
-// (lane 8 a zero row), lanes 16..24 the identity; after jacobi_rows_wave the null vector is the column of V
-// whose B V column has the smallest norm.  The 3x3 rank-2 projection runs on lane 0.
+// (lane 8 a zero row), lanes 16..24 the identity; null vector and rank-2 projection (on lane 0) are sfm_eight_point.h's,
+// shared with the robust two-view geometry.
 __global__ __launch_bounds__(64) void fund_eight_point_kernel(int n_hyp, const int* __restrict__ samples, const double* __restrict__ pairs,
                                                               double* __restrict__ F_out, int* __restrict__ status) {
   const int h = blockIdx.x;
@@ -93,47 +73,15 @@ __global__ __launch_bounds__(64) void fund_eight_point_kernel(int n_hyp, const i
   for (int c = 0; c < 9; ++c) row[c] = 0.0;
   if (lane < 8) {
     const int idx = samples ? samples[8 * h + lane] : lane;
-    const double* p = pairs + 4 * (size_t)idx;
-    const double x1 = p[0], y1 = p[1], x2 = p[2], y2 = p[3];
-    row[0] = x1 * x2; row[1] = y1 * x2; row[2] = x2;
-    row[3] = x1 * y2; row[4] = y1 * y2; row[5] = y2;
-    row[6] = x1;      row[7] = y1;      row[8] = 1.0;
+    eight_point_row(pairs + 4 * (size_t)idx, row);
   } else if (lane >= 16 && lane < 25) {
 #pragma unroll
     for (int c = 0; c < 9; ++c) row[c] = (c == lane - 16) ? 1.0 : 0.0;
   }
-  jacobi_rows_wave<9>(row, lane, 40);
-  int best = 0;
-  double bn = 0;
-#pragma unroll
-  for (int c = 0; c < 9; ++c) {
-    const double nn = wave_lane0(group_sum<16>(lane < 16 ? row[c] * row[c] : 0.0));
-    if (c == 0 || nn < bn) { bn = nn; best = c; }
-  }
-  double mine = 0.0;
-#pragma unroll
-  for (int c = 0; c < 9; ++c) mine = (c == best) ? row[c] : mine;
-  double f[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {                                  // f_ = reshape(null vector, (3, 3))
-    const int lo = __builtin_amdgcn_readlane(__double2loint(mine), 16 + k);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(mine), 16 + k);
-    f[k] = __hiloint2double(hi, lo);
-  }
+  double f[9], f2[9];
+  eight_point_null_vector(row, lane, f);
   if (lane != 0) return;
-  double B[3][3], V3[3][3], sig[3];
-  int ord[3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) B[i][j] = f[3 * i + j];
-  svd3(B, V3, sig, ord);
-  // matrix_rank tolerance: sigma_max * max(M, N) * eps (numpy.linalg.matrix_rank)
-  const double tol = sig[ord[0]] * 3.0 * 2.220446049250313e-16;
-  int st = (sig[ord[1]] > tol) ? SFM_OK : SFM_E_RANK;
-  if (!(sig[ord[0]] == sig[ord[0]])) st = SFM_E_RANK;
-  double f2[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j)       // u diag(s0, s1, 0) v^T = sum over the two largest of (sigma u)_i v_j
-      f2[3 * i + j] = B[i][ord[0]] * V3[j][ord[0]] + B[i][ord[1]] * V3[j][ord[1]];
+  const int st = eight_point_project(f, f2);
   for (int k = 0; k < 9; ++k) F_out[9 * (size_t)h + k] = f2[k] / f2[8];
   status[h] = st;
 }

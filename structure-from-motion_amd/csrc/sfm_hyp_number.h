@@ -2,7 +2,8 @@
 // (sfm_tri_ransac.hip) and the triples of a camera's observations (sfm_resect.hip), both in lexicographic order, all of
 // them up to max_hyp, else evenly spaced.  No random number anywhere.  The floating-point estimates below only seed integer
 // searches that end at the exact answer, so the results do not depend on how the including file contracts them.
-// Below the numbering, what else the two share: the six summary counters and the host frame of their entry points.
+// The eight-match samples of the robust two-view geometry (sfm_twoview.hip) are drawn by a stratified integer sampler.
+// Below the numbering, what else the three share: the six summary counters and the host frame of their entry points.
 #pragma once
 
 #include <algorithm>
@@ -57,6 +58,23 @@ __host__ __device__ inline void triple_of(int n, long long k, int* i, int* j, in
   *i = first;
   *j = first + 1 + r;
   *l = first + 1 + s;
+}
+
+// ---- eight-index samples of a set of matches (sfm_twoview.hip): C(n, 8) passes 2^63 near n = 2 000, so the 8-subsets are
+// not numbered; a stratified integer sampler takes their place.  Stratum k of a set of n >= 9 matches is
+// floor(k n / 8) .. floor((k + 1) n / 8) - 1 (never empty); hypothesis h takes from it the match
+// lo_k + mix(8 h + k) mod (hi_k - lo_k), mix being the splitmix64 finaliser: no state, no floating point, eight distinct
+// ascending indices.
+__host__ __device__ inline unsigned long long splitmix64_mix(unsigned long long z) {
+  z += 0x9E3779B97F4A7C15ULL;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+  return z ^ (z >> 31);
+}
+
+__host__ __device__ inline int twoview_sample_index(int n, int h, int k) {
+  const long long lo = (long long)k * n / 8, hi = (long long)(k + 1) * n / 8;
+  return (int)(lo + (long long)(splitmix64_mix(8ULL * (unsigned long long)h + (unsigned long long)k) % (unsigned long long)(hi - lo)));
 }
 
 // ---- the summary: 0 solved | 1 no model | 2 too few | 3 kept the hypothesis | 4 inliers | 5 outliers of the solved ----

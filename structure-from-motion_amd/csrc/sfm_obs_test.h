@@ -2,7 +2,9 @@
 // (u, v), its scaled square, the inlier predicate.  Whoever judges an observation (sfm_ba_screen, the robust triangulation
 // and resection, the residuals of the ragged-track kernels) projects by its own data layout (track_project for a 3x4 P,
 // rs_project_pose for [m | t], obs_project_cam for a prepared camera) and continues here: resect then screen, retriangulate
-// then cull, free and resident form agree on every decision because they execute the same function.
+// then cull, free and resident form agree on every decision because they execute the same function.  Below it the test
+// of one match against a fundamental matrix (the squared Sampson distance), which every stage of the robust two-view
+// geometry calls in the same way.
 //
 // Compiled WITHOUT automatic contraction, the FMAs spelled out.  The pragma is lexical and stays in force for the rest of
 // the translation unit: include this header outside any namespace and AFTER all code that keeps the compiler's default
@@ -39,6 +41,22 @@ __device__ __forceinline__ double obs_err2(const double* s, double u, double v, 
 // in front of the camera, finite, within the bound; no short circuit: a branch per observation would serialise a walk
 __device__ __forceinline__ bool obs_passes(const double* s, double err2, double max_err2) {
   return (s[2] > 0.0) & isfinite(err2) & (err2 <= max_err2);
+}
+
+// The test of one MATCH (x_l, y_l) <-> (x_r, y_r) against a fundamental matrix F (row-major, pixel coordinates): with
+// a = F (x_l, y_l, 1)^T, b = F^T (x_r, y_r, 1)^T and e = (x_r, y_r, 1) . a, the squared Sampson distance
+// d2 = e^2 / (a0^2 + a1^2 + b0^2 + b1^2) in pixels squared; an inlier iff d2 is finite and d2 <= max_err2.  Every stage
+// of the robust two-view geometry (sample gate, score, refit, judge) calls this one function; no branch.
+__host__ __device__ inline bool twoview_inlier(const double* F, double xl, double yl, double xr, double yr, double max_err2) {
+  const double a0 = __builtin_fma(F[0], xl, __builtin_fma(F[1], yl, F[2]));
+  const double a1 = __builtin_fma(F[3], xl, __builtin_fma(F[4], yl, F[5]));
+  const double a2 = __builtin_fma(F[6], xl, __builtin_fma(F[7], yl, F[8]));
+  const double b0 = __builtin_fma(F[0], xr, __builtin_fma(F[3], yr, F[6]));
+  const double b1 = __builtin_fma(F[1], xr, __builtin_fma(F[4], yr, F[7]));
+  const double e = __builtin_fma(xr, a0, __builtin_fma(yr, a1, a2));
+  const double den = __builtin_fma(a0, a0, a1 * a1) + __builtin_fma(b0, b0, b1 * b1);
+  const double d2 = (e * e) / den;
+  return (bool)((int)(__builtin_isfinite(d2) != 0) & (int)(d2 <= max_err2));
 }
 
 }  // namespace sfm

@@ -52,6 +52,10 @@ RANSAC_SUMMARY = ("pts_solved", "pts_no_model", "pts_too_few", "pts_kept_hypothe
 RESECT_TOO_FEW, RESECT_NO_MODEL, RESECT_KEPT_HYPOTHESIS, RESECT_SAMPLED, RESECT_HELD = 1, 2, 4, 8, 16
 RESECT_MAX_HYP, RESECT_DEFAULT_HYP, RESECT_MAX_OBS = 65536, 128, 1 << 20
 RESECT_SUMMARY = ("cams_solved", "cams_no_model", "cams_too_few", "cams_kept_hypothesis", "obs_inlier", "obs_outlier")
+TWOVIEW_TOO_FEW, TWOVIEW_NO_MODEL, TWOVIEW_KEPT_HYPOTHESIS = 1, 2, 4
+TWOVIEW_MAX_HYP, TWOVIEW_DEFAULT_HYP, TWOVIEW_MIN_MATCHES = 65536, 128, 9
+TWOVIEW_SUMMARY = ("sets_solved", "sets_no_model", "sets_too_few", "sets_kept_hypothesis", "matches_inlier", "matches_outlier")
+TWOVIEW_OUTPUTS = ("inlier", "n_inliers", "best_hyp", "status", "summary")
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2
 CAM_EMPTY, CAM_NONFINITE, CAM_BEHIND, CAM_HELD = 1, 2, 4, 8
 COV_CAM_HELD, COV_CAM_PIVOT, COV_PT_EMPTY, COV_PT_SINGULAR = 8, 16, 4, 8
@@ -226,6 +230,10 @@ SIGNATURES = {
     "sfm_resect_ransac_dev": [ci, _ip, i64, vp, vp, vp, cd, ci, cd, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp],
     "sfm_ba_resect": [vp, cd, ci, cd, ci, ci, ctypes.POINTER(ctypes.c_uint8), _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
     "sfm_resect_triple": [ci, ci, ci, _ip, _ip, _ip],
+    "sfm_twoview_ransac": [ci, _ip, i64, _dp, _dp, cd, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
+    "sfm_twoview_ransac_dev": [ci, _ip, i64, vp, vp, cd, ci, ci, vp, vp, vp, vp, vp, vp, vp],
+    "sfm_twoview_sample": [ci, ci, ci, _ip],
+    "sfm_twoview_verify_pairs": [vp, ci, ci, cd, ci, ci, _ip, _ip, _ip, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _ip],
     "sfm_ba_covariance": [vp, cd, ci, ci, ctypes.POINTER(ctypes.c_uint8), ci, _dp, _dp, _ip, _ip, _dp],
     "sfm_ba_covariance_plan": [ci, _ip, _ip, _ip, _ip],
     "sfm_ba_covariance_times": [vp, _dp],
@@ -584,6 +592,30 @@ def check_resect_views(view_ptr, uv, X):
     return view_ptr, uv, X
 
 
+def check_twoview(max_err2, max_hyp=0, iters=2):
+    """Options of a ``twoview_ransac`` call, without a device: returns ``(max_err2, max_hyp, iters)`` converted or raises
+    ValueError -- everything sfm_twoview_ransac refuses before it looks at the sets."""
+    max_err2 = float(max_err2)
+    if not max_err2 >= 0.0:
+        raise ValueError("max_err2 must be >= 0, got %r" % max_err2)
+    max_hyp = _count("max_hyp", max_hyp)
+    if max_hyp > TWOVIEW_MAX_HYP:
+        raise ValueError("max_hyp must be in 1 .. %d (0 = %d), got %r" % (TWOVIEW_MAX_HYP, TWOVIEW_DEFAULT_HYP, max_hyp))
+    return max_err2, max_hyp, _count("iters", iters)
+
+
+def check_twoview_sets(set_ptr, left, right):
+    """The arrays of a ``twoview_ransac`` call, without a device: ``(set_ptr int32 (S + 1,), left (2, M), right (2, M))``
+    converted or ValueError -- set_ptr must start at 0, not decrease and end at M."""
+    set_ptr = np.ascontiguousarray(set_ptr, dtype=np.int32).ravel()
+    left, right = f64(left), f64(right)
+    if left.ndim != 2 or left.shape[0] != 2 or right.shape != left.shape:
+        raise ValueError("left and right must both be (2, M), got %r and %r" % (left.shape, right.shape))
+    if set_ptr.shape[0] < 1 or set_ptr[0] != 0 or set_ptr[-1] != left.shape[1] or np.any(np.diff(set_ptr) < 0):
+        raise ValueError("set_ptr must start at 0, not decrease and end at M = %d" % left.shape[1])
+    return set_ptr, left, right
+
+
 def check_loss(kind, delta):
     """Arguments of a ``BaProblem.set_loss`` call, without a device: returns ``(kind, delta)`` converted or raises ValueError.
     ``kind`` is ``LOSS_NONE`` / ``LOSS_HUBER`` / ``LOSS_CAUCHY`` or its name; ``delta`` (normalised units) must be finite and
@@ -764,6 +796,45 @@ def resect_ransac_dev(view_ptr, n_obs, d_uv, d_X, max_err2, max_hyp=0, lam=0.5, 
     check(load().sfm_resect_ransac_dev(view_ptr.shape[0] - 1, iptr(view_ptr), int(n_obs), _vp(d_uv), _vp(d_X), _vp(d_cam_scale),
                                        max_err2, max_hyp, lam, iters, int(quirks), _vp(d_cams_init), _vp(d_cams_out), _vp(d_inlier),
                                        _vp(d_n_inliers), _vp(d_best_hyp), _vp(d_status), _vp(d_summary), _vp(stream)))
+
+
+def twoview_sample(n, max_hyp, h):
+    """``(H, idx)``: the hypothesis count of a set of ``n`` matches and the eight ascending match indices of hypothesis
+    ``h`` (sfm_twoview_sample; host only).  ``idx`` is eight times -1 when ``h`` is not in ``0 .. H - 1``."""
+    idx = np.full(8, -1, dtype=np.int32)
+    count = int(load().sfm_twoview_sample(int(n), int(max_hyp), int(h), iptr(idx)))
+    return count, tuple(int(i) for i in idx)
+
+
+def twoview_ransac(set_ptr, left, right, max_err2, max_hyp=0, iters=2, outputs=TWOVIEW_OUTPUTS):
+    """Robust fundamental matrix of every set of matches (sfm_twoview_ransac): stratified eight-point hypotheses scored by
+    their inlier count under the squared Sampson distance ``max_err2`` (pixels squared), then up to ``iters`` refits over
+    the inliers.  ``set_ptr`` (S + 1,) delimits the matches of a set in ``left`` / ``right`` (2, M) pixel coordinates.
+    Returns ``F (S, 3, 3)`` of Frobenius norm 1 (zeros without a model), ``inlier (M,) uint8, n_inliers (S,), best_hyp
+    (S,), status (S,) of TWOVIEW_* bits, summary (6,) int64`` in the order of ``TWOVIEW_SUMMARY``; an output not named in
+    ``outputs`` is not computed and comes back as None."""
+    set_ptr, left, right = check_twoview_sets(set_ptr, left, right)
+    max_err2, max_hyp, iters = check_twoview(max_err2, max_hyp, iters)
+    unknown = set(outputs) - set(TWOVIEW_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (TWOVIEW_OUTPUTS, sorted(unknown)))
+    n_sets, n_obs = set_ptr.shape[0] - 1, left.shape[1]
+    F = np.zeros((n_sets, 3, 3))
+    o = _ransac_outputs(n_sets, n_obs)
+    ptrs = [p if name in outputs else None for name, p in zip(TWOVIEW_OUTPUTS, _ransac_pointers(o))]
+    check(load().sfm_twoview_ransac(n_sets, iptr(set_ptr), n_obs, dptr(left), dptr(right), max_err2, max_hyp, iters, dptr(F), *ptrs))
+    return (F,) + tuple(getattr(o, name) if name in outputs else None for name in TWOVIEW_OUTPUTS)
+
+
+def twoview_ransac_dev(set_ptr, n_obs, d_left, d_right, max_err2, max_hyp=0, iters=2, d_F_out=0, d_inlier=0, d_n_inliers=0,
+                       d_best_hyp=0, d_status=0, d_summary=0, stream=0):
+    """``twoview_ransac`` on device pointers and a caller's stream (sfm_twoview_ransac_dev); ``set_ptr`` stays a host array,
+    optional arrays are 0."""
+    set_ptr = np.ascontiguousarray(set_ptr, dtype=np.int32).ravel()
+    max_err2, max_hyp, iters = check_twoview(max_err2, max_hyp, iters)
+    check(load().sfm_twoview_ransac_dev(set_ptr.shape[0] - 1, iptr(set_ptr), int(n_obs), _vp(d_left), _vp(d_right), max_err2,
+                                        max_hyp, iters, _vp(d_F_out), _vp(d_inlier), _vp(d_n_inliers), _vp(d_best_hyp),
+                                        _vp(d_status), _vp(d_summary), _vp(stream)))
 
 
 def pnp_nonlinear(uv_pix, pts_h, intrinsic, rot0, loc0, lam, iters, quirks=QUIRKS_REFERENCE):
@@ -1693,6 +1764,19 @@ class TrackStore:
         check(self._lib.sfm_track_pairs(self._h, int(ref), int(que), ctypes.byref(n), iptr(r), iptr(q), dptr(rp), dptr(qp)))
         n = n.value
         return r[:n], q[:n], rp[:3 * n].reshape(3, n), qp[:3 * n].reshape(3, n)
+
+    def verify_pairs(self, ref, que, max_err2, max_hyp=0, iters=2):
+        """The pairs of ``pairs(ref, que)`` verified on the device (sfm_twoview_verify_pairs): ``(r_idx (n,), q_idx (n,),
+        inlier (n,) uint8, F (3, 3), best_hyp, status)``; the coordinates are not downloaded."""
+        max_err2, max_hyp, iters = check_twoview(max_err2, max_hyp, iters)
+        cap = max(self.n_keys(ref), 1)
+        n, best, status = ctypes.c_int(), ctypes.c_int(-1), ctypes.c_int(0)
+        r, q, inl = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.uint8)
+        F = np.zeros((3, 3))
+        check(self._lib.sfm_twoview_verify_pairs(self._h, int(ref), int(que), max_err2, max_hyp, iters, ctypes.byref(n), iptr(r),
+                                               iptr(q), _u8ptr(inl), dptr(F), ctypes.byref(best), ctypes.byref(status)))
+        n = n.value
+        return r[:n], q[:n], inl[:n], F, int(best.value), int(status.value)
 
     def pairs_dev(self, ref, que, d_count, d_r_idx, d_q_idx, d_ref_pts, d_que_pts, stream=0):
         check(self._lib.sfm_track_pairs_dev(self._h, int(ref), int(que), _vp(d_count), _vp(d_r_idx), _vp(d_q_idx), _vp(d_ref_pts),

@@ -352,6 +352,52 @@ class HipEpipolarMixin:
     def extract_essential_mat(self, left_intrinsic_mat, right_intrinsic_mat):
         self.esse_mat = native.essential_from_fundamental(self.fund_mat, left_intrinsic_mat, right_intrinsic_mat)
 
+    @staticmethod
+    def _twoview_sets(list_of_matched_pairs):
+        """set_ptr, left (2, M), right (2, M) of a list of [ref_pts, que_pts] pairs ((2 or 3, n) pixel coordinates each)."""
+        lefts = [np.asarray(mp[0], dtype=np.float64)[0:2, :] for mp in list_of_matched_pairs]
+        rights = [np.asarray(mp[1], dtype=np.float64)[0:2, :] for mp in list_of_matched_pairs]
+        for l, r in zip(lefts, rights):
+            if l.shape != r.shape:
+                raise ValueError("matched pairs of different sizes : {} - {}".format(l.shape[1], r.shape[1]))
+        set_ptr = np.concatenate(([0], np.cumsum([l.shape[1] for l in lefts]))).astype(np.int32)
+        left = np.ascontiguousarray(np.hstack(lefts)) if lefts else np.zeros((2, 0))
+        right = np.ascontiguousarray(np.hstack(rights)) if rights else np.zeros((2, 0))
+        return set_ptr, left, right
+
+    def verify_matches(self, list_of_matched_pairs, max_sampson_px=2.0, max_hyp=128, iteration=2):
+        """Geometric verification of several sets of matches in ONE device call (``native.twoview_ransac``; no reference
+        counterpart): per set the fundamental matrix of its consistent subset under a Sampson distance of
+        ``max_sampson_px`` pixels.  Returns one ``(F (3, 3) of Frobenius norm 1, inlier indices (a list), status)`` per set;
+        a set without a model (fewer than nine matches, or no hypothesis with nine inliers) has a zero matrix and no
+        inliers.  ``twoview_last`` keeps the hypotheses, statuses and the summary of the call."""
+        if not float(max_sampson_px) >= 0.0:
+            raise ValueError("max_sampson_px must be >= 0, got {!r}".format(max_sampson_px))
+        set_ptr, left, right = self._twoview_sets(list_of_matched_pairs)
+        F, inlier, _n, best, status, summary = native.twoview_ransac(set_ptr, left, right, float(max_sampson_px) ** 2, max_hyp,
+                                                                     iteration)
+        self.twoview_last = {"hypothesis": best.tolist(), "status": status.tolist(), "summary": summary}
+        return [(F[s], np.flatnonzero(inlier[set_ptr[s]:set_ptr[s + 1]]).tolist(), int(status[s]))
+                for s in range(set_ptr.shape[0] - 1)]
+
+    def determine_fundamental_mat_robust(self, matched_pairs, max_sampson_px=2.0, max_hyp=128, iteration=2):
+        """``determine_fundamental_mat`` by the robust two-view geometry (``native.twoview_ransac``; no reference
+        counterpart): stratified eight-point hypotheses without a random number, scored by the Sampson distance in pixels,
+        the winner refitted over its inliers.  Sets ``self.fund_mat`` to the matrix divided by ``F[2][2]``, as
+        ``extract_essential_mat`` expects, and returns the inlier indices (a list); without a model ``fund_mat`` is left
+        as it was and the list is empty.  ``twoview_last`` keeps hypothesis, status and the summary."""
+        rows = np.asarray(matched_pairs[0]).shape[1]
+        if rows < 8:
+            logging.error('%s : number of matched pairs needs equal or more than eight')
+            raise ValueError("Insufficient matched pairs : {}".format(rows))
+        (F, inliers, status), = self.verify_matches([matched_pairs], max_sampson_px, max_hyp, iteration)
+        last = self.twoview_last
+        self.twoview_last = {"hypothesis": last["hypothesis"][0], "status": status, "summary": last["summary"]}
+        if status & (native.TWOVIEW_TOO_FEW | native.TWOVIEW_NO_MODEL):
+            return []
+        self.fund_mat = F / F[2][2]
+        return inliers
+
 
 class HipEpipolarProcessor(HipEpipolarMixin):
     """Standalone EpipolarProcessor (constructor of epipolar_processor.py:13-20)."""
@@ -1515,6 +1561,27 @@ class HipDeviceKeyTracker(HipKeyTrackerMixin):
 
 
 # ------------------------------------------------------------------------------------------------
+def verify_pairs(tracker, ref_idx, que_idx, max_sampson_px=2.0, max_hyp=128, iteration=2):
+    """The pairs ``tracker.generate_matched_pairs(ref_idx, que_idx)`` returns (``tracker``: a ``HipDeviceKeyTracker``),
+    verified geometrically without leaving the device (``TrackStore.verify_pairs``: the pairs are gathered into device
+    buffers and handed to the robust two-view geometry on the same stream; no coordinate comes down).  Returns
+    ``r_idx (1, n), q_idx (1, n), inlier (n,) bool``; ``tracker.twoview_last`` keeps the matrix (Frobenius norm 1),
+    hypothesis and status.  A function of the module, not a method: the tracker's class keeps the reference's public
+    methods and ``kt_release`` only."""
+    n_views = len(tracker.track_list)
+    if ref_idx < 0 or que_idx < 0 or ref_idx >= n_views or que_idx >= n_views:
+        print('{}:{} - invalid ref_idx {} or invalid que_idx {}'.format(
+            tracker.__class__.__name__, 'verify_pairs', ref_idx, que_idx))
+        return None
+    if not float(max_sampson_px) >= 0.0:
+        raise ValueError("max_sampson_px must be >= 0, got {!r}".format(max_sampson_px))
+    r_idx, q_idx, inlier, fund, best, status = tracker._store.verify_pairs(ref_idx, que_idx, float(max_sampson_px) ** 2, max_hyp,
+                                                                           iteration)
+    tracker.twoview_last = {"fund_mat": fund, "hypothesis": best, "status": status}
+    num = r_idx.shape[0]
+    return r_idx.reshape(1, num).astype(int), q_idx.reshape(1, num).astype(int), inlier.astype(bool)
+
+
 class HipKeyPoint:
     """The ``cv2.KeyPoint`` fields the reference reads and writes (view_processor.py:100-101, 178-180)."""
     __slots__ = ("pt", "size", "angle", "response", "octave", "class_id")
