@@ -6,7 +6,11 @@ decision is taken at ``max_err2 (1 -+ 1e-6)`` as well as at ``max_err2``: a set 
 winner, number of refit rounds that stood and final mask.  ``d_G`` is the largest difference between the six final matrices in
 the G measure: ``G = S F S / |S F S|`` with ``S = diag(c, c, 1)``, ``c`` the RMS coordinate magnitude of the set's matches in
 both images, the sign fixed as the rule fixes it.  (Entry-wise on F itself the quadratic-term entries, of order 1 / c^2,
-would go unchecked.)"""
+would go unchecked.)
+
+The scenes: ``CASES`` (the prototype scenes, every set size and max_hyp on one geometry, the degenerate sets) and, from
+``two_views``, ``GEOMETRY_CASES`` (eight families of geometry at three thresholds and 0, 1, 2 and 5 refit rounds) and
+``PATH_CASES`` (ties at the largest count, 259 sets in one call, non-finite coordinates)."""
 import functools
 from types import SimpleNamespace
 
@@ -144,16 +148,29 @@ def _hypotheses(l, r, H, route):
     return idx, F, ok & ok2, sampson(F, l, r)
 
 
+def _counts(hyp, max_err2):
+    """Step 6: the inlier count of every hypothesis, -1 where it is not valid (its matrix, or the sample gate)."""
+    idx, _Fh, valid, d2 = hyp
+    ok = inliers(d2, max_err2)
+    valid = valid & np.take_along_axis(ok, idx, axis=1).all(axis=1)               # the sample gate
+    return np.where(valid, ok.sum(axis=1), -1)
+
+
+def hypothesis_counts(l, r, max_err2, max_hyp, route=0):
+    """What the pick sees of one set of n >= 9 matches: (H,) counts, -1 for a hypothesis that is not valid."""
+    H = hypothesis_count(l.shape[1], max_hyp)
+    hyp = _hypotheses(l, r, H, route)
+    return np.full(H, -1) if hyp is None else _counts(hyp, max_err2)
+
+
 def _run(l, r, hyp, max_err2, iters, route):
     """Steps 6 to 9 of one set at one threshold: (status, best_hyp, stood, mask, F)."""
     n = l.shape[1]
     none = (NO_MODEL, -1, 0, np.zeros(n, dtype=bool), np.zeros((3, 3)))
     if hyp is None:
         return none
-    idx, Fh, valid, d2 = hyp
-    ok = inliers(d2, max_err2)
-    valid = valid & np.take_along_axis(ok, idx, axis=1).all(axis=1)               # the sample gate
-    counts = np.where(valid, ok.sum(axis=1), -1)
+    Fh = hyp[1]
+    counts = _counts(hyp, max_err2)
     best = int(np.argmax(counts))                                                 # the first of the largest counts
     if counts[best] < MIN_COUNT:
         return none
@@ -186,19 +203,26 @@ def g_difference(Fa, Fb, c):
     return float(np.max(np.abs(g_measure(Fa, c) - g_measure(Fb, c))))
 
 
-def solve_set(l, r, max_err2, max_hyp, iters):
-    """One set: the decisions of the run at (route 0, max_err2), the settled flag and d_G over the six runs."""
+def both_routes(l, r, max_hyp):
+    """The hypotheses of one set of n >= 9 matches by both routes: they depend on neither max_err2 nor iters."""
+    H = hypothesis_count(l.shape[1], max_hyp)
+    return tuple(_hypotheses(l, r, H, route) for route in (0, 1))
+
+
+def solve_set(l, r, max_err2, max_hyp, iters, hyps=None):
+    """One set: the decisions of the run at (route 0, max_err2), the settled flag and d_G over the six runs.  hyps: what
+    both_routes(l, r, max_hyp) returned, where a caller keeps it across thresholds and rounds."""
     n = l.shape[1]
     c = rms_coordinate(l, r)
     if n < MIN_MATCHES:
         return SimpleNamespace(status=TOO_FEW, best_hyp=-1, stood=0, mask=np.zeros(n, dtype=bool), F=np.zeros((3, 3)),
                                settled=True, d_G=0.0, c=c)
-    H = hypothesis_count(n, max_hyp)
+    if hyps is None:
+        hyps = both_routes(l, r, max_hyp)
     runs = []
     for route in (0, 1):
-        hyp = _hypotheses(l, r, H, route)
         for f in (1.0, 1.0 - 1e-6, 1.0 + 1e-6):
-            runs.append(_run(l, r, hyp, max_err2 * f, iters, route))
+            runs.append(_run(l, r, hyps[route], max_err2 * f, iters, route))
     first = runs[0]
     settled = all(o[0] == first[0] and o[1] == first[1] and o[2] == first[2] and np.array_equal(o[3], first[3]) for o in runs[1:])
     d_G = max(g_difference(first[4], o[4], c) for o in runs[1:])
@@ -206,8 +230,9 @@ def solve_set(l, r, max_err2, max_hyp, iters):
                            d_G=d_G, c=c)
 
 
-def reference(set_ptr, left, right, max_err2=MAX_ERR2, max_hyp=0, iters=ITERS):
-    """The whole call: arrays as native.twoview_ransac returns them, plus settled (S,), d_G (S,), stood (S,), c (S,)."""
+def reference(set_ptr, left, right, max_err2=MAX_ERR2, max_hyp=0, iters=ITERS, hyps=None):
+    """The whole call: arrays as native.twoview_ransac returns them, plus settled (S,), d_G (S,), stood (S,), c (S,).
+    hyps: per set what both_routes returned (None for a set below nine matches), or None to compute them here."""
     set_ptr = np.asarray(set_ptr, dtype=np.int64)
     S, M = set_ptr.shape[0] - 1, left.shape[1]
     out = SimpleNamespace(F=np.zeros((S, 3, 3)), inlier=np.zeros(M, dtype=np.uint8), n_inliers=np.zeros(S, dtype=np.int32),
@@ -216,7 +241,7 @@ def reference(set_ptr, left, right, max_err2=MAX_ERR2, max_hyp=0, iters=ITERS):
                           stood=np.zeros(S, dtype=np.int32), c=np.zeros(S))
     for s in range(S):
         lo, hi = int(set_ptr[s]), int(set_ptr[s + 1])
-        o = solve_set(left[:, lo:hi], right[:, lo:hi], max_err2, max_hyp, iters)
+        o = solve_set(left[:, lo:hi], right[:, lo:hi], max_err2, max_hyp, iters, None if hyps is None else hyps[s])
         out.F[s], out.inlier[lo:hi], out.n_inliers[s], out.best_hyp[s], out.status[s] = o.F, o.mask, o.mask.sum(), o.best_hyp, o.status
         out.settled[s], out.d_G[s], out.stood[s], out.c[s] = o.settled, o.d_G, o.stood, o.c
         if o.status & TOO_FEW:
@@ -257,6 +282,40 @@ def matches(n, frac, seed, noise=0.5):
     return l, r, bad
 
 
+def _rot_z(a):
+    return np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+
+
+def two_views(n, seed, K=K, R=None, t=(-1.0, 0.1, 0.2), depth=(4.0, 9.0), noise=0.5, plane=0.0, second=None, second_share=0.0,
+              offset=0.0, frac=0.0, displace=(30.0, 120.0)):
+    """n matches of two views with intrinsics K under the motion x' = R x + t (R: rot_y(0.15) if None), the points
+    `depth[0]` to `depth[1]` units deep and +-2 units wide, `noise` px on both keys.  A share `plane` of the points lies on
+    the plane z = mid-depth + 0.1 x + 0.05 y; a share `second_share` of the matches follows the motion second = (R2, t2)
+    instead; `offset` is added to every coordinate of both images; a share `frac` of the right keys is displaced by
+    `displace[0]` to `displace[1]` px.  The shares are drawn per match, so every stratum of the sampler holds its part of
+    each.  Returns left (2, n), right (2, n), displaced (n,) bool."""
+    rng = np.random.default_rng(seed)
+    R = _rot_y(0.15) if R is None else np.asarray(R, dtype=np.float64)
+    t = np.asarray(t, dtype=np.float64).reshape(3, 1)
+    X = np.vstack((rng.uniform(-2, 2, (2, n)), rng.uniform(depth[0], depth[1], (1, n))))
+    on_plane = rng.random(n) < plane
+    X[2] = np.where(on_plane, 0.5 * (depth[0] + depth[1]) + 0.1 * X[0] + 0.05 * X[1], X[2])
+    l = K @ X
+    l = l[:2] / l[2]
+    Y = R @ X + t
+    moved = rng.random(n) < second_share
+    if second is not None:
+        Y = np.where(moved, np.asarray(second[0], dtype=np.float64) @ X + np.asarray(second[1], dtype=np.float64).reshape(3, 1), Y)
+    r = K @ Y
+    r = r[:2] / r[2]
+    l = l + rng.normal(0, noise, l.shape)
+    r = r + rng.normal(0, noise, r.shape)
+    bad = rng.random(n) < frac
+    ang, mag = rng.uniform(0, 2 * np.pi, n), rng.uniform(displace[0], displace[1], n)
+    r = r + bad * np.vstack((np.cos(ang), np.sin(ang))) * mag
+    return l + offset, r + offset, bad
+
+
 def _batch(parts):
     counts = [p[0].shape[1] for p in parts]
     return SimpleNamespace(set_ptr=np.concatenate(([0], np.cumsum(counts))).astype(np.int32),
@@ -289,8 +348,74 @@ def degenerate_parts():
     return [(l, r, np.zeros(n, dtype=bool)), same, (ln, rn, bad)]
 
 
+# ---- the geometry families: what two_views is given besides n and the seed; every one as sets of FAMILY_COUNTS matches -----
+K_LARGE = np.array([[3200.0, 0, 2000], [0, 3200.0, 1500], [0, 0, 1]])
+FAMILIES = {
+    "half_displaced": dict(frac=0.5),
+    "forward": dict(R=_rot_z(0.05), t=(0.03, -0.02, -1.0), frac=0.1),          # both epipoles inside the image
+    "sideways": dict(R=np.eye(3), t=(-1.0, 0.0, 0.0), frac=0.1),               # both epipoles at infinity
+    "large_image": dict(K=K_LARGE, noise=2.0, frac=0.1, displace=(120.0, 480.0)),
+    "offset": dict(offset=1e4, frac=0.1),
+    "plane_dominant": dict(plane=0.8, frac=0.1),
+    "two_motions": dict(second=(_rot_y(-0.1) @ _rot_z(0.2), (0.6, -0.8, 0.3)), second_share=0.4, frac=0.05),
+    "rolled": dict(R=_rot_z(0.6) @ _rot_y(0.15), frac=0.2),
+}
+FAMILY_COUNTS = (40, 130, 300)        # below and above one slice of 64, above one wave-row of 256
+# One seed per count, chosen on the CPU so that the conditions of tests/test_twoview_ransac_host.py hold of the reference (every
+# set settled at every setting, KEPT_HYPOTHESIS in every family, every number of standing rounds from 0 to 5).
+FAMILY_SEEDS = {"half_displaced": (6, 2, 1), "forward": (1, 1, 6), "sideways": (5, 4, 7), "large_image": (7, 7, 5),
+                "offset": (7, 8, 7), "plane_dominant": (4, 4, 7), "two_motions": (7, 5, 1), "rolled": (1, 5, 1)}
+FAMILY_ERR2 = (1.0, 4.0, 16.0)        # times 16 for large_image: its pixels are a quarter the size
+FAMILY_ITERS = (0, 1, 2, 5)
+EVERYONE = 1e12                       # a threshold under which every finite match is every valid hypothesis' inlier
+TIES_HYP = 1000
+TIES_SEEDS = (3, 2)
+MANY_SEED = 2
+MANY_SIZES = (0, 8, 9, 12, 33, 70)
+MANY_CYCLES = 43                      # 43 x 6 + 1 = 259 sets
+
+
+def family_err2(name, max_err2):
+    return 16.0 * max_err2 if name == "large_image" and max_err2 != EVERYONE else max_err2
+
+
+def family_part(name, n, seed):
+    return two_views(n, seed, **FAMILIES[name])
+
+
+def ties_parts(seeds=(0, 0)):
+    """Noise-free matches, 30 % displaced: every hypothesis whose eight matches are clean ties at the same count."""
+    return [two_views(n, seed, noise=0.0, frac=0.3) for n, seed in zip((200, 203), seeds)]
+
+
+def many_sets_parts(seed=0):
+    """MANY_CYCLES rounds of sets of 0, 8, 9, 12, 33 and 70 matches and a last set of 8: the call begins and ends with a set
+    below nine matches, and every round has two of them side by side."""
+    sizes = MANY_SIZES * MANY_CYCLES + (8,)
+    return [two_views(n, 100000 * seed + k, frac=0.1) for k, n in enumerate(sizes)]
+
+
+def nonfinite_parts():
+    """60 clean matches with one +inf coordinate, and 1 100 whose only NaN is match 1 050: in the second score block."""
+    l0, r0, bad0 = two_views(60, 5)
+    l0 = l0.copy()
+    l0[0, 31] = np.inf
+    l1, r1, bad1 = two_views(1100, 6)
+    r1 = r1.copy()
+    r1[0, 1050] = np.nan
+    return [(l0, r0, bad0), (l1, r1, bad1)]
+
+
 @functools.lru_cache(maxsize=None)
 def scene(name):
+    if name in FAMILIES:
+        return _batch([family_part(name, n, seed) for n, seed in zip(FAMILY_COUNTS, FAMILY_SEEDS[name])])
+    if name == "ties":
+        return _batch(ties_parts(TIES_SEEDS))
+    if name == "many_sets":
+        return _batch(many_sets_parts(MANY_SEED))
+    if name == "nonfinite":
+        return _batch(nonfinite_parts())
     if name in PROTO:
         return _batch([matches(n, PROTO[name], 1000 + n + int(100 * PROTO[name])) for n in PROTO_COUNTS])
     if name == "paths":
@@ -300,11 +425,35 @@ def scene(name):
     raise KeyError(name)
 
 
+def set_of(sc, s):
+    lo, hi = int(sc.set_ptr[s]), int(sc.set_ptr[s + 1])
+    return sc.left[:, lo:hi], sc.right[:, lo:hi]
+
+
 @functools.lru_cache(maxsize=None)
-def scene_and_reference(name, max_hyp=128, iters=ITERS):
-    """The scene and its reference, computed once per (scene, max_hyp, iters) and shared; treat both as read-only."""
+def _scene_hypotheses(name, max_hyp):
+    """Per set of the scene what both_routes returns: shared by every (max_err2, iters) the scene is referenced at."""
     sc = scene(name)
-    return sc, reference(sc.set_ptr, sc.left, sc.right, MAX_ERR2, max_hyp, iters)
+    return [both_routes(*set_of(sc, s), max_hyp) if sc.counts[s] >= MIN_MATCHES else None for s in range(sc.counts.size)]
+
+
+@functools.lru_cache(maxsize=None)
+def scene_and_reference(name, max_hyp=128, iters=ITERS, max_err2=MAX_ERR2):
+    """The scene and its reference, computed once per (scene, max_hyp, iters, max_err2) and shared; treat both as read-only."""
+    sc = scene(name)
+    hyps = _scene_hypotheses(name, max_hyp) if name in FAMILIES else None     # the scenes referenced at many settings
+    return sc, reference(sc.set_ptr, sc.left, sc.right, max_err2, max_hyp, iters, hyps)
 
 
 CASES = [(name, 128) for name in PROTO] + [("paths", h) for h in PATHS_HYP] + [("degenerate", 128)]
+
+# (scene, max_err2, max_hyp, iters): every family at every threshold and number of rounds, and once at EVERYONE
+GEOMETRY_CASES = [(name, family_err2(name, e), 128, it) for name in FAMILIES for e in FAMILY_ERR2 for it in FAMILY_ITERS] + \
+                 [(name, EVERYONE, 128, ITERS) for name in FAMILIES]
+# the further scenes, in the same form
+PATH_CASES = [("ties", MAX_ERR2, TIES_HYP, ITERS), ("many_sets", MAX_ERR2, 128, ITERS), ("nonfinite", MAX_ERR2, 128, ITERS)]
+
+
+def case_reference(case):
+    name, max_err2, max_hyp, iters = case
+    return scene_and_reference(name, max_hyp, iters, max_err2)

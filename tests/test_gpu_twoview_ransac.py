@@ -12,38 +12,11 @@ import numpy as np
 import pytest
 
 import _twoview_ransac_reference as tv
+from _twoview_checks import check_against, run, same_bits, same_sets as _same_sets, subset as _subset
 
 pytestmark = pytest.mark.gpu
 
 _WORST = {"d_G": 0.0, "device": 0.0}
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def run(hip, sc, max_hyp=128, iters=tv.ITERS):
-    return hip.twoview_ransac(sc.set_ptr, sc.left, sc.right, tv.MAX_ERR2, max_hyp, iters)
-
-
-def check_against(ref, F, inlier, n_in, best, status, summary, where=""):
-    """Exact decisions, matrices at the per-set bound, sets without a model as nine zeros."""
-    assert ref.settled.all()
-    assert np.array_equal(status, ref.status), where
-    assert np.array_equal(best, ref.best_hyp), where
-    assert np.array_equal(n_in, ref.n_inliers), where
-    assert np.array_equal(inlier, ref.inlier), where
-    assert np.array_equal(summary, ref.summary), where
-    solved = ref.best_hyp >= 0
-    for s in np.flatnonzero(solved):
-        diff = tv.g_difference(F[s], ref.F[s], ref.c[s])
-        if ref.d_G[s] < 1e-3:                                   # (the noise-free plane: any [e]x H is a solution)
-            _WORST["d_G"] = max(_WORST["d_G"], ref.d_G[s]); _WORST["device"] = max(_WORST["device"], diff)
-        print(where, "set", s, "d_G %.3e device %.3e" % (ref.d_G[s], diff))
-        assert diff <= max(1e-9, 100.0 * ref.d_G[s]), (where, s, diff, ref.d_G[s])
-        assert abs(np.linalg.norm(F[s]) - 1.0) < 1e-14 and F[s].flat[np.argmax(np.abs(F[s]))] > 0
-    assert not F[~solved].any() and same_bits(F[~solved], np.zeros_like(F[~solved])), where
 
 
 # ---- parity with the reference: prototype scenes, the paths scene at every max_hyp, the degenerate sets ------------------
@@ -51,7 +24,7 @@ def check_against(ref, F, inlier, n_in, best, status, summary, where=""):
 def test_parity_with_the_reference(hip, name, max_hyp):
     sc, ref = tv.scene_and_reference(name, max_hyp)
     got = run(hip, sc, max_hyp)
-    check_against(ref, *got, where="%s/%d" % (name, max_hyp))
+    check_against(ref, *got, where="%s/%d" % (name, max_hyp), worst=_WORST)
     print("worst d_G %.3e, worst device difference %.3e so far" % (_WORST["d_G"], _WORST["device"]))
 
 
@@ -74,7 +47,7 @@ def test_degenerate_sets_bit_for_bit(hip):
 def test_no_refit_rounds(hip):
     sc, ref = tv.scene_and_reference("paths", 128, 0)
     got = run(hip, sc, 128, 0)
-    check_against(ref, *got, where="paths/128 iters 0")
+    check_against(ref, *got, where="paths/128 iters 0", worst=_WORST)
     assert not (got[4] & hip.TWOVIEW_KEPT_HYPOTHESIS).any()
     full = run(hip, sc, 128)
     assert np.array_equal(full[3], got[3])                    # the winner does not depend on the refit
@@ -82,23 +55,6 @@ def test_no_refit_rounds(hip):
 
 
 # ---- a set's bits depend on its own matches and the options only --------------------------------------------------------
-def _subset(sc, sets):
-    parts = [(sc.left[:, sc.set_ptr[s]:sc.set_ptr[s + 1]], sc.right[:, sc.set_ptr[s]:sc.set_ptr[s + 1]]) for s in sets]
-    counts = [p[0].shape[1] for p in parts]
-    return tv.SimpleNamespace(set_ptr=np.concatenate(([0], np.cumsum(counts))).astype(np.int32),
-                              left=np.ascontiguousarray(np.hstack([p[0] for p in parts])),
-                              right=np.ascontiguousarray(np.hstack([p[1] for p in parts])))
-
-
-def _same_sets(hip, sc, whole, sets, max_hyp, what):
-    sub = _subset(sc, sets)
-    F, inlier, n_in, best, status, _summary = run(hip, sub, max_hyp)
-    for k, s in enumerate(sets):
-        assert same_bits(F[k], whole[0][s]), (what, s)
-        assert same_bits(inlier[sub.set_ptr[k]:sub.set_ptr[k + 1]], whole[1][sc.set_ptr[s]:sc.set_ptr[s + 1]]), (what, s)
-        assert (n_in[k], best[k], status[k]) == (whole[2][s], whole[3][s], whole[4][s]), (what, s)
-
-
 @pytest.mark.parametrize("max_hyp", [65, 128])
 def test_batch_independence_bit_for_bit(hip, max_hyp):
     sc = tv.scene("paths")

@@ -1,7 +1,8 @@
 """Host-side checks of the robust two-view geometry (no GPU): the stratified sampler against the NumPy sampler and Python
 integers, the argument checks, and the NumPy reference of tests/_twoview_ransac_reference.py on the scenes the GPU tests
 use -- it rejects no clean match on the prototype scenes, and EVERY set of every scene any test uses is settled at every
-max_hyp used, so the GPU tests compare decisions exactly and leave nothing out."""
+max_hyp used, so the GPU tests compare decisions exactly and leave nothing out.  For the geometry families and the further
+scenes of tests/test_gpu_twoview_paths.py it also asserts that the reference reaches what those scenes are there for."""
 import numpy as np
 import pytest
 
@@ -101,3 +102,115 @@ def test_the_paths_scene_has_every_count():
     ref = tv.scene_and_reference("paths", 128)[1]
     assert np.array_equal((ref.status & tv.TOO_FEW) != 0, sc.counts < 9)
     assert np.all(ref.best_hyp[sc.counts >= 10] >= 0)            # (the nine matches of set 2 allow few samples: no model)
+
+
+# ---- the geometry families and the further scenes of tests/test_gpu_twoview_paths.py -------------------------------------
+# These conditions hold of the reference alone (the seeds were chosen for them): they keep the GPU tests, which walk the same
+# lists and leave no set out, from passing without having reached what they are there for.
+def _family_cases(name):
+    return [case for case in tv.GEOMETRY_CASES if case[0] == name]
+
+
+@pytest.mark.parametrize("name", list(tv.FAMILIES))
+def test_every_set_of_every_geometry_case_is_settled(name, capsys):
+    sc = tv.scene(name)
+    assert sc.counts.tolist() == list(tv.FAMILY_COUNTS)
+    cases = _family_cases(name)
+    assert len(cases) == len(tv.FAMILY_ERR2) * len(tv.FAMILY_ITERS) + 1
+    assert sorted({c[1] for c in cases}) == sorted([tv.family_err2(name, e) for e in tv.FAMILY_ERR2] + [tv.EVERYONE])
+    worst, statuses, stood = 0.0, np.zeros(8, dtype=int), np.zeros(6, dtype=int)
+    for case in cases:
+        ref = tv.case_reference(case)[1]
+        assert ref.settled.all(), (case, np.flatnonzero(~ref.settled))
+        assert ref.summary[0] + ref.summary[1] + ref.summary[2] == sc.counts.size and ref.summary[4] == ref.inlier.sum()
+        worst = max(worst, ref.d_G.max())
+        statuses += np.bincount(ref.status, minlength=8)
+        stood += np.bincount(ref.stood[ref.best_hyp >= 0], minlength=6)
+    with capsys.disabled():
+        print("\n%s: %d cases of %d sets, 0 unsettled, worst d_G %.3e, statuses 0 / NO_MODEL / KEPT: %d / %d / %d, stood 0..5: %s"
+              % (name, len(cases), sc.counts.size, worst, statuses[0], statuses[tv.NO_MODEL], statuses[tv.KEPT_HYPOTHESIS], stood.tolist()))
+
+
+def test_the_geometry_cases_reach_the_kept_hypothesis_and_every_number_of_rounds():
+    families, kept_iters, stood, rejected_later, kept_beside_no_model = set(), set(), set(), False, False
+    for case in tv.GEOMETRY_CASES:
+        name, _max_err2, _max_hyp, iters = case
+        ref = tv.case_reference(case)[1]
+        kept = (ref.status & tv.KEPT_HYPOTHESIS) != 0
+        assert not (kept & (ref.best_hyp < 0)).any() and np.array_equal(kept, (ref.best_hyp >= 0) & (ref.stood == 0) & (iters > 0))
+        assert ref.summary[3] == kept.sum() and np.all(ref.stood <= iters)
+        if kept.any():
+            families.add(name)
+            kept_iters.add(iters)
+        stood |= set(ref.stood[ref.best_hyp >= 0].tolist())
+        rejected_later |= bool(((ref.stood > 0) & (ref.stood < iters)).any())
+        kept_beside_no_model |= bool(ref.summary[3] > 0 and ref.summary[1] > 0)
+    assert len(families) >= 5, families
+    assert {1, 2, 5} <= kept_iters
+    assert stood == {0, 1, 2, 3, 4, 5}
+    assert rejected_later                 # a round is rejected after an earlier one stood
+    assert kept_beside_no_model           # one call with summary[3] > 0 and summary[1] > 0
+    # what the scenes that came with the feature never reach
+    for name, max_hyp in tv.CASES:
+        ref = tv.scene_and_reference(name, max_hyp)[1]
+        assert not (ref.status & tv.KEPT_HYPOTHESIS).any() and ref.stood.max() <= 2
+
+
+def test_under_the_threshold_of_everyone_the_first_valid_hypothesis_wins():
+    for case in tv.GEOMETRY_CASES:
+        name, max_err2, max_hyp, _iters = case
+        if max_err2 != tv.EVERYONE:
+            continue
+        sc, ref = tv.case_reference(case)
+        assert (ref.best_hyp >= 0).any()
+        for s in range(sc.counts.size):
+            counts = tv.hypothesis_counts(*tv.set_of(sc, s), max_err2, max_hyp)
+            valid = np.flatnonzero(counts >= 0)
+            if ref.best_hyp[s] >= 0:
+                assert ref.n_inliers[s] == sc.counts[s] and ref.best_hyp[s] == valid[0] and np.all(counts[valid] == sc.counts[s])
+            else:
+                assert valid.size == 0
+
+
+def test_the_ties_scene_has_ties_a_pick_can_get_wrong(capsys):
+    case = tv.PATH_CASES[0]
+    sc, ref = tv.case_reference(case)
+    assert case[0] == "ties" and sc.counts.size == 2 and ref.settled.all() and not ref.status.any()
+    for s in range(2):
+        counts = tv.hypothesis_counts(*tv.set_of(sc, s), case[1], case[2])
+        tied = np.flatnonzero(counts == counts.max())
+        with capsys.disabled():
+            print("\nties set %d: %d matches, %d hypotheses at the largest count %d, the first of them %s"
+                  % (s, sc.counts[s], tied.size, counts.max(), tied[:8].tolist()))
+        assert tied.size >= 3 and tied[0] != 0 and ref.best_hyp[s] == tied[0]
+        assert (tied >= 64).any()
+        # a pick that prefers the lower lane over the lower h takes another one: a later tied h sits in a lane below the first's
+        # (so there are h1 < h2 among the tied with h2 % 64 < h1 % 64)
+        assert (tied[1:] % 64 < tied[0] % 64).any()
+        for route in (0, 1):                                    # and the ties are no accident of one null-vector route
+            other = tv.hypothesis_counts(*tv.set_of(sc, s), case[1], case[2], route)
+            assert np.array_equal(np.flatnonzero(other == other.max()), tied)
+
+
+def test_the_many_sets_scene_is_what_it_says():
+    case = tv.PATH_CASES[1]
+    sc, ref = tv.case_reference(case)
+    n_sets = sc.counts.size
+    assert case[0] == "many_sets" and n_sets >= 257 and set(sc.counts.tolist()) == set(tv.MANY_SIZES)
+    small = sc.counts < tv.MIN_MATCHES
+    assert small[0] and small[-1] and (small[1:-1][:-1] & small[1:-1][1:]).any()
+    assert ref.settled.all()
+    assert ref.summary[0] + ref.summary[1] + ref.summary[2] == n_sets and np.all(ref.summary[:3] > 0)
+    assert ref.summary[2] == small.sum() and ref.summary[3] > 0
+
+
+def test_the_nonfinite_scene_is_what_it_says():
+    case = tv.PATH_CASES[2]
+    sc, ref = tv.case_reference(case)
+    assert case[0] == "nonfinite" and sc.counts.tolist() == [60, 1100]
+    both = np.hstack((sc.left, sc.right))
+    assert np.flatnonzero(~np.isfinite(sc.left[0])).tolist() == [31] and sc.left[0, 31] == np.inf and np.isfinite(sc.left[1]).all()
+    assert np.flatnonzero(~np.isfinite(sc.right[0])).tolist() == [60 + 1050] and np.isnan(sc.right[0, 60 + 1050])
+    assert np.isfinite(sc.right[1]).all() and (~np.isfinite(both)).sum() == 2
+    assert ref.settled.all() and ref.status.tolist() == [tv.NO_MODEL, tv.NO_MODEL] and ref.best_hyp.tolist() == [-1, -1]
+    assert not ref.F.any() and not ref.inlier.any() and ref.summary.tolist() == [0, 2, 0, 0, 0, 0]
