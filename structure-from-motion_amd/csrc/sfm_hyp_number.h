@@ -1,12 +1,10 @@
-// sfm_hyp_number.h -- the numbering of the hypotheses of the two robust operations (host and device): the pairs of a track
+// sfm_hyp_number.h -- the numbering of the hypotheses of the robust operations (host and device): the pairs of a track
 // (sfm_tri_ransac.hip) and the triples of a camera's observations (sfm_resect.hip), both in lexicographic order, all of
 // them up to max_hyp, else evenly spaced.  No random number anywhere.  The floating-point estimates below only seed integer
 // searches that end at the exact answer, so the results do not depend on how the including file contracts them.
 // The eight-match samples of the robust two-view geometry (sfm_twoview.hip) are drawn by a stratified integer sampler.
-// Below the numbering, what else the three share: the six summary counters and the host frame of their entry points.
 #pragma once
 
-#include <algorithm>
 #include <cmath>
 
 #include "sfm_common.h"
@@ -76,62 +74,5 @@ __host__ __device__ inline int twoview_sample_index(int n, int h, int k) {
   const long long lo = (long long)k * n / 8, hi = (long long)(k + 1) * n / 8;
   return (int)(lo + (long long)(splitmix64_mix(8ULL * (unsigned long long)h + (unsigned long long)k) % (unsigned long long)(hi - lo)));
 }
-
-// ---- the summary: 0 solved | 1 no model | 2 too few | 3 kept the hypothesis | 4 inliers | 5 outliers of the solved ----
-// One point or camera of n observations, nin of them inliers of what stands (too_few, kept_hyp: its status bits).  A held
-// camera (resection only) adds its inliers to slot 4 and is counted in none of the slots 0 .. 3.
-__device__ __forceinline__ void robust_summary_add(unsigned long long* summary, bool solved, bool held, int too_few, int kept_hyp,
-                                                   int n, int nin) {
-  if (solved) {
-    atomicAdd(&summary[0], 1ULL);
-    if (kept_hyp) atomicAdd(&summary[3], 1ULL);
-    if (nin) atomicAdd(&summary[4], (unsigned long long)nin);
-    if (n - nin) atomicAdd(&summary[5], (unsigned long long)(n - nin));
-  } else if (held) {
-    if (nin) atomicAdd(&summary[4], (unsigned long long)nin);
-  } else {
-    atomicAdd(&summary[1 + (too_few != 0)], 1ULL);
-  }
-}
-
-// ---- the host frame ----
-inline int robust_check_args(const char* who, double max_err2, int max_hyp, double lambda, int iters) {
-  if (!(max_err2 >= 0.0)) { set_error("%s: max_err2 = %g must be >= 0", who, max_err2); return SFM_E_SHAPE; }
-  if (max_hyp < 0 || max_hyp > kHypMax) { set_error("%s: max_hyp = %d must be in 1 .. %d (0 = %d)", who, max_hyp, kHypMax, kHypDefault); return SFM_E_SHAPE; }
-  if (iters < 0) { set_error("%s: iters = %d must be >= 0", who, iters); return SFM_E_SHAPE; }
-  if (!(lambda >= 0.0)) { set_error("%s: lambda = %g must be >= 0", who, lambda); return SFM_E_SHAPE; }
-  return SFM_OK;
-}
-
-inline void robust_summary_clear(int64_t* summary) { if (summary) std::fill(summary, summary + 6, (int64_t)0); }
-
-// The five optional outputs as device pointers, any of them null: [M], [n] per point or camera, [6].  `into` hands them
-// to the kernel arguments of either operation (the members carry these names there); the counters stay below 2^63, so
-// the kernels' unsigned words are the caller's int64_t as they are.
-struct RobustPtrs {
-  unsigned char* obs_inlier;
-  int *n_inliers, *best_hyp, *status;
-  int64_t* summary;
-  template <class Args>
-  void into(Args& a) const {
-    a.obs_inlier = obs_inlier; a.n_inliers = n_inliers; a.best_hyp = best_hyp; a.status = status;
-    a.summary = reinterpret_cast<unsigned long long*>(summary);
-  }
-};
-
-// ... and as a host-pointer entry point keeps them: device buffers for those the caller asked for, and their download.
-struct RobustOut {
-  HostOut<unsigned char> inlier;
-  HostOut<int> count, best, status;
-  HostOut<int64_t> summary;
-  int want(size_t m, size_t n, unsigned char* obs_inlier, int* n_inliers, int* best_hyp, int* st, int64_t* sum, hipStream_t s) {
-    SFM_TRY(inlier.want(obs_inlier, m, s)); SFM_TRY(count.want(n_inliers, n, s)); SFM_TRY(best.want(best_hyp, n, s));
-    SFM_TRY(status.want(st, n, s)); return summary.want(sum, 6, s);
-  }
-  RobustPtrs dev() const { return {inlier.dev(), count.dev(), best.dev(), status.dev(), summary.dev()}; }
-  int fetch(hipStream_t s) const {
-    SFM_TRY(inlier.fetch(s)); SFM_TRY(count.fetch(s)); SFM_TRY(best.fetch(s)); SFM_TRY(status.fetch(s)); return summary.fetch(s);
-  }
-};
 
 }  // namespace sfm

@@ -19,14 +19,16 @@
 // camera-major list) through CamObsView.  No floating-point value is accumulated with an atomic; the counts are integers;
 // the refit's 36 sums are formed per slice of 64 consecutive observations and added in slice order: a camera's bits depend
 // on its own observations, their points and the options only.
+// Shared with the robust two-view geometry, in sfm_robust.h: the plan of the hypotheses (HypPlan, hyp_owner), the batch
+// loop of `score` (robust_score_block), the tie rule of `pick` (wave_arg_best), the block reductions of `refit` and `judge`
+// (block_count, slice_totals, block_sum_int), the summary and the host frame.
 #include <climits>
 #include <cmath>
-#include <vector>
 
 #include "sfm_ba.h"
 #include "sfm_cam_fit.h"
-#include "sfm_hyp_number.h"
 #include "sfm_obs_test.h"      // contraction is off from here on
+#include "sfm_robust.h"
 
 namespace sfm {
 
@@ -174,12 +176,7 @@ __device__ __forceinline__ void rs_swap_if(bool sw, double& a, double& b) {
 __global__ __launch_bounds__(kRsThreads) void resect_hyp_kernel(RsArgs a, int n_hyp) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= n_hyp) return;
-  int lo = 0, hi = a.w.V;                                  // the camera whose hypotheses hold g: hyp_off[lo] <= g < hyp_off[lo + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (a.hyp_off[mid] <= g) lo = mid; else hi = mid;
-  }
-  const int cam = lo, h = g - a.hyp_off[cam];
+  const int cam = hyp_owner(a.hyp_off, a.w.V, g), h = g - a.hyp_off[cam];
   const int base = a.w.ptr[cam], n = a.w.ptr[cam + 1] - base;
   const long long T = triple_count(n);
   int idx[3];
@@ -285,26 +282,9 @@ __global__ __launch_bounds__(kRsThreads) void resect_score_kernel(RsArgs a) {
     cam_obs_load(a.w, cam, base + (i < n ? i : n - 1), ob[k], &sc[k]);
     if (!(i < n)) sc[k] = __builtin_nan("");
   }
-  for (int hb = 0; hb < H; hb += kRsBatch) {
-    const int nb = min(kRsBatch, H - hb);
-    const double* src = a.poses + (size_t)(h0 + hb) * 4 * kRsPose;
-    for (int i = tid; i < nb * 4 * kRsPose; i += kRsThreads) pose[i] = src[i];
-    if (tid < nb) okb[tid] = a.pose_ok[h0 + hb + tid];
-    __syncthreads();
-    for (int hh = 0; hh < nb; ++hh) {
-      const int bits = okb[hh];                            // the same for the whole workgroup: the branches are uniform
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (!(bits >> r & 1)) continue;
-        const double* m = pose + (hh * 4 + r) * kRsPose;   // every lane reads the same address: a broadcast
-        int cnt = 0;
-#pragma unroll
-        for (int k = 0; k < kMoPerLane; ++k) cnt += __popcll(__ballot(rs_inlier_pose(m, m + 9, ob[k], sc[k], a.max_err2)));
-        if ((tid & 63) == 0 && cnt) atomicAdd(&a.counts[(size_t)(h0 + hb + hh) * 4 + r], cnt);
-      }
-    }
-    __syncthreads();                                       // the batch has been read: the next one may be staged
-  }
+  robust_score_block<kRsThreads, kRsBatch, 4 * kRsPose, 4, kMoPerLane>(
+      a.poses, a.pose_ok, a.counts, h0, H, pose, okb,
+      [&](const double* m, int k) { return rs_inlier_pose(m, m + 9, ob[k], sc[k], a.max_err2); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -314,17 +294,9 @@ __global__ __launch_bounds__(64) void resect_pick_kernel(RsArgs a) {
   const int cam = blockIdx.x, lane = threadIdx.x;
   const int h0 = a.hyp_off[cam], H = a.hyp_off[cam + 1] - h0;
   // index 4 h + r ascends with (h, r): the first of the largest counts wins
-  int best_cnt = -1, best_i = INT_MAX;
-  for (int i = lane; i < 4 * H; i += 64) {
-    if (!(a.pose_ok[h0 + (i >> 2)] >> (i & 3) & 1)) continue;
-    const int cnt = a.counts[(size_t)h0 * 4 + i];
-    if (cnt > best_cnt) { best_cnt = cnt; best_i = i; }
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int oc = __shfl_xor(best_cnt, off, 64), oi = __shfl_xor(best_i, off, 64);
-    if (oc > best_cnt || (oc == best_cnt && oi < best_i)) { best_cnt = oc; best_i = oi; }
-  }
+  int best_cnt, best_i;
+  wave_arg_best(lane, 4 * H, [&](int i) { return a.pose_ok[h0 + (i >> 2)] >> (i & 3) & 1; },
+                [&](int i) { return a.counts[(size_t)h0 * 4 + i]; }, best_cnt, best_i);
   if (lane != 0) return;
   const bool won = best_cnt >= kRsMinCount;
   a.best_hyp[cam] = won ? best_i >> 2 : -1;
@@ -393,15 +365,7 @@ __global__ __launch_bounds__(kRsThreads) void resect_refit_kernel(RsArgs a) {
           }
         }
         mo_fold_row(acc, own, lane, red[tid >> 4]);
-        __syncthreads();
-        if (tid < kMoSums) {
-          double t = blk == 0 ? red[0][tid] : run + red[0][tid];
-#pragma unroll
-          for (int w = 1; w < ROWS; ++w) t += red[w][tid];  // slice order; the rows beyond the camera's slices hold zeros
-          run = t;
-          if (blk == n_blocks - 1) sums[tid] = t;
-        }
-        __syncthreads();                                   // sums complete / red free for the next block
+        slice_totals<kMoSums, ROWS>(red, sums, run, blk == 0, blk == n_blocks - 1, tid);
       }
       // from here on every thread holds the same values: the branches are uniform
       ok = mo_finite_probe(sums, kMoSums) == 0.0 && mo_step(sums, a.lambda, params, c);
@@ -421,7 +385,7 @@ __global__ __launch_bounds__(kRsThreads) void resect_refit_kernel(RsArgs a) {
             mine += rs_inlier_cam(c, ob, scale, a.max_err2);
           }
         }
-        rc += __syncthreads_count(mine & 1) + 2 * __syncthreads_count(mine & 2) + 4 * __syncthreads_count(mine & 4);
+        rc += block_count(mine);
       }
     }
     if (!(ok && rc >= hc)) {
@@ -451,8 +415,6 @@ __global__ __launch_bounds__(kRsThreads) void resect_judge_kernel(RsArgs a) {
   const int flags = a.status[cam];
   const bool solved = !(flags & (SFM_RESECT_HELD | SFM_RESECT_TOO_FEW | SFM_RESECT_NO_MODEL));
   const bool judged = solved || (flags & SFM_RESECT_HELD);
-  if (tid == 0) total = 0;
-  __syncthreads();
   CamPrep c;
   load_cam(c, a.prep + cam);
   int nin = 0;
@@ -465,12 +427,8 @@ __global__ __launch_bounds__(kRsThreads) void resect_judge_kernel(RsArgs a) {
     if (a.obs_inlier) a.obs_inlier[index] = in ? 1 : 0;
     nin += in;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) nin += __shfl_xor(nin, off, 64);
-  if ((tid & 63) == 0 && nin) atomicAdd(&total, nin);
-  __syncthreads();
+  nin = block_sum_int(nin, &total);
   if (tid != 0) return;
-  nin = total;
   if (a.n_inliers) a.n_inliers[cam] = nin;
   robust_summary_add(a.summary, solved, flags & SFM_RESECT_HELD, flags & SFM_RESECT_TOO_FEW, flags & SFM_RESECT_KEPT_HYPOTHESIS, n, nin);
 }
@@ -490,26 +448,18 @@ static int resect_check_counts(const char* who, int V, const int* ptr) {
 }
 
 static int resect_check_views(const char* who, int n_views, const int* view_ptr, long long M) {
-  if (n_views < 0 || M < 0 || M > INT_MAX) { set_error("%s: bad sizes n_views=%d M=%lld", who, n_views, M); return SFM_E_SHAPE; }
-  if (n_views == 0) return SFM_OK;
-  if (view_ptr == nullptr) { set_error("%s: null view_ptr", who); return SFM_E_SHAPE; }
-  if (view_ptr[0] != 0 || view_ptr[n_views] != M) {
-    set_error("%s: view_ptr must start at 0 and end at M = %lld (it runs from %d to %d)", who, M, view_ptr[0], view_ptr[n_views]);
-    return SFM_E_SHAPE;
-  }
-  for (int c = 0; c < n_views; ++c)
-    if (view_ptr[c + 1] < view_ptr[c]) { set_error("%s: view_ptr decreases at view %d", who, c); return SFM_E_SHAPE; }
-  return resect_check_counts(who, n_views, view_ptr);
+  SFM_TRY(robust_check_offsets(who, "view", "view_ptr", n_views, view_ptr, M, false));
+  return n_views ? resect_check_counts(who, n_views, view_ptr) : SFM_OK;
 }
 
 // What a call keeps on the device besides the caller's arrays.
 struct ResectWork {
-  DevBuf<int> hyp_off, best_hyp, win_count, status, counts, prep_status;
-  DevBuf<int2> blocks;
+  HypPlan plan;
+  RobustStandIns stand_in;
+  DevBuf<int> win_count, counts, prep_status;
   DevBuf<double> poses, win_pose, win_cam;
   DevBuf<unsigned char> pose_ok;
   DevBuf<CamPrep> prep;
-  DevBuf<unsigned long long> summary;
 };
 
 // Enqueue the kernels up to the refit on s.  h_ptr / h_mask: the host's copy of the list offsets (checked: no camera beyond
@@ -517,35 +467,21 @@ struct ResectWork {
 static int resect_enqueue(const char* who, RsArgs& a, ResectWork& w, const int* h_ptr, const unsigned char* h_mask, hipStream_t s) {
   const int V = a.w.V;
   if (a.max_hyp == 0) a.max_hyp = kHypDefault;
-  std::vector<int> off((size_t)V + 1, 0);
-  std::vector<int2> blocks;
-  long long total = 0;
-  for (int c = 0; c < V; ++c) {
-    const int n = h_ptr[c + 1] - h_ptr[c];
-    off[c] = (int)total;
-    if (n >= 4 && !(h_mask && h_mask[c] == 0)) {
-      total += hyp_count(triple_count(n), a.max_hyp);
-      for (int b = 0; b < n; b += kRsBlockObs) blocks.push_back(make_int2(c, b));
-    }
-    if (total > INT_MAX / (4 * kRsPose)) { set_error("%s: %lld hypotheses are beyond the workspace", who, total); return SFM_E_SHAPE; }
-  }
-  off[V] = (int)total;
-  const size_t v = (size_t)V, nh = (size_t)total;
-  SFM_TRY(w.hyp_off.upload(off.data(), v + 1, s));
-  SFM_TRY(w.blocks.upload(blocks.data(), blocks.size(), s));
+  SFM_TRY(w.plan.build(who, V, h_ptr, kRsBlockObs, INT_MAX / (4 * kRsPose), [&](int c, int n, long long& hyps) {
+    hyps = hyp_count(triple_count(n), a.max_hyp);
+    return n >= 4 && !(h_mask && h_mask[c] == 0);
+  }, s));
+  const size_t v = (size_t)V, nh = w.plan.n_hyp;
   SFM_TRY(w.poses.alloc(nh * 4 * kRsPose, s)); SFM_TRY(w.pose_ok.alloc(nh, s)); SFM_TRY(w.counts.alloc(nh * 4, s));
   SFM_TRY(w.win_count.alloc(v, s)); SFM_TRY(w.win_pose.alloc(v * kRsPose, s)); SFM_TRY(w.win_cam.alloc(v * 7, s));
-  if (!a.best_hyp) { SFM_TRY(w.best_hyp.alloc(v, s)); a.best_hyp = w.best_hyp.p; }
-  if (!a.status) { SFM_TRY(w.status.alloc(v, s)); a.status = w.status.p; }
-  if (!a.summary) { SFM_TRY(w.summary.alloc(6, s)); a.summary = w.summary.p; }
-  a.hyp_off = w.hyp_off.p; a.blocks = w.blocks.p;
+  SFM_TRY(w.stand_in.fill(a, v, true, s));
+  a.hyp_off = w.plan.hyp_off.p; a.blocks = w.plan.blocks.p;
   a.poses = w.poses.p; a.pose_ok = w.pose_ok.p; a.counts = w.counts.p;
   a.win_count = w.win_count.p; a.win_pose = w.win_pose.p; a.win_cam = w.win_cam.p;
-  SFM_HIP(hipMemsetAsync(a.summary, 0, 6 * sizeof(unsigned long long), s));
   if (nh) {
     SFM_HIP(hipMemsetAsync(a.counts, 0, sizeof(int) * nh * 4, s));
     resect_hyp_kernel<<<(unsigned)((nh + kRsThreads - 1) / kRsThreads), kRsThreads, 0, s>>>(a, (int)nh);
-    resect_score_kernel<<<(unsigned)blocks.size(), kRsThreads, 0, s>>>(a);
+    resect_score_kernel<<<w.plan.n_blocks, kRsThreads, 0, s>>>(a);
   }
   resect_pick_kernel<<<V, 64, 0, s>>>(a);
   resect_refit_kernel<<<V, kRsThreads, 0, s>>>(a);

@@ -12,13 +12,15 @@
 //            sfm_track_obs.h, the nine sums through group_sum<G>), then the judgement of the point that stands
 // No floating-point value is summed across lanes in `score`, and nothing is accumulated with atomics but the six summary
 // counters: the winner does not depend on G, on the other points of the call or on timing; a point's bits depend on
-// its track, its input, the options and G only.
+// its track, its input, the options and G only.  The summary counters and the host frame of the entry points are
+// sfm_robust.h's, shared with the resection and the two-view geometry; the scoring (one lane per hypothesis, a cosine
+// tie-break) is this file's own.
 #include <climits>
 #include <cmath>
 
 #include "sfm_ba.h"
 #include "sfm_track_obs.h"      // contraction is off from here on
-#include "sfm_hyp_number.h"
+#include "sfm_robust.h"
 
 namespace sfm {
 
@@ -285,9 +287,9 @@ static int ransac_check_args(const char* who, int n_pts, int n_views, long long 
 
 // What a call keeps on the device besides the caller's arrays.
 struct RansacWork {
-  DevBuf<int> best_hyp, hyp_count;
+  RobustStandIns stand_in;
+  DevBuf<int> hyp_count;
   DevBuf<double> hyp_x, centres;      // centres: the free form only
-  DevBuf<unsigned long long> summary;
 };
 
 // Enqueue both kernels on s; the CSR has been validated, max_track is its longest track.  a.best_hyp / a.summary may be
@@ -296,12 +298,10 @@ struct RansacWork {
 static int ransac_enqueue(RansacArgs a, RansacWork& w, int group, long long M, int max_track, hipStream_t s) {
   const size_t n = (size_t)a.t.n_pts;
   if (a.max_hyp == 0) a.max_hyp = kHypDefault;
-  if (!a.best_hyp) { SFM_TRY(w.best_hyp.alloc(n, s)); a.best_hyp = w.best_hyp.p; }
-  if (!a.summary) { SFM_TRY(w.summary.alloc(6, s)); a.summary = w.summary.p; }
+  SFM_TRY(w.stand_in.fill(a, n, false, s));      // the refit tests a.status itself
   SFM_TRY(w.hyp_count.alloc(n, s));
   SFM_TRY(w.hyp_x.alloc(3 * n, s));
   a.hyp_count = w.hyp_count.p; a.hyp_x = w.hyp_x.p;
-  SFM_HIP(hipMemsetAsync(a.summary, 0, 6 * sizeof(unsigned long long), s));
   if (a.t.n_pts <= 0) return SFM_OK;
   const int g = group ? group : sfm_tri_tracks_auto_group(a.t.n_pts, M, max_track);
   dispatch_group<1>(g, [&](auto G) { launch_ransac<decltype(G)::value>(a, s); });

@@ -19,13 +19,15 @@
 // One body per kernel serves every set size.  No floating-point value is accumulated with an atomic; the counts are
 // integers; every floating-point sum over matches is formed per slice of 64 consecutive matches and the slices are added
 // in ascending order: a set's bits depend on its own matches and the options only.
+// Shared with the robust resection, in sfm_robust.h: the plan of the hypotheses (HypPlan, hyp_owner), the batch loop of
+// `score` (robust_score_block), the tie rule of `pick` (wave_arg_best), the block reductions of `norm`, `refit` and `judge`
+// (block_count, slice_totals, block_sum_int), the summary and the host frame.
 #include <climits>
 #include <cmath>
-#include <vector>
 
 #include "sfm_eight_point.h"   // default contraction, as in sfm_epipolar.hip
-#include "sfm_hyp_number.h"
 #include "sfm_obs_test.h"      // contraction is off from here on
+#include "sfm_robust.h"
 
 namespace sfm {
 
@@ -107,15 +109,7 @@ __device__ __forceinline__ void tv_block_sums(double (&acc)[K], int tid, double 
 #pragma unroll
     for (int k = 0; k < K; ++k) red[tid >> 4][k] = acc[k];
   }
-  __syncthreads();
-  if (tid < K) {
-    double t = first ? red[0][tid] : run + red[0][tid];
-#pragma unroll
-    for (int w = 1; w < kTvRows; ++w) t += red[w][tid];
-    run = t;
-    if (last) sums[tid] = t;
-  }
-  __syncthreads();
+  slice_totals<K, kTvRows>(red, sums, run, first, last, tid);
 }
 
 // The Hartley transforms (epipolar_processor.py:97-137: centroid, scale sqrt(2) / mean distance) over the matches of the set
@@ -140,7 +134,7 @@ __device__ __forceinline__ TvNorm tv_hartley(const TvArgs& a, int base, int n, c
         mine += in;
       }
     }
-    m += __syncthreads_count(mine & 1) + 2 * __syncthreads_count(mine & 2) + 4 * __syncthreads_count(mine & 4);
+    m += block_count(mine);
     tv_block_sums<4>(acc, tid, red, sums, run, blk == 0, blk == n_blocks - 1);
   }
   TvNorm t;
@@ -228,12 +222,7 @@ __global__ __launch_bounds__(kTvThreads) void twoview_norm_kernel(TvArgs a) {
 __global__ __launch_bounds__(64) void twoview_hyp_kernel(TvArgs a, int n_hyp) {
   const int g = blockIdx.x, lane = threadIdx.x;
   if (g >= n_hyp) return;
-  int lo = 0, hi = a.n_sets;                              // the set whose hypotheses hold g: hyp_off[lo] <= g < hyp_off[lo + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (a.hyp_off[mid] <= g) lo = mid; else hi = mid;
-  }
-  const int s = lo, h = g - a.hyp_off[s];
+  const int s = hyp_owner(a.hyp_off, a.n_sets, g), h = g - a.hyp_off[s];
   const int base = a.ptr[s], n = a.ptr[s + 1] - base;
   const int idx = twoview_sample_index(n, h, lane & 7);
   double row[9];
@@ -280,32 +269,16 @@ __global__ __launch_bounds__(kTvThreads) void twoview_score_kernel(TvArgs a) {
   const int base = a.ptr[s], n = a.ptr[s + 1] - base;
   const int h0 = a.hyp_off[s], H = a.hyp_off[s + 1] - h0;
   // four matches per lane, a wave's loads contiguous; a slot beyond the set holds NaN and is nobody's inlier
-  TvMatch m0, m1, m2, m3;
-  {
-    const double nan = __builtin_nan("");
-    const int i0 = blk.y + tid, i1 = i0 + kTvThreads, i2 = i1 + kTvThreads, i3 = i2 + kTvThreads;
-    m0 = tv_load(a, (long long)base + (i0 < n ? i0 : n - 1)); if (!(i0 < n)) m0.xl = nan;
-    m1 = tv_load(a, (long long)base + (i1 < n ? i1 : n - 1)); if (!(i1 < n)) m1.xl = nan;
-    m2 = tv_load(a, (long long)base + (i2 < n ? i2 : n - 1)); if (!(i2 < n)) m2.xl = nan;
-    m3 = tv_load(a, (long long)base + (i3 < n ? i3 : n - 1)); if (!(i3 < n)) m3.xl = nan;
+  TvMatch m[kTvPerLane];
+#pragma unroll
+  for (int k = 0; k < kTvPerLane; ++k) {
+    const int i = blk.y + k * kTvThreads + tid;
+    m[k] = tv_load(a, (long long)base + (i < n ? i : n - 1));
+    if (!(i < n)) m[k].xl = __builtin_nan("");
   }
-  for (int hb = 0; hb < H; hb += kTvBatch) {
-    const int nb = min(kTvBatch, H - hb);
-    const double* src = a.hyp_F + (size_t)(h0 + hb) * 9;
-    for (int i = tid; i < nb * 9; i += kTvThreads) Fm[i] = src[i];
-    if (tid < nb) okb[tid] = a.hyp_ok[h0 + hb + tid];
-    __syncthreads();
-    for (int hh = 0; hh < nb; ++hh) {
-      if (!okb[hh]) continue;                              // the same for the whole workgroup: the branch is uniform
-      const double* F = Fm + hh * 9;                       // every lane reads the same address: a broadcast
-      int cnt = __popcll(__ballot(twoview_inlier(F, m0.xl, m0.yl, m0.xr, m0.yr, a.max_err2)));
-      cnt += __popcll(__ballot(twoview_inlier(F, m1.xl, m1.yl, m1.xr, m1.yr, a.max_err2)));
-      cnt += __popcll(__ballot(twoview_inlier(F, m2.xl, m2.yl, m2.xr, m2.yr, a.max_err2)));
-      cnt += __popcll(__ballot(twoview_inlier(F, m3.xl, m3.yl, m3.xr, m3.yr, a.max_err2)));
-      if ((tid & 63) == 0 && cnt) atomicAdd(&a.counts[h0 + hb + hh], cnt);
-    }
-    __syncthreads();                                       // the batch has been read: the next one may be staged
-  }
+  robust_score_block<kTvThreads, kTvBatch, 9, 1, kTvPerLane>(
+      a.hyp_F, a.hyp_ok, a.counts, h0, H, Fm, okb,
+      [&](const double* F, int k) { return twoview_inlier(F, m[k].xl, m[k].yl, m[k].xr, m[k].yr, a.max_err2); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -314,17 +287,8 @@ __global__ __launch_bounds__(kTvThreads) void twoview_score_kernel(TvArgs a) {
 __global__ __launch_bounds__(64) void twoview_pick_kernel(TvArgs a) {
   const int s = blockIdx.x, lane = threadIdx.x;
   const int h0 = a.hyp_off[s], H = a.hyp_off[s + 1] - h0;
-  int best_cnt = -1, best_h = INT_MAX;
-  for (int h = lane; h < H; h += 64) {                     // ascending h per lane: the first of the largest counts wins
-    if (!a.hyp_ok[h0 + h]) continue;
-    const int cnt = a.counts[h0 + h];
-    if (cnt > best_cnt) { best_cnt = cnt; best_h = h; }
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int oc = __shfl_xor(best_cnt, off, 64), oh = __shfl_xor(best_h, off, 64);
-    if (oc > best_cnt || (oc == best_cnt && oh < best_h)) { best_cnt = oc; best_h = oh; }
-  }
+  int best_cnt, best_h;                                    // the first of the largest counts wins
+  wave_arg_best(lane, H, [&](int h) { return a.hyp_ok[h0 + h] != 0; }, [&](int h) { return a.counts[h0 + h]; }, best_cnt, best_h);
   if (lane != 0) return;
   const bool won = best_cnt >= kTvMinCount;
   a.best_hyp[s] = won ? best_h : -1;
@@ -345,7 +309,7 @@ __device__ __forceinline__ int tv_count(const TvArgs& a, int base, int n, const 
       const int i = blk + k * kTvThreads + tid;
       if (i < n) mine += tv_inlier(F, tv_load(a, (long long)base + i), a.max_err2);
     }
-    total += __syncthreads_count(mine & 1) + 2 * __syncthreads_count(mine & 2) + 4 * __syncthreads_count(mine & 4);
+    total += block_count(mine);
   }
   return total;
 }
@@ -445,8 +409,6 @@ __global__ __launch_bounds__(kTvThreads) void twoview_judge_kernel(TvArgs a) {
   const int base = a.ptr[s], n = a.ptr[s + 1] - base;
   const int flags = a.status[s];
   const bool solved = !(flags & (SFM_TWOVIEW_TOO_FEW | SFM_TWOVIEW_NO_MODEL));
-  if (tid == 0) total = 0;
-  __syncthreads();
   double F[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) F[k] = a.F_out[9 * (size_t)s + k];
@@ -456,12 +418,8 @@ __global__ __launch_bounds__(kTvThreads) void twoview_judge_kernel(TvArgs a) {
     if (a.obs_inlier) a.obs_inlier[(size_t)base + i] = in ? 1 : 0;
     nin += in;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) nin += __shfl_xor(nin, off, 64);
-  if ((tid & 63) == 0 && nin) atomicAdd(&total, nin);
-  __syncthreads();
+  nin = block_sum_int(nin, &total);
   if (tid != 0) return;
-  nin = total;
   if (a.n_inliers) a.n_inliers[s] = nin;
   robust_summary_add(a.summary, solved, false, flags & SFM_TWOVIEW_TOO_FEW, flags & SFM_TWOVIEW_KEPT_HYPOTHESIS, n, nin);
 }
@@ -472,24 +430,16 @@ __global__ __launch_bounds__(kTvThreads) void twoview_judge_kernel(TvArgs a) {
 // host side
 // ---------------------------------------------------------------------------------------------
 static int twoview_check_sets(const char* who, int n_sets, const int* set_ptr, long long M) {
-  if (n_sets < 0 || M < 0 || M > INT_MAX) { set_error("%s: bad sizes n_sets=%d M=%lld", who, n_sets, M); return SFM_E_SHAPE; }
-  if (set_ptr == nullptr) { set_error("%s: null set_ptr", who); return SFM_E_SHAPE; }
-  if (set_ptr[0] != 0 || set_ptr[n_sets] != M) {
-    set_error("%s: set_ptr must start at 0 and end at M = %lld (it runs from %d to %d)", who, M, set_ptr[0], set_ptr[n_sets]);
-    return SFM_E_SHAPE;
-  }
-  for (int c = 0; c < n_sets; ++c)
-    if (set_ptr[c + 1] < set_ptr[c]) { set_error("%s: set_ptr decreases at set %d", who, c); return SFM_E_SHAPE; }
-  return SFM_OK;
+  return robust_check_offsets(who, "set", "set_ptr", n_sets, set_ptr, M, true);
 }
 
 // What a call keeps on the device besides the caller's arrays.
 struct TwoviewWork {
-  DevBuf<int> ptr, hyp_off, counts, win_count, best_hyp, status;
-  DevBuf<int2> blocks;
+  HypPlan plan;
+  RobustStandIns stand_in;
+  DevBuf<int> ptr, counts, win_count;
   DevBuf<double> pairs, T, hyp_F;
   DevBuf<unsigned char> hyp_ok;
-  DevBuf<unsigned long long> summary;
 };
 
 // The one body of sfm_twoview_ransac and sfm_twoview_ransac_dev: checked arguments and device pointers in (n_sets > 0),
@@ -498,41 +448,27 @@ static int twoview_run(const char* who, int n_sets, const int* set_ptr, long lon
                        double max_err2, int max_hyp, int iters, double* d_F_out, const RobustPtrs& out, TwoviewWork& w,
                        hipStream_t s) {
   if (max_hyp == 0) max_hyp = kHypDefault;
-  std::vector<int> off((size_t)n_sets + 1, 0);
-  std::vector<int2> blocks;
-  long long total = 0;
-  for (int c = 0; c < n_sets; ++c) {
-    const int n = set_ptr[c + 1] - set_ptr[c];
-    off[c] = (int)total;
-    if (n >= kTvMinSet) {
-      total += max_hyp;
-      for (int b = 0; b < n; b += kTvBlockObs) blocks.push_back(make_int2(c, b));
-    }
-    if (total > INT_MAX / 16) { set_error("%s: %lld hypotheses are beyond the workspace", who, total); return SFM_E_SHAPE; }
-  }
-  off[n_sets] = (int)total;
-  const size_t v = (size_t)n_sets, nh = (size_t)total;
+  SFM_TRY(w.plan.build(who, n_sets, set_ptr, kTvBlockObs, INT_MAX / 16, [&](int, int n, long long& hyps) {
+    hyps = max_hyp;
+    return n >= kTvMinSet;
+  }, s));
+  const size_t v = (size_t)n_sets, nh = w.plan.n_hyp;
   TvArgs a = {};
   a.n_sets = n_sets; a.M = M; a.left = d_left; a.right = d_right;
   a.max_err2 = max_err2; a.max_hyp = max_hyp; a.iters = iters; a.F_out = d_F_out;
   out.into(a);
   SFM_TRY(w.ptr.upload(set_ptr, v + 1, s));
-  SFM_TRY(w.hyp_off.upload(off.data(), v + 1, s));
-  SFM_TRY(w.blocks.upload(blocks.data(), blocks.size(), s));
   SFM_TRY(w.pairs.alloc(4 * (size_t)M, s)); SFM_TRY(w.T.alloc(18 * v, s));
   SFM_TRY(w.hyp_F.alloc(nh * 9, s)); SFM_TRY(w.hyp_ok.alloc(nh, s)); SFM_TRY(w.counts.alloc(nh, s));
   SFM_TRY(w.win_count.alloc(v, s));
-  if (!a.best_hyp) { SFM_TRY(w.best_hyp.alloc(v, s)); a.best_hyp = w.best_hyp.p; }
-  if (!a.status) { SFM_TRY(w.status.alloc(v, s)); a.status = w.status.p; }
-  if (!a.summary) { SFM_TRY(w.summary.alloc(6, s)); a.summary = w.summary.p; }
-  a.ptr = w.ptr.p; a.hyp_off = w.hyp_off.p; a.blocks = w.blocks.p;
+  SFM_TRY(w.stand_in.fill(a, v, true, s));
+  a.ptr = w.ptr.p; a.hyp_off = w.plan.hyp_off.p; a.blocks = w.plan.blocks.p;
   a.pairs = w.pairs.p; a.T = w.T.p; a.hyp_F = w.hyp_F.p; a.hyp_ok = w.hyp_ok.p; a.counts = w.counts.p; a.win_count = w.win_count.p;
-  SFM_HIP(hipMemsetAsync(a.summary, 0, 6 * sizeof(unsigned long long), s));
   if (nh) {
     SFM_HIP(hipMemsetAsync(a.counts, 0, sizeof(int) * nh, s));
     twoview_norm_kernel<<<n_sets, kTvThreads, 0, s>>>(a);
     twoview_hyp_kernel<<<(unsigned)nh, 64, 0, s>>>(a, (int)nh);
-    twoview_score_kernel<<<(unsigned)blocks.size(), kTvThreads, 0, s>>>(a);
+    twoview_score_kernel<<<w.plan.n_blocks, kTvThreads, 0, s>>>(a);
   }
   twoview_pick_kernel<<<n_sets, 64, 0, s>>>(a);
   twoview_refit_kernel<<<n_sets, kTvThreads, 0, s>>>(a);

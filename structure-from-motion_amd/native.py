@@ -545,75 +545,74 @@ def check_screen(n_cams, max_err2, cos_min_angle, min_obs, cam_scale, group=0):
     return max_err2, cos_min_angle, int(min_obs), _check_cam_scale(cam_scale, n_cams), group
 
 
+def _check_robust(max_err2, max_hyp, iters, lam=None, cos_min_angle=None):
+    """The options the robust operations share, refused in the order of the C entry points: returns
+    ``(max_err2, cos_min_angle, max_hyp, lam, iters)`` converted or raises ValueError.  ``lam`` / ``cos_min_angle`` None:
+    the operation has no such option."""
+    max_err2 = float(max_err2)
+    cos_min_angle = None if cos_min_angle is None else float(cos_min_angle)
+    lam = None if lam is None else float(lam)
+    if not max_err2 >= 0.0:
+        raise ValueError("max_err2 must be >= 0, got %r" % max_err2)
+    if cos_min_angle is not None and not cos_min_angle >= -1.0:
+        raise ValueError("cos_min_angle must be >= -1 (>= 1 switches the gate off), got %r" % cos_min_angle)
+    max_hyp = _count("max_hyp", max_hyp)
+    if max_hyp > RANSAC_MAX_HYP:      # one bound and one default for all three (the C side's kHypMax, kHypDefault)
+        raise ValueError("max_hyp must be in 1 .. %d (0 = %d), got %r" % (RANSAC_MAX_HYP, RANSAC_DEFAULT_HYP, max_hyp))
+    if lam is not None and not lam >= 0.0:
+        raise ValueError("lam must be >= 0, got %r" % lam)
+    return max_err2, cos_min_angle, max_hyp, lam, _count("iters", iters)
+
+
+def _check_offsets(name, ptr, m):
+    """The offsets of the groups of a free-form call as int32 (groups + 1,): they start at 0, do not decrease and end at
+    M = ``m``, or ValueError."""
+    ptr = np.ascontiguousarray(ptr, dtype=np.int32).ravel()
+    if ptr.shape[0] < 1 or ptr[0] != 0 or ptr[-1] != m or np.any(np.diff(ptr) < 0):
+        raise ValueError("%s must start at 0, not decrease and end at M = %d" % (name, m))
+    return ptr
+
+
 def check_ransac(n_cams, max_err2, cos_min_angle=1.0, max_hyp=0, lam=0.5, iters=3, cam_scale=None, group=0):
     """Arguments of a ``tri_tracks_ransac`` / ``BaProblem.retriangulate`` call, without a device: returns
     ``(max_err2, cos_min_angle, max_hyp, lam, iters, cam_scale, group)`` converted or raises ValueError -- everything
     sfm_tri_tracks_ransac refuses."""
-    max_err2, cos_min_angle, lam = float(max_err2), float(cos_min_angle), float(lam)
-    if not max_err2 >= 0.0:
-        raise ValueError("max_err2 must be >= 0, got %r" % max_err2)
-    if not cos_min_angle >= -1.0:
-        raise ValueError("cos_min_angle must be >= -1 (>= 1 switches the gate off), got %r" % cos_min_angle)
-    max_hyp = _count("max_hyp", max_hyp)
-    if max_hyp > RANSAC_MAX_HYP:
-        raise ValueError("max_hyp must be in 1 .. %d (0 = %d), got %r" % (RANSAC_MAX_HYP, RANSAC_DEFAULT_HYP, max_hyp))
-    if not lam >= 0.0:
-        raise ValueError("lam must be >= 0, got %r" % lam)
-    iters = _count("iters", iters)
+    options = _check_robust(max_err2, max_hyp, iters, lam, cos_min_angle)
     group = _check_group(group)
-    return max_err2, cos_min_angle, max_hyp, lam, iters, _check_cam_scale(cam_scale, n_cams), group
+    return options + (_check_cam_scale(cam_scale, n_cams), group)
 
 
 def check_resect(n_cams, max_err2, max_hyp=0, lam=0.5, iters=3, mask=None, cam_scale=None):
     """Arguments of a ``resect_ransac`` / ``BaProblem.resect`` call, without a device: returns
     ``(max_err2, max_hyp, lam, iters, mask, cam_scale)`` converted or raises ValueError -- everything sfm_resect_ransac
     refuses before it looks at the views."""
-    max_err2, lam = float(max_err2), float(lam)
-    if not max_err2 >= 0.0:
-        raise ValueError("max_err2 must be >= 0, got %r" % max_err2)
-    max_hyp = _count("max_hyp", max_hyp)
-    if max_hyp > RESECT_MAX_HYP:
-        raise ValueError("max_hyp must be in 1 .. %d (0 = %d), got %r" % (RESECT_MAX_HYP, RESECT_DEFAULT_HYP, max_hyp))
-    if not lam >= 0.0:
-        raise ValueError("lam must be >= 0, got %r" % lam)
-    iters = _count("iters", iters)
+    max_err2, _, max_hyp, lam, iters = _check_robust(max_err2, max_hyp, iters, lam)
     return max_err2, max_hyp, lam, iters, _cam_mask(mask, n_cams), _check_cam_scale(cam_scale, n_cams)
 
 
 def check_resect_views(view_ptr, uv, X):
     """The free form's arrays, without a device: ``(view_ptr int32 (V + 1,), uv (2, M), X (3, M))`` converted or ValueError --
     view_ptr must start at 0, not decrease and end at M."""
-    view_ptr = np.ascontiguousarray(view_ptr, dtype=np.int32).ravel()
     uv, X = f64(uv), f64(X)
     if uv.ndim != 2 or uv.shape[0] != 2 or X.ndim != 2 or X.shape != (3, uv.shape[1]):
         raise ValueError("uv must be (2, M) and X (3, M), got %r and %r" % (uv.shape, X.shape))
-    if view_ptr.shape[0] < 1 or view_ptr[0] != 0 or view_ptr[-1] != uv.shape[1] or np.any(np.diff(view_ptr) < 0):
-        raise ValueError("view_ptr must start at 0, not decrease and end at M = %d" % uv.shape[1])
-    return view_ptr, uv, X
+    return _check_offsets("view_ptr", view_ptr, uv.shape[1]), uv, X
 
 
 def check_twoview(max_err2, max_hyp=0, iters=2):
     """Options of a ``twoview_ransac`` call, without a device: returns ``(max_err2, max_hyp, iters)`` converted or raises
     ValueError -- everything sfm_twoview_ransac refuses before it looks at the sets."""
-    max_err2 = float(max_err2)
-    if not max_err2 >= 0.0:
-        raise ValueError("max_err2 must be >= 0, got %r" % max_err2)
-    max_hyp = _count("max_hyp", max_hyp)
-    if max_hyp > TWOVIEW_MAX_HYP:
-        raise ValueError("max_hyp must be in 1 .. %d (0 = %d), got %r" % (TWOVIEW_MAX_HYP, TWOVIEW_DEFAULT_HYP, max_hyp))
-    return max_err2, max_hyp, _count("iters", iters)
+    max_err2, _, max_hyp, _, iters = _check_robust(max_err2, max_hyp, iters)
+    return max_err2, max_hyp, iters
 
 
 def check_twoview_sets(set_ptr, left, right):
     """The arrays of a ``twoview_ransac`` call, without a device: ``(set_ptr int32 (S + 1,), left (2, M), right (2, M))``
     converted or ValueError -- set_ptr must start at 0, not decrease and end at M."""
-    set_ptr = np.ascontiguousarray(set_ptr, dtype=np.int32).ravel()
     left, right = f64(left), f64(right)
     if left.ndim != 2 or left.shape[0] != 2 or right.shape != left.shape:
         raise ValueError("left and right must both be (2, M), got %r and %r" % (left.shape, right.shape))
-    if set_ptr.shape[0] < 1 or set_ptr[0] != 0 or set_ptr[-1] != left.shape[1] or np.any(np.diff(set_ptr) < 0):
-        raise ValueError("set_ptr must start at 0, not decrease and end at M = %d" % left.shape[1])
-    return set_ptr, left, right
+    return _check_offsets("set_ptr", set_ptr, left.shape[1]), left, right
 
 
 def check_loss(kind, delta):
