@@ -684,6 +684,60 @@ int sfm_twoview_ransac_dev(int n_sets, const int* set_ptr /*host [n_sets+1]*/, i
  * for 0 <= h < H, the eight ascending match indices of hypothesis h. */
 int sfm_twoview_sample(int n, int max_hyp, int h, int idx[8]);
 
+/* ---- robust homography: sampled four-point hypotheses, inlier refit ------------------------------------------------
+ * A fundamental matrix is not determined when the matches lie on one plane or the camera only rotated: the eight-point
+ * solve then returns some rank-2 matrix that explains every match.  The model of those cases is the homography, the
+ * fourth robust estimator; with both models per pair a caller can tell the cases apart (processors.classify_matches).
+ * A call holds n_sets sets of matches; left and right are [2][M] pixel coordinates (the x row, then the y row); set s owns
+ * the matches set_ptr[s] .. set_ptr[s + 1] - 1, n of them.  The rule, per set, step for step that of the block above:
+ *   1. n < 5: SFM_HOMOGRAPHY_TOO_FEW.
+ *   2. The test.  A model is a pair of row-major 3x3 matrices (H, G) in pixel coordinates, H mapping left to right and G
+ *      right to left.  half(A, p, q): (u, v, w) = A (p_x, p_y, 1)^T, each row as fma(A0, x, fma(A1, y, A2));
+ *      eu = fma(-q_x, w, u), ev = fma(-q_y, w, v); lhs = fma(eu, eu, ev * ev), rhs = max_err2 * (w * w); true iff lhs is
+ *      finite, w * w > 0 and lhs <= rhs.  A match is an INLIER iff half(H, l, r) and half(G, r, l): the transfer error in
+ *      each image is at most max_err2 pixels squared, without a division.  One function (homography_inlier,
+ *      csrc/sfm_obs_test.h) that every stage below calls.
+ *   3. Normalisation.  Step 3 of the two-view rule: the Hartley transforms T_l, T_r over all n matches; if one of them is
+ *      not finite the set is SFM_HOMOGRAPHY_NO_MODEL.
+ *   4. Hypotheses.  H = max_hyp (0 means 128; range 1 .. 65 536), whatever n.  Hypothesis h uses, for k = 0 .. 3, the match
+ *      lo_k + mix(4 h + k) mod (hi_k - lo_k) with lo_k = floor(k n / 4), hi_k = floor((k + 1) n / 4): one match of every
+ *      quarter of the set, so the four indices are distinct and ascending.  mix is the splitmix64 finaliser of the two-view
+ *      rule.  sfm_homography_sample returns the same indices on any machine.
+ *   5. Matrix of a sample.  Every normalised match (x1, y1) -> (x2, y2) gives the design rows
+ *      (-x1, -y1, -1, 0, 0, 0, x2 x1, x2 y1, x2) and (0, 0, 0, -x1, -y1, -1, y2 x1, y2 y1, y2); the null vector of the 8x9
+ *      matrix, read as a 3x3 matrix h, is invalid unless sigma_2 > 3 eps sigma_0 (full rank).  H = T_r^-1 h T_l and
+ *      G = T_l^-1 adj(h) T_r, adj the adjugate (nothing is divided by a determinant); each is scaled to Frobenius norm 1
+ *      with its entry of largest magnitude positive (the lowest index on a tie).  Invalid if not finite.  How the null
+ *      vector and the adjugate are computed is not part of the rule.
+ *   6. Sample gate.  A hypothesis is invalid unless its own four matches are inliers of it.
+ *   7. Score, lexicographic: the inlier count over all n matches (an integer); then the lower h.  A winner needs a count
+ *      of at least 5, otherwise SFM_HOMOGRAPHY_NO_MODEL.
+ *   8. Refit, up to `iters` rounds.  The inlier mask of the standing model; the transforms of step 3 over those inliers
+ *      only; the 9x9 moment matrix A^T A of the inliers' design rows (two per inlier); its eigenvector of smallest
+ *      eigenvalue, then as in step 5.  The round stands iff the result is valid and its inlier count over all n is at least
+ *      the standing count; otherwise the rounds stop.  SFM_HOMOGRAPHY_KEPT_HYPOTHESIS iff iters > 0 and no round stood.
+ *   9. Outputs, all optional but H_out.  H_out[n_sets][9]: the standing H, scaled as in step 5; nine zeros with TOO_FEW or
+ *      NO_MODEL.  obs_inlier[M], n_inliers, best_hyp (-1 without a model), status and summary[6] have the meaning and
+ *      order they have for sfm_twoview_ransac and describe the standing model, judged once more by the function of step 2.
+ * Determinism, argument errors (SFM_E_SHAPE, nothing launched) and the conventions of the _dev form (set_ptr on the host,
+ * d_summary int64[6] on the device, work buffers returned to the pool, the call returns when the work is done) are those
+ * of sfm_twoview_ransac. */
+#define SFM_HOMOGRAPHY_TOO_FEW          1   /* the set has fewer than 5 matches */
+#define SFM_HOMOGRAPHY_NO_MODEL         2   /* no valid hypothesis with at least 5 inliers, or no finite normalisation */
+#define SFM_HOMOGRAPHY_KEPT_HYPOTHESIS  4   /* no refit round stood: the model is the winning hypothesis itself */
+int sfm_homography_ransac(int n_sets, const int* set_ptr /*host [n_sets+1]*/, int64_t M, const double* left /*[2][M]*/,
+                          const double* right /*[2][M]*/, double max_err2, int max_hyp, int iters,
+                          double* H_out /*[n_sets][9]*/, unsigned char* obs_inlier /*[M] or NULL*/,
+                          int* n_inliers /*[n_sets] or NULL*/, int* best_hyp /*[n_sets] or NULL*/,
+                          int* status /*[n_sets] or NULL*/, int64_t* summary /*[6] or NULL*/);
+int sfm_homography_ransac_dev(int n_sets, const int* set_ptr /*host [n_sets+1]*/, int64_t M, const double* d_left,
+                              const double* d_right, double max_err2, int max_hyp, int iters, double* d_H_out,
+                              unsigned char* d_obs_inlier, int* d_n_inliers, int* d_best_hyp, int* d_status,
+                              int64_t* d_summary, void* hip_stream);
+/* Host only, needs no device: the hypothesis count H of a set of n matches (0 for n < 5 or a max_hyp out of range) and,
+ * for 0 <= h < H, the four ascending match indices of hypothesis h. */
+int sfm_homography_sample(int n, int max_hyp, int h, int idx[4]);
+
 /* ---- covariance of the resident scene: per-camera and per-point blocks ---------------------------------------------
  * How well the current state is determined.  With H = J^T J + lambda I = [A B; B^T D] of one linearisation at the current
  * state (r, Jp, Jx exactly as the iterations form them, the Q2 bit of `quirks` honoured; with use_loss = 1 and a loss on

@@ -2,7 +2,8 @@
 // (sfm_tri_ransac.hip) and the triples of a camera's observations (sfm_resect.hip), both in lexicographic order, all of
 // them up to max_hyp, else evenly spaced.  No random number anywhere.  The floating-point estimates below only seed integer
 // searches that end at the exact answer, so the results do not depend on how the including file contracts them.
-// The eight-match samples of the robust two-view geometry (sfm_twoview.hip) are drawn by a stratified integer sampler.
+// The eight-match samples of the robust two-view geometry (sfm_twoview.hip) and the four-match samples of the robust
+// homography (sfm_homography.hip) are drawn by a stratified integer sampler.
 #pragma once
 
 #include <cmath>
@@ -73,6 +74,13 @@ __host__ __device__ inline unsigned long long splitmix64_mix(unsigned long long 
 __host__ __device__ inline int twoview_sample_index(int n, int h, int k) {
   const long long lo = (long long)k * n / 8, hi = (long long)(k + 1) * n / 8;
   return (int)(lo + (long long)(splitmix64_mix(8ULL * (unsigned long long)h + (unsigned long long)k) % (unsigned long long)(hi - lo)));
+}
+
+// ---- four-index samples of a set of n >= 5 matches (sfm_homography.hip): the same sampler over quarters, stratum k being
+// floor(k n / 4) .. floor((k + 1) n / 4) - 1 (never empty) and hypothesis h taking lo_k + mix(4 h + k) mod (hi_k - lo_k).
+__host__ __device__ inline int homography_sample_index(int n, int h, int k) {
+  const long long lo = (long long)k * n / 4, hi = (long long)(k + 1) * n / 4;
+  return (int)(lo + (long long)(splitmix64_mix(4ULL * (unsigned long long)h + (unsigned long long)k) % (unsigned long long)(hi - lo)));
 }
 
 }  // namespace sfm

@@ -4,7 +4,8 @@
 // rs_project_pose for [m | t], obs_project_cam for a prepared camera) and continues here: resect then screen, retriangulate
 // then cull, free and resident form agree on every decision because they execute the same function.  Below it the test
 // of one match against a fundamental matrix (the squared Sampson distance), which every stage of the robust two-view
-// geometry calls in the same way.
+// geometry calls in the same way, and the test of one match against a homography and its inverse (the transfer error in
+// each image), which every stage of the robust homography calls.
 //
 // Compiled WITHOUT automatic contraction, the FMAs spelled out.  The pragma is lexical and stays in force for the rest of
 // the translation unit: include this header outside any namespace and AFTER all code that keeps the compiler's default
@@ -57,6 +58,25 @@ __host__ __device__ inline bool twoview_inlier(const double* F, double xl, doubl
   const double den = __builtin_fma(a0, a0, a1 * a1) + __builtin_fma(b0, b0, b1 * b1);
   const double d2 = (e * e) / den;
   return (bool)((int)(__builtin_isfinite(d2) != 0) & (int)(d2 <= max_err2));
+}
+
+// One half of the test of a match against a homography: A (row-major 3x3) maps p to (u, v, w); the transfer error
+// against q, times w^2, is compared with max_err2 w^2 -- no division.  True iff the error is finite, w^2 > 0 and it is
+// within the bound.
+__host__ __device__ inline bool homography_half(const double* A, double px, double py, double qx, double qy, double max_err2) {
+  const double u = __builtin_fma(A[0], px, __builtin_fma(A[1], py, A[2]));
+  const double v = __builtin_fma(A[3], px, __builtin_fma(A[4], py, A[5]));
+  const double w = __builtin_fma(A[6], px, __builtin_fma(A[7], py, A[8]));
+  const double eu = __builtin_fma(-qx, w, u), ev = __builtin_fma(-qy, w, v);
+  const double lhs = __builtin_fma(eu, eu, ev * ev), rhs = max_err2 * (w * w);
+  return (bool)((int)(__builtin_isfinite(lhs) != 0) & (int)(w * w > 0.0) & (int)(lhs <= rhs));
+}
+
+// The test of one MATCH (x_l, y_l) <-> (x_r, y_r) against a model HG = (H, G) of 18 doubles, H mapping left to right and
+// G right to left (pixel coordinates): an inlier iff the transfer error in each image is at most max_err2 pixels squared.
+// Every stage of the robust homography (sample gate, score, refit, judge) calls this one function; no branch.
+__host__ __device__ inline bool homography_inlier(const double* HG, double xl, double yl, double xr, double yr, double max_err2) {
+  return (bool)((int)homography_half(HG, xl, yl, xr, yr, max_err2) & (int)homography_half(HG + 9, xr, yr, xl, yl, max_err2));
 }
 
 }  // namespace sfm

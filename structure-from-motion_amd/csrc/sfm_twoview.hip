@@ -21,24 +21,26 @@
 // in ascending order: a set's bits depend on its own matches and the options only.
 // Shared with the robust resection, in sfm_robust.h: the plan of the hypotheses (HypPlan, hyp_owner), the batch loop of
 // `score` (robust_score_block), the tie rule of `pick` (wave_arg_best), the block reductions of `norm`, `refit` and `judge`
-// (block_count, slice_totals, block_sum_int), the summary and the host frame.
+// (block_count, slice_totals, block_sum_int), the summary and the host frame.  Shared with the robust homography, in
+// sfm_match_norm.h: the match and its load, the Hartley pass with its slice-ordered sums, the scaling of a 3x3 matrix.
 #include <climits>
 #include <cmath>
 
 #include "sfm_eight_point.h"   // default contraction, as in sfm_epipolar.hip
 #include "sfm_obs_test.h"      // contraction is off from here on
 #include "sfm_robust.h"
+#include "sfm_match_norm.h"     // the match, the Hartley pass and the scaling, shared with sfm_homography.hip
 
 namespace sfm {
 
 constexpr int kTvMinSet = 9;          // a set needs one match besides a sample's eight
 constexpr int kTvMinCount = 9;        // ... and so does a winner
-constexpr int kTvThreads = 256;
-constexpr int kTvPerLane = 4;
-constexpr int kTvBlockObs = kTvThreads * kTvPerLane;      // 1 024 matches per workgroup and pass
+constexpr int kTvThreads = kMatchThreads;
+constexpr int kTvPerLane = kMatchPerLane;
+constexpr int kTvBlockObs = kMatchBlockObs;               // 1 024 matches per workgroup and pass
 constexpr int kTvBatch = 64;          // hypotheses per LDS batch: 64 x 9 doubles = 4 608 bytes
-constexpr int kTvRows = kTvThreads / 16;                  // slices of 64 matches per pass: 16 lanes x 4 matches each
-constexpr int kTvMoments = 45;        // upper triangle of the 9x9 moment matrix
+constexpr int kTvRows = kMatchRows;
+constexpr int kTvMoments = kMatchMoments;                 // upper triangle of the 9x9 moment matrix
 
 struct TvArgs {
   int n_sets;
@@ -64,128 +66,27 @@ struct TvArgs {
   unsigned long long* summary;  // [6]
 };
 
-struct TvMatch { double xl, yl, xr, yr; };
+__device__ __forceinline__ MatchView tv_view(const TvArgs& a) { return {a.left, a.right, a.M}; }
 
-__device__ __forceinline__ TvMatch tv_load(const TvArgs& a, long long i) {
-  return {a.left[i], a.left[a.M + i], a.right[i], a.right[a.M + i]};
-}
+__device__ __forceinline__ TvMatch tv_load(const TvArgs& a, long long i) { return match_load(tv_view(a), i); }
 
 __device__ __forceinline__ bool tv_inlier(const double (&F)[9], const TvMatch& m, double max_err2) {
   return twoview_inlier(F, m.xl, m.yl, m.xr, m.yr, max_err2);
 }
 
-// A Hartley transform as (mean x, mean y, scale): x^ = scale x + (-(mean x) scale).
-struct TvNorm { double ml[2], mr[2], sl, sr; };
-
-__device__ __forceinline__ void tv_normalise(const TvNorm& t, const TvMatch& m, double (&p)[4]) {
-  p[0] = __builtin_fma(t.sl, m.xl, -(t.ml[0] * t.sl));
-  p[1] = __builtin_fma(t.sl, m.yl, -(t.ml[1] * t.sl));
-  p[2] = __builtin_fma(t.sr, m.xr, -(t.mr[0] * t.sr));
-  p[3] = __builtin_fma(t.sr, m.yr, -(t.mr[1] * t.sr));
-}
-
-__device__ __forceinline__ void tv_transforms(const TvNorm& t, double (&tl)[9], double (&tr)[9]) {
-  const double l[9] = {t.sl, 0, -(t.ml[0] * t.sl), 0, t.sl, -(t.ml[1] * t.sl), 0, 0, 1};
-  const double r[9] = {t.sr, 0, -(t.mr[0] * t.sr), 0, t.sr, -(t.mr[1] * t.sr), 0, 0, 1};
-#pragma unroll
-  for (int k = 0; k < 9; ++k) { tl[k] = l[k]; tr[k] = r[k]; }
-}
-
-__device__ __forceinline__ bool tv_norm_finite(const TvNorm& t) {
-  const double probe = (t.ml[0] + t.ml[1] + t.mr[0] + t.mr[1] + t.sl + t.sr + t.ml[0] * t.sl + t.ml[1] * t.sl + t.mr[0] * t.sr +
-                        t.mr[1] * t.sr) * 0.0;
-  return probe == 0.0;
-}
-
-// The slice sums of one pass of 1 024 matches, added to the running totals in slice order.  acc: the lane's sums over its
-// four consecutive matches; 16 adjacent lanes hold a slice of 64 consecutive matches.  Threads 0 .. K-1 carry `run`; with
-// `last` they leave the totals in sums[].  Slices beyond the set hold zeros.  Ends with a barrier.
-template <int K>
-__device__ __forceinline__ void tv_block_sums(double (&acc)[K], int tid, double (*red)[kTvMoments], double* sums, double& run,
-                                              bool first, bool last) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) acc[k] = group_sum<16>(acc[k]);
-  if ((tid & 15) == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[tid >> 4][k] = acc[k];
-  }
-  slice_totals<K, kTvRows>(red, sums, run, first, last, tid);
-}
-
-// The Hartley transforms (epipolar_processor.py:97-137: centroid, scale sqrt(2) / mean distance) over the matches of the set
-// that are inliers of F (MASKED) or over all of them.  Every thread of the workgroup returns the same values; *count is the
-// number of matches taken.
-template <bool MASKED>
-__device__ __forceinline__ TvNorm tv_hartley(const TvArgs& a, int base, int n, const double (&F)[9], int tid,
-                                             double (*red)[kTvMoments], double* sums, int* count) {
-  const int n_blocks = (n + kTvBlockObs - 1) / kTvBlockObs;
-  double run = 0;
-  int m = 0;
-  for (int blk = 0; blk < n_blocks; ++blk) {
-    double acc[4] = {0, 0, 0, 0};
-    int mine = 0;
-#pragma unroll
-    for (int k = 0; k < kTvPerLane; ++k) {
-      const int i = blk * kTvBlockObs + kTvPerLane * tid + k;
-      if (i < n) {
-        const TvMatch mt = tv_load(a, (long long)base + i);
-        const bool in = MASKED ? tv_inlier(F, mt, a.max_err2) : true;
-        acc[0] += in ? mt.xl : 0.0; acc[1] += in ? mt.yl : 0.0; acc[2] += in ? mt.xr : 0.0; acc[3] += in ? mt.yr : 0.0;
-        mine += in;
-      }
-    }
-    m += block_count(mine);
-    tv_block_sums<4>(acc, tid, red, sums, run, blk == 0, blk == n_blocks - 1);
-  }
-  TvNorm t;
-  const double dm = (double)m;
-  t.ml[0] = sums[0] / dm; t.ml[1] = sums[1] / dm; t.mr[0] = sums[2] / dm; t.mr[1] = sums[3] / dm;
-  for (int blk = 0; blk < n_blocks; ++blk) {
-    double acc[2] = {0, 0};
-#pragma unroll
-    for (int k = 0; k < kTvPerLane; ++k) {
-      const int i = blk * kTvBlockObs + kTvPerLane * tid + k;
-      if (i < n) {
-        const TvMatch mt = tv_load(a, (long long)base + i);
-        const bool in = MASKED ? tv_inlier(F, mt, a.max_err2) : true;
-        const double ax = mt.xl - t.ml[0], ay = mt.yl - t.ml[1], bx = mt.xr - t.mr[0], by = mt.yr - t.mr[1];
-        const double dl = sqrt(__builtin_fma(ax, ax, ay * ay)), dr = sqrt(__builtin_fma(bx, bx, by * by));
-        acc[0] += in ? dl : 0.0; acc[1] += in ? dr : 0.0;
-      }
-    }
-    tv_block_sums<2>(acc, tid, red, sums, run, blk == 0, blk == n_blocks - 1);
-  }
-  t.sl = (1.4142135623730951 * dm) / sums[0];
-  t.sr = (1.4142135623730951 * dm) / sums[1];
-  __syncthreads();                                         // sums has been read: the next pass may write it
-  *count = m;
-  return t;
-}
-
-// T_r^T f2 T_l, scaled to Frobenius norm 1 with its entry of largest magnitude (the first of them) positive; false if the
-// result is not finite or zero.
+// T_r^T f2 T_l, scaled by canon9; false if the result is not finite or zero.
 __device__ __forceinline__ bool tv_denorm_canon(const double (&f)[9], const double (&tl)[9], const double (&tr)[9], double (&g)[9]) {
   double m[9];
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int c = 0; c < 3; ++c) m[3 * r + c] = __builtin_fma(tr[6 + r], f[6 + c], __builtin_fma(tr[3 + r], f[3 + c], tr[r] * f[c]));      // T_r^T f
-  double ss = 0, big = -1.0, sign = 1.0;
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double v = __builtin_fma(m[3 * r + 2], tl[6 + c], __builtin_fma(m[3 * r + 1], tl[3 + c], m[3 * r] * tl[c]));
-      g[3 * r + c] = v;
-      ss = __builtin_fma(v, v, ss);
-      const bool larger = fabs(v) > big;
-      sign = larger ? (v < 0.0 ? -1.0 : 1.0) : sign;
-      big = larger ? fabs(v) : big;
-    }
-  const double nrm = sign * sqrt(ss);
-#pragma unroll
-  for (int k = 0; k < 9; ++k) g[k] = g[k] / nrm;
-  return ss > 0.0 && isfinite(ss);                        // an overflowing or NaN entry makes ss non-finite
+    for (int c = 0; c < 3; ++c)
+      g[3 * r + c] = __builtin_fma(m[3 * r + 2], tl[6 + c], __builtin_fma(m[3 * r + 1], tl[3 + c], m[3 * r] * tl[c]));
+  return canon9(g);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -197,9 +98,8 @@ __global__ __launch_bounds__(kTvThreads) void twoview_norm_kernel(TvArgs a) {
   const int s = blockIdx.x, tid = threadIdx.x;
   const int base = a.ptr[s], n = a.ptr[s + 1] - base;
   if (n < kTvMinSet) return;
-  const double none[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   int count;
-  const TvNorm t = tv_hartley<false>(a, base, n, none, tid, red, sums, &count);
+  const TvNorm t = tv_hartley(tv_view(a), base, n, [](const TvMatch&) { return true; }, tid, red, sums, &count);
   for (int i = tid; i < n; i += kTvThreads) {
     double p[4];
     tv_normalise(t, tv_load(a, (long long)base + i), p);
@@ -332,7 +232,7 @@ __global__ __launch_bounds__(kTvThreads) void twoview_refit_kernel(TvArgs a) {
     // from here on every thread holds the same values: the branches are uniform
     for (int it = 0; it < a.iters; ++it) {
       int m;
-      const TvNorm t = tv_hartley<true>(a, base, n, F, tid, red, sums, &m);
+      const TvNorm t = tv_hartley(tv_view(a), base, n, [&](const TvMatch& mt) { return tv_inlier(F, mt, a.max_err2); }, tid, red, sums, &m);
       if (!tv_norm_finite(t)) break;
       double run = 0;
       for (int blk = 0; blk < n_blocks; ++blk) {

@@ -56,6 +56,10 @@ TWOVIEW_TOO_FEW, TWOVIEW_NO_MODEL, TWOVIEW_KEPT_HYPOTHESIS = 1, 2, 4
 TWOVIEW_MAX_HYP, TWOVIEW_DEFAULT_HYP, TWOVIEW_MIN_MATCHES = 65536, 128, 9
 TWOVIEW_SUMMARY = ("sets_solved", "sets_no_model", "sets_too_few", "sets_kept_hypothesis", "matches_inlier", "matches_outlier")
 TWOVIEW_OUTPUTS = ("inlier", "n_inliers", "best_hyp", "status", "summary")
+HOMOGRAPHY_TOO_FEW, HOMOGRAPHY_NO_MODEL, HOMOGRAPHY_KEPT_HYPOTHESIS = 1, 2, 4
+HOMOGRAPHY_MAX_HYP, HOMOGRAPHY_DEFAULT_HYP, HOMOGRAPHY_MIN_MATCHES = 65536, 128, 5
+HOMOGRAPHY_SUMMARY = TWOVIEW_SUMMARY
+HOMOGRAPHY_OUTPUTS = TWOVIEW_OUTPUTS
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2
 CAM_EMPTY, CAM_NONFINITE, CAM_BEHIND, CAM_HELD = 1, 2, 4, 8
 COV_CAM_HELD, COV_CAM_PIVOT, COV_PT_EMPTY, COV_PT_SINGULAR = 8, 16, 4, 8
@@ -233,6 +237,9 @@ SIGNATURES = {
     "sfm_twoview_ransac": [ci, _ip, i64, _dp, _dp, cd, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
     "sfm_twoview_ransac_dev": [ci, _ip, i64, vp, vp, cd, ci, ci, vp, vp, vp, vp, vp, vp, vp],
     "sfm_twoview_sample": [ci, ci, ci, _ip],
+    "sfm_homography_ransac": [ci, _ip, i64, _dp, _dp, cd, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
+    "sfm_homography_ransac_dev": [ci, _ip, i64, vp, vp, cd, ci, ci, vp, vp, vp, vp, vp, vp, vp],
+    "sfm_homography_sample": [ci, ci, ci, _ip],
     "sfm_twoview_verify_pairs": [vp, ci, ci, cd, ci, ci, _ip, _ip, _ip, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _ip],
     "sfm_ba_covariance": [vp, cd, ci, ci, ctypes.POINTER(ctypes.c_uint8), ci, _dp, _dp, _ip, _ip, _dp],
     "sfm_ba_covariance_plan": [ci, _ip, _ip, _ip, _ip],
@@ -834,6 +841,45 @@ def twoview_ransac_dev(set_ptr, n_obs, d_left, d_right, max_err2, max_hyp=0, ite
     check(load().sfm_twoview_ransac_dev(set_ptr.shape[0] - 1, iptr(set_ptr), int(n_obs), _vp(d_left), _vp(d_right), max_err2,
                                         max_hyp, iters, _vp(d_F_out), _vp(d_inlier), _vp(d_n_inliers), _vp(d_best_hyp),
                                         _vp(d_status), _vp(d_summary), _vp(stream)))
+
+
+def homography_sample(n, max_hyp, h):
+    """``(H, idx)``: the hypothesis count of a set of ``n`` matches and the four ascending match indices of hypothesis
+    ``h`` (sfm_homography_sample; host only).  ``idx`` is four times -1 when ``h`` is not in ``0 .. H - 1``."""
+    idx = np.full(4, -1, dtype=np.int32)
+    count = int(load().sfm_homography_sample(int(n), int(max_hyp), int(h), iptr(idx)))
+    return count, tuple(int(i) for i in idx)
+
+
+def homography_ransac(set_ptr, left, right, max_err2, max_hyp=0, iters=2, outputs=HOMOGRAPHY_OUTPUTS):
+    """Robust homography of every set of matches (sfm_homography_ransac): stratified four-point hypotheses scored by their
+    inlier count under a transfer error of ``max_err2`` (pixels squared) in both images, then up to ``iters`` refits over
+    the inliers.  The arrays and options are those of ``twoview_ransac`` (``check_twoview_sets``, ``check_twoview``).
+    Returns ``H (S, 3, 3)`` of Frobenius norm 1, mapping left to right (zeros without a model), ``inlier (M,) uint8,
+    n_inliers (S,), best_hyp (S,), status (S,) of HOMOGRAPHY_* bits, summary (6,) int64`` in the order of
+    ``HOMOGRAPHY_SUMMARY``; an output not named in ``outputs`` is not computed and comes back as None."""
+    set_ptr, left, right = check_twoview_sets(set_ptr, left, right)
+    max_err2, max_hyp, iters = check_twoview(max_err2, max_hyp, iters)
+    unknown = set(outputs) - set(HOMOGRAPHY_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (HOMOGRAPHY_OUTPUTS, sorted(unknown)))
+    n_sets, n_obs = set_ptr.shape[0] - 1, left.shape[1]
+    H = np.zeros((n_sets, 3, 3))
+    o = _ransac_outputs(n_sets, n_obs)
+    ptrs = [p if name in outputs else None for name, p in zip(HOMOGRAPHY_OUTPUTS, _ransac_pointers(o))]
+    check(load().sfm_homography_ransac(n_sets, iptr(set_ptr), n_obs, dptr(left), dptr(right), max_err2, max_hyp, iters, dptr(H), *ptrs))
+    return (H,) + tuple(getattr(o, name) if name in outputs else None for name in HOMOGRAPHY_OUTPUTS)
+
+
+def homography_ransac_dev(set_ptr, n_obs, d_left, d_right, max_err2, max_hyp=0, iters=2, d_H_out=0, d_inlier=0, d_n_inliers=0,
+                          d_best_hyp=0, d_status=0, d_summary=0, stream=0):
+    """``homography_ransac`` on device pointers and a caller's stream (sfm_homography_ransac_dev); ``set_ptr`` stays a host
+    array, optional arrays are 0."""
+    set_ptr = np.ascontiguousarray(set_ptr, dtype=np.int32).ravel()
+    max_err2, max_hyp, iters = check_twoview(max_err2, max_hyp, iters)
+    check(load().sfm_homography_ransac_dev(set_ptr.shape[0] - 1, iptr(set_ptr), int(n_obs), _vp(d_left), _vp(d_right), max_err2,
+                                           max_hyp, iters, _vp(d_H_out), _vp(d_inlier), _vp(d_n_inliers), _vp(d_best_hyp),
+                                           _vp(d_status), _vp(d_summary), _vp(stream)))
 
 
 def pnp_nonlinear(uv_pix, pts_h, intrinsic, rot0, loc0, lam, iters, quirks=QUIRKS_REFERENCE):

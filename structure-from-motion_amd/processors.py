@@ -398,6 +398,59 @@ class HipEpipolarMixin:
         self.fund_mat = F / F[2][2]
         return inliers
 
+    def determine_homography_robust(self, matched_pairs, max_transfer_px=2.0, max_hyp=128, iteration=2):
+        """The homography of one set of matches by the robust estimator (``native.homography_ransac``; no reference
+        counterpart): stratified four-point hypotheses without a random number, scored by the transfer error in both
+        images (``max_transfer_px`` pixels), the winner refitted over its inliers.  Sets ``self.homography`` (left to right)
+        to the matrix divided by ``H[2][2]`` and returns the inlier indices (a list); without a model ``homography`` is
+        left as it was and the list is empty.  ``homography_last`` keeps hypothesis, status and the summary."""
+        if not float(max_transfer_px) >= 0.0:
+            raise ValueError("max_transfer_px must be >= 0, got {!r}".format(max_transfer_px))
+        set_ptr, left, right = self._twoview_sets([matched_pairs])
+        H, inlier, _n, best, status, summary = native.homography_ransac(set_ptr, left, right, float(max_transfer_px) ** 2,
+                                                                        max_hyp, iteration)
+        self.homography_last = {"hypothesis": int(best[0]), "status": int(status[0]), "summary": summary}
+        if status[0] & (native.HOMOGRAPHY_TOO_FEW | native.HOMOGRAPHY_NO_MODEL):
+            return []
+        self.homography = H[0] / H[0][2][2]
+        return np.flatnonzero(inlier).tolist()
+
+    def classify_matches(self, list_of_matched_pairs, max_px=2.0, max_hyp=128, iteration=2, planar_ratio=0.8):
+        """Both two-view models of several sets of matches and a verdict per set (no reference counterpart): ONE
+        ``native.twoview_ransac`` call and ONE ``native.homography_ransac`` call over the same arrays, both at ``max_px``
+        pixels (Sampson distance and transfer error).  Returns one dict per set: ``F`` and ``H`` (3, 3) of Frobenius norm 1
+        (zeros without the model), ``F_inliers`` and ``H_inliers`` (lists of indices), ``F_status``, ``H_status`` and
+        ``verdict``:
+          ``"none"``        neither model stands;
+          ``"degenerate"``  the homography stands and either the fundamental matrix does not, or
+                            ``n_H >= planar_ratio * n_F`` of their inlier counts: the matches are explained by a plane or a
+                            pure rotation, and the fundamental matrix is not to be trusted;
+          ``"general"``     otherwise.
+        ``planar_ratio`` is the caller's option; its default 0.8 is the value COLMAP uses for the same test
+        (``max_H_inlier_ratio``), not a constant measured by this project.  ``twoview_last`` and ``homography_last`` keep
+        the hypotheses, statuses and summaries of the two calls."""
+        if not float(max_px) >= 0.0:
+            raise ValueError("max_px must be >= 0, got {!r}".format(max_px))
+        set_ptr, left, right = self._twoview_sets(list_of_matched_pairs)
+        F, f_in, f_n, f_best, f_status, f_summary = native.twoview_ransac(set_ptr, left, right, float(max_px) ** 2, max_hyp, iteration)
+        H, h_in, h_n, h_best, h_status, h_summary = native.homography_ransac(set_ptr, left, right, float(max_px) ** 2, max_hyp, iteration)
+        self.twoview_last = {"hypothesis": f_best.tolist(), "status": f_status.tolist(), "summary": f_summary}
+        self.homography_last = {"hypothesis": h_best.tolist(), "status": h_status.tolist(), "summary": h_summary}
+        out = []
+        for s in range(set_ptr.shape[0] - 1):
+            lo, hi = set_ptr[s], set_ptr[s + 1]
+            has_f, has_h = bool(f_best[s] >= 0), bool(h_best[s] >= 0)
+            if not (has_f or has_h):
+                verdict = "none"
+            elif has_h and (not has_f or h_n[s] >= planar_ratio * f_n[s]):
+                verdict = "degenerate"
+            else:
+                verdict = "general"
+            out.append({"F": F[s], "H": H[s], "F_inliers": np.flatnonzero(f_in[lo:hi]).tolist(),
+                        "H_inliers": np.flatnonzero(h_in[lo:hi]).tolist(), "F_status": int(f_status[s]),
+                        "H_status": int(h_status[s]), "verdict": verdict})
+        return out
+
 
 class HipEpipolarProcessor(HipEpipolarMixin):
     """Standalone EpipolarProcessor (constructor of epipolar_processor.py:13-20)."""
@@ -405,6 +458,7 @@ class HipEpipolarProcessor(HipEpipolarMixin):
     def __init__(self, ransac_config):
         self.fund_mat = np.identity(3)
         self.esse_mat = np.identity(3)
+        self.homography = np.identity(3)
         self.ransac = ransac_config
 
 
