@@ -1025,6 +1025,51 @@ int sfm_match(sfm_desc_set* query, int n_refs, sfm_desc_set* const* refs, int mo
 int sfm_match_dev(sfm_desc_set* query, int n_refs, sfm_desc_set* const* refs, int mode, int* d_best_idx, float* d_best_dist,
                   int* d_second_idx, float* d_second_dist, uint8_t* d_mutual, void* hip_stream);
 
+/* ---- guided matching: the descriptor search gated by a verified two-view model (no reference counterpart) ----------
+ * sfm_match with the candidates of every query restricted to the train keys that the model of the pair of views admits.
+ * Inputs: the query set with its key coordinates (qx[i], qy[i]); n_refs reference sets with theirs (rx[r][t], ry[r][t]);
+ * per reference r a gate kind[r] and a row-major 3x3 model model[9 r .. 9 r + 8] in pixel coordinates; one max_err2 in
+ * pixels squared.  As in sfm_twoview_verify_pairs(ref, que), the reference key is LEFT and the query key is RIGHT.
+ *   SFM_GUIDE_NONE         every pair is admitted: all outputs of that reference equal sfm_match's bit for bit; its
+ *                          model and coordinates are not read (they may be NULL);
+ *   SFM_GUIDE_FUNDAMENTAL  (train t, query i) is admitted iff the squared Sampson distance under F = model is finite and
+ *                          <= max_err2: twoview_inlier(F, x_t, y_t, x_i, y_i, max_err2), the test sfm_twoview_ransac uses;
+ *   SFM_GUIDE_HOMOGRAPHY   the model is H, left to right; G = adj H by cofactors, each as fma(a, b, -(c d)):
+ *                            G0 = fma(H4, H8, -(H5 H7))  G1 = fma(H2, H7, -(H1 H8))  G2 = fma(H1, H5, -(H2 H4))
+ *                            G3 = fma(H5, H6, -(H3 H8))  G4 = fma(H0, H8, -(H2 H6))  G5 = fma(H2, H3, -(H0 H5))
+ *                            G6 = fma(H3, H7, -(H4 H6))  G7 = fma(H1, H6, -(H0 H7))  G8 = fma(H0, H4, -(H1 H3))
+ *                          (sfm_homography_adjugate), not scaled, computed once on the host; the pair is admitted iff the
+ *                          transfer error in each image is finite and <= max_err2: homography_inlier((H, G), ...), the
+ *                          test sfm_homography_ransac uses.  This is the test with (H, adj H): the estimator formed its
+ *                          own G from the normalised matrix, so a match at the threshold may differ from its mask.
+ * Per (reference r, query i), at [r * n_query + i], among the ADMITTED train keys only: the best and second-best index
+ * and float32 distance by sfm_match's order (distance, train index); the mutual flag, where the best query of a train
+ * key is taken among the queries admitted with it (admission is a property of the pair, so crossCheck stays
+ * symmetric); n_admitted, the int32 number of admitted train keys.  No admitted key: index -1, distance +inf, mutual 0,
+ * count 0.  A NaN coordinate admits nothing (the tests require a finite error).
+ * Every output is optional and the non-NULL ones select the work: the cross-check runs only when mutual is wanted, the
+ * counts are kept only when n_admitted is.  There is no mode argument.  SFM_E_SHAPE, with nothing launched: a NaN or
+ * negative max_err2, an unknown kind, a non-finite model entry of a gated reference, a metric or dimension mismatch, an
+ * empty reference set, missing coordinates of a gated pair.  Counts are integers and there is no floating-point
+ * atomic: the bits of a (reference, query) row depend on that reference and that query only. */
+#define SFM_GUIDE_NONE         0
+#define SFM_GUIDE_FUNDAMENTAL  1
+#define SFM_GUIDE_HOMOGRAPHY   2
+/* Blocking host form: coordinates are HOST arrays (qx, qy of query n; rx[r], ry[r] of the reference's n), copied up;
+ * outputs [n_refs][query n], caller-allocated. */
+int sfm_match_guided(sfm_desc_set* query, const double* qx, const double* qy, int n_refs, sfm_desc_set* const* refs,
+                     const double* const* rx, const double* const* ry, const int* kind /*[n_refs]*/,
+                     const double* model /*[n_refs][9]*/, double max_err2, int* best_idx, float* best_dist, int* second_idx,
+                     float* second_dist, uint8_t* mutual, int* n_admitted);
+/* device form: d_qx, d_qy, the entries of the HOST arrays d_rx[n_refs], d_ry[n_refs] and the outputs are DEVICE
+ * pointers; kind and model are host arrays.  Enqueues on hip_stream (NULL = the library stream) and returns. */
+int sfm_match_guided_dev(sfm_desc_set* query, const double* d_qx, const double* d_qy, int n_refs, sfm_desc_set* const* refs,
+                         const double* const* d_rx, const double* const* d_ry, const int* kind, const double* model,
+                         double max_err2, int* d_best_idx, float* d_best_dist, int* d_second_idx, float* d_second_dist,
+                         uint8_t* d_mutual, int* d_n_admitted, void* hip_stream);
+/* G = adj H as above (host; needs no device). */
+int sfm_homography_adjugate(const double H[9], double G[9]);
+
 /* ---- SIFT detection: ViewProcessor.__extract_keys (view_processor.py:151-164, 199-202) --------------------------
  * cv.SIFT_create().detectAndCompute(img, None) by the contract of INTEGRATION.md 'SIFT detection' (firstOctave -1,
  * nfeatures 0, no mask): keypoints sorted by (x, y asc; size desc; angle asc; response desc; octave desc) without
@@ -1143,6 +1188,20 @@ int sfm_track_pairs(sfm_track_store* s, int ref, int que, int* n, int* r_idx, in
  * the two steps; the coordinates stay on the device. */
 int sfm_twoview_verify_pairs(sfm_track_store* s, int ref, int que, double max_err2, int max_hyp, int iters, int* n, int* r_idx,
                            int* q_idx, unsigned char* inlier, double F_out[9], int* best_hyp, int* status);
+/* (The next two work on a track store; like sfm_obs_* and sfm_twoview_verify_pairs they are not part of the KeyTrack /
+ * KeyTracker surface the sfm_track_* names cover.)
+ * sfm_match_guided_dev with the coordinates the store already holds: `query` is the descriptor set of view que_view,
+ * refs[r] that of view ref_views[r] (any views of the store, in any order; each set has its view's key count).  No
+ * coordinate is uploaded.  Outputs are DEVICE pointers; follows the store's stream rule (above). */
+int sfm_match_guided_track(sfm_track_store* s, int que_view, sfm_desc_set* query, int n_refs, const int* ref_views,
+                           sfm_desc_set* const* refs, const int* kind, const double* model, double max_err2, int* d_best_idx,
+                           float* d_best_dist, int* d_second_idx, float* d_second_dist, uint8_t* d_mutual, int* d_n_admitted,
+                           void* hip_stream);
+/* Replace the matches between the views ref and que by n pairs (host arrays): row que of table[ref] and row ref of
+ * table[que] are set to -1, then table[ref][que, r_idx[k]] = q_idx[k] and table[que][ref, q_idx[k]] = r_idx[k].  An index
+ * out of range or repeated on either side, ref == que, or a table without the row returns SFM_E_SHAPE and writes
+ * nothing.  The only way a guided result enters the tables.  Blocking. */
+int sfm_match_guided_set_pairs(sfm_track_store* s, int ref, int que, int n, const int* r_idx, const int* q_idx);
 /* KeyTrack.update_usage: table[view][view, keys[i]] = tri[i] (host arrays).  A key given twice takes the LAST value,
  * as NumPy's fancy assignment does; a key outside [0, n) returns SFM_E_SHAPE and writes nothing. */
 int sfm_track_update_usage(sfm_track_store* s, int view, int n, const int* keys, const int* tri);

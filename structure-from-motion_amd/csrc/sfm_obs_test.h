@@ -79,4 +79,18 @@ __host__ __device__ inline bool homography_inlier(const double* HG, double xl, d
   return (bool)((int)homography_half(HG, xl, yl, xr, yr, max_err2) & (int)homography_half(HG + 9, xr, yr, xl, yl, max_err2));
 }
 
+// G = adj H by cofactors, not scaled (H G = det H . I): the right-to-left half of a model (H, G) for a caller that
+// has H alone (guided matching).  Each cofactor is fma(a, b, -(c * d)) in the operand order written here.
+__host__ __device__ inline void homography_adjugate(const double* H, double* G) {
+  G[0] = __builtin_fma(H[4], H[8], -(H[5] * H[7]));
+  G[1] = __builtin_fma(H[2], H[7], -(H[1] * H[8]));
+  G[2] = __builtin_fma(H[1], H[5], -(H[2] * H[4]));
+  G[3] = __builtin_fma(H[5], H[6], -(H[3] * H[8]));
+  G[4] = __builtin_fma(H[0], H[8], -(H[2] * H[6]));
+  G[5] = __builtin_fma(H[2], H[3], -(H[0] * H[5]));
+  G[6] = __builtin_fma(H[3], H[7], -(H[4] * H[6]));
+  G[7] = __builtin_fma(H[1], H[6], -(H[0] * H[7]));
+  G[8] = __builtin_fma(H[0], H[4], -(H[1] * H[3]));
+}
+
 }  // namespace sfm

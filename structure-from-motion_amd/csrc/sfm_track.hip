@@ -283,6 +283,23 @@ __global__ void track_usage_write_kernel(const ViewDesc* __restrict__ views, int
   last[k] = -1;                     // only the winner of a key resets it: the scratch is all -1 again afterwards
 }
 
+// set_pairs: row que of table[ref] and row ref of table[que] to -1, then the pairs (the host has checked the indices:
+// in range, none repeated on either side, so every write has its own cell).
+__global__ void track_pairs_clear_kernel(const ViewDesc* __restrict__ views, int ref, int que) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const ViewDesc r = views[ref], q = views[que];
+  if (i < r.n) r.table[(size_t)que * r.n + i] = -1;
+  if (i < q.n) q.table[(size_t)ref * q.n + i] = -1;
+}
+__global__ void track_pairs_write_kernel(const ViewDesc* __restrict__ views, int ref, int que, int n, const int* __restrict__ r_idx,
+                                         const int* __restrict__ q_idx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const ViewDesc r = views[ref], q = views[que];
+  r.table[(size_t)que * r.n + r_idx[i]] = q_idx[i];
+  q.table[(size_t)ref * q.n + q_idx[i]] = r_idx[i];
+}
+
 // ---- observation list ------------------------------------------------------------------------------------------
 __global__ void obs_init_kernel(size_t cells, int* __restrict__ min_key, int* __restrict__ max_key) {
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -778,6 +795,66 @@ int sfm_track_update_usage(sfm_track_store* s, int view, int n, const int* keys,
   int* last = static_cast<int*>(s->usage_last.p);
   track_usage_last_kernel<<<blocks, 256, 0, st>>>(n, dk.p, last);
   track_usage_write_kernel<<<blocks, 256, 0, st>>>(s->d_views, view, n, dk.p, dt.p, last);
+  SFM_HIP(hipGetLastError());
+  return stream_sync(st);
+}
+
+int sfm_match_guided_track(sfm_track_store* s, int que_view, sfm_desc_set* query, int n_refs, const int* ref_views,
+                           sfm_desc_set* const* refs, const int* kind, const double* model, double max_err2, int* d_best_idx,
+                           float* d_best_dist, int* d_second_idx, float* d_second_dist, uint8_t* d_mutual, int* d_n_admitted,
+                           void* hip_stream) {
+  SFM_TRY(ensure_init());
+  if (!s || !query) return SFM_E_HANDLE;
+  SFM_TRY(valid_view(s, que_view, "sfm_match_guided_track"));
+  if (n_refs < 0 || (n_refs > 0 && (!ref_views || !refs))) { set_error("sfm_match_guided_track: bad reference list"); return SFM_E_SHAPE; }
+  int64_t cnt = 0;
+  SFM_TRY(sfm_desc_info(query, SFM_DESC_INFO_N, &cnt));
+  const View& qv = s->views[que_view];
+  if (cnt != qv.n) { set_error("sfm_match_guided_track: %d descriptors for a view of %d keys", (int)cnt, qv.n); return SFM_E_SHAPE; }
+  std::vector<const double*> rx((size_t)n_refs), ry((size_t)n_refs);
+  for (int r = 0; r < n_refs; ++r) {
+    SFM_TRY(valid_view(s, ref_views[r], "sfm_match_guided_track"));
+    if (!refs[r]) return SFM_E_HANDLE;
+    const View& w = s->views[ref_views[r]];
+    SFM_TRY(sfm_desc_info(refs[r], SFM_DESC_INFO_N, &cnt));
+    if (cnt != w.n) { set_error("sfm_match_guided_track: %d descriptors for view %d of %d keys", (int)cnt, ref_views[r], w.n); return SFM_E_SHAPE; }
+    rx[r] = w.xy;
+    ry[r] = w.xy + w.n;
+  }
+  hipStream_t st = pick(hip_stream);
+  SFM_TRY(note_stream(s, st));
+  return sfm_match_guided_dev(query, qv.xy, qv.xy + qv.n, n_refs, refs, rx.data(), ry.data(), kind, model, max_err2, d_best_idx,
+                              d_best_dist, d_second_idx, d_second_dist, d_mutual, d_n_admitted, st);
+}
+
+int sfm_match_guided_set_pairs(sfm_track_store* s, int ref, int que, int n, const int* r_idx, const int* q_idx) {
+  SFM_TRY(ensure_init());
+  if (!s) return SFM_E_HANDLE;
+  SFM_TRY(valid_view(s, ref, "sfm_match_guided_set_pairs"));
+  SFM_TRY(valid_view(s, que, "sfm_match_guided_set_pairs"));
+  if (ref == que) { set_error("sfm_match_guided_set_pairs: view %d against itself", ref); return SFM_E_SHAPE; }
+  const View& rv = s->views[ref];
+  const View& qv = s->views[que];
+  if (rv.rows <= que || qv.rows <= ref) { set_error("sfm_match_guided_set_pairs: tables %d and %d have no rows for each other", ref, que); return SFM_E_SHAPE; }
+  if (n < 0 || (n > 0 && (!r_idx || !q_idx))) { set_error("sfm_match_guided_set_pairs: bad sizes n=%d", n); return SFM_E_SHAPE; }
+  std::vector<char> seen_r((size_t)rv.n, 0), seen_q((size_t)qv.n, 0);
+  for (int i = 0; i < n; ++i) {
+    if (r_idx[i] < 0 || r_idx[i] >= rv.n || q_idx[i] < 0 || q_idx[i] >= qv.n) {
+      set_error("sfm_match_guided_set_pairs: pair %d (%d, %d) outside views of %d and %d keys", i, r_idx[i], q_idx[i], rv.n, qv.n);
+      return SFM_E_SHAPE;
+    }
+    if (seen_r[r_idx[i]] || seen_q[q_idx[i]]) { set_error("sfm_match_guided_set_pairs: pair %d (%d, %d) repeats a key", i, r_idx[i], q_idx[i]); return SFM_E_SHAPE; }
+    seen_r[r_idx[i]] = seen_q[q_idx[i]] = 1;
+  }
+  hipStream_t st = ctx().stream;
+  SFM_TRY(settle(s));
+  DevBuf<int> dr, dq;
+  SFM_TRY(dr.upload(r_idx, (size_t)n, st));
+  SFM_TRY(dq.upload(q_idx, (size_t)n, st));
+  s->upload_bytes += 8ll * n;
+  const int widest = rv.n > qv.n ? rv.n : qv.n;
+  if (widest > 0) track_pairs_clear_kernel<<<(unsigned)((widest + 255) / 256), 256, 0, st>>>(s->d_views, ref, que);
+  if (n > 0) track_pairs_write_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(s->d_views, ref, que, n, dr.p, dq.p);
   SFM_HIP(hipGetLastError());
   return stream_sync(st);
 }

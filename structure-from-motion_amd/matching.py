@@ -50,6 +50,20 @@ def filter_matches(best_idx, best_dist, second_idx, second_dist, mutual, is_knn_
     return q, best_idx[q].astype(np.int64), best_dist[q]
 
 
+def filter_guided(best_idx, best_dist, second_dist, mutual, ratio=RATIO):
+    """The match list of one (reference view, query view) pair after a guided match (``native.match_guided``), as
+    (query index, train index) in query order: query ``i`` is kept iff it has a best neighbour, is mutual, and either has
+    no second neighbour (``second_dist`` = inf: the gate left one candidate) or ``float64(d0) < ratio * float64(d1)``.
+    A zero second distance keeps nothing for that query and raises nothing; ``filter_matches`` and its quirks
+    (Q14 - Q16) are not involved."""
+    best_idx = np.asarray(best_idx)
+    d0 = np.asarray(best_dist, dtype=np.float32).astype(np.float64)
+    d1 = np.asarray(second_dist, dtype=np.float32).astype(np.float64)
+    keep = (best_idx >= 0) & np.asarray(mutual, dtype=bool) & (np.isposinf(d1) | (d0 < float(ratio) * d1))
+    q = np.flatnonzero(keep)
+    return q, best_idx[q].astype(np.int64)
+
+
 def dedup_kept(train_idx, dist):
     """Positions (into the filtered list) of the matches the duplicate loop of key_tracker.py:276-291 keeps, in the
     order of its output list.

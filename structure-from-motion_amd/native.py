@@ -33,6 +33,7 @@ LM_STOP_NAMES = ("max_trials", "ftol", "xtol", "gtol", "lambda_max", "breakdown"
 LM_MIN_GAIN = 1e-3
 MATCH_L2, MATCH_HAMMING = 0, 1
 MATCH_KNN2, MATCH_NN1, MATCH_MUTUAL = 0, 1, 2
+GUIDE_NONE, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY = 0, 1, 2
 DESC_U8, DESC_F32 = 0, 1
 DESC_INFO_N, DESC_INFO_DIM, DESC_INFO_EXACT, DESC_INFO_UPLOAD_BYTES = 1, 2, 3, 4
 SIFT_INFO_N, SIFT_INFO_N_OCTAVES, SIFT_INFO_N_PRE, SIFT_INFO_N_LAYERS, SIFT_INFO_KEEPS_PYRAMID = 1, 2, 3, 4, 5
@@ -181,6 +182,9 @@ SIGNATURES = {
     "sfm_desc_info": [vp, ci, _lp],
     "sfm_match": [vp, ci, _pp, ci, _ip, fp, _ip, fp, ctypes.POINTER(ctypes.c_uint8)],
     "sfm_match_dev": [vp, ci, _pp, ci, vp, vp, vp, vp, vp, vp],
+    "sfm_match_guided": [vp, _dp, _dp, ci, _pp, _pp, _pp, _ip, _dp, cd, vp, vp, vp, vp, vp, vp],
+    "sfm_match_guided_dev": [vp, vp, vp, ci, _pp, _pp, _pp, _ip, _dp, cd, vp, vp, vp, vp, vp, vp, vp],
+    "sfm_homography_adjugate": [_dp, _dp],
     "sfm_sift_detect": [vp, ci, ci, ci, i64, ctypes.POINTER(SiftParams), _pp],
     "sfm_sift_result_info": [vp, ci, _lp],
     "sfm_sift_result_level_shape": [vp, ci, _ip, _ip],
@@ -203,6 +207,8 @@ SIGNATURES = {
     "sfm_track_pairs_dev": [vp, ci, ci, vp, vp, vp, vp, vp, vp],
     "sfm_track_pairs": [vp, ci, ci, _ip, _ip, _ip, _dp, _dp],
     "sfm_track_update_usage": [vp, ci, ci, _ip, _ip],
+    "sfm_match_guided_track": [vp, ci, vp, ci, _ip, _pp, _ip, _dp, cd, vp, vp, vp, vp, vp, vp, vp],
+    "sfm_match_guided_set_pairs": [vp, ci, ci, ci, _ip, _ip],
     "sfm_track_constructed": [vp, ci, _ip, _ip, _ip],
     "sfm_track_unconstructed": [vp, ci, _ip, _ip],
     "sfm_track_copy_table": [vp, ci, _ip],
@@ -1601,6 +1607,110 @@ def match_dev(query, refs, mode, d_best_idx, d_best_dist, d_second_idx, d_second
                                _vp(d_second_dist), _vp(d_mutual), _vp(stream)))
 
 
+# ---- guided matching (sfm_match_guided*; no reference counterpart) ---------------------------------------------------
+GUIDE_NAMES = {"none": GUIDE_NONE, "fundamental": GUIDE_FUNDAMENTAL, "homography": GUIDE_HOMOGRAPHY}
+GUIDED_OUTPUTS = ("best_idx", "best_dist", "second_idx", "second_dist", "mutual", "n_admitted")
+_GUIDED_DTYPES = (np.int32, np.float32, np.int32, np.float32, np.uint8, np.int32)
+
+
+def homography_adjugate(H):
+    """adj H by the cofactor formula of include/sfm_hip.h ('guided matching'), as a (3, 3) array; runs on the host."""
+    H = f64(H).reshape(9)
+    G = np.zeros(9)
+    check(load().sfm_homography_adjugate(dptr(H), dptr(G)))
+    return G.reshape(3, 3)
+
+
+def check_guided(n_refs, kinds, models, max_err2):
+    """The arguments of a guided match as the library takes them: ``(kind (n_refs,) int32, model (n_refs, 9) float64,
+    max_err2)``.  ``kinds`` holds GUIDE_* values or their names; ``models`` one (3, 3) matrix per reference (``None`` for
+    an ungated one).  ValueError for what the library would answer with SFM_E_SHAPE."""
+    kinds, models = list(kinds), list(models)
+    if len(kinds) != n_refs or len(models) != n_refs:
+        raise ValueError("guided match: %d references, %d kinds, %d models" % (n_refs, len(kinds), len(models)))
+    max_err2 = float(max_err2)
+    if not max_err2 >= 0.0:
+        raise ValueError("guided match: max_err2 must be >= 0, got %r" % max_err2)
+    kind = np.zeros(max(n_refs, 1), dtype=np.int32)
+    model = np.zeros((max(n_refs, 1), 9))
+    for r in range(n_refs):
+        k = GUIDE_NAMES.get(kinds[r], kinds[r]) if isinstance(kinds[r], str) else kinds[r]
+        if k not in (GUIDE_NONE, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY):
+            raise ValueError("guided match: reference %d has the unknown gate %r" % (r, kinds[r]))
+        kind[r] = k
+        if k == GUIDE_NONE:
+            continue
+        m = np.asarray(models[r], dtype=np.float64)
+        if m.size != 9 or not np.all(np.isfinite(m)):
+            raise ValueError("guided match: the model of reference %d must be a finite 3x3 matrix" % r)
+        model[r] = m.reshape(9)
+    return kind, model, max_err2
+
+
+def _key_xy(xy, n, who):
+    xy = np.asarray(xy, dtype=np.float64)
+    if xy.shape != (n, 2):
+        raise ValueError("%s: key coordinates of shape %s for %d descriptors" % (who, xy.shape, n))
+    return np.ascontiguousarray(xy[:, 0]), np.ascontiguousarray(xy[:, 1])
+
+
+def match_guided(query, query_xy, refs, ref_xy, kinds, models, max_err2, outputs=GUIDED_OUTPUTS):
+    """``match`` with the candidates of every query restricted to the train keys its pair's model admits
+    (sfm_match_guided; the rule is in include/sfm_hip.h, 'guided matching').
+
+    ``query_xy`` is (query.n, 2); ``ref_xy[r]`` (refs[r].n, 2), or ``None`` for an ungated reference; ``kinds`` /
+    ``models`` as ``check_guided`` takes them; the reference key is left, the query key right.  Returns a dict of the
+    ``outputs`` asked for, each (len(refs), query.n): ``best_idx`` / ``second_idx`` int32, ``best_dist`` / ``second_dist``
+    float32, ``mutual`` bool, ``n_admitted`` int32.  What is not asked for is not computed."""
+    refs, ref_xy = list(refs), list(ref_xy)
+    nr, nq = len(refs), query.n
+    unknown = [o for o in outputs if o not in GUIDED_OUTPUTS]
+    if unknown:
+        raise ValueError("guided match: unknown outputs %s" % unknown)
+    if len(ref_xy) != nr:
+        raise ValueError("guided match: %d references, %d coordinate arrays" % (nr, len(ref_xy)))
+    kind, model, max_err2 = check_guided(nr, kinds, models, max_err2)
+    qx, qy = _key_xy(query_xy, nq, "guided match (query)")
+    keep = [qx, qy]
+    rx, ry = (_dp * max(nr, 1))(), (_dp * max(nr, 1))()
+    for r in range(nr):
+        if ref_xy[r] is None:
+            if kind[r] != GUIDE_NONE:
+                raise ValueError("guided match: reference %d has a gate and no coordinates" % r)
+            continue
+        x, y = _key_xy(ref_xy[r], refs[r].n, "guided match (reference %d)" % r)
+        keep += [x, y]
+        rx[r], ry[r] = dptr(x), dptr(y)
+    out = {name: np.zeros((nr, nq), dtype=dt) for name, dt in zip(GUIDED_OUTPUTS, _GUIDED_DTYPES) if name in outputs}
+    ptrs = [out[name].ctypes.data_as(vp) if name in out else None for name in GUIDED_OUTPUTS]
+    handles = (vp * max(nr, 1))(*[r._h for r in refs])
+    check(load().sfm_match_guided(query._h, dptr(qx), dptr(qy), nr, handles, ctypes.cast(rx, _pp), ctypes.cast(ry, _pp), iptr(kind),
+                                  dptr(model), max_err2, *ptrs))
+    if "mutual" in out:
+        out["mutual"] = out["mutual"].astype(bool)
+    return out
+
+
+def match_guided_dev(query, d_query_xy, refs, d_ref_xy, kinds, models, max_err2, d_best_idx=0, d_best_dist=0, d_second_idx=0,
+                     d_second_dist=0, d_mutual=0, d_n_admitted=0, stream=0):
+    """Stream-ordered form of ``match_guided``: ``d_query_xy`` = (d_x, d_y) and ``d_ref_xy[r]`` = (d_x, d_y) or ``None``
+    are device pointers (integers) of float64 arrays, the outputs device pointers of (len(refs), query.n) arrays; 0 = not
+    wanted."""
+    refs, d_ref_xy = list(refs), list(d_ref_xy)
+    nr = len(refs)
+    if len(d_ref_xy) != nr:
+        raise ValueError("guided match: %d references, %d coordinate arrays" % (nr, len(d_ref_xy)))
+    kind, model, max_err2 = check_guided(nr, kinds, models, max_err2)
+    rx, ry = (vp * max(nr, 1))(), (vp * max(nr, 1))()
+    for r in range(nr):
+        if d_ref_xy[r] is not None:
+            rx[r], ry[r] = int(d_ref_xy[r][0]), int(d_ref_xy[r][1])
+    handles = (vp * max(nr, 1))(*[r._h for r in refs])
+    check(load().sfm_match_guided_dev(query._h, _vp(d_query_xy[0]), _vp(d_query_xy[1]), nr, handles, rx, ry, iptr(kind), dptr(model),
+                                      max_err2, _vp(d_best_idx), _vp(d_best_dist), _vp(d_second_idx), _vp(d_second_dist),
+                                      _vp(d_mutual), _vp(d_n_admitted), _vp(stream)))
+
+
 # ---- SIFT detection (ViewProcessor.__extract_keys, view_processor.py:199-202) ------------------------------------
 def _sift_image(img):
     a = np.asarray(img)
@@ -1822,6 +1932,29 @@ class TrackStore:
                                                iptr(q), _u8ptr(inl), dptr(F), ctypes.byref(best), ctypes.byref(status)))
         n = n.value
         return r[:n], q[:n], inl[:n], F, int(best.value), int(status.value)
+
+    def match_guided(self, que_view, query, ref_views, refs, kinds, models, max_err2, d_best_idx=0, d_best_dist=0, d_second_idx=0,
+                     d_second_dist=0, d_mutual=0, d_n_admitted=0, stream=0):
+        """``match_guided_dev`` with the key coordinates the store holds (sfm_match_guided_track): ``query`` is the
+        DescriptorSet of view ``que_view``, ``refs[r]`` that of view ``ref_views[r]``; nothing is uploaded.  Outputs are
+        device pointers (integers) of (len(refs), query.n) arrays, 0 = not wanted."""
+        refs = list(refs)
+        views = i32(ref_views).reshape(-1)
+        if views.shape[0] != len(refs):
+            raise ValueError("guided match: %d reference views, %d descriptor sets" % (views.shape[0], len(refs)))
+        kind, model, max_err2 = check_guided(len(refs), kinds, models, max_err2)
+        handles = (vp * max(len(refs), 1))(*[r._h for r in refs])
+        check(self._lib.sfm_match_guided_track(self._h, int(que_view), query._h, len(refs), iptr(views), handles, iptr(kind),
+                                               dptr(model), max_err2, _vp(d_best_idx), _vp(d_best_dist), _vp(d_second_idx),
+                                               _vp(d_second_dist), _vp(d_mutual), _vp(d_n_admitted), _vp(stream)))
+
+    def set_pairs(self, ref, que, r_idx, q_idx):
+        """Replace the matches between the views ``ref`` and ``que`` by the pairs (r_idx[k], q_idx[k])
+        (sfm_match_guided_set_pairs); a bad or repeated index raises ValueError and writes nothing."""
+        r_idx, q_idx = i32(r_idx).reshape(-1), i32(q_idx).reshape(-1)
+        if r_idx.shape != q_idx.shape:
+            raise ValueError("set_pairs: %d reference keys, %d query keys" % (r_idx.shape[0], q_idx.shape[0]))
+        check(self._lib.sfm_match_guided_set_pairs(self._h, int(ref), int(que), r_idx.shape[0], iptr(r_idx), iptr(q_idx)))
 
     def pairs_dev(self, ref, que, d_count, d_r_idx, d_q_idx, d_ref_pts, d_que_pts, stream=0):
         check(self._lib.sfm_track_pairs_dev(self._h, int(ref), int(que), _vp(d_count), _vp(d_r_idx), _vp(d_q_idx), _vp(d_ref_pts),

@@ -452,6 +452,36 @@ class HipEpipolarMixin:
         return out
 
 
+    def guided_matches(self, query, query_xy, ref, ref_xy, model, max_px=2.0, ratio=matching.RATIO, metric=native.MATCH_L2):
+        """``guided_pairs`` over host arrays, for callers without a track store (no reference counterpart): ``query`` and
+        ``ref`` are (n, dim) descriptor arrays (or ``native.DescriptorSet`` objects, which are left open), ``query_xy`` and
+        ``ref_xy`` their (n, 2) key coordinates, ``model`` ``("fundamental", F)`` or ``("homography", H)`` with the reference
+        view left and the query view right.  One ``native.match_guided`` at ``max_px`` pixels, then
+        ``matching.filter_guided``.  Returns ``r_idx (1, n), q_idx (1, n)`` sorted by reference key; ``guided_last`` keeps
+        the number of admitted reference keys per query."""
+        if not float(max_px) >= 0.0:
+            raise ValueError("max_px must be >= 0, got {!r}".format(max_px))
+        kind, mat = _guided_model(model)
+        own = []
+        sets = []
+        for d in (query, ref):
+            if isinstance(d, native.DescriptorSet):
+                sets.append(d)
+            else:
+                sets.append(native.DescriptorSet(metric, d))
+                own.append(sets[-1])
+        try:
+            out = native.match_guided(sets[0], query_xy, [sets[1]], [ref_xy], [kind], [mat], float(max_px) ** 2,
+                                      outputs=("best_idx", "best_dist", "second_dist", "mutual", "n_admitted"))
+        finally:
+            for s in own:
+                s.close()
+        self.guided_last = {"n_admitted": out["n_admitted"][0]}
+        q, t = matching.filter_guided(out["best_idx"][0], out["best_dist"][0], out["second_dist"][0], out["mutual"][0], ratio)
+        order = np.argsort(t, kind="stable")
+        return t[order].reshape(1, -1).astype(int), q[order].reshape(1, -1).astype(int)
+
+
 class HipEpipolarProcessor(HipEpipolarMixin):
     """Standalone EpipolarProcessor (constructor of epipolar_processor.py:13-20)."""
 
@@ -1634,6 +1664,73 @@ def verify_pairs(tracker, ref_idx, que_idx, max_sampson_px=2.0, max_hyp=128, ite
     tracker.twoview_last = {"fund_mat": fund, "hypothesis": best, "status": status}
     num = r_idx.shape[0]
     return r_idx.reshape(1, num).astype(int), q_idx.reshape(1, num).astype(int), inlier.astype(bool)
+
+
+def _guided_model(model):
+    """(gate name, (3, 3) matrix) of a ``model`` argument of the guided-matching entry points."""
+    try:
+        kind, mat = model
+    except (TypeError, ValueError):
+        raise ValueError("model must be ('fundamental', F) or ('homography', H), got {!r}".format(model))
+    if kind not in ("fundamental", "homography"):
+        raise ValueError("model must be ('fundamental', F) or ('homography', H), got kind {!r}".format(kind))
+    mat = np.asarray(mat, dtype=np.float64)
+    if mat.shape != (3, 3):
+        raise ValueError("the {} model must be a (3, 3) matrix, got shape {}".format(kind, mat.shape))
+    return kind, mat
+
+
+def guided_pairs(tracker, ref_idx, que_idx, max_px=2.0, ratio=matching.RATIO, model=None, write=False, max_hyp=128, iteration=2):
+    """Guided matching of two views of a ``HipDeviceKeyTracker`` (no reference counterpart): the descriptor search
+    repeated with the candidates of every query key restricted to the reference keys a verified two-view model admits
+    within ``max_px`` pixels, so that a look-alike off the epipolar line no longer fails the ratio test.
+
+    ``model`` is ``("fundamental", F)`` or ``("homography", H)`` in pixel coordinates, the reference view left and the
+    query view right; with ``model=None`` the fundamental matrix comes from ``verify_pairs`` over the pairs the tables
+    hold, and ``None`` is returned when no model stands (``tracker.twoview_last`` keeps the status).  One
+    ``TrackStore.match_guided`` on the tracker's resident descriptor sets and coordinates (nothing goes up), then
+    ``matching.filter_guided``: mutual best neighbours among the admitted pairs that pass the ratio test (``ratio`` 0.7 is
+    the reference's constant) or have no admitted rival.  Returns ``r_idx (1, n), q_idx (1, n)`` sorted by reference key.
+    ``write=True`` replaces the matches of the two views in the device tables by these pairs (``TrackStore.set_pairs``)
+    and bumps their versions; nothing calls this on its own."""
+    n_views = len(tracker.track_list)
+    if ref_idx < 0 or que_idx < 0 or ref_idx >= n_views or que_idx >= n_views or ref_idx == que_idx:
+        print('{}:{} - invalid ref_idx {} or invalid que_idx {}'.format(
+            tracker.__class__.__name__, 'guided_pairs', ref_idx, que_idx))
+        return None
+    if not float(max_px) >= 0.0:
+        raise ValueError("max_px must be >= 0, got {!r}".format(max_px))
+    if model is None:
+        verify_pairs(tracker, ref_idx, que_idx, max_px, max_hyp, iteration)
+        if tracker.twoview_last["status"] & (native.TWOVIEW_TOO_FEW | native.TWOVIEW_NO_MODEL):
+            return None
+        model = ("fundamental", tracker.twoview_last["fund_mat"])
+    kind, mat = _guided_model(model)
+    sets = tracker.__dict__.get("_hip_desc", {})
+    if ref_idx not in sets or que_idx not in sets:
+        raise native.SfmHipError("guided_pairs: the descriptors of view {} or {} are not resident".format(ref_idx, que_idx))
+    ref_set, que_set = sets[ref_idx][1], sets[que_idx][1]
+    import torch
+    stream = tracker.__dict__.get("_guided_stream")
+    if stream is None:
+        stream = tracker.__dict__["_guided_stream"] = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        best = torch.empty((1, que_set.n), dtype=torch.int32, device="cuda")
+        d0 = torch.empty((1, que_set.n), dtype=torch.float32, device="cuda")
+        d1 = torch.empty((1, que_set.n), dtype=torch.float32, device="cuda")
+        mutual = torch.empty((1, que_set.n), dtype=torch.uint8, device="cuda")
+        tracker._store.match_guided(que_idx, que_set, [ref_idx], [ref_set], [kind], [mat], float(max_px) ** 2,
+                                    d_best_idx=best.data_ptr(), d_best_dist=d0.data_ptr(), d_second_dist=d1.data_ptr(),
+                                    d_mutual=mutual.data_ptr(), stream=stream.cuda_stream)
+        best, d0, d1, mutual = (t.cpu().numpy()[0] for t in (best, d0, d1, mutual))
+    q, t = matching.filter_guided(best, d0, d1, mutual, ratio)
+    order = np.argsort(t, kind="stable")
+    r_idx, q_idx = t[order], q[order]
+    if write:
+        tracker._store.set_pairs(ref_idx, que_idx, r_idx, q_idx)
+        tracker._versions[ref_idx] += 1
+        tracker._versions[que_idx] += 1
+    return r_idx.reshape(1, -1).astype(int), q_idx.reshape(1, -1).astype(int)
 
 
 class HipKeyPoint:

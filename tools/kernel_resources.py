@@ -39,7 +39,7 @@ names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), ca
                        text=True).stdout.splitlines()
 lines = []
 for r, n in zip(rows, names):
-    n = re.sub(r"^void ", "", n)
+    n = re.sub(r"^void ", "", n).replace("(anonymous namespace)::", "")
     n = re.sub(r"\(.*$", "", n).replace("sfm::", "")
     if r["file"] == "sfm_ba.hip" and not n.startswith(KEEP_BA):
         continue
