@@ -1070,6 +1070,76 @@ int sfm_match_guided_dev(sfm_desc_set* query, const double* d_qx, const double* 
 /* G = adj H as above (host; needs no device). */
 int sfm_homography_adjugate(const double H[9], double G[9]);
 
+/* ---- relative pose of a verified pair: four candidates, cheirality vote, parallax -------------------------------
+ * What follows a verified model of a pair of views (sfm_twoview_ransac: F; sfm_homography_ransac: H): the pose of the
+ * right view in the frame of the left one, for many sets of matches in one call.  A pose (R, t) means
+ * X_right = R X_left + t with |t| = 1.  The sets have the layout of sfm_twoview_ransac: set_ptr[n_sets + 1] on the host,
+ * left and right [2][M] pixel coordinates; obs_mask[M] (optional, NULL = every match) selects the matches that vote;
+ * model[n_sets][9] and kind[n_sets] (SFM_POSE_FROM_F or SFM_POSE_FROM_H) give the model of every set; K_left[9] and
+ * K_right[9], row-major, once per call, upper triangular with K[2][2] = 1 -- anything else is SFM_E_SHAPE.
+ *   1. Rays.  a = K_left^-1 (x_l, y_l, 1)^T and b = K_right^-1 (x_r, y_r, 1)^T by back substitution, third component 1.  A
+ *      match is SELECTED iff its mask byte is non-zero and a, b are finite.
+ *   2. Candidates from F.  E0 = K_right^T F K_left = U S V^T, s0 >= s1 >= s2; invalid unless E0 is finite and
+ *      s1 > 3 eps s0.  With W = [0 -1 0; 1 0 0; 0 0 1]: R_a = det(U W V^T) U W V^T, R_b = det(U W^T V^T) U W^T V^T;
+ *      t0 = +-U[:, 2] with its entry of largest magnitude positive (the lowest index on a tie).  The rotations are ordered
+ *      by trace, the larger first: R_0, R_1.  Candidate c = 2 i + j is (R_i, t0) for j = 0 and (R_i, -t0) for j = 1.
+ *   3. Candidates from H.  Hn = K_right^-1 H K_left; invalid unless Hn is finite and s2 > 3 eps s0 (the rank test of the
+ *      robust homography).  Hn is divided by s1.  Sign vote: over the selected matches the counts of b . (Hn a) > 0 and
+ *      < 0, integers; Hn is negated iff the negatives outnumber the positives.  With the eigenvalues l0 >= l1 >= l2 of
+ *      Hn^T Hn and their eigenvectors v0, v1, v2 (v0 x v1 = v2): invalid unless l0 - l2 > 0;
+ *      u+- = (sqrt(1 - l2) v0 +- sqrt(l0 - 1) v2) / sqrt(l0 - l2), the radicands clamped at 0; for each sign
+ *      U = [v1, u, v1 x u], W = [Hn v1, Hn u, (Hn v1) x (Hn u)], R = W U^T, n = v1 x u, T = (Hn - R) n (the four-solution
+ *      decomposition of Ma, Soatto, Kosecka and Sastry).  A rotation whose T is not finite or zero is invalid with both
+ *      its candidates.  The rotations are ordered by trace, the larger first; t0 = T / |T| takes the sign of step 2 and
+ *      the candidates 2 i + j are formed as there.  n_out is the normal of the winner, scaled and signed so that
+ *      Hn = R + (|T| t_out) n_out^T; zeros for kind F.
+ *   4. The test (pose_front, csrc/sfm_obs_test.h; one function for every stage and for sfm_twoview_pose_test).  For a
+ *      candidate (R, t) and a selected match: a' = R a; p = a'.a', q = b.b, r = a'.b, d = p q - r r;
+ *      m1 = r (b.t) - q (a'.t), m2 = p (b.t) - r (a'.t): the numerators of the two midpoint depths over the common
+ *      denominator d.  IN FRONT iff d, m1, m2 are finite and d > 0, m1 > 0, m2 > 0; no division.  HAS PARALLAX iff in
+ *      front and not (r > 0 and r r > cos2_min p q).  cos2_min is the squared cosine of the caller's minimum triangulation
+ *      angle, in [0, 1]; NaN or a value outside is SFM_E_SHAPE.  In the operation order of the function:
+ *        a'_i = fma(R[3i], a0, fma(R[3i+1], a1, R[3i+2]));  p = fma(a'0, a'0, fma(a'1, a'1, a'2 a'2));
+ *        q = fma(b0, b0, fma(b1, b1, 1));  r = fma(a'0, b0, fma(a'1, b1, a'2));  d = fma(p, q, -(r r));
+ *        bt = fma(b0, t0, fma(b1, t1, t2));  at = fma(a'0, t0, fma(a'1, t1, a'2 t2));
+ *        m1 = fma(r, bt, -(q at));  m2 = fma(p, bt, -(r at));  parallax: not (r > 0 and r r > cos2_min (p q)).
+ *   5. Score, lexicographic: the number of selected matches in front (an integer), then the lower candidate number.  A
+ *      winner needs a count of at least 1, otherwise SFM_POSE_NO_POSE.
+ *   6. Status bits as below.  min_parallax >= 0 is an integer option; a negative one is SFM_E_SHAPE.
+ *   7. Outputs, all optional but R_out and t_out: R_out[n_sets][9], t_out[n_sets][3] (zeros without a winner), n_out
+ *      [n_sets][3], cand_front[n_sets][4] (-1 for an invalid candidate), n_front and n_parallax of the winner, best_cand
+ *      (-1 without a winner), status, obs_front[M] (1 in front, 2 with parallax, 0 otherwise), X_out[3][M] (the midpoint
+ *      (lambda1 a' + t + lambda2 b) / 2 taken back to the left frame; NaN where the match is not in front), summary[6]:
+ *      sets posed | sets with a selected match and no winner (NO_MODEL, or NO_POSE alone) | EMPTY | TIED among the posed |
+ *      matches in front | selected matches of posed sets that are not in front.
+ *   8. No floating-point atomic, integer counts: a set's bits depend on the set, the intrinsics and the options only.  The
+ *      call returns when the work is done and the work buffers are back in the pool; the _dev form takes device pointers
+ *      (set_ptr, kind, model, K_left, K_right stay host arrays) and a stream (NULL = the library stream).  Both forms check
+ *      their arguments before they look for a device: a bad argument is SFM_E_SHAPE on a machine without one. */
+#define SFM_POSE_FROM_F       0
+#define SFM_POSE_FROM_H       1
+#define SFM_POSE_EMPTY        1   /* no selected match */
+#define SFM_POSE_NO_MODEL     2   /* the model is invalid by step 2 or step 3 */
+#define SFM_POSE_NO_POSE      4   /* there is no winner: no valid candidate has a selected match in front */
+#define SFM_POSE_TIED         8   /* another valid candidate has the winner's count */
+#define SFM_POSE_NO_PARALLAX 16   /* the winner's parallax count is below min_parallax */
+#define SFM_POSE_CANDIDATES   4
+int sfm_twoview_pose(int n_sets, const int* set_ptr /*host [n_sets+1]*/, int64_t M, const double* left /*[2][M]*/,
+                     const double* right /*[2][M]*/, const unsigned char* obs_mask /*[M] or NULL*/,
+                     const double* model /*[n_sets][9]*/, const int* kind /*[n_sets]*/, const double K_left[9],
+                     const double K_right[9], double cos2_min, int min_parallax, double* R_out /*[n_sets][9]*/,
+                     double* t_out /*[n_sets][3]*/, double* n_out, int* cand_front, int* n_front, int* n_parallax, int* best_cand,
+                     int* status, unsigned char* obs_front, double* X_out /*[3][M]*/, int64_t* summary /*[6]*/);
+int sfm_twoview_pose_dev(int n_sets, const int* set_ptr /*host*/, int64_t M, const double* d_left, const double* d_right,
+                         const unsigned char* d_obs_mask, const double* model /*host*/, const int* kind /*host*/,
+                         const double K_left[9] /*host*/, const double K_right[9] /*host*/, double cos2_min, int min_parallax,
+                         double* d_R_out, double* d_t_out, double* d_n_out, int* d_cand_front, int* d_n_front,
+                         int* d_n_parallax, int* d_best_cand, int* d_status, unsigned char* d_obs_front, double* d_X_out,
+                         int64_t* d_summary, void* hip_stream);
+/* The test of step 4 on the host (needs no device): a and b are the first two components of the rays. */
+int sfm_twoview_pose_test(const double R[9], const double t[3], const double a[2], const double b[2], double cos2_min,
+                          int* front, int* parallax);
+
 /* ---- SIFT detection: ViewProcessor.__extract_keys (view_processor.py:151-164, 199-202) --------------------------
  * cv.SIFT_create().detectAndCompute(img, None) by the contract of INTEGRATION.md 'SIFT detection' (firstOctave -1,
  * nfeatures 0, no mask): keypoints sorted by (x, y asc; size desc; angle asc; response desc; octave desc) without
@@ -1188,6 +1258,16 @@ int sfm_track_pairs(sfm_track_store* s, int ref, int que, int* n, int* r_idx, in
  * the two steps; the coordinates stay on the device. */
 int sfm_twoview_verify_pairs(sfm_track_store* s, int ref, int que, double max_err2, int max_hyp, int iters, int* n, int* r_idx,
                            int* q_idx, unsigned char* inlier, double F_out[9], int* best_hyp, int* status);
+/* processors.pose_pairs (a track store; not part of the KeyTrack interface): the pairs of table[ref][que] gathered on the
+ * device (the reference key LEFT, the query key RIGHT) and posed as one set.  Only the model and the intrinsics go up (and the
+ * optional mask `inlier` over the pairs in their order, a byte each, of which the first *n are read; the caller knows *n
+ * from the verification that produced the mask), only the count of pairs comes down between the two steps.  r_idx,
+ * q_idx and obs_front are host arrays of cap entries (cap = the keys of view ref), X_out of 3 cap, filled as [3][*n]. */
+int sfm_twoview_pose_pairs(sfm_track_store* s, int ref, int que, const unsigned char* inlier /*host [*n] or NULL*/,
+                           const double model[9], int kind, const double K_left[9], const double K_right[9], double cos2_min,
+                           int min_parallax, int* n, int* r_idx, int* q_idx, double R_out[9], double t_out[3], double n_out[3],
+                           int* cand_front, int* n_front, int* n_parallax, int* best_cand, int* status,
+                           unsigned char* obs_front, double* X_out);
 /* (The next two work on a track store; like sfm_obs_* and sfm_twoview_verify_pairs they are not part of the KeyTrack /
  * KeyTracker surface the sfm_track_* names cover.)
  * sfm_match_guided_dev with the coordinates the store already holds: `query` is the descriptor set of view que_view,

@@ -5,7 +5,8 @@
 // then cull, free and resident form agree on every decision because they execute the same function.  Below it the test
 // of one match against a fundamental matrix (the squared Sampson distance), which every stage of the robust two-view
 // geometry calls in the same way, and the test of one match against a homography and its inverse (the transfer error in
-// each image), which every stage of the robust homography calls.
+// each image), which every stage of the robust homography calls, and the test of one match against a relative pose (in
+// front of both cameras, with parallax), which every stage of the relative pose of a verified pair calls.
 //
 // Compiled WITHOUT automatic contraction, the FMAs spelled out.  The pragma is lexical and stays in force for the rest of
 // the translation unit: include this header outside any namespace and AFTER all code that keeps the compiler's default
@@ -91,6 +92,41 @@ __host__ __device__ inline void homography_adjugate(const double* H, double* G) 
   G[6] = __builtin_fma(H[3], H[7], -(H[4] * H[6]));
   G[7] = __builtin_fma(H[1], H[6], -(H[0] * H[7]));
   G[8] = __builtin_fma(H[0], H[4], -(H[1] * H[3]));
+}
+
+// The terms of the test of one MATCH against a relative pose (R, t), X_right = R X_left + t: the rays (a0, a1, 1) of the
+// left key and (b0, b1, 1) of the right key in normalised coordinates, a' = R a, p = a'.a', q = b.b, r = a'.b,
+// d = p q - r r, and the numerators m1, m2 of the depths along a' and b of the midpoint of the two rays, both over d.
+struct PoseTerms { double ap[3], p, q, r, d, m1, m2; };
+
+__host__ __device__ inline PoseTerms pose_terms(const double* R, const double* t, double a0, double a1, double b0, double b1) {
+  PoseTerms w;
+  w.ap[0] = __builtin_fma(R[0], a0, __builtin_fma(R[1], a1, R[2]));
+  w.ap[1] = __builtin_fma(R[3], a0, __builtin_fma(R[4], a1, R[5]));
+  w.ap[2] = __builtin_fma(R[6], a0, __builtin_fma(R[7], a1, R[8]));
+  w.p = __builtin_fma(w.ap[0], w.ap[0], __builtin_fma(w.ap[1], w.ap[1], w.ap[2] * w.ap[2]));
+  w.q = __builtin_fma(b0, b0, __builtin_fma(b1, b1, 1.0));
+  w.r = __builtin_fma(w.ap[0], b0, __builtin_fma(w.ap[1], b1, w.ap[2]));
+  w.d = __builtin_fma(w.p, w.q, -(w.r * w.r));
+  const double bt = __builtin_fma(b0, t[0], __builtin_fma(b1, t[1], t[2]));
+  const double at = __builtin_fma(w.ap[0], t[0], __builtin_fma(w.ap[1], t[1], w.ap[2] * t[2]));
+  w.m1 = __builtin_fma(w.r, bt, -(w.q * at));
+  w.m2 = __builtin_fma(w.p, bt, -(w.r * at));
+  return w;
+}
+
+// The test of one MATCH against a relative pose: IN FRONT of both cameras (the return value) iff d, m1, m2 are finite and
+// d > 0, m1 > 0, m2 > 0 -- no division; *parallax iff in front and not (r > 0 and r r > cos2_min p q), cos2_min the
+// squared cosine of the minimum triangulation angle.  Every stage of the relative pose of a verified pair (score, judge)
+// and sfm_twoview_pose_test call this one function; no branch.
+__host__ __device__ inline bool pose_front(const double* R, const double* t, double a0, double a1, double b0, double b1,
+                                           double cos2_min, bool* parallax) {
+  const PoseTerms w = pose_terms(R, t, a0, a1, b0, b1);
+  const int finite = (int)(__builtin_isfinite(w.d) != 0) & (int)(__builtin_isfinite(w.m1) != 0) & (int)(__builtin_isfinite(w.m2) != 0);
+  const int front = finite & (int)(w.d > 0.0) & (int)(w.m1 > 0.0) & (int)(w.m2 > 0.0);
+  const int narrow = (int)(w.r > 0.0) & (int)(w.r * w.r > cos2_min * (w.p * w.q));
+  *parallax = (bool)(front & (narrow ^ 1));
+  return (bool)front;
 }
 
 }  // namespace sfm

@@ -61,6 +61,12 @@ HOMOGRAPHY_TOO_FEW, HOMOGRAPHY_NO_MODEL, HOMOGRAPHY_KEPT_HYPOTHESIS = 1, 2, 4
 HOMOGRAPHY_MAX_HYP, HOMOGRAPHY_DEFAULT_HYP, HOMOGRAPHY_MIN_MATCHES = 65536, 128, 5
 HOMOGRAPHY_SUMMARY = TWOVIEW_SUMMARY
 HOMOGRAPHY_OUTPUTS = TWOVIEW_OUTPUTS
+POSE_FROM_F, POSE_FROM_H = 0, 1
+POSE_EMPTY, POSE_NO_MODEL, POSE_NO_POSE, POSE_TIED, POSE_NO_PARALLAX = 1, 2, 4, 8, 16
+POSE_CANDIDATES = 4
+POSE_KINDS = {"fundamental": POSE_FROM_F, "homography": POSE_FROM_H}
+POSE_SUMMARY = ("sets_posed", "sets_no_pose", "sets_empty", "sets_tied", "matches_front", "matches_not_front")
+POSE_OUTPUTS = ("normal", "cand_front", "n_front", "n_parallax", "best_cand", "status", "obs_front", "X", "summary")
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2
 CAM_EMPTY, CAM_NONFINITE, CAM_BEHIND, CAM_HELD = 1, 2, 4, 8
 COV_CAM_HELD, COV_CAM_PIVOT, COV_PT_EMPTY, COV_PT_SINGULAR = 8, 16, 4, 8
@@ -246,6 +252,12 @@ SIGNATURES = {
     "sfm_homography_ransac": [ci, _ip, i64, _dp, _dp, cd, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
     "sfm_homography_ransac_dev": [ci, _ip, i64, vp, vp, cd, ci, ci, vp, vp, vp, vp, vp, vp, vp],
     "sfm_homography_sample": [ci, ci, ci, _ip],
+    "sfm_twoview_pose": [ci, _ip, i64, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _dp, _dp, cd, ci, _dp, _dp, _dp, _ip, _ip, _ip,
+                         _ip, _ip, ctypes.POINTER(ctypes.c_uint8), _dp, _lp],
+    "sfm_twoview_pose_dev": [ci, _ip, i64, vp, vp, vp, _dp, _ip, _dp, _dp, cd, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "sfm_twoview_pose_test": [_dp, _dp, _dp, _dp, cd, _ip, _ip],
+    "sfm_twoview_pose_pairs": [vp, ci, ci, ctypes.POINTER(ctypes.c_uint8), _dp, ci, _dp, _dp, cd, ci, _ip, _ip, _ip, _dp, _dp, _dp, _ip,
+                               _ip, _ip, _ip, _ip, ctypes.POINTER(ctypes.c_uint8), _dp],
     "sfm_twoview_verify_pairs": [vp, ci, ci, cd, ci, ci, _ip, _ip, _ip, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _ip],
     "sfm_ba_covariance": [vp, cd, ci, ci, ctypes.POINTER(ctypes.c_uint8), ci, _dp, _dp, _ip, _ip, _dp],
     "sfm_ba_covariance_plan": [ci, _ip, _ip, _ip, _ip],
@@ -886,6 +898,91 @@ def homography_ransac_dev(set_ptr, n_obs, d_left, d_right, max_err2, max_hyp=0, 
     check(load().sfm_homography_ransac_dev(set_ptr.shape[0] - 1, iptr(set_ptr), int(n_obs), _vp(d_left), _vp(d_right), max_err2,
                                            max_hyp, iters, _vp(d_H_out), _vp(d_inlier), _vp(d_n_inliers), _vp(d_best_hyp),
                                            _vp(d_status), _vp(d_summary), _vp(stream)))
+
+
+# ---- relative pose of a verified pair (sfm_twoview_pose*; no reference counterpart) ------------------------------------
+def check_pose(n_sets, models, kinds, K_left, K_right, cos2_min, min_parallax):
+    """The arguments of a ``twoview_pose`` call besides the matches, without a device: ``(model (n_sets, 9) float64, kind
+    (n_sets,) int32, K_left (9,), K_right (9,), cos2_min, min_parallax)`` converted or ValueError -- everything
+    sfm_twoview_pose refuses.  ``kinds`` holds POSE_FROM_F / POSE_FROM_H or the names of ``POSE_KINDS``."""
+    cos2_min = float(cos2_min)
+    if not 0.0 <= cos2_min <= 1.0:
+        raise ValueError("cos2_min must be in [0, 1], got %r" % cos2_min)
+    min_parallax = _count("min_parallax", min_parallax)
+    kind = np.zeros(n_sets, dtype=np.int32)
+    kinds = list(kinds) if not isinstance(kinds, np.ndarray) else kinds.tolist()
+    if len(kinds) != n_sets:
+        raise ValueError("relative pose: %d sets, %d kinds" % (n_sets, len(kinds)))
+    for s, k in enumerate(kinds):
+        k = POSE_KINDS.get(k, k) if isinstance(k, str) else k
+        if k not in (POSE_FROM_F, POSE_FROM_H):
+            raise ValueError("relative pose: set %d has the unknown kind %r" % (s, kinds[s]))
+        kind[s] = k
+    model = f64(models).reshape(-1, 9) if n_sets else np.zeros((0, 9))
+    if model.shape[0] != n_sets:
+        raise ValueError("relative pose: %d sets, %d models" % (n_sets, model.shape[0]))
+    out = []
+    for name, K in (("K_left", K_left), ("K_right", K_right)):
+        K = f64(K)
+        if K.shape != (3, 3) or not np.all(np.isfinite(K)) or K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 or K[2, 2] != 1:
+            raise ValueError("%s must be a finite upper triangular (3, 3) matrix with K[2][2] = 1" % name)
+        out.append(K.reshape(9).copy())
+    return model, kind, out[0], out[1], cos2_min, min_parallax
+
+
+def twoview_pose_test(R, t, a, b, cos2_min):
+    """``(front, parallax)`` of one match with the rays ``(a[0], a[1], 1)`` and ``(b[0], b[1], 1)`` against the pose
+    ``(R, t)`` (sfm_twoview_pose_test: the function the kernels call, on the host)."""
+    R, t, a, b = f64(R).reshape(9), f64(t).reshape(3), f64(a).reshape(2), f64(b).reshape(2)
+    front, par = ci(0), ci(0)
+    check(load().sfm_twoview_pose_test(dptr(R), dptr(t), dptr(a), dptr(b), float(cos2_min), ctypes.byref(front), ctypes.byref(par)))
+    return int(front.value), int(par.value)
+
+
+def twoview_pose(set_ptr, left, right, models, kinds, K_left, K_right, cos2_min, min_parallax=1, mask=None, outputs=POSE_OUTPUTS):
+    """Relative pose of every set of matches from its verified model (sfm_twoview_pose; the rule is in include/sfm_hip.h,
+    'relative pose of a verified pair'): four candidates from F or H, an integer cheirality vote over the matches ``mask``
+    (M,) selects (None: all), the parallax count of the winner.  ``set_ptr``, ``left``, ``right`` as in ``twoview_ransac``;
+    ``cos2_min`` is the squared cosine of the minimum triangulation angle.  Returns a dict: ``R (S, 3, 3)`` and ``t (S, 3)``
+    with X_right = R X_left + t (zeros without a winner) and, of ``POSE_OUTPUTS``, what ``outputs`` names (None
+    otherwise): ``normal (S, 3), cand_front (S, 4), n_front (S,), n_parallax (S,), best_cand (S,), status (S,) of POSE_*
+    bits, obs_front (M,) uint8 (1 in front, 2 with parallax), X (3, M), summary (6,) int64`` in the order of
+    ``POSE_SUMMARY``."""
+    set_ptr, left, right = check_twoview_sets(set_ptr, left, right)
+    n_sets, m = set_ptr.shape[0] - 1, left.shape[1]
+    model, kind, kl, kr, cos2_min, min_parallax = check_pose(n_sets, models, kinds, K_left, K_right, cos2_min, min_parallax)
+    unknown = set(outputs) - set(POSE_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (POSE_OUTPUTS, sorted(unknown)))
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
+        if mask.shape[0] != m:
+            raise ValueError("mask must have one entry per match (%d), got %d" % (m, mask.shape[0]))
+    o = {"R": np.zeros((n_sets, 3, 3)), "t": np.zeros((n_sets, 3))}
+    shapes = {"normal": ((n_sets, 3), np.float64), "cand_front": ((n_sets, 4), np.int32), "n_front": (n_sets, np.int32),
+              "n_parallax": (n_sets, np.int32), "best_cand": (n_sets, np.int32), "status": (n_sets, np.int32),
+              "obs_front": (m, np.uint8), "X": ((3, m), np.float64), "summary": (6, np.int64)}
+    for name in POSE_OUTPUTS:
+        o[name] = np.zeros(shapes[name][0], dtype=shapes[name][1]) if name in outputs else None
+    check(load().sfm_twoview_pose(n_sets, iptr(set_ptr), m, dptr(left), dptr(right), _u8ptr(mask), dptr(model), iptr(kind), dptr(kl),
+                                  dptr(kr), cos2_min, min_parallax, dptr(o["R"]), dptr(o["t"]), dptr(o["normal"]),
+                                  iptr(o["cand_front"]), iptr(o["n_front"]), iptr(o["n_parallax"]), iptr(o["best_cand"]),
+                                  iptr(o["status"]), _u8ptr(o["obs_front"]), dptr(o["X"]), _lptr(o["summary"])))
+    return o
+
+
+def twoview_pose_dev(set_ptr, n_obs, d_left, d_right, models, kinds, K_left, K_right, cos2_min, min_parallax=1, d_mask=0, d_R_out=0,
+                     d_t_out=0, d_normal=0, d_cand_front=0, d_n_front=0, d_n_parallax=0, d_best_cand=0, d_status=0, d_obs_front=0,
+                     d_X_out=0, d_summary=0, stream=0):
+    """``twoview_pose`` on device pointers and a caller's stream (sfm_twoview_pose_dev); ``set_ptr``, the models, kinds and
+    intrinsics stay host arrays, optional arrays are 0."""
+    set_ptr = np.ascontiguousarray(set_ptr, dtype=np.int32).ravel()
+    n_sets = max(set_ptr.shape[0] - 1, 0)
+    model, kind, kl, kr, cos2_min, min_parallax = check_pose(n_sets, models, kinds, K_left, K_right, cos2_min, min_parallax)
+    check(load().sfm_twoview_pose_dev(set_ptr.shape[0] - 1, iptr(set_ptr), int(n_obs), _vp(d_left), _vp(d_right), _vp(d_mask),
+                                      dptr(model), iptr(kind), dptr(kl), dptr(kr), cos2_min, min_parallax, _vp(d_R_out), _vp(d_t_out),
+                                      _vp(d_normal), _vp(d_cand_front), _vp(d_n_front), _vp(d_n_parallax), _vp(d_best_cand),
+                                      _vp(d_status), _vp(d_obs_front), _vp(d_X_out), _vp(d_summary), _vp(stream)))
 
 
 def pnp_nonlinear(uv_pix, pts_h, intrinsic, rot0, loc0, lam, iters, quirks=QUIRKS_REFERENCE):
@@ -1932,6 +2029,33 @@ class TrackStore:
                                                iptr(q), _u8ptr(inl), dptr(F), ctypes.byref(best), ctypes.byref(status)))
         n = n.value
         return r[:n], q[:n], inl[:n], F, int(best.value), int(status.value)
+
+    def pose_pairs(self, ref, que, model, kind, K_left, K_right, cos2_min, min_parallax=1, inlier=None):
+        """The pairs of ``pairs(ref, que)`` posed on the device as one set (sfm_twoview_pose_pairs): a dict with ``r_idx``,
+        ``q_idx`` (n,), and ``R``, ``t``, ``normal``, ``cand_front``, ``n_front``, ``n_parallax``, ``best_cand``, ``status``,
+        ``obs_front`` (n,), ``X`` (3, n) of ``twoview_pose`` for that set.  ``inlier`` (n,) is the optional mask of the matches
+        that vote; the coordinates are not downloaded and nothing goes up but the model, the intrinsics and that mask."""
+        model, kind, kl, kr, cos2_min, min_parallax = check_pose(1, [model], [kind], K_left, K_right, cos2_min, min_parallax)
+        cap = max(self.n_keys(ref), 1)
+        if inlier is not None:
+            inlier = np.ascontiguousarray(np.asarray(inlier) != 0, dtype=np.uint8).reshape(-1)
+            if inlier.shape[0] > cap:
+                raise ValueError("pose_pairs: %d mask entries for at most %d pairs" % (inlier.shape[0], cap))
+            inlier = np.concatenate((inlier, np.zeros(cap - inlier.shape[0], dtype=np.uint8)))
+        n = ctypes.c_int()
+        ints = {name: ctypes.c_int(0) for name in ("n_front", "n_parallax", "best_cand", "status")}
+        r, q, front = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.uint8)
+        R, t, normal, cand, X = np.zeros((3, 3)), np.zeros(3), np.zeros(3), np.zeros(4, dtype=np.int32), np.zeros(3 * cap)
+        check(self._lib.sfm_twoview_pose_pairs(self._h, int(ref), int(que), _u8ptr(inlier), dptr(model), int(kind[0]), dptr(kl), dptr(kr),
+                                               cos2_min, min_parallax, ctypes.byref(n), iptr(r), iptr(q), dptr(R), dptr(t),
+                                               dptr(normal), iptr(cand), ctypes.byref(ints["n_front"]),
+                                               ctypes.byref(ints["n_parallax"]), ctypes.byref(ints["best_cand"]),
+                                               ctypes.byref(ints["status"]), _u8ptr(front), dptr(X)))
+        n = n.value
+        out = {"r_idx": r[:n], "q_idx": q[:n], "R": R, "t": t, "normal": normal, "cand_front": cand, "obs_front": front[:n],
+               "X": X[:3 * n].reshape(3, n)}
+        out.update({name: int(v.value) for name, v in ints.items()})
+        return out
 
     def match_guided(self, que_view, query, ref_views, refs, kinds, models, max_err2, d_best_idx=0, d_best_dist=0, d_second_idx=0,
                      d_second_dist=0, d_mutual=0, d_n_admitted=0, stream=0):

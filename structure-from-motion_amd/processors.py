@@ -331,6 +331,38 @@ class HipCamposeMixin:
             return 0, []
         return best, np.flatnonzero(mask[best]).tolist()
 
+    def estimate_relative_pose_robust(self, matched_pairs, model, kind, K_left, K_right, inliers=None, min_angle_deg=2.0,
+                                      min_parallax=8):
+        """The pose of the right (query) view relative to the left (reference) view from a verified two-view model (one
+        ``native.twoview_pose``; no reference counterpart): ``model`` is the fundamental matrix (``kind="fundamental"``)
+        or the homography (``kind="homography"``) of ``matched_pairs`` ([ref_pts, que_pts], (2 or 3, n) pixel coordinates),
+        ``inliers`` the indices of the matches that vote (None: all).  The four candidate poses are scored by the number of
+        voting matches in front of both cameras, and the winner's matches that subtend at least ``min_angle_deg`` degrees
+        are counted as its parallax.
+
+        Returns ``rot, centre (3, 1), front_idx (a list), counts``: ``rot`` and ``centre`` in the convention of
+        ``extract_cam_pose_from_essential_mat`` / ``ba_processor.py:81-97`` (projection ``K [rot^T | -rot^T centre]``).  The
+        library's pose is (R, t) with ``X_right = R X_left + t`` and ``|t| = 1``; the conversion is ``rot = R^T`` and
+        ``centre = -R^T t``.  Without a winner ``rot`` is the identity, ``centre`` zeros and the list empty.  ``counts`` is a
+        dict: ``n_front``, ``n_parallax``, ``cand_front`` (4,), ``best_cand``, ``status`` (``native.POSE_*`` bits).
+        ``pose_last`` keeps these, ``R``, ``t``, the plane normal, ``obs_front`` and the triangulated points ``X`` (3, n).
+        ``min_angle_deg`` and ``min_parallax`` are the caller's options; the defaults (2 degrees, 8 matches) are common
+        choices for an initial pair, not constants measured by this project."""
+        if not 0.0 <= float(min_angle_deg) <= 90.0:
+            raise ValueError("min_angle_deg must be in [0, 90], got {!r}".format(min_angle_deg))
+        left = np.asarray(matched_pairs[0], dtype=np.float64)[0:2, :]
+        right = np.asarray(matched_pairs[1], dtype=np.float64)[0:2, :]
+        if left.shape != right.shape:
+            raise ValueError("matched pairs of different sizes : {} - {}".format(left.shape[1], right.shape[1]))
+        num = left.shape[1]
+        mask = None
+        if inliers is not None:
+            mask = np.zeros(num, dtype=np.uint8)
+            mask[np.asarray(inliers, dtype=np.int64)] = 1
+        out = native.twoview_pose([0, num], left, right, [model], [kind], K_left, K_right, math.cos(math.radians(float(min_angle_deg))) ** 2,
+                                  min_parallax, mask)
+        return _pose_result(self, out, 0, 0, num)
+
 
 class HipEpipolarMixin:
     """Eight-point RANSAC and essential-matrix extraction of ``EpipolarProcessor`` (epipolar_processor.py:22-95)
@@ -450,6 +482,45 @@ class HipEpipolarMixin:
                         "H_inliers": np.flatnonzero(h_in[lo:hi]).tolist(), "F_status": int(f_status[s]),
                         "H_status": int(h_status[s]), "verdict": verdict})
         return out
+
+    def initialise_pairs(self, list_of_matched_pairs, K, K_right=None, max_px=2.0, max_hyp=128, iteration=2, planar_ratio=0.8,
+                         min_angle_deg=2.0, min_parallax=8):
+        """Verdict and relative pose of several sets of matches (no reference counterpart): ``classify_matches`` and then ONE
+        ``native.twoview_pose`` over all sets, every set posed from the model its verdict trusts with that model's inliers
+        voting: F for ``"general"``, H for ``"degenerate"``; a ``"none"`` set is passed with an empty mask and comes back
+        without a pose.  ``K`` is the intrinsic matrix of every left view and, unless ``K_right`` is given, of every right
+        view.  Returns one dict per set: ``verdict``, ``kind``, ``R``, ``t`` (X_right = R X_left + t), ``rot``, ``centre`` (the
+        reference's convention, see ``estimate_relative_pose_robust``), ``normal``, ``front`` (indices), ``n_front``,
+        ``n_parallax``, ``cand_front``, ``best_cand``, ``status``, and the entries of ``classify_matches``.  A pair to start
+        from has a pose, no ``native.POSE_NO_PARALLAX`` and the largest ``n_parallax``.  ``pose_last`` keeps the summary."""
+        if not 0.0 <= float(min_angle_deg) <= 90.0:
+            raise ValueError("min_angle_deg must be in [0, 90], got {!r}".format(min_angle_deg))
+        verdicts = self.classify_matches(list_of_matched_pairs, max_px, max_hyp, iteration, planar_ratio)
+        set_ptr, left, right = self._twoview_sets(list_of_matched_pairs)
+        mask = np.zeros(left.shape[1], dtype=np.uint8)
+        models, kinds = [], []
+        for s, v in enumerate(verdicts):
+            use_h = v["verdict"] == "degenerate"
+            kinds.append(native.POSE_FROM_H if use_h else native.POSE_FROM_F)
+            models.append(v["H"] if use_h else v["F"])
+            if v["verdict"] != "none":
+                mask[set_ptr[s] + np.asarray(v["H_inliers"] if use_h else v["F_inliers"], dtype=np.int64)] = 1
+        out = native.twoview_pose(set_ptr, left, right, models, kinds, K, K if K_right is None else K_right,
+                                  math.cos(math.radians(float(min_angle_deg))) ** 2, min_parallax, mask,
+                                  outputs=("normal", "cand_front", "n_front", "n_parallax", "best_cand", "status", "obs_front", "summary"))
+        self.pose_last = {"summary": out["summary"], "status": out["status"].tolist()}
+        result = []
+        for s, v in enumerate(verdicts):
+            R, t = out["R"][s], out["t"][s]
+            won = out["best_cand"][s] >= 0
+            entry = dict(v)
+            entry.update({"kind": "homography" if kinds[s] == native.POSE_FROM_H else "fundamental", "R": R, "t": t,
+                          "rot": R.T.copy() if won else np.identity(3), "centre": (-R.T @ t).reshape(3, 1),
+                          "normal": out["normal"][s], "front": np.flatnonzero(out["obs_front"][set_ptr[s]:set_ptr[s + 1]]).tolist(),
+                          "n_front": int(out["n_front"][s]), "n_parallax": int(out["n_parallax"][s]),
+                          "cand_front": out["cand_front"][s], "best_cand": int(out["best_cand"][s]), "status": int(out["status"][s])})
+            result.append(entry)
+        return result
 
 
     def guided_matches(self, query, query_xy, ref, ref_xy, model, max_px=2.0, ratio=matching.RATIO, metric=native.MATCH_L2):
@@ -1664,6 +1735,44 @@ def verify_pairs(tracker, ref_idx, que_idx, max_sampson_px=2.0, max_hyp=128, ite
     tracker.twoview_last = {"fund_mat": fund, "hypothesis": best, "status": status}
     num = r_idx.shape[0]
     return r_idx.reshape(1, num).astype(int), q_idx.reshape(1, num).astype(int), inlier.astype(bool)
+
+
+def _pose_result(owner, out, s, lo, hi):
+    """(rot, centre, front indices, counts) of set ``s`` of a ``native.twoview_pose`` result (matches lo .. hi - 1), kept as
+    ``owner.pose_last``."""
+    R, t = out["R"][s], out["t"][s]
+    won = out["best_cand"][s] >= 0
+    counts = {"n_front": int(out["n_front"][s]), "n_parallax": int(out["n_parallax"][s]), "cand_front": out["cand_front"][s].copy(),
+              "best_cand": int(out["best_cand"][s]), "status": int(out["status"][s])}
+    last = dict(counts)
+    last.update({"R": R, "t": t, "normal": out["normal"][s], "obs_front": out["obs_front"][lo:hi], "X": out["X"][:, lo:hi]})
+    owner.pose_last = last
+    rot = R.T.copy() if won else np.identity(3)
+    return rot, (-R.T @ t).reshape(3, 1), np.flatnonzero(out["obs_front"][lo:hi]).tolist(), counts
+
+
+def pose_pairs(tracker, ref_idx, que_idx, model, kind, K_left, K_right, inlier=None, min_angle_deg=2.0, min_parallax=8):
+    """``estimate_relative_pose_robust`` over the pairs ``tracker.generate_matched_pairs(ref_idx, que_idx)`` returns
+    (``tracker``: a ``HipDeviceKeyTracker``) without leaving the device (``TrackStore.pose_pairs``: the pairs are gathered
+    into device buffers and posed on the same stream; nothing goes up but the model, the intrinsics and the optional mask
+    ``inlier`` (n,) of ``verify_pairs``, no coordinate comes down).  Returns ``r_idx (1, n), q_idx (1, n), rot, centre,
+    front_idx, counts`` as that method does; ``tracker.pose_last`` keeps what its ``pose_last`` keeps.  A function of the
+    module, like ``verify_pairs``."""
+    n_views = len(tracker.track_list)
+    if ref_idx < 0 or que_idx < 0 or ref_idx >= n_views or que_idx >= n_views:
+        print('{}:{} - invalid ref_idx {} or invalid que_idx {}'.format(
+            tracker.__class__.__name__, 'pose_pairs', ref_idx, que_idx))
+        return None
+    if not 0.0 <= float(min_angle_deg) <= 90.0:
+        raise ValueError("min_angle_deg must be in [0, 90], got {!r}".format(min_angle_deg))
+    o = tracker._store.pose_pairs(ref_idx, que_idx, model, kind, K_left, K_right, math.cos(math.radians(float(min_angle_deg))) ** 2,
+                                  min_parallax, inlier)
+    num = o["r_idx"].shape[0]
+    out = {"R": o["R"][None], "t": o["t"][None], "normal": o["normal"][None], "cand_front": o["cand_front"][None],
+           "obs_front": o["obs_front"], "X": o["X"]}
+    out.update({name: np.array([o[name]]) for name in ("n_front", "n_parallax", "best_cand", "status")})
+    rot, centre, front, counts = _pose_result(tracker, out, 0, 0, num)
+    return o["r_idx"].reshape(1, num).astype(int), o["q_idx"].reshape(1, num).astype(int), rot, centre, front, counts
 
 
 def _guided_model(model):
