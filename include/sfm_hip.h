@@ -1140,6 +1140,79 @@ int sfm_twoview_pose_dev(int n_sets, const int* set_ptr /*host*/, int64_t M, con
 int sfm_twoview_pose_test(const double R[9], const double t[3], const double a[2], const double b[2], double cos2_min,
                           int* front, int* parallax);
 
+/* ---- refinement of a relative pose: damped Gauss-Newton on the Sampson distance, five parameters -----------------
+ * What follows sfm_twoview_pose: for many sets of matches in one call, a given pose (R, t), X_right = R X_left + t, is
+ * moved on its 5-dimensional manifold to the minimum of the sum of squared Sampson distances IN PIXELS of the selected
+ * matches, and the matches are judged against the result.  The sets, obs_mask and the intrinsics are those of
+ * sfm_twoview_pose; R_in[n_sets][9] (row-major) and t_in[n_sets][3] are the poses.  Options: lambda >= 0 (damping),
+ * iters >= 0, max_err2 >= 0 (the judge's squared Sampson bound), cos2_min in [0, 1]; anything else is SFM_E_SHAPE.
+ *   1. Selected.  A match is SELECTED iff its mask byte is non-zero and its four pixel coordinates are finite; n_used is
+ *      their number.
+ *   2. Pose check.  A set whose R_in or t_in is not finite, or whose t_in is zero (or has no finite squared length), is
+ *      BAD_POSE -- a set sfm_twoview_pose left without a winner is.  Otherwise t = t_in / |t_in|; R_in is taken as a
+ *      rotation, it is the caller's.
+ *   3. Model of a pose (refine_model, csrc/sfm_obs_test.h).  E = [t]x R; F = K_right^-T E K_left^-1 by substitution through
+ *      the triangular intrinsics, not scaled.  Chart at (R, t): theta = (w0, w1, w2, d0, d1), R(theta) = exp([w]x) R by
+ *      Rodrigues' formula, t(theta) = (t + d0 b1 + d1 b2) / |.| with k the index of the smallest |t_k| (the lowest on a tie),
+ *      b1 = (t x e_k) / |t x e_k|, b2 = t x b1.  The derivatives at theta = 0 are dF_j = K_right^-T dE_j K_left^-1 with
+ *      dE_j = [t]x [e_j]x R for j < 3, dE_3 = [b1]x R, dE_4 = [b2]x R.
+ *   4. Residual of a match (refine_residual, csrc/sfm_obs_test.h; one function for the passes, the judge and
+ *      sfm_twoview_refine_test).  With x = (x_l, y_l, 1), y = (x_r, y_r, 1), a = F x, b = F^T y: e = y . a,
+ *      s = a0^2 + a1^2 + b0^2 + b1^2, r = e / sqrt(s), and with da = dF_j x, db = dF_j^T y
+ *      J_j = (y . dF_j x) / sqrt(s) - (e / s^(3/2)) (a0 da0 + a1 da1 + b0 db0 + b1 db1).  In the operation order of the function:
+ *        a_i = fma(F[3i], x_l, fma(F[3i+1], y_l, F[3i+2]));  b_i = fma(F[i], x_r, fma(F[3+i], y_r, F[6+i]));
+ *        e = fma(x_r, a0, fma(y_r, a1, a2));  s = fma(a0, a0, a1 a1) + fma(b0, b0, b1 b1);  r = e / sqrt(s);
+ *        de = fma(x_r, da0, fma(y_r, da1, da2));  g = fma(a0, da0, fma(a1, da1, fma(b0, db0, b1 db1)));
+ *        J_j = fma(-(r / s), g, de (1 / sqrt(s))).
+ *   5. One pass.  c = sum r^2, U = sum J^T J (15 sums), g = sum J^T r (5 sums) over the selected matches; an unselected match
+ *      adds zeros.  The 21 sums are formed per slice of 64 consecutive matches of the set and the slices are added in
+ *      slice order.
+ *   6. One step.  (U + lambda diag U) d = -g by a 5x5 Cholesky factorisation; a pivot that is not finite or not > 0 sets
+ *      SINGULAR and ends the iterations at the standing pose.  Otherwise the pose becomes (R(d), t(d)).  `iters` steps,
+ *      unconditionally -- no step is accepted or rejected -- and at most iters + 1 passes: the last pass gives the cost and
+ *      U at the iterated pose.
+ *   7. Guard.  The output is the iterated pose iff a step was taken, every entry of the pose and both costs are finite
+ *      (NONFINITE otherwise) and c_out <= c_in (1 + 2^-30).  Otherwise the input (R_in, t_in) comes back bit for bit, with
+ *      KEPT_INPUT, its cost in both entries of `cost` and U of the first pass in `info`.  iters = 0 is a pure evaluation.
+ *   8. Too few.  n_used < 8 is TOO_FEW (EMPTY as well at 0): no pass is made and the input comes back.
+ *   9. Judge at the output pose (R_out, t_out as they are written), over every match of the set whether selected or not:
+ *      obs_res[M] the signed residual of step 4 (NaN where a coordinate is not finite or the set is BAD_POSE);
+ *      obs_inlier[M] = twoview_inlier(F_out, ..., max_err2); obs_front[M] 0 / 1 / 2 by the test of the relative pose
+ *      (pose_front) at cos2_min, needing finite rays; X_out[3][M] the midpoint as sfm_twoview_pose gives it, NaN where the
+ *      match is not in front; n_inliers, n_front, n_parallax count the SELECTED matches.  A BAD_POSE set has zeros.
+ *  10. Outputs, all optional but R_out and t_out: F_out[n_sets][9] the pixel fundamental matrix of the output pose with
+ *      the norm and sign of sfm_twoview_ransac's F_out (zeros for BAD_POSE); cost[2][n_sets] the input and the output
+ *      cost and info[n_sets][15] the upper triangle of U at the output pose, row by row (zeros where no pass was made);
+ *      n_used, status; summary[6]: sets that made a pass | BAD_POSE | other sets with EMPTY or TOO_FEW | KEPT_INPUT among
+ *      the first | their inliers | their selected matches that are not inliers.
+ *  No floating-point atomic: a set's bits depend on the set, its pose, the intrinsics and the options only.  The _dev
+ *  form takes device pointers (set_ptr and the intrinsics stay host arrays) and a stream (NULL = the library stream).
+ *  Both forms check their arguments before they look for a device. */
+#define SFM_REFINE_EMPTY       1   /* no selected match */
+#define SFM_REFINE_TOO_FEW     2   /* fewer than 8 selected matches */
+#define SFM_REFINE_BAD_POSE    4   /* the input pose is not finite or its translation is zero */
+#define SFM_REFINE_SINGULAR    8   /* a pivot of the damped normal equations was not positive: the iterations ended there */
+#define SFM_REFINE_NONFINITE  16   /* the iterated pose or a cost is not finite */
+#define SFM_REFINE_KEPT_INPUT 32   /* the output is the input, bit for bit */
+int sfm_twoview_refine(int n_sets, const int* set_ptr /*host [n_sets+1]*/, int64_t M, const double* left /*[2][M]*/,
+                       const double* right /*[2][M]*/, const unsigned char* obs_mask /*[M] or NULL*/,
+                       const double* R_in /*[n_sets][9]*/, const double* t_in /*[n_sets][3]*/, const double K_left[9],
+                       const double K_right[9], double lambda, int iters, double max_err2, double cos2_min,
+                       double* R_out /*[n_sets][9]*/, double* t_out /*[n_sets][3]*/, double* F_out, double* cost /*[2][n_sets]*/,
+                       double* info /*[n_sets][15]*/, int* n_used, int* status, double* obs_res /*[M]*/,
+                       unsigned char* obs_inlier, unsigned char* obs_front, double* X_out /*[3][M]*/, int* n_inliers,
+                       int* n_front, int* n_parallax, int64_t* summary /*[6]*/);
+int sfm_twoview_refine_dev(int n_sets, const int* set_ptr /*host*/, int64_t M, const double* d_left, const double* d_right,
+                           const unsigned char* d_obs_mask, const double* d_R_in, const double* d_t_in,
+                           const double K_left[9] /*host*/, const double K_right[9] /*host*/, double lambda, int iters,
+                           double max_err2, double cos2_min, double* d_R_out, double* d_t_out, double* d_F_out, double* d_cost,
+                           double* d_info, int* d_n_used, int* d_status, double* d_obs_res, unsigned char* d_obs_inlier,
+                           unsigned char* d_obs_front, double* d_X_out, int* d_n_inliers, int* d_n_front, int* d_n_parallax,
+                           int64_t* d_summary, void* hip_stream);
+/* Steps 3 and 4 on the host (needs no device): the residual and the Jacobian row of one match at the pose (R, t) as given. */
+int sfm_twoview_refine_test(const double R[9], const double t[3], const double K_left[9], const double K_right[9], double xl,
+                            double yl, double xr, double yr, double* r, double J[5]);
+
 /* ---- SIFT detection: ViewProcessor.__extract_keys (view_processor.py:151-164, 199-202) --------------------------
  * cv.SIFT_create().detectAndCompute(img, None) by the contract of INTEGRATION.md 'SIFT detection' (firstOctave -1,
  * nfeatures 0, no mask): keypoints sorted by (x, y asc; size desc; angle asc; response desc; octave desc) without
@@ -1268,6 +1341,17 @@ int sfm_twoview_pose_pairs(sfm_track_store* s, int ref, int que, const unsigned 
                            int min_parallax, int* n, int* r_idx, int* q_idx, double R_out[9], double t_out[3], double n_out[3],
                            int* cand_front, int* n_front, int* n_parallax, int* best_cand, int* status,
                            unsigned char* obs_front, double* X_out);
+/* TrackStore.refine_pairs: the same pairs gathered on the device and their pose (R_in, t_in) refined as one set by
+ * sfm_twoview_refine's rule.  Nothing goes up but the pose, the intrinsics and the optional mask `inlier` (of which the
+ * first *n bytes are read), only the count of pairs comes down between the two steps.  r_idx, q_idx, obs_res, obs_inlier and
+ * obs_front are host arrays of cap entries (cap = the keys of view ref), X_out of 3 cap, filled as [3][*n]; every output
+ * but n, R_out and t_out may be NULL. */
+int sfm_twoview_refine_pairs(sfm_track_store* s, int ref, int que, const unsigned char* inlier /*host [*n] or NULL*/,
+                             const double R_in[9], const double t_in[3], const double K_left[9], const double K_right[9],
+                             double lambda, int iters, double max_err2, double cos2_min, int* n, int* r_idx, int* q_idx,
+                             double R_out[9], double t_out[3], double F_out[9], double cost[2], double info[15], int* n_used,
+                             int* status, double* obs_res, unsigned char* obs_inlier, unsigned char* obs_front, double* X_out,
+                             int* n_inliers, int* n_front, int* n_parallax);
 /* (The next two work on a track store; like sfm_obs_* and sfm_twoview_verify_pairs they are not part of the KeyTrack /
  * KeyTracker surface the sfm_track_* names cover.)
  * sfm_match_guided_dev with the coordinates the store already holds: `query` is the descriptor set of view que_view,

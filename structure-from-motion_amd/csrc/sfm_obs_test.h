@@ -6,7 +6,9 @@
 // of one match against a fundamental matrix (the squared Sampson distance), which every stage of the robust two-view
 // geometry calls in the same way, and the test of one match against a homography and its inverse (the transfer error in
 // each image), which every stage of the robust homography calls, and the test of one match against a relative pose (in
-// front of both cameras, with parallax), which every stage of the relative pose of a verified pair calls.
+// front of both cameras, with parallax), which every stage of the relative pose of a verified pair calls, and the model
+// of a pose with the signed Sampson residual of one match and its Jacobian row, which the passes and the judge of the
+// refinement of a relative pose call.
 //
 // Compiled WITHOUT automatic contraction, the FMAs spelled out.  The pragma is lexical and stays in force for the rest of
 // the translation unit: include this header outside any namespace and AFTER all code that keeps the compiler's default
@@ -127,6 +129,123 @@ __host__ __device__ inline bool pose_front(const double* R, const double* t, dou
   const int narrow = (int)(w.r > 0.0) & (int)(w.r * w.r > cos2_min * (w.p * w.q));
   *parallax = (bool)(front & (narrow ^ 1));
   return (bool)front;
+}
+
+// The model of a relative pose (R, t) for its refinement (sfm_twoview_refine): F = K_r^-T [t]x R K_l^-1 in pixels, not
+// scaled, and its five derivatives dF[j] at the origin of the chart (w0, w1, w2, d0, d1) of the pose:
+// R(w) = exp([w]x) R, t(d) = (t + d0 b1 + d1 b2) / |.| with b1 = (t x e_k) / |t x e_k|, k the index of the smallest |t_k|
+// (the lowest on a tie), and b2 = t x b1.  54 doubles; b1 and b2 are kept for the step.
+struct RefineModel { double F[9], dF[5][9], b1[3], b2[3]; };
+
+// out = [v]x M, both row-major.
+__host__ __device__ inline void refine_cross_mat(const double* v, const double* M, double* out) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    out[c] = __builtin_fma(v[1], M[6 + c], -(v[2] * M[3 + c]));
+    out[3 + c] = __builtin_fma(v[2], M[c], -(v[0] * M[6 + c]));
+    out[6 + c] = __builtin_fma(v[0], M[3 + c], -(v[1] * M[c]));
+  }
+}
+
+// F = K_r^-T E K_l^-1 by substitution through the upper triangular intrinsics (K[8] = 1): K_r^T Y = E column by column from
+// the top, then F K_l = Y row by row from the left; the four divisions by the focal lengths are taken once, as reciprocals.
+__host__ __device__ inline void refine_to_pixels(const double* Kl, const double* Kr, const double* E, double* F) {
+  const double ir0 = 1.0 / Kr[0], ir4 = 1.0 / Kr[4], il0 = 1.0 / Kl[0], il4 = 1.0 / Kl[4];
+  double Y[9];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    Y[c] = E[c] * ir0;
+    Y[3 + c] = __builtin_fma(-Kr[1], Y[c], E[3 + c]) * ir4;
+    Y[6 + c] = __builtin_fma(-Kr[5], Y[3 + c], __builtin_fma(-Kr[2], Y[c], E[6 + c]));
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    F[3 * r] = Y[3 * r] * il0;
+    F[3 * r + 1] = __builtin_fma(-F[3 * r], Kl[1], Y[3 * r + 1]) * il4;
+    F[3 * r + 2] = __builtin_fma(-F[3 * r + 1], Kl[5], __builtin_fma(-F[3 * r], Kl[2], Y[3 * r + 2]));
+  }
+}
+
+// The basis (b1, b2) of the tangent plane of the unit sphere at t.
+__host__ __device__ inline void refine_basis(const double* t, double* b1, double* b2) {
+  int k = 0;
+  double least = __builtin_fabs(t[0]);
+#pragma unroll
+  for (int i = 1; i < 3; ++i) {
+    const bool less = __builtin_fabs(t[i]) < least;
+    k = less ? i : k;
+    least = less ? __builtin_fabs(t[i]) : least;
+  }
+  const double ek[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
+  double c[3];
+  c[0] = __builtin_fma(t[1], ek[2], -(t[2] * ek[1]));
+  c[1] = __builtin_fma(t[2], ek[0], -(t[0] * ek[2]));
+  c[2] = __builtin_fma(t[0], ek[1], -(t[1] * ek[0]));
+  const double nrm = __builtin_sqrt(__builtin_fma(c[2], c[2], __builtin_fma(c[1], c[1], c[0] * c[0])));
+#pragma unroll
+  for (int i = 0; i < 3; ++i) b1[i] = c[i] / nrm;
+  b2[0] = __builtin_fma(t[1], b1[2], -(t[2] * b1[1]));
+  b2[1] = __builtin_fma(t[2], b1[0], -(t[0] * b1[2]));
+  b2[2] = __builtin_fma(t[0], b1[1], -(t[1] * b1[0]));
+}
+
+// One of the six matrices of the model: part 0 is F, part 1 + j is dF[j].  The parts do not depend on each other (six
+// lanes form them side by side); part 0 also leaves b1 and b2.
+__host__ __device__ inline void refine_model_part(const double* R, const double* t, const double* Kl, const double* Kr, int part,
+                                                  RefineModel& m) {
+  double b1[3], b2[3], E[9], G[9];
+  refine_basis(t, b1, b2);
+  if (part == 0) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { m.b1[i] = b1[i]; m.b2[i] = b2[i]; }
+    refine_cross_mat(t, R, E);
+  } else if (part <= 3) {
+    const int j = part - 1;
+    const double ej[3] = {j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0};
+    refine_cross_mat(ej, R, G);
+    refine_cross_mat(t, G, E);
+  } else {
+    refine_cross_mat(part == 4 ? b1 : b2, R, E);
+  }
+  refine_to_pixels(Kl, Kr, E, part == 0 ? m.F : m.dF[part - 1]);
+}
+
+__host__ __device__ inline void refine_model(const double* R, const double* t, const double* Kl, const double* Kr, RefineModel& m) {
+  for (int part = 0; part < 6; ++part) refine_model_part(R, t, Kl, Kr, part, m);
+}
+
+// The residual of one MATCH against the model of a pose and its Jacobian row: with x = (x_l, y_l, 1), y = (x_r, y_r, 1),
+// a = F x, b = F^T y, e = y . a and s = a0^2 + a1^2 + b0^2 + b1^2 the signed Sampson distance r = e / sqrt(s) in pixels,
+// and J[j] = (y . dF_j x) / sqrt(s) - (e / s^(3/2)) (a0 da0 + a1 da1 + b0 db0 + b1 db1), da = dF_j x, db = dF_j^T y.  J may be
+// null.  The pass and the judge of sfm_twoview_refine and sfm_twoview_refine_test call this one function; no branch on the
+// data.
+__host__ __device__ inline double refine_residual(const double* F, const double (*dF)[9], double xl, double yl, double xr, double yr,
+                                                  double* J) {
+  const double a0 = __builtin_fma(F[0], xl, __builtin_fma(F[1], yl, F[2]));
+  const double a1 = __builtin_fma(F[3], xl, __builtin_fma(F[4], yl, F[5]));
+  const double a2 = __builtin_fma(F[6], xl, __builtin_fma(F[7], yl, F[8]));
+  const double b0 = __builtin_fma(F[0], xr, __builtin_fma(F[3], yr, F[6]));
+  const double b1 = __builtin_fma(F[1], xr, __builtin_fma(F[4], yr, F[7]));
+  const double e = __builtin_fma(xr, a0, __builtin_fma(yr, a1, a2));
+  const double s = __builtin_fma(a0, a0, a1 * a1) + __builtin_fma(b0, b0, b1 * b1);
+  const double root = __builtin_sqrt(s);
+  const double r = e / root;
+  if (J) {
+    const double inv = 1.0 / root, q = r / s;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const double* D = dF[j];
+      const double da0 = __builtin_fma(D[0], xl, __builtin_fma(D[1], yl, D[2]));
+      const double da1 = __builtin_fma(D[3], xl, __builtin_fma(D[4], yl, D[5]));
+      const double da2 = __builtin_fma(D[6], xl, __builtin_fma(D[7], yl, D[8]));
+      const double db0 = __builtin_fma(D[0], xr, __builtin_fma(D[3], yr, D[6]));
+      const double db1 = __builtin_fma(D[1], xr, __builtin_fma(D[4], yr, D[7]));
+      const double de = __builtin_fma(xr, da0, __builtin_fma(yr, da1, da2));
+      const double g = __builtin_fma(a0, da0, __builtin_fma(a1, da1, __builtin_fma(b0, db0, b1 * db1)));
+      J[j] = __builtin_fma(-q, g, de * inv);
+    }
+  }
+  return r;
 }
 
 }  // namespace sfm

@@ -25,6 +25,7 @@
 #include "sfm_obs_test.h"      // contraction is off from here on
 #include "sfm_robust.h"
 #include "sfm_match_norm.h"
+#include "sfm_pose_rays.h"
 
 namespace sfm {
 
@@ -67,29 +68,11 @@ struct PoseArgs {
 
 __device__ __forceinline__ MatchView pose_view(const PoseArgs& a) { return {a.left, a.right, a.M}; }
 
-struct PoseRays { double a0, a1, b0, b1; };
-
-// (x, y, 1) = K (r0, r1, 1) solved from the bottom row up, K upper triangular with K[8] = 1.
-__device__ __forceinline__ void pose_ray(const double* K, double x, double y, double& r0, double& r1) {
-  r1 = (y - K[5]) / K[4];
-  r0 = (__builtin_fma(-K[1], r1, x) - K[2]) / K[0];
-}
-
 // The rays of match i and whether it is SELECTED.
 __device__ __forceinline__ bool pose_rays(const PoseArgs& a, long long i, PoseRays& r) {
-  const TvMatch m = match_load(pose_view(a), i);
-  pose_ray(a.Kl, m.xl, m.yl, r.a0, r.a1);
-  pose_ray(a.Kr, m.xr, m.yr, r.b0, r.b1);
-  const bool finite = ((r.a0 + r.a1 + r.b0 + r.b1) * 0.0) == 0.0;
+  const bool finite = pose_rays_of(a.Kl, a.Kr, match_load(pose_view(a), i), r);
   const bool on = a.mask ? a.mask[i] != 0 : true;
   return finite & on;
-}
-
-__device__ __forceinline__ bool pose_finite9(const double* m) {
-  double probe = 0.0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) probe += m[k] * 0.0;
-  return probe == 0.0;
 }
 
 __device__ __forceinline__ void pose_mul3(const double* A, const double* B, double* C) {   // C = A B, row-major
@@ -111,16 +94,6 @@ __device__ __forceinline__ void pose_hn(const PoseArgs& a, const double* H, doub
     const double x = __builtin_fma(-K[2], z, __builtin_fma(-K[1], y, P[c])) / K[0];
     Hn[c] = x; Hn[3 + c] = y; Hn[6 + c] = z;
   }
-}
-
-__device__ __forceinline__ void pose_cross(const double* u, const double* v, double* w) {
-  w[0] = __builtin_fma(u[1], v[2], -(u[2] * v[1]));
-  w[1] = __builtin_fma(u[2], v[0], -(u[0] * v[2]));
-  w[2] = __builtin_fma(u[0], v[1], -(u[1] * v[0]));
-}
-
-__device__ __forceinline__ double pose_dot(const double* u, const double* v) {
-  return __builtin_fma(u[2], v[2], __builtin_fma(u[1], v[1], u[0] * v[0]));
 }
 
 // t scaled to length 1 with its entry of largest magnitude (the first of them) positive; `flip` is the sign applied.
@@ -363,18 +336,10 @@ __global__ __launch_bounds__(kMatchThreads) void pose_judge_kernel(PoseArgs a) {
     nf += front; np += par;
     if (a.obs_front) a.obs_front[(size_t)base + i] = front ? (par ? 2 : 1) : 0;
     if (a.X_out) {
-      // the midpoint of the two rays in the right frame, taken back to the left one: a value, not a decision
-      const PoseTerms w = pose_terms(P, P + 9, r.a0, r.a1, r.b0, r.b1);
-      const double l1 = w.m1 / w.d, l2 = w.m2 / w.d;
-      const double b[3] = {r.b0, r.b1, 1.0};
-      double y[3];
+      double x[3];
+      pose_midpoint(P, r, x);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) y[k] = 0.5 * (__builtin_fma(l1, w.ap[k], P[9 + k]) + l2 * b[k]) - P[9 + k];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double x = __builtin_fma(P[6 + k], y[2], __builtin_fma(P[3 + k], y[1], P[k] * y[0]));     // R^T (y - t)
-        a.X_out[(size_t)k * a.M + base + i] = front ? x : __builtin_nan("");
-      }
+      for (int k = 0; k < 3; ++k) a.X_out[(size_t)k * a.M + base + i] = front ? x[k] : __builtin_nan("");
     }
   }
   nf = block_sum_int(nf, &total[0]);
@@ -418,17 +383,6 @@ struct PoseWork {
   DevBuf<double> model, cand, normal;
   DevBuf<unsigned char> cand_ok;
 };
-
-static int pose_check_k(const char* who, const char* name, const double* K) {
-  if (K == nullptr) { set_error("%s: null %s", who, name); return SFM_E_SHAPE; }
-  bool finite = true;
-  for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(K[k]);
-  if (!finite || K[3] != 0.0 || K[6] != 0.0 || K[7] != 0.0 || K[8] != 1.0) {
-    set_error("%s: %s must be finite and upper triangular with %s[2][2] = 1", who, name, name);
-    return SFM_E_SHAPE;
-  }
-  return SFM_OK;
-}
 
 // Everything the entry points refuse, without a device.
 static int pose_check_args(const char* who, int n_sets, const int* set_ptr, long long M, const int* kind, const double* K_left,

@@ -67,6 +67,11 @@ POSE_CANDIDATES = 4
 POSE_KINDS = {"fundamental": POSE_FROM_F, "homography": POSE_FROM_H}
 POSE_SUMMARY = ("sets_posed", "sets_no_pose", "sets_empty", "sets_tied", "matches_front", "matches_not_front")
 POSE_OUTPUTS = ("normal", "cand_front", "n_front", "n_parallax", "best_cand", "status", "obs_front", "X", "summary")
+REFINE_EMPTY, REFINE_TOO_FEW, REFINE_BAD_POSE, REFINE_SINGULAR, REFINE_NONFINITE, REFINE_KEPT_INPUT = 1, 2, 4, 8, 16, 32
+REFINE_MIN_USED = 8
+REFINE_SUMMARY = ("sets_refined", "sets_bad_pose", "sets_too_few", "sets_kept_input", "matches_inlier", "matches_not_inlier")
+REFINE_OUTPUTS = ("F", "cost", "info", "n_used", "status", "obs_res", "obs_inlier", "obs_front", "X", "n_inliers", "n_front", "n_parallax",
+                  "summary")
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2
 CAM_EMPTY, CAM_NONFINITE, CAM_BEHIND, CAM_HELD = 1, 2, 4, 8
 COV_CAM_HELD, COV_CAM_PIVOT, COV_PT_EMPTY, COV_PT_SINGULAR = 8, 16, 4, 8
@@ -258,6 +263,14 @@ SIGNATURES = {
     "sfm_twoview_pose_test": [_dp, _dp, _dp, _dp, cd, _ip, _ip],
     "sfm_twoview_pose_pairs": [vp, ci, ci, ctypes.POINTER(ctypes.c_uint8), _dp, ci, _dp, _dp, cd, ci, _ip, _ip, _ip, _dp, _dp, _dp, _ip,
                                _ip, _ip, _ip, _ip, ctypes.POINTER(ctypes.c_uint8), _dp],
+    "sfm_twoview_refine": [ci, _ip, i64, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _dp, _dp, _dp, cd, ci, cd, cd, _dp, _dp, _dp, _dp, _dp,
+                           _ip, _ip, _dp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _ip, _ip, _lp],
+    "sfm_twoview_refine_dev": [ci, _ip, i64, vp, vp, vp, vp, vp, _dp, _dp, cd, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                               vp, vp, vp, vp],
+    "sfm_twoview_refine_test": [_dp, _dp, _dp, _dp, cd, cd, cd, cd, _dp, _dp],
+    "sfm_twoview_refine_pairs": [vp, ci, ci, ctypes.POINTER(ctypes.c_uint8), _dp, _dp, _dp, _dp, cd, ci, cd, cd, _ip, _ip, _ip, _dp, _dp,
+                                 _dp, _dp, _dp, _ip, _ip, _dp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), _dp, _ip,
+                                 _ip, _ip],
     "sfm_twoview_verify_pairs": [vp, ci, ci, cd, ci, ci, _ip, _ip, _ip, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _ip],
     "sfm_ba_covariance": [vp, cd, ci, ci, ctypes.POINTER(ctypes.c_uint8), ci, _dp, _dp, _ip, _ip, _dp],
     "sfm_ba_covariance_plan": [ci, _ip, _ip, _ip, _ip],
@@ -983,6 +996,97 @@ def twoview_pose_dev(set_ptr, n_obs, d_left, d_right, models, kinds, K_left, K_r
                                       dptr(model), iptr(kind), dptr(kl), dptr(kr), cos2_min, min_parallax, _vp(d_R_out), _vp(d_t_out),
                                       _vp(d_normal), _vp(d_cand_front), _vp(d_n_front), _vp(d_n_parallax), _vp(d_best_cand),
                                       _vp(d_status), _vp(d_obs_front), _vp(d_X_out), _vp(d_summary), _vp(stream)))
+
+
+# ---- refinement of a relative pose (sfm_twoview_refine*; no reference counterpart) ------------------------------------------
+def check_refine(n_sets, R_in, t_in, K_left, K_right, lam, iters, max_err2, cos2_min):
+    """The arguments of a ``twoview_refine`` call besides the matches, without a device: ``(R (n_sets, 9), t (n_sets, 3), K_left
+    (9,), K_right (9,), lam, iters, max_err2, cos2_min)`` converted or ValueError -- everything sfm_twoview_refine refuses."""
+    lam, max_err2, cos2_min = float(lam), float(max_err2), float(cos2_min)
+    if not lam >= 0.0:
+        raise ValueError("lam must be >= 0, got %r" % lam)
+    iters = _count("iters", iters)
+    if not max_err2 >= 0.0:
+        raise ValueError("max_err2 must be >= 0, got %r" % max_err2)
+    if not 0.0 <= cos2_min <= 1.0:
+        raise ValueError("cos2_min must be in [0, 1], got %r" % cos2_min)
+    R = f64(R_in).reshape(-1, 9) if n_sets else np.zeros((0, 9))
+    t = f64(t_in).reshape(-1, 3) if n_sets else np.zeros((0, 3))
+    if R.shape[0] != n_sets or t.shape[0] != n_sets:
+        raise ValueError("pose refinement: %d sets, %d rotations, %d translations" % (n_sets, R.shape[0], t.shape[0]))
+    out = []
+    for name, K in (("K_left", K_left), ("K_right", K_right)):
+        K = f64(K)
+        if K.shape != (3, 3) or not np.all(np.isfinite(K)) or K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 or K[2, 2] != 1:
+            raise ValueError("%s must be a finite upper triangular (3, 3) matrix with K[2][2] = 1" % name)
+        out.append(K.reshape(9).copy())
+    return np.ascontiguousarray(R), np.ascontiguousarray(t), out[0], out[1], lam, iters, max_err2, cos2_min
+
+
+def twoview_refine_test(R, t, K_left, K_right, xl, yl, xr, yr):
+    """``(r, J (5,))``: the signed Sampson distance in pixels of one match at the pose ``(R, t)`` as given and its Jacobian row in
+    the chart of the pose (sfm_twoview_refine_test: the functions the kernels call, on the host)."""
+    R, t, kl, kr = f64(R).reshape(9), f64(t).reshape(3), f64(K_left).reshape(9), f64(K_right).reshape(9)
+    r, J = ctypes.c_double(0.0), np.zeros(5)
+    check(load().sfm_twoview_refine_test(dptr(R), dptr(t), dptr(kl), dptr(kr), float(xl), float(yl), float(xr), float(yr), ctypes.byref(r),
+                                         dptr(J)))
+    return float(r.value), J
+
+
+def info_matrix(info):
+    """The (5, 5) matrix U = sum J^T J of the packed upper triangle ``info`` (15,) a refinement returns."""
+    U = np.zeros((5, 5))
+    U[np.triu_indices(5)] = np.asarray(info, dtype=np.float64).reshape(15)
+    return U + np.triu(U, 1).T
+
+
+def twoview_refine(set_ptr, left, right, R_in, t_in, K_left, K_right, lam=0.0, iters=6, max_err2=4.0, cos2_min=1.0, mask=None,
+                   outputs=REFINE_OUTPUTS):
+    """Refine the relative pose of every set of matches by damped Gauss-Newton on the Sampson distance in pixels and judge the
+    matches against the result (sfm_twoview_refine; the rule is in include/sfm_hip.h, 'refinement of a relative pose').
+    ``set_ptr``, ``left``, ``right``, ``mask`` as in ``twoview_pose``; ``R_in (S, 3, 3)``, ``t_in (S, 3)`` with
+    X_right = R X_left + t.  Returns a dict: ``R (S, 3, 3)``, ``t (S, 3)`` and, of ``REFINE_OUTPUTS``, what ``outputs`` names
+    (None otherwise): ``F (S, 3, 3)`` of Frobenius norm 1, ``cost (2, S)`` before and after, ``info (S, 15)`` (see
+    ``info_matrix``), ``n_used (S,)``, ``status (S,)`` of REFINE_* bits, ``obs_res (M,)`` the signed Sampson distance,
+    ``obs_inlier (M,)``, ``obs_front (M,)`` uint8, ``X (3, M)``, ``n_inliers``, ``n_front``, ``n_parallax (S,)`` over the
+    selected matches, ``summary (6,)`` int64 in the order of ``REFINE_SUMMARY``."""
+    set_ptr, left, right = check_twoview_sets(set_ptr, left, right)
+    n_sets, m = set_ptr.shape[0] - 1, left.shape[1]
+    R, t, kl, kr, lam, iters, max_err2, cos2_min = check_refine(n_sets, R_in, t_in, K_left, K_right, lam, iters, max_err2, cos2_min)
+    unknown = set(outputs) - set(REFINE_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (REFINE_OUTPUTS, sorted(unknown)))
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
+        if mask.shape[0] != m:
+            raise ValueError("mask must have one entry per match (%d), got %d" % (m, mask.shape[0]))
+    o = {"R": np.zeros((n_sets, 3, 3)), "t": np.zeros((n_sets, 3))}
+    shapes = {"F": ((n_sets, 3, 3), np.float64), "cost": ((2, n_sets), np.float64), "info": ((n_sets, 15), np.float64),
+              "n_used": (n_sets, np.int32), "status": (n_sets, np.int32), "obs_res": (m, np.float64), "obs_inlier": (m, np.uint8),
+              "obs_front": (m, np.uint8), "X": ((3, m), np.float64), "n_inliers": (n_sets, np.int32), "n_front": (n_sets, np.int32),
+              "n_parallax": (n_sets, np.int32), "summary": (6, np.int64)}
+    for name in REFINE_OUTPUTS:
+        o[name] = np.zeros(shapes[name][0], dtype=shapes[name][1]) if name in outputs else None
+    check(load().sfm_twoview_refine(n_sets, iptr(set_ptr), m, dptr(left), dptr(right), _u8ptr(mask), dptr(R), dptr(t), dptr(kl), dptr(kr),
+                                    lam, iters, max_err2, cos2_min, dptr(o["R"]), dptr(o["t"]), dptr(o["F"]), dptr(o["cost"]),
+                                    dptr(o["info"]), iptr(o["n_used"]), iptr(o["status"]), dptr(o["obs_res"]), _u8ptr(o["obs_inlier"]),
+                                    _u8ptr(o["obs_front"]), dptr(o["X"]), iptr(o["n_inliers"]), iptr(o["n_front"]),
+                                    iptr(o["n_parallax"]), _lptr(o["summary"])))
+    return o
+
+
+def twoview_refine_dev(set_ptr, n_obs, d_left, d_right, d_R_in, d_t_in, K_left, K_right, lam=0.0, iters=6, max_err2=4.0, cos2_min=1.0,
+                       d_mask=0, d_R_out=0, d_t_out=0, d_F_out=0, d_cost=0, d_info=0, d_n_used=0, d_status=0, d_obs_res=0, d_obs_inlier=0,
+                       d_obs_front=0, d_X_out=0, d_n_inliers=0, d_n_front=0, d_n_parallax=0, d_summary=0, stream=0):
+    """``twoview_refine`` on device pointers and a caller's stream (sfm_twoview_refine_dev); ``set_ptr`` and the intrinsics stay
+    host arrays, optional arrays are 0."""
+    set_ptr = np.ascontiguousarray(set_ptr, dtype=np.int32).ravel()
+    _R, _t, kl, kr, lam, iters, max_err2, cos2_min = check_refine(0, None, None, K_left, K_right, lam, iters, max_err2, cos2_min)
+    check(load().sfm_twoview_refine_dev(set_ptr.shape[0] - 1, iptr(set_ptr), int(n_obs), _vp(d_left), _vp(d_right), _vp(d_mask),
+                                        _vp(d_R_in), _vp(d_t_in), dptr(kl), dptr(kr), lam, iters, max_err2, cos2_min, _vp(d_R_out),
+                                        _vp(d_t_out), _vp(d_F_out), _vp(d_cost), _vp(d_info), _vp(d_n_used), _vp(d_status),
+                                        _vp(d_obs_res), _vp(d_obs_inlier), _vp(d_obs_front), _vp(d_X_out), _vp(d_n_inliers),
+                                        _vp(d_n_front), _vp(d_n_parallax), _vp(d_summary), _vp(stream)))
 
 
 def pnp_nonlinear(uv_pix, pts_h, intrinsic, rot0, loc0, lam, iters, quirks=QUIRKS_REFERENCE):
@@ -2054,6 +2158,35 @@ class TrackStore:
         n = n.value
         out = {"r_idx": r[:n], "q_idx": q[:n], "R": R, "t": t, "normal": normal, "cand_front": cand, "obs_front": front[:n],
                "X": X[:3 * n].reshape(3, n)}
+        out.update({name: int(v.value) for name, v in ints.items()})
+        return out
+
+    def refine_pairs(self, ref, que, R_in, t_in, K_left, K_right, lam=0.0, iters=6, max_err2=4.0, cos2_min=1.0, inlier=None):
+        """The pairs of ``pairs(ref, que)`` and the refinement of their pose on the device as one set
+        (sfm_twoview_refine_pairs): a dict with ``r_idx``, ``q_idx`` (n,), and ``R``, ``t``, ``F``, ``cost`` (2,), ``info`` (15,),
+        ``n_used``, ``status``, ``obs_res``, ``obs_inlier``, ``obs_front`` (n,), ``X`` (3, n), ``n_inliers``, ``n_front``,
+        ``n_parallax`` of ``twoview_refine`` for that set.  ``inlier`` (n,) is the optional mask of the matches that count; the
+        coordinates are not downloaded and nothing goes up but the pose, the intrinsics and that mask."""
+        R, t, kl, kr, lam, iters, max_err2, cos2_min = check_refine(1, [R_in], [t_in], K_left, K_right, lam, iters, max_err2, cos2_min)
+        cap = max(self.n_keys(ref), 1)
+        if inlier is not None:
+            inlier = np.ascontiguousarray(np.asarray(inlier) != 0, dtype=np.uint8).reshape(-1)
+            if inlier.shape[0] > cap:
+                raise ValueError("refine_pairs: %d mask entries for at most %d pairs" % (inlier.shape[0], cap))
+            inlier = np.concatenate((inlier, np.zeros(cap - inlier.shape[0], dtype=np.uint8)))
+        n = ctypes.c_int()
+        ints = {name: ctypes.c_int(0) for name in ("n_used", "status", "n_inliers", "n_front", "n_parallax")}
+        r, q = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+        inl, front, res = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype=np.uint8), np.zeros(cap)
+        Ro, to, F, cost, info, X = np.zeros((3, 3)), np.zeros(3), np.zeros((3, 3)), np.zeros(2), np.zeros(15), np.zeros(3 * cap)
+        check(self._lib.sfm_twoview_refine_pairs(self._h, int(ref), int(que), _u8ptr(inlier), dptr(R), dptr(t), dptr(kl), dptr(kr), lam, iters,
+                                                 max_err2, cos2_min, ctypes.byref(n), iptr(r), iptr(q), dptr(Ro), dptr(to), dptr(F),
+                                                 dptr(cost), dptr(info), ctypes.byref(ints["n_used"]), ctypes.byref(ints["status"]),
+                                                 dptr(res), _u8ptr(inl), _u8ptr(front), dptr(X), ctypes.byref(ints["n_inliers"]),
+                                                 ctypes.byref(ints["n_front"]), ctypes.byref(ints["n_parallax"])))
+        n = n.value
+        out = {"r_idx": r[:n], "q_idx": q[:n], "R": Ro, "t": to, "F": F, "cost": cost, "info": info, "obs_res": res[:n],
+               "obs_inlier": inl[:n], "obs_front": front[:n], "X": X[:3 * n].reshape(3, n)}
         out.update({name: int(v.value) for name, v in ints.items()})
         return out
 

@@ -363,6 +363,38 @@ class HipCamposeMixin:
                                   min_parallax, mask)
         return _pose_result(self, out, 0, 0, num)
 
+    def refine_relative_pose(self, matched_pairs, rot, centre, K_left, K_right, inliers=None, iters=6, damping=0.0, max_px=2.0,
+                             min_angle_deg=2.0):
+        """A relative pose refined on the matches themselves (one ``native.twoview_refine``; no reference counterpart): damped
+        Gauss-Newton on the Sampson distance in pixels over the five parameters of a calibrated pair, ``iters`` steps with
+        the damping ``damping``, over the matches ``inliers`` indexes (None: all).  ``rot`` and ``centre`` are in the convention
+        of ``estimate_relative_pose_robust`` in and out (``rot = R^T``, ``centre = -R^T t``); the baseline comes back with
+        unit length.  The matches are then judged against the refined pose at ``max_px`` pixels and ``min_angle_deg``.
+
+        Returns ``rot, centre (3, 1), rms_before, rms_after, inlier_idx, front_idx, info, status``: the RMS Sampson distance of
+        the matches that counted before and after (NaN without a pass), the indices of all matches within ``max_px`` and of those
+        in front of both cameras, ``info`` the (5, 5) matrix sum J^T J at the refined pose in its chart (three rotation and
+        two baseline-direction parameters; the caller derives conditioning or a covariance from it) and ``status``
+        (``native.REFINE_*`` bits).  With ``native.REFINE_KEPT_INPUT`` the pose that went in comes back.  ``refine_last`` keeps
+        the whole result of the call."""
+        if not 0.0 <= float(min_angle_deg) <= 90.0:
+            raise ValueError("min_angle_deg must be in [0, 90], got {!r}".format(min_angle_deg))
+        if not float(max_px) >= 0.0:
+            raise ValueError("max_px must be >= 0, got {!r}".format(max_px))
+        left = np.asarray(matched_pairs[0], dtype=np.float64)[0:2, :]
+        right = np.asarray(matched_pairs[1], dtype=np.float64)[0:2, :]
+        if left.shape != right.shape:
+            raise ValueError("matched pairs of different sizes : {} - {}".format(left.shape[1], right.shape[1]))
+        num = left.shape[1]
+        mask = None
+        if inliers is not None:
+            mask = np.zeros(num, dtype=np.uint8)
+            mask[np.asarray(inliers, dtype=np.int64)] = 1
+        R, t = pose_from_reference_convention(rot, centre)
+        out = native.twoview_refine([0, num], left, right, [R], [t], K_left, K_right, damping, iters, float(max_px) ** 2,
+                                    math.cos(math.radians(float(min_angle_deg))) ** 2, mask)
+        return _refine_result(self, out)
+
 
 class HipEpipolarMixin:
     """Eight-point RANSAC and essential-matrix extraction of ``EpipolarProcessor`` (epipolar_processor.py:22-95)
@@ -484,7 +516,7 @@ class HipEpipolarMixin:
         return out
 
     def initialise_pairs(self, list_of_matched_pairs, K, K_right=None, max_px=2.0, max_hyp=128, iteration=2, planar_ratio=0.8,
-                         min_angle_deg=2.0, min_parallax=8):
+                         min_angle_deg=2.0, min_parallax=8, refine_iters=0):
         """Verdict and relative pose of several sets of matches (no reference counterpart): ``classify_matches`` and then ONE
         ``native.twoview_pose`` over all sets, every set posed from the model its verdict trusts with that model's inliers
         voting: F for ``"general"``, H for ``"degenerate"``; a ``"none"`` set is passed with an empty mask and comes back
@@ -492,9 +524,18 @@ class HipEpipolarMixin:
         view.  Returns one dict per set: ``verdict``, ``kind``, ``R``, ``t`` (X_right = R X_left + t), ``rot``, ``centre`` (the
         reference's convention, see ``estimate_relative_pose_robust``), ``normal``, ``front`` (indices), ``n_front``,
         ``n_parallax``, ``cand_front``, ``best_cand``, ``status``, and the entries of ``classify_matches``.  A pair to start
-        from has a pose, no ``native.POSE_NO_PARALLAX`` and the largest ``n_parallax``.  ``pose_last`` keeps the summary."""
+        from has a pose, no ``native.POSE_NO_PARALLAX`` and the largest ``n_parallax``.  ``pose_last`` keeps the summary.
+
+        With ``refine_iters > 0`` ONE ``native.twoview_refine`` follows over all sets, each pose refined on its matches in front
+        (``obs_front > 0``) by that many Gauss-Newton steps and judged at ``max_px``; a set with ``native.POSE_NO_POSE`` or
+        ``native.POSE_NO_PARALLAX`` is passed with an empty mask and comes back as it went in (after a pure rotation the
+        baseline is not determined and the iteration would wander).  Every dict then also has ``R_refined``, ``t_refined``,
+        ``rot_refined``, ``centre_refined``, ``F_refined`` (Frobenius norm 1, for guided matching), ``refine_inliers`` and
+        ``refine_front`` (indices), ``refine_cost`` (before, after), ``refine_used`` and ``refine_status``
+        (``native.REFINE_*`` bits); ``refine_last`` keeps the summary."""
         if not 0.0 <= float(min_angle_deg) <= 90.0:
             raise ValueError("min_angle_deg must be in [0, 90], got {!r}".format(min_angle_deg))
+        refine_iters = native._count("refine_iters", refine_iters)
         verdicts = self.classify_matches(list_of_matched_pairs, max_px, max_hyp, iteration, planar_ratio)
         set_ptr, left, right = self._twoview_sets(list_of_matched_pairs)
         mask = np.zeros(left.shape[1], dtype=np.uint8)
@@ -520,6 +561,18 @@ class HipEpipolarMixin:
                           "n_front": int(out["n_front"][s]), "n_parallax": int(out["n_parallax"][s]),
                           "cand_front": out["cand_front"][s], "best_cand": int(out["best_cand"][s]), "status": int(out["status"][s])})
             result.append(entry)
+        if refine_iters > 0:
+            skip = native.POSE_NO_POSE | native.POSE_NO_PARALLAX
+            front = (out["obs_front"] > 0).astype(np.uint8)
+            for s in range(len(verdicts)):
+                if out["status"][s] & skip:
+                    front[set_ptr[s]:set_ptr[s + 1]] = 0
+            ref = native.twoview_refine(set_ptr, left, right, out["R"], out["t"], K, K if K_right is None else K_right, 0.0, refine_iters,
+                                        float(max_px) ** 2, math.cos(math.radians(float(min_angle_deg))) ** 2, front,
+                                        outputs=("F", "cost", "n_used", "status", "obs_inlier", "obs_front", "summary"))
+            self.refine_last = {"summary": ref["summary"], "status": ref["status"].tolist()}
+            for s, entry in enumerate(result):
+                entry.update(_refined_entry(ref, s, set_ptr[s], set_ptr[s + 1], entry["best_cand"] >= 0))
         return result
 
 
@@ -1751,13 +1804,54 @@ def _pose_result(owner, out, s, lo, hi):
     return rot, (-R.T @ t).reshape(3, 1), np.flatnonzero(out["obs_front"][lo:hi]).tolist(), counts
 
 
-def pose_pairs(tracker, ref_idx, que_idx, model, kind, K_left, K_right, inlier=None, min_angle_deg=2.0, min_parallax=8):
+def pose_from_reference_convention(rot, centre):
+    """(R, t) with X_right = R X_left + t and |t| = 1 of a pose given as ``rot = R^T`` and ``centre = -R^T t``; a centre at the
+    origin gives t = 0, which the refinement answers with ``native.REFINE_BAD_POSE``."""
+    R = np.ascontiguousarray(np.asarray(rot, dtype=np.float64).reshape(3, 3).T)
+    t = -R @ np.asarray(centre, dtype=np.float64).reshape(3)
+    norm = np.linalg.norm(t)
+    return R, (t / norm if norm > 0 and np.isfinite(norm) else t)
+
+
+def _refined_entry(ref, s, lo, hi, posed):
+    """The keys a refinement adds to the dict of set ``s`` (matches lo .. hi - 1) of ``initialise_pairs`` / ``pose_pairs``."""
+    R, t = ref["R"][s], ref["t"][s]
+    return {"R_refined": R, "t_refined": t, "rot_refined": R.T.copy() if posed else np.identity(3),
+            "centre_refined": (-R.T @ t).reshape(3, 1), "F_refined": ref["F"][s],
+            "refine_inliers": np.flatnonzero(ref["obs_inlier"][lo:hi]).tolist(),
+            "refine_front": np.flatnonzero(ref["obs_front"][lo:hi]).tolist(), "refine_cost": ref["cost"][:, s].copy(),
+            "refine_used": int(ref["n_used"][s]), "refine_status": int(ref["status"][s])}
+
+
+def _refine_result(owner, out):
+    """(rot, centre, rms before, rms after, inlier indices, front indices, info (5, 5), status) of the one set of a
+    ``native.twoview_refine`` result, kept as ``owner.refine_last``."""
+    R, t = out["R"][0], out["t"][0]
+    used, status = int(out["n_used"][0]), int(out["status"][0])
+    passes = used >= native.REFINE_MIN_USED and not status & native.REFINE_BAD_POSE
+    rms = np.sqrt(out["cost"][:, 0] / used) if passes else np.full(2, np.nan)
+    last = {name: (out[name][0] if name in ("F", "info", "n_used", "status", "n_inliers", "n_front", "n_parallax") else out[name])
+            for name in native.REFINE_OUTPUTS if name != "summary"}
+    last.update({"R": R, "t": t, "cost": out["cost"][:, 0].copy()})
+    owner.refine_last = last
+    return (R.T.copy(), (-R.T @ t).reshape(3, 1), float(rms[0]), float(rms[1]), np.flatnonzero(out["obs_inlier"]).tolist(),
+            np.flatnonzero(out["obs_front"]).tolist(), native.info_matrix(out["info"][0]), status)
+
+
+def pose_pairs(tracker, ref_idx, que_idx, model, kind, K_left, K_right, inlier=None, min_angle_deg=2.0, min_parallax=8, refine_iters=0,
+               max_px=2.0):
     """``estimate_relative_pose_robust`` over the pairs ``tracker.generate_matched_pairs(ref_idx, que_idx)`` returns
     (``tracker``: a ``HipDeviceKeyTracker``) without leaving the device (``TrackStore.pose_pairs``: the pairs are gathered
     into device buffers and posed on the same stream; nothing goes up but the model, the intrinsics and the optional mask
     ``inlier`` (n,) of ``verify_pairs``, no coordinate comes down).  Returns ``r_idx (1, n), q_idx (1, n), rot, centre,
     front_idx, counts`` as that method does; ``tracker.pose_last`` keeps what its ``pose_last`` keeps.  A function of the
-    module, like ``verify_pairs``."""
+    module, like ``verify_pairs``.
+
+    With ``refine_iters > 0`` ONE ``TrackStore.refine_pairs`` follows on the same pairs, still without a coordinate coming
+    down: the pose refined on its matches in front by that many Gauss-Newton steps and judged at ``max_px`` pixels, with an
+    empty mask if the pose has ``native.POSE_NO_POSE`` or ``native.POSE_NO_PARALLAX``.  ``counts`` then also has the keys
+    ``initialise_pairs`` adds (``R_refined`` ... ``refine_status``); the pose returned stays the unrefined one."""
+    refine_iters = native._count("refine_iters", refine_iters)
     n_views = len(tracker.track_list)
     if ref_idx < 0 or que_idx < 0 or ref_idx >= n_views or que_idx >= n_views:
         print('{}:{} - invalid ref_idx {} or invalid que_idx {}'.format(
@@ -1772,6 +1866,17 @@ def pose_pairs(tracker, ref_idx, que_idx, model, kind, K_left, K_right, inlier=N
            "obs_front": o["obs_front"], "X": o["X"]}
     out.update({name: np.array([o[name]]) for name in ("n_front", "n_parallax", "best_cand", "status")})
     rot, centre, front, counts = _pose_result(tracker, out, 0, 0, num)
+    if refine_iters > 0:
+        if not float(max_px) >= 0.0:
+            raise ValueError("max_px must be >= 0, got {!r}".format(max_px))
+        skip = o["status"] & (native.POSE_NO_POSE | native.POSE_NO_PARALLAX)
+        mask = np.zeros(num, dtype=np.uint8) if skip else (o["obs_front"] > 0).astype(np.uint8)
+        f = tracker._store.refine_pairs(ref_idx, que_idx, o["R"], o["t"], K_left, K_right, 0.0, refine_iters, float(max_px) ** 2,
+                                        math.cos(math.radians(float(min_angle_deg))) ** 2, mask)
+        ref = {"R": f["R"][None], "t": f["t"][None], "F": f["F"][None], "cost": f["cost"].reshape(2, 1), "obs_inlier": f["obs_inlier"],
+               "obs_front": f["obs_front"], "n_used": np.array([f["n_used"]]), "status": np.array([f["status"]])}
+        counts.update(_refined_entry(ref, 0, 0, num, counts["best_cand"] >= 0))
+        tracker.refine_last = f
     return o["r_idx"].reshape(1, num).astype(int), o["q_idx"].reshape(1, num).astype(int), rot, centre, front, counts
 
 
