@@ -1213,6 +1213,52 @@ int sfm_twoview_refine_dev(int n_sets, const int* set_ptr /*host*/, int64_t M, c
 int sfm_twoview_refine_test(const double R[9], const double t[3], const double K_left[9], const double K_right[9], double xl,
                             double yl, double xr, double yr, double* r, double J[5]);
 
+/* ---- robust essential matrix: sampled five-point hypotheses ----------------------------------------------------------
+ * The calibrated estimator of the two-view chain: every hypothesis comes from five matches and the caller's intrinsics
+ * and is an essential matrix already.  Sets are laid out as in sfm_twoview_ransac: set_ptr[n_sets + 1] on the host, left
+ * and right [2][M] pixels; K_left, K_right as in sfm_twoview_pose (upper triangular, K[2][2] = 1, else SFM_E_SHAPE).  Per
+ * set of n matches:
+ *   1. n < 6: SFM_ESSENTIAL_TOO_FEW.
+ *   2. Rays a = K_left^-1 (x_l, y_l, 1)^T, b = K_right^-1 (x_r, y_r, 1)^T by back substitution.
+ *   3. The test of a match against an essential matrix E is twoview_inlier(F, ...): the squared Sampson distance in
+ *      pixels against max_err2, with F = K_r^-T E K_l^-1 formed by substitution through the triangular intrinsics and
+ *      scaled to Frobenius norm 1 with its entry of largest magnitude positive.  One function forms F in the hypothesis
+ *      kernel and on the host; one function tests in the hypothesis kernel, the score and the judge.
+ *   4. H = max_hyp hypotheses (0 = 128; 1 .. 65 536).  Hypothesis h uses, for k = 0 .. 4, the match
+ *      lo_k + mix(5 h + k) mod (hi_k - lo_k), lo_k = floor(k n / 5), hi_k = floor((k + 1) n / 5), mix the splitmix64 finaliser.
+ *   5. The solutions of a sample: with N0 .. N3 a basis of the null space of the 5x9 matrix of rows b (x) a (entry
+ *      3 i + j multiplies b_i a_j), the real solutions (x, y, z) of det E = 0 and 2 E E^T E - tr(E E^T) E = 0 for
+ *      E = x N0 + y N1 + z N2 + N3.  Each E is scaled to Frobenius norm 1 with its entry of largest magnitude positive
+ *      (the lowest index on a tie); the solutions are numbered r = 0, 1, ... by ascending E[0] of that form.  At most ten;
+ *      non-finite ones are left out.  How null space and roots are found is not part of the rule.
+ *   6. Sample gate: a candidate is invalid unless its own five matches are inliers of it.
+ *   7. Score, lexicographic: the inlier count over all n matches, then the lower h, then the lower r.  A winner needs a
+ *      count of at least 6, otherwise SFM_ESSENTIAL_NO_MODEL.  There is no refit (compose sfm_twoview_refine).
+ *   8. Outputs, all optional but E_out: E_out[n_sets][9] canonical as in step 5; F_out[n_sets][9] as in step 3 (the norm
+ *      and sign of sfm_twoview_ransac's F_out); obs_inlier[M], n_inliers, best_hyp, best_root (-1 without a model);
+ *      n_valid[n_sets] the candidates that passed the gate; status; summary[6]: sets solved | NO_MODEL | TOO_FEW | 0 |
+ *      matches flagged inlier | matches of solved sets flagged outlier.  Zeros for TOO_FEW and NO_MODEL.
+ *  No floating-point atomic, integer counts: a set's bits depend on its matches, the intrinsics and the options only.
+ *  The _dev form takes device pointers (set_ptr and the intrinsics stay host arrays; d_summary is int64[6] on the device)
+ *  and a stream (NULL = the library stream).  Both forms check their arguments (a NaN or negative max_err2, max_hyp out of
+ *  range, bad offsets, bad intrinsics: SFM_E_SHAPE) before they look for a device. */
+#define SFM_ESSENTIAL_TOO_FEW   1   /* the set has fewer than 6 matches */
+#define SFM_ESSENTIAL_NO_MODEL  2   /* no valid candidate with at least 6 inliers */
+int sfm_essential_ransac(int n_sets, const int* set_ptr /*host [n_sets+1]*/, int64_t M, const double* left /*[2][M]*/,
+                         const double* right /*[2][M]*/, const double K_left[9], const double K_right[9], double max_err2,
+                         int max_hyp, double* E_out /*[n_sets][9]*/, double* F_out /*[n_sets][9]*/, unsigned char* obs_inlier,
+                         int* n_inliers, int* best_hyp, int* best_root, int* n_valid, int* status, int64_t* summary /*[6]*/);
+int sfm_essential_ransac_dev(int n_sets, const int* set_ptr /*host*/, int64_t M, const double* d_left, const double* d_right,
+                             const double K_left[9] /*host*/, const double K_right[9] /*host*/, double max_err2, int max_hyp,
+                             double* d_E_out, double* d_F_out, unsigned char* d_obs_inlier, int* d_n_inliers, int* d_best_hyp,
+                             int* d_best_root, int* d_n_valid, int* d_status, int64_t* d_summary, void* hip_stream);
+/* Step 4 on the host: the five indices of hypothesis h of a set of n matches; returns H (0 for n < 6 or a bad max_hyp).
+ * idx is written only for 0 <= h < H. */
+int sfm_essential_sample(int n, int max_hyp, int h, int idx[5]);
+/* Step 5 on the host, by the function the hypothesis kernel runs: a[5][2], b[5][2] the first two components of the rays,
+ * E[10][9] the canonical solutions in the order of step 5 (zeros beyond *n). */
+int sfm_essential_solve(const double* a /*[5][2]*/, const double* b /*[5][2]*/, double* E /*[10][9]*/, int* n);
+
 /* ---- SIFT detection: ViewProcessor.__extract_keys (view_processor.py:151-164, 199-202) --------------------------
  * cv.SIFT_create().detectAndCompute(img, None) by the contract of INTEGRATION.md 'SIFT detection' (firstOctave -1,
  * nfeatures 0, no mask): keypoints sorted by (x, y asc; size desc; angle asc; response desc; octave desc) without

@@ -2,8 +2,9 @@
 // (sfm_tri_ransac.hip) and the triples of a camera's observations (sfm_resect.hip), both in lexicographic order, all of
 // them up to max_hyp, else evenly spaced.  No random number anywhere.  The floating-point estimates below only seed integer
 // searches that end at the exact answer, so the results do not depend on how the including file contracts them.
-// The eight-match samples of the robust two-view geometry (sfm_twoview.hip) and the four-match samples of the robust
-// homography (sfm_homography.hip) are drawn by a stratified integer sampler.
+// The eight-match samples of the robust two-view geometry (sfm_twoview.hip), the four-match samples of the robust
+// homography (sfm_homography.hip) and the five-match samples of the robust essential matrix (sfm_essential.hip) are drawn
+// by a stratified integer sampler.
 #pragma once
 
 #include <cmath>
@@ -81,6 +82,13 @@ __host__ __device__ inline int twoview_sample_index(int n, int h, int k) {
 __host__ __device__ inline int homography_sample_index(int n, int h, int k) {
   const long long lo = (long long)k * n / 4, hi = (long long)(k + 1) * n / 4;
   return (int)(lo + (long long)(splitmix64_mix(4ULL * (unsigned long long)h + (unsigned long long)k) % (unsigned long long)(hi - lo)));
+}
+
+// ---- five-index samples of a set of n >= 6 matches (sfm_essential.hip): the same sampler over fifths, stratum k being
+// floor(k n / 5) .. floor((k + 1) n / 5) - 1 (never empty) and hypothesis h taking lo_k + mix(5 h + k) mod (hi_k - lo_k).
+__host__ __device__ inline int essential_sample_index(int n, int h, int k) {
+  const long long lo = (long long)k * n / 5, hi = (long long)(k + 1) * n / 5;
+  return (int)(lo + (long long)(splitmix64_mix(5ULL * (unsigned long long)h + (unsigned long long)k) % (unsigned long long)(hi - lo)));
 }
 
 }  // namespace sfm

@@ -47,10 +47,12 @@ __device__ __forceinline__ int hyp_owner(const int* hyp_off, int n_groups, int g
 // doubles each, bit r of ok[] saying whether candidate r is valid.  The hypotheses pass through lds[BATCH * STRIDE] in
 // batches of BATCH (okb[BATCH] their valid bits, read uniformly); test(model, k) is the lane's observation k against the
 // model, which every lane reads from the same LDS address (a broadcast), and must be false for a slot beyond the group.
-// A wave adds the popcounts of its PER ballots and issues one integer atomicAdd per candidate: counts[][CANDS].
-template <int THREADS, int BATCH, int STRIDE, int CANDS, int PER, class Test>
-__device__ __forceinline__ void robust_score_block(const double* hyp, const unsigned char* ok, int* counts, int h0, int H,
-                                                   double* lds, unsigned char* okb, Test test) {
+// A wave adds the popcounts of its PER ballots and issues one integer atomicAdd per candidate: counts[][CANDS].  Ok is the
+// word that holds the valid bits of a hypothesis: a byte up to eight candidates, wider for the ten of the five-point solver.
+template <int THREADS, int BATCH, int STRIDE, int CANDS, int PER, class Test, class Ok>
+__device__ __forceinline__ void robust_score_block(const double* hyp, const Ok* ok, int* counts, int h0, int H,
+                                                   double* lds, Ok* okb, Test test) {
+  static_assert(CANDS <= 8 * (int)sizeof(Ok), "a valid bit per candidate");
   const int tid = threadIdx.x;
   for (int hb = 0; hb < H; hb += BATCH) {
     const int nb = min(BATCH, H - hb);

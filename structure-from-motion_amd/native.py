@@ -61,6 +61,10 @@ HOMOGRAPHY_TOO_FEW, HOMOGRAPHY_NO_MODEL, HOMOGRAPHY_KEPT_HYPOTHESIS = 1, 2, 4
 HOMOGRAPHY_MAX_HYP, HOMOGRAPHY_DEFAULT_HYP, HOMOGRAPHY_MIN_MATCHES = 65536, 128, 5
 HOMOGRAPHY_SUMMARY = TWOVIEW_SUMMARY
 HOMOGRAPHY_OUTPUTS = TWOVIEW_OUTPUTS
+ESSENTIAL_TOO_FEW, ESSENTIAL_NO_MODEL = 1, 2
+ESSENTIAL_MAX_HYP, ESSENTIAL_DEFAULT_HYP, ESSENTIAL_MIN_MATCHES, ESSENTIAL_MAX_SOLUTIONS = 65536, 128, 6, 10
+ESSENTIAL_SUMMARY = ("sets_solved", "sets_no_model", "sets_too_few", "unused", "matches_inlier", "matches_outlier")
+ESSENTIAL_OUTPUTS = ("F", "inlier", "n_inliers", "best_hyp", "best_root", "n_valid", "status", "summary")
 POSE_FROM_F, POSE_FROM_H = 0, 1
 POSE_EMPTY, POSE_NO_MODEL, POSE_NO_POSE, POSE_TIED, POSE_NO_PARALLAX = 1, 2, 4, 8, 16
 POSE_CANDIDATES = 4
@@ -257,6 +261,11 @@ SIGNATURES = {
     "sfm_homography_ransac": [ci, _ip, i64, _dp, _dp, cd, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
     "sfm_homography_ransac_dev": [ci, _ip, i64, vp, vp, cd, ci, ci, vp, vp, vp, vp, vp, vp, vp],
     "sfm_homography_sample": [ci, ci, ci, _ip],
+    "sfm_essential_ransac": [ci, _ip, i64, _dp, _dp, _dp, _dp, cd, ci, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _ip,
+                             _ip, _lp],
+    "sfm_essential_ransac_dev": [ci, _ip, i64, vp, vp, _dp, _dp, cd, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "sfm_essential_sample": [ci, ci, ci, _ip],
+    "sfm_essential_solve": [_dp, _dp, _dp, _ip],
     "sfm_twoview_pose": [ci, _ip, i64, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _dp, _dp, cd, ci, _dp, _dp, _dp, _ip, _ip, _ip,
                          _ip, _ip, ctypes.POINTER(ctypes.c_uint8), _dp, _lp],
     "sfm_twoview_pose_dev": [ci, _ip, i64, vp, vp, vp, _dp, _ip, _dp, _dp, cd, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -911,6 +920,84 @@ def homography_ransac_dev(set_ptr, n_obs, d_left, d_right, max_err2, max_hyp=0, 
     check(load().sfm_homography_ransac_dev(set_ptr.shape[0] - 1, iptr(set_ptr), int(n_obs), _vp(d_left), _vp(d_right), max_err2,
                                            max_hyp, iters, _vp(d_H_out), _vp(d_inlier), _vp(d_n_inliers), _vp(d_best_hyp),
                                            _vp(d_status), _vp(d_summary), _vp(stream)))
+
+
+# ---- robust essential matrix (sfm_essential_*; no reference counterpart) ------------------------------------------------
+def _check_intrinsics(K_left, K_right):
+    out = []
+    for name, K in (("K_left", K_left), ("K_right", K_right)):
+        K = f64(K)
+        if K.shape != (3, 3) or not np.all(np.isfinite(K)) or K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 or K[2, 2] != 1:
+            raise ValueError("%s must be a finite upper triangular (3, 3) matrix with K[2][2] = 1" % name)
+        out.append(K.reshape(9).copy())
+    return out[0], out[1]
+
+
+def check_essential(set_ptr, left, right, K_left, K_right, max_err2, max_hyp=0):
+    """The arguments of an ``essential_ransac`` call, without a device: ``(set_ptr int32 (S + 1,), left (2, M), right (2, M),
+    K_left (9,), K_right (9,), max_err2, max_hyp)`` converted or ValueError -- everything sfm_essential_ransac refuses."""
+    max_err2, _, max_hyp, _, _ = _check_robust(max_err2, max_hyp, 0)
+    K_left, K_right = _check_intrinsics(K_left, K_right)
+    set_ptr, left, right = check_twoview_sets(set_ptr, left, right)
+    return set_ptr, left, right, K_left, K_right, max_err2, max_hyp
+
+
+def essential_sample(n, max_hyp, h):
+    """``(H, idx)``: the hypothesis count of a set of ``n`` matches and the five ascending match indices of hypothesis
+    ``h`` (sfm_essential_sample; host only).  ``idx`` is five times -1 when ``h`` is not in ``0 .. H - 1``."""
+    idx = np.full(5, -1, dtype=np.int32)
+    count = int(load().sfm_essential_sample(int(n), int(max_hyp), int(h), iptr(idx)))
+    return count, tuple(int(i) for i in idx)
+
+
+def essential_solve(a, b):
+    """The essential matrices of five matches with the rays ``(a[k, 0], a[k, 1], 1)`` and ``(b[k, 0], b[k, 1], 1)``, b^T E a = 0
+    (sfm_essential_solve: the solver the hypothesis kernel runs, on the host): ``E (n, 3, 3)``, n <= 10, each of Frobenius
+    norm 1 with its entry of largest magnitude positive, by ascending ``E[0, 0]``."""
+    a, b = f64(a), f64(b)
+    if a.shape != (5, 2) or b.shape != (5, 2):
+        raise ValueError("a and b must both be (5, 2), got %r and %r" % (a.shape, b.shape))
+    E = np.zeros((ESSENTIAL_MAX_SOLUTIONS, 3, 3))
+    n = np.zeros(1, dtype=np.int32)
+    check(load().sfm_essential_solve(dptr(a), dptr(b), dptr(E), iptr(n)))
+    return E[:int(n[0])].copy()
+
+
+def essential_ransac(set_ptr, left, right, K_left, K_right, max_err2, max_hyp=0, outputs=ESSENTIAL_OUTPUTS):
+    """Robust essential matrix of every set of matches (sfm_essential_ransac; the rule is in include/sfm_hip.h, 'robust
+    essential matrix'): stratified five-point hypotheses, up to ten solutions each, scored by their inlier count under the
+    squared Sampson distance ``max_err2`` (pixels squared); no refit.  ``set_ptr``, ``left``, ``right`` as in
+    ``twoview_ransac``, the intrinsics as in ``twoview_pose``.  Returns a dict: ``E (S, 3, 3)`` canonical (zeros without a
+    model) and, of ``ESSENTIAL_OUTPUTS``, what ``outputs`` names (None otherwise): ``F (S, 3, 3)`` in pixels with the norm and
+    sign of ``twoview_ransac``'s, ``inlier (M,) uint8, n_inliers (S,), best_hyp (S,), best_root (S,), n_valid (S,), status
+    (S,) of ESSENTIAL_* bits, summary (6,) int64`` in the order of ``ESSENTIAL_SUMMARY``."""
+    set_ptr, left, right, K_left, K_right, max_err2, max_hyp = check_essential(set_ptr, left, right, K_left, K_right, max_err2, max_hyp)
+    unknown = set(outputs) - set(ESSENTIAL_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (ESSENTIAL_OUTPUTS, sorted(unknown)))
+    n_sets, n_obs = set_ptr.shape[0] - 1, left.shape[1]
+    o = {"E": np.zeros((n_sets, 3, 3)), "F": np.zeros((n_sets, 3, 3)), "inlier": np.zeros(n_obs, dtype=np.uint8),
+         "n_inliers": np.zeros(n_sets, dtype=np.int32), "best_hyp": np.zeros(n_sets, dtype=np.int32),
+         "best_root": np.zeros(n_sets, dtype=np.int32), "n_valid": np.zeros(n_sets, dtype=np.int32),
+         "status": np.zeros(n_sets, dtype=np.int32), "summary": np.zeros(6, dtype=np.int64)}
+    cast = {"F": dptr, "inlier": _u8ptr, "summary": _lptr}
+    ptrs = [cast.get(name, iptr)(o[name]) if name in outputs else None for name in ESSENTIAL_OUTPUTS]
+    check(load().sfm_essential_ransac(n_sets, iptr(set_ptr), n_obs, dptr(left), dptr(right), dptr(K_left), dptr(K_right), max_err2,
+                                      max_hyp, dptr(o["E"]), *ptrs))
+    return {name: (o[name] if name == "E" or name in outputs else None) for name in o}
+
+
+def essential_ransac_dev(set_ptr, n_obs, d_left, d_right, K_left, K_right, max_err2, max_hyp=0, d_E_out=0, d_F_out=0, d_inlier=0,
+                         d_n_inliers=0, d_best_hyp=0, d_best_root=0, d_n_valid=0, d_status=0, d_summary=0, stream=0):
+    """``essential_ransac`` on device pointers and a caller's stream (sfm_essential_ransac_dev); ``set_ptr`` and the
+    intrinsics stay host arrays, optional arrays are 0."""
+    set_ptr = np.ascontiguousarray(set_ptr, dtype=np.int32).ravel()
+    max_err2, _, max_hyp, _, _ = _check_robust(max_err2, max_hyp, 0)
+    K_left, K_right = _check_intrinsics(K_left, K_right)
+    check(load().sfm_essential_ransac_dev(set_ptr.shape[0] - 1, iptr(set_ptr), int(n_obs), _vp(d_left), _vp(d_right), dptr(K_left),
+                                          dptr(K_right), max_err2, max_hyp, _vp(d_E_out), _vp(d_F_out), _vp(d_inlier),
+                                          _vp(d_n_inliers), _vp(d_best_hyp), _vp(d_best_root), _vp(d_n_valid), _vp(d_status),
+                                          _vp(d_summary), _vp(stream)))
 
 
 # ---- relative pose of a verified pair (sfm_twoview_pose*; no reference counterpart) ------------------------------------

@@ -395,6 +395,38 @@ class HipCamposeMixin:
                                     math.cos(math.radians(float(min_angle_deg))) ** 2, mask)
         return _refine_result(self, out)
 
+    def estimate_relative_pose_minimal(self, matched_pairs, K_left, K_right, max_px=2.0, max_hyp=128, refine_iters=6, min_angle_deg=2.0):
+        """The relative pose of a calibrated pair straight from its matches (no reference counterpart): ONE
+        ``native.essential_ransac`` (five-point hypotheses at ``max_px`` pixels of Sampson distance), then ONE
+        ``native.twoview_pose`` with the winner's pixel matrix as a fundamental matrix and its inliers voting, then ONE
+        ``native.twoview_refine`` of ``refine_iters`` Gauss-Newton steps over the matches in front, judged at ``max_px`` and
+        ``min_angle_deg``.  ``matched_pairs`` is [ref_pts, que_pts], (2 or 3, n) pixel coordinates.
+
+        Returns what ``refine_relative_pose`` returns, in the reference's convention: ``rot, centre (3, 1), rms_before,
+        rms_after, inlier_idx, front_idx, info, status``.  Without a model or without a pose the refinement sees an empty
+        mask and answers with ``native.REFINE_*`` bits; what the pose call left comes back.  ``essential_last`` keeps the
+        result of the first call, ``pose_last`` and ``refine_last`` those of the other two."""
+        if not 0.0 <= float(min_angle_deg) <= 90.0:
+            raise ValueError("min_angle_deg must be in [0, 90], got {!r}".format(min_angle_deg))
+        if not float(max_px) >= 0.0:
+            raise ValueError("max_px must be >= 0, got {!r}".format(max_px))
+        left = np.asarray(matched_pairs[0], dtype=np.float64)[0:2, :]
+        right = np.asarray(matched_pairs[1], dtype=np.float64)[0:2, :]
+        if left.shape != right.shape:
+            raise ValueError("matched pairs of different sizes : {} - {}".format(left.shape[1], right.shape[1]))
+        num = left.shape[1]
+        cos2 = math.cos(math.radians(float(min_angle_deg))) ** 2
+        ess = native.essential_ransac([0, num], left, right, K_left, K_right, float(max_px) ** 2, max_hyp)
+        self.essential_last = _essential_entry(ess, 0, 0, num)
+        posed = native.twoview_pose([0, num], left, right, ess["F"], [native.POSE_FROM_F], K_left, K_right, cos2, 1, ess["inlier"])
+        _pose_result(self, posed, 0, 0, num)
+        front = (posed["obs_front"] > 0).astype(np.uint8)
+        if posed["best_cand"][0] < 0:
+            front[:] = 0
+        out = native.twoview_refine([0, num], left, right, posed["R"], posed["t"], K_left, K_right, 0.0, refine_iters, float(max_px) ** 2,
+                                    cos2, front)
+        return _refine_result(self, out)
+
 
 class HipEpipolarMixin:
     """Eight-point RANSAC and essential-matrix extraction of ``EpipolarProcessor`` (epipolar_processor.py:22-95)
@@ -479,6 +511,25 @@ class HipEpipolarMixin:
         self.homography = H[0] / H[0][2][2]
         return np.flatnonzero(inlier).tolist()
 
+    def determine_essential_mat_robust(self, matched_pairs, K_left, K_right, max_sampson_px=2.0, max_hyp=128):
+        """The essential matrix of one set of matches of a calibrated pair (``native.essential_ransac``; no reference
+        counterpart): stratified five-point hypotheses without a random number, up to ten solutions each, scored by the
+        Sampson distance in pixels; no refit.  Sets ``self.esse_mat`` to the canonical matrix (Frobenius norm 1) and
+        ``self.fund_mat`` to its pixel matrix divided by ``F[2][2]``, and returns the inlier indices (a list); without a model
+        both are left as they were and the list is empty.  ``essential_last`` keeps E, F (norm 1), hypothesis, root, the
+        number of valid candidates, status and the summary."""
+        if not float(max_sampson_px) >= 0.0:
+            raise ValueError("max_sampson_px must be >= 0, got {!r}".format(max_sampson_px))
+        set_ptr, left, right = self._twoview_sets([matched_pairs])
+        out = native.essential_ransac(set_ptr, left, right, K_left, K_right, float(max_sampson_px) ** 2, max_hyp)
+        self.essential_last = _essential_entry(out, 0, 0, left.shape[1])
+        self.essential_last["summary"] = out["summary"]
+        if out["status"][0]:
+            return []
+        self.esse_mat = out["E"][0]
+        self.fund_mat = out["F"][0] / out["F"][0][2][2]
+        return self.essential_last["inliers"]
+
     def classify_matches(self, list_of_matched_pairs, max_px=2.0, max_hyp=128, iteration=2, planar_ratio=0.8):
         """Both two-view models of several sets of matches and a verdict per set (no reference counterpart): ONE
         ``native.twoview_ransac`` call and ONE ``native.homography_ransac`` call over the same arrays, both at ``max_px``
@@ -516,7 +567,7 @@ class HipEpipolarMixin:
         return out
 
     def initialise_pairs(self, list_of_matched_pairs, K, K_right=None, max_px=2.0, max_hyp=128, iteration=2, planar_ratio=0.8,
-                         min_angle_deg=2.0, min_parallax=8, refine_iters=0):
+                         min_angle_deg=2.0, min_parallax=8, refine_iters=0, minimal=False):
         """Verdict and relative pose of several sets of matches (no reference counterpart): ``classify_matches`` and then ONE
         ``native.twoview_pose`` over all sets, every set posed from the model its verdict trusts with that model's inliers
         voting: F for ``"general"``, H for ``"degenerate"``; a ``"none"`` set is passed with an empty mask and comes back
@@ -532,19 +583,33 @@ class HipEpipolarMixin:
         baseline is not determined and the iteration would wander).  Every dict then also has ``R_refined``, ``t_refined``,
         ``rot_refined``, ``centre_refined``, ``F_refined`` (Frobenius norm 1, for guided matching), ``refine_inliers`` and
         ``refine_front`` (indices), ``refine_cost`` (before, after), ``refine_used`` and ``refine_status``
-        (``native.REFINE_*`` bits); ``refine_last`` keeps the summary."""
+        (``native.REFINE_*`` bits); ``refine_last`` keeps the summary.
+
+        With ``minimal=True`` the sets whose verdict is ``"general"`` take their model from ONE ``native.essential_ransac``
+        over all sets at the same ``max_px`` and ``max_hyp`` (five-point hypotheses with the intrinsics) in place of the
+        eight-point F: where that call has a model, its pixel matrix poses the set and its inliers vote, and the dict gains
+        ``E``, ``E_inliers``, ``E_status``, ``E_hypothesis`` and ``E_root`` (``kind`` is then ``"essential"``); a general set
+        without an essential model keeps its F.  The verdicts themselves do not change; ``essential_last`` keeps the summary."""
         if not 0.0 <= float(min_angle_deg) <= 90.0:
             raise ValueError("min_angle_deg must be in [0, 90], got {!r}".format(min_angle_deg))
         refine_iters = native._count("refine_iters", refine_iters)
         verdicts = self.classify_matches(list_of_matched_pairs, max_px, max_hyp, iteration, planar_ratio)
         set_ptr, left, right = self._twoview_sets(list_of_matched_pairs)
+        ess = None
+        if minimal:
+            ess = native.essential_ransac(set_ptr, left, right, K, K if K_right is None else K_right, float(max_px) ** 2, max_hyp)
+            self.essential_last = {"summary": ess["summary"], "status": ess["status"].tolist()}
         mask = np.zeros(left.shape[1], dtype=np.uint8)
-        models, kinds = [], []
+        models, kinds, from_e = [], [], []
         for s, v in enumerate(verdicts):
             use_h = v["verdict"] == "degenerate"
+            use_e = ess is not None and v["verdict"] == "general" and ess["status"][s] == 0
+            from_e.append(use_e)
             kinds.append(native.POSE_FROM_H if use_h else native.POSE_FROM_F)
-            models.append(v["H"] if use_h else v["F"])
-            if v["verdict"] != "none":
+            models.append(ess["F"][s] if use_e else (v["H"] if use_h else v["F"]))
+            if use_e:
+                mask[set_ptr[s]:set_ptr[s + 1]] = ess["inlier"][set_ptr[s]:set_ptr[s + 1]]
+            elif v["verdict"] != "none":
                 mask[set_ptr[s] + np.asarray(v["H_inliers"] if use_h else v["F_inliers"], dtype=np.int64)] = 1
         out = native.twoview_pose(set_ptr, left, right, models, kinds, K, K if K_right is None else K_right,
                                   math.cos(math.radians(float(min_angle_deg))) ** 2, min_parallax, mask,
@@ -560,6 +625,10 @@ class HipEpipolarMixin:
                           "normal": out["normal"][s], "front": np.flatnonzero(out["obs_front"][set_ptr[s]:set_ptr[s + 1]]).tolist(),
                           "n_front": int(out["n_front"][s]), "n_parallax": int(out["n_parallax"][s]),
                           "cand_front": out["cand_front"][s], "best_cand": int(out["best_cand"][s]), "status": int(out["status"][s])})
+            if from_e[s]:
+                e = _essential_entry(ess, s, set_ptr[s], set_ptr[s + 1])
+                entry.update({"kind": "essential", "E": e["esse_mat"], "E_inliers": e["inliers"], "E_status": e["status"],
+                              "E_hypothesis": e["hypothesis"], "E_root": e["root"]})
             result.append(entry)
         if refine_iters > 0:
             skip = native.POSE_NO_POSE | native.POSE_NO_PARALLAX
@@ -1787,6 +1856,57 @@ def verify_pairs(tracker, ref_idx, que_idx, max_sampson_px=2.0, max_hyp=128, ite
                                                                            iteration)
     tracker.twoview_last = {"fund_mat": fund, "hypothesis": best, "status": status}
     num = r_idx.shape[0]
+    return r_idx.reshape(1, num).astype(int), q_idx.reshape(1, num).astype(int), inlier.astype(bool)
+
+
+def _essential_entry(out, s, lo, hi):
+    """What the callers of ``native.essential_ransac`` keep of set ``s`` (matches lo .. hi - 1) of its result."""
+    return {"esse_mat": out["E"][s], "fund_mat": out["F"][s], "inliers": np.flatnonzero(out["inlier"][lo:hi]).tolist(),
+            "hypothesis": int(out["best_hyp"][s]), "root": int(out["best_root"][s]), "n_valid": int(out["n_valid"][s]),
+            "status": int(out["status"][s])}
+
+
+def essential_pairs(tracker, ref_idx, que_idx, K_left, K_right, max_sampson_px=2.0, max_hyp=128):
+    """``determine_essential_mat_robust`` over the pairs ``tracker.generate_matched_pairs(ref_idx, que_idx)`` returns
+    (``tracker``: a ``HipDeviceKeyTracker``; the reference key is LEFT, the query key RIGHT) without a coordinate leaving the
+    device: the gather of ``verify_pairs`` (``TrackStore.pairs_dev``) fills device buffers, and ``native.essential_ransac_dev``
+    reads them on the same stream as one set.  Only the count of pairs comes down between the two steps, and the indices, the
+    mask and the model after them.  Returns ``r_idx (1, n), q_idx (1, n), inlier (n,) bool``; ``tracker.essential_last`` keeps
+    what ``determine_essential_mat_robust`` keeps.  A function of the module, like ``verify_pairs``."""
+    n_views = len(tracker.track_list)
+    if ref_idx < 0 or que_idx < 0 or ref_idx >= n_views or que_idx >= n_views:
+        print('{}:{} - invalid ref_idx {} or invalid que_idx {}'.format(
+            tracker.__class__.__name__, 'essential_pairs', ref_idx, que_idx))
+        return None
+    if not float(max_sampson_px) >= 0.0:
+        raise ValueError("max_sampson_px must be >= 0, got {!r}".format(max_sampson_px))
+    import torch
+    store = tracker._store
+    cap = max(store.n_keys(ref_idx), 1)
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        d_count = torch.empty(2, dtype=torch.int32, device="cuda")
+        d_r, d_q = (torch.empty(cap, dtype=torch.int32, device="cuda") for _ in range(2))
+        d_ref, d_que = (torch.empty(3 * cap, dtype=torch.float64, device="cuda") for _ in range(2))
+        store.pairs_dev(ref_idx, que_idx, d_count.data_ptr(), d_r.data_ptr(), d_q.data_ptr(), d_ref.data_ptr(), d_que.data_ptr(),
+                        stream.cuda_stream)
+        count = d_count.cpu().numpy()
+        if count[1]:
+            raise ValueError("table[{}][{}] names a key the query view does not have".format(ref_idx, que_idx))
+        num = int(count[0])
+        d_E, d_F = (torch.empty(9, dtype=torch.float64, device="cuda") for _ in range(2))
+        d_in = torch.empty(max(num, 1), dtype=torch.uint8, device="cuda")
+        d_int = torch.empty(5, dtype=torch.int32, device="cuda")      # n_inliers, best_hyp, best_root, n_valid, status
+        ints = [d_int.data_ptr() + 4 * k for k in range(5)]
+        # the packed (3, n) point arrays begin with the x row and the y row: the [2][n] layout of the robust estimators
+        native.essential_ransac_dev([0, num], num, d_ref.data_ptr(), d_que.data_ptr(), K_left, K_right, float(max_sampson_px) ** 2,
+                                    max_hyp, d_E.data_ptr(), d_F.data_ptr(), d_in.data_ptr(), *ints, stream=stream.cuda_stream)
+        r_idx, q_idx = d_r[:num].cpu().numpy(), d_q[:num].cpu().numpy()
+        inlier = d_in[:num].cpu().numpy()
+        got = d_int.cpu().numpy()
+        out = {"E": d_E.cpu().numpy().reshape(1, 3, 3), "F": d_F.cpu().numpy().reshape(1, 3, 3), "inlier": inlier}
+    out.update({name: got[k:k + 1] for k, name in enumerate(("n_inliers", "best_hyp", "best_root", "n_valid", "status"))})
+    tracker.essential_last = _essential_entry(out, 0, 0, num)
     return r_idx.reshape(1, num).astype(int), q_idx.reshape(1, num).astype(int), inlier.astype(bool)
 
 
