@@ -1259,6 +1259,81 @@ int sfm_essential_sample(int n, int max_hyp, int h, int idx[5]);
  * E[10][9] the canonical solutions in the order of step 5 (zeros beyond *n). */
 int sfm_essential_solve(const double* a /*[5][2]*/, const double* b /*[5][2]*/, double* E /*[10][9]*/, int* n);
 
+/* ---- robust similarity: sampled three-point hypotheses, inlier refit; moving and aligning the resident scene ---------
+ * What every call above returns lives in a frame of its own: a verified pair in the pair's frame with a baseline of
+ * length one, a resident scene in the gauge of its first two views, surveyed points in metres.  The relation between two
+ * such frames is the seven-parameter similarity b ~ s A a + t (s > 0, A a rotation), the sixth robust estimator.
+ * A call holds n_sets sets of 3D-3D correspondences; src and dst are [3][M] (the x row, the y row, the z row); set k owns
+ * the correspondences set_ptr[k] .. set_ptr[k + 1] - 1, n of them.  The rule, per set:
+ *   1. n < 4: SFM_SIMILARITY_TOO_FEW.
+ *   2. The test.  A model under test is 12 doubles (Mx, t) with Mx[i][j] = s * A[i][j] (one rounding each).
+ *      e_i = b_i - fma(Mx_i0, a_x, fma(Mx_i1, a_y, fma(Mx_i2, a_z, t_i))); lhs = fma(e_0, e_0, fma(e_1, e_1, e_2 * e_2)).
+ *      A correspondence is an INLIER iff lhs is finite and lhs <= max_err2, in squared units of the dst frame.  The
+ *      back-transfer error times s^2 is the same quantity, so there is no second half.  One function (similarity_inlier,
+ *      csrc/sfm_obs_test.h) that every stage below calls.
+ *   3. Hypotheses.  H = max_hyp (0 means 128; range 1 .. 65 536), whatever n.  Hypothesis h uses, for k = 0 .. 2, the
+ *      correspondence lo_k + mix(3 h + k) mod (hi_k - lo_k) with lo_k = floor(k n / 3), hi_k = floor((k + 1) n / 3): one of
+ *      every third of the set, so the three indices are distinct and ascending.  mix is the splitmix64 finaliser of the
+ *      two-view rule.  sfm_similarity_sample returns the same indices on any machine.
+ *   4. Model of a sample, and of an inlier set (Umeyama 1991).  Over its m correspondences the centroids mu_a, mu_b first;
+ *      from the centred coordinates Sigma = (1/m) sum (b - mu_b)(a - mu_a)^T and var_a = (1/m) sum |a - mu_a|^2 (two passes:
+ *      targets a million units from the origin lose nothing).  With Sigma = U D V^T, A = U diag(1, 1, det U det V) V^T,
+ *      never a reflection; s = (D_0 + D_1 + det U det V D_2) / var_a, or s = 1 with SFM_SIMILARITY_RIGID in flags;
+ *      t = mu_b - s A mu_a.  Valid iff everything is finite, var_a > 0, s > 0 and D_1 > 3 eps D_0: a collinear sample leaves
+ *      the rotation about its line free.  How the decomposition is computed is not part of the rule.
+ *   5. Sample gate.  A hypothesis is invalid unless its own three correspondences are inliers of it (with scale, three
+ *      points over-determine the seven parameters).
+ *   6. Score, lexicographic: the inlier count over all n (an integer); then the lower h.  A winner needs a count of at
+ *      least 4, otherwise SFM_SIMILARITY_NO_MODEL.
+ *   7. Refit, up to `iters` rounds.  Step 4 over the inliers of the standing model.  The round stands iff its model is
+ *      valid and its inlier count over all n is at least the standing count; otherwise the rounds stop.
+ *      SFM_SIMILARITY_KEPT_HYPOTHESIS iff iters > 0 and no round stood.
+ *   8. Outputs, all optional but sim_out.  sim_out[n_sets][13]: s, A row-major, t of the standing model; thirteen zeros with
+ *      TOO_FEW or NO_MODEL.  obs_inlier[M], n_inliers, best_hyp (-1 without a model), status and summary[6] have the meaning
+ *      and order they have for sfm_homography_ransac and describe the standing model, judged once more by the function of
+ *      step 2.
+ * No floating-point atomic, integer counts, slice-ordered sums: a set's bits depend on its correspondences and the options
+ * only.  Argument errors (a NaN or negative max_err2, max_hyp out of range, iters < 0, unknown flag bits, bad offsets, a
+ * null array: SFM_E_SHAPE, nothing launched, outputs untouched) are found before a device is looked for.  The _dev form
+ * takes device pointers (set_ptr stays a host array, d_summary is int64[6] on the device) and a stream (NULL = the library
+ * stream); it returns when the work is done. */
+#define SFM_SIMILARITY_TOO_FEW          1   /* the set has fewer than 4 correspondences */
+#define SFM_SIMILARITY_NO_MODEL         2   /* no valid hypothesis with at least 4 inliers */
+#define SFM_SIMILARITY_KEPT_HYPOTHESIS  4   /* no refit round stood: the model is the winning hypothesis itself */
+#define SFM_SIMILARITY_RIGID            1   /* flags: s = 1, a rigid motion */
+int sfm_similarity_ransac(int n_sets, const int* set_ptr /*host [n_sets+1]*/, int64_t M, const double* src /*[3][M]*/,
+                          const double* dst /*[3][M]*/, double max_err2, int max_hyp, int iters, int flags,
+                          double* sim_out /*[n_sets][13]: s, A row-major, t*/, unsigned char* obs_inlier /*[M] or NULL*/,
+                          int* n_inliers /*[n_sets] or NULL*/, int* best_hyp /*[n_sets] or NULL*/,
+                          int* status /*[n_sets] or NULL*/, int64_t* summary /*[6] or NULL*/);
+int sfm_similarity_ransac_dev(int n_sets, const int* set_ptr /*host [n_sets+1]*/, int64_t M, const double* d_src,
+                              const double* d_dst, double max_err2, int max_hyp, int iters, int flags, double* d_sim_out,
+                              unsigned char* d_obs_inlier, int* d_n_inliers, int* d_best_hyp, int* d_status,
+                              int64_t* d_summary, void* hip_stream);
+/* Host only, needs no device: the hypothesis count H of a set of n correspondences (0 for n < 4 or a max_hyp out of range)
+ * and, for 0 <= h < H, the three ascending indices of hypothesis h. */
+int sfm_similarity_sample(int n, int max_hyp, int h, int idx[3]);
+/* The resident scene moved by X' = s A X + t, on the device: every point by the formula, every camera block [C, q] to
+ * C' = s A C + t and q' = q(A R(q)), the library's canonical quaternion of the product (qw >= 0, not renormalised).
+ * Refused before any launch: s not finite or not positive (SFM_E_SHAPE), A failing verify_rotation
+ * (SFM_E_BAD_ROTATION), a communicator attached.  The new cameras go to a work buffer first; if q(A R(q)) of any camera
+ * fails (a half turn: |qw| < 1e-6) the call fails with that camera's status and the lowest such camera named, and the
+ * scene is left bit for bit as it was.  Reprojection residuals are invariant, R'^T (X' - C') = s R^T (X - C): the cost and
+ * every inlier decision of the scene are those of before.  Not invariant: the damping lambda I of an iteration (a step of
+ * the moved scene is not the moved step unless s = 1 and lambda = 0 up to rounding) and every covariance in world units
+ * (sfm_ba_covariance), which scales with s^2 and turns with A.  Afterwards the state is treated as after sfm_ba_set_state. */
+int sfm_ba_transform(sfm_ba_problem* p, double s, const double A[9], const double t[3]);
+/* The resident scene aligned to targets: the resident points point_idx[0 .. n) are gathered on the device as src, target is
+ * uploaded as dst, and sfm_similarity_ransac_dev runs on them as one set on the problem's stream (options as above).  With
+ * apply != 0 and a model the scene is then moved by it as sfm_ba_transform moves it, the model read from device memory:
+ * nothing comes down between the two.  Then the outputs are downloaded: sim_out[13], inlier[n], n_inliers, best_hyp,
+ * status (any of the last four may be NULL).  A point_idx outside 0 .. N - 1: SFM_E_SHAPE.  n = 0, too few correspondences
+ * or no model are not errors: `status` says so and the scene is untouched.  A camera at a half turn fails the call as it
+ * fails sfm_ba_transform, the scene untouched and the outputs written. */
+int sfm_ba_align(sfm_ba_problem* p, int n, const int* point_idx /*host [n]*/, const double* target /*host [3][n]*/,
+                 double max_err2, int max_hyp, int iters, int flags, int apply, double* sim_out /*[13]*/,
+                 unsigned char* inlier /*[n] or NULL*/, int* n_inliers, int* best_hyp, int* status);
+
 /* ---- SIFT detection: ViewProcessor.__extract_keys (view_processor.py:151-164, 199-202) --------------------------
  * cv.SIFT_create().detectAndCompute(img, None) by the contract of INTEGRATION.md 'SIFT detection' (firstOctave -1,
  * nfeatures 0, no mask): keypoints sorted by (x, y asc; size desc; angle asc; response desc; octave desc) without

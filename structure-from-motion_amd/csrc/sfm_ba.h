@@ -378,6 +378,8 @@ inline CamObsView cam_obs_view_resident(const sfm_ba_problem* p, const double* c
 // What an operation on the resident scene is given (sfm_ba_host.hip; DESIGN.md, "What an operation on the resident scene
 // is given").  `who` names the entry point in the message.
 int ba_check_handle(const sfm_ba_problem* p);
+// The options of a robust similarity, for sfm_ba_align to refuse before it touches the scene (sfm_similarity.hip).
+int similarity_check_options(const char* who, double max_err2, int max_hyp, int iters, int flags);
 int ba_refuse_comm(const sfm_ba_problem* p, const char* who, const char* why);      // "<who>: not with a communicator attached (<why>)"
 // download d.status behind whatever the caller has enqueued, wait for the stream, and fail with
 // "<who>: camera %d is invalid<when> (status %d)" on a camera that did not pass its checks

@@ -206,6 +206,80 @@ __global__ void ba_rederive_quat_kernel(int first, int count, const CamPrep* __r
   for (int k = 0; k < 4; ++k) cams[7 * c + 3 + k] = prep[c].q[k];
 }
 
+// The scene moved by a similarity X' = s A X + t (sfm_ba_transform, sfm_ba_align): sim = (s, A row-major, t) in device
+// memory, so that a model an estimator left there is applied without coming down.  `gate`, if not null, is that
+// estimator's status word: without a model (bit 1 or 2) both kernels do nothing.
+constexpr unsigned long long kTransformClean = ~0ULL;
+__device__ __forceinline__ bool ba_transform_gated(const int* gate) { return gate != nullptr && (*gate & 3) != 0; }
+
+__device__ __forceinline__ void ba_transform_point(const double* sim, double x, double y, double z, double* out) {
+  const double s = sim[0];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) out[i] = s * (sim[1 + 3 * i] * x + sim[2 + 3 * i] * y + sim[3 + 3 * i] * z) + sim[10 + i];
+}
+
+// First the cameras, into work[V][7]: C' = s A C + t, q' = q(A R(q)).  A camera whose quaternion fails leaves
+// (camera << 3 | -status) in *fail, the lowest camera winning.
+__global__ void ba_transform_cams_kernel(int V, const double* __restrict__ cams, const double* __restrict__ sim,
+                                         const int* __restrict__ gate, double* __restrict__ work, unsigned long long* fail) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= V || ba_transform_gated(gate)) return;
+  double R[9], AR[9], q[4] = {0, 0, 0, 0}, C[3];
+  quat_to_rot(cams + 7 * c + 3, R);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) AR[3 * i + j] = sim[1 + 3 * i] * R[j] + sim[2 + 3 * i] * R[3 + j] + sim[3 + 3 * i] * R[6 + j];
+  const int st = rot_to_quat(AR, q);
+  ba_transform_point(sim, cams[7 * c], cams[7 * c + 1], cams[7 * c + 2], C);
+  if (st != SFM_OK) atomicMin(fail, ((unsigned long long)c << 3) | (unsigned long long)(-st));
+#pragma unroll
+  for (int k = 0; k < 3; ++k) work[7 * c + k] = C[k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) work[7 * c + 3 + k] = q[k];
+}
+
+// Then, if every camera passed, the commit: the cameras from the work buffer and the points by the formula.
+__global__ void ba_transform_commit_kernel(int V, int N, const double* __restrict__ work, const double* __restrict__ sim,
+                                           const int* __restrict__ gate, const unsigned long long* __restrict__ fail,
+                                           double* __restrict__ cams, double* __restrict__ px, double* __restrict__ py,
+                                           double* __restrict__ pz) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (*fail != kTransformClean || ba_transform_gated(gate)) return;
+  if (i < 7 * V) cams[i] = work[i];
+  if (i < N) {
+    double X[3];
+    ba_transform_point(sim, px[i], py[i], pz[i], X);
+    px[i] = X[0]; py[i] = X[1]; pz[i] = X[2];
+  }
+}
+
+// Enqueue both on p->stream; *fail_word (device) is left for the caller to read behind them.
+static int ba_enqueue_transform(sfm_ba_problem* p, const double* d_sim, const int* d_gate, DevBuf<double>& work,
+                                DevBuf<unsigned long long>& fail) {
+  BaDev& d = p->dev;
+  hipStream_t s = p->stream;
+  SFM_TRY(work.alloc(7 * (size_t)d.V, s));
+  SFM_TRY(fail.alloc(1, s));
+  SFM_HIP(hipMemsetAsync(fail.p, 0xFF, sizeof(unsigned long long), s));
+  const int span = std::max(7 * d.V, d.N);
+  if (d.V > 0) ba_transform_cams_kernel<<<(d.V + 63) / 64, 64, 0, s>>>(d.V, d.cams, d_sim, d_gate, work.p, fail.p);
+  if (span > 0) ba_transform_commit_kernel<<<(span + 255) / 256, 256, 0, s>>>(d.V, d.N, work.p, d_sim, d_gate, fail.p, d.cams, d.px, d.py, d.pz);
+  SFM_HIP(hipGetLastError());
+  return SFM_OK;
+}
+
+// The word the transform left, downloaded and the stream waited for: a failed camera is the call's error.
+static int ba_transform_verdict(sfm_ba_problem* p, const char* who, const DevBuf<unsigned long long>& fail) {
+  unsigned long long word = kTransformClean;
+  SFM_TRY(fail.download(&word, 1, p->stream));
+  SFM_TRY(stream_sync(p->stream));
+  if (word == kTransformClean) return SFM_OK;
+  const int st = -(int)(word & 7);
+  set_error("%s: camera %d has no quaternion after the transform (status %d); the scene is unchanged", who, (int)(word >> 3), st);
+  return st;
+}
+
 __global__ void ba_gather_rot_kernel(int V, const CamPrep* __restrict__ prep, double* __restrict__ rots) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 9 * V) return;
@@ -656,6 +730,74 @@ int sfm_ba_set_state(sfm_ba_problem* p, const double* cams, const double* pts) {
   SFM_TRY(ba_reset_stats(p));
   SFM_TRY(stream_sync(p->stream));
   p->prep_valid = false;
+  return SFM_OK;
+}
+
+int sfm_ba_transform(sfm_ba_problem* p, double s, const double A[9], const double t[3]) {
+  const char* who = "sfm_ba_transform";
+  SFM_TRY(ba_check_handle(p));
+  if (A == nullptr || t == nullptr) { set_error("%s: null pointer", who); return SFM_E_SHAPE; }
+  if (!(s > 0.0 && s <= 1.7976931348623157e308)) { set_error("%s: s = %g must be finite and > 0", who, s); return SFM_E_SHAPE; }
+  double sim[13] = {s};
+  bool finite = true;
+  for (int k = 0; k < 9; ++k) { sim[1 + k] = A[k]; finite = finite && std::isfinite(A[k]); }
+  for (int k = 0; k < 3; ++k) { sim[10 + k] = t[k]; finite = finite && std::isfinite(t[k]); }
+  if (!finite) { set_error("%s: A and t must be finite", who); return SFM_E_SHAPE; }
+  if (!verify_rotation(A)) { set_error("%s: A is not a rotation matrix", who); return SFM_E_BAD_ROTATION; }
+  SFM_TRY(ba_refuse_comm(p, who, "the points are sharded; every rank would have to move its part by the same call"));
+  SFM_TRY(ba_flush(p));
+  DevBuf<double> d_sim, work;
+  DevBuf<unsigned long long> fail;
+  SFM_TRY(d_sim.upload(sim, 13, p->stream));
+  p->upload_bytes += (long long)sizeof(sim);
+  SFM_TRY(ba_enqueue_transform(p, d_sim.p, nullptr, work, fail));
+  SFM_TRY(ba_transform_verdict(p, who, fail));
+  return ba_state_changed(p);
+}
+
+int sfm_ba_align(sfm_ba_problem* p, int n, const int* point_idx, const double* target, double max_err2, int max_hyp, int iters,
+                 int flags, int apply, double* sim_out, unsigned char* inlier, int* n_inliers, int* best_hyp, int* status) {
+  const char* who = "sfm_ba_align";
+  SFM_TRY(ba_check_handle(p));
+  SFM_TRY(similarity_check_options(who, max_err2, max_hyp, iters, flags));
+  BaDev& d = p->dev;
+  if (n < 0 || sim_out == nullptr || (n > 0 && (point_idx == nullptr || target == nullptr))) { set_error("%s: bad sizes or null pointer (n = %d)", who, n); return SFM_E_SHAPE; }
+  for (int i = 0; i < n; ++i)
+    if (point_idx[i] < 0 || point_idx[i] >= d.N) { set_error("%s: point_idx[%d] = %d is outside the %d points", who, i, point_idx[i], d.N); return SFM_E_SHAPE; }
+  SFM_TRY(ba_refuse_comm(p, who, "the points are sharded; every rank would have to move its part by the same call"));
+  SFM_TRY(ba_flush(p));
+  if (n == 0) {
+    std::fill(sim_out, sim_out + 13, 0.0);
+    if (n_inliers) *n_inliers = 0;
+    if (best_hyp) *best_hyp = -1;
+    if (status) *status = SFM_SIMILARITY_TOO_FEW;
+    return SFM_OK;
+  }
+  hipStream_t s = p->stream;
+  const size_t m = (size_t)n;
+  DevBuf<int> d_idx, d_small;                    // d_small: n_inliers, best_hyp, status
+  DevBuf<double> d_src, d_dst, d_sim, work;
+  DevBuf<unsigned char> d_inl;
+  DevBuf<unsigned long long> fail;
+  SFM_TRY(d_idx.upload(point_idx, m, s));
+  SFM_TRY(d_dst.upload(target, 3 * m, s));
+  p->upload_bytes += (long long)(sizeof(int) * m + sizeof(double) * 3 * m);
+  SFM_TRY(d_src.alloc(4 * m, s)); SFM_TRY(d_sim.alloc(13, s)); SFM_TRY(d_small.alloc(3, s)); SFM_TRY(d_inl.alloc(m, s));
+  SFM_TRY(sfm_gather_points_dev(n, d_idx.p, d.px, d.py, d.pz, d_src.p, s));      // rows X, Y, Z of [4][n]: src as [3][n]
+  const int set_ptr[2] = {0, n};
+  SFM_TRY(sfm_similarity_ransac_dev(1, set_ptr, n, d_src.p, d_dst.p, max_err2, max_hyp, iters, flags, d_sim.p, d_inl.p, d_small.p,
+                                    d_small.p + 1, d_small.p + 2, nullptr, s));
+  if (apply) SFM_TRY(ba_enqueue_transform(p, d_sim.p, d_small.p + 2, work, fail));
+  int small[3] = {0, -1, 0};
+  SFM_TRY(d_sim.download(sim_out, 13, s));
+  SFM_TRY(d_small.download(small, 3, s));
+  if (inlier) SFM_TRY(d_inl.download(inlier, m, s));
+  const int verdict = apply ? ba_transform_verdict(p, who, fail) : stream_sync(s);
+  if (n_inliers) *n_inliers = small[0];
+  if (best_hyp) *best_hyp = small[1];
+  if (status) *status = small[2];
+  SFM_TRY(verdict);
+  if (apply && !(small[2] & (SFM_SIMILARITY_TOO_FEW | SFM_SIMILARITY_NO_MODEL))) SFM_TRY(ba_state_changed(p));
   return SFM_OK;
 }
 

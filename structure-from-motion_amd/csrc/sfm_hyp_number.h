@@ -3,8 +3,8 @@
 // them up to max_hyp, else evenly spaced.  No random number anywhere.  The floating-point estimates below only seed integer
 // searches that end at the exact answer, so the results do not depend on how the including file contracts them.
 // The eight-match samples of the robust two-view geometry (sfm_twoview.hip), the four-match samples of the robust
-// homography (sfm_homography.hip) and the five-match samples of the robust essential matrix (sfm_essential.hip) are drawn
-// by a stratified integer sampler.
+// homography (sfm_homography.hip), the five-match samples of the robust essential matrix (sfm_essential.hip) and the
+// three-correspondence samples of the robust similarity (sfm_similarity.hip) are drawn by a stratified integer sampler.
 #pragma once
 
 #include <cmath>
@@ -89,6 +89,13 @@ __host__ __device__ inline int homography_sample_index(int n, int h, int k) {
 __host__ __device__ inline int essential_sample_index(int n, int h, int k) {
   const long long lo = (long long)k * n / 5, hi = (long long)(k + 1) * n / 5;
   return (int)(lo + (long long)(splitmix64_mix(5ULL * (unsigned long long)h + (unsigned long long)k) % (unsigned long long)(hi - lo)));
+}
+
+// ---- three-index samples of a set of n >= 4 correspondences (sfm_similarity.hip): the same sampler over thirds, stratum k
+// being floor(k n / 3) .. floor((k + 1) n / 3) - 1 (never empty) and hypothesis h taking lo_k + mix(3 h + k) mod (hi_k - lo_k).
+__host__ __device__ inline int similarity_sample_index(int n, int h, int k) {
+  const long long lo = (long long)k * n / 3, hi = (long long)(k + 1) * n / 3;
+  return (int)(lo + (long long)(splitmix64_mix(3ULL * (unsigned long long)h + (unsigned long long)k) % (unsigned long long)(hi - lo)));
 }
 
 }  // namespace sfm

@@ -8,7 +8,8 @@
 // each image), which every stage of the robust homography calls, and the test of one match against a relative pose (in
 // front of both cameras, with parallax), which every stage of the relative pose of a verified pair calls, and the model
 // of a pose with the signed Sampson residual of one match and its Jacobian row, which the passes and the judge of the
-// refinement of a relative pose call.
+// refinement of a relative pose call, and the test of one 3D-3D correspondence against a similarity, which every stage of
+// the robust similarity calls.
 //
 // Compiled WITHOUT automatic contraction, the FMAs spelled out.  The pragma is lexical and stays in force for the rest of
 // the translation unit: include this header outside any namespace and AFTER all code that keeps the compiler's default
@@ -94,6 +95,20 @@ __host__ __device__ inline void homography_adjugate(const double* H, double* G) 
   G[6] = __builtin_fma(H[3], H[7], -(H[4] * H[6]));
   G[7] = __builtin_fma(H[1], H[6], -(H[0] * H[7]));
   G[8] = __builtin_fma(H[0], H[4], -(H[1] * H[3]));
+}
+
+// The test of one CORRESPONDENCE a <-> b between two 3D frames against a similarity b ~ s A a + t.  A model under test is
+// 12 doubles (Mx, t): Mx row-major with Mx[i][j] = s * A[i][j] (one rounding each), then t.  e = b - (Mx a + t), the squared
+// length of e in the units of the b frame; an inlier iff it is finite and <= max_err2.  The back-transfer error times s^2
+// is the same quantity: one half suffices.  Every stage of the robust similarity (sample gate, score, refit, judge) and
+// the alignment of a resident scene call this one function; no branch.
+__host__ __device__ inline bool similarity_inlier(const double* Mt, double ax, double ay, double az, double bx, double by, double bz,
+                                                  double max_err2) {
+  const double e0 = bx - __builtin_fma(Mt[0], ax, __builtin_fma(Mt[1], ay, __builtin_fma(Mt[2], az, Mt[9])));
+  const double e1 = by - __builtin_fma(Mt[3], ax, __builtin_fma(Mt[4], ay, __builtin_fma(Mt[5], az, Mt[10])));
+  const double e2 = bz - __builtin_fma(Mt[6], ax, __builtin_fma(Mt[7], ay, __builtin_fma(Mt[8], az, Mt[11])));
+  const double lhs = __builtin_fma(e0, e0, __builtin_fma(e1, e1, e2 * e2));
+  return (bool)((int)(__builtin_isfinite(lhs) != 0) & (int)(lhs <= max_err2));
 }
 
 // The terms of the test of one MATCH against a relative pose (R, t), X_right = R X_left + t: the rays (a0, a1, 1) of the

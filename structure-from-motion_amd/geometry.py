@@ -125,3 +125,25 @@ def normalise_pixels(uv_pix, intrinsic):
     cam = np.linalg.inv(np.asarray(intrinsic, dtype=np.float64)) @ hom
     cam = cam / cam[2:3, :]
     return np.ascontiguousarray(cam[0:2, :])
+
+
+def apply_similarity(sim, cams, pts):
+    """The NumPy counterpart of ``BaProblem.transform``: ``sim`` is ``(s, A, t)`` or the 13 doubles ``s, A row-major, t`` of
+    ``similarity_ransac``; camera blocks (V, 7) ``[C, q]`` go to ``C' = s A C + t`` and ``q' = q(A R(q))`` (the canonical
+    quaternion, qw >= 0, ``ValueError`` at a half turn), points (3, N) to ``s A X + t``.  Either of ``cams`` / ``pts`` may be
+    None.  Returns ``(cams', pts')``."""
+    if isinstance(sim, (tuple, list)) and len(sim) == 3:
+        s, A, t = float(sim[0]), np.asarray(sim[1], dtype=np.float64).reshape(3, 3), np.asarray(sim[2], dtype=np.float64).reshape(3)
+    else:
+        flat = np.asarray(sim, dtype=np.float64).reshape(13)
+        s, A, t = float(flat[0]), flat[1:10].reshape(3, 3), flat[10:13]
+    new_cams = new_pts = None
+    if cams is not None:
+        cams = np.asarray(cams, dtype=np.float64).reshape(-1, 7)
+        new_cams = np.empty_like(cams)
+        new_cams[:, 0:3] = s * (cams[:, 0:3] @ A.T) + t
+        for c in range(cams.shape[0]):
+            new_cams[c, 3:7] = rotation_to_quaternion(A @ quaternion_to_rotation_unchecked(cams[c, 3:7])).reshape(4)
+    if pts is not None:
+        new_pts = s * (A @ np.asarray(pts, dtype=np.float64)) + t[:, None]
+    return new_cams, new_pts

@@ -65,6 +65,11 @@ ESSENTIAL_TOO_FEW, ESSENTIAL_NO_MODEL = 1, 2
 ESSENTIAL_MAX_HYP, ESSENTIAL_DEFAULT_HYP, ESSENTIAL_MIN_MATCHES, ESSENTIAL_MAX_SOLUTIONS = 65536, 128, 6, 10
 ESSENTIAL_SUMMARY = ("sets_solved", "sets_no_model", "sets_too_few", "unused", "matches_inlier", "matches_outlier")
 ESSENTIAL_OUTPUTS = ("F", "inlier", "n_inliers", "best_hyp", "best_root", "n_valid", "status", "summary")
+SIMILARITY_TOO_FEW, SIMILARITY_NO_MODEL, SIMILARITY_KEPT_HYPOTHESIS = 1, 2, 4
+SIMILARITY_RIGID = 1
+SIMILARITY_MAX_HYP, SIMILARITY_DEFAULT_HYP, SIMILARITY_MIN_SET = 65536, 128, 4
+SIMILARITY_SUMMARY = ("sets_solved", "sets_no_model", "sets_too_few", "sets_kept_hypothesis", "pairs_inlier", "pairs_outlier")
+SIMILARITY_OUTPUTS = TWOVIEW_OUTPUTS
 POSE_FROM_F, POSE_FROM_H = 0, 1
 POSE_EMPTY, POSE_NO_MODEL, POSE_NO_POSE, POSE_TIED, POSE_NO_PARALLAX = 1, 2, 4, 8, 16
 POSE_CANDIDATES = 4
@@ -266,6 +271,11 @@ SIGNATURES = {
     "sfm_essential_ransac_dev": [ci, _ip, i64, vp, vp, _dp, _dp, cd, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "sfm_essential_sample": [ci, ci, ci, _ip],
     "sfm_essential_solve": [_dp, _dp, _dp, _ip],
+    "sfm_similarity_ransac": [ci, _ip, i64, _dp, _dp, cd, ci, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
+    "sfm_similarity_ransac_dev": [ci, _ip, i64, vp, vp, cd, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp],
+    "sfm_similarity_sample": [ci, ci, ci, _ip],
+    "sfm_ba_transform": [vp, cd, _dp, _dp],
+    "sfm_ba_align": [vp, ci, _ip, _dp, cd, ci, ci, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip],
     "sfm_twoview_pose": [ci, _ip, i64, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _dp, _dp, cd, ci, _dp, _dp, _dp, _ip, _ip, _ip,
                          _ip, _ip, ctypes.POINTER(ctypes.c_uint8), _dp, _lp],
     "sfm_twoview_pose_dev": [ci, _ip, i64, vp, vp, vp, _dp, _ip, _dp, _dp, cd, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -662,6 +672,23 @@ def check_twoview_sets(set_ptr, left, right):
     return _check_offsets("set_ptr", set_ptr, left.shape[1]), left, right
 
 
+def check_similarity(max_err2, max_hyp=0, iters=2, rigid=False):
+    """Options of a ``similarity_ransac`` / ``BaProblem.align`` call, without a device: returns
+    ``(max_err2, max_hyp, iters, flags)`` converted or raises ValueError -- everything sfm_similarity_ransac refuses before
+    it looks at the sets."""
+    max_err2, _, max_hyp, _, iters = _check_robust(max_err2, max_hyp, iters)
+    return max_err2, max_hyp, iters, SIMILARITY_RIGID if rigid else 0
+
+
+def check_similarity_sets(set_ptr, src, dst):
+    """The arrays of a ``similarity_ransac`` call, without a device: ``(set_ptr int32 (S + 1,), src (3, M), dst (3, M))``
+    converted or ValueError -- set_ptr must start at 0, not decrease and end at M."""
+    src, dst = f64(src), f64(dst)
+    if src.ndim != 2 or src.shape[0] != 3 or dst.shape != src.shape:
+        raise ValueError("src and dst must both be (3, M), got %r and %r" % (src.shape, dst.shape))
+    return _check_offsets("set_ptr", set_ptr, src.shape[1]), src, dst
+
+
 def check_loss(kind, delta):
     """Arguments of a ``BaProblem.set_loss`` call, without a device: returns ``(kind, delta)`` converted or raises ValueError.
     ``kind`` is ``LOSS_NONE`` / ``LOSS_HUBER`` / ``LOSS_CAUCHY`` or its name; ``delta`` (normalised units) must be finite and
@@ -920,6 +947,53 @@ def homography_ransac_dev(set_ptr, n_obs, d_left, d_right, max_err2, max_hyp=0, 
     check(load().sfm_homography_ransac_dev(set_ptr.shape[0] - 1, iptr(set_ptr), int(n_obs), _vp(d_left), _vp(d_right), max_err2,
                                            max_hyp, iters, _vp(d_H_out), _vp(d_inlier), _vp(d_n_inliers), _vp(d_best_hyp),
                                            _vp(d_status), _vp(d_summary), _vp(stream)))
+
+
+# ---- robust similarity between two 3D frames (sfm_similarity_*; no reference counterpart) -------------------------------
+def similarity_sample(n, max_hyp, h):
+    """``(H, idx)``: the hypothesis count of a set of ``n`` correspondences and the three ascending indices of hypothesis
+    ``h`` (sfm_similarity_sample; host only).  ``idx`` is three times -1 when ``h`` is not in ``0 .. H - 1``."""
+    idx = np.full(3, -1, dtype=np.int32)
+    count = int(load().sfm_similarity_sample(int(n), int(max_hyp), int(h), iptr(idx)))
+    return count, tuple(int(i) for i in idx)
+
+
+def similarity_ransac(set_ptr, src, dst, max_err2, max_hyp=0, iters=2, rigid=False, outputs=SIMILARITY_OUTPUTS):
+    """Robust similarity ``dst ~ s A src + t`` of every set of 3D-3D correspondences (sfm_similarity_ransac): stratified
+    three-point hypotheses scored by their inlier count under a squared distance of ``max_err2`` in the ``dst`` frame, then
+    up to ``iters`` refits over the inliers; ``rigid`` holds ``s = 1``.  ``set_ptr`` (S + 1,) delimits the correspondences of
+    a set in ``src`` / ``dst`` (3, M).  Returns ``sim (S, 13)`` -- s, A row-major, t; zeros without a model -- and ``inlier
+    (M,) uint8, n_inliers (S,), best_hyp (S,), status (S,) of SIMILARITY_* bits, summary (6,) int64`` in the order of
+    ``SIMILARITY_SUMMARY``; an output not named in ``outputs`` is not computed and comes back as None."""
+    set_ptr, src, dst = check_similarity_sets(set_ptr, src, dst)
+    max_err2, max_hyp, iters, flags = check_similarity(max_err2, max_hyp, iters, rigid)
+    unknown = set(outputs) - set(SIMILARITY_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (SIMILARITY_OUTPUTS, sorted(unknown)))
+    n_sets, n_obs = set_ptr.shape[0] - 1, src.shape[1]
+    sim = np.zeros((n_sets, 13))
+    o = _ransac_outputs(n_sets, n_obs)
+    ptrs = [p if name in outputs else None for name, p in zip(SIMILARITY_OUTPUTS, _ransac_pointers(o))]
+    check(load().sfm_similarity_ransac(n_sets, iptr(set_ptr), n_obs, dptr(src), dptr(dst), max_err2, max_hyp, iters, flags,
+                                       dptr(sim), *ptrs))
+    return (sim,) + tuple(getattr(o, name) if name in outputs else None for name in SIMILARITY_OUTPUTS)
+
+
+def similarity_ransac_dev(set_ptr, n_obs, d_src, d_dst, max_err2, max_hyp=0, iters=2, rigid=False, d_sim_out=0, d_inlier=0,
+                          d_n_inliers=0, d_best_hyp=0, d_status=0, d_summary=0, stream=0):
+    """``similarity_ransac`` on device pointers and a caller's stream (sfm_similarity_ransac_dev); ``set_ptr`` stays a host
+    array, optional arrays are 0."""
+    set_ptr = np.ascontiguousarray(set_ptr, dtype=np.int32).ravel()
+    max_err2, max_hyp, iters, flags = check_similarity(max_err2, max_hyp, iters, rigid)
+    check(load().sfm_similarity_ransac_dev(set_ptr.shape[0] - 1, iptr(set_ptr), int(n_obs), _vp(d_src), _vp(d_dst), max_err2,
+                                           max_hyp, iters, flags, _vp(d_sim_out), _vp(d_inlier), _vp(d_n_inliers),
+                                           _vp(d_best_hyp), _vp(d_status), _vp(d_summary), _vp(stream)))
+
+
+def split_similarity(sim):
+    """``(s, A (3, 3), t (3,))`` of one model of 13 doubles."""
+    sim = f64(sim).reshape(13)
+    return float(sim[0]), sim[1:10].reshape(3, 3).copy(), sim[10:13].copy()
 
 
 # ---- robust essential matrix (sfm_essential_*; no reference counterpart) ------------------------------------------------
@@ -1517,6 +1591,33 @@ class BaProblem:
         if cams.shape[0] != self.n_cams or pts.shape != (3, self.n_pts):
             raise ValueError("state shapes do not match the problem")
         check(self._lib.sfm_ba_set_state(self._h, dptr(cams), dptr(pts)))
+
+    def transform(self, s, A, t):
+        """Move the resident scene by ``X' = s A X + t`` on the device (sfm_ba_transform): points by the formula, every
+        camera to ``C' = s A C + t``, ``q' = q(A R(q))``.  ValueError for a non-positive ``s``, an ``A`` that is no rotation,
+        or a camera the move takes to a half turn (the scene is then unchanged)."""
+        A, t = f64(A).reshape(3, 3), f64(t).reshape(3)
+        check(self._lib.sfm_ba_transform(self._h, float(s), dptr(A), dptr(t)))
+
+    def align(self, point_idx, targets, max_err2, max_hyp=0, iters=2, rigid=False, apply=True):
+        """Align the resident scene to ``targets`` (3, n) of its points ``point_idx`` (n,) by a robust similarity
+        (sfm_ba_align): the points are gathered on the device, ``similarity_ransac`` runs on them as one set, and with
+        ``apply`` and a model the scene is moved by it without a round trip.  Returns ``(sim (13,), inlier (n,) uint8,
+        n_inliers, best_hyp, status)``; too few correspondences or no model leave the scene untouched and say so in
+        ``status``."""
+        point_idx = np.ascontiguousarray(point_idx, dtype=np.int32).ravel()
+        targets = f64(targets)
+        n = point_idx.shape[0]
+        if targets.shape != (3, n):
+            raise ValueError("targets must be (3, %d), got %r" % (n, targets.shape))
+        max_err2, max_hyp, iters, flags = check_similarity(max_err2, max_hyp, iters, rigid)
+        sim = np.zeros(13)
+        inlier = np.zeros(n, dtype=np.uint8)
+        cnt, best, status = ci(0), ci(-1), ci(0)
+        check(self._lib.sfm_ba_align(self._h, n, iptr(point_idx) if n else None, dptr(targets) if n else None, max_err2, max_hyp,
+                                     iters, flags, 1 if apply else 0, dptr(sim), _u8ptr(inlier) if n else None,
+                                     ctypes.byref(cnt), ctypes.byref(best), ctypes.byref(status)))
+        return sim, inlier, int(cnt.value), int(best.value), int(status.value)
 
     def set_cameras(self, cams):
         cams = f64(cams).reshape(-1, 7)

@@ -395,6 +395,41 @@ class HipCamposeMixin:
                                     math.cos(math.radians(float(min_angle_deg))) ** 2, mask)
         return _refine_result(self, out)
 
+    similarity_last = None                       # what the last register_pair_points call returned from the device
+
+    def register_pair_points(self, scene_pts, pair_pts, pair_rot=None, pair_centre=None, max_err=0.05, max_hyp=128, iteration=2,
+                             rigid=False):
+        """Chain a verified pair onto a scene (one ``native.similarity_ransac``; no reference counterpart): ``pair_pts``
+        (3 or 4, n) are the points ``estimate_relative_pose_robust`` triangulated for the pair, in the pair's frame (the
+        left camera at the origin, a baseline of length one), ``scene_pts`` (3 or 4, n) the scene's points of the same
+        tracks.  The similarity ``scene ~ s A pair + t`` is estimated with correspondences farther than ``max_err`` (scene
+        units) from their target counted as wrong.
+
+        Returns ``s, A (3, 3), t (3, 1), inlier_idx (a list), rot, centre (3, 1)``: the last two are the pair's second
+        camera (``pair_rot``, ``pair_centre`` in the reference's convention, projection ``K [rot^T | -rot^T centre]``; None:
+        the identity at the origin, i.e. the pair's first camera) moved into the scene's frame, ``rot = A pair_rot`` and
+        ``centre = s A pair_centre + t``.  Without a model ``s`` is 0, ``A`` and ``rot`` are the identity, ``t`` and ``centre``
+        zeros and the list empty.  ``similarity_last`` keeps ``sim``, ``inlier``, ``n_inliers``, ``best_hyp``, ``status``."""
+        scene_pts = np.asarray(scene_pts, dtype=np.float64)
+        pair_pts = np.asarray(pair_pts, dtype=np.float64)
+        if scene_pts.ndim != 2 or pair_pts.ndim != 2 or scene_pts.shape[0] not in (3, 4) or pair_pts.shape[0] not in (3, 4) \
+                or scene_pts.shape[1] != pair_pts.shape[1]:
+            raise ValueError("scene_pts and pair_pts must be (3 or 4, n), got {} and {}".format(scene_pts.shape, pair_pts.shape))
+        if not float(max_err) >= 0.0:
+            raise ValueError("max_err must be >= 0, got {!r}".format(max_err))
+        n = pair_pts.shape[1]
+        src, dst = np.ascontiguousarray(pair_pts[0:3]), np.ascontiguousarray(scene_pts[0:3])
+        sim, inlier, n_inliers, best_hyp, status, _summary = native.similarity_ransac([0, n], src, dst, float(max_err) ** 2, max_hyp,
+                                                                                       iteration, rigid)
+        self.similarity_last = dict(sim=sim[0], inlier=inlier, n_inliers=int(n_inliers[0]), best_hyp=int(best_hyp[0]),
+                                    status=int(status[0]))
+        if status[0] & (native.SIMILARITY_TOO_FEW | native.SIMILARITY_NO_MODEL):
+            return 0.0, np.eye(3), np.zeros((3, 1)), [], np.eye(3), np.zeros((3, 1))
+        s, A, t = native.split_similarity(sim[0])
+        rot = np.eye(3) if pair_rot is None else np.asarray(pair_rot, dtype=np.float64).reshape(3, 3)
+        centre = np.zeros(3) if pair_centre is None else np.asarray(pair_centre, dtype=np.float64).reshape(3)
+        return s, A, t.reshape(3, 1), np.flatnonzero(inlier).tolist(), A @ rot, (s * (A @ centre) + t).reshape(3, 1)
+
     def estimate_relative_pose_minimal(self, matched_pairs, K_left, K_right, max_px=2.0, max_hyp=128, refine_iters=6, min_angle_deg=2.0):
         """The relative pose of a calibrated pair straight from its matches (no reference counterpart): ONE
         ``native.essential_ransac`` (five-point hypotheses at ``max_px`` pixels of Sampson distance), then ONE
@@ -1225,6 +1260,46 @@ class HipBaMixin:
         except Exception:
             self.ba_release()
             raise
+
+    def align_structure(self, point_idx, targets, max_err, max_hyp=128, iteration=2, rigid=False, apply=True):
+        """Align the resident scene to ``targets`` (3, n) of its points ``point_idx`` (n,) -- surveyed control points, the
+        points another reconstruction has for the same tracks -- by a robust similarity (``BaProblem.align``), after the scene
+        has been brought up to date exactly as ``refine_structure`` does.  ``max_err`` is in the units of ``targets``.  With
+        ``apply`` and a model the scene moves on the device, and ``tri_processor.tri_pts[0:3]`` and every view's pose are
+        written back as ``resect_motion`` writes them; without, nothing changes.  Returns the native tuple ``(sim (13,),
+        inlier (n,), n_inliers, best_hyp, status)``.  The cost of the scene is that of before; its covariances and the
+        meaning of a damping factor are not (include/sfm_hip.h).  Needs ``ba_resident``; nothing in ``process()`` calls it."""
+        if not self.ba_resident:
+            raise TypeError("align_structure needs ba_resident")
+        if self.ba_device_tracks:
+            self._ba_check_device_tracks()
+        if not float(max_err) >= 0.0:
+            raise ValueError("max_err must be >= 0, got {!r}".format(max_err))
+        native.check_similarity(float(max_err) ** 2, max_hyp, iteration, rigid)      # before anything reaches the device
+        views = self.view_processor.view_list
+        tri_pts = self.tri_processor.tri_pts
+        init_rots = np.stack([np.asarray(v.rot, dtype=np.float64) for v in views])
+        init_locs = np.stack([np.asarray(v.loc, dtype=np.float64).reshape(3) for v in views])
+        init_tri_pts = np.ascontiguousarray(tri_pts[0:3, :], dtype=np.float64)
+        scene = self._ba_update_resident(views, init_rots, init_locs, init_tri_pts)
+        scene.pts_written = init_tri_pts.copy()
+        scene.rots_written, scene.locs_written = init_rots, init_locs
+        try:
+            result = scene.prob.align(point_idx, targets, float(max_err) ** 2, max_hyp, iteration, rigid, apply)
+            moved = bool(apply) and not result[4] & (native.SIMILARITY_TOO_FEW | native.SIMILARITY_NO_MODEL)
+            if moved:
+                scene.cams_synced = False
+                cams, pts, rots = scene.prob.get_state_rot()
+        except Exception:
+            self.ba_release()
+            raise
+        if moved:
+            scene.pts_written = pts
+            scene.rots_written, scene.locs_written = rots, cams[:, 0:3].copy()
+            tri_pts[0:3, :] = pts
+            for view_idx, view in enumerate(views):
+                view.update_cam_pose(rots[view_idx].copy(), cams[view_idx, 0:3].reshape(3, 1).copy())
+        return result
 
     def filter_structure(self, max_reproj_px=4.0, min_angle_deg=1.5, min_obs=2):
         """``screen_structure``, then remove what failed from the resident scene on the device (``BaProblem.cull``): the
