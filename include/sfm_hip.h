@@ -1313,6 +1313,79 @@ int sfm_similarity_ransac_dev(int n_sets, const int* set_ptr /*host [n_sets+1]*/
 /* Host only, needs no device: the hypothesis count H of a set of n correspondences (0 for n < 4 or a max_hyp out of range)
  * and, for 0 <= h < H, the three ascending indices of hypothesis h. */
 int sfm_similarity_sample(int n, int max_hyp, int h, int idx[3]);
+
+/* ---- rotation averaging: spanning-tree hypotheses of a view graph, inlier refit on the Lie algebra -------------------
+ * The seventh robust estimator.  A graph has V views and E edges; edge e is (i_e, j_e, Rel_e[9]) with i_e != j_e and says
+ * R_j = Rel_e R_i, R_v taking world coordinates to the frame of view v: the R of sfm_twoview_pose with left i and right j.
+ * Parallel edges are allowed.  `root` is the view whose rotation is the identity.  All matrices are row-major.  The rule:
+ *   1. The test.  For rotations R_i, R_j and edge e, P = Rel_e R_i with
+ *        P[a][b] = fma(Rel[a][0], R_i[0][b], fma(Rel[a][1], R_i[1][b], Rel[a][2] * R_i[2][b])),
+ *      lhs = trace(R_j^T P), started as P[0][0] * R_j[0][0] and continued lhs = fma(P[a][b], R_j[a][b], lhs) over the other
+ *      eight entries in row-major order.  The edge is an INLIER iff lhs is finite and lhs >= fma(2, cos_max, 1); cos_max, in
+ *      (0, 1], is the cosine of the largest admitted residual angle.  No division, no acos.  One function
+ *      (rotation_edge_inlier, csrc/sfm_obs_test.h) that every stage calls; sfm_rotation_edge_test is its host entry.
+ *   2. Hypotheses: spanning trees.  H = max_hyp (0 means 128; range 1 .. 65 536).  Hypothesis h is a breadth-first tree from
+ *      the view `root` for h = 0 and mix((h << 32) | 0xFFFFFFFF) mod V otherwise (64-bit words).  The views of level d are
+ *      those without a depth that have an edge to a view of depth d - 1; such a view takes as parent edge the one among
+ *      those edges with the smallest (key, e), key = e for h = 0 and mix((h << 32) | e) otherwise; mix is the splitmix64
+ *      finaliser of the two-view rule.  Rotations follow the tree from the identity at its root: forward along an edge
+ *      R_j = Rel_e R_i by the product of step 1, backward R_i = Rel_e^T R_j with
+ *        Q[a][b] = fma(Rel[0][a], R_j[0][b], fma(Rel[1][a], R_j[1][b], Rel[2][a] * R_j[2][b])).
+ *      Views the tree does not reach hold NaN.  A hypothesis is valid iff its tree has an edge, reaches `root` and every
+ *      reached rotation is finite.  sfm_rotation_tree returns the same tree on any machine.
+ *   3. Score, lexicographic: the inlier count over all E edges (an integer; an edge with a NaN end is an outlier, a tree edge
+ *      an inlier by construction); then the lower h.  No valid hypothesis (root has no edge): SFM_ROTAVG_NO_MODEL.
+ *   4. Gauge.  The winner is multiplied on the right by R_root^T once,
+ *        G[a][b] = fma(R_v[a][0], R_root[b][0], fma(R_v[a][1], R_root[b][1], R_v[a][2] * R_root[b][2])),
+ *      and the root itself takes the exact identity.  The count that stands is the one scored.
+ *   5. Refit, up to `iters` rounds of `steps` Gauss-Newton steps each.  S is the inlier set of the standing model; the FREE
+ *      views are those connected to `root` through edges of S, except `root`; every other view is held for the round.  Per
+ *      step, for every edge of S between connected views, d_e = log(R_j^T Rel_e R_i) as a 3-vector (with v the vee of
+ *      (M - M^T) / 2, c = (trace - 1) / 2: d = (atan2(|v|, c) / |v|) v, the series 1 + |v|^2 / 6 + 3 |v|^4 / 40 below |v| = 1e-4;
+ *      cos_max > 0 keeps the angle below a quarter turn).  The update w minimises sum_S |d_e + w_i - w_j|^2 with w = 0 on
+ *      `root` and on held views: the graph Laplacian of S (integer degrees) times I_3 on the free views, right-hand side
+ *      b_v = sum of d_e over the edges of S with j_e = v minus the sum over those with i_e = v.  Then R_v <- R_v exp([w_v]x).
+ *      How the system is solved is not part of the rule; the library runs Jacobi-preconditioned conjugate gradients from
+ *      w = 0 until |r|^2 <= cg_tol^2 |b|^2 or for cg_max iterations (then SFM_ROTAVG_CG_LIMIT is set and the step is taken
+ *      with what it has).  A round stands iff every rotation of a free view is finite and its inlier count over all E is at
+ *      least the standing count; otherwise the rounds stop.  SFM_ROTAVG_KEPT_HYPOTHESIS iff iters > 0 and no round stood.
+ *   6. Outputs, all optional but R_out.  R_out[V][9]: nine zeros for a view outside root's component, or with no model.
+ *      edge_inlier[E] (0 with no model).  edge_cos[E]: (lhs - 1) / 2 of the standing model, NaN where an end has no rotation.
+ *      view_status[V]: SFM_ROTAVG_UNREACHED, no path from `root` in the input graph; SFM_ROTAVG_HELD, not connected to `root`
+ *      through the final inlier edges (its rotation is the last one it had; with no model every view is held).  n_inliers,
+ *      best_hyp (-1 with no model), status.  summary[6]: views with a rotation | unreached | held | inlier edges | outlier
+ *      edges between two views with rotations | rounds that stood.
+ *   7. Argument errors (SFM_E_SHAPE, found before a device is looked for, nothing launched, outputs untouched): V < 2, E < 1,
+ *      E >= 2^31 (and E >= 2^30: the 2 E edge ends are numbered by an int), an index out of range, i == j, root out of range,
+ *      cos_max NaN or outside (0, 1], max_hyp out of range, iters < 0, steps < 1, cg_tol not in (0, 1), cg_max < 1, a null
+ *      array.  Each Rel_e must pass verify_rotation: SFM_E_BAD_ROTATION, sfm_last_error naming the lowest such edge (the
+ *      _dev form finds it with one kernel, before anything else is launched).
+ * No floating-point atomic, integer counts, dot products per slice of 64 views in slice order: the bits depend on the graph
+ * and the options only.  The hypotheses are scored in batches whose rotations [batch][V][9] stay within 256 MiB; the winner
+ * is carried across batches by (count, h).  One graph per call.  The _dev form takes d_rel and every output on the device
+ * and a stream (NULL = the library stream); `edges` stays a HOST array, as set_ptr does elsewhere: it is checked, uploaded
+ * and turned into the view-major adjacency by the call.  It returns when the work is done. */
+#define SFM_ROTAVG_NO_MODEL         1   /* status: no valid spanning tree */
+#define SFM_ROTAVG_KEPT_HYPOTHESIS  2   /* status: no refit round stood: the model is the winning tree itself */
+#define SFM_ROTAVG_CG_LIMIT         4   /* status: a Gauss-Newton step ended its CG at cg_max */
+#define SFM_ROTAVG_UNREACHED        1   /* view_status: no path from root in the input graph */
+#define SFM_ROTAVG_HELD             2   /* view_status: not connected to root through the final inlier edges */
+int sfm_rotation_average(int V, int64_t E, const int* edges /*[E][2]*/, const double* rel /*[E][9]*/, int root, double cos_max,
+                         int max_hyp, int iters, int steps, double cg_tol, int cg_max, double* R_out /*[V][9]*/,
+                         unsigned char* edge_inlier /*[E] or NULL*/, double* edge_cos /*[E] or NULL*/,
+                         int* view_status /*[V] or NULL*/, int* n_inliers, int* best_hyp, int* status, int64_t* summary /*[6]*/);
+int sfm_rotation_average_dev(int V, int64_t E, const int* edges /*host [E][2]*/, const double* d_rel, int root, double cos_max,
+                             int max_hyp, int iters, int steps, double cg_tol, int cg_max, double* d_R_out,
+                             unsigned char* d_edge_inlier, double* d_edge_cos, int* d_view_status, int* d_n_inliers,
+                             int* d_best_hyp, int* d_status, int64_t* d_summary, void* hip_stream);
+/* Host only, needs no device: the hypothesis count H (0 for bad arguments) and, for 0 <= h < H, the tree of hypothesis h:
+ * parent_edge_out[V] (-1 for the tree's root and for views it does not reach) and depth_out[V] (-1 where not reached). */
+int sfm_rotation_tree(int V, int64_t E, const int* edges /*[E][2]*/, int root, int max_hyp, int h, int* parent_edge_out, int* depth_out);
+/* Step 1 on the host, by the function the kernels run: 1 for an inlier, *lhs_out (may be NULL) the trace. */
+int sfm_rotation_edge_test(const double Ri[9], const double Rj[9], const double Rel[9], double cos_max, double* lhs_out);
+/* The batch plan, host only: hypotheses per batch and the number of batches for V views under a cap of cap_bytes on the
+ * rotations of a batch.  cap_bytes also becomes the cap of the calls that follow (a hook for tests); 0 restores 256 MiB. */
+int sfm_rotation_plan(int V, int max_hyp, int64_t cap_bytes, int* batch, int* n_batches);
 /* The resident scene moved by X' = s A X + t, on the device: every point by the formula, every camera block [C, q] to
  * C' = s A C + t and q' = q(A R(q)), the library's canonical quaternion of the product (qw >= 0, not renormalised).
  * Refused before any launch: s not finite or not positive (SFM_E_SHAPE), A failing verify_rotation

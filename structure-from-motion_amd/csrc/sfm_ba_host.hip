@@ -385,6 +385,24 @@ static int ba_finish_structure(BaScene& sc, hipStream_t s, const char* who) {
   return SFM_E_SHAPE;
 }
 
+// The chain above for any list of M keys in 0 .. V - 1 on the device (the cameras of the scene's observations, the ends of
+// the edges of a view graph): d_ptr[V + 1] and d_list[M], the entries of a key in ascending order.  Enqueued on s.
+int key_major_list(long long M, int V, const int* d_key, int* d_ptr, int* d_list, hipStream_t s) {
+  // at most 1 024 chunks of at least 1 024 entries: the count table stays within 1 024 V integers
+  const int chunk_obs = (int)std::max<long long>(1024, ((M + 1023) / 1024 + 63) / 64 * 64);
+  const int nchunks = (int)((M + chunk_obs - 1) / chunk_obs);
+  DevBuf<int> table, cnt;
+  SFM_TRY(table.alloc((size_t)nchunks * V, s));
+  SFM_TRY(cnt.alloc((size_t)V, s));
+  SFM_HIP(hipMemsetAsync(table.p, 0, sizeof(int) * (size_t)nchunks * V, s));
+  ba_cam_list_count_kernel<<<(unsigned)((M + 255) / 256), 256, 0, s>>>(M, V, chunk_obs, d_key, table.p);
+  ba_cam_list_chunk_scan_kernel<<<(V + 255) / 256, 256, 0, s>>>(V, nchunks, table.p, cnt.p);
+  ba_cam_list_ptr_scan_kernel<<<1, kScanBlock, 0, s>>>(V, cnt.p, d_ptr);
+  ba_cam_list_fill_kernel<<<nchunks, 64, 0, s>>>(M, V, chunk_obs, d_key, d_ptr, table.p, d_list);
+  SFM_HIP(hipGetLastError());
+  return SFM_OK;
+}
+
 // The scene's camera-major list, built on first use by the row-panel product or the motion-only refinement (a grown or
 // culled scene is a new BaScene and starts without one).  Needs M > 0; blocks once for the host copy of cam_ptr.
 int ba_cam_list_ensure(sfm_ba_problem* p) {
@@ -395,18 +413,7 @@ int ba_cam_list_ensure(sfm_ba_problem* p) {
   const long long M = d.M;
   SFM_TRY(scene_alloc(*p, p->cam_ptr, (size_t)V + 1));
   SFM_TRY(scene_alloc(*p, p->cam_obs, (size_t)M));
-  // at most 1 024 chunks of at least 1 024 observations: the count table stays within 1 024 V integers
-  const int chunk_obs = (int)std::max<long long>(1024, ((M + 1023) / 1024 + 63) / 64 * 64);
-  const int nchunks = (int)((M + chunk_obs - 1) / chunk_obs);
-  DevBuf<int> table, cnt;
-  SFM_TRY(table.alloc((size_t)nchunks * V, s));
-  SFM_TRY(cnt.alloc((size_t)V, s));
-  SFM_HIP(hipMemsetAsync(table.p, 0, sizeof(int) * (size_t)nchunks * V, s));
-  ba_cam_list_count_kernel<<<(unsigned)((M + 255) / 256), 256, 0, s>>>(M, V, chunk_obs, d.cam_idx, table.p);
-  ba_cam_list_chunk_scan_kernel<<<(V + 255) / 256, 256, 0, s>>>(V, nchunks, table.p, cnt.p);
-  ba_cam_list_ptr_scan_kernel<<<1, kScanBlock, 0, s>>>(V, cnt.p, p->cam_ptr);
-  ba_cam_list_fill_kernel<<<nchunks, 64, 0, s>>>(M, V, chunk_obs, d.cam_idx, p->cam_ptr, table.p, p->cam_obs);
-  SFM_HIP(hipGetLastError());
+  SFM_TRY(key_major_list(M, V, d.cam_idx, p->cam_ptr, p->cam_obs, s));
   p->h_cam_ptr.assign((size_t)V + 1, 0);
   SFM_HIP(hipMemcpyAsync(p->h_cam_ptr.data(), p->cam_ptr, sizeof(int) * ((size_t)V + 1), hipMemcpyDeviceToHost, s));
   SFM_TRY(stream_sync(s));

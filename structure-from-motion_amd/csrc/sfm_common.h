@@ -118,6 +118,11 @@ struct TrackObservations {
 };
 int track_observations(sfm_track_store* s, const char* who, TrackObservations* out);      // sfm_track.hip
 
+// The key-major list of M keys in 0 .. V - 1 held on the device (sfm_ba_host.hip): d_ptr[V + 1] the offsets, d_list[M] the
+// entries of every key in ascending order.  The camera-major observation list of a scene and the view-major adjacency of a
+// view graph (sfm_rotavg.hip) are both this list.  Waits for s before it returns (its work buffers go back to the pool).
+int key_major_list(long long M, int V, const int* d_key, int* d_ptr, int* d_list, hipStream_t s);
+
 // First-failure status word written by kernels: status[0] = code (0 = ok), status[1] = index.
 __device__ __forceinline__ void report_status(int* status, int code, int index) {
   if (code != SFM_OK && atomicCAS(&status[0], 0, code) == 0) status[1] = index;

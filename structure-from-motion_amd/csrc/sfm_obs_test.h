@@ -111,6 +111,41 @@ __host__ __device__ inline bool similarity_inlier(const double* Mt, double ax, d
   return (bool)((int)(__builtin_isfinite(lhs) != 0) & (int)(lhs <= max_err2));
 }
 
+// P = Rel R, both row-major: P[a][b] = fma(Rel[a][0], R[0][b], fma(Rel[a][1], R[1][b], Rel[a][2] * R[2][b])).  The step forward
+// along an edge of a view graph (R_j = Rel R_i) and the first half of its test.
+__host__ __device__ inline void rotation_forward(const double* Rel, const double* R, double* P) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+      P[3 * a + b] = __builtin_fma(Rel[3 * a], R[b], __builtin_fma(Rel[3 * a + 1], R[3 + b], Rel[3 * a + 2] * R[6 + b]));
+}
+
+// Q = Rel^T R: Q[a][b] = fma(Rel[0][a], R[0][b], fma(Rel[1][a], R[1][b], Rel[2][a] * R[2][b])).  The step backward along an
+// edge (R_i = Rel^T R_j).
+__host__ __device__ inline void rotation_backward(const double* Rel, const double* R, double* Q) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+      Q[3 * a + b] = __builtin_fma(Rel[a], R[b], __builtin_fma(Rel[3 + a], R[3 + b], Rel[6 + a] * R[6 + b]));
+}
+
+// The test of one EDGE (i, j, Rel) of a view graph against the rotations R_i, R_j of its ends: with P = Rel R_i
+// (rotation_forward), lhs = trace(R_j^T P) = sum_ab P[a][b] R_j[a][b], started as P[0] * R_j[0] and continued as
+// lhs = fma(P[k], R_j[k], lhs) for k = 1 .. 8 in row-major order; 1 + 2 cos of the residual angle.  An inlier iff lhs is
+// finite and lhs >= thr, thr = fma(2, cos_max, 1) formed once by the caller.  No division, no acos.  Every stage of the
+// rotation averaging (score, refit, judge) and sfm_rotation_edge_test call this one function; no branch.
+__host__ __device__ inline bool rotation_edge_inlier(const double* Ri, const double* Rj, const double* Rel, double thr, double* lhs_out) {
+  double P[9];
+  rotation_forward(Rel, Ri, P);
+  double lhs = P[0] * Rj[0];
+#pragma unroll
+  for (int k = 1; k < 9; ++k) lhs = __builtin_fma(P[k], Rj[k], lhs);
+  *lhs_out = lhs;
+  return (bool)((int)(__builtin_isfinite(lhs) != 0) & (int)(lhs >= thr));
+}
+
 // The terms of the test of one MATCH against a relative pose (R, t), X_right = R X_left + t: the rays (a0, a1, 1) of the
 // left key and (b0, b1, 1) of the right key in normalised coordinates, a' = R a, p = a'.a', q = b.b, r = a'.b,
 // d = p q - r r, and the numerators m1, m2 of the depths along a' and b of the midpoint of the two rays, both over d.

@@ -147,3 +147,33 @@ def apply_similarity(sim, cams, pts):
     if pts is not None:
         new_pts = s * (A @ np.asarray(pts, dtype=np.float64)) + t[:, None]
     return new_cams, new_pts
+
+
+def so3_log(rot):
+    """The rotation vector (3,) of a rotation whose angle is below a half turn, as the rotation averaging takes it
+    (include/sfm_hip.h, "rotation averaging", step 5): ``v`` the vee of ``(M - M^T) / 2``, ``c = (trace - 1) / 2``,
+    ``(atan2(|v|, c) / |v|) v`` with the series ``1 + |v|^2 / 6 + 3 |v|^4 / 40`` below ``|v| = 1e-4``."""
+    M = np.asarray(rot, dtype=np.float64).reshape(3, 3)
+    v = 0.5 * np.array([M[2, 1] - M[1, 2], M[0, 2] - M[2, 0], M[1, 0] - M[0, 1]])
+    c = 0.5 * (M[0, 0] + M[1, 1] + M[2, 2] - 1.0)
+    s = math.sqrt(float(v @ v))
+    f = 1.0 + s * s * (1.0 / 6.0 + s * s * (3.0 / 40.0)) if s < 1e-4 else math.atan2(s, c) / s
+    return f * v
+
+
+def so3_exp(w):
+    """``exp([w]x) = I + A [w]x + B [w]x^2`` with ``A = sin(t) / t``, ``B = (1 - cos t) / t^2``, ``t = |w|``, and their series
+    below ``t = 1e-4``: the update of the rotation averaging, ``R <- R exp([w]x)``."""
+    w = np.asarray(w, dtype=np.float64).reshape(3)
+    t2 = float(w @ w)
+    t = math.sqrt(t2)
+    A = 1.0 - t2 / 6.0 if t < 1e-4 else math.sin(t) / t
+    B = 0.5 - t2 / 24.0 if t < 1e-4 else (1.0 - math.cos(t)) / t2
+    W = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    return np.identity(3) + A * W + B * (W @ W)
+
+
+def compose_relative(R_i, rel):
+    """``R_j = rel R_i``: the rotation of the right view of a pair from the left one's and the pair's relative rotation (the
+    ``R`` of ``native.twoview_pose``, X_right = R X_left + t); both take world coordinates to the view's frame."""
+    return np.asarray(rel, dtype=np.float64).reshape(3, 3) @ np.asarray(R_i, dtype=np.float64).reshape(3, 3)

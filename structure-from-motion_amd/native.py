@@ -70,6 +70,11 @@ SIMILARITY_RIGID = 1
 SIMILARITY_MAX_HYP, SIMILARITY_DEFAULT_HYP, SIMILARITY_MIN_SET = 65536, 128, 4
 SIMILARITY_SUMMARY = ("sets_solved", "sets_no_model", "sets_too_few", "sets_kept_hypothesis", "pairs_inlier", "pairs_outlier")
 SIMILARITY_OUTPUTS = TWOVIEW_OUTPUTS
+ROTAVG_NO_MODEL, ROTAVG_KEPT_HYPOTHESIS, ROTAVG_CG_LIMIT = 1, 2, 4
+ROTAVG_UNREACHED, ROTAVG_HELD = 1, 2
+ROTAVG_MAX_HYP, ROTAVG_DEFAULT_HYP = 65536, 128
+ROTAVG_SUMMARY = ("views_with_rotation", "views_unreached", "views_held", "edges_inlier", "edges_outlier", "rounds_stood")
+ROTAVG_OUTPUTS = ("edge_inlier", "edge_cos", "view_status", "n_inliers", "best_hyp", "status", "summary")
 POSE_FROM_F, POSE_FROM_H = 0, 1
 POSE_EMPTY, POSE_NO_MODEL, POSE_NO_POSE, POSE_TIED, POSE_NO_PARALLAX = 1, 2, 4, 8, 16
 POSE_CANDIDATES = 4
@@ -274,6 +279,11 @@ SIGNATURES = {
     "sfm_similarity_ransac": [ci, _ip, i64, _dp, _dp, cd, ci, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip, _lp],
     "sfm_similarity_ransac_dev": [ci, _ip, i64, vp, vp, cd, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp],
     "sfm_similarity_sample": [ci, ci, ci, _ip],
+    "sfm_rotation_average": [ci, i64, _ip, _dp, ci, cd, ci, ci, ci, cd, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _ip, _ip, _ip, _lp],
+    "sfm_rotation_average_dev": [ci, i64, _ip, vp, ci, cd, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "sfm_rotation_tree": [ci, i64, _ip, ci, ci, ci, _ip, _ip],
+    "sfm_rotation_edge_test": [_dp, _dp, _dp, cd, _dp],
+    "sfm_rotation_plan": [ci, ci, i64, _ip, _ip],
     "sfm_ba_transform": [vp, cd, _dp, _dp],
     "sfm_ba_align": [vp, ci, _ip, _dp, cd, ci, ci, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip],
     "sfm_twoview_pose": [ci, _ip, i64, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _dp, _dp, cd, ci, _dp, _dp, _dp, _ip, _ip, _ip,
@@ -994,6 +1004,147 @@ def split_similarity(sim):
     """``(s, A (3, 3), t (3,))`` of one model of 13 doubles."""
     sim = f64(sim).reshape(13)
     return float(sim[0]), sim[1:10].reshape(3, 3).copy(), sim[10:13].copy()
+
+
+# ---- rotation averaging over a view graph (sfm_rotation_*; no reference counterpart) ------------------------------------
+def check_rotation_graph(n_views, edges, rel, root=0, cos_max=1.0, max_hyp=0, iters=2, steps=2, cg_tol=1e-12, cg_max=200):
+    """The arguments of a ``rotation_average`` call, without a device: ``(n_views, edges int32 (E, 2), rel (E, 9), root,
+    cos_max, max_hyp, iters, steps, cg_tol, cg_max)`` converted or ValueError -- everything sfm_rotation_average refuses, in
+    its order; a ``Rel`` that is no rotation raises the ValueError of the library's verify_rotation and names the edge."""
+    def integer(name, value):
+        if isinstance(value, bool) or int(value) != value:
+            raise ValueError("%s must be an integer, got %r" % (name, value))
+        return int(value)
+    n_views, root = integer("n_views", n_views), integer("root", root)
+    max_hyp, iters, steps, cg_max = integer("max_hyp", max_hyp), integer("iters", iters), integer("steps", steps), integer("cg_max", cg_max)
+    cos_max, cg_tol = float(cos_max), float(cg_tol)
+    edges_in = np.asarray(edges)
+    if edges_in.ndim != 2 or edges_in.shape[1] != 2 or (edges_in.size and not np.all(edges_in == np.floor(edges_in))):
+        raise ValueError("edges must be integers of shape (E, 2), got %r" % (edges_in.shape,))
+    rel = f64(rel)
+    n_edges = edges_in.shape[0]
+    if rel.size != 9 * n_edges or rel.ndim not in (2, 3):
+        raise ValueError("rel must be (E, 9) or (E, 3, 3) with E = %d, got %r" % (n_edges, rel.shape))
+    rel = rel.reshape(n_edges, 9)
+    if n_views < 2 or n_edges < 1 or n_edges >= 2 ** 30:
+        raise ValueError("bad sizes V=%d E=%d (V >= 2, 1 <= E < 2^30)" % (n_views, n_edges))
+    if not 0 <= root < n_views:
+        raise ValueError("root = %d must be in 0 .. %d" % (root, n_views - 1))
+    if not (0.0 < cos_max <= 1.0):
+        raise ValueError("cos_max = %r must be in (0, 1]" % cos_max)
+    if not 0 <= max_hyp <= ROTAVG_MAX_HYP:
+        raise ValueError("max_hyp = %d must be in 1 .. %d (0 = %d)" % (max_hyp, ROTAVG_MAX_HYP, ROTAVG_DEFAULT_HYP))
+    if iters < 0:
+        raise ValueError("iters = %d must be >= 0" % iters)
+    if steps < 1:
+        raise ValueError("steps = %d must be >= 1" % steps)
+    if not (0.0 < cg_tol < 1.0):
+        raise ValueError("cg_tol = %r must be in (0, 1)" % cg_tol)
+    if cg_max < 1:
+        raise ValueError("cg_max = %d must be >= 1" % cg_max)
+    bad = (edges_in < 0) | (edges_in >= n_views)
+    bad = bad[:, 0] | bad[:, 1] | (edges_in[:, 0] == edges_in[:, 1])
+    if bad.any():
+        e = int(np.argmax(bad))
+        raise ValueError("edge %d = (%d, %d) must join two different views in 0 .. %d" % (e, edges_in[e, 0], edges_in[e, 1], n_views - 1))
+    edges = np.ascontiguousarray(edges_in, dtype=np.int32)
+    bad = ~_verify_rotations(rel)
+    if bad.any():
+        raise ValueError("convert_quaternion_to_rotation : Invalid output rotation matrix (Rel of edge %d is not a rotation)"
+                         % int(np.argmax(bad)))
+    return n_views, edges, rel, root, cos_max, max_hyp, iters, steps, cg_tol, cg_max
+
+
+def _verify_rotations(R):
+    """The library's verify_rotation (csrc/sfm_math.h) on rows of nine: False iff det - 1 >= 1e-8 or an entry of the inverse by
+    adjugate exceeds the transpose's by more than 1e-8; a NaN passes, as it does there."""
+    with np.errstate(all="ignore"):
+        m = [R[:, k] for k in range(9)]
+        det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6])
+        inv_det = 1.0 / det
+        inv = [(m[4] * m[8] - m[5] * m[7]), (m[2] * m[7] - m[1] * m[8]), (m[1] * m[5] - m[2] * m[4]),
+               (m[5] * m[6] - m[3] * m[8]), (m[0] * m[8] - m[2] * m[6]), (m[2] * m[3] - m[0] * m[5]),
+               (m[3] * m[7] - m[4] * m[6]), (m[1] * m[6] - m[0] * m[7]), (m[0] * m[4] - m[1] * m[3])]
+        ok = ~(det - 1 >= 1e-8)
+        for i in range(3):
+            for j in range(3):
+                ok &= ~(inv[3 * i + j] * inv_det - m[3 * j + i] > 1e-8)
+    return ok
+
+
+def rotation_edge_test(R_i, R_j, rel, cos_max):
+    """``(inlier, lhs)`` of one edge against the rotations of its ends (sfm_rotation_edge_test; host only): ``lhs`` is the trace
+    of ``R_j^T Rel R_i`` in the library's operation order, an inlier iff it is finite and ``>= fma(2, cos_max, 1)``."""
+    R_i, R_j, rel = f64(R_i).reshape(9), f64(R_j).reshape(9), f64(rel).reshape(9)
+    lhs = np.zeros(1)
+    inlier = load().sfm_rotation_edge_test(dptr(R_i), dptr(R_j), dptr(rel), float(cos_max), dptr(lhs))
+    return bool(inlier), float(lhs[0])
+
+
+def rotation_tree(n_views, edges, root, max_hyp, h):
+    """``(H, parent_edge (V,), depth (V,))``: the breadth-first spanning tree of hypothesis ``h`` of a view graph
+    (sfm_rotation_tree; host only); -1 marks the tree's root (parent) and views it does not reach (both).  ``H`` is 0 for
+    arguments the library refuses."""
+    edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+    parent = np.full(max(int(n_views), 1), -1, dtype=np.int32)
+    depth = np.full(max(int(n_views), 1), -1, dtype=np.int32)
+    count = int(load().sfm_rotation_tree(int(n_views), edges.shape[0], iptr(edges), int(root), int(max_hyp), int(h), iptr(parent), iptr(depth)))
+    return count, parent, depth
+
+
+def rotation_plan(n_views, max_hyp=0, cap_bytes=0):
+    """``(batch, n_batches)`` of the hypotheses of a call for ``n_views`` views when the rotations of a batch stay within
+    ``cap_bytes`` (sfm_rotation_plan; host only).  The cap also holds for the calls that follow -- a hook for tests; 0
+    restores the library's 256 MiB."""
+    batch, n_batches = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    check(load().sfm_rotation_plan(int(n_views), int(max_hyp), int(cap_bytes), iptr(batch), iptr(n_batches)))
+    return int(batch[0]), int(n_batches[0])
+
+
+def rotation_average(n_views, edges, rel, root=0, cos_max=None, max_hyp=0, iters=2, steps=2, cg_tol=1e-12, cg_max=200,
+                     max_angle_deg=5.0, outputs=ROTAVG_OUTPUTS):
+    """Robust absolute rotations of a view graph (sfm_rotation_average): edge ``e = (i, j)`` with ``rel[e]`` says
+    ``R_j = rel[e] R_i``; spanning-tree hypotheses scored by their inlier count under a residual angle whose cosine is at
+    least ``cos_max`` (default: that of ``max_angle_deg``), then up to ``iters`` rounds of ``steps`` Gauss-Newton steps over
+    the inliers.  Returns ``R (V, 3, 3)`` -- zeros outside the root's component or without a model -- and ``edge_inlier (E,)
+    uint8, edge_cos (E,), view_status (V,) of ROTAVG_UNREACHED / ROTAVG_HELD bits, n_inliers, best_hyp, status of ROTAVG_*
+    bits, summary (6,) int64`` in the order of ``ROTAVG_SUMMARY``; an output not named in ``outputs`` is not computed and
+    comes back as None."""
+    if cos_max is None:
+        cos_max = float(np.cos(np.deg2rad(float(max_angle_deg))))
+    V, edges, rel, root, cos_max, max_hyp, iters, steps, cg_tol, cg_max = check_rotation_graph(
+        n_views, edges, rel, root, cos_max, max_hyp, iters, steps, cg_tol, cg_max)
+    unknown = set(outputs) - set(ROTAVG_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (ROTAVG_OUTPUTS, sorted(unknown)))
+    E = edges.shape[0]
+    R = np.zeros((V, 9))
+    o = {"edge_inlier": np.zeros(E, dtype=np.uint8), "edge_cos": np.zeros(E), "view_status": np.zeros(V, dtype=np.int32),
+         "n_inliers": np.zeros(1, dtype=np.int32), "best_hyp": np.zeros(1, dtype=np.int32), "status": np.zeros(1, dtype=np.int32),
+         "summary": np.zeros(6, dtype=np.int64)}
+    w = {k: (v if k in outputs else None) for k, v in o.items()}
+    check(load().sfm_rotation_average(V, E, iptr(edges), dptr(rel), root, cos_max, max_hyp, iters, steps, cg_tol, cg_max, dptr(R),
+                                      _u8ptr(w["edge_inlier"]), dptr(w["edge_cos"]), iptr(w["view_status"]), iptr(w["n_inliers"]),
+                                      iptr(w["best_hyp"]), iptr(w["status"]), _lptr(w["summary"])))
+    out = []
+    for name in ROTAVG_OUTPUTS:
+        v = w[name]
+        out.append(None if v is None else (int(v[0]) if name in ("n_inliers", "best_hyp", "status") else v))
+    return (R.reshape(V, 3, 3),) + tuple(out)
+
+
+def rotation_average_dev(n_views, edges, d_rel, root=0, cos_max=None, max_hyp=0, iters=2, steps=2, cg_tol=1e-12, cg_max=200,
+                         max_angle_deg=5.0, d_R_out=0, d_edge_inlier=0, d_edge_cos=0, d_view_status=0, d_n_inliers=0, d_best_hyp=0,
+                         d_status=0, d_summary=0, stream=0):
+    """``rotation_average`` with ``d_rel`` (E, 9) and the outputs as device pointers and a caller's stream
+    (sfm_rotation_average_dev); ``edges`` stays a host array, optional arrays are 0."""
+    if cos_max is None:
+        cos_max = float(np.cos(np.deg2rad(float(max_angle_deg))))
+    edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+    check(load().sfm_rotation_average_dev(int(n_views), edges.shape[0], iptr(edges), _vp(d_rel), int(root), float(cos_max), int(max_hyp),
+                                          int(iters), int(steps), float(cg_tol), int(cg_max), _vp(d_R_out), _vp(d_edge_inlier),
+                                          _vp(d_edge_cos), _vp(d_view_status), _vp(d_n_inliers), _vp(d_best_hyp), _vp(d_status),
+                                          _vp(d_summary), _vp(stream)))
 
 
 # ---- robust essential matrix (sfm_essential_*; no reference counterpart) ------------------------------------------------

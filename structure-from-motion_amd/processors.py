@@ -430,6 +430,46 @@ class HipCamposeMixin:
         centre = np.zeros(3) if pair_centre is None else np.asarray(pair_centre, dtype=np.float64).reshape(3)
         return s, A, t.reshape(3, 1), np.flatnonzero(inlier).tolist(), A @ rot, (s * (A @ centre) + t).reshape(3, 1)
 
+    def average_rotations(self, pair_results, n_views, root=0, max_angle_deg=5.0, max_hyp=128, iteration=2):
+        """Absolute rotations of ``n_views`` views from the relative poses of their verified pairs (one
+        ``native.rotation_average``; no reference counterpart).  ``pair_results`` holds one entry per pair: a triple
+        ``(ref, que, R)`` with ``X_que = R X_ref + t``, or a dict ``initialise_pairs`` returned to which the caller added the
+        view indices as ``"ref"`` and ``"que"``.  A pair without a pose (``R`` None or all zeros; a dict with
+        ``best_cand < 0`` or ``native.POSE_NO_POSE``) is skipped.  An edge counts as consistent while its residual angle is at
+        most ``max_angle_deg``; ``max_hyp`` spanning trees are scored and ``iteration`` refit rounds of two Gauss-Newton
+        steps follow.
+
+        Returns ``rots, verdict``: ``rots`` is a list of ``n_views`` (3, 3) matrices in the reference's convention
+        (``rot = R_v^T``, projection ``K [rot^T | -rot^T centre]``; the identity for ``root``, None for a view without a
+        rotation) and ``verdict`` a dict with ``pairs`` (the index into ``pair_results`` of every edge), ``edge_inlier``,
+        ``edge_cos``, ``view_status``, ``n_inliers``, ``best_hyp``, ``status`` and ``summary``.  ``rotation_last`` keeps it."""
+        if not 0.0 <= float(max_angle_deg) < 90.0:
+            raise ValueError("max_angle_deg must be in [0, 90), got {!r}".format(max_angle_deg))
+        edges, rel, used = [], [], []
+        for k, entry in enumerate(pair_results):
+            if isinstance(entry, dict):
+                if entry.get("best_cand", 0) < 0 or entry.get("status", 0) & native.POSE_NO_POSE:
+                    continue
+                ref, que, R = entry["ref"], entry["que"], entry["R"]
+            else:
+                ref, que, R = entry
+            if R is None or not np.any(R):
+                continue
+            edges.append((int(ref), int(que)))
+            rel.append(np.asarray(R, dtype=np.float64).reshape(9))
+            used.append(k)
+        if not edges:
+            raise ValueError("average_rotations: no pair with a pose")
+        R, edge_inlier, edge_cos, view_status, n_inliers, best_hyp, status, summary = native.rotation_average(
+            n_views, np.array(edges, dtype=np.int32), np.array(rel), root=root, max_angle_deg=float(max_angle_deg), max_hyp=max_hyp,
+            iters=iteration, steps=2)
+        has = (view_status & native.ROTAVG_UNREACHED) == 0 if not status & native.ROTAVG_NO_MODEL else np.zeros(int(n_views), dtype=bool)
+        rots = [R[v].T.copy() if has[v] else None for v in range(int(n_views))]
+        verdict = dict(pairs=used, edge_inlier=edge_inlier.astype(bool), edge_cos=edge_cos, view_status=view_status, n_inliers=n_inliers,
+                       best_hyp=best_hyp, status=status, summary=summary)
+        self.rotation_last = verdict
+        return rots, verdict
+
     def estimate_relative_pose_minimal(self, matched_pairs, K_left, K_right, max_px=2.0, max_hyp=128, refine_iters=6, min_angle_deg=2.0):
         """The relative pose of a calibrated pair straight from its matches (no reference counterpart): ONE
         ``native.essential_ransac`` (five-point hypotheses at ``max_px`` pixels of Sampson distance), then ONE
@@ -2073,6 +2113,35 @@ def pose_pairs(tracker, ref_idx, que_idx, model, kind, K_left, K_right, inlier=N
         counts.update(_refined_entry(ref, 0, 0, num, counts["best_cand"] >= 0))
         tracker.refine_last = f
     return o["r_idx"].reshape(1, num).astype(int), o["q_idx"].reshape(1, num).astype(int), rot, centre, front, counts
+
+
+def orient_views(tracker, pairs, K, K_right=None, root=0, max_sampson_px=2.0, max_hyp=128, iteration=2, min_angle_deg=2.0,
+                 min_parallax=8, max_angle_deg=5.0, tree_hyp=128, rounds=2):
+    """Absolute rotations of the views of a ``HipDeviceKeyTracker`` from the listed ``pairs`` ``(ref_idx, que_idx)``: per
+    pair ONE ``verify_pairs`` and, where it has a model, ONE ``pose_pairs`` from that model with its inliers voting (no
+    coordinate comes down), then ONE ``HipCamposeMixin.average_rotations`` over the poses found.  Returns ``rots, verdict,
+    poses``: the first two as ``average_rotations`` returns them (``verdict["pairs"]`` indexes ``pairs``), ``poses`` one dict
+    per listed pair (``R``, ``t``, ``status`` of the pose call, ``twoview_status``; ``R`` is None without a pose).  A
+    function of the module, like ``verify_pairs``; ``process()`` does not call it."""
+    K_right = K if K_right is None else K_right
+    n_views = len(tracker.track_list)
+    poses, triples = [], []
+    for ref_idx, que_idx in pairs:
+        entry = {"ref": int(ref_idx), "que": int(que_idx), "R": None, "t": None, "status": native.POSE_NO_POSE, "twoview_status": None}
+        got = verify_pairs(tracker, ref_idx, que_idx, max_sampson_px, max_hyp, iteration)
+        if got is not None:
+            entry["twoview_status"] = int(tracker.twoview_last["status"])
+            if tracker.twoview_last["hypothesis"] >= 0:
+                posed = pose_pairs(tracker, ref_idx, que_idx, tracker.twoview_last["fund_mat"], "fundamental", K, K_right, got[2],
+                                   min_angle_deg, min_parallax)
+                counts = posed[5]
+                entry["status"] = counts["status"]
+                if counts["best_cand"] >= 0 and not counts["status"] & native.POSE_NO_POSE:
+                    entry["R"], entry["t"] = tracker.pose_last["R"].copy(), tracker.pose_last["t"].copy()
+        poses.append(entry)
+        triples.append((entry["ref"], entry["que"], entry["R"]))
+    rots, verdict = HipCamposeMixin().average_rotations(triples, n_views, root, max_angle_deg, tree_hyp, rounds)
+    return rots, verdict, poses
 
 
 def _guided_model(model):
