@@ -1386,6 +1386,85 @@ int sfm_rotation_edge_test(const double Ri[9], const double Rj[9], const double 
 /* The batch plan, host only: hypotheses per batch and the number of batches for V views under a cap of cap_bytes on the
  * rotations of a batch.  cap_bytes also becomes the cap of the calls that follow (a hook for tests); 0 restores 256 MiB. */
 int sfm_rotation_plan(int V, int max_hyp, int64_t cap_bytes, int* batch, int* n_batches);
+
+/* ---- translation averaging: view positions from the directions of a view graph, rotations known ----------------------
+ * The graph is that of the rotation averaging: V views, E edges (i_e, j_e), i_e != j_e, parallel edges allowed.  R[V][9] are
+ * the absolute rotations (world to view, row-major: the R_out of sfm_rotation_average; nine zeros: the view has no
+ * rotation), t[E][3] the t of sfm_twoview_pose with left i_e and right j_e (X_j = Rel X_i + t; its length is not used),
+ * edge_mask[E] optional bytes (0 excludes an edge; NULL: none is excluded).  `root` is the view at the origin.  The rule:
+ *   1. Directions.  u[a] = -fma(R_j[0][a], t[0], fma(R_j[1][a], t[1], R_j[2][a] * t[2])), m = fma(u[0], u[0], fma(u[1], u[1],
+ *      u[2] * u[2])), d_e[a] = u[a] / sqrt(m): with R_j = Rel_e R_i the world direction from c_i to c_j.  The edge is USED iff
+ *      its mask byte is non-zero (or there is no mask), both ends have a rotation (an entry of the nine is non-zero) and
+ *      tt = fma(t[0], t[0], fma(t[1], t[1], t[2] * t[2])) is finite and positive.  Every other edge has weight 0 throughout
+ *      and verdict 0.
+ *   2. The test.  For positions c: v = c_j - c_i, dv = fma(d[0], v[0], fma(d[1], v[1], d[2] * v[2])), n2 = fma(v[0], v[0],
+ *      fma(v[1], v[1], v[2] * v[2])).  A used edge is an INLIER iff dv and n2 are finite, dv > 0 and dv * dv >= cc * n2 with
+ *      cc = cos_max * cos_max formed once; cos_max, in (0, 1], is the cosine of the largest admitted angle between d_e and
+ *      c_j - c_i.  No division, no square root, no acos.  One function (translation_edge_inlier, csrc/sfm_obs_test.h) that
+ *      every stage calls; sfm_translation_edge_test is its host entry.
+ *   3. A solve takes weights w_e and target lengths l_e; an edge takes part iff w_e > 0 (a NaN does not).  The FREE views are
+ *      those joined to `root` through edges that take part, except `root`; every other view is held at the position it has
+ *      (zero before the first solve); `root` is at zero throughout.  The solve minimises
+ *        sum_e w_e ( |P_e v_e|^2 + mu (d_e . v_e - l_e)^2 ),  P_e = I - d_e d_e^T,  v_e = c_j - c_i
+ *      over the free views (mu in (0, 1]; 0 means 0.01): a symmetric positive definite system of 3x3 blocks with the edge
+ *      block B_e = w_e (I - (1 - mu) d_e d_e^T), the diagonal block of a view the sum of B_e over its edges, -B_e between
+ *      the ends of an edge, and the right-hand side + w_e mu l_e d_e at j_e, - the same at i_e.  The library forms, per
+ *      view and over its adjacency in the order of the key-major list (entry x = 2 e + dir, dir = 1 where the view is j_e),
+ *        B_e y:  g = (1 - mu) * fma(d[0], y[0], fma(d[1], y[1], d[2] * y[2])),  z[a] = w * fma(-g, d[a], y[a]),  y = u_v - u_o,
+ *        the diagonal block D[a][b] += w * fma(-(1 - mu), d[a] * d[b], a == b), the right-hand side b[a] += sg * (((w * mu) * l) * d[a]),
+ *      and the inverse of D by its cofactors over the determinant.  How the system is solved is not part of the rule: the
+ *      library runs conjugate gradients preconditioned by those inverses, from the standing positions, until
+ *      |r|^2 <= cg_tol^2 |b|^2 (looked at before the first iteration too) or for cg_max iterations; then
+ *      SFM_TRANSAVG_CG_LIMIT is set and the result is taken as it is.  Every dot product is formed per slice of 64 views
+ *      and the slices are added in slice order.
+ *   4. Rounds.  Round 0 solves with w_e = 1 on the used edges and l_e = 1.  Then `rounds` times weights and lengths are
+ *      reset from the standing positions and the system is solved again: s2 = 2 - 2 * (dv / sqrt(n2)), the squared chord of
+ *      the residual angle (s2 = 2 where n2 is zero or not finite); w_e = 1 / (1 + s2 / sigma2), sigma2 = 2 - 2 * cos_max, a
+ *      Cauchy weight at the admitted angle; l_e = dv where dv > 0, else 1.  After the last solve every used edge is judged
+ *      by step 2; that set and its count stand.
+ *   5. Polish.  If `polish`, one more solve with w_e = 1 on the inliers, 0 elsewhere, and l_e = dv of the standing model.  It
+ *      stands iff every free position is finite and its inlier count over all used edges is at least the standing count;
+ *      otherwise the standing model is kept and SFM_TRANSAVG_KEPT_ROUNDS is set.  The decision is taken on the device.
+ *   6. Status SFM_TRANSAVG_NO_MODEL: `root` has no rotation, `root` has no used edge, or a free position is not finite after
+ *      round 0; then C_out is all zeros, every verdict is 0, every view is held and the log is all zeros.  Outputs, all
+ *      optional but C_out.  C_out[V][3]: zeros for a view without a position (not reached from `root` over used edges).
+ *      edge_inlier[E].  edge_cos[E]: dv / sqrt(n2), NaN where n2 is zero or not finite or the edge is not used.  edge_len[E]:
+ *      dv of the final model, the baseline in the solution's unit (the caller scales a pair's own reconstruction with it);
+ *      NaN where the edge is not used.  view_status[V]: SFM_TRANSAVG_NO_ROTATION | SFM_TRANSAVG_UNREACHED (no path from `root`
+ *      over used edges) | SFM_TRANSAVG_HELD (not joined to `root` through the final inliers).  n_inliers, status.
+ *      summary[6]: views with a position | without a rotation | unreached | held | inlier edges | used outlier edges.
+ *      log[rounds + 2][4] doubles, a row per solve (row rounds + 1 is the polish, zeros without one): its inlier count, its
+ *      CG iterations, whether it stood (1 for a round), and its cost sum_e w_e ((n2 - dv * dv) + mu (dv - l_e)^2) under the
+ *      weights of that solve, summed per slice of 64 edges in slice order.
+ *   7. Argument errors (SFM_E_SHAPE, found before a device is looked for, nothing launched, outputs untouched): V < 2, E < 1,
+ *      E >= 2^30, an index out of range, i == j, root out of range, cos_max NaN or outside (0, 1], mu NaN or outside [0, 1],
+ *      rounds < 0, polish not 0 or 1, cg_tol not in (0, 1), cg_max < 1, a null required array.  A non-zero R_v that fails
+ *      verify_rotation: SFM_E_BAD_ROTATION, sfm_last_error naming the lowest such view (the _dev form finds it with one
+ *      kernel, before anything else is launched).
+ * No floating-point atomic, integer counts, slice-ordered sums: the bits depend on the graph and the options only.  The host
+ * reads nothing between the launches of a call.  One graph per call.  With cos_max = 1 and rounds > 0 sigma2 is zero and the
+ * weights are 0 or NaN: no edge takes part in the later rounds and the positions of round 0 stay.  The _dev form takes d_R,
+ * d_t, d_edge_mask and every output on the device and a stream (NULL = the library stream); `edges` stays a HOST array.  It
+ * returns when the work is done. */
+#define SFM_TRANSAVG_NO_MODEL     1   /* status: root has no rotation or no used edge, or round 0 gave no finite positions */
+#define SFM_TRANSAVG_KEPT_ROUNDS  2   /* status: the polish did not stand: the model is that of the rounds */
+#define SFM_TRANSAVG_CG_LIMIT     4   /* status: a solve ended its CG at cg_max */
+#define SFM_TRANSAVG_NO_ROTATION  1   /* view_status: R_v is nine zeros */
+#define SFM_TRANSAVG_UNREACHED    2   /* view_status: no path from root over used edges */
+#define SFM_TRANSAVG_HELD         4   /* view_status: not joined to root through the final inlier edges */
+int sfm_translation_average(int V, int64_t E, const int* edges /*[E][2]*/, const double* R /*[V][9]*/, const double* t /*[E][3]*/,
+                            const unsigned char* edge_mask /*[E] or NULL*/, int root, double cos_max, double mu, int rounds,
+                            int polish, double cg_tol, int cg_max, double* C_out /*[V][3]*/, unsigned char* edge_inlier /*[E] or NULL*/,
+                            double* edge_cos /*[E] or NULL*/, double* edge_len /*[E] or NULL*/, int* view_status /*[V] or NULL*/,
+                            int* n_inliers, int* status, int64_t* summary /*[6]*/, double* log /*[rounds + 2][4]*/);
+int sfm_translation_average_dev(int V, int64_t E, const int* edges /*host [E][2]*/, const double* d_R, const double* d_t,
+                                const unsigned char* d_edge_mask, int root, double cos_max, double mu, int rounds, int polish,
+                                double cg_tol, int cg_max, double* d_C_out, unsigned char* d_edge_inlier, double* d_edge_cos,
+                                double* d_edge_len, int* d_view_status, int* d_n_inliers, int* d_status, int64_t* d_summary,
+                                double* d_log, void* hip_stream);
+/* Step 2 on the host, by the function the kernels run: 1 for an inlier; *dv_out and *n2_out (may be NULL) its terms. */
+int sfm_translation_edge_test(const double d[3], const double ci[3], const double cj[3], double cos_max, double* dv_out,
+                              double* n2_out);
 /* The resident scene moved by X' = s A X + t, on the device: every point by the formula, every camera block [C, q] to
  * C' = s A C + t and q' = q(A R(q)), the library's canonical quaternion of the product (qw >= 0, not renormalised).
  * Refused before any launch: s not finite or not positive (SFM_E_SHAPE), A failing verify_rotation

@@ -146,6 +146,21 @@ __host__ __device__ inline bool rotation_edge_inlier(const double* Ri, const dou
   return (bool)((int)(__builtin_isfinite(lhs) != 0) & (int)(lhs >= thr));
 }
 
+// The test of one EDGE (i, j) of a view graph with the world direction d from c_i to c_j against the positions c_i, c_j of
+// its ends: v = c_j - c_i, dv = fma(d0, v0, fma(d1, v1, d2 * v2)), n2 = fma(v0, v0, fma(v1, v1, v2 * v2)).  An inlier iff dv
+// and n2 are finite, dv > 0 and dv * dv >= cc * n2, cc = cos_max * cos_max formed once by the caller.  No division, no
+// square root, no acos.  Every stage of the translation averaging (rounds, polish, outputs) and
+// sfm_translation_edge_test call this one function; no branch.
+__host__ __device__ inline bool translation_edge_inlier(const double* d, const double* ci, const double* cj, double cc, double* dv_out,
+                                                        double* n2_out) {
+  const double v0 = cj[0] - ci[0], v1 = cj[1] - ci[1], v2 = cj[2] - ci[2];
+  const double dv = __builtin_fma(d[0], v0, __builtin_fma(d[1], v1, d[2] * v2));
+  const double n2 = __builtin_fma(v0, v0, __builtin_fma(v1, v1, v2 * v2));
+  *dv_out = dv;
+  *n2_out = n2;
+  return (bool)((int)(__builtin_isfinite(dv) != 0) & (int)(__builtin_isfinite(n2) != 0) & (int)(dv > 0.0) & (int)(dv * dv >= cc * n2));
+}
+
 // The terms of the test of one MATCH against a relative pose (R, t), X_right = R X_left + t: the rays (a0, a1, 1) of the
 // left key and (b0, b1, 1) of the right key in normalised coordinates, a' = R a, p = a'.a', q = b.b, r = a'.b,
 // d = p q - r r, and the numerators m1, m2 of the depths along a' and b of the midpoint of the two rays, both over d.

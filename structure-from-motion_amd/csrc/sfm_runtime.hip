@@ -299,7 +299,7 @@ using namespace sfm;
 
 extern "C" {
 
-int sfm_version(void) { return 107; }
+int sfm_version(void) { return 108; }
 
 const char* sfm_last_error(void) { return g_err; }
 

@@ -177,3 +177,16 @@ def compose_relative(R_i, rel):
     """``R_j = rel R_i``: the rotation of the right view of a pair from the left one's and the pair's relative rotation (the
     ``R`` of ``native.twoview_pose``, X_right = R X_left + t); both take world coordinates to the view's frame."""
     return np.asarray(rel, dtype=np.float64).reshape(3, 3) @ np.asarray(R_i, dtype=np.float64).reshape(3, 3)
+
+
+def world_directions(R, edges, t):
+    """``d_e = -R_j^T t_e`` normalised, (E, 3): the world direction from the centre of view ``i_e`` to that of view ``j_e`` of
+    every edge ``(i_e, j_e)`` whose pair has the pose ``X_j = Rel X_i + t_e`` -- with ``R_j = Rel R_i`` the baseline
+    ``c_j - c_i = -R_j^T t_e`` (include/sfm_hip.h, "translation averaging", step 1).  ``R (V, 3, 3)`` are the absolute
+    rotations, world to view.  A zero ``t`` gives NaN."""
+    R = np.asarray(R, dtype=np.float64).reshape(-1, 3, 3)
+    edges = np.asarray(edges).reshape(-1, 2)
+    t = np.asarray(t, dtype=np.float64).reshape(edges.shape[0], 3)
+    u = -np.einsum("eba,eb->ea", R[edges[:, 1]], t)
+    with np.errstate(all="ignore"):
+        return u / np.sqrt(np.sum(u * u, axis=1))[:, None]

@@ -75,6 +75,10 @@ ROTAVG_UNREACHED, ROTAVG_HELD = 1, 2
 ROTAVG_MAX_HYP, ROTAVG_DEFAULT_HYP = 65536, 128
 ROTAVG_SUMMARY = ("views_with_rotation", "views_unreached", "views_held", "edges_inlier", "edges_outlier", "rounds_stood")
 ROTAVG_OUTPUTS = ("edge_inlier", "edge_cos", "view_status", "n_inliers", "best_hyp", "status", "summary")
+TRANSAVG_NO_MODEL, TRANSAVG_KEPT_ROUNDS, TRANSAVG_CG_LIMIT = 1, 2, 4
+TRANSAVG_NO_ROTATION, TRANSAVG_UNREACHED, TRANSAVG_HELD = 1, 2, 4
+TRANSAVG_SUMMARY = ("views_with_position", "views_no_rotation", "views_unreached", "views_held", "edges_inlier", "edges_used_outlier")
+TRANSAVG_OUTPUTS = ("edge_inlier", "edge_cos", "edge_len", "view_status", "n_inliers", "status", "summary", "log")
 POSE_FROM_F, POSE_FROM_H = 0, 1
 POSE_EMPTY, POSE_NO_MODEL, POSE_NO_POSE, POSE_TIED, POSE_NO_PARALLAX = 1, 2, 4, 8, 16
 POSE_CANDIDATES = 4
@@ -284,6 +288,10 @@ SIGNATURES = {
     "sfm_rotation_tree": [ci, i64, _ip, ci, ci, ci, _ip, _ip],
     "sfm_rotation_edge_test": [_dp, _dp, _dp, cd, _dp],
     "sfm_rotation_plan": [ci, ci, i64, _ip, _ip],
+    "sfm_translation_average": [ci, i64, _ip, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), ci, cd, cd, ci, ci, cd, ci, _dp,
+                                ctypes.POINTER(ctypes.c_uint8), _dp, _dp, _ip, _ip, _ip, _lp, _dp],
+    "sfm_translation_average_dev": [ci, i64, _ip, vp, vp, vp, ci, cd, cd, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "sfm_translation_edge_test": [_dp, _dp, _dp, cd, _dp, _dp],
     "sfm_ba_transform": [vp, cd, _dp, _dp],
     "sfm_ba_align": [vp, ci, _ip, _dp, cd, ci, ci, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip],
     "sfm_twoview_pose": [ci, _ip, i64, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _dp, _dp, cd, ci, _dp, _dp, _dp, _ip, _ip, _ip,
@@ -1145,6 +1153,120 @@ def rotation_average_dev(n_views, edges, d_rel, root=0, cos_max=None, max_hyp=0,
                                           int(iters), int(steps), float(cg_tol), int(cg_max), _vp(d_R_out), _vp(d_edge_inlier),
                                           _vp(d_edge_cos), _vp(d_view_status), _vp(d_n_inliers), _vp(d_best_hyp), _vp(d_status),
                                           _vp(d_summary), _vp(stream)))
+
+
+# ---- translation averaging over a view graph (sfm_translation_*; no reference counterpart) ------------------------------
+def check_translation_graph(n_views, edges, R, t, edge_mask=None, root=0, cos_max=1.0, mu=0.01, rounds=8, polish=1, cg_tol=1e-13,
+                            cg_max=500):
+    """The arguments of a ``translation_average`` call, without a device: ``(n_views, edges int32 (E, 2), R (V, 9), t (E, 3),
+    edge_mask uint8 (E,) or None, root, cos_max, mu, rounds, polish, cg_tol, cg_max)`` converted or ValueError -- everything
+    sfm_translation_average refuses, in its order; a non-zero ``R_v`` that is no rotation raises the ValueError of the
+    library's verify_rotation and names the view."""
+    def integer(name, value):
+        if isinstance(value, bool) or int(value) != value:
+            raise ValueError("%s must be an integer, got %r" % (name, value))
+        return int(value)
+    n_views, root = integer("n_views", n_views), integer("root", root)
+    rounds, polish, cg_max = integer("rounds", rounds), integer("polish", int(polish) if isinstance(polish, bool) else polish), integer("cg_max", cg_max)
+    cos_max, mu, cg_tol = float(cos_max), float(mu), float(cg_tol)
+    edges_in = np.asarray(edges)
+    if edges_in.ndim != 2 or edges_in.shape[1] != 2 or (edges_in.size and not np.all(edges_in == np.floor(edges_in))):
+        raise ValueError("edges must be integers of shape (E, 2), got %r" % (edges_in.shape,))
+    n_edges = edges_in.shape[0]
+    R, t = f64(R), f64(t)
+    if R.size != 9 * max(n_views, 0) or R.ndim not in (2, 3):
+        raise ValueError("R must be (V, 9) or (V, 3, 3) with V = %d, got %r" % (n_views, R.shape))
+    if t.size != 3 * n_edges or t.ndim not in (2, 3):
+        raise ValueError("t must be (E, 3) or (E, 3, 1) with E = %d, got %r" % (n_edges, t.shape))
+    R, t = R.reshape(-1, 9), t.reshape(n_edges, 3)
+    if edge_mask is not None:
+        edge_mask = np.ascontiguousarray(np.asarray(edge_mask).reshape(-1) != 0, dtype=np.uint8)
+        if edge_mask.size != n_edges:
+            raise ValueError("edge_mask must hold E = %d entries, got %d" % (n_edges, edge_mask.size))
+    if n_views < 2 or n_edges < 1 or n_edges >= 2 ** 30:
+        raise ValueError("bad sizes V=%d E=%d (V >= 2, 1 <= E < 2^30)" % (n_views, n_edges))
+    if not 0 <= root < n_views:
+        raise ValueError("root = %d must be in 0 .. %d" % (root, n_views - 1))
+    if not (0.0 < cos_max <= 1.0):
+        raise ValueError("cos_max = %r must be in (0, 1]" % cos_max)
+    if not (0.0 <= mu <= 1.0):
+        raise ValueError("mu = %r must be in (0, 1] (0 = 0.01)" % mu)
+    if rounds < 0:
+        raise ValueError("rounds = %d must be >= 0" % rounds)
+    if polish not in (0, 1):
+        raise ValueError("polish = %d must be 0 or 1" % polish)
+    if not (0.0 < cg_tol < 1.0):
+        raise ValueError("cg_tol = %r must be in (0, 1)" % cg_tol)
+    if cg_max < 1:
+        raise ValueError("cg_max = %d must be >= 1" % cg_max)
+    bad = (edges_in < 0) | (edges_in >= n_views)
+    bad = bad[:, 0] | bad[:, 1] | (edges_in[:, 0] == edges_in[:, 1])
+    if bad.any():
+        e = int(np.argmax(bad))
+        raise ValueError("edge %d = (%d, %d) must join two different views in 0 .. %d" % (e, edges_in[e, 0], edges_in[e, 1], n_views - 1))
+    edges = np.ascontiguousarray(edges_in, dtype=np.int32)
+    bad = np.any(R != 0.0, axis=1) & ~_verify_rotations(R)
+    if bad.any():
+        raise ValueError("convert_quaternion_to_rotation : Invalid output rotation matrix (R of view %d is not a rotation)"
+                         % int(np.argmax(bad)))
+    return n_views, edges, R, t, edge_mask, root, cos_max, mu, rounds, polish, cg_tol, cg_max
+
+
+def translation_edge_test(d, c_i, c_j, cos_max):
+    """``(inlier, dv, n2)`` of one edge with the world direction ``d`` against the positions of its ends
+    (sfm_translation_edge_test; host only): ``dv = d . (c_j - c_i)``, ``n2 = |c_j - c_i|^2`` in the library's operation order,
+    an inlier iff both are finite, ``dv > 0`` and ``dv * dv >= cos_max^2 * n2``."""
+    d, c_i, c_j = f64(d).reshape(3), f64(c_i).reshape(3), f64(c_j).reshape(3)
+    dv, n2 = np.zeros(1), np.zeros(1)
+    inlier = load().sfm_translation_edge_test(dptr(d), dptr(c_i), dptr(c_j), float(cos_max), dptr(dv), dptr(n2))
+    return bool(inlier), float(dv[0]), float(n2[0])
+
+
+def translation_average(n_views, edges, R, t, edge_mask=None, root=0, cos_max=None, mu=0.01, rounds=8, polish=1, cg_tol=1e-13,
+                        cg_max=500, max_angle_deg=5.0, outputs=TRANSAVG_OUTPUTS):
+    """Robust positions of the views of a graph whose rotations are known (sfm_translation_average): edge ``e = (i, j)`` with
+    ``t[e]`` the translation of the pair's pose ``X_j = Rel X_i + t``, ``R (V, 3, 3)`` the absolute rotations (zeros: none),
+    ``edge_mask`` optional (0 excludes an edge).  A reweighted linear estimator: ``rounds`` Cauchy rounds after the first
+    solve, an optional polish over the inliers; an edge is an inlier while the angle between its direction and ``c_j - c_i``
+    has a cosine of at least ``cos_max`` (default: that of ``max_angle_deg``).  Returns ``C (V, 3)`` -- zeros for a view
+    without a position -- and ``edge_inlier (E,) uint8, edge_cos (E,), edge_len (E,), view_status (V,) of TRANSAVG_NO_ROTATION /
+    UNREACHED / HELD bits, n_inliers, status of TRANSAVG_* bits, summary (6,) int64`` in the order of ``TRANSAVG_SUMMARY``,
+    ``log (rounds + 2, 4)``; an output not named in ``outputs`` is not computed and comes back as None."""
+    if cos_max is None:
+        cos_max = float(np.cos(np.deg2rad(float(max_angle_deg))))
+    V, edges, R, t, edge_mask, root, cos_max, mu, rounds, polish, cg_tol, cg_max = check_translation_graph(
+        n_views, edges, R, t, edge_mask, root, cos_max, mu, rounds, polish, cg_tol, cg_max)
+    unknown = set(outputs) - set(TRANSAVG_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (TRANSAVG_OUTPUTS, sorted(unknown)))
+    E = edges.shape[0]
+    C = np.zeros((V, 3))
+    o = {"edge_inlier": np.zeros(E, dtype=np.uint8), "edge_cos": np.zeros(E), "edge_len": np.zeros(E),
+         "view_status": np.zeros(V, dtype=np.int32), "n_inliers": np.zeros(1, dtype=np.int32), "status": np.zeros(1, dtype=np.int32),
+         "summary": np.zeros(6, dtype=np.int64), "log": np.zeros((rounds + 2, 4))}
+    w = {k: (v if k in outputs else None) for k, v in o.items()}
+    check(load().sfm_translation_average(V, E, iptr(edges), dptr(R), dptr(t), _u8ptr(edge_mask), root, cos_max, mu, rounds, polish, cg_tol,
+                                         cg_max, dptr(C), _u8ptr(w["edge_inlier"]), dptr(w["edge_cos"]), dptr(w["edge_len"]),
+                                         iptr(w["view_status"]), iptr(w["n_inliers"]), iptr(w["status"]), _lptr(w["summary"]), dptr(w["log"])))
+    out = []
+    for name in TRANSAVG_OUTPUTS:
+        v = w[name]
+        out.append(None if v is None else (int(v[0]) if name in ("n_inliers", "status") else v))
+    return (C,) + tuple(out)
+
+
+def translation_average_dev(n_views, edges, d_R, d_t, d_edge_mask=0, root=0, cos_max=None, mu=0.01, rounds=8, polish=1, cg_tol=1e-13,
+                            cg_max=500, max_angle_deg=5.0, d_C_out=0, d_edge_inlier=0, d_edge_cos=0, d_edge_len=0, d_view_status=0,
+                            d_n_inliers=0, d_status=0, d_summary=0, d_log=0, stream=0):
+    """``translation_average`` with ``d_R`` (V, 9), ``d_t`` (E, 3), ``d_edge_mask`` (E,) bytes and the outputs as device pointers
+    and a caller's stream (sfm_translation_average_dev); ``edges`` stays a host array, optional arrays are 0."""
+    if cos_max is None:
+        cos_max = float(np.cos(np.deg2rad(float(max_angle_deg))))
+    edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+    check(load().sfm_translation_average_dev(int(n_views), edges.shape[0], iptr(edges), _vp(d_R), _vp(d_t), _vp(d_edge_mask), int(root),
+                                             float(cos_max), float(mu), int(rounds), int(polish), float(cg_tol), int(cg_max), _vp(d_C_out),
+                                             _vp(d_edge_inlier), _vp(d_edge_cos), _vp(d_edge_len), _vp(d_view_status), _vp(d_n_inliers),
+                                             _vp(d_status), _vp(d_summary), _vp(d_log), _vp(stream)))
 
 
 # ---- robust essential matrix (sfm_essential_*; no reference counterpart) ------------------------------------------------

@@ -470,6 +470,57 @@ class HipCamposeMixin:
         self.rotation_last = verdict
         return rots, verdict
 
+    def average_translations(self, pair_results, rots_or_R, n_views, root=0, max_angle_deg=5.0, rounds=8, edge_mask=None):
+        """Positions of ``n_views`` views from the unit translations of their posed pairs and known rotations (one
+        ``native.translation_average``; no reference counterpart).  ``pair_results`` holds the entries ``average_rotations``
+        takes, with the translation: a quadruple ``(ref, que, R, t)`` or a dict of ``initialise_pairs`` with ``"ref"`` and
+        ``"que"`` added; a pair without a pose (or without ``t``) is skipped exactly as there, so that the edges of the two calls
+        are the same.  ``rots_or_R`` is the list ``average_rotations`` returned (``rot = R_v^T``, None without a rotation) or an
+        array (V, 3, 3) of the library's ``R_v``.  ``edge_mask`` has one entry per EDGE (``edge_inlier`` of the rotation
+        verdict): a zero leaves the edge out.  An edge counts as consistent while the angle between its direction and the
+        baseline of the solution is at most ``max_angle_deg``; ``rounds`` reweighted solves follow the first, then a polish.
+
+        Returns ``centres, verdict``: ``centres`` a list of ``n_views`` (3, 1) columns in the reference's convention (the
+        camera centre in world coordinates; zeros for ``root``, None for a view without a position) and ``verdict`` a dict
+        with ``pairs``, ``edge_inlier``, ``edge_cos``, ``edge_len``, ``view_status``, ``n_inliers``, ``status``, ``summary``
+        and ``log``.  ``translation_last`` keeps it."""
+        if not 0.0 <= float(max_angle_deg) < 90.0:
+            raise ValueError("max_angle_deg must be in [0, 90), got {!r}".format(max_angle_deg))
+        n_views = int(n_views)
+        if isinstance(rots_or_R, np.ndarray):
+            R = np.asarray(rots_or_R, dtype=np.float64).reshape(n_views, 3, 3)
+        else:
+            if len(rots_or_R) != n_views:
+                raise ValueError("average_translations: {} rotations for {} views".format(len(rots_or_R), n_views))
+            R = np.zeros((n_views, 3, 3))
+            for v, rot in enumerate(rots_or_R):
+                if rot is not None:
+                    R[v] = np.asarray(rot, dtype=np.float64).reshape(3, 3).T
+        edges, ts, used = [], [], []
+        for k, entry in enumerate(pair_results):
+            if isinstance(entry, dict):
+                if entry.get("best_cand", 0) < 0 or entry.get("status", 0) & native.POSE_NO_POSE:
+                    continue
+                ref, que, Rel, t = entry["ref"], entry["que"], entry["R"], entry["t"]
+            else:
+                ref, que, Rel, t = entry
+            if Rel is None or not np.any(Rel) or t is None:
+                continue
+            edges.append((int(ref), int(que)))
+            ts.append(np.asarray(t, dtype=np.float64).reshape(3))
+            used.append(k)
+        if not edges:
+            raise ValueError("average_translations: no pair with a pose")
+        C, edge_inlier, edge_cos, edge_len, view_status, n_inliers, status, summary, log = native.translation_average(
+            n_views, np.array(edges, dtype=np.int32), R, np.array(ts), edge_mask=edge_mask, root=root, max_angle_deg=float(max_angle_deg),
+            rounds=rounds, polish=1)
+        has = (view_status & native.TRANSAVG_UNREACHED) == 0 if not status & native.TRANSAVG_NO_MODEL else np.zeros(n_views, dtype=bool)
+        centres = [C[v].reshape(3, 1).copy() if has[v] else None for v in range(n_views)]
+        verdict = dict(pairs=used, edge_inlier=edge_inlier.astype(bool), edge_cos=edge_cos, edge_len=edge_len, view_status=view_status,
+                       n_inliers=n_inliers, status=status, summary=summary, log=log)
+        self.translation_last = verdict
+        return centres, verdict
+
     def estimate_relative_pose_minimal(self, matched_pairs, K_left, K_right, max_px=2.0, max_hyp=128, refine_iters=6, min_angle_deg=2.0):
         """The relative pose of a calibrated pair straight from its matches (no reference counterpart): ONE
         ``native.essential_ransac`` (five-point hypotheses at ``max_px`` pixels of Sampson distance), then ONE
@@ -2142,6 +2193,25 @@ def orient_views(tracker, pairs, K, K_right=None, root=0, max_sampson_px=2.0, ma
         triples.append((entry["ref"], entry["que"], entry["R"]))
     rots, verdict = HipCamposeMixin().average_rotations(triples, n_views, root, max_angle_deg, tree_hyp, rounds)
     return rots, verdict, poses
+
+
+def locate_views(tracker, pairs, K, K_right=None, root=0, max_sampson_px=2.0, max_hyp=128, iteration=2, min_angle_deg=2.0,
+                 min_parallax=8, max_angle_deg=5.0, tree_hyp=128, rounds=2, max_direction_deg=5.0, translation_rounds=8):
+    """Absolute rotations AND positions of the views of a ``HipDeviceKeyTracker``: ``orient_views`` over the listed ``pairs``,
+    then ONE ``HipCamposeMixin.average_translations`` over the same poses with the rotations found and the rotation verdict
+    as the edge mask (a pair whose rotation disagrees with the graph lends no direction).  Returns ``rots, centres, verdicts,
+    poses``: ``rots`` and ``poses`` as ``orient_views`` returns them, ``centres`` as ``average_translations`` does (all None
+    where the rotations have no model), ``verdicts`` the dict ``{"rotation": ..., "translation": ...}`` (the second None
+    without a rotation model).  A function of the module, like ``orient_views``; ``process()`` does not call it."""
+    rots, rot_verdict, poses = orient_views(tracker, pairs, K, K_right, root, max_sampson_px, max_hyp, iteration, min_angle_deg,
+                                            min_parallax, max_angle_deg, tree_hyp, rounds)
+    n_views = len(tracker.track_list)
+    if rot_verdict["status"] & native.ROTAVG_NO_MODEL:
+        return rots, [None] * n_views, {"rotation": rot_verdict, "translation": None}, poses
+    quads = [(p["ref"], p["que"], p["R"], p["t"]) for p in poses]
+    centres, tr_verdict = HipCamposeMixin().average_translations(quads, rots, n_views, root, max_direction_deg, translation_rounds,
+                                                                 edge_mask=rot_verdict["edge_inlier"])
+    return rots, centres, {"rotation": rot_verdict, "translation": tr_verdict}, poses
 
 
 def _guided_model(model):
