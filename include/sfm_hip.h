@@ -102,6 +102,12 @@ extern "C" {
                                    * data-flow solve's launch (no ba_schur_reduce launch: one GPU, 37 to 237 cameras, not deterministic), else 0 */
 #define SFM_INFO_PCG_HELD_POINTS 9 /* points whose D_p was not positive definite or not finite in the last outer iteration of
                                    * sfm_ba_iterate_pcg: they were held for that iteration (arises only at lambda = 0) */
+#define SFM_INFO_SOLVE_PATH    10 /* how the next reduced camera solve runs: SFM_SOLVE_SMALL (one workgroup, up to 8 cameras), SFM_SOLVE_FLOW
+                                   * (the persistent data-flow launch: 9 to 237 cameras on a device of at least 2 compute units) or
+                                   * SFM_SOLVE_STEPS (one launch per block column) */
+#define SFM_SOLVE_SMALL 0
+#define SFM_SOLVE_FLOW  1
+#define SFM_SOLVE_STEPS 2
 
 /* ---- kernel ids for sfm_ba_kernel_time ------------------------------------------------------- */
 #define SFM_K_PREP       0
@@ -122,6 +128,17 @@ int sfm_shutdown(void);
  * A resident BA problem keeps the stream it was given (sfm_ba_set_stream), whatever this is set to later. */
 int sfm_set_stream(void* hip_stream);
 int sfm_synchronize(void);
+/* A hook for tests, in the sense of sfm_rotation_plan's cap_bytes: every launch shape and plan that depends on the device's
+ * compute-unit count is made for min(n, the device's count) from now on, so that the plans of a partitioned MI355X (CPX: 32
+ * compute units per logical device, QPX 64, DPX 128) can be run on a whole one.  n = 0 removes the limit; n < 0 is
+ * SFM_E_SHAPE.  The effective count never exceeds the device's own: more would oversubscribe launches whose workgroups
+ * wait for each other.  Works before sfm_init (the host-only plan functions then see min(n, 256)) and survives
+ * sfm_shutdown.  A resident BA problem sized its workspaces from the plans of its creation: while any sfm_ba_problem
+ * exists the call returns SFM_E_SHAPE and changes nothing.  The workgroups still run on every compute unit of the device:
+ * the limit shapes the plans, it does not mask hardware. */
+int sfm_set_cu_limit(int n);
+/* *device = the device's compute units (256 before sfm_init), *effective = what the plans see.  Either may be NULL. */
+int sfm_cu_count(int* device, int* effective);
 /* Diagnostic: 1 when the process runs with SFM_POOL_REDZONE=1 -- every device buffer of the library then sits between
  * two 4 KB zones of 0xA5 that are checked (after a device-wide synchronise) whenever the buffer goes back to the pool;
  * a kernel that wrote outside its buffer aborts the process with a message.  For test runs only. */
@@ -193,7 +210,10 @@ int sfm_pnp_nonlinear_batch_dev(int n_views, const int* d_offsets /*[n_views+1]*
                                 int max_view_points /* size of the largest view (the offsets are on the device); 0 = unknown.
                                                        Views of up to 1024 points and larger ones run on different kernels, each
                                                        launched over the whole batch; a truthful value <= 1024 saves the second
-                                                       launch.  A view's result depends on its own size only, never on the batch. */,
+                                                       launch.  A view's result depends on its own size only, never on the batch.
+                                                       A view LARGER than a non-zero value is not refined: d_R_out, d_C_out are its
+                                                       d_R0, d_C0 and its d_status is SFM_E_SHAPE; the call still returns SFM_OK, and
+                                                       every view within the value gets what a truthful call gives it. */,
                                 void* hip_stream);
 /* X_out[4][n] = (px, py, pz, 1)[index[i]]: the 2D-3D association of ba_processor.py:184-188 (np.take of tri_pts) for points
  * that already live on the device (sfm_ba_points_ptr), so that the per-view PnP uploads keys and indices only. */
@@ -370,6 +390,10 @@ int sfm_ba_debug_stamps(sfm_ba_problem* p, unsigned long long* out, int n);
  * block of a row + its two hand-over blocks, 2 = the hand-over block (i, i-1), 3 = a block of the rhs row, 4 = a block of an
  * identity row.  Returns the number of tasks (0 outside 2 .. 52 block columns); fills at most `capacity` of them. */
 int sfm_ba_flow_tasks(int nbk, int* out, int capacity);
+/* Workgroups of that launch on a device of n_cus compute units for a table of n_tasks tasks (host only): the chain, and
+ * min(n_tasks, n_cus - 32) task workgroups from 41 compute units on, min(n_tasks, n_cus - 1) below, never fewer than one.
+ * 0 for n_cus < 2 or n_tasks < 1: there is no such launch, the solve runs one launch per block column. */
+int sfm_ba_flow_grid(int n_cus, int n_tasks);
 /* The same for n_cams cameras with the reduce deferred into the launch (sfm_ba_iterate on one GPU, dense product): type 5 = the
  * accumulators of camera `row`, part `column` of 4; type 6 = block (row, column) of S, rows 8 q .. 8 q + 7 with q = key & 3. */
 int sfm_ba_flow_tasks_deferred(int n_cams, int* out, int capacity);

@@ -397,6 +397,7 @@ int ba_schur_prepare_dense(sfm_ba_problem* p, hipStream_t s);
 int ba_enqueue_schur(sfm_ba_problem* p, hipStream_t s, bool allow_defer);
 SchurPlan ba_schur_dense_plan(const sfm_ba_problem* p);
 bool ba_solve_can_defer_reduce(const sfm_ba_problem* p);      // sfm_ba_solve.hip
+int ba_solve_path(const sfm_ba_problem* p);                   // sfm_ba_solve.hip: SFM_SOLVE_* of the next reduced solve
 void ba_tick(sfm_ba_problem* p, int kernel_class, bool begin, hipStream_t s);   // hipEvent bracket of a kernel class (SFM_OPT_TIMING)
 bool ba_schur_uses_mfma(const sfm_ba_problem* p);
 int ba_schur_choice(const sfm_ba_problem* p);

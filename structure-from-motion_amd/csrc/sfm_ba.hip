@@ -464,7 +464,7 @@ static int enqueue_backsub(sfm_ba_problem* p, double lambda, int quirks) {
   const BaDev& d = p->dev;
   const int g = pick_group(p);
   const int gpb = 256 / g;
-  int grid = std::min((d.N + gpb - 1) / gpb, 4 * ctx().num_cus);
+  int grid = std::min((d.N + gpb - 1) / gpb, 4 * plan_cus());
   if (grid < 1) grid = 1;
   const size_t lds = sizeof(double) * (size_t)d.V * (19 + 7);
   ba_tick(p, SFM_K_BACKSUB, true, s);
@@ -501,7 +501,7 @@ int ba_enqueue_linearize_reduce(sfm_ba_problem* p, double lambda, int quirks, bo
   p->red_clean = false;
   const int g = pick_group(p);
   const int gpb = (p->deterministic ? 64 : 256) / g;
-  int grid = std::min((d.N + gpb - 1) / gpb, kLinGridPerCu * ctx().num_cus);
+  int grid = std::min((d.N + gpb - 1) / gpb, kLinGridPerCu * plan_cus());
   if (grid < 1) grid = 1;
   const size_t lds = sizeof(double) * (size_t)d.V * (19 + 35);
   ba_tick(p, SFM_K_LINEARIZE, true, s);

@@ -443,7 +443,7 @@ static int ba_scene_alloc(BaScene& sc, int V, int N, long long M, hipStream_t st
   BaDev& d = sc.dev;
   d.V = V; d.N = N; d.M = M; d.P = 7 * V;
   d.nbk = (d.P + kNB - 1) / kNB;
-  const size_t lin_wgs = (size_t)kLinGridPerCu * ctx().num_cus;
+  const size_t lin_wgs = (size_t)kLinGridPerCu * plan_cus();
   SFM_TRY(scene_alloc(sc, d.pt_ptr, (size_t)N + 1));
   SFM_TRY(scene_alloc(sc, d.cam_idx, (size_t)M));
   SFM_TRY(scene_alloc(sc, d.obs_pt, (size_t)M));
@@ -587,6 +587,7 @@ int sfm_ba_create(int V, int N, int64_t M, const int* pt_ptr, const int* cam_idx
   if (M > 0 && uv_norm == nullptr) { set_error("sfm_ba_create: uv_norm is null"); return SFM_E_SHAPE; }
   if (N > 0 && (pt_ptr[0] != 0 || pt_ptr[N] != M)) { set_error("sfm_ba_create: pt_ptr must span [0, M]"); return SFM_E_SHAPE; }
   sfm_ba_problem* p = new sfm_ba_problem();
+  ++ba_live_problems();      // (sfm_set_cu_limit is refused while one exists)
   p->stream = ctx().stream;
   const int zero_ptr = 0;
   const int st = ba_grow(p, V, N, M, 0, "sfm_ba_create", [&](const BaDev& d) -> int {
@@ -611,6 +612,7 @@ int sfm_ba_destroy(sfm_ba_problem* p) {
     for (auto& e : t.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   p->magic = 0;
   delete p;
+  --ba_live_problems();
   return SFM_OK;
 }
 
@@ -686,6 +688,7 @@ int sfm_ba_info(sfm_ba_problem* p, int what, int64_t* value) {
     case SFM_INFO_GRAPH_REPLAYS: *value = p->graph_replays; return SFM_OK;
     case SFM_INFO_REDUCE_IN_SOLVE: *value = p->last_reduce_deferred ? 1 : 0; return SFM_OK;
     case SFM_INFO_PCG_HELD_POINTS: *value = p->pcg_held_points; return SFM_OK;
+    case SFM_INFO_SOLVE_PATH: *value = ba_solve_path(p); return SFM_OK;
     default: set_error("sfm_ba_info: unknown item %d", what); return SFM_E_SHAPE;
   }
 }
@@ -996,6 +999,7 @@ int sfm_ba_create_from_tracks(sfm_track_store* store, sfm_ba_problem** out) {
   SFM_TRY(track_observations(store, "sfm_ba_create_from_tracks", &t));      // waits for the store's pending work
   if (t.n_views < 1) { set_error("sfm_ba_create_from_tracks: the list was built for %d views", t.n_views); return SFM_E_SHAPE; }
   sfm_ba_problem* p = new sfm_ba_problem();
+  ++ba_live_problems();      // (sfm_set_cu_limit is refused while one exists)
   p->stream = ctx().stream;
   // (the check synchronises: the store may build its next list)
   const int st = ba_grow(p, t.n_views, t.n_pts, t.n_obs, 0, "sfm_ba_create_from_tracks",

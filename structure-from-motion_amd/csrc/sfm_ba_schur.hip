@@ -495,14 +495,14 @@ static SchurPlan make_plan(const BaDev& d) {
   const double cost[4] = {16.0, 2.0 * pl.ra_last, 9.0, (double)diag_cost(pl.ra_last)};
   double total = 0;
   for (int c = 0; c < 4; ++c) total += cost[c] * plan_tiles_in_class(pl, c);
-  double budget = total * slabs / std::max(1, ctx().num_cus);      // cost x slabs per workgroup
+  double budget = total * slabs / std::max(1, plan_cus());      // cost x slabs per workgroup
   for (int attempt = 0; attempt < 200; ++attempt) {
     for (int c = 0; c < 4; ++c) {
       int slabs_per = std::max(1, std::min(slabs, (int)(budget / cost[c])));
       pl.chunks[c] = (slabs + slabs_per - 1) / slabs_per;
       pl.rpc[c] = slabs_per * KSL;
     }
-    if (plan_wgs(pl) <= ctx().num_cus) break;
+    if (plan_wgs(pl) <= plan_cus()) break;
     budget *= 1.01;
   }
   // ONE tile (up to 18 cameras): it is split into at most kSchurMaxChunks = 128 slabs, and a workgroup gets at least three slabs of 16 rows,
@@ -533,7 +533,7 @@ static SchurPlan make_pairs_plan(const BaDev& d) {
   pl.ra_last = 8;
   pl.cam_blocks = 1;
   const int ntiles = pl.n_off + pl.nblk;
-  int chunks = std::max(1, 2 * ctx().num_cus / ntiles);
+  int chunks = std::max(1, 2 * plan_cus() / ntiles);
   chunks = std::max(1, std::min(chunks, (d.N + PAIR_WAVES - 1) / PAIR_WAVES));
   const int ppc = std::max(1, (d.N + chunks - 1) / chunks);
   chunks = std::max(1, (d.N + ppc - 1) / ppc);      // (an empty shard -- N = 0 -- still plans one chunk per tile)

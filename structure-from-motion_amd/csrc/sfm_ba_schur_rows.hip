@@ -172,7 +172,7 @@ static int ba_rows_plan(sfm_ba_problem* p) {
   const int G = (d.V + R - 1) / R;
   double total = 0;
   for (int c = 0; c < d.V; ++c) total += (double)p->h_cam_pairs[c] + 4.0 * (p->h_cam_ptr[c + 1] - p->h_cam_ptr[c]);
-  const int target = std::max(G, 2 * ctx().num_cus);
+  const int target = std::max(G, 2 * plan_cus());
   std::vector<RowsWg> table;
   std::vector<int> first((size_t)G + 1, 0);
   for (int g = 0; g < G; ++g) {

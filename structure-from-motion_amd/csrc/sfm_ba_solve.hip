@@ -779,22 +779,36 @@ static int flow_task_table(int key, int nbk, int V, const void** table, int* nta
   return SFM_OK;
 }
 
+// Workgroups of the data-flow launch on n_cus compute units: the chain and at least one, at most n_tasks task workgroups.  The ticket
+// scheme needs the chain and ONE task workgroup resident, nothing more; every workgroup owns a CU (121 KB of LDS), so there are at
+// most n_cus of them, and from 41 CUs on 32 are left to whatever else the device runs (the next problem's linearisation on another
+// stream).  Below 2 CUs there is no such launch: ba_flow_setup leaves the problem on the column steps.
+static int flow_grid(int n_cus, int n_tasks) {
+  const int room = n_cus > 40 ? n_cus - 32 : n_cus - 1;
+  return 1 + std::max(1, std::min(n_tasks, room));
+}
+
 int ba_flow_setup(BaScene& sc, hipStream_t s) {
   BaDev& d = sc.dev;
   if (d.nbk < 2 || d.nbk > kFlowMaxNbk) return SFM_OK;
+  if (plan_cus() < 2) return SFM_OK;      // d.flow stays null: the column-step launches (solve_uses_flow)
   // field switch: SFM_FLOW_SOLVE=0 keeps every problem on the column-step launches (what SFM_OPT_DEBUG bit 1024 does per handle)
   static const bool enabled = [] { const char* e = getenv("SFM_FLOW_SOLVE"); return !(e && atoi(e) == 0); }();
   if (!enabled) return SFM_OK;
-  SFM_TRY(flow_task_table(d.nbk, d.nbk, 0, &d.flow_tasks, &d.flow_ntasks));
-  SFM_TRY(flow_task_table(1000 + d.V, d.nbk, d.V, &sc.flow_tasks_red, &sc.flow_ntasks_red));
-  SFM_TRY(scene_alloc(sc, d.flow, flow_words(d.nbk)));
-  SFM_HIP(hipMemsetAsync(d.flow, 0, sizeof(unsigned) * flow_words(d.nbk), s));
-  SFM_TRY(scene_alloc(sc, sc.flow_camsum, 4 * 35 * (size_t)d.V));
+  // a device that refuses the launch its 121 KB of LDS keeps every problem on the column steps, which need none of it
   static int attr_device = -1;
+  static bool attr_ok = false;
   if (attr_device != ctx().device) {
-    SFM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_chol_flow_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFlowLdsBytes));
+    attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(ba_chol_flow_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFlowLdsBytes) == hipSuccess;
+    if (!attr_ok) (void)hipGetLastError();
     attr_device = ctx().device;
   }
+  if (!attr_ok) return SFM_OK;
+  SFM_TRY(flow_task_table(d.nbk, d.nbk, 0, &d.flow_tasks, &d.flow_ntasks));
+  SFM_TRY(flow_task_table(1000 + d.V, d.nbk, d.V, &sc.flow_tasks_red, &sc.flow_ntasks_red));
+  SFM_TRY(scene_alloc(sc, sc.flow_camsum, 4 * 35 * (size_t)d.V));
+  SFM_TRY(scene_alloc(sc, d.flow, flow_words(d.nbk)));
+  SFM_HIP(hipMemsetAsync(d.flow, 0, sizeof(unsigned) * flow_words(d.nbk), s));
   return SFM_OK;
 }
 
@@ -804,6 +818,10 @@ static bool solve_uses_flow(const BaDev& d) {
   // the identity rows ride along (SFM_OPT_DEBUG bit 512: leave them out and back-substitute block row by block row);
   // SFM_OPT_DEBUG bit 1024: column steps as separate launches where the data-flow launch would run
   return !solve_uses_small(d) && !(d.debug & 512) && d.nbk <= kInvRowsMaxNbk && d.flow != nullptr && !(d.debug & 1024);
+}
+
+int ba_solve_path(const sfm_ba_problem* p) {
+  return solve_uses_small(p->dev) ? SFM_SOLVE_SMALL : (solve_uses_flow(p->dev) ? SFM_SOLVE_FLOW : SFM_SOLVE_STEPS);
 }
 
 // The split-K reduce of the dense product can be left to the data-flow launch (FlowRed in sfm_ba_flow.h) when nothing but that launch
@@ -848,7 +866,7 @@ int ba_enqueue_reduced_solve(sfm_ba_problem* p, double lambda) {
       tasks = static_cast<const FlowTask*>(p->flow_tasks_red); ntasks = p->flow_ntasks_red;
       p->reduce_deferred = false;
     }
-    const int grid = 1 + std::min(ntasks, ctx().num_cus - 32);
+    const int grid = flow_grid(plan_cus(), ntasks);
     // SFM_OPT_DEBUG bit 2048: dp = X y and the camera update as their own launch behind the data-flow launch
     const bool fused_dp = !(d.debug & 2048);
     ba_chol_flow_kernel<<<grid, 512, kFlowLdsBytes, s>>>(d, d.flow, tasks, ntasks, lambda, fused_dp ? p->cur : -1, fr);
@@ -905,6 +923,11 @@ extern "C" int sfm_ba_flow_tasks_deferred(int n_cams, int* out, int capacity) {
   if (out != nullptr)
     for (size_t q = 0; q < t.size() && (int)q < capacity; ++q) { out[4 * q] = t[q].type; out[4 * q + 1] = t[q].i; out[4 * q + 2] = t[q].k; out[4 * q + 3] = t[q].key; }
   return (int)t.size();
+}
+
+extern "C" int sfm_ba_flow_grid(int n_cus, int n_tasks) {
+  if (n_cus < 2 || n_tasks < 1) return 0;
+  return sfm::flow_grid(n_cus, n_tasks);
 }
 
 extern "C" int sfm_ba_flow_tasks(int nbk, int* out, int capacity) {

@@ -19,11 +19,20 @@ struct Context {
   int device = -1;
   hipStream_t stream = nullptr;       // default stream of the library: `own` or the one installed by sfm_set_stream
   hipStream_t own = nullptr;          // created at sfm_init, lives until sfm_shutdown
-  int num_cus = 256;
+  int num_cus = 256;                  // the device's own count (256 before sfm_init: what the host-only plan functions see)
+  int cu_limit = 0;                   // sfm_set_cu_limit: 0 = none; survives sfm_init and sfm_shutdown
 };
 
 Context& ctx();
 int ensure_init();
+// The compute-unit count every launch shape and plan is made for: the device's own, or less under sfm_set_cu_limit.
+// No plan reads Context::num_cus itself.
+inline int plan_cus() {
+  const Context& c = ctx();
+  return c.cu_limit > 0 ? (c.cu_limit < c.num_cus ? c.cu_limit : c.num_cus) : c.num_cus;
+}
+// live sfm_ba_problem handles (sfm_ba_create / sfm_ba_destroy): their workspaces are sized from the plans of their creation
+int& ba_live_problems();
 
 // Device-memory pool: hipMalloc/hipFree cost tens of microseconds each and a host-buffer call makes ~25 of
 // them, which dominates small problems (incremental SfM sizes).  Blocks are rounded up to a power of two
@@ -202,7 +211,7 @@ inline int narrowest_group(Pred&& pred) {
   return i;
 }
 inline int widen_for_waves(int i, int n_pts, int cap) {
-  const long long want_waves = 2LL * 4 * ctx().num_cus;
+  const long long want_waves = 2LL * 4 * plan_cus();
   while (i < 5 && (long long)n_pts * kGroupWidths[i] / 64 < want_waves && kGroupWidths[i + 1] <= cap) ++i;
   return i;
 }

@@ -719,9 +719,21 @@ static int pnp_split_min() {
 // ~0.25 us to the hand-over (5 000 points: 5.65 us per iteration at 1 024, 6.61 at 512, 9.60 at 256; profiles/r4/time_pnp_slices.txt)
 static int pnp_split_slice() { return 1024; }
 
+// A view larger than the caller of the device-pointer form said its largest view is (`told`): no size class below was planned for
+// it -- not launched at all, or with too few slices -- so none refines it.  It comes back as it went in, R_out = R0 and C_out = C0,
+// with status SFM_E_SHAPE.  Its own launch, ahead of the classes, which leave such a view alone (n_hi <= told): always one writer.
+__global__ void pnp_untold_kernel(int n_views, const int* __restrict__ offsets, int told, const double* R0, const double* C0,
+                                  double* R_out, double* C_out, int* __restrict__ status) {
+  const int view = blockIdx.x * blockDim.x + threadIdx.x;
+  if (view >= n_views || offsets[view + 1] - offsets[view] <= told) return;
+  for (int k = 0; k < 9; ++k) R_out[9 * view + k] = R0[9 * view + k];
+  for (int k = 0; k < 3; ++k) C_out[3 * view + k] = C0[3 * view + k];
+  status[view] = SFM_E_SHAPE;
+}
+
 static int enqueue_pnp_nonlinear(int n_views, const int* offsets, int total, const double* uv_pix, const double* X,
                                  const double* K, const double* R0, const double* C0, double lambda, int iters, int quirks,
-                                 double* R_out, double* C_out, int* status, hipStream_t s, int narrowest, int widest) {
+                                 double* R_out, double* C_out, int* status, hipStream_t s, int narrowest, int widest, bool told = false) {
   // Three size classes, each with its own launch over all views (a workgroup whose view belongs to another class returns at
   // once), so that the kernel a view runs on -- and with it every bit of its result -- depends on the view's own size and
   // not on what else is in the batch (a shard of a batch returns what the whole batch returns):
@@ -731,14 +743,17 @@ static int enqueue_pnp_nonlinear(int n_views, const int* offsets, int total, con
   //                            sums once per iteration (pnp_nonlinear_kernel<256, 4, true>).
   // `narrowest` / `widest`: the smallest and the largest view (the host entry point has the offsets; the device-pointer
   // entry is told the largest, or reads the offsets back when it is not).  A class no view can be in is not launched.
-  constexpr int kSmall = 1024, kAll = 0x7fffffff;
+  // `told`: widest is the caller's word, not a fact.  No class touches a view above it (the split class' kmax, and with it the
+  // flag and exchange words a slice may read, is made for `widest` points), and pnp_untold_kernel reports such a view.
+  constexpr int kSmall = 1024;
   const int split_min = pnp_split_min();
+  if (told) pnp_untold_kernel<<<(n_views + 255) / 256, 256, 0, s>>>(n_views, offsets, widest, R0, C0, R_out, C_out, status);
   const bool small_class = narrowest <= kSmall;
   const bool mid_class = widest > kSmall && narrowest < split_min;
   const bool split_class = widest >= split_min;
   if (small_class)
     pnp_nonlinear_kernel<256, 4><<<n_views, 256, 0, s>>>(offsets, total, uv_pix, X, K, R0, C0, lambda, iters, quirks, R_out, C_out, status, 0, 0,
-                                                         0, kSmall);
+                                                         0, std::min(kSmall, widest));
   if (mid_class) {
     // dynamic LDS the kernel may ask for = what the device offers a workgroup minus the kernel's static arrays; the staging
     // capacities follow from it (the attribute call's result was dropped and the capacities were constants), and
@@ -759,7 +774,7 @@ static int enqueue_pnp_nonlinear(int n_views, const int* offsets, int total, con
     const int cap = mode == 1 ? cap_all : (mode == 2 ? cap_key : 0);
     const size_t lds = sizeof(double) * (size_t)cap * (mode == 1 ? 6 : 2);
     pnp_nonlinear_kernel<512, 2><<<n_views, 512, lds, s>>>(offsets, total, uv_pix, X, K, R0, C0, lambda, iters, quirks, R_out, C_out, status, mode, cap,
-                                                          kSmall + 1, split_min - 1);
+                                                          kSmall + 1, std::min(split_min - 1, widest));
   }
   if (split_class) {
     const int slice_pts = pnp_split_slice();
@@ -770,11 +785,11 @@ static int enqueue_pnp_nonlinear(int n_views, const int* offsets, int total, con
     SFM_HIP(hipMemsetAsync(ws.ctr, 0, sizeof(int) * (size_t)n_views * kmax, s));
     // the slices of a view wait for each other inside the launch: keep a launch's workgroups within what is resident at
     // once (sibling workgroups are neighbours in the grid; workgroups of views of other classes leave at once)
-    const int views_per_launch = std::max(1, 2 * ctx().num_cus / kmax);
+    const int views_per_launch = std::max(1, 2 * plan_cus() / kmax);
     for (int v0 = 0; v0 < n_views; v0 += views_per_launch) {
       const int nv = std::min(views_per_launch, n_views - v0);
       pnp_nonlinear_kernel<256, 4, true><<<nv * kmax, 256, 0, s>>>(offsets, total, uv_pix, X, K, R0, C0, lambda, iters, quirks, R_out, C_out, status,
-                                                                  0, 0, split_min, kAll, ws, v0);
+                                                                  0, 0, split_min, widest, ws, v0);
     }
   }
   SFM_HIP(hipGetLastError());
@@ -953,9 +968,11 @@ int sfm_pnp_nonlinear_batch_dev(int n_views, const int* d_offsets, int total, co
     set_error("sfm_pnp_nonlinear_batch_dev: null device pointer");
     return SFM_E_SHAPE;
   }
-  // the offsets live on the device: the caller says how large its largest view is (0: unknown -- both size classes are
-  // launched; a view larger than the caller said is still refined, by the small-view kernel re-reading its points)
+  // the offsets live on the device: the caller says how large its largest view is, and the size classes are launched for
+  // views up to that size; a view larger than the caller said is refined by none of them and comes back with R0, C0 and
+  // status SFM_E_SHAPE (pnp_untold_kernel).  0: unknown -- the offsets are read back and every view is refined.
   hipStream_t s = pick_stream(hip_stream);
+  const bool told = max_view_points > 0;
   int widest = max_view_points, narrowest = 0;
   if (widest <= 0) {      // not told: the size classes are a function of the views' sizes, so read them (blocking once)
     std::vector<int> off((size_t)n_views + 1);
@@ -965,7 +982,7 @@ int sfm_pnp_nonlinear_batch_dev(int n_views, const int* d_offsets, int total, co
     for (int v = 0; v < n_views; ++v) { widest = std::max(widest, off[v + 1] - off[v]); narrowest = std::min(narrowest, off[v + 1] - off[v]); }
   }
   SFM_TRY(enqueue_pnp_nonlinear(n_views, d_offsets, total, d_uv_pix, d_X, d_K, d_R0, d_C0, lambda, iters, quirks, d_R_out,
-                                d_C_out, d_status, s, narrowest, widest));
+                                d_C_out, d_status, s, narrowest, widest, told));
   return SFM_OK;
 }
 

@@ -47,6 +47,11 @@ int stream_sync(hipStream_t s) {
   return SFM_OK;
 }
 
+int& ba_live_problems() {
+  static int n = 0;
+  return n;
+}
+
 int ensure_init() {
   if (ctx().inited) return SFM_OK;
   return sfm_init(0);
@@ -299,7 +304,7 @@ using namespace sfm;
 
 extern "C" {
 
-int sfm_version(void) { return 108; }
+int sfm_version(void) { return 109; }
 
 const char* sfm_last_error(void) { return g_err; }
 
@@ -341,7 +346,26 @@ int sfm_shutdown(void) {
   pnp_split_release();
   pool_release_all();
   if (c.own) (void)hipStreamDestroy(c.own);
+  const int cu_limit = c.cu_limit;      // the test hook outlives the device (it works before sfm_init)
   c = Context();
+  c.cu_limit = cu_limit;
+  return SFM_OK;
+}
+
+int sfm_set_cu_limit(int n) {
+  if (n < 0) { set_error("sfm_set_cu_limit: n = %d is negative (0 removes the limit)", n); return SFM_E_SHAPE; }
+  if (ba_live_problems() > 0) {
+    set_error("sfm_set_cu_limit: %d sfm_ba_problem handle(s) exist, and their workspaces were sized for the current count; destroy them first",
+              ba_live_problems());
+    return SFM_E_SHAPE;
+  }
+  ctx().cu_limit = n;
+  return SFM_OK;
+}
+
+int sfm_cu_count(int* device, int* effective) {
+  if (device) *device = ctx().num_cus;
+  if (effective) *effective = plan_cus();
   return SFM_OK;
 }
 

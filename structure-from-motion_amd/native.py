@@ -27,6 +27,8 @@ KERNEL_NAMES = ("prep", "linearize", "schur", "solve", "backsub", "reduce")
 INFO_SCHUR_KERNEL, INFO_UPLOAD_BYTES, INFO_N_CAMS, INFO_N_PTS, INFO_N_OBS, INFO_MAX_TRACK, INFO_GRAPH_REPLAYS = 1, 2, 3, 4, 5, 6, 7
 INFO_REDUCE_IN_SOLVE = 8
 INFO_PCG_HELD_POINTS = 9
+INFO_SOLVE_PATH = 10
+SOLVE_SMALL, SOLVE_FLOW, SOLVE_STEPS = 0, 1, 2
 PCG_CONVERGED, PCG_MAX_ITERS, PCG_BREAKDOWN = 0, 1, 2
 LM_STOP_MAX_TRIALS, LM_STOP_FTOL, LM_STOP_XTOL, LM_STOP_GTOL, LM_STOP_LAMBDA_MAX, LM_STOP_BREAKDOWN, LM_STOP_SINGULAR = 0, 1, 2, 3, 4, 5, 6
 LM_STOP_NAMES = ("max_trials", "ftol", "xtol", "gtol", "lambda_max", "breakdown", "singular")
@@ -142,6 +144,8 @@ SIGNATURES = {
     "sfm_shutdown": [],
     "sfm_set_stream": [vp],
     "sfm_synchronize": [],
+    "sfm_set_cu_limit": [ci],
+    "sfm_cu_count": [_ip, _ip],
     "sfm_last_error": [],
     "sfm_quat_to_rot": [ci, _dp, _dp, _ip],
     "sfm_rot_to_quat": [ci, _dp, _dp, _ip],
@@ -205,6 +209,7 @@ SIGNATURES = {
     "sfm_ba_get_state_rot": [vp, _dp, _dp, _dp],
     "sfm_ba_rederive_quaternions": [vp, ci, ci],
     "sfm_ba_flow_tasks": [ci, _ip, ci],
+    "sfm_ba_flow_grid": [ci, ci],
     "sfm_ba_flow_tasks_deferred": [ci, _ip, ci],
     "sfm_desc_create": [ci, ci, ci, ci, vp, _pp],
     "sfm_desc_destroy": [vp],
@@ -413,6 +418,24 @@ def set_stream(stream_ptr):
 
 def synchronize():
     check(load().sfm_synchronize())
+
+
+def set_cu_limit(n):
+    """Make every launch shape and plan for min(n, the device's compute units); 0 removes the limit (sfm_set_cu_limit: a hook
+    for tests, refused with ValueError while a BaProblem exists)."""
+    check(load().sfm_set_cu_limit(int(n)))
+
+
+def cu_count():
+    """(the device's compute units -- 256 before init --, the count the plans see)."""
+    dev, eff = ctypes.c_int(), ctypes.c_int()
+    check(load().sfm_cu_count(ctypes.byref(dev), ctypes.byref(eff)))
+    return int(dev.value), int(eff.value)
+
+
+def flow_grid(n_cus, n_tasks):
+    """Workgroups of the data-flow solve's launch on n_cus compute units for n_tasks tasks (host only); 0: no such launch."""
+    return int(load().sfm_ba_flow_grid(int(n_cus), int(n_tasks)))
 
 
 def _task_table(fn, n):
