@@ -1489,6 +1489,59 @@ int sfm_translation_average_dev(int V, int64_t E, const int* edges /*host [E][2]
 /* Step 2 on the host, by the function the kernels run: 1 for an inlier; *dv_out and *n2_out (may be NULL) its terms. */
 int sfm_translation_edge_test(const double d[3], const double ci[3], const double cj[3], double cos_max, double* dv_out,
                               double* n2_out);
+
+/* ---- track linking: multi-view tracks from verified pairwise matches ---------------------------------------------------
+ * V views; key_ptr[V + 1] (host) gives key k of view v the global id g = key_ptr[v] + k, K = key_ptr[V] < 2^31.  P pairs:
+ * pair_views[P][2] (host) and pair_ptr[P + 1] (host, int64); the matches of pair p are a[m], b[m] for pair_ptr[p] <= m <
+ * pair_ptr[p + 1], a[m] a key of the pair's first view and b[m] a key of its second; M = pair_ptr[P].  mask[M] optional
+ * bytes.  min_len >= 2.  The rule:
+ *   1. A match is USED iff mask is NULL or its byte is non-zero.  Duplicate matches, a pair listed twice and a pair listed
+ *      as (i, j) and as (j, i) are all legal.
+ *   2. label[g] is the smallest global id in the connected component of g under the used matches.  The definition does
+ *      not depend on the order of matches, pairs, launches or timing: any algorithm that reaches it gives the same bits.
+ *   3. Per component: `size` is its number of keys.  It is in CONFLICT iff two of its keys belong to one view; size > V is
+ *      a conflict by counting alone.  A component of one key is UNMATCHED.  Otherwise CONFLICT takes precedence over SHORT
+ *      (size < min_len), and everything else is KEPT.
+ *   4. Kept components are numbered 0 .. n_tracks - 1 by ascending label.  key_track[K]: the track number, or
+ *      SFM_LINK_UNMATCHED, SFM_LINK_SHORT, SFM_LINK_CONFLICT.  pt_ptr[n_tracks + 1].  cam_idx[] and key_idx[] hold a
+ *      track's members by ascending global id, which is ascending view: the order sfm_tri_tracks and sfm_ba_create take;
+ *      key_idx is the key's index inside its view.
+ *   5. summary[8] (int64): used matches | components of at least two keys | kept components | conflicting components |
+ *      short components | observations (pt_ptr[n_tracks]) | the longest kept track | the largest component.
+ *   6. Optional output label_out[K].
+ * Every output may be NULL.  The caller's buffers are sized from K: pt_ptr holds K / 2 + 2 entries, cam_idx and key_idx
+ * hold K; only pt_ptr[0 .. n_tracks] and the first pt_ptr[n_tracks] entries of cam_idx and key_idx are written.  There is
+ * no two-call protocol.
+ * Refusals (SFM_E_SHAPE, sfm_last_error names the item, found before a device is looked for, every output untouched):
+ * key_ptr not starting at 0 or decreasing; a pair with a view out of range or with both views equal; pair_ptr not
+ * starting at 0 or decreasing; min_len < 2; a bad `group` or `scan`; and a key index out of its view's range, in a used
+ * match or a masked one alike -- the host form finds the lowest such match on the host, the _dev form by one verify kernel
+ * (atomicMin) whose word is read once before anything else is launched.
+ * How: a lock-free union-find (the root with the larger id is hooked under the root with the smaller one by
+ * compare-and-swap, so a component's root is its minimum), integer counts, prefix sums over the roots in id order, a
+ * scatter, then a group of `group` lanes per component (0 = automatic; 1, 4 .. 64) that ranks the members by id and finds
+ * a conflict as two neighbouring members of one view, a second prefix sum over the kept flags and a gather.  Only integer
+ * atomics whose result does not depend on their order; no workgroup waits for another one.  `scan` picks the prefix-sum
+ * route: 0 automatic, 1 one workgroup, 2 device-wide (three launches); the bits do not depend on it or on `group`.
+ * sfm_link_tracks takes host arrays and blocks.  sfm_link_tracks_dev takes a, b, mask and every output on the device and a
+ * stream (NULL = the library stream); key_ptr, pair_views and pair_ptr stay HOST arrays.  The host reads the verify word,
+ * then the two counts *n_tracks and *n_obs (host, may be NULL) at the end, and nothing else; it returns when the work is
+ * done. */
+#define SFM_LINK_UNMATCHED  -1
+#define SFM_LINK_SHORT      -2
+#define SFM_LINK_CONFLICT   -3
+int sfm_link_tracks(int V, const int* key_ptr /*[V + 1]*/, int P, const int* pair_views /*[P][2]*/, const int64_t* pair_ptr /*[P + 1]*/,
+                   const int* a /*[M]*/, const int* b /*[M]*/, const unsigned char* mask /*[M] or NULL*/, int min_len, int group,
+                   int scan, int* key_track /*[K]*/, int* pt_ptr /*[K / 2 + 2]*/, int* cam_idx /*[K]*/, int* key_idx /*[K]*/,
+                   int64_t* summary /*[8]*/, int* label_out /*[K]*/);
+int sfm_link_tracks_dev(int V, const int* key_ptr /*host*/, int P, const int* pair_views /*host*/, const int64_t* pair_ptr /*host*/,
+                       const int* d_a, const int* d_b, const unsigned char* d_mask, int min_len, int group, int scan,
+                       int* d_key_track, int* d_pt_ptr, int* d_cam_idx, int* d_key_idx, int64_t* d_summary, int* d_label_out,
+                       int* n_tracks /*host*/, int64_t* n_obs /*host*/, void* hip_stream);
+/* The launch plan, host only: plan[8] = grid of the union (and verify) kernel | lane-group width | grid of the ordering
+ * kernel | grid of the pass over components beyond 64 members | prefix-sum route over the K keys (1 one workgroup, 2
+ * device-wide) | its tiles | route over the K / 2 components | its tiles.  Grids follow sfm_set_cu_limit. */
+int sfm_link_tracks_plan(int V, int64_t K, int64_t M, int group, int scan, int* plan /*[8]*/);
 /* The resident scene moved by X' = s A X + t, on the device: every point by the formula, every camera block [C, q] to
  * C' = s A C + t and q' = q(A R(q)), the library's canonical quaternion of the product (qw >= 0, not renormalised).
  * Refused before any launch: s not finite or not positive (SFM_E_SHAPE), A failing verify_rotation
@@ -1693,6 +1746,20 @@ int sfm_obs_build(sfm_track_store* s, int n_views, int n_pts, int64_t* n_obs);
 /* Blocking: the list of the last build (uv is (2, M) row-major: all u, then all v).  Any output may be NULL; the sizes
  * come from sfm_track_info (SFM_TRACK_INFO_OBS_PTS, SFM_TRACK_INFO_N_OBS).  Counted as download bytes. */
 int sfm_obs_copy(sfm_track_store* s, int* pt_ptr, int* cam_idx, int* key_idx, double* uv);
+
+/* The store form of the track linking (block "track linking" above).  pairs[P][2] = (ref, que) (host).  The matches of pair p are the entries q = table[ref][que, r] with
+ * q > 0 (quirk Q3), exactly the set sfm_track_pairs returns, read where they lie: a = r, b = q.  key_mask (host or NULL)
+ * holds one byte per key of each pair's reference view, concatenated in pair order (match (r, q) is used iff the byte of r
+ * is non-zero); it is the only upload.  The result becomes the store's current observation list, in the buffers
+ * sfm_obs_build fills: n_views is the store's view count, n_pts = n_tracks, u and v are gathered from the normalised
+ * tables (sfm_obs_set_normalised); sfm_track_info(OBS_*), sfm_obs_copy, sfm_ba_create_from_tracks and sfm_ba_sync_tracks
+ * then work on it unchanged.  Refused with the store as it was: a view out of range, ref == que, a table without the row, a
+ * view named in `pairs` that has keys but no normalised coordinates, min_len < 2.  A table entry that names a key its
+ * query view does not have is found by the verify kernel; the store is then left without a current observation list.  No
+ * table is written.  d_key_track: [total keys of the store] on the device, or NULL.  Blocking, on the library stream, after
+ * the store's pending work (the store's stream rule). */
+int sfm_link_tracks_views(sfm_track_store* s, int P, const int* pairs /*host [P][2]*/, const unsigned char* key_mask /*host or NULL*/,
+                         int min_len, int* d_key_track, int64_t* summary /*[8]*/);
 
 /* A resident BA problem (see sfm_ba_create) whose structure is the store's current observation list, copied device to
  * device: nothing is uploaded, SFM_INFO_UPLOAD_BYTES starts at 0.  Cameras and points are set as after sfm_ba_create.

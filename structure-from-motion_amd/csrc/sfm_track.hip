@@ -36,6 +36,7 @@
 
 #include "sfm_common.h"
 #include "sfm_scan.h"
+#include "sfm_track_link.h"
 
 // the ratio test must be the plain division followed by the comparison
 #pragma clang fp contract(off)
@@ -989,6 +990,59 @@ int sfm_obs_copy(sfm_track_store* s, int* pt_ptr, int* cam_idx, int* key_idx, do
     SFM_HIP(hipMemcpy(uv + m, u + cap1, sizeof(double) * m, hipMemcpyDeviceToHost));
     s->download_bytes += 16ll * (int64_t)m;
   }
+  return SFM_OK;
+}
+
+// The store form of the track linking (sfm_hip.h, block "track linking"): the matches of pair p are the entries q > 0 of
+// table[ref][que, :], read where they lie; the result becomes the store's observation list.
+int sfm_link_tracks_views(sfm_track_store* s, int P, const int* pairs, const unsigned char* key_mask, int min_len, int* d_key_track,
+                         int64_t* summary) {
+  const char* who = "sfm_link_tracks_views";
+  SFM_TRY(ensure_init());
+  if (!s) return SFM_E_HANDLE;
+  const int V = (int)s->views.size();
+  if (P < 0 || (P > 0 && !pairs)) { set_error("%s: %d pairs", who, P); return SFM_E_SHAPE; }
+  std::vector<int> key_ptr((size_t)V + 1, 0);
+  for (int v = 0; v < V; ++v) key_ptr[v + 1] = key_ptr[v] + s->views[v].n;
+  std::vector<int64_t> pair_ptr((size_t)P + 1, 0);
+  std::vector<const int*> rows((size_t)(P > 0 ? P : 1), nullptr);
+  std::vector<const double*> nu((size_t)(V > 0 ? V : 1), nullptr), nv((size_t)(V > 0 ? V : 1), nullptr);
+  for (int p = 0; p < P; ++p) {
+    const int ref = pairs[2 * p], que = pairs[2 * p + 1];
+    SFM_TRY(valid_view(s, ref, who));
+    SFM_TRY(valid_view(s, que, who));
+    const View& r = s->views[ref];
+    if (r.rows <= que) { set_error("%s: table %d has no row %d", who, ref, que); return SFM_E_SHAPE; }
+    for (int v : {ref, que})
+      if (s->views[v].n > 0 && !s->views[v].norm) { set_error("%s: view %d has no normalised coordinates", who, v); return SFM_E_SHAPE; }
+    pair_ptr[p + 1] = pair_ptr[p] + r.n;
+    rows[p] = r.table + (size_t)que * r.n;
+  }
+  SFM_TRY(track_link_check(who, V, key_ptr.data(), P, pairs, pair_ptr.data(), min_len, 0, 0));
+  for (int v = 0; v < V; ++v) { nu[v] = s->views[v].norm; nv[v] = s->views[v].norm ? s->views[v].norm + s->views[v].n : nullptr; }
+  const size_t cap = (size_t)key_ptr[V], M = (size_t)pair_ptr[P];
+  hipStream_t st = ctx().stream;
+  SFM_TRY(settle(s));
+  s->obs_views = -1;
+  SFM_TRY(s->obs_ptr.reserve(sizeof(int) * (cap / 2 + 2)));
+  SFM_TRY(s->obs_idx.reserve(sizeof(int) * 2 * (cap + 1)));
+  SFM_TRY(s->obs_uv.reserve(sizeof(double) * 2 * (cap + 1)));
+  DevBuf<unsigned char> d_mask;
+  DevBuf<int64_t> d_summary;
+  if (key_mask) { SFM_TRY(d_mask.upload(key_mask, M, st)); s->upload_bytes += (int64_t)M; }
+  SFM_TRY(d_summary.alloc(8, st));
+  int* cam = static_cast<int*>(s->obs_idx.p);
+  double* u = static_cast<double*>(s->obs_uv.p);
+  LinkProblem q;
+  q.V = V; q.P = P; q.min_len = min_len; q.key_ptr = key_ptr.data(); q.pair_views = pairs; q.pair_ptr = pair_ptr.data();
+  q.rows = rows.data(); q.d_mask = d_mask.p;
+  q.d_key_track = d_key_track; q.d_pt_ptr = static_cast<int*>(s->obs_ptr.p); q.d_cam_idx = cam; q.d_key_idx = cam + cap + 1;
+  q.d_summary = d_summary.p; q.view_nu = nu.data(); q.view_nv = nv.data(); q.d_u = u; q.d_v = u + cap + 1;
+  int n_tracks = 0;
+  int64_t n_obs = 0;
+  SFM_TRY(track_link_run(who, q, &n_tracks, &n_obs, st));
+  if (summary) { SFM_TRY(d_summary.download(summary, 8, st)); SFM_TRY(stream_sync(st)); }
+  s->obs_views = V; s->obs_pts = n_tracks; s->obs_cap = (int)cap; s->obs_m = n_obs;
   return SFM_OK;
 }
 

@@ -81,6 +81,11 @@ TRANSAVG_NO_MODEL, TRANSAVG_KEPT_ROUNDS, TRANSAVG_CG_LIMIT = 1, 2, 4
 TRANSAVG_NO_ROTATION, TRANSAVG_UNREACHED, TRANSAVG_HELD = 1, 2, 4
 TRANSAVG_SUMMARY = ("views_with_position", "views_no_rotation", "views_unreached", "views_held", "edges_inlier", "edges_used_outlier")
 TRANSAVG_OUTPUTS = ("edge_inlier", "edge_cos", "edge_len", "view_status", "n_inliers", "status", "summary", "log")
+LINK_UNMATCHED, LINK_SHORT, LINK_CONFLICT = -1, -2, -3
+LINK_SUMMARY = ("matches_used", "components", "tracks", "conflicts", "short", "observations", "longest_track", "largest_component")
+LINK_OUTPUTS = ("key_track", "pt_ptr", "cam_idx", "key_idx", "summary", "label")
+LINK_PLAN = ("union_grid", "group", "order_grid", "big_grid", "scan_keys", "tiles_keys", "scan_components", "tiles_components")
+LINK_SCAN_AUTO, LINK_SCAN_ONE_BLOCK, LINK_SCAN_DEVICE = 0, 1, 2
 POSE_FROM_F, POSE_FROM_H = 0, 1
 POSE_EMPTY, POSE_NO_MODEL, POSE_NO_POSE, POSE_TIED, POSE_NO_PARALLAX = 1, 2, 4, 8, 16
 POSE_CANDIDATES = 4
@@ -297,6 +302,10 @@ SIGNATURES = {
                                 ctypes.POINTER(ctypes.c_uint8), _dp, _dp, _ip, _ip, _ip, _lp, _dp],
     "sfm_translation_average_dev": [ci, i64, _ip, vp, vp, vp, ci, cd, cd, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "sfm_translation_edge_test": [_dp, _dp, _dp, cd, _dp, _dp],
+    "sfm_link_tracks": [ci, _ip, ci, _ip, _lp, _ip, _ip, ctypes.POINTER(ctypes.c_uint8), ci, ci, ci, _ip, _ip, _ip, _ip, _lp, _ip],
+    "sfm_link_tracks_dev": [ci, _ip, ci, _ip, _lp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, _ip, _lp, vp],
+    "sfm_link_tracks_plan": [ci, i64, i64, ci, ci, _ip],
+    "sfm_link_tracks_views": [vp, ci, _ip, ctypes.POINTER(ctypes.c_uint8), ci, vp, _lp],
     "sfm_ba_transform": [vp, cd, _dp, _dp],
     "sfm_ba_align": [vp, ci, _ip, _dp, cd, ci, ci, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip],
     "sfm_twoview_pose": [ci, _ip, i64, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _dp, _dp, cd, ci, _dp, _dp, _dp, _ip, _ip, _ip,
@@ -1290,6 +1299,121 @@ def translation_average_dev(n_views, edges, d_R, d_t, d_edge_mask=0, root=0, cos
                                              float(cos_max), float(mu), int(rounds), int(polish), float(cg_tol), int(cg_max), _vp(d_C_out),
                                              _vp(d_edge_inlier), _vp(d_edge_cos), _vp(d_edge_len), _vp(d_view_status), _vp(d_n_inliers),
                                              _vp(d_status), _vp(d_summary), _vp(d_log), _vp(stream)))
+
+
+# ---- track linking: multi-view tracks from verified pairwise matches (sfm_link_tracks*; no reference counterpart) ---------
+def check_track_link(key_ptr, pair_views, pair_ptr, a, b, mask=None, min_len=2, group=0, scan=0):
+    """The arguments of a ``track_link`` call, without a device: ``(key_ptr int32 (V + 1,), pair_views int32 (P, 2), pair_ptr
+    int64 (P + 1,), a int32 (M,), b int32 (M,), mask uint8 (M,) or None, min_len, group, scan)`` converted or ValueError --
+    everything sfm_link_tracks refuses, in its order, naming the item."""
+    def integer(name, value):
+        if isinstance(value, bool) or int(value) != value:
+            raise ValueError("%s must be an integer, got %r" % (name, value))
+        return int(value)
+
+    def integers(name, value, dtype, shape):
+        arr = np.asarray(value)
+        if arr.size and not np.all(arr == np.floor(arr)):
+            raise ValueError("%s must hold integers" % name)
+        arr = arr.reshape(shape)
+        if arr.size and (arr.min() < np.iinfo(dtype).min or arr.max() > np.iinfo(dtype).max):
+            raise ValueError("%s does not fit %s" % (name, np.dtype(dtype).name))
+        return np.ascontiguousarray(arr, dtype=dtype)
+    min_len, group, scan = integer("min_len", min_len), integer("group", group), integer("scan", scan)
+    key_ptr = integers("key_ptr", key_ptr, np.int64, (-1,))
+    pair_views = integers("pair_views", pair_views, np.int64, (-1, 2))
+    pair_ptr = integers("pair_ptr", pair_ptr, np.int64, (-1,))
+    if key_ptr.size < 1 or pair_ptr.size != pair_views.shape[0] + 1:
+        raise ValueError("key_ptr must hold V + 1 >= 1 entries and pair_ptr P + 1 = %d, got %d and %d"
+                         % (pair_views.shape[0] + 1, key_ptr.size, pair_ptr.size))
+    V, P = key_ptr.size - 1, pair_views.shape[0]
+    if min_len < 2:
+        raise ValueError("min_len = %d must be >= 2" % min_len)
+    _check_group(group)
+    if scan not in (0, 1, 2):
+        raise ValueError("scan = %d must be 0 (automatic), 1 (one workgroup) or 2 (device-wide)" % scan)
+    if key_ptr[0] != 0:
+        raise ValueError("key_ptr[0] = %d must be 0" % key_ptr[0])
+    down = np.diff(key_ptr) < 0
+    if down.any():
+        raise ValueError("key_ptr decreases at view %d" % int(np.argmax(down)))
+    if key_ptr[-1] >= 2 ** 31:
+        raise ValueError("K = %d must be below 2^31" % key_ptr[-1])
+    if pair_ptr[0] != 0:
+        raise ValueError("pair_ptr[0] = %d must be 0" % pair_ptr[0])
+    for p in range(P):
+        i, j = int(pair_views[p, 0]), int(pair_views[p, 1])
+        if not (0 <= i < V and 0 <= j < V) or i == j:
+            raise ValueError("pair %d = (%d, %d) must join two different views in 0 .. %d" % (p, i, j, V - 1))
+        if pair_ptr[p + 1] < pair_ptr[p]:
+            raise ValueError("pair_ptr decreases at pair %d" % p)
+    M = int(pair_ptr[-1])
+    a, b = integers("a", a, np.int64, (-1,)), integers("b", b, np.int64, (-1,))
+    if a.size != M or b.size != M:
+        raise ValueError("a and b must hold M = pair_ptr[P] = %d matches, got %d and %d" % (M, a.size, b.size))
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        if mask.size != M:
+            raise ValueError("mask must hold M = %d entries, got %d" % (M, mask.size))
+    if M:
+        n_keys = np.diff(key_ptr)
+        pair_of = np.repeat(np.arange(P), np.diff(pair_ptr))
+        bad = (a < 0) | (a >= n_keys[pair_views[pair_of, 0]]) | (b < 0) | (b >= n_keys[pair_views[pair_of, 1]])
+        if bad.any():
+            raise ValueError("match %d names a key outside its view" % int(np.argmax(bad)))
+    return (key_ptr.astype(np.int32), np.ascontiguousarray(pair_views, dtype=np.int32), pair_ptr, a.astype(np.int32), b.astype(np.int32),
+            mask, min_len, group, scan)
+
+
+def track_link_plan(n_views, n_keys, n_matches, group=0, scan=0):
+    """The launch plan of a ``track_link`` call as a dict over ``LINK_PLAN`` (sfm_link_tracks_plan; host only; the grids
+    follow ``set_cu_limit``)."""
+    plan = np.zeros(8, dtype=np.int32)
+    check(load().sfm_link_tracks_plan(int(n_views), int(n_keys), int(n_matches), int(group), int(scan), iptr(plan)))
+    return dict(zip(LINK_PLAN, (int(v) for v in plan)))
+
+
+def track_link(key_ptr, pair_views, pair_ptr, a, b, mask=None, min_len=2, group=0, scan=0, outputs=LINK_OUTPUTS):
+    """Multi-view tracks from pairwise matches (sfm_link_tracks): the connected components of the used matches over (view,
+    key) nodes; a component with two keys of one view is dropped as a conflict, one below ``min_len`` as short.  Global key
+    ``key_ptr[v] + k``; the matches of pair ``p = (i, j)`` are ``a[m]`` (keys of ``i``) and ``b[m]`` (keys of ``j``) for
+    ``pair_ptr[p] <= m < pair_ptr[p + 1]``.  Returns a dict: ``key_track (K,)`` (track, or LINK_UNMATCHED / LINK_SHORT /
+    LINK_CONFLICT), ``pt_ptr (n_tracks + 1,)``, ``cam_idx``, ``key_idx (n_obs,)`` by ascending view inside a track, ``summary
+    (8,) int64`` in the order of ``LINK_SUMMARY``, ``label (K,)`` the smallest global key of every key's component; an output
+    not named in ``outputs`` is not computed and comes back as None."""
+    key_ptr, pair_views, pair_ptr, a, b, mask, min_len, group, scan = check_track_link(key_ptr, pair_views, pair_ptr, a, b, mask, min_len,
+                                                                                       group, scan)
+    unknown = set(outputs) - set(LINK_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (LINK_OUTPUTS, sorted(unknown)))
+    V, P, K = key_ptr.size - 1, pair_views.shape[0], int(key_ptr[-1])
+    summary = np.zeros(8, dtype=np.int64)              # always: it holds the two counts that size the CSR
+    o = {"key_track": np.zeros(K, dtype=np.int32), "pt_ptr": np.zeros(K // 2 + 2, dtype=np.int32), "cam_idx": np.zeros(K, dtype=np.int32),
+         "key_idx": np.zeros(K, dtype=np.int32), "label": np.zeros(K, dtype=np.int32)}
+    w = {k: (v if k in outputs else None) for k, v in o.items()}
+    check(load().sfm_link_tracks(V, iptr(key_ptr), P, iptr(pair_views), _lptr(pair_ptr), iptr(a), iptr(b), _u8ptr(mask), min_len, group, scan,
+                                iptr(w["key_track"]), iptr(w["pt_ptr"]), iptr(w["cam_idx"]), iptr(w["key_idx"]), _lptr(summary),
+                                iptr(w["label"])))
+    n_tracks, n_obs = int(summary[2]), int(summary[5])
+    for name, n in (("pt_ptr", n_tracks + 1), ("cam_idx", n_obs), ("key_idx", n_obs)):
+        if w[name] is not None:
+            w[name] = w[name][:n].copy()
+    w["summary"] = summary if "summary" in outputs else None
+    return w
+
+
+def track_link_dev(key_ptr, pair_views, pair_ptr, d_a, d_b, d_mask=0, min_len=2, group=0, scan=0, d_key_track=0, d_pt_ptr=0, d_cam_idx=0,
+                   d_key_idx=0, d_summary=0, d_label=0, stream=0):
+    """``track_link`` with ``a``, ``b``, ``mask`` and the outputs as device pointers (``d_pt_ptr`` holds K / 2 + 2 entries,
+    ``d_cam_idx`` and ``d_key_idx`` K) and a caller's stream (sfm_link_tracks_dev); ``key_ptr``, ``pair_views`` and ``pair_ptr``
+    stay host arrays, optional arrays are 0.  Returns ``(n_tracks, n_obs)``."""
+    key_ptr, pair_ptr = i32(key_ptr).reshape(-1), np.ascontiguousarray(pair_ptr, dtype=np.int64).reshape(-1)
+    pair_views = i32(pair_views).reshape(-1, 2)
+    n_tracks, n_obs = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int64)
+    check(load().sfm_link_tracks_dev(key_ptr.size - 1, iptr(key_ptr), pair_views.shape[0], iptr(pair_views), _lptr(pair_ptr), _vp(d_a), _vp(d_b),
+                                    _vp(d_mask), int(min_len), int(group), int(scan), _vp(d_key_track), _vp(d_pt_ptr), _vp(d_cam_idx),
+                                    _vp(d_key_idx), _vp(d_summary), _vp(d_label), iptr(n_tracks), _lptr(n_obs), _vp(stream)))
+    return int(n_tracks[0]), int(n_obs[0])
 
 
 # ---- robust essential matrix (sfm_essential_*; no reference counterpart) ------------------------------------------------
@@ -2745,8 +2869,26 @@ class TrackStore:
         check(self._lib.sfm_obs_build(self._h, int(n_views), int(n_pts), ctypes.byref(m)))
         return int(m.value)
 
+    def link(self, pairs, key_mask=None, min_len=2, d_key_track=0):
+        """Link the matches of ``pairs`` ((P, 2) of (ref, que): the entries ``table[ref][que, r] > 0``, read where they lie) into
+        multi-view tracks and make them the store's observation list (sfm_link_tracks_views).  ``key_mask``: one byte per key
+        of each pair's reference view, concatenated in pair order (a match is used iff the byte of its reference key is
+        non-zero) -- the only upload.  ``d_key_track``: a device pointer for the per-key verdicts (all keys of the store), or 0.
+        Returns ``summary (8,) int64`` in the order of ``LINK_SUMMARY``; ``observations()`` and ``BaProblem.from_tracks`` then
+        see the tracks."""
+        pairs = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), dtype=np.int32)
+        if key_mask is not None:
+            key_mask = np.ascontiguousarray(np.asarray(key_mask).reshape(-1) != 0, dtype=np.uint8)
+            want = sum(self.n_keys(int(r)) for r in pairs[:, 0] if 0 <= r < self.n_views)
+            if key_mask.size != want:
+                raise ValueError("link: key_mask holds %d bytes, the reference views of the pairs %d keys" % (key_mask.size, want))
+        summary = np.zeros(8, dtype=np.int64)
+        check(self._lib.sfm_link_tracks_views(self._h, pairs.shape[0], iptr(pairs), _u8ptr(key_mask), int(min_len), _vp(d_key_track),
+                                             _lptr(summary)))
+        return summary
+
     def observations(self):
-        """(pt_ptr (N+1,), cam_idx (M,), key_idx (M,), uv (2, M)) of the last ``build_observations``."""
+        """(pt_ptr (N+1,), cam_idx (M,), key_idx (M,), uv (2, M)) of the last ``build_observations`` or ``link``."""
         n, m = self.info(TRACK_INFO_OBS_PTS), self.info(TRACK_INFO_N_OBS)
         pt_ptr, cam, key = np.zeros(n + 1, dtype=np.int32), np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
         uv = np.zeros((2, m))

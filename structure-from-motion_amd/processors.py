@@ -2189,6 +2189,7 @@ def orient_views(tracker, pairs, K, K_right=None, root=0, max_sampson_px=2.0, ma
                 entry["status"] = counts["status"]
                 if counts["best_cand"] >= 0 and not counts["status"] & native.POSE_NO_POSE:
                     entry["R"], entry["t"] = tracker.pose_last["R"].copy(), tracker.pose_last["t"].copy()
+            entry["r_idx"], entry["q_idx"], entry["inlier"] = got[0].reshape(-1), got[1].reshape(-1), got[2]      # for link_views
         poses.append(entry)
         triples.append((entry["ref"], entry["que"], entry["R"]))
     rots, verdict = HipCamposeMixin().average_rotations(triples, n_views, root, max_angle_deg, tree_hyp, rounds)
@@ -2212,6 +2213,144 @@ def locate_views(tracker, pairs, K, K_right=None, root=0, max_sampson_px=2.0, ma
     centres, tr_verdict = HipCamposeMixin().average_translations(quads, rots, n_views, root, max_direction_deg, translation_rounds,
                                                                  edge_mask=rot_verdict["edge_inlier"])
     return rots, centres, {"rotation": rot_verdict, "translation": tr_verdict}, poses
+
+
+def link_key_mask(n_ref_keys, inliers=None, pair_mask=None):
+    """The per-key mask ``TrackStore.link`` takes, on the host: for pair ``p`` ``n_ref_keys[p]`` bytes, one per key of its
+    reference view, the pairs concatenated in their order.  ``inliers[p]`` is None (every match of the pair is used: all
+    ones) or ``(r_idx, mask)``: the reference keys of the pair's matches as ``generate_matched_pairs`` / ``verify_pairs``
+    return them and the mask over those matches; the byte of ``r_idx[k]`` is set iff ``mask[k]``.  ``pair_mask[p]`` false
+    drops the whole pair (all zeros).  A key without a match has no table entry, so its byte is never looked at."""
+    n_ref_keys = [int(n) for n in n_ref_keys]
+    P = len(n_ref_keys)
+    if inliers is not None and len(inliers) != P:
+        raise ValueError("link: {} inlier masks for {} pairs".format(len(inliers), P))
+    if pair_mask is not None and len(pair_mask) != P:
+        raise ValueError("link: {} pair verdicts for {} pairs".format(len(pair_mask), P))
+    parts = []
+    for p, n in enumerate(n_ref_keys):
+        if pair_mask is not None and not pair_mask[p]:
+            parts.append(np.zeros(n, dtype=np.uint8))
+            continue
+        if inliers is None or inliers[p] is None:
+            parts.append(np.ones(n, dtype=np.uint8))
+            continue
+        r_idx, mask = inliers[p]
+        r_idx, mask = np.asarray(r_idx, dtype=np.int64).reshape(-1), np.asarray(mask).reshape(-1) != 0
+        if r_idx.shape != mask.shape:
+            raise ValueError("link: pair {} has {} matches and {} mask entries".format(p, r_idx.size, mask.size))
+        if r_idx.size and (r_idx.min() < 0 or r_idx.max() >= n):
+            raise ValueError("link: pair {} names a reference key outside 0 .. {}".format(p, n - 1))
+        part = np.zeros(n, dtype=np.uint8)
+        part[r_idx[mask]] = 1
+        parts.append(part)
+    return np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+
+
+def link_views(tracker, pairs, inliers=None, pair_mask=None, min_len=2, want_key_track=True):
+    """Multi-view tracks of a ``HipDeviceKeyTracker`` from the matches of the listed ``pairs`` ``(ref_idx, que_idx)``
+    (``TrackStore.link``: connected components of the match graph, read from the tables where they lie; a component with two
+    keys of one view is dropped).  ``inliers[p]`` is the mask ``verify_pairs`` returned over the pair's matches -- or the
+    tuple ``(r_idx, mask)``, which saves fetching the table row to find the matches' reference keys -- or None; ``pair_mask``
+    drops whole pairs (the rotation and translation verdicts).  Only the per-key mask goes up.  The tracks become the
+    store's observation list (every view named needs ``set_normalised`` coordinates), ready for
+    ``BaProblem.from_tracks``.  Returns ``summary, key_track``: a dict over ``native.LINK_SUMMARY`` and the per-key verdicts of
+    all keys of the store, views concatenated (None unless ``want_key_track``).  A function of the module, like
+    ``verify_pairs``; ``process()`` does not call it."""
+    store = tracker._store
+    pairs = [(int(r), int(q)) for r, q in pairs]
+    n_views = len(tracker.track_list)
+    for r, q in pairs:
+        if not (0 <= r < n_views and 0 <= q < n_views) or r == q:
+            raise ValueError("link: pair ({}, {}) must join two different views in 0 .. {}".format(r, q, n_views - 1))
+    key_mask = None
+    if inliers is not None or pair_mask is not None:
+        filled = None
+        if inliers is not None:
+            filled = []
+            for p, item in enumerate(inliers):
+                if item is None or isinstance(item, tuple):
+                    filled.append(item)
+                else:                                                   # a bare mask: the matches are the row's entries > 0
+                    filled.append((np.flatnonzero(store.row(pairs[p][0], pairs[p][1]) > 0), item))
+        key_mask = link_key_mask([store.n_keys(r) for r, _ in pairs], filled, pair_mask)
+    key_track = None
+    if want_key_track:
+        import torch
+        total = sum(store.n_keys(v) for v in range(n_views))
+        d_track = torch.empty(max(total, 1), dtype=torch.int32, device="cuda")
+        summary = store.link(pairs, key_mask, min_len, d_track.data_ptr())
+        key_track = d_track[:total].cpu().numpy()
+    else:
+        summary = store.link(pairs, key_mask, min_len)
+    return dict(zip(native.LINK_SUMMARY, (int(v) for v in summary))), key_track
+
+
+def reconstruct_views(tracker, pairs, K, root=0, min_len=2, lam=5.0, iters=10, solver="iterate", refine_iters=20, retriangulate_px=None,
+                      cull_px=None, set_normalised=True, **locate):
+    """A global reconstruction of the views of a ``HipDeviceKeyTracker`` from the listed ``pairs``, on the device from the
+    matches to the adjusted scene: ``locate_views`` (``locate`` are its options; one intrinsic matrix ``K`` for every view),
+    ``link_views`` over the pairs both verdicts admit with each pair's verification inliers, a ``BaProblem`` from the tracks
+    with the averaged rotations and centres as cameras, ``refine_points`` (DLT, then Gauss-Newton) for the points, with
+    ``retriangulate_px`` the robust re-triangulation and with ``cull_px`` a cull at that many pixels, then ``iters``
+    iterations of ``solver``: ``"iterate"`` (all cameras move, the gauge is the damping's) or ``"pcg"`` (``minimize_pcg`` with
+    ``root`` and the view farthest from it held: the second fixes the scale).  Only the per-key masks go up -- and, with
+    ``set_normalised``, once the normalised key coordinates the observation list gathers from; the verdicts and the result
+    come down.  Returns a dict: ``rots``, ``centres`` (lists in the reference's convention, None for a view without a pose),
+    ``points`` (3, n_tracks), ``key_track``, ``summary`` of the linking, ``verdicts``, ``poses``, ``pair_mask``, ``cameras`` (V, 7),
+    ``rots_averaged`` and ``centres_averaged`` (what ``locate_views`` gave, before the adjustment), ``pt_ptr`` and ``cam_idx`` of the
+    adjusted scene and ``cost`` (the cost after the points were made, then after every iteration or accepted trial).  A function of the
+    module, like ``locate_views``; ``process()`` does not call it."""
+    if solver not in ("iterate", "pcg"):
+        raise ValueError("solver must be 'iterate' or 'pcg', got {!r}".format(solver))
+    pairs = [(int(r), int(q)) for r, q in pairs]
+    rots, centres, verdicts, poses = locate_views(tracker, pairs, K, None, root, **locate)
+    tv = verdicts["translation"]
+    if tv is None or tv["status"] & native.TRANSAVG_NO_MODEL:
+        raise ValueError("reconstruct_views: the pairs give no rotations or no positions")
+    pair_mask = np.zeros(len(pairs), dtype=bool)
+    both = verdicts["rotation"]["edge_inlier"] & tv["edge_inlier"]
+    pair_mask[np.asarray(tv["pairs"], dtype=np.int64)[both]] = True
+    located = [rots[v] is not None and centres[v] is not None for v in range(len(rots))]
+    for p, (r, q) in enumerate(pairs):
+        pair_mask[p] &= located[r] and located[q]
+    store = tracker._store
+    n_views = len(tracker.track_list)
+    if set_normalised:
+        for v in range(n_views):
+            store.set_normalised(v, normalise_pixels(tracker._xy[v].T, K))
+    inliers = [(e["r_idx"], e["inlier"]) if "inlier" in e else None for e in poses]
+    summary, key_track = link_views(tracker, pairs, inliers, pair_mask, min_len)
+    cams = pack_cameras([rots[v] if located[v] else np.identity(3) for v in range(n_views)],
+                                 [centres[v] if located[v] else np.zeros(3) for v in range(n_views)])
+    px2 = 1.0 / float(K[0][0]) ** 2                                         # a squared pixel in normalised units
+    with native.BaProblem.from_tracks(store) as prob:
+        prob.set_state(cams, np.zeros((3, prob.n_pts)))
+        prob.refine_points(0.0, 0, native.TRACKS_LINEAR, want_outputs=False)
+        prob.refine_points(0.5, refine_iters, native.TRACKS_NONLINEAR, want_outputs=False)
+        if retriangulate_px is not None:
+            prob.retriangulate(float(retriangulate_px) ** 2 * px2, want_outputs=False)
+        if cull_px is not None:
+            prob.cull(float(cull_px) ** 2 * px2, want_outputs=False)
+        cost = [prob.cost()]
+        if solver == "iterate":
+            for _ in range(int(iters)):
+                prob.iterate(lam, 1)
+                cost.append(prob.cost())
+        else:
+            free = np.array(located, dtype=np.uint8)
+            far = max((v for v in range(n_views) if located[v]), key=lambda v: float(np.linalg.norm(centres[v] - centres[root])))
+            free[[root, far]] = 0
+            done = prob.minimize_pcg(free, lambda0=lam, max_trials=int(iters))
+            cost.extend(float(c) for c in done.log["cost"][done.log["accepted"] != 0])
+        cams_out, points = prob.get_state()
+        structure = prob.structure(want_uv=False)
+    rot_out = quaternions_to_rotations(cams_out[:, 3:7])
+    return {"rots": [rot_out[v] if located[v] else None for v in range(n_views)],
+            "centres": [cams_out[v, 0:3].reshape(3, 1).copy() if located[v] else None for v in range(n_views)], "points": points,
+            "key_track": key_track, "summary": summary, "verdicts": verdicts, "poses": poses, "pair_mask": pair_mask, "cameras": cams_out,
+            "rots_averaged": rots, "centres_averaged": centres,
+            "pt_ptr": structure[0], "cam_idx": structure[1], "cost": np.array(cost)}
 
 
 def _guided_model(model):
