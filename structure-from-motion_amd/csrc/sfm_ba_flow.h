@@ -11,19 +11,20 @@
 // block, LEFT-looking (S_ik - sum_m L[i][m] L[k][m]^T, then the product with W_k = L_kk^-1), taken by the other workgroups
 // of the launch one after the other in column order (a ticket per task).  Blocks travel through global memory: write-through (sc1) stores, one flag word per block,
 // sc1 loads on the consuming side (MI355X_MICROARCH.md, inter-workgroup visibility; every workgroup of this launch owns its
-// CU: 121 KB of LDS).
+// CU: 113 KB of LDS).
 //
-// Who computes what (the chain keeps the two sub-diagonals to itself):
+// Who computes what (the chain keeps the first sub-diagonal to itself):
 //   chain, step j:   elimination waves (0-3, LDS only): [D_j; I] -> X_j, W_j = X_j^T; then L[j+1][j] = T W_j^T (TRSM as a product),
 //                    D_j+1 -= L[j+1][j] L[j+1][j]^T.
-//                    preparation waves (4-7), concurrently with the elimination, row r = j+1: take over the blocks
-//                    (r, r-2), (r, r-1), (r, r) (fetched a step ahead), L[r][r-2] = T W_j-1^T, and apply columns r-3 / r-2 to
-//                    (r, r-1) and column r-2 to (r, r); behind the elimination they publish X_j -> xinv(j, j), W_j -> ldiag[j], L[j+1][j].
-//   tasks of block row i >= 3:  L[i][k] for k <= i-4; the "closer" L[i][i-3] together with the hand-over blocks (i, i-2) and
-//                    (i, i) through column i-3 (sums through column i-4 formed before W_i-3 exists -- but for the one term that needs
-//                    the chain's L[i-2][i-4], announced with W_i-3 --, the last terms out of LDS);
-//                    the hand-over block (i, i-1) through column i-4 — levels chosen so that no hand-over waits for a block
-//                    the chain publishes later than W_i-3.
+//                    preparation waves (4-7), concurrently with the elimination, row r = j+1: copy the finished hand-over blocks
+//                    (r, r-1) and (r, r) into LDS -- no matrix instruction beside the elimination from row 3 on (rows 1 and 2 are
+//                    read from S and prepared here); behind the elimination they publish X_j -> xinv(j, j), W_j -> ldiag[j], L[j+1][j].
+//   tasks of block row i >= 3:  L[i][k] for k <= i-4; the hand-over block (i, i-1) through column i-4; the "closer": L[i][i-3]
+//                    (sums through column i-4 formed before W_i-3 exists -- but for the one term that needs L[i-2][i-4], announced
+//                    with W_i-3 --, the last terms out of LDS), then, behind W_i-2, L[i][i-2] and the hand-over blocks (i, i-1) and
+//                    (i, i) through column i-2.  L[i-1][i-2], which the chain announces only behind its first matrix phase, is formed
+//                    by the closer itself from the hand-over block (i-1, i-2) of the closer above and W_i-2: same tiles, same order,
+//                    same bits.  No hand-over waits for anything the chain publishes later than W_i-2 (row 3: L[2][1]).
 //   tasks of the rhs row and of the identity rows e = 0 .. nbk-2: the same recurrence with their own blocks; the task that finishes
 //                    an identity row forms its part of dp = X y, the last one to arrive updates the cameras.
 //   with the split-K reduce riding in the launch (FlowRed, below): tasks ahead of all these sum ba_linearize's camera accumulators
@@ -46,7 +47,8 @@ __host__ __device__ inline int flow_fl(int nbk, int i, int k) { return kFlowHdr 
 __host__ __device__ inline int flow_fx(int nbk, int e, int m) { return kFlowHdr + nbk * nbk + e * nbk + m; }          // X[e][m] published
 __host__ __device__ inline int flow_fw(int nbk, int k) { return kFlowHdr + 2 * nbk * nbk + k; }                       // W_k published
 __host__ __device__ inline int flow_fy(int nbk, int k) { return kFlowHdr + 2 * nbk * nbk + nbk + k; }                 // y_k published
-__host__ __device__ inline int flow_fh(int nbk, int i, int t) { return kFlowHdr + 2 * nbk * nbk + 2 * nbk + 3 * i + t; }   // hand-over block (i, i-2+t)
+__host__ __device__ inline int flow_fh(int nbk, int i, int t) { return kFlowHdr + 2 * nbk * nbk + 2 * nbk + 3 * i + t; }   // hand-over of row i: t = 1 block (i, i-1) through column i-4 (hand-over task, in red);
+                                                                                                                           // t = 0 the same block through column i-2 (closer, in flow_hand[i]); t = 2 block (i, i) through column i-2 (closer, in red)
 __host__ __device__ inline int flow_words_solve(int nbk) { return kFlowHdr + 2 * nbk * nbk + 5 * nbk; }
 // deferred reduce (S summed from the product's split-K slabs inside this launch): camera c's accumulators, part 0..3; quarter q of block (i, k) of S
 __host__ __device__ inline int flow_fc(int nbk, int c, int part) { return flow_words_solve(nbk) + 4 * c + part; }
@@ -75,12 +77,12 @@ constexpr int FS_XM = 1056;               // [32][33] X_j rows as the eliminatio
 constexpr int FS_XY = 2112;               // f64x2[16][64] published pivots of chol_trsm_cols
 constexpr int FS_W = 4160;                // [2][1024] W_j, W_j-1 (k-interleaved)
 constexpr int FS_LA = 6208;               // [2][1024] L[j+1][j] of this and the previous step
-constexpr int FS_LB = 8256;               // [2][1024] L[r][r-2] of this and the previous step
-constexpr int FS_B = 10304;               // [3][1024] the row being taken over: (r, r-2), (r, r-1), (r, r); tasks: T and L
-constexpr int FS_XL = 13376;              // [1024] X_j in the operand layout, for the preparation waves to publish
-constexpr int FS_XM2 = 14400;             // [32][33] the second X_j row buffer
-constexpr int FS_INT = 15456;             // ints: [0..4] the chain's elimination flag, group-barrier counters and step counters; task workgroups: [15] last-arriver flag of dp, [20] ticket
-constexpr int FS_TOTAL = 15472;
+constexpr int FS_LB = 8256;               // [1024] L[2][0] (row 2 is prepared by the chain itself); the closer keeps its blocks in FS_W and FS_LA
+constexpr int FS_B = 9280;                // [3][1024] the row being taken over: (r, r-2) for r = 2, (r, r-1), (r, r); tasks: T and L
+constexpr int FS_XL = 12352;              // [1024] X_j in the operand layout, for the preparation waves to publish
+constexpr int FS_XM2 = 13376;             // [32][33] the second X_j row buffer
+constexpr int FS_INT = 14432;             // ints: [0..4] the chain's elimination flag, group-barrier counters and step counters; task workgroups: [15] last-arriver flag of dp, [20] ticket
+constexpr int FS_TOTAL = 14448;
 constexpr size_t kFlowLdsBytes = FS_TOTAL * sizeof(double);
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -133,6 +135,10 @@ __device__ __forceinline__ f64x4 ctile_ld_lds(const double* blk, int off) {
 __device__ __forceinline__ void ctile_st_sc1(FlowBuf b, size_t blk, int off, const f64x4& v) {
   st2_sc1(b, blk + off, f64x2{v[0], v[1]});
   st2_sc1(b, blk + off + 256, f64x2{v[2], v[3]});
+}
+__device__ __forceinline__ f64x4 ctile_ld_sc1(FlowBuf b, size_t blk, int off) {
+  const f64x2 p = ld2_sc1(b, blk + off), q = ld2_sc1(b, blk + off + 256);
+  return f64x4{p.x, p.y, q.x, q.y};
 }
 
 // Waiting.  Lane 0.. poll flags, lane 63 the abort word, relaxed agent-scope loads (sc1).  After a give-up (a sibling never
@@ -226,7 +232,7 @@ __device__ __forceinline__ void flow_group_sync(int* ctr, int& target) {
 }
 
 struct FlowCtx {
-  FlowBuf red, xinv, ldiag;
+  FlowBuf red, xinv, ldiag, hand;
   double* redp; double* rhs;      // plain views (S blocks, the rhs segment)
   unsigned* flow; unsigned epoch; int nbk;
   double* sm; int* smi;
@@ -434,8 +440,9 @@ __device__ __forceinline__ void flow_task_h1(FlowCtx& c, int i) {
   if (threadIdx.x == 0) flow_publish(c.flow, flow_fh(c.nbk, i, 1), c.epoch);
 }
 
-// L[i][i-3] and the hand-over blocks (i, i-2), (i, i) through column i-3: the three sums through column i-4 share the operand
-// tiles of row i and are complete before W_i-3 exists; what W_i-3 releases is one product, an LDS round trip and two terms.
+// L[i][i-3] and the blocks (i, i-2), (i, i) through column i-3: the three sums through column i-4 share the operand tiles of
+// row i and are complete before W_i-3 exists; what W_i-3 releases is one product, an LDS round trip and two terms.  Then the
+// row is finished through column i-2 behind W_i-2 (four products in two rounds) and handed to the chain: L[i][i-2], (i, i-1), (i, i).
 __device__ __forceinline__ void flow_task_closer(FlowCtx& c, int i) {
   const int coff = ctile_off(c.sx, c.sy, c.lr, c.lk), k = i - 3, nbk = c.nbk;
   flow_wait_S(c, i, k, i);
@@ -502,18 +509,62 @@ __device__ __forceinline__ void flow_task_closer(FlowCtx& c, int i) {
   ctile_st_sc1(c.red, red_blk_base(i, k), coff, o);
   ctile_st_lds(Lx, coff, o);
   if (k >= 1) mfma8(acc0, a0p, bl);      // the deferred term
+  flow_drain();
   __syncthreads();
+  if (threadIdx.x == 0) flow_publish(c.flow, flow_fl(nbk, i, k), c.epoch);      // L[i][i-3] is out: its readers do not wait for the rest
   if (stamp) stamp[3] = __builtin_amdgcn_s_memrealtime();
   op_lds(Lx, c.sy, c.lr, c.lk, b);
   op_lds(Lx, c.sx, c.lr, c.lk, a);
   mfma8(acc0, a0, b);
   mfma8(acc2, a, b);
-  ctile_st_sc1(c.red, red_blk_base(i, i - 2), coff, s0 - acc0);
-  ctile_st_sc1(c.red, red_blk_base(i, i), coff, s2 - acc2);
+  // ---- columns i-3 and i-2 applied to the row: what the chain's preparation waves did beside the elimination, with the same operand
+  // tiles in the same order (the bits are the chain's).  T0 = (i, i-2) through column i-3 stays in LDS; (i, i) in registers.
+  double* T0x = c.sm + FS_W;
+  double* LBx = c.sm + FS_W + kBlk;
+  double* LAx = c.sm + FS_LA;
+  ctile_st_lds(T0x, coff, s0 - acc0);
+  f64x4 d2 = s2 - acc2;
+  // before W_i-2 exists: (i, i-1) -= L[i][i-3] L[i-1][i-3]^T (kept in the accumulator until the second term is there), the hand-over
+  // task's block, and the block (i-1, i-2) the closer of row i-1 finished -- L[i-1][i-2] is formed here from it, not awaited: the
+  // chain announces it only behind its first matrix phase.  Row 3 has no closer above it: L[2][1] comes from the chain.
+  if (i >= 4) c.w.wait(flow_fl(nbk, i - 1, k), flow_fh(nbk, i, 1), flow_fh(nbk, i - 1, 0)); else c.w.wait(flow_fl(nbk, i - 1, k), flow_fh(nbk, i, 1));
+  double hb[8];
+  op_sc1(c.red, red_blk_base(i - 1, k), c.sx, c.lr, c.lk, a);
+  const f64x4 h1 = ctile_ld_sc1(c.red, red_blk_base(i, i - 1), coff);
+  if (i >= 4) op_sc1(c.hand, (size_t)(i - 1) * kBlk, c.sy, c.lr, c.lk, hb);
+  f64x4 acc1 = {0, 0, 0, 0};
+  mfma8(acc1, a, b);
+  __syncthreads();      // T0 complete
+  if (i >= 4) c.w.wait(flow_fw(nbk, i - 2)); else c.w.wait(flow_fw(nbk, i - 2), flow_fl(nbk, 2, 1));
+  if (stamp) stamp[7] = __builtin_amdgcn_s_memrealtime();
+  op_sc1(c.ldiag, (size_t)(i - 2) * kBlk, c.sx, c.lr, c.lk, a);
+  op_lds(T0x, c.sy, c.lr, c.lk, b);
+  f64x4 o2 = {0, 0, 0, 0};
+  mfma8(o2, a, b);      // L[i][i-2]^T = W_i-2 T0^T
+  ctile_st_sc1(c.red, red_blk_base(i, i - 2), coff, o2);
+  ctile_st_lds(LBx, coff, o2);
+  if (i >= 4) {
+    f64x4 la = {0, 0, 0, 0};
+    mfma8(la, a, hb);      // L[i-1][i-2]^T = W_i-2 (i-1, i-2)^T
+    ctile_st_lds(LAx, coff, la);
+  }
+  __syncthreads();
+  // (i, i-1) -= L[i][i-2] L[i-1][i-2]^T ; (i, i) -= L[i][i-2] L[i][i-2]^T (lower tiles)
+  op_lds(LBx, c.sy, c.lr, c.lk, b);
+  if (i >= 4) op_lds(LAx, c.sx, c.lr, c.lk, a); else op_sc1(c.red, red_blk_base(2, 1), c.sx, c.lr, c.lk, a);
+  mfma8(acc1, a, b);
+  ctile_st_sc1(c.hand, (size_t)i * kBlk, coff, h1 - acc1);
+  if (c.gw != 2) {
+    op_lds(LBx, c.sx, c.lr, c.lk, a);
+    f64x4 acc3 = {0, 0, 0, 0};
+    mfma8(acc3, a, b);
+    d2 = d2 - acc3;
+  }
+  ctile_st_sc1(c.red, red_blk_base(i, i), coff, d2);
   flow_drain();
   __syncthreads();
   if (threadIdx.x == 0) {
-    flow_publish(c.flow, flow_fl(nbk, i, k), c.epoch);
+    flow_publish(c.flow, flow_fl(nbk, i, i - 2), c.epoch);
     flow_publish(c.flow, flow_fh(nbk, i, 0), c.epoch);
     flow_publish(c.flow, flow_fh(nbk, i, 2), c.epoch);
   }
@@ -658,14 +709,6 @@ __device__ __forceinline__ void flow_chain(FlowCtx& c, const BaDev& d, double la
 #pragma unroll
     for (int h = 0; h < 2; ++h) { const int u = 2 * (u0 + 256 * h); st2_sc1(dst, base + u, *reinterpret_cast<const f64x2*>(src + u)); }
   };
-  // preparation waves: the next row's hand-over blocks (and the operand tiles of L[r][r-3]) fetched one step ahead
-  f64x2 pf[3][2];
-  double pfb[8];
-  bool pf_ok = false;
-#pragma unroll
-  for (int t = 0; t < 3; ++t) { pf[t][0] = f64x2{0, 0}; pf[t][1] = f64x2{0, 0}; }
-#pragma unroll
-  for (int t = 0; t < 8; ++t) pfb[t] = 0;
   if (c.sred) {
     // Deferred reduce: D_0 is summed here, by all eight waves, straight into LDS -- no task, no flag, no second trip through memory
     // between the slabs and the first elimination.  Thread = (row, column pair): one 16-byte load per slab, all of them in flight.
@@ -708,8 +751,7 @@ __device__ __forceinline__ void flow_chain(FlowCtx& c, const BaDev& d, double la
     const double* Wprev = sm + FS_W + ((j & 1) ^ 1) * kBlk;
     double* LAcur = sm + FS_LA + (j & 1) * kBlk;
     const double* LAprev = sm + FS_LA + ((j & 1) ^ 1) * kBlk;
-    double* LBcur = sm + FS_LB + (j & 1) * kBlk;
-    const double* LBprev = sm + FS_LB + ((j & 1) ^ 1) * kBlk;
+    double* LB = sm + FS_LB;
     double* B0 = sm + FS_B, *B1 = sm + FS_B + kBlk, *B2 = sm + FS_B + 2 * kBlk;
     // X_j rows of the elimination: two buffers in turn (the preparation waves read step j's while the elimination waves are in step j+1)
     double(*Xm)[NB + 1] = reinterpret_cast<double(*)[NB + 1]>(sm + ((j & 1) ? FS_XM2 : FS_XM));
@@ -727,76 +769,64 @@ __device__ __forceinline__ void flow_chain(FlowCtx& c, const BaDev& d, double la
         for (int u = 0; u < 8; ++u) { const int k = 8 * gw + u; Xm[row][k] = (k >= row) ? cc[u] : 0.0; }
       }
     } else if (has_r) {
-      // ---- preparation of row r = j + 1 beside the elimination: wave 4 + s owns tile s of every product.  (Its 64-cycle matrix
-      // instructions share the SIMDs with the elimination waves and cost the elimination ~2 000 cycles per step; keeping a wave
-      // from issuing them while the elimination wave of its SIMD owns the pivot chain, or giving the work to the two waves whose
-      // SIMDs are idle after the first chain segments, only made the preparation the longer path: EXPERIMENTS.md.)
+      // ---- row r = j + 1 beside the elimination.  From row 3 on it arrives finished through column r-2 from its closer (which waits
+      // for W_j-1, announced behind the previous step's barrier, so there is nothing to fetch earlier than here) and is only
+      // copied into LDS: these waves issue no matrix instruction while the elimination runs -- a v_mfma_f64_16x16x4 holds its SIMD's
+      // FP64 pipe for 64 cycles and stalled the elimination wave of that SIMD, ~2 000 cycles per step (EXPERIMENTS.md).  Rows 1 and
+      // 2 have no closer: read from S and prepared here, wave 4 + s owning tile s of every product.
       const int u0 = tid - 256;
-      if (r >= 3 && !pf_ok) {
-        c.w.wait(flow_fh(nbk, r, 0), flow_fh(nbk, r, 1), flow_fh(nbk, r, 2));
+      f64x2 pf[2][2];
+      if (r >= 3) {
+        c.w.wait(flow_fh(nbk, r, 0), flow_fh(nbk, r, 2));
 #pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) pf[t][h] = ld2_sc1(c.red, red_blk_base(r, r - 2 + t) + 2 * (u0 + 256 * h));
-        op_sc1(c.red, red_blk_base(r, r - 3), sy, lr, lk, pfb);
+        for (int h = 0; h < 2; ++h) {
+          pf[0][h] = ld2_sc1(c.hand, (size_t)r * kBlk + 2 * (u0 + 256 * h));
+          pf[1][h] = ld2_sc1(c.red, red_blk_base(r, r) + 2 * (u0 + 256 * h));
+        }
       }
       if (stamp) { stamp[8 * j + 5] = __builtin_amdgcn_s_memtime(); stamp[384 + 8 * j + 1] = __builtin_amdgcn_s_memrealtime(); }
       flow_lds_wait(c2_done, j);            // step j-1 has read the last of B0..B2
       if (r >= 3) {
 #pragma unroll
-        for (int t = 0; t < 3; ++t)
+        for (int t = 0; t < 2; ++t)
 #pragma unroll
-          for (int h = 0; h < 2; ++h) *reinterpret_cast<f64x2*>(B0 + t * kBlk + 2 * (u0 + 256 * h)) = pf[t][h];
+          for (int h = 0; h < 2; ++h) *reinterpret_cast<f64x2*>(B1 + t * kBlk + 2 * (u0 + 256 * h)) = pf[t][h];
+        if (stamp) { stamp[256 + 8 * j + 0] = __builtin_amdgcn_s_memtime(); stamp[384 + 8 * j + 2] = __builtin_amdgcn_s_memrealtime(); }
       } else {
         flow_wait_S(c, r, 0, r);
         if (r == 2) ctile_st_lds(B0, coff, flow_ld_S(c, 2, 0, sx, sy));
         ctile_st_lds(B1, coff, flow_ld_S(c, r, r - 1, sx, sy));
         ctile_st_lds(B2, coff, flow_ld_S(c, r, r, sx, sy));
-      }
-      pf_ok = false;
-      if (stamp) { stamp[256 + 8 * j + 0] = __builtin_amdgcn_s_memtime(); stamp[384 + 8 * j + 2] = __builtin_amdgcn_s_memrealtime(); }
-      flow_group_sync(pctr, ptarget);
-      if (stamp) stamp[256 + 8 * j + 1] = __builtin_amdgcn_s_memtime();
-      f64x4 acc1 = {0, 0, 0, 0};
-      double a[8], b[8];
-      if (r >= 3) {
-        // (r, r-1) -= L[r][r-3] L[r-1][r-3]^T (kept in the accumulator until the second term is there)
-        op_lds(LBprev, sx, lr, lk, a);
-        mfma8(acc1, a, pfb);
-      }
-      if (r >= 2) {
-        // L[r][r-2]^T = W_j-1 T^T
-        op_lds(Wprev, sx, lr, lk, a);
-        op_lds(B0, sy, lr, lk, b);
-        f64x4 o = {0, 0, 0, 0};
-        mfma8(o, a, b);
-        ctile_st_lds(LBcur, coff, o);
-        ctile_st_sc1(c.red, red_blk_base(r, r - 2), coff, o);
-        if (stamp) stamp[256 + 8 * j + 3] = __builtin_amdgcn_s_memtime();
+        if (stamp) { stamp[256 + 8 * j + 0] = __builtin_amdgcn_s_memtime(); stamp[384 + 8 * j + 2] = __builtin_amdgcn_s_memrealtime(); }
         flow_group_sync(pctr, ptarget);
-        if (stamp) stamp[256 + 8 * j + 4] = __builtin_amdgcn_s_memtime();
-        // (r, r-1) -= L[r][r-2] L[r-1][r-2]^T ; (r, r) -= L[r][r-2] L[r][r-2]^T (lower tiles)
-        op_lds(LBcur, sy, lr, lk, b);
-        op_lds(LAprev, sx, lr, lk, a);
-        mfma8(acc1, a, b);
-        ctile_st_lds(B1, coff, ctile_ld_lds(B1, coff) - acc1);
-        if (gw != 2) {
-          op_lds(LBcur, sx, lr, lk, a);
-          f64x4 acc2 = {0, 0, 0, 0};
+        if (stamp) stamp[256 + 8 * j + 1] = __builtin_amdgcn_s_memtime();
+        if (r == 2) {
+          // L[2][0]^T = W_0 T^T
+          double a[8], b[8];
+          op_lds(Wprev, sx, lr, lk, a);
+          op_lds(B0, sy, lr, lk, b);
+          f64x4 o = {0, 0, 0, 0};
+          mfma8(o, a, b);
+          ctile_st_lds(LB, coff, o);
+          ctile_st_sc1(c.red, red_blk_base(2, 0), coff, o);
+          if (stamp) stamp[256 + 8 * j + 3] = __builtin_amdgcn_s_memtime();
+          flow_group_sync(pctr, ptarget);
+          if (stamp) stamp[256 + 8 * j + 4] = __builtin_amdgcn_s_memtime();
+          // (2, 1) -= L[2][0] L[1][0]^T ; (2, 2) -= L[2][0] L[2][0]^T (lower tiles)
+          f64x4 acc1 = {0, 0, 0, 0};
+          op_lds(LB, sy, lr, lk, b);
+          op_lds(LAprev, sx, lr, lk, a);
+          mfma8(acc1, a, b);
+          ctile_st_lds(B1, coff, ctile_ld_lds(B1, coff) - acc1);
+          if (gw != 2) {
+            op_lds(LB, sx, lr, lk, a);
+            f64x4 acc2 = {0, 0, 0, 0};
             mfma8(acc2, a, b);
-          ctile_st_lds(B2, coff, ctile_ld_lds(B2, coff) - acc2);
+            ctile_st_lds(B2, coff, ctile_ld_lds(B2, coff) - acc2);
+          }
         }
       }
       if (stamp) stamp[8 * j + 6] = __builtin_amdgcn_s_memtime();
-      // the next row's hand-over, if it is there already: its loads travel while the elimination finishes
-      if (r + 1 < nbk && r + 1 >= 3 && c.w.poll(flow_fh(nbk, r + 1, 0), flow_fh(nbk, r + 1, 1), flow_fh(nbk, r + 1, 2))) {
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) pf[t][h] = ld2_sc1(c.red, red_blk_base(r + 1, r - 1 + t) + 2 * (u0 + 256 * h));
-        op_sc1(c.red, red_blk_base(r + 1, r - 2), sy, lr, lk, pfb);
-        pf_ok = true;
-      }
     }
     __syncthreads();                                                  // B: X_j rows in Xm, row r prepared
     if (stamp) stamp[8 * j + 1] = __builtin_amdgcn_s_memtime();
@@ -850,7 +880,7 @@ __device__ __forceinline__ void flow_chain(FlowCtx& c, const BaDev& d, double la
       if (tid == 256 && !((d.debug & 8192) && j == 1)) {
         flow_publish(c.flow, flow_fw(nbk, j), c.epoch);
         flow_publish(c.flow, flow_fx(nbk, j, j), c.epoch);
-        if (has_r && r >= 2) flow_publish(c.flow, flow_fl(nbk, r, r - 2), c.epoch);      // stored by the preparation above, drained here
+        if (r == 2 && has_r) flow_publish(c.flow, flow_fl(nbk, 2, 0), c.epoch);      // stored by the preparation above, drained here
         if (stamp) stamp[384 + 8 * j + 3] = __builtin_amdgcn_s_memrealtime();
       }
       if (!has_r) break;
@@ -870,7 +900,7 @@ __global__ __launch_bounds__(512) void ba_chol_flow_kernel(BaDev d, unsigned* fl
   extern __shared__ __attribute__((aligned(16))) double flow_sm[];
   const int tid = threadIdx.x;
   FlowCtx c;
-  c.red = flow_buf(d.red); c.xinv = flow_buf(d.xinv); c.ldiag = flow_buf(d.ldiag);
+  c.red = flow_buf(d.red); c.xinv = flow_buf(d.xinv); c.ldiag = flow_buf(d.ldiag); c.hand = flow_buf(d.flow_hand);
   c.redp = d.red; c.rhs = d.red + red_rhs_off(d.nbk);
   c.flow = flow; c.nbk = d.nbk;
   c.epoch = __hip_atomic_load(flow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
@@ -955,8 +985,11 @@ inline std::vector<FlowTask> flow_build_tasks(int nbk, int V = 0) {
         }
   }
   for (int i = 3; i < nbk; ++i) {
-    t.push_back(FlowTask{FLOW_CLOSER, i, i - 3, 64 * (i - 3) + 40});
     t.push_back(FlowTask{FLOW_H1, i, i - 1, 64 * std::max(0, i - 4) + 48});      // after the block (i, i-4) of the same column
+    // The closer reads the hand-over task's block of its own row and the blocks of the closer of row i-1; the hand-over task of row i+1
+    // (same key: the stable sort keeps this order) reads the closer's L[i][i-3].  Once taken the closer stays until W_i-2: of column i-3
+    // the chain needs nothing before that but the closer of row i-1, which is ahead.
+    t.push_back(FlowTask{FLOW_CLOSER, i, i - 3, 64 * (i - 3) + 48});
     for (int k = 0; k <= i - 4; ++k) t.push_back(FlowTask{FLOW_T1, i, k, 64 * k + 44});
   }
   for (int k = 0; k < nbk; ++k) t.push_back(FlowTask{FLOW_RHS, 0, k, 64 * k + 52});

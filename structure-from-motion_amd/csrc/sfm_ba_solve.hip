@@ -780,7 +780,7 @@ static int flow_task_table(int key, int nbk, int V, const void** table, int* nta
 }
 
 // Workgroups of the data-flow launch on n_cus compute units: the chain and at least one, at most n_tasks task workgroups.  The ticket
-// scheme needs the chain and ONE task workgroup resident, nothing more; every workgroup owns a CU (121 KB of LDS), so there are at
+// scheme needs the chain and ONE task workgroup resident, nothing more; every workgroup owns a CU (113 KB of LDS), so there are at
 // most n_cus of them, and from 41 CUs on 32 are left to whatever else the device runs (the next problem's linearisation on another
 // stream).  Below 2 CUs there is no such launch: ba_flow_setup leaves the problem on the column steps.
 static int flow_grid(int n_cus, int n_tasks) {
@@ -795,7 +795,7 @@ int ba_flow_setup(BaScene& sc, hipStream_t s) {
   // field switch: SFM_FLOW_SOLVE=0 keeps every problem on the column-step launches (what SFM_OPT_DEBUG bit 1024 does per handle)
   static const bool enabled = [] { const char* e = getenv("SFM_FLOW_SOLVE"); return !(e && atoi(e) == 0); }();
   if (!enabled) return SFM_OK;
-  // a device that refuses the launch its 121 KB of LDS keeps every problem on the column steps, which need none of it
+  // a device that refuses the launch its 113 KB of LDS keeps every problem on the column steps, which need none of it
   static int attr_device = -1;
   static bool attr_ok = false;
   if (attr_device != ctx().device) {
@@ -807,6 +807,7 @@ int ba_flow_setup(BaScene& sc, hipStream_t s) {
   SFM_TRY(flow_task_table(d.nbk, d.nbk, 0, &d.flow_tasks, &d.flow_ntasks));
   SFM_TRY(flow_task_table(1000 + d.V, d.nbk, d.V, &sc.flow_tasks_red, &sc.flow_ntasks_red));
   SFM_TRY(scene_alloc(sc, sc.flow_camsum, 4 * 35 * (size_t)d.V));
+  SFM_TRY(scene_alloc(sc, d.flow_hand, (size_t)d.nbk * kBlk));
   SFM_TRY(scene_alloc(sc, d.flow, flow_words(d.nbk)));
   SFM_HIP(hipMemsetAsync(d.flow, 0, sizeof(unsigned) * flow_words(d.nbk), s));
   return SFM_OK;

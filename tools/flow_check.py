@@ -31,7 +31,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "stamps":
             j, pr[j, 5] - el[j, 0], pd[j, 0] - el[j, 0], pd[j, 1] - el[j, 0], pd[j, 3] - el[j, 0], pd[j, 4] - el[j, 0], pr[j, 6] - el[j, 0]))
     print("chain total ticks", el[10, 2] - t0, " kernel entry -> D_0 in LDS, first step starts:", t0 - el[0, 5])
     rt = raw[896:1024].reshape(16, 8)      # chain, constant 100 MHz clock (s_memrealtime): [0] step start, [1] preparation starts, [2] row in LDS, [3] W_j announced, [4] L[j+1][j] announced
-    cl = raw[640:768].reshape(16, 8)       # closer of row i, same clock: [0] start, [6] last term of the sums there, [1] sums done, [5] W seen, [2] L[i-2][k] seen, [3] L formed, [4] hand-over announced
+    cl = raw[640:768].reshape(16, 8)       # closer of row i, same clock: [0] start, [6] last term of the sums there, [1] sums done, [5] W seen, [2] L[i-2][k] seen, [3] L[i][i-3] formed and announced, [7] W_i-2 seen, [4] hand-over (through column i-2) announced
     t1 = raw[128:256].reshape(16, 8)       # task L[i][i-4], same clock: [0] start, [1] sum done, [2] W seen, [3] announced
     r0 = rt[0, 0]
     if t1[0, 0]:      # deferred reduce: the way to D_0 (us since the chain workgroup's entry)
@@ -42,9 +42,9 @@ if len(sys.argv) > 1 and sys.argv[1] == "stamps":
     print("cross-workgroup timeline, us on the 100 MHz clock since the chain's first step")
     for i in range(4, 11):
         k = i - 3
-        print("  row %2d | chain: W_%d announced %6.2f, W_%d announced %6.2f, L[%d][%d] announced %6.2f | task L[%d][%d]: sum done %6.2f, W_%d seen %6.2f, announced %6.2f | closer: last term there %6.2f, sums done %6.2f, W_%d seen %6.2f, L seen %6.2f, L formed %6.2f, hand-over announced %6.2f | chain step %d: start %6.2f, preparation starts %6.2f, row in LDS %6.2f" % (
+        print("  row %2d | chain: W_%d announced %6.2f, W_%d announced %6.2f, L[%d][%d] announced %6.2f | task L[%d][%d]: sum done %6.2f, W_%d seen %6.2f, announced %6.2f | closer: last term there %6.2f, sums done %6.2f, W_%d seen %6.2f, L seen %6.2f, L formed %6.2f, W_%d seen %6.2f, hand-over announced %6.2f | chain step %d: start %6.2f, preparation starts %6.2f, row in LDS %6.2f" % (
             i, k - 1, us(rt[k - 1, 3]), k, us(rt[k, 3]), k + 1, k, us(rt[k, 4]), i, k - 1, us(t1[i, 1]), k - 1, us(t1[i, 2]), us(t1[i, 3]),
-            us(cl[i, 6]), us(cl[i, 1]), k, us(cl[i, 5]), us(cl[i, 2]), us(cl[i, 3]), us(cl[i, 4]), i - 1, us(rt[i - 1, 0]), us(rt[i - 1, 1]), us(rt[i - 1, 2])))
+            us(cl[i, 6]), us(cl[i, 1]), k, us(cl[i, 5]), us(cl[i, 2]), us(cl[i, 3]), k + 1, us(cl[i, 7]), us(cl[i, 4]), i - 1, us(rt[i - 1, 0]), us(rt[i - 1, 1]), us(rt[i - 1, 2])))
     sys.exit(0)
 
 oracle = importlib.import_module("sfm_oracle")
