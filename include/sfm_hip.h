@@ -1542,6 +1542,54 @@ int sfm_link_tracks_dev(int V, const int* key_ptr /*host*/, int P, const int* pa
  * kernel | grid of the pass over components beyond 64 members | prefix-sum route over the K keys (1 one workgroup, 2
  * device-wide) | its tiles | route over the K / 2 components | its tiles.  Grids follow sfm_set_cu_limit. */
 int sfm_link_tracks_plan(int V, int64_t K, int64_t M, int group, int scan, int* plan /*[8]*/);
+
+/* ---- view triplets: the cycle-consistency filter of a view graph -------------------------------------------------------
+ * The graph is that of the rotation averaging: V views, E edges (i_e, j_e, Rel_e[9]), i_e != j_e, parallel edges allowed,
+ * R_j = Rel_e R_i, row-major.  Around every triangle of the graph the three relative rotations must compose to the
+ * identity; a wrong edge breaks every triangle it lies in.  edge_mask[E] optional bytes (0 excludes an edge; NULL: none is
+ * excluded).  The rule:
+ *   1. Oriented edge.  For edge e with ends lo < hi: M_e (frame lo -> frame hi) is Rel_e if i_e = lo, otherwise its
+ *      transpose: a copy of entries, exact.
+ *   2. Triplet.  Three edges (e_ab, e_bc, e_ac) over three distinct views a < b < c, e_ab joining a and b and so on.  Every
+ *      combination of parallel edges is a triplet of its own: two parallel edges on each side give eight.  A masked edge is
+ *      in no triplet.
+ *   3. The test is rotation_edge_inlier(Ri = M_ab, Rj = M_ac, Rel = M_bc, thr) of csrc/sfm_obs_test.h, unchanged (step 1 of
+ *      the rotation averaging): P = M_bc M_ab in that function's fma order, lhs = trace(M_ac^T P) in its order.  The triplet
+ *      is CONSISTENT iff lhs is finite and lhs >= fma(2, cos_loop, 1); cos_loop, in (0, 1], is the cosine of the largest
+ *      admitted loop angle.  A triplet's bits depend on the triplet alone, whichever edge or lane finds it.
+ *      sfm_view_triplet_test is the host entry.
+ *   4. Per-edge counts (int64): n_tri[e] the number of triplets that hold e, n_ok[e] the consistent ones among them.
+ *   5. Verdict edge_keep[e], all in integers: a masked edge gets 0; an edge with n_tri = 0 is UNTESTED and gets
+ *      keep_untested (0 or 1); otherwise 1 iff n_ok >= min_ok (min_ok >= 1; 0 means 1) and 100 * n_ok >= min_pct * n_tri
+ *      (min_pct in 0 .. 100; 64-bit products).
+ *   6. Outputs, all optional.  edge_keep[E] (bytes), n_tri[E], n_ok[E].  kept_idx[E] (int32) with *n_kept (host): the
+ *      ascending edge numbers with edge_keep = 1, by a prefix sum -- what the caller compacts `edges` and `rel` with; only
+ *      its first *n_kept entries are written.  summary[8] (int64): triplets | consistent triplets | edges tested | kept |
+ *      dropped though tested | untested | masked | the largest n_tri.
+ *   7. Argument errors (SFM_E_SHAPE, found before a device is looked for, nothing launched, outputs untouched): V < 3, E < 1,
+ *      E >= 2^30 (the 2 E edge ends are numbered by an int), an index out of range, i == j, cos_loop NaN or outside (0, 1],
+ *      min_ok < 0, min_pct outside 0 .. 100, keep_untested not 0 or 1, a bad `group`, a null `edges` or `rel`.  Each Rel_e
+ *      must pass verify_rotation: SFM_E_BAD_ROTATION, sfm_last_error naming the lowest such edge (the _dev form finds it
+ *      with one kernel, before anything else is launched).
+ * The definition does not depend on the order of edges, lanes, launches or timing: any enumeration that reaches it gives
+ * the same bits.  How: the view-major adjacency sorted by (view, neighbour, edge) -- two stable passes of the key-major list,
+ * the other end first -- then a group of `group` lanes per edge (0 = automatic; 1, 4 .. 64) that strides over the shorter
+ * adjacency of the edge's ends and looks every neighbour up in the longer one by binary search.  Every edge enumerates all
+ * its triplets, so a triplet is tested three times, always in the order of step 3, and there is no atomic on the way to
+ * n_tri and n_ok; the summary uses 64-bit integer atomics.  No floating-point sum at all: the bits do not depend on `group`.
+ * sfm_view_triplets takes host arrays and blocks.  sfm_view_triplets_dev takes d_rel, d_edge_mask and every output array on
+ * the device and a stream (NULL = the library stream); `edges` stays a HOST array, as in the two averaging calls.  The host
+ * reads the verify word and *n_kept (host, may be NULL) and nothing else; it returns when the work is done. */
+int sfm_view_triplets(int V, int64_t E, const int* edges /*[E][2]*/, const double* rel /*[E][9]*/,
+                      const unsigned char* edge_mask /*[E] or NULL*/, double cos_loop, int min_ok, int min_pct, int keep_untested,
+                      int group, unsigned char* edge_keep /*[E]*/, int64_t* n_tri /*[E]*/, int64_t* n_ok /*[E]*/,
+                      int* kept_idx /*[E]*/, int64_t* summary /*[8]*/, int* n_kept);
+int sfm_view_triplets_dev(int V, int64_t E, const int* edges /*host [E][2]*/, const double* d_rel, const unsigned char* d_edge_mask,
+                          double cos_loop, int min_ok, int min_pct, int keep_untested, int group, unsigned char* d_edge_keep,
+                          int64_t* d_n_tri, int64_t* d_n_ok, int* d_kept_idx, int64_t* d_summary, int* n_kept /*host*/,
+                          void* hip_stream);
+/* Step 3 on the host, by the function the kernels run: 1 for a consistent triplet, *lhs_out (may be NULL) the trace. */
+int sfm_view_triplet_test(const double Mab[9], const double Mbc[9], const double Mac[9], double cos_loop, double* lhs_out);
 /* The resident scene moved by X' = s A X + t, on the device: every point by the formula, every camera block [C, q] to
  * C' = s A C + t and q' = q(A R(q)), the library's canonical quaternion of the product (qw >= 0, not renormalised).
  * Refused before any launch: s not finite or not positive (SFM_E_SHAPE), A failing verify_rotation

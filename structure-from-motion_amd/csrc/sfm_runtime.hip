@@ -304,7 +304,7 @@ using namespace sfm;
 
 extern "C" {
 
-int sfm_version(void) { return 110; }
+int sfm_version(void) { return 111; }
 
 const char* sfm_last_error(void) { return g_err; }
 

@@ -86,6 +86,9 @@ LINK_SUMMARY = ("matches_used", "components", "tracks", "conflicts", "short", "o
 LINK_OUTPUTS = ("key_track", "pt_ptr", "cam_idx", "key_idx", "summary", "label")
 LINK_PLAN = ("union_grid", "group", "order_grid", "big_grid", "scan_keys", "tiles_keys", "scan_components", "tiles_components")
 LINK_SCAN_AUTO, LINK_SCAN_ONE_BLOCK, LINK_SCAN_DEVICE = 0, 1, 2
+TRIPLET_SUMMARY = ("triplets", "triplets_consistent", "edges_tested", "edges_kept", "edges_dropped", "edges_untested", "edges_masked",
+                   "largest_n_tri")
+TRIPLET_OUTPUTS = ("edge_keep", "n_tri", "n_ok", "kept_idx", "summary")
 POSE_FROM_F, POSE_FROM_H = 0, 1
 POSE_EMPTY, POSE_NO_MODEL, POSE_NO_POSE, POSE_TIED, POSE_NO_PARALLAX = 1, 2, 4, 8, 16
 POSE_CANDIDATES = 4
@@ -306,6 +309,10 @@ SIGNATURES = {
     "sfm_link_tracks_dev": [ci, _ip, ci, _ip, _lp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, _ip, _lp, vp],
     "sfm_link_tracks_plan": [ci, i64, i64, ci, ci, _ip],
     "sfm_link_tracks_views": [vp, ci, _ip, ctypes.POINTER(ctypes.c_uint8), ci, vp, _lp],
+    "sfm_view_triplets": [ci, i64, _ip, _dp, ctypes.POINTER(ctypes.c_uint8), cd, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_uint8), _lp, _lp,
+                          _ip, _lp, _ip],
+    "sfm_view_triplets_dev": [ci, i64, _ip, vp, vp, cd, ci, ci, ci, ci, vp, vp, vp, vp, vp, _ip, vp],
+    "sfm_view_triplet_test": [_dp, _dp, _dp, cd, _dp],
     "sfm_ba_transform": [vp, cd, _dp, _dp],
     "sfm_ba_align": [vp, ci, _ip, _dp, cd, ci, ci, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip],
     "sfm_twoview_pose": [ci, _ip, i64, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _dp, _dp, cd, ci, _dp, _dp, _dp, _ip, _ip, _ip,
@@ -1185,6 +1192,108 @@ def rotation_average_dev(n_views, edges, d_rel, root=0, cos_max=None, max_hyp=0,
                                           int(iters), int(steps), float(cg_tol), int(cg_max), _vp(d_R_out), _vp(d_edge_inlier),
                                           _vp(d_edge_cos), _vp(d_view_status), _vp(d_n_inliers), _vp(d_best_hyp), _vp(d_status),
                                           _vp(d_summary), _vp(stream)))
+
+
+# ---- view triplets: the cycle-consistency filter of a view graph (sfm_view_triplet*; no reference counterpart) ----------
+def check_view_triplets(n_views, edges, rel, edge_mask=None, cos_loop=1.0, min_ok=1, min_pct=0, keep_untested=0, group=0):
+    """The arguments of a ``view_triplets`` call, without a device: ``(n_views, edges int32 (E, 2), rel (E, 9), edge_mask uint8
+    (E,) or None, cos_loop, min_ok, min_pct, keep_untested, group)`` converted or ValueError -- everything sfm_view_triplets
+    refuses, in its order; a ``Rel`` that is no rotation raises the ValueError of the library's verify_rotation and names the
+    edge."""
+    def integer(name, value):
+        if isinstance(value, bool) or int(value) != value:
+            raise ValueError("%s must be an integer, got %r" % (name, value))
+        return int(value)
+    n_views, min_ok, min_pct, group = integer("n_views", n_views), integer("min_ok", min_ok), integer("min_pct", min_pct), integer("group", group)
+    keep_untested = int(keep_untested) if isinstance(keep_untested, (bool, np.bool_)) else integer("keep_untested", keep_untested)
+    cos_loop = float(cos_loop)
+    edges_in = np.asarray(edges)
+    if edges_in.ndim != 2 or edges_in.shape[1] != 2 or (edges_in.size and not np.all(edges_in == np.floor(edges_in))):
+        raise ValueError("edges must be integers of shape (E, 2), got %r" % (edges_in.shape,))
+    rel = f64(rel)
+    n_edges = edges_in.shape[0]
+    if rel.size != 9 * n_edges or rel.ndim not in (2, 3):
+        raise ValueError("rel must be (E, 9) or (E, 3, 3) with E = %d, got %r" % (n_edges, rel.shape))
+    rel = rel.reshape(n_edges, 9)
+    if edge_mask is not None:
+        edge_mask = np.ascontiguousarray(np.asarray(edge_mask).reshape(-1) != 0, dtype=np.uint8)
+        if edge_mask.shape[0] != n_edges:
+            raise ValueError("edge_mask must have E = %d entries, got %d" % (n_edges, edge_mask.shape[0]))
+    if n_views < 3 or n_edges < 1 or n_edges >= 2 ** 30:
+        raise ValueError("bad sizes V=%d E=%d (V >= 3, 1 <= E < 2^30)" % (n_views, n_edges))
+    if not (0.0 < cos_loop <= 1.0):
+        raise ValueError("cos_loop = %r must be in (0, 1]" % cos_loop)
+    if min_ok < 0:
+        raise ValueError("min_ok = %d must be >= 1 (0 = 1)" % min_ok)
+    if not 0 <= min_pct <= 100:
+        raise ValueError("min_pct = %d must be in 0 .. 100" % min_pct)
+    if keep_untested not in (0, 1):
+        raise ValueError("keep_untested = %d must be 0 or 1" % keep_untested)
+    if group not in (0, 1, 4, 8, 16, 32, 64):
+        raise ValueError("group %d is not one of 0, 1, 4, 8, 16, 32, 64" % group)
+    bad = (edges_in < 0) | (edges_in >= n_views)
+    bad = bad[:, 0] | bad[:, 1] | (edges_in[:, 0] == edges_in[:, 1])
+    if bad.any():
+        e = int(np.argmax(bad))
+        raise ValueError("edge %d = (%d, %d) must join two different views in 0 .. %d" % (e, edges_in[e, 0], edges_in[e, 1], n_views - 1))
+    edges = np.ascontiguousarray(edges_in, dtype=np.int32)
+    bad = ~_verify_rotations(rel)
+    if bad.any():
+        raise ValueError("convert_quaternion_to_rotation : Invalid output rotation matrix (Rel of edge %d is not a rotation)"
+                         % int(np.argmax(bad)))
+    return n_views, edges, rel, edge_mask, cos_loop, min_ok, min_pct, keep_untested, group
+
+
+def view_triplet_test(M_ab, M_bc, M_ac, cos_loop):
+    """``(consistent, lhs)`` of one triplet of oriented edges over views ``a < b < c`` (sfm_view_triplet_test; host only):
+    ``lhs`` is the trace of ``M_ac^T M_bc M_ab`` in the library's operation order, consistent iff it is finite and
+    ``>= fma(2, cos_loop, 1)``."""
+    M_ab, M_bc, M_ac = f64(M_ab).reshape(9), f64(M_bc).reshape(9), f64(M_ac).reshape(9)
+    lhs = np.zeros(1)
+    ok = load().sfm_view_triplet_test(dptr(M_ab), dptr(M_bc), dptr(M_ac), float(cos_loop), dptr(lhs))
+    return bool(ok), float(lhs[0])
+
+
+def view_triplets(n_views, edges, rel, edge_mask=None, cos_loop=None, min_ok=1, min_pct=0, keep_untested=0, group=0, max_loop_deg=5.0,
+                  outputs=TRIPLET_OUTPUTS):
+    """The triplet filter of a view graph (sfm_view_triplets): around every triangle the three relative rotations must
+    compose to the identity within a loop angle whose cosine is at least ``cos_loop`` (default: that of ``max_loop_deg``).
+    An edge is kept iff at least ``min_ok`` and ``min_pct`` per cent of its triplets are consistent; an edge in no triplet
+    gets ``keep_untested``.  Returns ``edge_keep (E,) uint8, n_tri (E,) int64, n_ok (E,) int64, kept_idx (n_kept,) int32,
+    summary (8,) int64`` in the order of ``TRIPLET_SUMMARY``; an output not named in ``outputs`` is not fetched and comes back
+    as None."""
+    if cos_loop is None:
+        cos_loop = float(np.cos(np.deg2rad(float(max_loop_deg))))
+    V, edges, rel, edge_mask, cos_loop, min_ok, min_pct, keep_untested, group = check_view_triplets(
+        n_views, edges, rel, edge_mask, cos_loop, min_ok, min_pct, keep_untested, group)
+    unknown = set(outputs) - set(TRIPLET_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (TRIPLET_OUTPUTS, sorted(unknown)))
+    E = edges.shape[0]
+    o = {"edge_keep": np.zeros(E, dtype=np.uint8), "n_tri": np.zeros(E, dtype=np.int64), "n_ok": np.zeros(E, dtype=np.int64),
+         "kept_idx": np.full(E, -1, dtype=np.int32), "summary": np.zeros(8, dtype=np.int64)}
+    w = {k: (v if k in outputs else None) for k, v in o.items()}
+    n_kept = np.zeros(1, dtype=np.int32)
+    check(load().sfm_view_triplets(V, E, iptr(edges), dptr(rel), _u8ptr(edge_mask), cos_loop, min_ok, min_pct, keep_untested, group,
+                                   _u8ptr(w["edge_keep"]), _lptr(w["n_tri"]), _lptr(w["n_ok"]), iptr(w["kept_idx"]),
+                                   _lptr(w["summary"]), iptr(n_kept)))
+    if w["kept_idx"] is not None:
+        w["kept_idx"] = w["kept_idx"][:int(n_kept[0])].copy()
+    return tuple(w[name] for name in TRIPLET_OUTPUTS)
+
+
+def view_triplets_dev(n_views, edges, d_rel, d_edge_mask=0, cos_loop=None, min_ok=1, min_pct=0, keep_untested=0, group=0,
+                      max_loop_deg=5.0, d_edge_keep=0, d_n_tri=0, d_n_ok=0, d_kept_idx=0, d_summary=0, stream=0):
+    """``view_triplets`` with ``d_rel`` (E, 9), ``d_edge_mask`` and the outputs as device pointers and a caller's stream
+    (sfm_view_triplets_dev); ``edges`` stays a host array, optional arrays are 0.  Returns ``n_kept``."""
+    if cos_loop is None:
+        cos_loop = float(np.cos(np.deg2rad(float(max_loop_deg))))
+    edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+    n_kept = np.zeros(1, dtype=np.int32)
+    check(load().sfm_view_triplets_dev(int(n_views), edges.shape[0], iptr(edges), _vp(d_rel), _vp(d_edge_mask), float(cos_loop), int(min_ok),
+                                       int(min_pct), int(keep_untested), int(group), _vp(d_edge_keep), _vp(d_n_tri), _vp(d_n_ok),
+                                       _vp(d_kept_idx), _vp(d_summary), iptr(n_kept), _vp(stream)))
+    return int(n_kept[0])
 
 
 # ---- translation averaging over a view graph (sfm_translation_*; no reference counterpart) ------------------------------

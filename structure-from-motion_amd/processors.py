@@ -430,21 +430,10 @@ class HipCamposeMixin:
         centre = np.zeros(3) if pair_centre is None else np.asarray(pair_centre, dtype=np.float64).reshape(3)
         return s, A, t.reshape(3, 1), np.flatnonzero(inlier).tolist(), A @ rot, (s * (A @ centre) + t).reshape(3, 1)
 
-    def average_rotations(self, pair_results, n_views, root=0, max_angle_deg=5.0, max_hyp=128, iteration=2):
-        """Absolute rotations of ``n_views`` views from the relative poses of their verified pairs (one
-        ``native.rotation_average``; no reference counterpart).  ``pair_results`` holds one entry per pair: a triple
-        ``(ref, que, R)`` with ``X_que = R X_ref + t``, or a dict ``initialise_pairs`` returned to which the caller added the
-        view indices as ``"ref"`` and ``"que"``.  A pair without a pose (``R`` None or all zeros; a dict with
-        ``best_cand < 0`` or ``native.POSE_NO_POSE``) is skipped.  An edge counts as consistent while its residual angle is at
-        most ``max_angle_deg``; ``max_hyp`` spanning trees are scored and ``iteration`` refit rounds of two Gauss-Newton
-        steps follow.
-
-        Returns ``rots, verdict``: ``rots`` is a list of ``n_views`` (3, 3) matrices in the reference's convention
-        (``rot = R_v^T``, projection ``K [rot^T | -rot^T centre]``; the identity for ``root``, None for a view without a
-        rotation) and ``verdict`` a dict with ``pairs`` (the index into ``pair_results`` of every edge), ``edge_inlier``,
-        ``edge_cos``, ``view_status``, ``n_inliers``, ``best_hyp``, ``status`` and ``summary``.  ``rotation_last`` keeps it."""
-        if not 0.0 <= float(max_angle_deg) < 90.0:
-            raise ValueError("max_angle_deg must be in [0, 90), got {!r}".format(max_angle_deg))
+    @staticmethod
+    def _rotation_edges(pair_results, who):
+        """``edges (E, 2) int32, rel (E, 9), used``: the posed entries of ``pair_results`` as the edges of a view graph;
+        ``used[e]`` is the entry of edge ``e``."""
         edges, rel, used = [], [], []
         for k, entry in enumerate(pair_results):
             if isinstance(entry, dict):
@@ -459,14 +448,78 @@ class HipCamposeMixin:
             rel.append(np.asarray(R, dtype=np.float64).reshape(9))
             used.append(k)
         if not edges:
-            raise ValueError("average_rotations: no pair with a pose")
+            raise ValueError("{}: no pair with a pose".format(who))
+        return np.array(edges, dtype=np.int32), np.array(rel), used
+
+    def filter_view_graph(self, pair_results, n_views, max_loop_deg=5.0, min_ok=1, min_pct=0, keep_untested=False):
+        """The triplet filter over the relative poses of verified pairs (one ``native.view_triplets``; no reference
+        counterpart): around every triangle of the view graph the three relative rotations must compose to the identity
+        within ``max_loop_deg``.  ``pair_results`` holds the entries ``average_rotations`` takes, and a pair without a pose is
+        skipped exactly as there.  A pair is kept iff at least ``min_ok`` and ``min_pct`` per cent of its triangles are
+        consistent; a pair in no triangle gets ``keep_untested``.
+
+        Returns ``keep, verdict``: ``keep`` one bool per entry of ``pair_results`` (False without a pose) and ``verdict`` a
+        dict with ``pairs`` (the index into ``pair_results`` of every edge), ``edge_keep``, ``n_tri``, ``n_ok``, ``kept_idx``
+        (all per edge) and ``summary`` (a dict over ``native.TRIPLET_SUMMARY``).  ``triplets_last`` keeps it."""
+        edges, rel, used = self._rotation_edges(pair_results, "filter_view_graph")
+        verdict = self._filter_edges(edges, rel, used, n_views, max_loop_deg, min_ok, min_pct, keep_untested)
+        keep = np.zeros(len(pair_results), dtype=bool)
+        keep[np.asarray(used, dtype=np.int64)[verdict["kept_idx"]]] = True
+        return keep, verdict
+
+    def _filter_edges(self, edges, rel, used, n_views, max_loop_deg=5.0, min_ok=1, min_pct=0, keep_untested=False):
+        """The verdict dict of ``filter_view_graph`` for the edges ``_rotation_edges`` made."""
+        if not 0.0 <= float(max_loop_deg) < 90.0:
+            raise ValueError("max_loop_deg must be in [0, 90), got {!r}".format(max_loop_deg))
+        edge_keep, n_tri, n_ok, kept_idx, summary = native.view_triplets(
+            n_views, edges, rel, max_loop_deg=float(max_loop_deg), min_ok=min_ok, min_pct=min_pct, keep_untested=int(bool(keep_untested)))
+        verdict = dict(pairs=used, edge_keep=edge_keep.astype(bool), n_tri=n_tri, n_ok=n_ok, kept_idx=kept_idx,
+                       summary=dict(zip(native.TRIPLET_SUMMARY, (int(v) for v in summary))))
+        self.triplets_last = verdict
+        return verdict
+
+    def average_rotations(self, pair_results, n_views, root=0, max_angle_deg=5.0, max_hyp=128, iteration=2, triplets=None):
+        """Absolute rotations of ``n_views`` views from the relative poses of their verified pairs (one
+        ``native.rotation_average``; no reference counterpart).  ``pair_results`` holds one entry per pair: a triple
+        ``(ref, que, R)`` with ``X_que = R X_ref + t``, or a dict ``initialise_pairs`` returned to which the caller added the
+        view indices as ``"ref"`` and ``"que"``.  A pair without a pose (``R`` None or all zeros; a dict with
+        ``best_cand < 0`` or ``native.POSE_NO_POSE``) is skipped.  An edge counts as consistent while its residual angle is at
+        most ``max_angle_deg``; ``max_hyp`` spanning trees are scored and ``iteration`` refit rounds of two Gauss-Newton
+        steps follow.  ``triplets`` is None or a dict of the options of ``filter_view_graph`` (``max_loop_deg``, ``min_ok``,
+        ``min_pct``, ``keep_untested``): the filter runs first and the averaging sees the kept edges only.
+
+        Returns ``rots, verdict``: ``rots`` is a list of ``n_views`` (3, 3) matrices in the reference's convention
+        (``rot = R_v^T``, projection ``K [rot^T | -rot^T centre]``; the identity for ``root``, None for a view without a
+        rotation) and ``verdict`` a dict with ``pairs`` (the index into ``pair_results`` of every edge), ``edge_inlier``,
+        ``edge_cos``, ``view_status``, ``n_inliers``, ``best_hyp``, ``status`` and ``summary``.  With ``triplets`` the edges are
+        still all posed pairs: an edge the filter dropped has ``edge_inlier`` False and ``edge_cos`` NaN, and
+        ``verdict["triplets"]`` is the filter's verdict over the same edges.  ``rotation_last`` keeps it."""
+        if not 0.0 <= float(max_angle_deg) < 90.0:
+            raise ValueError("max_angle_deg must be in [0, 90), got {!r}".format(max_angle_deg))
+        edges, rel, used = self._rotation_edges(pair_results, "average_rotations")
+        filtered = None
+        if triplets is not None:
+            unknown = set(triplets) - {"max_loop_deg", "min_ok", "min_pct", "keep_untested"}
+            if unknown:
+                raise ValueError("average_rotations: unknown triplets options {!r}".format(sorted(unknown)))
+            filtered = self._filter_edges(edges, rel, used, n_views, **triplets)
+            kept = filtered["kept_idx"]
+            if kept.size == 0:
+                raise ValueError("average_rotations: the triplet filter kept no pair")
+            all_edges, edges, rel = edges, edges[kept], rel[kept]
         R, edge_inlier, edge_cos, view_status, n_inliers, best_hyp, status, summary = native.rotation_average(
-            n_views, np.array(edges, dtype=np.int32), np.array(rel), root=root, max_angle_deg=float(max_angle_deg), max_hyp=max_hyp,
-            iters=iteration, steps=2)
+            n_views, edges, rel, root=root, max_angle_deg=float(max_angle_deg), max_hyp=max_hyp, iters=iteration, steps=2)
         has = (view_status & native.ROTAVG_UNREACHED) == 0 if not status & native.ROTAVG_NO_MODEL else np.zeros(int(n_views), dtype=bool)
         rots = [R[v].T.copy() if has[v] else None for v in range(int(n_views))]
-        verdict = dict(pairs=used, edge_inlier=edge_inlier.astype(bool), edge_cos=edge_cos, view_status=view_status, n_inliers=n_inliers,
+        edge_inlier = edge_inlier.astype(bool)
+        if filtered is not None:
+            full_inlier, full_cos = np.zeros(all_edges.shape[0], dtype=bool), np.full(all_edges.shape[0], np.nan)
+            full_inlier[kept], full_cos[kept] = edge_inlier, edge_cos
+            edge_inlier, edge_cos = full_inlier, full_cos
+        verdict = dict(pairs=used, edge_inlier=edge_inlier, edge_cos=edge_cos, view_status=view_status, n_inliers=n_inliers,
                        best_hyp=best_hyp, status=status, summary=summary)
+        if filtered is not None:
+            verdict["triplets"] = filtered
         self.rotation_last = verdict
         return rots, verdict
 
@@ -2167,13 +2220,14 @@ def pose_pairs(tracker, ref_idx, que_idx, model, kind, K_left, K_right, inlier=N
 
 
 def orient_views(tracker, pairs, K, K_right=None, root=0, max_sampson_px=2.0, max_hyp=128, iteration=2, min_angle_deg=2.0,
-                 min_parallax=8, max_angle_deg=5.0, tree_hyp=128, rounds=2):
+                 min_parallax=8, max_angle_deg=5.0, tree_hyp=128, rounds=2, triplets=None):
     """Absolute rotations of the views of a ``HipDeviceKeyTracker`` from the listed ``pairs`` ``(ref_idx, que_idx)``: per
     pair ONE ``verify_pairs`` and, where it has a model, ONE ``pose_pairs`` from that model with its inliers voting (no
     coordinate comes down), then ONE ``HipCamposeMixin.average_rotations`` over the poses found.  Returns ``rots, verdict,
     poses``: the first two as ``average_rotations`` returns them (``verdict["pairs"]`` indexes ``pairs``), ``poses`` one dict
-    per listed pair (``R``, ``t``, ``status`` of the pose call, ``twoview_status``; ``R`` is None without a pose).  A
-    function of the module, like ``verify_pairs``; ``process()`` does not call it."""
+    per listed pair (``R``, ``t``, ``status`` of the pose call, ``twoview_status``; ``R`` is None without a pose).
+    ``triplets`` (None, or a dict of the options of ``filter_view_graph``) puts the triplet filter in front of the averaging,
+    as ``average_rotations`` describes.  A function of the module, like ``verify_pairs``; ``process()`` does not call it."""
     K_right = K if K_right is None else K_right
     n_views = len(tracker.track_list)
     poses, triples = [], []
@@ -2192,20 +2246,22 @@ def orient_views(tracker, pairs, K, K_right=None, root=0, max_sampson_px=2.0, ma
             entry["r_idx"], entry["q_idx"], entry["inlier"] = got[0].reshape(-1), got[1].reshape(-1), got[2]      # for link_views
         poses.append(entry)
         triples.append((entry["ref"], entry["que"], entry["R"]))
-    rots, verdict = HipCamposeMixin().average_rotations(triples, n_views, root, max_angle_deg, tree_hyp, rounds)
+    rots, verdict = HipCamposeMixin().average_rotations(triples, n_views, root, max_angle_deg, tree_hyp, rounds, triplets=triplets)
     return rots, verdict, poses
 
 
 def locate_views(tracker, pairs, K, K_right=None, root=0, max_sampson_px=2.0, max_hyp=128, iteration=2, min_angle_deg=2.0,
-                 min_parallax=8, max_angle_deg=5.0, tree_hyp=128, rounds=2, max_direction_deg=5.0, translation_rounds=8):
+                 min_parallax=8, max_angle_deg=5.0, tree_hyp=128, rounds=2, max_direction_deg=5.0, translation_rounds=8, triplets=None):
     """Absolute rotations AND positions of the views of a ``HipDeviceKeyTracker``: ``orient_views`` over the listed ``pairs``,
     then ONE ``HipCamposeMixin.average_translations`` over the same poses with the rotations found and the rotation verdict
     as the edge mask (a pair whose rotation disagrees with the graph lends no direction).  Returns ``rots, centres, verdicts,
     poses``: ``rots`` and ``poses`` as ``orient_views`` returns them, ``centres`` as ``average_translations`` does (all None
     where the rotations have no model), ``verdicts`` the dict ``{"rotation": ..., "translation": ...}`` (the second None
-    without a rotation model).  A function of the module, like ``orient_views``; ``process()`` does not call it."""
+    without a rotation model).  ``triplets`` goes to ``orient_views``: a pair the triplet filter dropped is no inlier of the
+    rotation verdict and lends no direction either.  A function of the module, like ``orient_views``; ``process()`` does not
+    call it."""
     rots, rot_verdict, poses = orient_views(tracker, pairs, K, K_right, root, max_sampson_px, max_hyp, iteration, min_angle_deg,
-                                            min_parallax, max_angle_deg, tree_hyp, rounds)
+                                            min_parallax, max_angle_deg, tree_hyp, rounds, triplets=triplets)
     n_views = len(tracker.track_list)
     if rot_verdict["status"] & native.ROTAVG_NO_MODEL:
         return rots, [None] * n_views, {"rotation": rot_verdict, "translation": None}, poses
@@ -2289,7 +2345,8 @@ def link_views(tracker, pairs, inliers=None, pair_mask=None, min_len=2, want_key
 def reconstruct_views(tracker, pairs, K, root=0, min_len=2, lam=5.0, iters=10, solver="iterate", refine_iters=20, retriangulate_px=None,
                       cull_px=None, set_normalised=True, **locate):
     """A global reconstruction of the views of a ``HipDeviceKeyTracker`` from the listed ``pairs``, on the device from the
-    matches to the adjusted scene: ``locate_views`` (``locate`` are its options; one intrinsic matrix ``K`` for every view),
+    matches to the adjusted scene: ``locate_views`` (``locate`` are its options, ``triplets=`` for the triplet filter among
+    them; one intrinsic matrix ``K`` for every view),
     ``link_views`` over the pairs both verdicts admit with each pair's verification inliers, a ``BaProblem`` from the tracks
     with the averaged rotations and centres as cameras, ``refine_points`` (DLT, then Gauss-Newton) for the points, with
     ``retriangulate_px`` the robust re-triangulation and with ``cull_px`` a cull at that many pixels, then ``iters``
