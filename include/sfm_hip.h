@@ -1590,6 +1590,79 @@ int sfm_view_triplets_dev(int V, int64_t E, const int* edges /*host [E][2]*/, co
                           void* hip_stream);
 /* Step 3 on the host, by the function the kernels run: 1 for a consistent triplet, *lhs_out (may be NULL) the trace. */
 int sfm_view_triplet_test(const double Mab[9], const double Mbc[9], const double Mac[9], double cos_loop, double* lhs_out);
+
+/* ---- view pairs: which pairs of views to match, from one short descriptor per view -------------------------------------
+ * A vocabulary of K words is trained from the resident descriptor sets, every view is summarised by one VLAD descriptor
+ * (per word the power-normalised sum of the residuals of its keys), all views are compared through these descriptors and
+ * each view keeps its k best partners.  The whole rule is stated in integers, except the score, which is three correctly
+ * rounded fp64 operations: every output is a function of the input alone.
+ * Sets: every set of a call is an exact L2 set (SFM_DESC_INFO_EXACT = 1) of one dimension D <= 256; anything else is
+ * SFM_E_SHAPE with nothing launched.  s(x, c) = sum (x[d] - c[d])^2, an exact integer.  mix = the splitmix64 finaliser of
+ * the robust estimators' samplers (block "robust two-view geometry").  Limits: 1 <= K <= 1024, K D <= 131 072, a view has
+ * at most 2^22 keys, V <= 65 536, 1 <= k <= 64; the keys of a describe call number fewer than 2^31.
+ *   1. Vocabulary, sfm_vocab_train.  The rows of the n_sets sets are numbered by concatenation in set order, N in all.
+ *      train_cap = 0 stands for 2^20, its maximum is 2^22.  The training rows are all rows when N <= train_cap, otherwise
+ *      rows floor(j N / train_cap), j = 0 .. train_cap - 1; T is their number; T < K is SFM_E_SHAPE.
+ *      Start: word w is training row lo_w + mix(seed K + w) mod (hi_w - lo_w), lo_w = floor(w T / K), hi_w =
+ *      floor((w + 1) T / K), seed K + w taken mod 2^64.  sfm_vocab_init_rows returns, on any machine, the K rows of the
+ *      CONCATENATION these are (the training row mapped through floor(j N / train_cap) where N > train_cap).
+ *      A round: a(j) = argmin_w (s(x_j, c_w), w) -- a tie goes to the lower word; n_w the number of rows of word w and
+ *      S_w[d] = sum x_j[d] (below 2^31 by the cap); c_w[d] = floor((2 S_w[d] + n_w) / (2 n_w)), the mean rounded half up,
+ *      where n_w > 0; a word without a row keeps its bytes.  `iters` rounds are run unconditionally, 0 <= iters <= 64;
+ *      iters = 0 returns the start.  words_out[K][D] uint8 (host).
+ *      log (host, int64 [iters + 1][3], may be NULL): per round, under the words the round started with: the inertia
+ *      sum_j s(x_j, c_a(j)) | the number of words without a row | the number of words whose bytes the round changed; the
+ *      last row is the same under the final words, with 0 changed.
+ *   2. View descriptors, sfm_view_describe(vocab, n_views, views, ...): vocab is a set of K rows (sfm_desc_create of
+ *      words_out, or a vocabulary from elsewhere).  Per view: a(i) as above; r[w][d] = sum over a(i) = w of
+ *      (x_i[d] - c_w[d]), int32; q[w][d] = sgn(r) min(isqrt(|r|), 127), int8, isqrt the exact floor square root;
+ *      norm2 = sum q^2 (below 2^31).  Outputs, all optional, the non-NULL ones select the work: desc int8 [V][K D],
+ *      word-major; norm2 int64 [V]; word_count int32 [V][K]; assign int32 per key, the views concatenated; residual int32
+ *      [V][K D].  An empty view gives zeros.
+ *   3. Pairs, sfm_view_pairs(V, len, desc int8 [V][len], norm2 int64 [V], k, min_score, mutual, sequential, ...), len <=
+ *      131 072, every |desc| <= 127 (so that the dot products stay in int32: 127^2 * 131 072 < 2^31).
+ *      dot(a, b) = sum desc_a desc_b, exact.  score(a, b) = (double)dot / sqrt((double)norm2_a * (double)norm2_b): a
+ *      product, a square root and a division, each correctly rounded, never contracted.  sfm_view_score is that function
+ *      on the host and returns the kernel's bits.
+ *      b is a CANDIDATE of a iff b != a, norm2_a > 0, norm2_b > 0 and score >= min_score (NaN min_score: SFM_E_SHAPE).
+ *      The NEIGHBOURS of a are its first k candidates by (score descending, b ascending): nbr[V][k] int32 and
+ *      nbr_score[V][k] double; missing entries are -1 and -inf.
+ *      The pair a < b is LISTED iff (mutual = 0: b is a neighbour of a or a is a neighbour of b; mutual = 1: both) or
+ *      b - a <= sequential (sequential >= 0, 0 = none: the consecutive frames of a sequence, whatever their descriptors).
+ *      pairs[cap][2] int32, sorted lexicographically, and *n_pairs, the true count: only the first min(*n_pairs, cap)
+ *      rows of pairs, how and pair_score are written.  how int32 per pair: 1 (a lists b) | 2 (b lists a) | 4
+ *      (sequential).  pair_score double per pair: the score, -inf where a norm is zero.  dot int32 [V][V], optional.
+ *      The rule names no order of evaluation: permuting the views permutes the result.
+ *   4. Argument errors (SFM_E_SHAPE before a device is looked for, outputs untouched): a NULL or non-exact or Hamming set,
+ *      mixed D, K or K D or V or k or iters or train_cap outside the limits, T < K, NaN min_score, mutual not 0 or 1,
+ *      sequential < 0, cap < 0, len outside 1 .. 131 072, a NULL desc or norm2, how or pair_score without pairs
+ *      where cap > 0.
+ * How.  Assignment (training and describing): tiles of 128 rows against all K words by v_mfma_f32_16x16x32_bf16 on the sets'
+ * resident bf16 rows and integer norms (exact: block "descriptor matching"), a lane's running best by one unsigned compare
+ * of (s << 32 | w).  Accumulation: int32 sums of x per (word, dimension) and the word counts, per workgroup in LDS where
+ * (K D + K) 4 bytes fit, by global int32 atomics otherwise -- integer addition is associative, the route does not show;
+ * r = S - n c.  Scores: the V x V dot products by v_mfma_i32_16x16x64_i8 in strips of rows (a bounded work buffer, or
+ * `dot` itself when it is asked for), a wave per view selects its neighbours with (score key, index) compares; the
+ * reverse lists by the key-major list; a count per view, the shared prefix sum, a fill, and one wave per listed pair for
+ * pair_score.  No floating-point atomic and no floating-point sum anywhere: the bits do not depend on the device, the
+ * compute-unit limit or timing.
+ * The host forms take host arrays (the sets are handles) and block; the _dev forms take device arrays and a stream (NULL
+ * = the library stream); *n_pairs is a host integer. */
+int sfm_vocab_train(int n_sets, sfm_desc_set* const* sets, int K, int iters, uint64_t seed, int64_t train_cap,
+                    uint8_t* words_out /*[K][D]*/, int64_t* log /*[iters + 1][3] or NULL*/);
+int sfm_vocab_init_rows(int64_t N, int K, uint64_t seed, int64_t train_cap, int64_t* rows_out /*[K]*/);
+int sfm_view_describe(sfm_desc_set* vocab, int n_views, sfm_desc_set* const* views, int8_t* desc, int64_t* norm2, int* word_count,
+                      int* assign, int* residual);
+int sfm_view_describe_dev(sfm_desc_set* vocab, int n_views, sfm_desc_set* const* views, int8_t* d_desc, int64_t* d_norm2,
+                          int* d_word_count, int* d_assign, int* d_residual, void* hip_stream);
+int sfm_view_pairs(int V, int len, const int8_t* desc, const int64_t* norm2, int k, double min_score, int mutual, int sequential,
+                   int64_t cap, int* nbr /*[V][k]*/, double* nbr_score /*[V][k]*/, int* pairs /*[cap][2]*/, int* how /*[cap]*/,
+                   double* pair_score /*[cap]*/, int* dot /*[V][V]*/, int64_t* n_pairs);
+int sfm_view_pairs_dev(int V, int len, const int8_t* d_desc, const int64_t* d_norm2, int k, double min_score, int mutual,
+                       int sequential, int64_t cap, int* d_nbr, double* d_nbr_score, int* d_pairs, int* d_how, double* d_pair_score,
+                       int* d_dot, int64_t* n_pairs /*host*/, void* hip_stream);
+/* The score of step 3 on the host, by the function the kernels run.  SFM_E_SHAPE for a NULL score_out. */
+int sfm_view_score(int dot, int64_t norm2_a, int64_t norm2_b, double* score_out);
 /* The resident scene moved by X' = s A X + t, on the device: every point by the formula, every camera block [C, q] to
  * C' = s A C + t and q' = q(A R(q)), the library's canonical quaternion of the product (qw >= 0, not renormalised).
  * Refused before any launch: s not finite or not positive (SFM_E_SHAPE), A failing verify_rotation

@@ -31,10 +31,11 @@
 #include <vector>
 
 #include "sfm_common.h"
+#include "sfm_desc.h"
 
 namespace {
 
-constexpr int CHUNK = 1024;         // train columns per workgroup
+constexpr int CHUNK = 1024;        // train columns per workgroup
 constexpr int ROW_PAD = 128;        // rows of every set are padded to a multiple of this (query tile of the MFMA kernel)
 constexpr int MFMA_ROWS = 128;      // query rows per workgroup of the MFMA kernel: 4 waves x 2 strips x 16
 constexpr int SIMT_ROWS = 256;      // query rows per workgroup of the thread-per-query kernels
@@ -445,16 +446,10 @@ __device__ __forceinline__ bool gate_admits<SFM_GUIDE_HOMOGRAPHY>(const double* 
 
 }  // namespace
 
-struct sfm_desc_set {
-  int metric, n, dim, dtype, kind, n_pad, dp;
-  uint16_t* bf = nullptr;
-  int* norm = nullptr;
-  float* f32 = nullptr;
-  uint32_t* words = nullptr;
-  int64_t upload_bytes = 0;
-};
-
 namespace {
+
+static_assert(KIND_EXACT == sfm::kDescKindExact && KIND_HAMMING == sfm::kDescKindHamming && KIND_FLOAT == sfm::kDescKindFloat,
+              "sfm_desc.h names the kinds for the other readers of a set");
 
 int set_kind(const sfm_desc_set* s, bool all_exact) {
   if (s->metric == SFM_MATCH_HAMMING) return KIND_HAMMING;

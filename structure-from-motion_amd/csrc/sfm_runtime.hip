@@ -304,7 +304,7 @@ using namespace sfm;
 
 extern "C" {
 
-int sfm_version(void) { return 111; }
+int sfm_version(void) { return 112; }
 
 const char* sfm_last_error(void) { return g_err; }
 

@@ -89,6 +89,11 @@ LINK_SCAN_AUTO, LINK_SCAN_ONE_BLOCK, LINK_SCAN_DEVICE = 0, 1, 2
 TRIPLET_SUMMARY = ("triplets", "triplets_consistent", "edges_tested", "edges_kept", "edges_dropped", "edges_untested", "edges_masked",
                    "largest_n_tri")
 TRIPLET_OUTPUTS = ("edge_keep", "n_tri", "n_ok", "kept_idx", "summary")
+RETRIEVE_MAX_WORDS, RETRIEVE_MAX_LEN, RETRIEVE_MAX_DIM, RETRIEVE_MAX_VIEWS, RETRIEVE_MAX_K, RETRIEVE_MAX_ITERS = 1024, 131072, 256, 65536, 64, 64
+RETRIEVE_MAX_VIEW_KEYS, RETRIEVE_CAP_DEFAULT, RETRIEVE_CAP_MAX = 1 << 22, 1 << 20, 1 << 22
+PAIR_HOW_FORWARD, PAIR_HOW_BACKWARD, PAIR_HOW_SEQUENTIAL = 1, 2, 4
+DESCRIBE_OUTPUTS = ("desc", "norm2", "word_count", "assign", "residual")
+PAIRS_OUTPUTS = ("nbr", "nbr_score", "pairs", "how", "pair_score", "dot")
 POSE_FROM_F, POSE_FROM_H = 0, 1
 POSE_EMPTY, POSE_NO_MODEL, POSE_NO_POSE, POSE_TIED, POSE_NO_PARALLAX = 1, 2, 4, 8, 16
 POSE_CANDIDATES = 4
@@ -313,6 +318,13 @@ SIGNATURES = {
                           _ip, _lp, _ip],
     "sfm_view_triplets_dev": [ci, i64, _ip, vp, vp, cd, ci, ci, ci, ci, vp, vp, vp, vp, vp, _ip, vp],
     "sfm_view_triplet_test": [_dp, _dp, _dp, cd, _dp],
+    "sfm_vocab_train": [ci, _pp, ci, ci, ctypes.c_uint64, i64, ctypes.POINTER(ctypes.c_uint8), _lp],
+    "sfm_vocab_init_rows": [i64, ci, ctypes.c_uint64, i64, _lp],
+    "sfm_view_describe": [vp, ci, _pp, ctypes.POINTER(ctypes.c_int8), _lp, _ip, _ip, _ip],
+    "sfm_view_describe_dev": [vp, ci, _pp, vp, vp, vp, vp, vp, vp],
+    "sfm_view_pairs": [ci, ci, ctypes.POINTER(ctypes.c_int8), _lp, ci, cd, ci, ci, i64, _ip, _dp, _ip, _ip, _dp, _ip, _lp],
+    "sfm_view_pairs_dev": [ci, ci, vp, vp, ci, cd, ci, ci, i64, vp, vp, vp, vp, vp, vp, _lp, vp],
+    "sfm_view_score": [ci, i64, i64, _dp],
     "sfm_ba_transform": [vp, cd, _dp, _dp],
     "sfm_ba_align": [vp, ci, _ip, _dp, cd, ci, ci, ci, ci, _dp, ctypes.POINTER(ctypes.c_uint8), _ip, _ip, _ip],
     "sfm_twoview_pose": [ci, _ip, i64, _dp, _dp, ctypes.POINTER(ctypes.c_uint8), _dp, _ip, _dp, _dp, cd, ci, _dp, _dp, _dp, _ip, _ip, _ip,
@@ -2523,6 +2535,214 @@ def match_dev(query, refs, mode, d_best_idx, d_best_dist, d_second_idx, d_second
     handles = (ctypes.c_void_p * max(len(refs), 1))(*[r._h for r in refs])
     check(load().sfm_match_dev(query._h, len(refs), handles, int(mode), _vp(d_best_idx), _vp(d_best_dist), _vp(d_second_idx),
                                _vp(d_second_dist), _vp(d_mutual), _vp(stream)))
+
+
+# ---- view pairs: which pairs of views to match (sfm_vocab_*, sfm_view_describe*, sfm_view_pairs*; no reference counterpart) ----
+def _set_facts(s):
+    """``(n, dim, metric, exact)`` of a DescriptorSet, or of a tuple that stands for one where there is no device."""
+    if isinstance(s, (tuple, list)):
+        n, dim, metric, exact = s
+        return int(n), int(dim), int(metric), bool(exact)
+    return int(s.n), int(s.dim), int(s.metric), bool(s.exact)
+
+
+def _integer(name, value):
+    if isinstance(value, (bool, np.bool_)) or int(value) != value:
+        raise ValueError("%s must be an integer, got %r" % (name, value))
+    return int(value)
+
+
+def _check_retrieve_sets(what, sets):
+    sets = list(sets)
+    if not 1 <= len(sets) <= RETRIEVE_MAX_VIEWS:
+        raise ValueError("%d %ss (1 .. %d)" % (len(sets), what, RETRIEVE_MAX_VIEWS))
+    dim0, total = None, 0
+    for i, s in enumerate(sets):
+        if s is None:
+            raise ValueError("%s %d is null" % (what, i))
+        n, dim, metric, exact = _set_facts(s)
+        if metric != MATCH_L2 or not exact:
+            raise ValueError("%s %d is not an exact L2 set (Hamming and non-integer float sets are not described)" % (what, i))
+        dim0 = dim if dim0 is None else dim0
+        if dim != dim0:
+            raise ValueError("%s %d has dim %d, %s 0 has %d" % (what, i, dim, what, dim0))
+        if n > RETRIEVE_MAX_VIEW_KEYS:
+            raise ValueError("%s %d has %d keys (at most 2^22)" % (what, i, n))
+        total += n
+    return sets, dim0, total
+
+
+def _check_retrieve_words(K, D):
+    if not 1 <= K <= RETRIEVE_MAX_WORDS:
+        raise ValueError("K = %d words (1 .. %d)" % (K, RETRIEVE_MAX_WORDS))
+    if not 1 <= D <= RETRIEVE_MAX_DIM:
+        raise ValueError("dim %d (1 .. %d)" % (D, RETRIEVE_MAX_DIM))
+    if K * D > RETRIEVE_MAX_LEN:
+        raise ValueError("K * D = %d exceeds %d" % (K * D, RETRIEVE_MAX_LEN))
+
+
+def check_vocab_train(sets, K, iters=4, seed=1, train_cap=0):
+    """The arguments of a ``vocab_train`` call, without a device: ``(sets, K, iters, seed, train_cap, D, N, T)`` converted or
+    ValueError -- everything sfm_vocab_train refuses, in its order and with its messages.  A set is a DescriptorSet or, where
+    there is no device, a tuple ``(n, dim, metric, exact)``; ``T`` is the number of training rows."""
+    K, iters, train_cap = _integer("K", K), _integer("iters", iters), _integer("train_cap", train_cap)
+    seed = _integer("seed", seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be in 0 .. 2^64 - 1, got %d" % seed)
+    if not 1 <= K <= RETRIEVE_MAX_WORDS:
+        raise ValueError("K = %d words (1 .. %d)" % (K, RETRIEVE_MAX_WORDS))
+    if not 0 <= iters <= RETRIEVE_MAX_ITERS:
+        raise ValueError("iters = %d (0 .. %d)" % (iters, RETRIEVE_MAX_ITERS))
+    if not 0 <= train_cap <= RETRIEVE_CAP_MAX:
+        raise ValueError("train_cap = %d (0 = 2^20, at most 2^22)" % train_cap)
+    sets, D, N = _check_retrieve_sets("set", sets)
+    _check_retrieve_words(K, D)
+    T = min(N, train_cap if train_cap else RETRIEVE_CAP_DEFAULT)
+    if T < K:
+        raise ValueError("T = %d training rows for K = %d words" % (T, K))
+    return sets, K, iters, seed, train_cap, D, N, T
+
+
+def check_view_describe(vocab, views):
+    """The arguments of a ``view_describe`` call, without a device: ``(views, K, D, N)`` or ValueError, as sfm_view_describe."""
+    if vocab is None:
+        raise ValueError("the vocabulary is null")
+    _, D, K = _check_retrieve_sets("vocabulary", [vocab])
+    _check_retrieve_words(K, D)
+    views, Dv, N = _check_retrieve_sets("view", views)
+    if Dv != D:
+        raise ValueError("the views have dim %d, the vocabulary %d" % (Dv, D))
+    if N >= 2 ** 31:
+        raise ValueError("%d keys in all (fewer than 2^31)" % N)
+    return views, K, D, N
+
+
+def check_view_pairs(n_views, length, k=8, min_score=-np.inf, mutual=False, sequential=0, cap=0):
+    """The scalar arguments of a ``view_pairs`` call, without a device: ``(V, len, k, min_score, mutual, sequential, cap)``
+    converted or ValueError -- what sfm_view_pairs refuses, in its order and with its messages."""
+    V, length, k, sequential, cap = (_integer("n_views", n_views), _integer("len", length), _integer("k", k),
+                                     _integer("sequential", sequential), _integer("cap", cap))
+    mutual = int(mutual) if isinstance(mutual, (bool, np.bool_)) else _integer("mutual", mutual)
+    min_score = float(min_score)
+    if not 1 <= V <= RETRIEVE_MAX_VIEWS:
+        raise ValueError("V = %d views (1 .. %d)" % (V, RETRIEVE_MAX_VIEWS))
+    if not 1 <= length <= RETRIEVE_MAX_LEN:
+        raise ValueError("len = %d (1 .. %d)" % (length, RETRIEVE_MAX_LEN))
+    if not 1 <= k <= RETRIEVE_MAX_K:
+        raise ValueError("k = %d neighbours (1 .. %d)" % (k, RETRIEVE_MAX_K))
+    if min_score != min_score:
+        raise ValueError("min_score is NaN")
+    if mutual not in (0, 1):
+        raise ValueError("mutual = %d must be 0 or 1" % mutual)
+    if sequential < 0:
+        raise ValueError("sequential = %d must be >= 0" % sequential)
+    if cap < 0:
+        raise ValueError("cap = %d must be >= 0" % cap)
+    if V * (2 * k + min(sequential, V)) >= 2 ** 31:
+        raise ValueError("V (2 k + sequential) reaches 2^31 pairs")
+    return V, length, k, min_score, mutual, min(sequential, 2 ** 31 - 1), cap
+
+
+def _set_handles(sets):
+    return (ctypes.c_void_p * max(len(sets), 1))(*[s._h for s in sets])
+
+
+def view_score(dot, norm2_a, norm2_b):
+    """``dot / sqrt(norm2_a * norm2_b)`` in the library's three fp64 operations (sfm_view_score; host only): the kernel's bits."""
+    out = np.zeros(1)
+    check(load().sfm_view_score(int(dot), int(norm2_a), int(norm2_b), dptr(out)))
+    return float(out[0])
+
+
+def vocab_init_rows(n_rows, K, seed=1, train_cap=0):
+    """The rows of the concatenation of ``n_rows`` descriptors that ``vocab_train`` starts its ``K`` words from
+    (sfm_vocab_init_rows; host only), int64 (K,)."""
+    rows = np.zeros(max(int(K), 1), dtype=np.int64)
+    check(load().sfm_vocab_init_rows(int(n_rows), int(K), ctypes.c_uint64(int(seed) % 2 ** 64), int(train_cap), _lptr(rows)))
+    return rows[:int(K)]
+
+
+def vocab_train(sets, K, iters=4, seed=1, train_cap=0):
+    """A vocabulary of ``K`` words from resident exact L2 DescriptorSets by ``iters`` rounds of integer k-means
+    (sfm_vocab_train).  Returns ``words`` uint8 (K, D) and ``log`` int64 (iters + 1, 3): inertia, words without a row, words
+    changed, per round under the words it started with; the last row under the final words."""
+    sets, K, iters, seed, train_cap, D, N, T = check_vocab_train(sets, K, iters, seed, train_cap)
+    words = np.zeros((K, D), dtype=np.uint8)
+    log = np.zeros((iters + 1, 3), dtype=np.int64)
+    check(load().sfm_vocab_train(len(sets), _set_handles(sets), K, iters, ctypes.c_uint64(seed), train_cap, _u8ptr(words), _lptr(log)))
+    return words, log
+
+
+def view_describe(vocab, views, outputs=DESCRIBE_OUTPUTS):
+    """One VLAD descriptor per view (sfm_view_describe): ``vocab`` a DescriptorSet of the K words, ``views`` DescriptorSets.
+    Returns a dict of ``desc`` int8 (V, K * D), ``norm2`` int64 (V,), ``word_count`` int32 (V, K), ``assign`` int32 (keys of all
+    views,), ``residual`` int32 (V, K * D); an output not named in ``outputs`` is not computed and comes back as None."""
+    views, K, D, N = check_view_describe(vocab, views)
+    unknown = set(outputs) - set(DESCRIBE_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (DESCRIBE_OUTPUTS, sorted(unknown)))
+    V = len(views)
+    o = {"desc": np.zeros((V, K * D), dtype=np.int8), "norm2": np.zeros(V, dtype=np.int64), "word_count": np.zeros((V, K), dtype=np.int32),
+         "assign": np.zeros(N, dtype=np.int32), "residual": np.zeros((V, K * D), dtype=np.int32)}
+    w = {name: (o[name] if name in outputs else None) for name in DESCRIBE_OUTPUTS}
+    desc_p = w["desc"].ctypes.data_as(ctypes.POINTER(ctypes.c_int8)) if w["desc"] is not None else None
+    check(load().sfm_view_describe(vocab._h, V, _set_handles(views), desc_p, _lptr(w["norm2"]), iptr(w["word_count"]), iptr(w["assign"]),
+                                   iptr(w["residual"])))
+    return w
+
+
+def view_describe_dev(vocab, views, d_desc=0, d_norm2=0, d_word_count=0, d_assign=0, d_residual=0, stream=0):
+    """``view_describe`` with the outputs as device pointers (0 = not wanted) and a caller's stream (sfm_view_describe_dev)."""
+    views = list(views)
+    check(load().sfm_view_describe_dev(vocab._h, len(views), _set_handles(views), _vp(d_desc), _vp(d_norm2), _vp(d_word_count),
+                                       _vp(d_assign), _vp(d_residual), _vp(stream)))
+
+
+def view_pairs(desc, norm2, k=8, min_score=-np.inf, mutual=False, sequential=0, cap=None, outputs=PAIRS_OUTPUTS[:5]):
+    """The pairs of views to match (sfm_view_pairs): ``desc`` int8 (V, len), ``norm2`` int64 (V,).  Every view keeps its first
+    ``k`` candidates by (score descending, index ascending); the pair a < b is listed iff one lists the other (``mutual``:
+    both do) or ``b - a <= sequential``.  ``cap`` bounds the rows of ``pairs`` that are written (default: every pair that can
+    be listed).  Returns a dict of ``nbr`` int32 (V, k), ``nbr_score`` (V, k), ``pairs`` int32 (min(n_pairs, cap), 2), ``how``
+    int32, ``pair_score``, ``dot`` int32 (V, V) -- None where not in ``outputs`` -- and ``n_pairs``, the true count."""
+    desc = np.ascontiguousarray(desc, dtype=np.int8)
+    norm2 = np.ascontiguousarray(norm2, dtype=np.int64).reshape(-1)
+    if desc.ndim != 2 or norm2.shape[0] != desc.shape[0]:
+        raise ValueError("desc must be (V, len) and norm2 (V,), got %r and %r" % (desc.shape, norm2.shape))
+    V, length = desc.shape
+    if cap is None:
+        cap = min(V * (V - 1) // 2, V * (2 * int(k) + min(int(sequential), V)))
+    V, length, k, min_score, mutual, sequential, cap = check_view_pairs(V, length, k, min_score, mutual, sequential, cap)
+    unknown = set(outputs) - set(PAIRS_OUTPUTS)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (PAIRS_OUTPUTS, sorted(unknown)))
+    o = {"nbr": np.zeros((V, k), dtype=np.int32), "nbr_score": np.zeros((V, k)), "pairs": np.zeros((cap, 2), dtype=np.int32),
+         "how": np.zeros(cap, dtype=np.int32), "pair_score": np.zeros(cap), "dot": None}
+    if "dot" in outputs:
+        o["dot"] = np.zeros((V, V), dtype=np.int32)
+    w = {name: (o[name] if name in outputs else None) for name in PAIRS_OUTPUTS}
+    if w["pairs"] is None and (w["how"] is not None or w["pair_score"] is not None):
+        raise ValueError("how and pair_score come with pairs")
+    n_pairs = np.zeros(1, dtype=np.int64)
+    check(load().sfm_view_pairs(V, length, desc.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)), _lptr(norm2), k, min_score, mutual, sequential,
+                                cap, iptr(w["nbr"]), dptr(w["nbr_score"]), iptr(w["pairs"]), iptr(w["how"]), dptr(w["pair_score"]),
+                                iptr(w["dot"]), _lptr(n_pairs)))
+    written = min(int(n_pairs[0]), cap)
+    for name in ("pairs", "how", "pair_score"):
+        if w[name] is not None:
+            w[name] = w[name][:written].copy()
+    w["n_pairs"] = int(n_pairs[0])
+    return w
+
+
+def view_pairs_dev(n_views, length, d_desc, d_norm2, k=8, min_score=-np.inf, mutual=False, sequential=0, cap=0, d_nbr=0, d_nbr_score=0,
+                   d_pairs=0, d_how=0, d_pair_score=0, d_dot=0, stream=0):
+    """``view_pairs`` with every array as a device pointer (0 = not wanted) and a caller's stream (sfm_view_pairs_dev).  Returns
+    ``n_pairs``, the true count; the first ``min(n_pairs, cap)`` rows of ``d_pairs``, ``d_how``, ``d_pair_score`` are written."""
+    n_pairs = np.zeros(1, dtype=np.int64)
+    check(load().sfm_view_pairs_dev(int(n_views), int(length), _vp(d_desc), _vp(d_norm2), int(k), float(min_score), int(mutual),
+                                    int(sequential), int(cap), _vp(d_nbr), _vp(d_nbr_score), _vp(d_pairs), _vp(d_how), _vp(d_pair_score),
+                                    _vp(d_dot), _lptr(n_pairs), _vp(stream)))
+    return int(n_pairs[0])
 
 
 # ---- guided matching (sfm_match_guided*; no reference counterpart) ---------------------------------------------------

@@ -1974,6 +1974,28 @@ class HipDeviceKeyTracker(HipKeyTrackerMixin):
         else:
             self._KeyTracker__extend_list(new_view, views, is_knn_match, is_fund_inlier, ransac_config)
 
+    def _register_views(self, views):
+        """Bring the views ``views[len(self.track_list):]`` into the store WITHOUT matching them: their coordinates and
+        descriptors go up, every table gets their (empty) rows and ``track_list`` their ``HipDeviceKeyTrack``.  What
+        ``match_pairs`` fills afterwards; ``add_new_view`` may still follow.  Returns the number of views added."""
+        first = len(self.track_list)
+        if self._store is not None and self._store.n_views != first:
+            raise native.SfmHipError("HipDeviceKeyTracker: the device store holds %d views, track_list %d" % (self._store.n_views, first))
+        for idx in range(first, len(views)):
+            view = views[idx]
+            xy = self._key_xy(view)
+            d = view.key_descriptors
+            if d is not None and len(d) and len(d) != xy.shape[0]:
+                raise ValueError("{} descriptors for {} keys".format(len(d), xy.shape[0]))
+            if self._store is None:
+                self._store = native.TrackStore()
+            self._kt_set(idx, d)
+            self._store.add_view(xy)
+            self._versions = [v + 1 for v in self._versions] + [0]
+            self._xy.append(xy)
+            self.track_list.append(HipDeviceKeyTrack(self, idx, xy.shape[0]))
+        return len(self.track_list) - first
+
     def _extend_list(self, new_view, views, is_knn_match=False, is_fund_inlier=False, ransac_config=None):
         key_num = len(new_view.key_pts)
         new_idx = len(self.track_list)
@@ -2475,6 +2497,110 @@ def guided_pairs(tracker, ref_idx, que_idx, max_px=2.0, ratio=matching.RATIO, mo
         tracker._versions[ref_idx] += 1
         tracker._versions[que_idx] += 1
     return r_idx.reshape(1, -1).astype(int), q_idx.reshape(1, -1).astype(int)
+
+
+def _resident_sets(tracker, who, n_views=None):
+    sets = tracker.__dict__.get("_hip_desc", {})
+    n = len(sets) if n_views is None else n_views
+    missing = [v for v in range(n) if v not in sets]
+    if n == 0 or missing:
+        raise native.SfmHipError("{}: the descriptors of view {} are not resident".format(who, missing[0] if missing else 0))
+    return [sets[v][1] for v in range(n)]
+
+
+def register_views(tracker, views):
+    """Bring ``views`` into a ``HipDeviceKeyTracker`` without matching them (``_register_views``: coordinates and descriptors go
+    up, the tables get their empty rows), so that ``select_pairs`` and ``match_pairs`` can follow.  A function of the module:
+    the tracker's class keeps the reference's public methods and ``kt_release`` only.  Returns the number of views added."""
+    if not isinstance(tracker, HipDeviceKeyTracker):
+        raise TypeError("register_views runs on a HipDeviceKeyTracker, got {}".format(type(tracker).__name__))
+    return tracker._register_views(views)
+
+
+def select_pairs(tracker, K=64, iters=4, seed=1, k=8, min_score=-np.inf, mutual=False, sequential=0, vocab=None):
+    """Which pairs of views to match (no reference counterpart; include/sfm_hip.h, block "view pairs"), from the resident
+    descriptor sets of a ``HipKeyTracker`` or ``HipDeviceKeyTracker`` (views 0 .. n - 1, e.g. after ``register_views``): a
+    vocabulary of ``K`` words trained on them by ``iters`` rounds (``native.vocab_train``; or ``vocab``, uint8 (K, D) words
+    from elsewhere), one VLAD descriptor per view (``native.view_describe``), every view's ``k`` best partners by score and
+    the list of pairs (``native.view_pairs``): a < b is listed iff one lists the other (``mutual``: both do) or
+    ``b - a <= sequential``.  Returns ``(pairs, verdict)``: the list of ``(ref_idx, que_idx)``, ref < que, sorted, that
+    ``match_pairs``, ``orient_views`` and ``reconstruct_views`` take, and a dict of ``nbr``, ``nbr_score``, ``how``,
+    ``pair_score``, ``word_count``, ``norm2``, ``words`` and ``log`` (None with a given vocabulary).  Nothing calls this on
+    its own."""
+    sets = _resident_sets(tracker, "select_pairs")
+    log = None
+    if vocab is None:
+        words, log = native.vocab_train(sets, K, iters, seed)
+    else:
+        words = np.ascontiguousarray(vocab, dtype=np.uint8)
+        if words.ndim != 2 or words.shape[1] != sets[0].dim:
+            raise ValueError("vocab must be uint8 (K, {}), got shape {}".format(sets[0].dim, words.shape))
+    with native.DescriptorSet(native.MATCH_L2, words) as voc:
+        d = native.view_describe(voc, sets, outputs=("desc", "norm2", "word_count"))
+    p = native.view_pairs(d["desc"], d["norm2"], k, min_score, mutual, sequential)
+    verdict = dict(nbr=p["nbr"], nbr_score=p["nbr_score"], how=p["how"], pair_score=p["pair_score"], word_count=d["word_count"],
+                   norm2=d["norm2"], words=words, log=log)
+    return [(int(a), int(b)) for a, b in p["pairs"]], verdict
+
+
+def match_pairs(tracker, views, pairs, is_knn_match=None):
+    """Match only the listed ``pairs`` of ``views`` into the tables of a ``HipDeviceKeyTracker`` (no reference counterpart).
+
+    The views not yet in the store are registered without matching (``_register_views``).  Then, for every query view, ONE
+    ``TrackStore.match_guided`` with no gate over its listed earlier views -- the neighbours ``sfm_match`` gives, bit for bit
+    -- followed by what the host tracker does with them (``matching.filter_matches``, the duplicate removal of quirk Q14,
+    ``matching.table_writes``) and ``TrackStore.set_pairs``: the rows of a listed pair are those ``add_new_view`` writes
+    for it, the rows of every other pair stay -1.  ``pairs`` holds ``(ref_idx, que_idx)`` in either order; a pair listed
+    twice is matched once.  The fundamental-inlier option (quirk Q15) is not supported.  Returns the number of pairs
+    matched."""
+    if not isinstance(tracker, HipDeviceKeyTracker):
+        raise TypeError("match_pairs runs on a HipDeviceKeyTracker, got {}".format(type(tracker).__name__))
+    if tracker.is_fund_inlier:
+        raise ValueError("match_pairs does not support is_fund_inlier (quirk Q15): match with add_new_view instead")
+    if not is_knn_match:                                                        # falsy -> instance default, as add_new_view
+        is_knn_match = tracker.is_knn_match
+    n_views = len(views)
+    by_query = {}
+    for a, b in pairs:
+        a, b = int(a), int(b)
+        if a == b or min(a, b) < 0 or max(a, b) >= n_views:
+            raise ValueError("pair ({}, {}) must name two different views in 0 .. {}".format(a, b, n_views - 1))
+        by_query.setdefault(max(a, b), set()).add(min(a, b))
+    tracker._register_views(views)
+    sets = _resident_sets(tracker, "match_pairs", n_views)
+    cross = bool(tracker.is_cross_check)
+    import torch
+    stream = tracker.__dict__.get("_guided_stream")
+    if stream is None:
+        stream = tracker.__dict__["_guided_stream"] = torch.cuda.Stream()
+    done = 0
+    for que in sorted(by_query):
+        refs = sorted(by_query[que])
+        query = sets[que]
+        for r in refs:
+            if sets[r].n == 0:      # undefined without cv2 (INTEGRATION.md, deviation of Q16)
+                raise ValueError("reference view {} has no descriptors".format(r))
+        if query.n == 0:
+            continue
+        shape = (len(refs), query.n)
+        with torch.cuda.stream(stream):
+            bi = torch.empty(shape, dtype=torch.int32, device="cuda")
+            si = torch.empty(shape, dtype=torch.int32, device="cuda")
+            bd = torch.empty(shape, dtype=torch.float32, device="cuda")
+            sd = torch.empty(shape, dtype=torch.float32, device="cuda")
+            mu = torch.zeros(shape, dtype=torch.uint8, device="cuda")
+            tracker._store.match_guided(que, query, refs, [sets[r] for r in refs], ["none"] * len(refs), np.zeros((len(refs), 9)), 0.0,
+                                        d_best_idx=bi.data_ptr(), d_best_dist=bd.data_ptr(), d_second_idx=si.data_ptr(),
+                                        d_second_dist=sd.data_ptr(), d_mutual=mu.data_ptr() if cross else 0, stream=stream.cuda_stream)
+            bi, bd, si, sd, mu = (t.cpu().numpy() for t in (bi, bd, si, sd, mu))
+        for i, ref in enumerate(refs):
+            q, t, d = matching.filter_matches(bi[i], bd[i], si[i], sd[i], mu[i].astype(bool), is_knn_match, cross)
+            wq, wt = matching.table_writes(q, t, d)
+            tracker._store.set_pairs(ref, que, wt, wq)
+            tracker._versions[ref] += 1
+            done += 1
+        tracker._versions[que] += 1
+    return done
 
 
 class HipKeyPoint:
