@@ -176,6 +176,13 @@ __device__ __forceinline__ int group_sum(int v) {
 }
 
 template <int G>
+__device__ __forceinline__ long long group_sum(long long v) {
+#pragma unroll
+  for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <int G>
 __device__ __forceinline__ double group_min(double v) {
 #pragma unroll
   for (int off = G / 2; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));

@@ -99,7 +99,9 @@ __device__ __forceinline__ int block_count(int mine) {
   return __syncthreads_count(mine & 1) + 2 * __syncthreads_count(mine & 2) + 4 * __syncthreads_count(mine & 4);
 }
 
-// The workgroup's sum of any per-thread integer through one LDS word, on every thread.  Two barriers.
+// The workgroup's sum of any per-thread integer through one LDS word, on every thread.  Two barriers.  The call returns
+// without a barrier after the total is read, and the next call on the same word starts by zeroing it: two calls may not use
+// the same word without a __syncthreads() between them.  Several sums at once: block_sums below.
 __device__ __forceinline__ int block_sum_int(int v, int* lds_total) {
   if (threadIdx.x == 0) *lds_total = 0;
   __syncthreads();
@@ -107,6 +109,22 @@ __device__ __forceinline__ int block_sum_int(int v, int* lds_total) {
   if ((threadIdx.x & 63) == 0 && v) atomicAdd(lds_total, v);
   __syncthreads();
   return *lds_total;
+}
+
+// K such sums through the K words of lds, v[k] replaced by its total on every thread.  Two barriers for all of them; the
+// same rule holds for the words.
+template <int K>
+__device__ __forceinline__ void block_sums(int (&v)[K], int* lds) {
+  if (threadIdx.x < K) lds[threadIdx.x] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int s = group_sum<64>(v[k]);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(&lds[k], s);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = lds[k];
 }
 
 // One pass of a slice-ordered floating-point sum: red[ROWS][] holds the K sums of the pass's slices, written by their

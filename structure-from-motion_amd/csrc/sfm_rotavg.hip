@@ -3,19 +3,18 @@
 // The seventh robust estimator.  From the relative rotations on the edges of a view graph, some of them wrong, one absolute
 // rotation per view and the verdict on every edge.  The rule is stated in sfm_hip.h, block "rotation averaging".  One
 // graph per call; the stages:
-//   adjacency  the view-major list of the 2 E edge ends (entry x = 2 e + dir, dir = 1 where the view is the edge's j): the
-//              key-major list of sfm_common.h over the index pairs as they lie in memory, stable in edge order
-//   tree       a workgroup per hypothesis: breadth-first levels, a lane per view scanning its own adjacency for neighbours
-//              of the previous depth, the smallest (key, e) as parent edge, the rotation formed from the parent's; depths in
-//              LDS up to kRotLdsViews views, in global memory beyond.  With an edge mask and no rotations the same kernel
-//              gives the connectivity of the refit and of the judge
+//   adjacency  the view-major list of the 2 E edge ends (view_adjacency of sfm_view_graph.h)
+//   tree       a workgroup per hypothesis: breadth-first levels (graph_levels), a lane per view scanning its own adjacency
+//              for neighbours of the previous depth, the smallest (key, e) as parent edge, the rotation formed from the
+//              parent's; depths in LDS up to kRotLdsViews views, in global memory beyond.  With an edge mask and no
+//              rotations the same kernel gives the connectivity of the refit and of the judge
 //   score      the hot path: grid = (blocks of 1 024 edges, slices of the batch's hypotheses); Rel_e and the two indices of
 //              four edges per lane stay in registers, the two rotations are gathered, ballots are counted and one integer
 //              atomicAdd per workgroup and hypothesis goes out
 //   adopt      one workgroup per batch: wave_arg_best over the batch, carried across batches by (count, h); the winner's
 //              rotations leave the work buffer through the gauge
 //   step       one workgroup per Gauss-Newton step: the logs per edge, the right-hand side and q = L p per view in adjacency
-//              order, every dot product per slice of 64 views in slice order, Jacobi-preconditioned CG, the exponential update
+//              order, every dot product by block_dot, Jacobi-preconditioned CG, the exponential update
 //   accept     one workgroup per round: the count over all edges, the stand/stop decision, taken on the device
 //   judge      the outputs
 // No floating-point value is accumulated with an atomic; the counts are integers.
@@ -24,7 +23,7 @@
 #include <vector>
 
 #include "sfm_obs_test.h"      // contraction is off from here on
-#include "sfm_robust.h"
+#include "sfm_view_graph.h"
 
 namespace sfm {
 
@@ -36,7 +35,7 @@ constexpr int kRotBlock = 1024;               // the one workgroup of step, acce
 constexpr long long kRotWorkCap = 256LL << 20;      // the rotations of a batch of hypotheses stay below this many bytes
 
 // state words of a call on the device
-enum { kStCount = 0, kStHyp = 1, kStStopped = 2, kStStood = 3, kStFlags = 4, kStBadEdge = 5, kStWords = 8 };
+enum { kStCount = 0, kStHyp = 1, kStStopped = 2, kStStood = 3, kStFlags = 4, kStWords = 5 };
 
 struct RotArgs {
   int V, E, root;
@@ -90,46 +89,35 @@ __global__ __launch_bounds__(kRotTreeThreads) void rotavg_tree_kernel(RotArgs a,
   double* R = rot ? rot + (size_t)b * V * 9 : nullptr;
   const int r0 = rot_tree_root(h, V, a.root);
   const double nan = __builtin_nan("");
-  for (int v = tid; v < V; v += kRotTreeThreads) {
-    depth[v] = v == r0 ? 0 : -1;
-    if (R) {
+  if (R)
+    for (int v = tid; v < V; v += kRotTreeThreads) {
 #pragma unroll
       for (int k = 0; k < 9; ++k) R[(size_t)v * 9 + k] = v == r0 ? ((k & 3) == 0 ? 1.0 : 0.0) : nan;
     }
-  }
-  __syncthreads();
-  int bad = 0, any = 0;
-  for (int d = 1; d < V; ++d) {            // a level adds at least one view, so V - 1 levels at the most
-    int added = 0;
-    for (int v = tid; v < V; v += kRotTreeThreads) {
-      if (depth[v] != -1) continue;
-      unsigned long long best_key = 0;
-      int best_x = -1, best_o = -1;
-      for (int k = a.adj_ptr[v]; k < a.adj_ptr[v + 1]; ++k) {
-        const int x = a.adj[k], e = x >> 1;
-        if (mask && !mask[e]) continue;
-        const int o = a.edges[x ^ 1];
-        // a view that takes its depth in this very level holds -1 or d here, never d - 1
-        if (depth[o] != d - 1) continue;
-        const unsigned long long key = h == 0 ? (unsigned long long)e : rot_key(h, (unsigned)e);
-        if (best_x < 0 || key < best_key) { best_key = key; best_x = x; best_o = o; }      // ascending e: the first of equal keys stays
-      }
-      if (best_x < 0) continue;
-      if (R) {
-        double Rp[9], Rel[9], Rv[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { Rp[k] = R[(size_t)best_o * 9 + k]; Rel[k] = a.rel[(size_t)(best_x >> 1) * 9 + k]; }
-        if (best_x & 1) rotation_forward(Rel, Rp, Rv); else rotation_backward(Rel, Rp, Rv);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R[(size_t)v * 9 + k] = Rv[k];
-        bad |= rot_finite9(Rv) ? 0 : 1;
-      }
-      depth[v] = d;
-      added = 1;
+  int bad = 0;
+  const bool any = graph_levels<kRotTreeThreads>(V, r0, depth, [&](int v, int d) {
+    unsigned long long best_key = 0;
+    int best_x = -1, best_o = -1;
+    for (int k = a.adj_ptr[v]; k < a.adj_ptr[v + 1]; ++k) {
+      const int x = a.adj[k], e = x >> 1;
+      if (mask && !mask[e]) continue;
+      const int o = a.edges[x ^ 1];
+      if (depth[o] != d - 1) continue;
+      const unsigned long long key = h == 0 ? (unsigned long long)e : rot_key(h, (unsigned)e);
+      if (best_x < 0 || key < best_key) { best_key = key; best_x = x; best_o = o; }      // ascending e: the first of equal keys stays
     }
-    if (!__syncthreads_or(added)) break;
-    any = 1;
-  }
+    if (best_x < 0) return false;
+    if (R) {
+      double Rp[9], Rel[9], Rv[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) { Rp[k] = R[(size_t)best_o * 9 + k]; Rel[k] = a.rel[(size_t)(best_x >> 1) * 9 + k]; }
+      if (best_x & 1) rotation_forward(Rel, Rp, Rv); else rotation_backward(Rel, Rp, Rv);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) R[(size_t)v * 9 + k] = Rv[k];
+      bad |= rot_finite9(Rv) ? 0 : 1;
+    }
+    return true;
+  });
   bad = __syncthreads_or(bad);
   if (ok && tid == 0) ok[b] = (any && depth[a.root] >= 0 && !bad) ? 1 : 0;
   if (depth_out)
@@ -263,31 +251,6 @@ __device__ inline void rot_apply_exp(double* R, const double* w) {
   for (int k = 0; k < 9; ++k) R[k] = out[k];
 }
 
-// The workgroup's sum of one value per view: chunks of kRotBlock views, a wave's 64 views summed in the wave
-// (group_sum<64>'s fixed order), the slices then added in slice order by thread 0.  val(v) is called for v < V.  Every
-// thread returns the total.  The barriers also order the global-memory vectors between the phases of the CG.
-template <class Val>
-__device__ __forceinline__ double rot_block_dot(int V, Val val, double* red, double* total) {
-  const int tid = threadIdx.x;
-  double run = 0.0;
-  for (int base = 0; base < V; base += kRotBlock) {
-    const int v = base + tid;
-    const double s = group_sum<64>(v < V ? val(v) : 0.0);
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) {
-      const int slices = (min(V - base, kRotBlock) + 63) / 64;
-      for (int w = 0; w < slices; ++w) run += red[w];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) *total = run;
-  __syncthreads();
-  const double t = *total;
-  __syncthreads();
-  return t;
-}
-
 __global__ __launch_bounds__(kRotBlock) void rotavg_step_kernel(RotArgs a) {
   __shared__ double red[kRotBlock / 64];
   __shared__ double total;
@@ -335,8 +298,8 @@ __global__ __launch_bounds__(kRotBlock) void rotavg_step_kernel(RotArgs a) {
   auto dot3 = [&](const double* x, const double* y, int v) {
     return __builtin_fma(x[3 * (size_t)v + 2], y[3 * (size_t)v + 2], __builtin_fma(x[3 * (size_t)v + 1], y[3 * (size_t)v + 1], x[3 * (size_t)v] * y[3 * (size_t)v]));
   };
-  const double bb = rot_block_dot(V, [&](int v) { return dot3(vb, vb, v); }, red, &total);
-  double rz = rot_block_dot(V, [&](int v) { return dot3(vr, vp, v); }, red, &total);      // p = z at the start
+  const double bb = block_dot<kRotBlock>(V, [&](int v) { return dot3(vb, vb, v); }, red, &total);
+  double rz = block_dot<kRotBlock>(V, [&](int v) { return dot3(vr, vp, v); }, red, &total);      // p = z at the start
   bool done = !(bb > 0.0);                                   // nothing to move (or NaN: the round will not stand)
   for (int it = 0; it < a.cg_max && !done; ++it) {
     // q = L p: a held view and the root carry p = 0
@@ -360,7 +323,7 @@ __global__ __launch_bounds__(kRotBlock) void rotavg_step_kernel(RotArgs a) {
       for (int c = 0; c < 3; ++c) vq[3 * (size_t)v + c] = q[c];
     }
     __syncthreads();
-    const double pq = rot_block_dot(V, [&](int v) { return dot3(vp, vq, v); }, red, &total);
+    const double pq = block_dot<kRotBlock>(V, [&](int v) { return dot3(vp, vq, v); }, red, &total);
     const double alpha = rz / pq;
     for (int v = tid; v < V; v += kRotBlock) {
 #pragma unroll
@@ -371,9 +334,9 @@ __global__ __launch_bounds__(kRotBlock) void rotavg_step_kernel(RotArgs a) {
       }
     }
     __syncthreads();
-    const double rr = rot_block_dot(V, [&](int v) { return dot3(vr, vr, v); }, red, &total);
+    const double rr = block_dot<kRotBlock>(V, [&](int v) { return dot3(vr, vr, v); }, red, &total);
     if (rr <= a.cg_tol2 * bb) { done = true; break; }
-    const double rz_new = rot_block_dot(V, [&](int v) { return vinv[v] * dot3(vr, vr, v); }, red, &total);
+    const double rz_new = block_dot<kRotBlock>(V, [&](int v) { return vinv[v] * dot3(vr, vr, v); }, red, &total);
     const double beta = rz_new / rz;
     rz = rz_new;
     for (int v = tid; v < V; v += kRotBlock) {
@@ -436,7 +399,7 @@ __global__ __launch_bounds__(kRotBlock) void rotavg_accept_kernel(RotArgs a) {
 // judge: the outputs
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kRotBlock) void rotavg_judge_kernel(RotArgs a) {
-  __shared__ int lds_total;
+  __shared__ int lds_sums[5];
   const int tid = threadIdx.x;
   const bool model = a.st[kStHyp] >= 0;
   const double nan = __builtin_nan("");
@@ -460,30 +423,19 @@ __global__ __launch_bounds__(kRotBlock) void rotavg_judge_kernel(RotArgs a) {
     if (a.view_status) a.view_status[v] = (a.reach[v] < 0 ? SFM_ROTAVG_UNREACHED : 0) | (held ? SFM_ROTAVG_HELD : 0);
     n_rot += has; n_unreached += a.reach[v] < 0; n_held += held;
   }
-  n_in = block_sum_int(n_in, &lds_total);
-  n_out = block_sum_int(n_out, &lds_total);
-  n_rot = block_sum_int(n_rot, &lds_total);
-  n_unreached = block_sum_int(n_unreached, &lds_total);
-  n_held = block_sum_int(n_held, &lds_total);
+  int n[5] = {n_rot, n_unreached, n_held, n_in, n_out};       // the order of the summary
+  block_sums(n, lds_sums);
   if (tid != 0) return;
   const int stood = a.st[kStStood];
   const int flags = model ? ((a.iters > 0 && stood == 0 ? SFM_ROTAVG_KEPT_HYPOTHESIS : 0) | a.st[kStFlags]) : SFM_ROTAVG_NO_MODEL;
-  if (a.n_inliers) *a.n_inliers = n_in;
+  if (a.n_inliers) *a.n_inliers = n[3];
   if (a.best_hyp) *a.best_hyp = model ? a.st[kStHyp] : -1;
   if (a.status) *a.status = flags;
   if (a.summary) {
-    a.summary[0] = n_rot; a.summary[1] = n_unreached; a.summary[2] = n_held; a.summary[3] = n_in; a.summary[4] = n_out; a.summary[5] = stood;
-  }
-}
-
-// the lowest edge whose Rel fails verify_rotation (the _dev form: the host form looks on the host)
-__global__ __launch_bounds__(256) void rotavg_verify_kernel(RotArgs a) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= a.E) return;
-  double Rel[9];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) Rel[k] = a.rel[(size_t)e * 9 + k];
-  if (!verify_rotation(Rel)) atomicMin(&a.st[kStBadEdge], (int)e);
+    for (int k = 0; k < 5; ++k) a.summary[k] = n[k];
+    a.summary[5] = stood;
+  }
 }
 
 #pragma clang fp contract(on)
@@ -502,7 +454,7 @@ static void rot_plan(int V, int H, int* batch, int* n_batches) {
   *n_batches = (int)((H + b - 1) / b);
 }
 
-static int rot_check(const char* who, int V, long long E, const int* edges, const double* rel, bool rel_on_host, int root, double cos_max,
+static int rot_check(const char* who, int V, long long E, const int* edges, const double* rel, int root, double cos_max,
                      int max_hyp, int iters, int steps, double cg_tol, int cg_max, const void* R_out) {
   if (V < 2 || E < 1 || E >= (1LL << 31)) { set_error("%s: bad sizes V=%d E=%lld (V >= 2, 1 <= E < 2^31)", who, V, E); return SFM_E_SHAPE; }
   if (E > INT_MAX / 2) { set_error("%s: E=%lld edges are beyond the workspace", who, E); return SFM_E_SHAPE; }
@@ -514,14 +466,7 @@ static int rot_check(const char* who, int V, long long E, const int* edges, cons
   if (steps < 1) { set_error("%s: steps = %d must be >= 1", who, steps); return SFM_E_SHAPE; }
   if (!(cg_tol > 0.0 && cg_tol < 1.0)) { set_error("%s: cg_tol = %g must be in (0, 1)", who, cg_tol); return SFM_E_SHAPE; }
   if (cg_max < 1) { set_error("%s: cg_max = %d must be >= 1", who, cg_max); return SFM_E_SHAPE; }
-  for (long long e = 0; e < E; ++e) {
-    const int i = edges[2 * e], j = edges[2 * e + 1];
-    if (i < 0 || i >= V || j < 0 || j >= V || i == j) { set_error("%s: edge %lld = (%d, %d) must join two different views in 0 .. %d", who, e, i, j, V - 1); return SFM_E_SHAPE; }
-  }
-  if (rel_on_host)
-    for (long long e = 0; e < E; ++e)
-      if (!verify_rotation(rel + 9 * e)) { set_error("%s: Rel of edge %lld is not a rotation", who, e); return SFM_E_BAD_ROTATION; }
-  return SFM_OK;
+  return view_graph_check_edges(who, V, E, edges);
 }
 
 // The breadth-first tree of hypothesis h on the host (the rule's step 2, without rotations).
@@ -558,25 +503,29 @@ struct RotWork {
   DevBuf<unsigned char> ok, mask, mask_try;
 };
 
+// The arguments of the kernels, but for the work buffers: the inputs and outputs of either form, on the device.
+static RotArgs rot_args(int V, long long E, const int* d_edges, const double* d_rel, int root, double cos_max, int iters, int steps,
+                        double cg_tol, int cg_max, double* R_out, unsigned char* edge_inlier, double* edge_cos, int* view_status,
+                        int* n_inliers, int* best_hyp, int* status, int64_t* summary) {
+  RotArgs a = {};
+  a.V = V; a.E = (int)E; a.root = root; a.edges = d_edges; a.rel = d_rel; a.thr = __builtin_fma(2.0, cos_max, 1.0);
+  a.iters = iters; a.steps = steps; a.cg_max = cg_max; a.cg_tol2 = cg_tol * cg_tol;
+  a.R_out = R_out; a.edge_inlier = edge_inlier; a.edge_cos = edge_cos; a.view_status = view_status;
+  a.n_inliers = n_inliers; a.best_hyp = best_hyp; a.status = status; a.summary = reinterpret_cast<unsigned long long*>(summary);
+  return a;
+}
+
 // The one body of both forms: checked arguments and device pointers in, everything enqueued on s.
-static int rot_run(const char* who, RotArgs a, int max_hyp, bool verify_on_device, RotWork& w, hipStream_t s) {
+static int rot_run(RotArgs a, int max_hyp, RotWork& w, hipStream_t s) {
   if (max_hyp == 0) max_hyp = kHypDefault;
   const int V = a.V, E = a.E;
   int batch, n_batches;
   rot_plan(V, max_hyp, &batch, &n_batches);
   SFM_TRY(w.st.alloc(kStWords, s));
-  const int st0[kStWords] = {-1, -1, 0, 0, 0, INT_MAX, 0, 0};
+  const int st0[kStWords] = {-1, -1, 0, 0, 0};
   SFM_HIP(hipMemcpyAsync(w.st.p, st0, sizeof(st0), hipMemcpyHostToDevice, s));
   a.st = w.st.p;
-  if (verify_on_device) {
-    rotavg_verify_kernel<<<(unsigned)((E + 255) / 256), 256, 0, s>>>(a);
-    int st[kStWords];
-    SFM_HIP(hipMemcpyAsync(st, w.st.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipStreamSynchronize(s));
-    if (st[kStBadEdge] != INT_MAX) { set_error("%s: Rel of edge %d is not a rotation", who, st[kStBadEdge]); return SFM_E_BAD_ROTATION; }
-  }
-  SFM_TRY(w.adj_ptr.alloc((size_t)V + 1, s)); SFM_TRY(w.adj.alloc((size_t)2 * E, s));
-  SFM_TRY(key_major_list(2LL * E, V, a.edges, w.adj_ptr.p, w.adj.p, s));
+  SFM_TRY(view_adjacency(V, E, a.edges, w.adj_ptr, w.adj, s));
   a.adj_ptr = w.adj_ptr.p; a.adj = w.adj.p;
   SFM_TRY(w.reach.alloc(V, s)); SFM_TRY(w.conn.alloc(V, s)); SFM_TRY(w.counts.alloc(batch, s)); SFM_TRY(w.ok.alloc(batch, s));
   SFM_TRY(w.rot.alloc((size_t)batch * V * 9, s)); SFM_TRY(w.R_cur.alloc((size_t)V * 9, s)); SFM_TRY(w.R_try.alloc((size_t)V * 9, s));
@@ -626,10 +575,8 @@ int sfm_rotation_edge_test(const double* Ri, const double* Rj, const double* Rel
 int sfm_rotation_tree(int V, int64_t E, const int* edges, int root, int max_hyp, int h, int* parent_edge_out, int* depth_out) {
   if (max_hyp == 0) max_hyp = kHypDefault;
   if (V < 2 || E < 1 || E > INT_MAX / 2 || edges == nullptr || root < 0 || root >= V || max_hyp < 1 || max_hyp > kHypMax) return 0;
-  for (int64_t e = 0; e < E; ++e) {
-    const int i = edges[2 * e], j = edges[2 * e + 1];
-    if (i < 0 || i >= V || j < 0 || j >= V || i == j) return 0;
-  }
+  for (int64_t e = 0; e < E; ++e)
+    if (!view_graph_edge_ok(V, edges[2 * e], edges[2 * e + 1])) return 0;
   if (h >= 0 && h < max_hyp && parent_edge_out != nullptr && depth_out != nullptr) rot_tree_host(V, E, edges, h, root, parent_edge_out, depth_out);
   return max_hyp;
 }
@@ -647,18 +594,16 @@ int sfm_rotation_average_dev(int V, int64_t E, const int* edges, const double* d
                              unsigned char* d_edge_inlier, double* d_edge_cos, int* d_view_status, int* d_n_inliers, int* d_best_hyp,
                              int* d_status, int64_t* d_summary, void* hip_stream) {
   const char* who = "sfm_rotation_average_dev";
-  SFM_TRY(rot_check(who, V, E, edges, d_rel, false, root, cos_max, max_hyp, iters, steps, cg_tol, cg_max, d_R_out));
+  SFM_TRY(rot_check(who, V, E, edges, d_rel, root, cos_max, max_hyp, iters, steps, cg_tol, cg_max, d_R_out));
   SFM_TRY(ensure_init());
   hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx().stream;
+  SFM_TRY(check_rotations_dev(who, "Rel of edge %lld", E, d_rel, false, s));
   DevBuf<int> dE;                       // the checked host copy: no kernel indexes with a value that was not looked at
   SFM_TRY(dE.upload(edges, 2 * (size_t)E, s));
-  RotArgs a = {};
-  a.V = V; a.E = (int)E; a.root = root; a.edges = dE.p; a.rel = d_rel; a.thr = __builtin_fma(2.0, cos_max, 1.0);
-  a.iters = iters; a.steps = steps; a.cg_max = cg_max; a.cg_tol2 = cg_tol * cg_tol;
-  a.R_out = d_R_out; a.edge_inlier = d_edge_inlier; a.edge_cos = d_edge_cos; a.view_status = d_view_status;
-  a.n_inliers = d_n_inliers; a.best_hyp = d_best_hyp; a.status = d_status; a.summary = reinterpret_cast<unsigned long long*>(d_summary);
+  const RotArgs a = rot_args(V, E, dE.p, d_rel, root, cos_max, iters, steps, cg_tol, cg_max, d_R_out, d_edge_inlier, d_edge_cos,
+                             d_view_status, d_n_inliers, d_best_hyp, d_status, d_summary);
   RotWork w;
-  SFM_TRY(rot_run(who, a, max_hyp, true, w, s));
+  SFM_TRY(rot_run(a, max_hyp, w, s));
   return stream_sync(s);
 }
 
@@ -666,7 +611,8 @@ int sfm_rotation_average(int V, int64_t E, const int* edges, const double* rel, 
                          int steps, double cg_tol, int cg_max, double* R_out, unsigned char* edge_inlier, double* edge_cos,
                          int* view_status, int* n_inliers, int* best_hyp, int* status, int64_t* summary) {
   const char* who = "sfm_rotation_average";
-  SFM_TRY(rot_check(who, V, E, edges, rel, true, root, cos_max, max_hyp, iters, steps, cg_tol, cg_max, R_out));
+  SFM_TRY(rot_check(who, V, E, edges, rel, root, cos_max, max_hyp, iters, steps, cg_tol, cg_max, R_out));
+  SFM_TRY(check_rotations_host(who, "Rel of edge %lld", E, rel, false));
   SFM_TRY(ensure_init());
   hipStream_t s = ctx().stream;
   const size_t v = (size_t)V, m = (size_t)E;
@@ -682,12 +628,9 @@ int sfm_rotation_average(int V, int64_t E, const int* edges, const double* rel, 
   SFM_TRY(oR.want(R_out, 9 * v, s)); SFM_TRY(oCos.want(edge_cos, m, s)); SFM_TRY(oIn.want(edge_inlier, m, s));
   SFM_TRY(oView.want(view_status, v, s)); SFM_TRY(oN.want(n_inliers, 1, s)); SFM_TRY(oBest.want(best_hyp, 1, s));
   SFM_TRY(oStatus.want(status, 1, s)); SFM_TRY(oSum.want(summary, 6, s));
-  RotArgs a = {};
-  a.V = V; a.E = (int)E; a.root = root; a.edges = dE.p; a.rel = dRel.p; a.thr = __builtin_fma(2.0, cos_max, 1.0);
-  a.iters = iters; a.steps = steps; a.cg_max = cg_max; a.cg_tol2 = cg_tol * cg_tol;
-  a.R_out = oR.dev(); a.edge_inlier = oIn.dev(); a.edge_cos = oCos.dev(); a.view_status = oView.dev();
-  a.n_inliers = oN.dev(); a.best_hyp = oBest.dev(); a.status = oStatus.dev(); a.summary = reinterpret_cast<unsigned long long*>(oSum.dev());
-  SFM_TRY(rot_run(who, a, max_hyp, false, w, s));
+  const RotArgs a = rot_args(V, E, dE.p, dRel.p, root, cos_max, iters, steps, cg_tol, cg_max, oR.dev(), oIn.dev(), oCos.dev(), oView.dev(),
+                             oN.dev(), oBest.dev(), oStatus.dev(), oSum.dev());
+  SFM_TRY(rot_run(a, max_hyp, w, s));
   SFM_TRY(oR.fetch(s)); SFM_TRY(oCos.fetch(s)); SFM_TRY(oIn.fetch(s)); SFM_TRY(oView.fetch(s)); SFM_TRY(oN.fetch(s));
   SFM_TRY(oBest.fetch(s)); SFM_TRY(oStatus.fetch(s)); SFM_TRY(oSum.fetch(s));
   return stream_sync(s);

@@ -3,24 +3,22 @@
 // From the unit translations on the edges of a view graph, some of them wrong, and the absolute rotations of its views, one
 // position per view and the verdict on every edge.  The rule is stated in sfm_hip.h, block "translation averaging".  One
 // graph per call; the stages:
-//   adjacency  the view-major list of the 2 E edge ends (entry x = 2 e + dir, dir = 1 where the view is the edge's j): the
-//              key-major list of sfm_common.h, as the rotation averaging builds it
-//   verify     the _dev form only: the lowest view whose non-zero R fails verify_rotation
+//   adjacency  the view-major list of the 2 E edge ends (view_adjacency of sfm_view_graph.h)
+//   verify     the _dev form only: the lowest view whose non-zero R fails verify_rotation (check_rotations_dev)
 //   direct     a lane per edge: d_e = -R_j^T t_e normalised, the used flag, the weights and lengths of round 0
-//   conn       one workgroup: breadth-first levels from root over the edges that take part (w_e > 0) or over a byte mask
+//   conn       one workgroup: breadth-first levels (graph_levels) from root over the edges that take part (w_e > 0) or over
+//              a byte mask
 //   solve      the hot path, one workgroup per solve: the diagonal blocks, their inverses and the right-hand side per view
 //              over its adjacency, block-Jacobi CG with q = A p formed on the fly from d_e and w_e (nothing of size E x 9 is
-//              stored), every dot product per slice of 64 views in slice order, the convergence test; then the edge pass:
+//              stored), every dot product by block_dot, the convergence test; then the edge pass:
 //              the verdicts, the count, the cost, the weights and lengths of the next solve, and for the polish the stand
 //              decision, all on the device
 //   output     one workgroup: the outputs
 // No floating-point value is accumulated with an atomic; the counts are integers.
-#include <climits>
 #include <cmath>
-#include <vector>
 
 #include "sfm_obs_test.h"      // contraction is off from here on
-#include "sfm_robust.h"
+#include "sfm_view_graph.h"
 
 namespace sfm {
 
@@ -28,7 +26,7 @@ constexpr int kTrBlock = 1024;               // the one workgroup of solve and o
 constexpr int kTrConnThreads = 256;
 
 // state words of a call on the device
-enum { kTsNoModel = 0, kTsCount = 1, kTsFlags = 2, kTsBadView = 3, kTsWords = 4 };
+enum { kTsNoModel = 0, kTsCount = 1, kTsFlags = 2, kTsWords = 3 };
 enum { kTrRound = 0, kTrLastRound = 1, kTrPolish = 2 };
 
 struct TrArgs {
@@ -65,23 +63,6 @@ struct TrArgs {
   double* log;                  // [rounds + 2][4] or null
 };
 
-__device__ __forceinline__ bool tr_has_rotation(const double* R) {
-  bool any = false;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) any |= R[k] != 0.0;
-  return any;
-}
-
-// the lowest view whose non-zero R fails verify_rotation (the _dev form: the host form looks on the host)
-__global__ __launch_bounds__(256) void transavg_verify_kernel(TrArgs a) {
-  const int v = blockIdx.x * 256 + threadIdx.x;
-  if (v >= a.V) return;
-  double R[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) R[k] = a.R[(size_t)v * 9 + k];
-  if (tr_has_rotation(R) && !verify_rotation(R)) atomicMin(&a.st[kTsBadView], v);
-}
-
 // ---------------------------------------------------------------------------------------------
 // direct: step 1, and the weights and lengths of round 0
 // ---------------------------------------------------------------------------------------------
@@ -98,7 +79,7 @@ __global__ __launch_bounds__(256) void transavg_direct_kernel(TrArgs a) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) u[c] = -__builtin_fma(Rj[c], t0, __builtin_fma(Rj[3 + c], t1, Rj[6 + c] * t2));
   const double m = __builtin_fma(u[0], u[0], __builtin_fma(u[1], u[1], u[2] * u[2])), len = sqrt(m);
-  const bool used = (a.edge_mask == nullptr || a.edge_mask[e] != 0) && tr_has_rotation(Ri) && tr_has_rotation(Rj) &&
+  const bool used = (a.edge_mask == nullptr || a.edge_mask[e] != 0) && has_rotation(Ri) && has_rotation(Rj) &&
                     __builtin_isfinite(tt) && tt > 0.0;
 #pragma unroll
   for (int c = 0; c < 3; ++c) a.d[3 * e + c] = used ? u[c] / len : 0.0;
@@ -114,57 +95,21 @@ __global__ __launch_bounds__(256) void transavg_direct_kernel(TrArgs a) {
 __global__ __launch_bounds__(kTrConnThreads) void transavg_conn_kernel(TrArgs a, const double* w, const unsigned char* mask, int* depth,
                                                                        int flag_root) {
   if (a.st[kTsNoModel]) return;
-  const int tid = threadIdx.x, V = a.V;
-  for (int v = tid; v < V; v += kTrConnThreads) depth[v] = v == a.root ? 0 : -1;
-  __syncthreads();
-  int any = 0;
-  for (int lev = 1; lev < V; ++lev) {            // a level adds at least one view, so V - 1 levels at the most
-    int added = 0;
-    for (int v = tid; v < V; v += kTrConnThreads) {
-      if (depth[v] != -1) continue;
-      bool hit = false;
-      for (int k = a.adj_ptr[v]; k < a.adj_ptr[v + 1] && !hit; ++k) {
-        const int x = a.adj[k], e = x >> 1;
-        if (w ? !(w[e] > 0.0) : !mask[e]) continue;
-        // a view that takes its depth in this very level holds -1 or lev here, never lev - 1
-        hit = depth[a.edges[x ^ 1]] == lev - 1;
-      }
-      if (hit) { depth[v] = lev; added = 1; }
+  const bool any = graph_levels<kTrConnThreads>(a.V, a.root, depth, [&](int v, int lev) {
+    bool hit = false;
+    for (int k = a.adj_ptr[v]; k < a.adj_ptr[v + 1] && !hit; ++k) {
+      const int x = a.adj[k], e = x >> 1;
+      if (w ? !(w[e] > 0.0) : !mask[e]) continue;
+      hit = depth[a.edges[x ^ 1]] == lev - 1;
     }
-    if (!__syncthreads_or(added)) break;
-    any = 1;
-  }
-  if (flag_root && !any && tid == 0) a.st[kTsNoModel] = 1;      // root has no used edge (or no rotation: then none of its edges is used)
+    return hit;
+  });
+  if (flag_root && !any && threadIdx.x == 0) a.st[kTsNoModel] = 1;      // root has no used edge (or no rotation: then none of its edges is used)
 }
 
 // ---------------------------------------------------------------------------------------------
 // solve: one solve of the rule and the edge pass after it, one workgroup
 // ---------------------------------------------------------------------------------------------
-// The workgroup's sum of one value per item: chunks of kTrBlock items, a wave's 64 items summed in the wave (group_sum<64>'s
-// fixed order), the slices then added in slice order by thread 0.  val(k) is called once for every k < n.  Every thread
-// returns the total.  The barriers also order the global-memory vectors between the phases of the CG.
-template <class Val>
-__device__ __forceinline__ double tr_block_dot(int n, Val val, double* red, double* total) {
-  const int tid = threadIdx.x;
-  double run = 0.0;
-  for (int base = 0; base < n; base += kTrBlock) {
-    const int k = base + tid;
-    const double s = group_sum<64>(k < n ? val(k) : 0.0);
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) {
-      const int slices = (min(n - base, kTrBlock) + 63) / 64;
-      for (int q = 0; q < slices; ++q) run += red[q];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) *total = run;
-  __syncthreads();
-  const double t = *total;
-  __syncthreads();
-  return t;
-}
-
 // z = B_e y = w (y - (1 - mu) d (d . y)), added onto acc
 __device__ __forceinline__ void tr_edge_block(const double* d, double w, double om, double y0, double y1, double y2, double* acc) {
   const double g = om * __builtin_fma(d[0], y0, __builtin_fma(d[1], y1, d[2] * y2));
@@ -235,9 +180,9 @@ __global__ __launch_bounds__(kTrBlock) void transavg_solve_kernel(TrArgs a, int 
   auto dot3 = [&](const double* x, const double* y, int v) {
     return __builtin_fma(x[3 * (size_t)v + 2], y[3 * (size_t)v + 2], __builtin_fma(x[3 * (size_t)v + 1], y[3 * (size_t)v + 1], x[3 * (size_t)v] * y[3 * (size_t)v]));
   };
-  const double bb = tr_block_dot(V, [&](int v) { return dot3(vb, vb, v); }, red, &total);
-  const double rr0 = tr_block_dot(V, [&](int v) { return dot3(vr, vr, v); }, red, &total);
-  double rz = tr_block_dot(V, [&](int v) { return dot3(vr, vz, v); }, red, &total);
+  const double bb = block_dot<kTrBlock>(V, [&](int v) { return dot3(vb, vb, v); }, red, &total);
+  const double rr0 = block_dot<kTrBlock>(V, [&](int v) { return dot3(vr, vr, v); }, red, &total);
+  double rz = block_dot<kTrBlock>(V, [&](int v) { return dot3(vr, vz, v); }, red, &total);
   bool done = rr0 <= a.cg_tol2 * bb;
   int iters = 0;
   for (int it = 0; it < a.cg_max && !done; ++it) {
@@ -249,7 +194,7 @@ __global__ __launch_bounds__(kTrBlock) void transavg_solve_kernel(TrArgs a, int 
       for (int c = 0; c < 3; ++c) vq[3 * (size_t)v + c] = q[c];
     }
     __syncthreads();
-    const double pq = tr_block_dot(V, [&](int v) { return dot3(vp, vq, v); }, red, &total);
+    const double pq = block_dot<kTrBlock>(V, [&](int v) { return dot3(vp, vq, v); }, red, &total);
     const double alpha = rz / pq;
     for (int v = tid; v < V; v += kTrBlock) {
       const double* inv = a.dinv + 6 * (size_t)v;
@@ -267,9 +212,9 @@ __global__ __launch_bounds__(kTrBlock) void transavg_solve_kernel(TrArgs a, int 
     }
     __syncthreads();
     ++iters;
-    const double rr = tr_block_dot(V, [&](int v) { return dot3(vr, vr, v); }, red, &total);
+    const double rr = block_dot<kTrBlock>(V, [&](int v) { return dot3(vr, vr, v); }, red, &total);
     if (rr <= a.cg_tol2 * bb) { done = true; break; }
-    const double rz_new = tr_block_dot(V, [&](int v) { return dot3(vr, vz, v); }, red, &total);
+    const double rz_new = block_dot<kTrBlock>(V, [&](int v) { return dot3(vr, vz, v); }, red, &total);
     const double beta = rz_new / rz;
     rz = rz_new;
     for (size_t k = tid; k < n3; k += kTrBlock) vp[k] = __builtin_fma(beta, vp[k], vz[k]);
@@ -288,7 +233,7 @@ __global__ __launch_bounds__(kTrBlock) void transavg_solve_kernel(TrArgs a, int 
   // the edge pass over the positions of this solve: verdict, cost under the weights of this solve, the next weights and lengths
   unsigned char* verdict = mode == kTrPolish ? a.mask_try : a.mask;
   int mine = 0;
-  const double cost = tr_block_dot(a.E, [&](int e) {
+  const double cost = block_dot<kTrBlock>(a.E, [&](int e) {
     if (!a.used[e]) { verdict[e] = 0; return 0.0; }
     const int i = a.edges[2 * (size_t)e], j = a.edges[2 * (size_t)e + 1];
     const double d[3] = {a.d[3 * (size_t)e], a.d[3 * (size_t)e + 1], a.d[3 * (size_t)e + 2]};
@@ -331,7 +276,7 @@ __global__ __launch_bounds__(kTrBlock) void transavg_solve_kernel(TrArgs a, int 
 // output: step 6
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kTrBlock) void transavg_output_kernel(TrArgs a) {
-  __shared__ int lds_total;
+  __shared__ int lds_sums[6];
   const int tid = threadIdx.x;
   const bool model = a.st[kTsNoModel] == 0;
   const double nan = __builtin_nan("");
@@ -354,24 +299,21 @@ __global__ __launch_bounds__(kTrBlock) void transavg_output_kernel(TrArgs a) {
     double R[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = a.R[(size_t)v * 9 + k];
-    const bool norot = !tr_has_rotation(R), unreached = a.reach[v] < 0, has = model && !unreached, held = !(model && a.conn[v] >= 0);
+    const bool norot = !has_rotation(R), unreached = a.reach[v] < 0, has = model && !unreached, held = !(model && a.conn[v] >= 0);
 #pragma unroll
     for (int c = 0; c < 3; ++c) a.C_out[3 * (size_t)v + c] = has ? a.C[3 * (size_t)v + c] : 0.0;
     if (a.view_status)
       a.view_status[v] = (norot ? SFM_TRANSAVG_NO_ROTATION : 0) | (unreached ? SFM_TRANSAVG_UNREACHED : 0) | (held ? SFM_TRANSAVG_HELD : 0);
     n_pos += has; n_norot += norot; n_unreached += unreached; n_held += held;
   }
-  n_in = block_sum_int(n_in, &lds_total); __syncthreads();
-  n_out = block_sum_int(n_out, &lds_total); __syncthreads();
-  n_pos = block_sum_int(n_pos, &lds_total); __syncthreads();
-  n_norot = block_sum_int(n_norot, &lds_total); __syncthreads();
-  n_unreached = block_sum_int(n_unreached, &lds_total); __syncthreads();
-  n_held = block_sum_int(n_held, &lds_total);
+  int n[6] = {n_pos, n_norot, n_unreached, n_held, n_in, n_out};       // the order of the summary
+  block_sums(n, lds_sums);
   if (tid != 0) return;
-  if (a.n_inliers) *a.n_inliers = n_in;
+  if (a.n_inliers) *a.n_inliers = n[4];
   if (a.status) *a.status = model ? a.st[kTsFlags] : SFM_TRANSAVG_NO_MODEL;
   if (a.summary) {
-    a.summary[0] = n_pos; a.summary[1] = n_norot; a.summary[2] = n_unreached; a.summary[3] = n_held; a.summary[4] = n_in; a.summary[5] = n_out;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a.summary[k] = n[k];
   }
   if (a.log && !model)
     for (int k = 0; k < 4 * (a.rounds + 2); ++k) a.log[k] = 0.0;
@@ -382,13 +324,7 @@ __global__ __launch_bounds__(kTrBlock) void transavg_output_kernel(TrArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static bool tr_has_rotation_host(const double* R) {
-  for (int k = 0; k < 9; ++k)
-    if (R[k] != 0.0) return true;
-  return false;
-}
-
-static int tr_check(const char* who, int V, long long E, const int* edges, const double* R, bool R_on_host, const double* t, int root,
+static int tr_check(const char* who, int V, long long E, const int* edges, const double* R, const double* t, int root,
                     double cos_max, double mu, int rounds, int polish, double cg_tol, int cg_max, const void* C_out) {
   if (V < 2 || E < 1 || E >= (1LL << 30)) { set_error("%s: bad sizes V=%d E=%lld (V >= 2, 1 <= E < 2^30)", who, V, E); return SFM_E_SHAPE; }
   if (edges == nullptr || R == nullptr || t == nullptr || C_out == nullptr) { set_error("%s: null pointer", who); return SFM_E_SHAPE; }
@@ -399,14 +335,7 @@ static int tr_check(const char* who, int V, long long E, const int* edges, const
   if (polish != 0 && polish != 1) { set_error("%s: polish = %d must be 0 or 1", who, polish); return SFM_E_SHAPE; }
   if (!(cg_tol > 0.0 && cg_tol < 1.0)) { set_error("%s: cg_tol = %g must be in (0, 1)", who, cg_tol); return SFM_E_SHAPE; }
   if (cg_max < 1) { set_error("%s: cg_max = %d must be >= 1", who, cg_max); return SFM_E_SHAPE; }
-  for (long long e = 0; e < E; ++e) {
-    const int i = edges[2 * e], j = edges[2 * e + 1];
-    if (i < 0 || i >= V || j < 0 || j >= V || i == j) { set_error("%s: edge %lld = (%d, %d) must join two different views in 0 .. %d", who, e, i, j, V - 1); return SFM_E_SHAPE; }
-  }
-  if (R_on_host)
-    for (int v = 0; v < V; ++v)
-      if (tr_has_rotation_host(R + 9 * (size_t)v) && !verify_rotation(R + 9 * (size_t)v)) { set_error("%s: R of view %d is not a rotation", who, v); return SFM_E_BAD_ROTATION; }
-  return SFM_OK;
+  return view_graph_check_edges(who, V, E, edges);
 }
 
 struct TrWork {
@@ -415,28 +344,28 @@ struct TrWork {
   DevBuf<unsigned char> used, mask, mask_try;
 };
 
-static void tr_options(TrArgs& a, double cos_max, double mu, int rounds, int polish, double cg_tol, int cg_max) {
+// The arguments of the kernels, but for the work buffers: the inputs and outputs of either form, on the device.
+static TrArgs tr_args(int V, long long E, const int* d_edges, const double* d_R, const double* d_t, const unsigned char* d_edge_mask, int root,
+                      double cos_max, double mu, int rounds, int polish, double cg_tol, int cg_max, double* C_out, unsigned char* edge_inlier,
+                      double* edge_cos, double* edge_len, int* view_status, int* n_inliers, int* status, int64_t* summary, double* log) {
+  TrArgs a = {};
+  a.V = V; a.E = (int)E; a.root = root; a.edges = d_edges; a.R = d_R; a.t = d_t; a.edge_mask = d_edge_mask;
   if (mu == 0.0) mu = 0.01;
   a.cc = cos_max * cos_max; a.sigma2 = 2.0 - 2.0 * cos_max; a.mu = mu; a.om = 1.0 - mu;
   a.rounds = rounds; a.polish = polish; a.cg_max = cg_max; a.cg_tol2 = cg_tol * cg_tol;
+  a.C_out = C_out; a.edge_inlier = edge_inlier; a.edge_cos = edge_cos; a.edge_len = edge_len; a.view_status = view_status;
+  a.n_inliers = n_inliers; a.status = status; a.summary = reinterpret_cast<unsigned long long*>(summary); a.log = log;
+  return a;
 }
 
 // The one body of both forms: checked arguments and device pointers in, everything enqueued on s.
-static int tr_run(const char* who, TrArgs a, bool verify_on_device, TrWork& w, hipStream_t s) {
+static int tr_run(TrArgs a, TrWork& w, hipStream_t s) {
   const int V = a.V, E = a.E;
   SFM_TRY(w.st.alloc(kTsWords, s));
-  const int st0[kTsWords] = {0, 0, 0, INT_MAX};
+  const int st0[kTsWords] = {0, 0, 0};
   SFM_HIP(hipMemcpyAsync(w.st.p, st0, sizeof(st0), hipMemcpyHostToDevice, s));
   a.st = w.st.p;
-  if (verify_on_device) {
-    transavg_verify_kernel<<<(unsigned)((V + 255) / 256), 256, 0, s>>>(a);
-    int st[kTsWords];
-    SFM_HIP(hipMemcpyAsync(st, w.st.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipStreamSynchronize(s));
-    if (st[kTsBadView] != INT_MAX) { set_error("%s: R of view %d is not a rotation", who, st[kTsBadView]); return SFM_E_BAD_ROTATION; }
-  }
-  SFM_TRY(w.adj_ptr.alloc((size_t)V + 1, s)); SFM_TRY(w.adj.alloc((size_t)2 * E, s));
-  SFM_TRY(key_major_list(2LL * E, V, a.edges, w.adj_ptr.p, w.adj.p, s));
+  SFM_TRY(view_adjacency(V, E, a.edges, w.adj_ptr, w.adj, s));
   a.adj_ptr = w.adj_ptr.p; a.adj = w.adj.p;
   SFM_TRY(w.reach.alloc(V, s)); SFM_TRY(w.conn.alloc(V, s)); SFM_TRY(w.used.alloc(E, s)); SFM_TRY(w.mask.alloc(E, s)); SFM_TRY(w.mask_try.alloc(E, s));
   SFM_TRY(w.d.alloc((size_t)3 * E, s)); SFM_TRY(w.w.alloc(E, s)); SFM_TRY(w.l.alloc(E, s));
@@ -484,18 +413,16 @@ int sfm_translation_average_dev(int V, int64_t E, const int* edges, const double
                                 unsigned char* d_edge_inlier, double* d_edge_cos, double* d_edge_len, int* d_view_status, int* d_n_inliers,
                                 int* d_status, int64_t* d_summary, double* d_log, void* hip_stream) {
   const char* who = "sfm_translation_average_dev";
-  SFM_TRY(tr_check(who, V, E, edges, d_R, false, d_t, root, cos_max, mu, rounds, polish, cg_tol, cg_max, d_C_out));
+  SFM_TRY(tr_check(who, V, E, edges, d_R, d_t, root, cos_max, mu, rounds, polish, cg_tol, cg_max, d_C_out));
   SFM_TRY(ensure_init());
   hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx().stream;
+  SFM_TRY(check_rotations_dev(who, "R of view %lld", V, d_R, true, s));
   DevBuf<int> dE;                       // the checked host copy: no kernel indexes with a value that was not looked at
   SFM_TRY(dE.upload(edges, 2 * (size_t)E, s));
-  TrArgs a = {};
-  a.V = V; a.E = (int)E; a.root = root; a.edges = dE.p; a.R = d_R; a.t = d_t; a.edge_mask = d_edge_mask;
-  tr_options(a, cos_max, mu, rounds, polish, cg_tol, cg_max);
-  a.C_out = d_C_out; a.edge_inlier = d_edge_inlier; a.edge_cos = d_edge_cos; a.edge_len = d_edge_len; a.view_status = d_view_status;
-  a.n_inliers = d_n_inliers; a.status = d_status; a.summary = reinterpret_cast<unsigned long long*>(d_summary); a.log = d_log;
+  const TrArgs a = tr_args(V, E, dE.p, d_R, d_t, d_edge_mask, root, cos_max, mu, rounds, polish, cg_tol, cg_max, d_C_out, d_edge_inlier,
+                           d_edge_cos, d_edge_len, d_view_status, d_n_inliers, d_status, d_summary, d_log);
   TrWork w;
-  SFM_TRY(tr_run(who, a, true, w, s));
+  SFM_TRY(tr_run(a, w, s));
   return stream_sync(s);
 }
 
@@ -504,7 +431,8 @@ int sfm_translation_average(int V, int64_t E, const int* edges, const double* R,
                             unsigned char* edge_inlier, double* edge_cos, double* edge_len, int* view_status, int* n_inliers, int* status,
                             int64_t* summary, double* log) {
   const char* who = "sfm_translation_average";
-  SFM_TRY(tr_check(who, V, E, edges, R, true, t, root, cos_max, mu, rounds, polish, cg_tol, cg_max, C_out));
+  SFM_TRY(tr_check(who, V, E, edges, R, t, root, cos_max, mu, rounds, polish, cg_tol, cg_max, C_out));
+  SFM_TRY(check_rotations_host(who, "R of view %lld", V, R, true));
   SFM_TRY(ensure_init());
   hipStream_t s = ctx().stream;
   const size_t v = (size_t)V, m = (size_t)E;
@@ -521,12 +449,9 @@ int sfm_translation_average(int V, int64_t E, const int* edges, const double* R,
   SFM_TRY(oC.want(C_out, 3 * v, s)); SFM_TRY(oCos.want(edge_cos, m, s)); SFM_TRY(oLen.want(edge_len, m, s)); SFM_TRY(oIn.want(edge_inlier, m, s));
   SFM_TRY(oView.want(view_status, v, s)); SFM_TRY(oN.want(n_inliers, 1, s)); SFM_TRY(oStatus.want(status, 1, s));
   SFM_TRY(oSum.want(summary, 6, s)); SFM_TRY(oLog.want(log, 4 * (size_t)(rounds + 2), s));
-  TrArgs a = {};
-  a.V = V; a.E = (int)E; a.root = root; a.edges = dE.p; a.R = dR.p; a.t = dT.p; a.edge_mask = dMask.p;
-  tr_options(a, cos_max, mu, rounds, polish, cg_tol, cg_max);
-  a.C_out = oC.dev(); a.edge_inlier = oIn.dev(); a.edge_cos = oCos.dev(); a.edge_len = oLen.dev(); a.view_status = oView.dev();
-  a.n_inliers = oN.dev(); a.status = oStatus.dev(); a.summary = reinterpret_cast<unsigned long long*>(oSum.dev()); a.log = oLog.dev();
-  SFM_TRY(tr_run(who, a, false, w, s));
+  const TrArgs a = tr_args(V, E, dE.p, dR.p, dT.p, dMask.p, root, cos_max, mu, rounds, polish, cg_tol, cg_max, oC.dev(), oIn.dev(),
+                           oCos.dev(), oLen.dev(), oView.dev(), oN.dev(), oStatus.dev(), oSum.dev(), oLog.dev());
+  SFM_TRY(tr_run(a, w, s));
   SFM_TRY(oC.fetch(s)); SFM_TRY(oCos.fetch(s)); SFM_TRY(oLen.fetch(s)); SFM_TRY(oIn.fetch(s)); SFM_TRY(oView.fetch(s));
   SFM_TRY(oN.fetch(s)); SFM_TRY(oStatus.fetch(s)); SFM_TRY(oSum.fetch(s)); SFM_TRY(oLog.fetch(s));
   return stream_sync(s);

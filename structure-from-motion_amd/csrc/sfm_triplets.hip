@@ -19,7 +19,7 @@
 #include <cmath>
 
 #include "sfm_obs_test.h"      // contraction is off from here on
-#include "sfm_robust.h"
+#include "sfm_view_graph.h"
 #include "sfm_scan.h"
 
 namespace sfm {
@@ -29,8 +29,8 @@ constexpr int kTriScanCrossover = 1 << 14;      // the device-wide scan from thi
 
 typedef unsigned long long u64;
 
-// state words of a call on the device (64-bit each)
-enum { kTsBad = 0, kTsTri, kTsOk, kTsTested, kTsKept, kTsDropped, kTsUntested, kTsMasked, kTsLargest, kTsNKept, kTsWords };
+// state words of a call on the device (64-bit counters)
+enum { kTsTri = 0, kTsOk, kTsTested, kTsKept, kTsDropped, kTsUntested, kTsMasked, kTsLargest, kTsNKept, kTsWords };
 
 struct TriArgs {
   int V, E;
@@ -61,13 +61,6 @@ __device__ __forceinline__ void tri_oriented(const TriArgs& a, int e, double* M)
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int c = 0; c < 3; ++c) M[3 * r + c] = tr ? R[3 * c + r] : R[3 * r + c];
-}
-
-template <int G>
-__device__ __forceinline__ long long tri_group_sum(long long v) {
-#pragma unroll
-  for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -146,8 +139,8 @@ __global__ __launch_bounds__(kTriThreads) void triplets_enumerate_kernel(TriArgs
         }
       }
     }
-    nt = tri_group_sum<G>(nt);
-    nk = tri_group_sum<G>(nk);
+    nt = group_sum<G>(nt);
+    nk = group_sum<G>(nk);
     if (live && lane == 0) {
       a.n_tri[e] = nt;
       a.n_ok[e] = nk;
@@ -170,7 +163,7 @@ __global__ __launch_bounds__(256) void triplets_summary_kernel(TriArgs a) {
     largest = nt > largest ? nt : largest;
   }
 #pragma unroll
-  for (int k = 0; k < 7; ++k) v[k] = tri_group_sum<64>(v[k]);
+  for (int k = 0; k < 7; ++k) v[k] = group_sum<64>(v[k]);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) { const long long o = __shfl_xor(largest, off, 64); largest = o > largest ? o : largest; }
   if ((threadIdx.x & 63) != 0) return;
@@ -198,23 +191,13 @@ struct TriScanKept {
   }
 };
 
-// the lowest edge whose Rel fails verify_rotation (the _dev form: the host form looks on the host)
-__global__ __launch_bounds__(256) void triplets_verify_kernel(TriArgs a) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= a.E) return;
-  double Rel[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) Rel[k] = a.rel[(size_t)e * 9 + k];
-  if (!verify_rotation(Rel)) atomicMin(&a.st[kTsBad], (u64)e);
-}
-
 #pragma clang fp contract(on)
 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int tri_check(const char* who, int V, long long E, const int* edges, const double* rel, bool rel_on_host, double cos_loop, int min_ok,
-                     int min_pct, int keep_untested, int group) {
+static int tri_check(const char* who, int V, long long E, const int* edges, const double* rel, double cos_loop, int min_ok, int min_pct,
+                     int keep_untested, int group) {
   if (V < 3 || E < 1 || E >= (1LL << 30)) { set_error("%s: bad sizes V=%d E=%lld (V >= 3, 1 <= E < 2^30)", who, V, E); return SFM_E_SHAPE; }
   if (edges == nullptr || rel == nullptr) { set_error("%s: null pointer", who); return SFM_E_SHAPE; }
   if (!(cos_loop > 0.0 && cos_loop <= 1.0)) { set_error("%s: cos_loop = %g must be in (0, 1]", who, cos_loop); return SFM_E_SHAPE; }
@@ -222,14 +205,7 @@ static int tri_check(const char* who, int V, long long E, const int* edges, cons
   if (min_pct < 0 || min_pct > 100) { set_error("%s: min_pct = %d must be in 0 .. 100", who, min_pct); return SFM_E_SHAPE; }
   if (keep_untested != 0 && keep_untested != 1) { set_error("%s: keep_untested = %d must be 0 or 1", who, keep_untested); return SFM_E_SHAPE; }
   SFM_TRY(group_width_check(who, group));
-  for (long long e = 0; e < E; ++e) {
-    const int i = edges[2 * e], j = edges[2 * e + 1];
-    if (i < 0 || i >= V || j < 0 || j >= V || i == j) { set_error("%s: edge %lld = (%d, %d) must join two different views in 0 .. %d", who, e, i, j, V - 1); return SFM_E_SHAPE; }
-  }
-  if (rel_on_host)
-    for (long long e = 0; e < E; ++e)
-      if (!verify_rotation(rel + 9 * e)) { set_error("%s: Rel of edge %lld is not a rotation", who, e); return SFM_E_BAD_ROTATION; }
-  return SFM_OK;
+  return view_graph_check_edges(who, V, E, edges);
 }
 
 // `group` = 0: the narrowest width that covers the mean adjacency, wider while the device would be short of waves
@@ -239,8 +215,20 @@ static int tri_auto_group(int V, long long E) {
   return kGroupWidths[widen_for_waves(i, (int)E, 64)];
 }
 
+// The arguments of the kernels, but for the work buffers: the inputs and outputs of either form, on the device.
+static TriArgs tri_args(int V, long long E, const int* d_edges, const double* d_rel, const unsigned char* d_edge_mask, double cos_loop,
+                        int min_ok, int min_pct, int keep_untested, unsigned char* edge_keep, int64_t* n_tri, int64_t* n_ok, int* kept_idx,
+                        int64_t* summary) {
+  TriArgs a = {};
+  a.V = V; a.E = (int)E; a.edges = d_edges; a.rel = d_rel; a.mask = d_edge_mask; a.thr = __builtin_fma(2.0, cos_loop, 1.0);
+  a.min_ok = min_ok == 0 ? 1 : min_ok; a.min_pct = min_pct; a.keep_untested = keep_untested;
+  a.keep = edge_keep; a.n_tri = reinterpret_cast<long long*>(n_tri); a.n_ok = reinterpret_cast<long long*>(n_ok);
+  a.kept_idx = kept_idx; a.summary = reinterpret_cast<long long*>(summary);
+  return a;
+}
+
 // The one body of both forms: checked arguments and device pointers in, everything enqueued on s; *n_kept is read at the end.
-static int tri_run(const char* who, TriArgs a, int group, bool verify_on_device, int* n_kept, hipStream_t s) {
+static int tri_run(TriArgs a, int group, int* n_kept, hipStream_t s) {
   const int V = a.V, E = a.E;
   const size_t ends = 2 * (size_t)E;
   DevBuf<u64> st;
@@ -248,18 +236,10 @@ static int tri_run(const char* who, TriArgs a, int group, bool verify_on_device,
   DevBuf<unsigned char> keep;
   DevBuf<long long> n_tri, n_ok;
   SFM_TRY(st.alloc(kTsWords, s));
-  u64 st0[kTsWords] = {};
-  st0[kTsBad] = ~0ULL;
+  const u64 st0[kTsWords] = {};
   SFM_HIP(hipMemcpyAsync(st.p, st0, sizeof(st0), hipMemcpyHostToDevice, s));
   a.st = st.p;
   const unsigned edge_blocks = (unsigned)((E + 255) / 256), end_blocks = (unsigned)((ends + 255) / 256);
-  if (verify_on_device) {
-    triplets_verify_kernel<<<edge_blocks, 256, 0, s>>>(a);
-    u64 bad = 0;
-    SFM_HIP(hipMemcpyAsync(&bad, st.p + kTsBad, sizeof(bad), hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipStreamSynchronize(s));
-    if (bad != ~0ULL) { set_error("%s: Rel of edge %llu is not a rotation", who, bad); return SFM_E_BAD_ROTATION; }
-  }
   if (a.keep == nullptr) { SFM_TRY(keep.alloc(E, s)); a.keep = keep.p; }
   if (a.n_tri == nullptr) { SFM_TRY(n_tri.alloc(E, s)); a.n_tri = n_tri.p; }
   if (a.n_ok == nullptr) { SFM_TRY(n_ok.alloc(E, s)); a.n_ok = n_ok.p; }
@@ -310,17 +290,15 @@ int sfm_view_triplets_dev(int V, int64_t E, const int* edges, const double* d_re
                           int min_ok, int min_pct, int keep_untested, int group, unsigned char* d_edge_keep, int64_t* d_n_tri,
                           int64_t* d_n_ok, int* d_kept_idx, int64_t* d_summary, int* n_kept, void* hip_stream) {
   const char* who = "sfm_view_triplets_dev";
-  SFM_TRY(tri_check(who, V, E, edges, d_rel, false, cos_loop, min_ok, min_pct, keep_untested, group));
+  SFM_TRY(tri_check(who, V, E, edges, d_rel, cos_loop, min_ok, min_pct, keep_untested, group));
   SFM_TRY(ensure_init());
   hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx().stream;
+  SFM_TRY(check_rotations_dev(who, "Rel of edge %lld", E, d_rel, false, s));
   DevBuf<int> dE;                       // the checked host copy: no kernel indexes with a value that was not looked at
   SFM_TRY(dE.upload(edges, 2 * (size_t)E, s));
-  TriArgs a = {};
-  a.V = V; a.E = (int)E; a.edges = dE.p; a.rel = d_rel; a.mask = d_edge_mask; a.thr = __builtin_fma(2.0, cos_loop, 1.0);
-  a.min_ok = min_ok == 0 ? 1 : min_ok; a.min_pct = min_pct; a.keep_untested = keep_untested;
-  a.keep = d_edge_keep; a.n_tri = reinterpret_cast<long long*>(d_n_tri); a.n_ok = reinterpret_cast<long long*>(d_n_ok);
-  a.kept_idx = d_kept_idx; a.summary = reinterpret_cast<long long*>(d_summary);
-  SFM_TRY(tri_run(who, a, group, true, n_kept, s));
+  const TriArgs a = tri_args(V, E, dE.p, d_rel, d_edge_mask, cos_loop, min_ok, min_pct, keep_untested, d_edge_keep, d_n_tri, d_n_ok,
+                             d_kept_idx, d_summary);
+  SFM_TRY(tri_run(a, group, n_kept, s));
   return stream_sync(s);
 }
 
@@ -328,7 +306,8 @@ int sfm_view_triplets(int V, int64_t E, const int* edges, const double* rel, con
                       int min_pct, int keep_untested, int group, unsigned char* edge_keep, int64_t* n_tri, int64_t* n_ok, int* kept_idx,
                       int64_t* summary, int* n_kept) {
   const char* who = "sfm_view_triplets";
-  SFM_TRY(tri_check(who, V, E, edges, rel, true, cos_loop, min_ok, min_pct, keep_untested, group));
+  SFM_TRY(tri_check(who, V, E, edges, rel, cos_loop, min_ok, min_pct, keep_untested, group));
+  SFM_TRY(check_rotations_host(who, "Rel of edge %lld", E, rel, false));
   SFM_TRY(ensure_init());
   hipStream_t s = ctx().stream;
   const size_t m = (size_t)E;
@@ -343,13 +322,10 @@ int sfm_view_triplets(int V, int64_t E, const int* edges, const double* rel, con
   SFM_TRY(dMask.upload_if(edge_mask, m, s));
   SFM_TRY(oKeep.want(edge_keep, m, s)); SFM_TRY(oTri.want(n_tri, m, s)); SFM_TRY(oOk.want(n_ok, m, s));
   SFM_TRY(oIdx.want(kept_idx, m, s)); SFM_TRY(oSum.want(summary, 8, s));
-  TriArgs a = {};
-  a.V = V; a.E = (int)E; a.edges = dE.p; a.rel = dRel.p; a.mask = dMask.p; a.thr = __builtin_fma(2.0, cos_loop, 1.0);
-  a.min_ok = min_ok == 0 ? 1 : min_ok; a.min_pct = min_pct; a.keep_untested = keep_untested;
-  a.keep = oKeep.dev(); a.n_tri = reinterpret_cast<long long*>(oTri.dev()); a.n_ok = reinterpret_cast<long long*>(oOk.dev());
-  a.kept_idx = oIdx.dev(); a.summary = reinterpret_cast<long long*>(oSum.dev());
+  const TriArgs a = tri_args(V, E, dE.p, dRel.p, dMask.p, cos_loop, min_ok, min_pct, keep_untested, oKeep.dev(), oTri.dev(), oOk.dev(),
+                             oIdx.dev(), oSum.dev());
   int count = 0;
-  SFM_TRY(tri_run(who, a, group, false, &count, s));
+  SFM_TRY(tri_run(a, group, &count, s));
   // only the first `count` entries of kept_idx were written: the rest of the caller's array stays as it was
   SFM_TRY(oKeep.fetch(s)); SFM_TRY(oTri.fetch(s)); SFM_TRY(oOk.fetch(s)); SFM_TRY(oSum.fetch(s));
   if (kept_idx != nullptr && count > 0) SFM_TRY(oIdx.buf.download(kept_idx, (size_t)count, s));

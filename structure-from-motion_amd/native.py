@@ -1065,21 +1065,69 @@ def split_similarity(sim):
     return float(sim[0]), sim[1:10].reshape(3, 3).copy(), sim[10:13].copy()
 
 
+# ---- what the view-graph operations share: their argument checks and their optional outputs ------------------------------
+def _integer(name, value):
+    if isinstance(value, (bool, np.bool_)) or int(value) != value:
+        raise ValueError("%s must be an integer, got %r" % (name, value))
+    return int(value)
+
+
+def _graph_edges(edges):
+    """``edges`` as it came, an array: ValueError unless it holds integers in the shape (E, 2)."""
+    edges_in = np.asarray(edges)
+    if edges_in.ndim != 2 or edges_in.shape[1] != 2 or (edges_in.size and not np.all(edges_in == np.floor(edges_in))):
+        raise ValueError("edges must be integers of shape (E, 2), got %r" % (edges_in.shape,))
+    return edges_in
+
+
+def _refuse_bad_edges(edges_in, n_views):
+    """ValueError naming the first edge that does not join two different views in 0 .. n_views - 1."""
+    bad = (edges_in < 0) | (edges_in >= n_views)
+    bad = bad[:, 0] | bad[:, 1] | (edges_in[:, 0] == edges_in[:, 1])
+    if bad.any():
+        e = int(np.argmax(bad))
+        raise ValueError("edge %d = (%d, %d) must join two different views in 0 .. %d" % (e, edges_in[e, 0], edges_in[e, 1], n_views - 1))
+
+
+def _refuse_bad_rotations(R, what, skip_zero=False):
+    """The ValueError of the library's verify_rotation naming the first row of ``R (n, 9)`` that fails it (``what`` is a format
+    for its index); with ``skip_zero`` nine zeros stand for "no rotation" and pass."""
+    bad = ~_verify_rotations(R)
+    if skip_zero:
+        bad &= np.any(R != 0.0, axis=1)
+    if bad.any():
+        raise ValueError("convert_quaternion_to_rotation : Invalid output rotation matrix (%s is not a rotation)"
+                         % (what % int(np.argmax(bad))))
+
+
+def _cos_or_degrees(cos, deg):
+    """``cos`` if given, else the cosine of ``deg`` degrees."""
+    return float(np.cos(np.deg2rad(float(deg)))) if cos is None else cos
+
+
+def _optional_outputs(outputs, known, arrays, scalars=()):
+    """``(wanted, result)`` of a call with optional output arrays: ``wanted[name]`` is ``arrays[name]`` where ``outputs`` names it
+    and None otherwise -- ValueError for a name that is not in ``known``; ``result()``, after the call, is the tuple in the
+    order of ``known``, the one-element arrays named in ``scalars`` as ints."""
+    unknown = set(outputs) - set(known)
+    if unknown:
+        raise ValueError("outputs must be among %r, got %r" % (known, sorted(unknown)))
+    wanted = {k: (v if k in outputs else None) for k, v in arrays.items()}
+
+    def result():
+        return tuple(None if wanted[k] is None else (int(wanted[k][0]) if k in scalars else wanted[k]) for k in known)
+    return wanted, result
+
+
 # ---- rotation averaging over a view graph (sfm_rotation_*; no reference counterpart) ------------------------------------
 def check_rotation_graph(n_views, edges, rel, root=0, cos_max=1.0, max_hyp=0, iters=2, steps=2, cg_tol=1e-12, cg_max=200):
     """The arguments of a ``rotation_average`` call, without a device: ``(n_views, edges int32 (E, 2), rel (E, 9), root,
     cos_max, max_hyp, iters, steps, cg_tol, cg_max)`` converted or ValueError -- everything sfm_rotation_average refuses, in
     its order; a ``Rel`` that is no rotation raises the ValueError of the library's verify_rotation and names the edge."""
-    def integer(name, value):
-        if isinstance(value, bool) or int(value) != value:
-            raise ValueError("%s must be an integer, got %r" % (name, value))
-        return int(value)
-    n_views, root = integer("n_views", n_views), integer("root", root)
-    max_hyp, iters, steps, cg_max = integer("max_hyp", max_hyp), integer("iters", iters), integer("steps", steps), integer("cg_max", cg_max)
+    n_views, root = _integer("n_views", n_views), _integer("root", root)
+    max_hyp, iters, steps, cg_max = _integer("max_hyp", max_hyp), _integer("iters", iters), _integer("steps", steps), _integer("cg_max", cg_max)
     cos_max, cg_tol = float(cos_max), float(cg_tol)
-    edges_in = np.asarray(edges)
-    if edges_in.ndim != 2 or edges_in.shape[1] != 2 or (edges_in.size and not np.all(edges_in == np.floor(edges_in))):
-        raise ValueError("edges must be integers of shape (E, 2), got %r" % (edges_in.shape,))
+    edges_in = _graph_edges(edges)
     rel = f64(rel)
     n_edges = edges_in.shape[0]
     if rel.size != 9 * n_edges or rel.ndim not in (2, 3):
@@ -1101,16 +1149,9 @@ def check_rotation_graph(n_views, edges, rel, root=0, cos_max=1.0, max_hyp=0, it
         raise ValueError("cg_tol = %r must be in (0, 1)" % cg_tol)
     if cg_max < 1:
         raise ValueError("cg_max = %d must be >= 1" % cg_max)
-    bad = (edges_in < 0) | (edges_in >= n_views)
-    bad = bad[:, 0] | bad[:, 1] | (edges_in[:, 0] == edges_in[:, 1])
-    if bad.any():
-        e = int(np.argmax(bad))
-        raise ValueError("edge %d = (%d, %d) must join two different views in 0 .. %d" % (e, edges_in[e, 0], edges_in[e, 1], n_views - 1))
+    _refuse_bad_edges(edges_in, n_views)
     edges = np.ascontiguousarray(edges_in, dtype=np.int32)
-    bad = ~_verify_rotations(rel)
-    if bad.any():
-        raise ValueError("convert_quaternion_to_rotation : Invalid output rotation matrix (Rel of edge %d is not a rotation)"
-                         % int(np.argmax(bad)))
+    _refuse_bad_rotations(rel, "Rel of edge %d")
     return n_views, edges, rel, root, cos_max, max_hyp, iters, steps, cg_tol, cg_max
 
 
@@ -1169,27 +1210,19 @@ def rotation_average(n_views, edges, rel, root=0, cos_max=None, max_hyp=0, iters
     uint8, edge_cos (E,), view_status (V,) of ROTAVG_UNREACHED / ROTAVG_HELD bits, n_inliers, best_hyp, status of ROTAVG_*
     bits, summary (6,) int64`` in the order of ``ROTAVG_SUMMARY``; an output not named in ``outputs`` is not computed and
     comes back as None."""
-    if cos_max is None:
-        cos_max = float(np.cos(np.deg2rad(float(max_angle_deg))))
+    cos_max = _cos_or_degrees(cos_max, max_angle_deg)
     V, edges, rel, root, cos_max, max_hyp, iters, steps, cg_tol, cg_max = check_rotation_graph(
         n_views, edges, rel, root, cos_max, max_hyp, iters, steps, cg_tol, cg_max)
-    unknown = set(outputs) - set(ROTAVG_OUTPUTS)
-    if unknown:
-        raise ValueError("outputs must be among %r, got %r" % (ROTAVG_OUTPUTS, sorted(unknown)))
     E = edges.shape[0]
     R = np.zeros((V, 9))
-    o = {"edge_inlier": np.zeros(E, dtype=np.uint8), "edge_cos": np.zeros(E), "view_status": np.zeros(V, dtype=np.int32),
-         "n_inliers": np.zeros(1, dtype=np.int32), "best_hyp": np.zeros(1, dtype=np.int32), "status": np.zeros(1, dtype=np.int32),
-         "summary": np.zeros(6, dtype=np.int64)}
-    w = {k: (v if k in outputs else None) for k, v in o.items()}
+    w, result = _optional_outputs(outputs, ROTAVG_OUTPUTS, {
+        "edge_inlier": np.zeros(E, dtype=np.uint8), "edge_cos": np.zeros(E), "view_status": np.zeros(V, dtype=np.int32),
+        "n_inliers": np.zeros(1, dtype=np.int32), "best_hyp": np.zeros(1, dtype=np.int32), "status": np.zeros(1, dtype=np.int32),
+        "summary": np.zeros(6, dtype=np.int64)}, scalars=("n_inliers", "best_hyp", "status"))
     check(load().sfm_rotation_average(V, E, iptr(edges), dptr(rel), root, cos_max, max_hyp, iters, steps, cg_tol, cg_max, dptr(R),
                                       _u8ptr(w["edge_inlier"]), dptr(w["edge_cos"]), iptr(w["view_status"]), iptr(w["n_inliers"]),
                                       iptr(w["best_hyp"]), iptr(w["status"]), _lptr(w["summary"])))
-    out = []
-    for name in ROTAVG_OUTPUTS:
-        v = w[name]
-        out.append(None if v is None else (int(v[0]) if name in ("n_inliers", "best_hyp", "status") else v))
-    return (R.reshape(V, 3, 3),) + tuple(out)
+    return (R.reshape(V, 3, 3),) + result()
 
 
 def rotation_average_dev(n_views, edges, d_rel, root=0, cos_max=None, max_hyp=0, iters=2, steps=2, cg_tol=1e-12, cg_max=200,
@@ -1197,8 +1230,7 @@ def rotation_average_dev(n_views, edges, d_rel, root=0, cos_max=None, max_hyp=0,
                          d_status=0, d_summary=0, stream=0):
     """``rotation_average`` with ``d_rel`` (E, 9) and the outputs as device pointers and a caller's stream
     (sfm_rotation_average_dev); ``edges`` stays a host array, optional arrays are 0."""
-    if cos_max is None:
-        cos_max = float(np.cos(np.deg2rad(float(max_angle_deg))))
+    cos_max = _cos_or_degrees(cos_max, max_angle_deg)
     edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
     check(load().sfm_rotation_average_dev(int(n_views), edges.shape[0], iptr(edges), _vp(d_rel), int(root), float(cos_max), int(max_hyp),
                                           int(iters), int(steps), float(cg_tol), int(cg_max), _vp(d_R_out), _vp(d_edge_inlier),
@@ -1212,16 +1244,10 @@ def check_view_triplets(n_views, edges, rel, edge_mask=None, cos_loop=1.0, min_o
     (E,) or None, cos_loop, min_ok, min_pct, keep_untested, group)`` converted or ValueError -- everything sfm_view_triplets
     refuses, in its order; a ``Rel`` that is no rotation raises the ValueError of the library's verify_rotation and names the
     edge."""
-    def integer(name, value):
-        if isinstance(value, bool) or int(value) != value:
-            raise ValueError("%s must be an integer, got %r" % (name, value))
-        return int(value)
-    n_views, min_ok, min_pct, group = integer("n_views", n_views), integer("min_ok", min_ok), integer("min_pct", min_pct), integer("group", group)
-    keep_untested = int(keep_untested) if isinstance(keep_untested, (bool, np.bool_)) else integer("keep_untested", keep_untested)
+    n_views, min_ok, min_pct, group = _integer("n_views", n_views), _integer("min_ok", min_ok), _integer("min_pct", min_pct), _integer("group", group)
+    keep_untested = int(keep_untested) if isinstance(keep_untested, (bool, np.bool_)) else _integer("keep_untested", keep_untested)
     cos_loop = float(cos_loop)
-    edges_in = np.asarray(edges)
-    if edges_in.ndim != 2 or edges_in.shape[1] != 2 or (edges_in.size and not np.all(edges_in == np.floor(edges_in))):
-        raise ValueError("edges must be integers of shape (E, 2), got %r" % (edges_in.shape,))
+    edges_in = _graph_edges(edges)
     rel = f64(rel)
     n_edges = edges_in.shape[0]
     if rel.size != 9 * n_edges or rel.ndim not in (2, 3):
@@ -1243,16 +1269,9 @@ def check_view_triplets(n_views, edges, rel, edge_mask=None, cos_loop=1.0, min_o
         raise ValueError("keep_untested = %d must be 0 or 1" % keep_untested)
     if group not in (0, 1, 4, 8, 16, 32, 64):
         raise ValueError("group %d is not one of 0, 1, 4, 8, 16, 32, 64" % group)
-    bad = (edges_in < 0) | (edges_in >= n_views)
-    bad = bad[:, 0] | bad[:, 1] | (edges_in[:, 0] == edges_in[:, 1])
-    if bad.any():
-        e = int(np.argmax(bad))
-        raise ValueError("edge %d = (%d, %d) must join two different views in 0 .. %d" % (e, edges_in[e, 0], edges_in[e, 1], n_views - 1))
+    _refuse_bad_edges(edges_in, n_views)
     edges = np.ascontiguousarray(edges_in, dtype=np.int32)
-    bad = ~_verify_rotations(rel)
-    if bad.any():
-        raise ValueError("convert_quaternion_to_rotation : Invalid output rotation matrix (Rel of edge %d is not a rotation)"
-                         % int(np.argmax(bad)))
+    _refuse_bad_rotations(rel, "Rel of edge %d")
     return n_views, edges, rel, edge_mask, cos_loop, min_ok, min_pct, keep_untested, group
 
 
@@ -1274,32 +1293,27 @@ def view_triplets(n_views, edges, rel, edge_mask=None, cos_loop=None, min_ok=1, 
     gets ``keep_untested``.  Returns ``edge_keep (E,) uint8, n_tri (E,) int64, n_ok (E,) int64, kept_idx (n_kept,) int32,
     summary (8,) int64`` in the order of ``TRIPLET_SUMMARY``; an output not named in ``outputs`` is not fetched and comes back
     as None."""
-    if cos_loop is None:
-        cos_loop = float(np.cos(np.deg2rad(float(max_loop_deg))))
+    cos_loop = _cos_or_degrees(cos_loop, max_loop_deg)
     V, edges, rel, edge_mask, cos_loop, min_ok, min_pct, keep_untested, group = check_view_triplets(
         n_views, edges, rel, edge_mask, cos_loop, min_ok, min_pct, keep_untested, group)
-    unknown = set(outputs) - set(TRIPLET_OUTPUTS)
-    if unknown:
-        raise ValueError("outputs must be among %r, got %r" % (TRIPLET_OUTPUTS, sorted(unknown)))
     E = edges.shape[0]
-    o = {"edge_keep": np.zeros(E, dtype=np.uint8), "n_tri": np.zeros(E, dtype=np.int64), "n_ok": np.zeros(E, dtype=np.int64),
-         "kept_idx": np.full(E, -1, dtype=np.int32), "summary": np.zeros(8, dtype=np.int64)}
-    w = {k: (v if k in outputs else None) for k, v in o.items()}
+    w, result = _optional_outputs(outputs, TRIPLET_OUTPUTS, {
+        "edge_keep": np.zeros(E, dtype=np.uint8), "n_tri": np.zeros(E, dtype=np.int64), "n_ok": np.zeros(E, dtype=np.int64),
+        "kept_idx": np.full(E, -1, dtype=np.int32), "summary": np.zeros(8, dtype=np.int64)})
     n_kept = np.zeros(1, dtype=np.int32)
     check(load().sfm_view_triplets(V, E, iptr(edges), dptr(rel), _u8ptr(edge_mask), cos_loop, min_ok, min_pct, keep_untested, group,
                                    _u8ptr(w["edge_keep"]), _lptr(w["n_tri"]), _lptr(w["n_ok"]), iptr(w["kept_idx"]),
                                    _lptr(w["summary"]), iptr(n_kept)))
     if w["kept_idx"] is not None:
         w["kept_idx"] = w["kept_idx"][:int(n_kept[0])].copy()
-    return tuple(w[name] for name in TRIPLET_OUTPUTS)
+    return result()
 
 
 def view_triplets_dev(n_views, edges, d_rel, d_edge_mask=0, cos_loop=None, min_ok=1, min_pct=0, keep_untested=0, group=0,
                       max_loop_deg=5.0, d_edge_keep=0, d_n_tri=0, d_n_ok=0, d_kept_idx=0, d_summary=0, stream=0):
     """``view_triplets`` with ``d_rel`` (E, 9), ``d_edge_mask`` and the outputs as device pointers and a caller's stream
     (sfm_view_triplets_dev); ``edges`` stays a host array, optional arrays are 0.  Returns ``n_kept``."""
-    if cos_loop is None:
-        cos_loop = float(np.cos(np.deg2rad(float(max_loop_deg))))
+    cos_loop = _cos_or_degrees(cos_loop, max_loop_deg)
     edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
     n_kept = np.zeros(1, dtype=np.int32)
     check(load().sfm_view_triplets_dev(int(n_views), edges.shape[0], iptr(edges), _vp(d_rel), _vp(d_edge_mask), float(cos_loop), int(min_ok),
@@ -1315,16 +1329,10 @@ def check_translation_graph(n_views, edges, R, t, edge_mask=None, root=0, cos_ma
     edge_mask uint8 (E,) or None, root, cos_max, mu, rounds, polish, cg_tol, cg_max)`` converted or ValueError -- everything
     sfm_translation_average refuses, in its order; a non-zero ``R_v`` that is no rotation raises the ValueError of the
     library's verify_rotation and names the view."""
-    def integer(name, value):
-        if isinstance(value, bool) or int(value) != value:
-            raise ValueError("%s must be an integer, got %r" % (name, value))
-        return int(value)
-    n_views, root = integer("n_views", n_views), integer("root", root)
-    rounds, polish, cg_max = integer("rounds", rounds), integer("polish", int(polish) if isinstance(polish, bool) else polish), integer("cg_max", cg_max)
+    n_views, root = _integer("n_views", n_views), _integer("root", root)
+    rounds, polish, cg_max = _integer("rounds", rounds), _integer("polish", int(polish) if isinstance(polish, (bool, np.bool_)) else polish), _integer("cg_max", cg_max)
     cos_max, mu, cg_tol = float(cos_max), float(mu), float(cg_tol)
-    edges_in = np.asarray(edges)
-    if edges_in.ndim != 2 or edges_in.shape[1] != 2 or (edges_in.size and not np.all(edges_in == np.floor(edges_in))):
-        raise ValueError("edges must be integers of shape (E, 2), got %r" % (edges_in.shape,))
+    edges_in = _graph_edges(edges)
     n_edges = edges_in.shape[0]
     R, t = f64(R), f64(t)
     if R.size != 9 * max(n_views, 0) or R.ndim not in (2, 3):
@@ -1352,16 +1360,9 @@ def check_translation_graph(n_views, edges, R, t, edge_mask=None, root=0, cos_ma
         raise ValueError("cg_tol = %r must be in (0, 1)" % cg_tol)
     if cg_max < 1:
         raise ValueError("cg_max = %d must be >= 1" % cg_max)
-    bad = (edges_in < 0) | (edges_in >= n_views)
-    bad = bad[:, 0] | bad[:, 1] | (edges_in[:, 0] == edges_in[:, 1])
-    if bad.any():
-        e = int(np.argmax(bad))
-        raise ValueError("edge %d = (%d, %d) must join two different views in 0 .. %d" % (e, edges_in[e, 0], edges_in[e, 1], n_views - 1))
+    _refuse_bad_edges(edges_in, n_views)
     edges = np.ascontiguousarray(edges_in, dtype=np.int32)
-    bad = np.any(R != 0.0, axis=1) & ~_verify_rotations(R)
-    if bad.any():
-        raise ValueError("convert_quaternion_to_rotation : Invalid output rotation matrix (R of view %d is not a rotation)"
-                         % int(np.argmax(bad)))
+    _refuse_bad_rotations(R, "R of view %d", skip_zero=True)
     return n_views, edges, R, t, edge_mask, root, cos_max, mu, rounds, polish, cg_tol, cg_max
 
 
@@ -1385,27 +1386,19 @@ def translation_average(n_views, edges, R, t, edge_mask=None, root=0, cos_max=No
     without a position -- and ``edge_inlier (E,) uint8, edge_cos (E,), edge_len (E,), view_status (V,) of TRANSAVG_NO_ROTATION /
     UNREACHED / HELD bits, n_inliers, status of TRANSAVG_* bits, summary (6,) int64`` in the order of ``TRANSAVG_SUMMARY``,
     ``log (rounds + 2, 4)``; an output not named in ``outputs`` is not computed and comes back as None."""
-    if cos_max is None:
-        cos_max = float(np.cos(np.deg2rad(float(max_angle_deg))))
+    cos_max = _cos_or_degrees(cos_max, max_angle_deg)
     V, edges, R, t, edge_mask, root, cos_max, mu, rounds, polish, cg_tol, cg_max = check_translation_graph(
         n_views, edges, R, t, edge_mask, root, cos_max, mu, rounds, polish, cg_tol, cg_max)
-    unknown = set(outputs) - set(TRANSAVG_OUTPUTS)
-    if unknown:
-        raise ValueError("outputs must be among %r, got %r" % (TRANSAVG_OUTPUTS, sorted(unknown)))
     E = edges.shape[0]
     C = np.zeros((V, 3))
-    o = {"edge_inlier": np.zeros(E, dtype=np.uint8), "edge_cos": np.zeros(E), "edge_len": np.zeros(E),
-         "view_status": np.zeros(V, dtype=np.int32), "n_inliers": np.zeros(1, dtype=np.int32), "status": np.zeros(1, dtype=np.int32),
-         "summary": np.zeros(6, dtype=np.int64), "log": np.zeros((rounds + 2, 4))}
-    w = {k: (v if k in outputs else None) for k, v in o.items()}
+    w, result = _optional_outputs(outputs, TRANSAVG_OUTPUTS, {
+        "edge_inlier": np.zeros(E, dtype=np.uint8), "edge_cos": np.zeros(E), "edge_len": np.zeros(E),
+        "view_status": np.zeros(V, dtype=np.int32), "n_inliers": np.zeros(1, dtype=np.int32), "status": np.zeros(1, dtype=np.int32),
+        "summary": np.zeros(6, dtype=np.int64), "log": np.zeros((rounds + 2, 4))}, scalars=("n_inliers", "status"))
     check(load().sfm_translation_average(V, E, iptr(edges), dptr(R), dptr(t), _u8ptr(edge_mask), root, cos_max, mu, rounds, polish, cg_tol,
                                          cg_max, dptr(C), _u8ptr(w["edge_inlier"]), dptr(w["edge_cos"]), dptr(w["edge_len"]),
                                          iptr(w["view_status"]), iptr(w["n_inliers"]), iptr(w["status"]), _lptr(w["summary"]), dptr(w["log"])))
-    out = []
-    for name in TRANSAVG_OUTPUTS:
-        v = w[name]
-        out.append(None if v is None else (int(v[0]) if name in ("n_inliers", "status") else v))
-    return (C,) + tuple(out)
+    return (C,) + result()
 
 
 def translation_average_dev(n_views, edges, d_R, d_t, d_edge_mask=0, root=0, cos_max=None, mu=0.01, rounds=8, polish=1, cg_tol=1e-13,
@@ -1413,8 +1406,7 @@ def translation_average_dev(n_views, edges, d_R, d_t, d_edge_mask=0, root=0, cos
                             d_n_inliers=0, d_status=0, d_summary=0, d_log=0, stream=0):
     """``translation_average`` with ``d_R`` (V, 9), ``d_t`` (E, 3), ``d_edge_mask`` (E,) bytes and the outputs as device pointers
     and a caller's stream (sfm_translation_average_dev); ``edges`` stays a host array, optional arrays are 0."""
-    if cos_max is None:
-        cos_max = float(np.cos(np.deg2rad(float(max_angle_deg))))
+    cos_max = _cos_or_degrees(cos_max, max_angle_deg)
     edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
     check(load().sfm_translation_average_dev(int(n_views), edges.shape[0], iptr(edges), _vp(d_R), _vp(d_t), _vp(d_edge_mask), int(root),
                                              float(cos_max), float(mu), int(rounds), int(polish), float(cg_tol), int(cg_max), _vp(d_C_out),
@@ -2544,12 +2536,6 @@ def _set_facts(s):
         n, dim, metric, exact = s
         return int(n), int(dim), int(metric), bool(exact)
     return int(s.n), int(s.dim), int(s.metric), bool(s.exact)
-
-
-def _integer(name, value):
-    if isinstance(value, (bool, np.bool_)) or int(value) != value:
-        raise ValueError("%s must be an integer, got %r" % (name, value))
-    return int(value)
 
 
 def _check_retrieve_sets(what, sets):
